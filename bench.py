@@ -13,7 +13,9 @@ count).  Workload = BASELINE.json configs[1] ("C2"): 1M x 150 bp reads per GPU, 
           the others.  value = distinct k-mers over all partitions / max-over-ranks time.
           Launched by `torch.distributed.run` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or by itself: with
           --gpus N and no WORLD_SIZE it starts its N ranks as child processes before touching torch or HIP.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run measures the headline only; --full adds what is measured next to it (the
+stream yardstick, at N = 1 the mode_G, pcie_inclusive and c3 objects and the CPU baseline).  --dump-outputs DIR writes
+what the last timed step left in the table (see dump_outputs).
 """
 import argparse
 import json
@@ -239,6 +241,49 @@ def c3_object(ctx):
     return res
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 0x5EED_D0C5
+
+
+def dump_outputs(out_dir, m, occ_last, rank, world):
+    """--dump-outputs: what the last timed step left in the table, as float64 .npy files that a run of another build with the
+    same arguments can be compared with file for file (the reads are seeded, so the inputs are the same from run to run).
+      occurrences     k-mer windows the last count_reads_dev counted (sharded: the keys this rank's owner counted)
+      distinct_kmers  m.size()
+      count_sum       the sum of all counts in the table (gk_map_verify)
+      table_checksum  gk_map_verify's order-independent checksum of the (key, count) set, as [low 32 bits, high 32 bits]
+      sample_keys     (n, 4) [lo & 0xffffffff, lo >> 32, hi & 0xffffffff, hi >> 32] of a fixed sample of the stored keys
+      sample_counts   (n,) their counts
+    The slot order of the table is an implementation detail, so the sample does not depend on it: every key whose SplitMix64
+    finaliser of (lo, hi, DUMP_SAMPLE_SEED) has its top 7 bits clear (about 1 in 128), sorted by (hi, lo) and cut where the files
+    would pass DUMP_MAX_BYTES.  With world > 1 every rank writes its own partition, the names suffixed _rank<r>."""
+    os.makedirs(out_dir, exist_ok=True)
+    _, _, count_sum, checksum = m.verify_checksum()
+    lo, hi, cnt = m.items()
+    with np.errstate(over="ignore"):
+        z = lo ^ (hi * np.uint64(0x9E3779B97F4A7C15)) ^ np.uint64(DUMP_SAMPLE_SEED)
+        z ^= z >> np.uint64(30)
+        z *= np.uint64(0xBF58476D1CE4E5B9)
+        z ^= z >> np.uint64(27)
+        z *= np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    sel = np.flatnonzero((z >> np.uint64(57)) == 0)
+    del z
+    lo, hi, cnt = lo[sel], hi[sel], cnt[sel]
+    order = np.lexsort((lo, hi))
+    cap = (DUMP_MAX_BYTES // world - 4096) // (5 * 8)            # 4 key columns + 1 count column, float64
+    order = order[:cap]
+    lo, hi, cnt = lo[order], hi[order], cnt[order]
+    m32 = np.uint64(0xFFFFFFFF)
+    keys = np.stack([lo & m32, lo >> np.uint64(32), hi & m32, hi >> np.uint64(32)], axis=1).astype(np.float64)
+    arrays = {"occurrences": [occ_last], "distinct_kmers": [m.size()], "count_sum": [count_sum],
+              "table_checksum": [checksum & 0xFFFFFFFF, checksum >> 32],
+              "sample_keys": keys, "sample_counts": cnt.astype(np.float64)}
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.asarray(a, np.float64))
+
+
 def launch_ranks(n, argv, launch_only):
     """`bench.py --gpus N` without an outer launcher (WORLD_SIZE unset): start N fresh copies of this script, one rank per GPU,
     BEFORE this process has imported torch or touched HIP (the reference driver deploys its own partitions too,
@@ -291,10 +336,15 @@ def main():
                     help="direct: one global CAS/add per k-mer; partitioned: radix-partition by table segment, build in LDS")
     ap.add_argument("--sharded", action="store_true", help="run the N>1 code path (owner bucketing + all-to-all + owner insert) "
                     "even with one rank: the only way to exercise it on a 1-GPU box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what sits next to the headline: roofline.measured_stream "
+                    "(gk_dev_stream_bench), and at N=1 the mode_G, pcie_inclusive and c3 objects and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last step left in the table "
+                    "as float64 DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--opt", action="append", default=[], help="gk_ctx_set_option name=value (A/B switches of the insert pipeline)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the objects measured next to the headline at N=1: mode_G, pcie_inclusive, c3")
-    ap.add_argument("--no-c3", action="store_true", help="skip only the c3 object (A/B runs of the C2 pipeline)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the objects measured next to the headline at N=1: "
+                    "mode_G, pcie_inclusive, c3")
+    ap.add_argument("--no-c3", action="store_true", help="with --full: skip only the c3 object (A/B runs of the C2 pipeline)")
     ap.add_argument("--launch-only", action="store_true", help="with --gpus N and no WORLD_SIZE: start the N ranks, let each report its "
                     "environment and exit (checks the launcher without a GPU)")
     args = ap.parse_args()
@@ -335,7 +385,7 @@ def main():
     # The pinned host buffer of the pcie_inclusive object is taken NOW, the way an application takes its I/O buffers at start-up:
     # pinned late, after the process has churned through host memory, the same buffer uploaded at 26 instead of 56 GB/s in three
     # runs out of four (pages on the right NUMA node both times: presumably small pages behind the IOMMU instead of large ones).
-    want_extras = (world == 1 and not (world > 1 or args.sharded) and not args.no_extras
+    want_extras = (args.full and world == 1 and not (world > 1 or args.sharded) and not args.no_extras
                    and args.mode == "U" and n == 1_000_000 and L == 150 and k == 31)
     hb = ctx.host_alloc(n * stride) if want_extras else None
     rec = ctx.alloc(n * stride + 64)
@@ -361,12 +411,12 @@ def main():
     m.set_insert_path(args.insert_path)
 
     kernel_ms, kernel_units, phase_ms, dist_ms = [], [], [], []
-    begun = [0]
+    begun, occ_last = [0], [0]
 
     def step(i=0, K=1):
         m.clear()
         if not sharded:
-            m.count_reads_dev(rec, n, L)
+            occ_last[0] = m.count_reads_dev(rec, n, L)
             ms, kocc = m.last_count_kernel()
             kernel_ms.append(ms); kernel_units.append(kocc); phase_ms.append(m.last_phase_ms())
             return
@@ -379,6 +429,7 @@ def main():
             pm.route_begin(rec, n, L)
             begun[0] += 1
         _, owned = pm.count_routed()
+        occ_last[0] = owned
         ms, _ = m.last_count_kernel()
         kernel_ms.append(ms); kernel_units.append(owned); phase_ms.append(m.last_phase_ms()); dist_ms.append(hd.last_ms())
 
@@ -398,6 +449,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m, occ_last[0], rank, world)
     distinct_rank = m.size()
     if sharded:
         dt_max = float(hd.allreduce([dt], "max")[0])
@@ -480,16 +533,17 @@ def main():
                 return {"error": repr(e)}
 
         rl = out["roofline"]
-        sb = extra("measured_stream", lambda: ctx.stream_bench(1 << 30, 10))
-        if "error" in sb:
-            rl["measured_stream"] = sb
-        else:
-            rl["measured_stream"] = dict(sb, what="gk_dev_stream_bench: 16-byte copy / fill / sum kernels over 1 GiB buffers, GB/s "
-                                                 "(copy counts bytes read + written)")
-            rl["frac_of_measured_copy"] = achieved / sb["copy_GBps"] if sb["copy_GBps"] else None
-            if traffic:
-                rl["traffic_GBps"] = traffic / (avg_kernel_ms * 1e-3) / 1e9
-                rl["traffic_over_measured_copy"] = rl["traffic_GBps"] / sb["copy_GBps"] if sb["copy_GBps"] else None
+        if args.full:
+            sb = extra("measured_stream", lambda: ctx.stream_bench(1 << 30, 10))
+            if "error" in sb:
+                rl["measured_stream"] = sb
+            else:
+                rl["measured_stream"] = dict(sb, what="gk_dev_stream_bench: 16-byte copy / fill / sum kernels over 1 GiB buffers, GB/s "
+                                                     "(copy counts bytes read + written)")
+                rl["frac_of_measured_copy"] = achieved / sb["copy_GBps"] if sb["copy_GBps"] else None
+                if traffic:
+                    rl["traffic_GBps"] = traffic / (avg_kernel_ms * 1e-3) / 1e9
+                    rl["traffic_over_measured_copy"] = rl["traffic_GBps"] / sb["copy_GBps"] if sb["copy_GBps"] else None
         if sharded and dist_ms:
             out["per_rank_step_ms"] = {k_: float(np.mean([x[k_] for x in dist_ms])) for k_ in dist_ms[0]}
             out["per_rank_step_ms"]["what"] = ("rank 0, wall ms inside gk_dist_count_routed: route_wait = waiting for the routing kernel (reads -> super-k-mer records "
@@ -497,7 +551,7 @@ def main():
                                                "exchange = counts + records of the NEXT batch over RCCL, posted on the communication stream before this batch is counted (enqueue + the one host sync for the sizes); owner_count = "
                                                "the pipeline over what arrived (stream-ordered behind the receives)")
         default_workload = args.mode == "U" and n == 1_000_000 and L == 150 and k == 31
-        if world == 1 and not sharded and not args.no_extras and default_workload:
+        if args.full and world == 1 and not sharded and not args.no_extras and default_workload:
             def mode_g():
                 recg = ctx.alloc(n * stride + 64)
                 ctx.synth_reads(recg, n, L, "G", 2, 0, 5_000_000, 0.01)
@@ -525,14 +579,14 @@ def main():
             out["pcie_inclusive"] = extra("pcie_inclusive", pcie)
             if not args.no_c3:
                 out["c3"] = extra("c3", lambda: c3_object(ctx))
-        if not args.no_cpu_baseline and world == 1 and not sharded:
+        if args.full and not args.no_cpu_baseline and world == 1 and not sharded:
             def cpu():
                 sample_reads = min(n, 400_000)
                 host = ctx.download(rec, sample_reads * stride).reshape(sample_reads, stride)
                 return cpu_baseline(host, sample_reads, k)
 
             out["cpu_baseline"] = extra("cpu_baseline", cpu)
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = None
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)

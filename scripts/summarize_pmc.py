@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the PMC passes of scripts/profile_round.sh <tag> (gpurun_out/<tag>_pmc_{fetch,write,req}) into
+"""Turn the PMC passes of scripts/profile_round.sh <tag> ($OUT_DIR/<tag>_pmc_{fetch,write,req}, run_out/ by default) into
 profiles/r02/pmc_pipeline_<tag>.json (the file bench.py reads `roofline.traffic` from) and copy the raw
 counter CSVs, the kernel stats and the bench line next to it.  Corrections: FETCH_SIZE x2 (gfx950 tallies
 128-B read requests at 64 B; calibrated on k_part_hist2 in v3/v4), WRITE_SIZE as reported; both are
@@ -15,11 +15,12 @@ import sys
 tag = sys.argv[1]
 note = sys.argv[2] if len(sys.argv) > 2 else ""
 out_dir = sys.argv[3] if len(sys.argv) > 3 else "profiles/r02"
+runs = os.environ.get("OUT_DIR", "run_out")              # where scripts/profile_round.sh wrote its passes
 PIPE = ("k_op_scatter1_reads", "k_part_hist1_reads", "k_part_scatter1_reads", "k_part_hist2", "k_part_scatter2", "k_seg_insert")
 
 
 def load(kind):
-    f = max(glob.glob(f"gpurun_out/{tag}_pmc_{kind}/*/*counter_collection.csv"), key=os.path.getmtime)      # newest run of that tag
+    f = max(glob.glob(f"{runs}/{tag}_pmc_{kind}/*/*counter_collection.csv"), key=os.path.getmtime)      # newest run of that tag
     shutil.copy(f, f"{out_dir}/pmc_{tag}_{kind}_counter_collection.csv")
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     for r in csv.DictReader(open(f)):
@@ -45,8 +46,8 @@ doc = {"command": f"scripts/profile_round.sh {tag} auto  (rocprofv3 --pmc <group
        "correction": "FETCH_SIZE x2 (gfx950 tallies 128-B read requests at 64 B for coalesced streams); WRITE_SIZE exact",
        "per_kernel": per_kernel, "hbm_bytes_per_launch": total, "note": note}
 json.dump(doc, open(f"{out_dir}/pmc_pipeline_{tag}.json", "w"), indent=1)
-ks = glob.glob(f"gpurun_out/{tag}_stats/*/*kernel_stats.csv")
+ks = glob.glob(f"{runs}/{tag}_stats/*/*kernel_stats.csv")
 if ks:
     shutil.copy(max(ks, key=os.path.getmtime), f"{out_dir}/bench_n1_{tag}_kernel_stats.csv")
-shutil.copy(f"gpurun_out/{tag}_bench.json", f"{out_dir}/bench_n1_{tag}.json")
+shutil.copy(f"{runs}/{tag}_bench.json", f"{out_dir}/bench_n1_{tag}.json")
 print(json.dumps({k: {a: b for a, b in v.items() if "bytes" in a} for k, v in per_kernel.items()}, indent=1), total)
