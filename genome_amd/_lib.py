@@ -111,6 +111,7 @@ SIGNATURES = {
     "gk_dist_gather_map": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "gk_dist_gather_classified_map": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "gk_dist_classify_queries": (C.c_int, [vp, u64p]),
+    "gk_dist_reduce_support": (C.c_int, [vp, vp, vp]),
     "gk_vmap_create": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp)]),
     "gk_vmap_destroy": (None, [vp]),
     "gk_vmap_k": (C.c_int, [vp]),
@@ -127,12 +128,15 @@ SIGNATURES = {
     "gk_graph_add_node": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32)]),
     "gk_graph_replace_start": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
     "gk_graph_id_bounds": (C.c_int, [vp, u64p, u64p]),
+    "gk_graph_id_fingerprint": (C.c_int, [vp, u64p]),
     "gk_graph_remove_edges_by_id": (C.c_int, [vp, u32p, C.c_uint64, u64p]),
     "gk_support_create": (C.c_int, [vp, C.POINTER(vp)]),
     "gk_support_destroy": (None, [vp]),
     "gk_support_size": (C.c_int, [vp, u64p, u64p, u64p]),
     "gk_support_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "gk_support_export": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, u64p]),
+    "gk_support_add": (C.c_int, [vp, u32p, u32p, u32p, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "gk_support_merge": (C.c_int, [vp, vp]),
     "gk_graph_walk_pairs": (C.c_int, [vp, vp, vp, u8p, C.c_size_t, C.c_uint64, C.c_int, C.c_int]),
     "gk_graph_split_by_support": (C.c_int, [vp, vp, C.c_int, u64p, u64p]),
     "gk_graph_replace_end": (C.c_int, [vp, C.c_uint32, C.c_uint32]),

@@ -33,6 +33,8 @@
 #include <vector>
 
 #include "gk_dist.h"
+#include "gk_graph.h"
+#include "gk_support.h"
 #include "gk_tile.h"
 
 using namespace gk;
@@ -825,3 +827,212 @@ int gk_dist_classify_queries(gk_dist *d, uint64_t *n) {
 #undef HIPD
 
 }  // extern "C"
+
+// ---- the paired-end support over the ranks (gk_dist_reduce_support) -----------------------------------------------------------
+// Reference: every storage node's WalkingActor counts the (inEdge, outEdge) pairs of the walks it did and the driver sums them
+// into one pathsMap (S/scripts/GraphSimplifier.scala:172-186, 209-248).  Here the sum is sharded: a pair's OWNER (a hash of
+// the key, not the slot hash) merges every rank's count of it, and the owners' shards — disjoint — then go to every rank,
+// which builds its table from their concatenation.  Steps, every rank taking the same ones whatever happens to it locally:
+//   1. the replica's canonical edge numbering (graph_edge_canon); all-gather (status | distinct pairs) and the replica's CONTENT
+//      fingerprint: any failure or a content mismatch -> everybody stops
+//   2. bucket by owner, the keys translated to the canonical numbering; all-to-all of region sizes (~0 = failed)
+//   3. room for the arrivals and the owner's shard table; max-reduction of "no room"
+//   4. records (12 bytes) to their owners; the owner merge (overflow-checked); the shard compacted back into the arrival buffer
+//   5. all-gather of shard sizes (~0 failed, ~0 - 1 a count passed 2^32-1): -> everybody stops
+//   6. room for every shard and the new table; max-reduction of "no room"
+//   7. every shard to every rank; the keys back to this replica's ids; the rebuild; one sum-reduction of {bad pairs, walked, failures}: the table is swapped in only
+//      where, and when, every rank has its own
+// Every allocation is made in front of the agreement that covers it, and nothing is allocated between an agreement and the
+// payload it guards.
+namespace {
+struct DevBufs {          // device staging of one call, freed together.  hipMalloc / hipFree here ARE the context's block pool
+                          // (gk_internal.h maps them to pool_malloc / pool_free by macro, hence the ctx member): no device-wide sync
+    gk_ctx *ctx;
+    std::vector<void *> p;
+    explicit DevBufs(gk_ctx *c) : ctx(c) {}
+    ~DevBufs() { for (void *q : p) (void)hipFree(q); }
+    template <class T> bool get(T **out, u64 n) {
+        *out = nullptr;
+        if (hipMalloc((void **)out, std::max<u64>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
+        p.push_back(*out);
+        return true;
+    }
+};
+struct SupHandle {        // a temporary support table on the handle's context
+    gk_support *s = nullptr;
+    ~SupHandle() { if (s) gk_support_destroy(s); }
+};
+}  // namespace
+
+extern "C" int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup) {
+    if (int rc = dist_check(d)) return rc;
+    gk_ctx *ctx = d->ctx;
+    if (int rc = dist_quiesce(d)) return rc;
+    const int P = d->world, me = d->rank;
+    const char *who = "gk_dist_reduce_support: ";
+    // A local failure is not returned at once: the peers are about to wait for this rank's words.  It is announced, and every
+    // rank returns from the same step.
+    int my_rc = GK_OK;
+    std::string my_err;
+    auto local = [&](int rc) { if (rc != GK_OK && my_rc == GK_OK) { my_rc = rc; my_err = ctx->err; } };
+    auto comm_fail = [&](int grc) { return fail(ctx, GK_E_COMM, who + comm_error_text(grc)); };
+    auto give_up = [&](const std::string &why) { return my_rc ? fail(ctx, my_rc, my_err) : fail(ctx, GK_E_COMM, who + why); };
+#define HIPR(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(ctx, e__, #call); } while (0)
+#define XPR(call) do { const int g__ = (call); if (g__ != XP_SUCCESS) return comm_fail(g__); } while (0)
+    unsigned long long *d_w = d->d_cnt;                           // the handle's own words: they exist whatever fails here
+    // grouped exchange of one word with every rank (itself included): out[p] -> rank p, in[p] <- rank p
+    auto words_all_to_all = [&](const unsigned long long *out, unsigned long long *in) -> int {
+        HIPR(hipMemcpyAsync(d_w + 4 * 64, out, P * 8, hipMemcpyHostToDevice, ctx->stream));
+        int grc = xGroupStart(d);
+        for (int p = 0; p < P && grc == XP_SUCCESS; p++) {
+            grc = xSend(d, d_w + 4 * 64 + p, 1, XP_UINT64, p, ctx->stream);
+            if (grc == XP_SUCCESS) grc = xRecv(d, d_w + 5 * 64 + p, 1, XP_UINT64, p, ctx->stream);
+        }
+        { const int gend = xGroupEnd(d); if (grc == XP_SUCCESS) grc = gend; }
+        if (grc != XP_SUCCESS) return comm_fail(grc);
+        HIPR(hipMemcpyAsync(in, d_w + 5 * 64, P * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPR(hipStreamSynchronize(ctx->stream));
+        return GK_OK;
+    };
+    // one word of every rank, in rank order
+    auto word_all_gather = [&](unsigned long long mine, unsigned long long *all) -> int {
+        HIPR(hipMemcpyAsync(d_w + 2 * 64, &mine, 8, hipMemcpyHostToDevice, ctx->stream));
+        XPR(xAllGather(d, d_w + 2 * 64, d_w, 1, XP_UINT64, ctx->stream));
+        HIPR(hipMemcpyAsync(all, d_w, P * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPR(hipStreamSynchronize(ctx->stream));
+        return GK_OK;
+    };
+    // max over the ranks of "this rank cannot go on"
+    auto any_rank = [&](bool mine, bool *any) -> int {
+        unsigned long long w = mine ? 1ull : 0ull;
+        HIPR(hipMemcpyAsync(d_w + 2 * 64, &w, 8, hipMemcpyHostToDevice, ctx->stream));
+        XPR(xAllReduce(d, d_w + 2 * 64, d_w + 2 * 64 + 1, 1, XP_UINT64, XP_MAX, ctx->stream));
+        HIPR(hipMemcpyAsync(&w, d_w + 2 * 64 + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPR(hipStreamSynchronize(ctx->stream));
+        *any = w != 0;
+        return GK_OK;
+    };
+    // ---- 1. status and the replicas' content.  The replicas need not number their edges alike (a build numbers in table slot
+    //      order, with atomic output cursors): the pairs travel in the CANONICAL numbering of graph_edge_canon — live edges
+    //      ordered by (start k-mer, first base) — which is the same on every replica that holds the same edges.
+    DevBufs buf(ctx);
+    u64 fp = 0, nlive = 0;
+    u32 *d_canon = nullptr, *d_inv = nullptr;
+    unsigned long long ctr[4] = {0, 0, 0, 0};
+    if (!g || !sup) local(fail(ctx, GK_E_INVALID, std::string(who) + "null graph or support"));
+    else if (check_graph(g) != GK_OK) local(GK_E_INVALID);
+    else if (g->ctx != ctx || sup->ctx != ctx) local(fail(ctx, GK_E_INVALID, std::string(who) + "the graph and the support must live on the handle's context"));
+    if (!my_rc) {
+        local(graph_edge_canon(g, &d_canon, &d_inv, &nlive, &fp));
+        if (d_canon) buf.p.push_back(d_canon);
+        if (d_inv) buf.p.push_back(d_inv);
+    }
+    if (!my_rc) local(support_counters(sup, ctr));
+    std::vector<unsigned long long> st(P), fps(P);
+    if (int rc = word_all_gather(my_rc ? ~0ull : ctr[0], st.data())) return rc;
+    if (int rc = word_all_gather(fp, fps.data())) return rc;
+    for (int p = 0; p < P; p++)
+        if (st[p] == ~0ull) return give_up("rank " + std::to_string(p) + " could not take part; every rank gave up, nothing was changed");
+    for (int p = 0; p < P; p++)
+        if (fps[p] != fps[me])
+            return fail(ctx, GK_E_STATE, std::string(who) + "the graph replicas differ (content fingerprint of rank " + std::to_string(p) + ": " + std::to_string(fps[p]) +
+                                             ", of this rank: " + std::to_string(fps[me]) + "): they do not hold the same edges, nothing was added up");
+    if (P == 1) return GK_OK;
+    // ---- 2. this rank's pairs by owner, in the canonical numbering; region sizes to every owner
+    SupHandle shard, fresh;
+    u64 *d_sk = nullptr, *d_rk = nullptr, *d_ak = nullptr;       // by owner (send) | arrivals, then this rank's shard | every shard
+    u32 *d_sc = nullptr, *d_rc = nullptr, *d_ac = nullptr;
+    std::vector<u64> region(P + 1, 0);
+    const u64 mine = ctr[0];
+    if (!buf.get(&d_sk, mine) || !buf.get(&d_sc, mine)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(mine) + " pairs"));
+    if (!my_rc) local(support_bucket(sup, P, d_sk, d_sc, mine, region.data(), d_canon, g->v.n_edges));
+    std::vector<unsigned long long> out(P), in(P);
+    for (int p = 0; p < P; p++) out[p] = my_rc ? ~0ull : region[p + 1] - region[p];
+    if (int rc = words_all_to_all(out.data(), in.data())) return rc;
+    u64 nin = 0;
+    std::vector<u64> roff(P + 1, 0);
+    for (int p = 0; p < P; p++) {
+        if (in[p] == ~0ull) return give_up("rank " + std::to_string(p) + " could not bucket its pairs; every rank gave up, nothing was changed");
+        roff[p] = nin;
+        nin += in[p];
+    }
+    if (my_rc) return give_up("");                                // (unreachable: this rank sent ~0 to itself)
+    // ---- 3. room for the arrivals and the shard table
+    if (!buf.get(&d_rk, nin) || !buf.get(&d_rc, nin)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(nin) + " arriving pairs"));
+    if (!my_rc) local(gk_support_create(ctx, &shard.s));
+    if (!my_rc) local(support_reserve(shard.s, nin));
+    {
+        bool any = false;
+        if (int rc = any_rank(my_rc != GK_OK, &any)) return rc;
+        if (any) return give_up("a rank had no room for the pairs it owns; every rank gave up, nothing was changed");
+    }
+    // ---- 4. the records to their owners, the owner merge
+    {
+        int grc = xGroupStart(d);
+        for (int p = 0; p < P && grc == XP_SUCCESS; p++) {
+            const u64 n = region[p + 1] - region[p];
+            if (n) grc = xSend(d, d_sk + region[p], (size_t)n, XP_UINT64, p, ctx->stream);
+            if (n && grc == XP_SUCCESS) grc = xSend(d, d_sc + region[p], (size_t)n * 4, XP_UINT8, p, ctx->stream);
+            if (in[p] && grc == XP_SUCCESS) grc = xRecv(d, d_rk + roff[p], (size_t)in[p], XP_UINT64, p, ctx->stream);
+            if (in[p] && grc == XP_SUCCESS) grc = xRecv(d, d_rc + roff[p], (size_t)in[p] * 4, XP_UINT8, p, ctx->stream);
+        }
+        { const int gend = xGroupEnd(d); if (grc == XP_SUCCESS) grc = gend; }
+        if (grc != XP_SUCCESS) return comm_fail(grc);
+    }
+    bool wrapped = false;
+    local(support_insert(shard.s, d_rk, d_rc, nin, true, &wrapped));
+    if (ctx->hook_dist_fail_reduce) {         // test hook: this rank alone fails its owner merge, after the payload has moved
+        ctx->hook_dist_fail_reduce = 0;
+        local(fail(ctx, GK_E_STATE, std::string(who) + "injected failure (test_dist_fail_reduce)"));
+    }
+    std::vector<u64> sreg(2, 0);
+    if (!my_rc && !wrapped) local(support_bucket(shard.s, 1, d_rk, d_rc, nin, sreg.data()));       // the shard, compacted where the arrivals were
+    // ---- 5. shard sizes: the owners' verdicts
+    std::vector<unsigned long long> ssz(P);
+    if (int rc = word_all_gather(my_rc ? ~0ull : wrapped ? ~0ull - 1 : sreg[1], ssz.data())) return rc;
+    bool over = false;
+    for (int p = 0; p < P; p++) {
+        if (ssz[p] == ~0ull) return give_up("rank " + std::to_string(p) + " failed its owner merge; every rank gave up, nothing was changed");
+        over |= ssz[p] == ~0ull - 1;
+    }
+    if (over) return fail(ctx, GK_E_CAPACITY, std::string(who) + "a pair's count summed over the ranks would pass 2^32-1; nothing was changed");
+    u64 total = 0;
+    std::vector<u64> soff(P + 1, 0);
+    for (int p = 0; p < P; p++) { soff[p] = total; total += ssz[p]; }
+    // ---- 6. room for every shard and the new table
+    if (!buf.get(&d_ak, total) || !buf.get(&d_ac, total)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(total) + " pairs"));
+    if (!my_rc) local(gk_support_create(ctx, &fresh.s));
+    if (!my_rc) local(support_reserve(fresh.s, total));
+    {
+        bool any = false;
+        if (int rc = any_rank(my_rc != GK_OK, &any)) return rc;
+        if (any) return give_up("a rank had no room for the summed support; every rank gave up, nothing was changed");
+    }
+    // ---- 7. every shard to every rank, the rebuild, the last agreement
+    {
+        const u64 n = ssz[me];
+        int grc = xGroupStart(d);
+        for (int p = 0; p < P && grc == XP_SUCCESS; p++) {
+            if (n) grc = xSend(d, d_rk, (size_t)n, XP_UINT64, p, ctx->stream);
+            if (n && grc == XP_SUCCESS) grc = xSend(d, d_rc, (size_t)n * 4, XP_UINT8, p, ctx->stream);
+            if (ssz[p] && grc == XP_SUCCESS) grc = xRecv(d, d_ak + soff[p], (size_t)ssz[p], XP_UINT64, p, ctx->stream);
+            if (ssz[p] && grc == XP_SUCCESS) grc = xRecv(d, d_ac + soff[p], (size_t)ssz[p] * 4, XP_UINT8, p, ctx->stream);
+        }
+        { const int gend = xGroupEnd(d); if (grc == XP_SUCCESS) grc = gend; }
+        if (grc != XP_SUCCESS) return comm_fail(grc);
+    }
+    local(support_keys_uncanon(ctx, d_ak, total, d_inv, nlive));          // back to this replica's own edge ids
+    if (!my_rc) local(support_insert(fresh.s, d_ak, d_ac, total, false, nullptr));      // (the shards are disjoint: every record is a new key)
+    unsigned long long got[4] = {0, 0, 0, 0};
+    if (!my_rc) local(support_counters(fresh.s, got));
+    if (!my_rc && got[0] != total) local(fail(ctx, GK_E_STATE, std::string(who) + "rebuilt " + std::to_string(got[0]) + " pairs from " + std::to_string(total) + " shard records"));
+    unsigned long long sums[3] = {ctr[1], ctr[2], my_rc ? 1ull : 0ull};
+    HIPR(hipMemcpyAsync(d_w + 2 * 64, sums, 24, hipMemcpyHostToDevice, ctx->stream));
+    XPR(xAllReduce(d, d_w + 2 * 64, d_w + 3 * 64, 3, XP_UINT64, XP_SUM, ctx->stream));
+    HIPR(hipMemcpyAsync(sums, d_w + 3 * 64, 24, hipMemcpyDeviceToHost, ctx->stream));
+    HIPR(hipStreamSynchronize(ctx->stream));
+    if (sums[2]) return give_up("a rank could not rebuild the summed support; every rank gave up, nothing was changed");
+    return support_adopt(sup, fresh.s, sums[0], sums[1]);
+#undef XPR
+#undef HIPR
+}

@@ -74,6 +74,7 @@ struct gk_ctx {
     // what the same two kernels measure on the box of the round 1-2 profiles (64 MiB working sets: partly Infinity Cache)
     double ref_copy_tbps = 5.9, ref_cas_gps = 26.7;        // (measured by these kernels in run 6 of round 3: 5.91 TB/s, 26.66 G/s)
     std::string err;
+    int hook_dist_fail_reduce = 0;   // test hook: this context's next gk_dist_reduce_support fails its owner merge, after the records have been exchanged
 };
 
 namespace gk {

@@ -16,6 +16,9 @@
 // states, resolve, emit.  A walk that outgrows its LDS sets (256 reached nodes, 384 states, 96 pairs) is not truncated: its
 // orientation goes to an overflow list and the host walker (the round-2 form, kept below) does it — exact either way.
 // Round 2 ran ALL walks on <= 16 host threads over a snapshot: 1.0-1.5e7 pairs/s, ten times everything before it at C3.
+#include <cstring>
+#include <rocprim/device/device_radix_sort.hpp>          // (first: gk_internal.h maps hipMalloc / hipFree onto the context's block pool by macro)
+
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -23,6 +26,7 @@
 
 #include "gk_graph.h"
 #include "gk_scan.h"
+#include "gk_support.h"
 #include "gk_tile.h"
 
 struct gk_vmap;
@@ -35,20 +39,7 @@ gk_ctx *vmap_ctx(const gk_vmap *m);
 // ---------------------------------------------------------------------------------------------
 // gk_support: pathsMap (:209) + badPairs (:211) on the device
 // ---------------------------------------------------------------------------------------------
-static constexpr u64 SUP_EMPTY = ~0ull;
-struct SupView { u64 *keys; u32 *cnt; u64 mask; unsigned long long *ctr; };     // ctr: [0] distinct pairs [1] bad pairs [2] orientations walked [3] table full
-struct gk_support {
-    gk_ctx *ctx = nullptr;
-    u64 *d_keys = nullptr;                     // (e1 << 32 | e2), open addressing, power-of-two capacity
-    u32 *d_cnt = nullptr;
-    u64 cap = 0;
-    unsigned long long *d_ctr = nullptr;
-    std::unordered_map<u64, u32> paths;        // host copy for the split (support_to_host), valid while host_valid
-    bool host_valid = false;
-    float last_ms[5] = {0, 0, 0, 0, 0};        // last gk_graph_walk_pairs: keys from the stream, getAll batch, in-edge lists + checks, walks, overflow walks on the host
-    u64 last_overflow = 0;                     // orientations of the last call that went to the host walker
-};
-
+// (SupView, gk_support: gk_support.h)
 __device__ __forceinline__ void sup_add(const SupView &s, u64 key, u32 c) {
     u64 i = mix64(key) & s.mask;
     for (u64 n = 0; n <= s.mask; n++) {
@@ -68,6 +59,161 @@ __global__ __launch_bounds__(BLOCK) void k_sup_rehash(const u64 *okeys, const u3
 }
 __global__ __launch_bounds__(BLOCK) void k_sup_add_list(const u64 *keys, const u32 *cnt, u64 n, SupView s) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) sup_add(s, keys[i], cnt[i]);
+}
+
+// ---- merging supports (gk_support_add / gk_support_merge, the N-rank reduce of gk_dist.hip) ---------------------------------
+// sup_add with a check the walks do not need (one count per pair orientation cannot wrap): a u32 count that wraps raises ctr[4]
+__device__ __forceinline__ void sup_add_checked(const SupView &s, u64 key, u32 c) {
+    u64 i = mix64(key) & s.mask;
+    for (u64 n = 0; n <= s.mask; n++) {
+        u64 cur = s.keys[i];
+        if (cur == SUP_EMPTY) {
+            cur = atomicCAS(reinterpret_cast<unsigned long long *>(&s.keys[i]), (unsigned long long)SUP_EMPTY, (unsigned long long)key);
+            if (cur == SUP_EMPTY) { atomicAdd(&s.ctr[0], 1ull); cur = key; }
+        }
+        if (cur == key) {
+            const u32 old = atomicAdd(&s.cnt[i], c);
+            if (old + c < old) s.ctr[4] = 1;
+            return;
+        }
+        i = (i + 1) & s.mask;
+    }
+    s.ctr[3] = 1;
+}
+__global__ __launch_bounds__(BLOCK) void k_sup_add_list_checked(const u64 *keys, const u32 *cnt, u64 n, SupView s) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) sup_add_checked(s, keys[i], cnt[i]);
+}
+__device__ __forceinline__ u32 sup_get(const SupView &s, u64 key) {
+    u64 i = mix64(key) & s.mask;
+    for (u64 n = 0; n <= s.mask; n++) {
+        const u64 cur = s.keys[i];
+        if (cur == key) return s.cnt[i];
+        if (cur == SUP_EMPTY) return 0u;
+        i = (i + 1) & s.mask;
+    }
+    return 0u;
+}
+// would dst += src wrap a count?  src's keys are distinct, so one read-only lookup per key decides it before anything is written
+__global__ __launch_bounds__(BLOCK) void k_sup_check_merge(const u64 *skeys, const u32 *scnt, u64 scap, SupView d, u32 *wraps) {
+    bool w = false;
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < scap; i += (u64)gridDim.x * BLOCK) {
+        const u64 key = skeys[i];
+        if (key == SUP_EMPTY) continue;
+        const u32 a = sup_get(d, key), c = scnt[i];
+        if (a + c < a) w = true;
+    }
+    if (__any(w) && (threadIdx.x & 63) == 0) *wraps = 1u;
+}
+// The owner rank of a pair in the N-rank reduce.  splitmix64's finalizer, NOT mix64: the owner's shard table places its keys by
+// mix64, and owners cut from the same hash would leave every shard with keys from a few of its slot ranges only.
+__device__ __forceinline__ u32 sup_owner(u64 key, u32 P) {
+    key ^= key >> 30; key *= 0xbf58476d1ce4e5b9ULL;
+    key ^= key >> 27; key *= 0x94d049bb133111ebULL;
+    key ^= key >> 31;
+    return (u32)(((key >> 32) * (u64)P) >> 32);
+}
+// A pair key in the CANONICAL edge numbering of the N-rank reduce (canon[local edge id], see k_edge_canon); SUP_EMPTY if one
+// of its edges is not a live edge of this replica (raises *bad).  canon == nullptr: the key as it is.
+__device__ __forceinline__ u64 sup_canon_key(u64 key, const u32 *canon, u64 nmap, u32 *bad) {
+    if (!canon) return key;
+    const u64 a = key >> 32, b = key & 0xffffffffull;
+    const u32 ca = a < nmap ? canon[a] : NONE, cb = b < nmap ? canon[b] : NONE;
+    if (ca == NONE || cb == NONE) { *bad = 1u; return SUP_EMPTY; }
+    return ((u64)ca << 32) | cb;
+}
+// k_sup_bucket: the live slots of workgroup w's contiguous `chunk` of the table, counted per owner in LDS -> counts[p * nwg + w]
+// (owner-major: one scan gives every (owner, workgroup) its place, workgroups in order inside an owner's region)
+__global__ __launch_bounds__(BLOCK) void k_sup_bucket_count(const u64 *__restrict__ keys, u64 cap, u64 chunk, u32 P, const u32 *__restrict__ canon, u64 nmap,
+                                                            u32 *__restrict__ counts, u32 *bad) {
+    __shared__ u32 hist[64];
+    for (u32 p = threadIdx.x; p < 64; p += BLOCK) hist[p] = 0;
+    __syncthreads();
+    const u64 a = (u64)blockIdx.x * chunk, b = min(a + chunk, cap);
+    for (u64 i = a + threadIdx.x; i < b; i += BLOCK) {
+        u64 key = keys[i];
+        if (key != SUP_EMPTY) key = sup_canon_key(key, canon, nmap, bad);
+        if (key != SUP_EMPTY) atomicAdd(&hist[sup_owner(key, P)], 1u);
+    }
+    __syncthreads();
+    for (u32 p = threadIdx.x; p < P; p += BLOCK) counts[(u64)p * gridDim.x + blockIdx.x] = hist[p];
+}
+// the same slots again, each record written at its (owner, workgroup) offset + its rank among them (an LDS cursor)
+__global__ __launch_bounds__(BLOCK) void k_sup_bucket_scatter(const u64 *__restrict__ keys, const u32 *__restrict__ cnt, u64 cap, u64 chunk, u32 P,
+                                                              const u32 *__restrict__ canon, u64 nmap, u32 *bad,
+                                                              const unsigned long long *__restrict__ off, u64 *__restrict__ okeys, u32 *__restrict__ ocnt) {
+    __shared__ u32 cursor[64];
+    for (u32 p = threadIdx.x; p < 64; p += BLOCK) cursor[p] = 0;
+    __syncthreads();
+    const u64 a = (u64)blockIdx.x * chunk, b = min(a + chunk, cap);
+    for (u64 i = a + threadIdx.x; i < b; i += BLOCK) {
+        u64 key = keys[i];
+        if (key == SUP_EMPTY) continue;
+        key = sup_canon_key(key, canon, nmap, bad);
+        if (key == SUP_EMPTY) continue;
+        const u32 p = sup_owner(key, P);
+        const u64 at = off[(u64)p * gridDim.x + blockIdx.x] + atomicAdd(&cursor[p], 1u);
+        okeys[at] = key;
+        ocnt[at] = cnt[i];
+    }
+}
+// region[p] = off[p * nwg] for p = 0..P (off[P * nwg] is the scan's total)
+__global__ void k_sup_regions(const unsigned long long *off, u64 nwg, u32 P, unsigned long long *region) {
+    for (u32 p = threadIdx.x; p <= P; p += blockDim.x) region[p] = off[(u64)p * nwg];
+}
+// gk_graph_id_fingerprint: every live node (id, k-mer) and live edge (id, start, end, first base, length) through a 64-bit mixer,
+// summed mod 2^64 — order-independent as a sum, id-exact because the id is mixed in with what it names
+__device__ __forceinline__ u64 fp_mix(u64 acc, u64 v) { return mix64(acc ^ (v + 0x9e3779b97f4a7c15ULL)); }
+// ---- the canonical edge numbering of the N-rank reduce: replicas need not number alike, only hold the same edges ----------
+// An edge's content key: its start k-mer and first base — what identifies an edge of a freshly built (or retained) graph; a
+// node split makes copies that share a k-mer, and such a graph is refused (duplicate keys below).  As a 64-bit hash: two
+// different edges of one replica with one hash are refused too, never merged.
+__device__ __forceinline__ u64 edge_content_key(const GraphView &g, u64 e) {
+    const u32 s = g.e_start[e];
+    const u64 h = fp_mix(fp_mix(fp_mix(0x636f6e74656e74ULL, g.node_lo[s]), g.node_hi[s]), g.e_first[e]);
+    return h == ~0ull ? h - 1 : h;                                  // (~0 sorts the dead edges last)
+}
+// keys[e] = content key (~0 dead), ids[e] = e; out[0] += live edges, out[1] += sum over live edges of (content key, end k-mer,
+// length) mixed: the replica's CONTENT fingerprint, equal on two replicas iff they hold the same edges whatever their ids
+__global__ __launch_bounds__(BLOCK) void k_edge_content(GraphView g, u64 *keys, u32 *ids, unsigned long long *out) {
+    u64 live = 0, fp = 0;
+    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK) {
+        ids[e] = (u32)e;
+        if (!g.e_alive[e]) { keys[e] = ~0ull; continue; }
+        const u64 h = edge_content_key(g, e);
+        const u32 t = g.e_end[e];
+        keys[e] = h;
+        live++;
+        fp += fp_mix(fp_mix(fp_mix(h, g.node_lo[t]), g.node_hi[t]), g.e_len[e]);
+    }
+    for (int d = 32; d; d >>= 1) { live += __shfl_down(live, d); fp += __shfl_down(fp, d); }
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&out[0], (unsigned long long)live); atomicAdd(&out[1], (unsigned long long)fp); }
+}
+// after the sort by content key: canon[local id] = rank in that order (NONE for dead edges), inv[rank] = local id; two equal
+// neighbours raise *dup
+__global__ __launch_bounds__(BLOCK) void k_edge_canon(const u64 *skeys, const u32 *sids, u64 nlive, u32 *canon, u32 *inv, u32 *dup) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < nlive; i += (u64)gridDim.x * BLOCK) {
+        canon[sids[i]] = (u32)i;
+        inv[i] = sids[i];
+        if (i && skeys[i] == skeys[i - 1]) *dup = 1u;
+    }
+}
+// canonical pair keys back to this replica's ids (a key outside the numbering raises *bad)
+__global__ __launch_bounds__(BLOCK) void k_sup_uncanon(u64 *keys, u64 n, const u32 *inv, u64 nlive, u32 *bad) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        const u64 key = keys[i], a = key >> 32, b = key & 0xffffffffull;
+        if (a >= nlive || b >= nlive) { *bad = 1u; keys[i] = SUP_EMPTY; continue; }
+        keys[i] = ((u64)inv[a] << 32) | inv[b];
+    }
+}
+__global__ __launch_bounds__(BLOCK) void k_graph_id_fingerprint(GraphView g, unsigned long long *out) {
+    u64 h = 0;
+    const u64 tid = (u64)blockIdx.x * BLOCK + threadIdx.x, stride = (u64)gridDim.x * BLOCK;
+    for (u64 n = tid; n < g.n_nodes; n += stride)
+        if (g.node_alive[n]) h += fp_mix(fp_mix(fp_mix(0x6e6f6465ULL, n), g.node_lo[n]), g.node_hi[n]);
+    for (u64 e = tid; e < g.n_edges; e += stride)
+        if (g.e_alive[e]) h += fp_mix(fp_mix(fp_mix(fp_mix(fp_mix(0x65646765ULL, e), g.e_start[e]), g.e_end[e]), g.e_first[e]), g.e_len[e]);
+    for (int d = 32; d; d >>= 1) h += __shfl_down(h, d);
+    if ((threadIdx.x & 63) == 0) atomicAdd(out, (unsigned long long)h);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -570,8 +716,9 @@ struct Tmp {      // device arrays of one call, freed together
 };
 
 SupView sup_view(const gk_support *s) { return SupView{s->d_keys, s->d_cnt, s->cap - 1, s->d_ctr}; }
+}  // namespace
 
-// room for `want` distinct pairs at load <= 0.5 (a power of two of slots); contents are kept
+namespace gk {
 int support_reserve(gk_support *s, u64 want) {
     gk_ctx *ctx = s->ctx;
     const u64 need = pow2ceil(std::max<u64>(2 * want + 1024, 4096));
@@ -604,6 +751,146 @@ int support_counters(const gk_support *s, unsigned long long *h4) {
     GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return GK_OK;
 }
+
+int support_bucket(gk_support *s, int P, u64 *d_keys, u32 *d_cnt, u64 room, u64 *region, const u32 *canon, u64 nmap) {
+    gk_ctx *ctx = s->ctx;
+    if (P < 1 || P > 64) return fail(ctx, GK_E_INVALID, "support_bucket: 1..64 owners (the world limit of gk_dist_create)");
+    for (int p = 0; p <= P; p++) region[p] = 0;
+    if (s->cap == 0) return GK_OK;
+    const u64 nwg = (u64)ggrid(ctx, s->cap), chunk = (s->cap + nwg - 1) / nwg, n = nwg * (u64)P;
+    Tmp tmp(ctx);
+    u32 *d_counts = nullptr;
+    unsigned long long *d_off = nullptr, *d_region = nullptr;
+    u64 *d_sums = nullptr;
+    u32 *d_bad = nullptr, h_bad = 0;
+    hipError_t e = tmp.get(&d_counts, n);
+    if (e == hipSuccess) e = tmp.get(&d_off, n + 1);
+    if (e == hipSuccess) e = tmp.get(&d_sums, n / SCAN_CHUNK + 2);
+    if (e == hipSuccess) e = tmp.get(&d_region, (u64)P + 1);
+    if (e == hipSuccess) e = tmp.get(&d_bad, 1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 4, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "support_bucket: scratch");
+    hipLaunchKernelGGL(k_sup_bucket_count, dim3((unsigned)nwg), dim3(BLOCK), 0, ctx->stream, s->d_keys, s->cap, chunk, (u32)P, canon, nmap, d_counts, d_bad);
+    GK_HIP(ctx, hipGetLastError());
+    GK_HIP(ctx, scan_counts(ctx, d_counts, n, d_off, d_sums));
+    hipLaunchKernelGGL(k_sup_regions, dim3(1), dim3(64), 0, ctx->stream, d_off, nwg, (u32)P, d_region);
+    GK_HIP(ctx, hipGetLastError());
+    std::vector<unsigned long long> h(P + 1);
+    GK_HIP(ctx, hipMemcpyAsync(h.data(), d_region, (P + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_bad) return fail(ctx, GK_E_STATE, "the support names an edge that is not a live edge of this graph");
+    if (h[P] > room) return fail(ctx, GK_E_STATE, "support_bucket: " + std::to_string(h[P]) + " live slots, room for " + std::to_string(room));
+    if (h[P]) {
+        hipLaunchKernelGGL(k_sup_bucket_scatter, dim3((unsigned)nwg), dim3(BLOCK), 0, ctx->stream, s->d_keys, s->d_cnt, s->cap, chunk, (u32)P, canon, nmap, d_bad,
+                           d_off, d_keys, d_cnt);
+        GK_HIP(ctx, hipGetLastError());
+        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));         // (the scratch goes with this scope)
+    }
+    for (int p = 0; p <= P; p++) region[p] = h[p];
+    return GK_OK;
+}
+
+int support_insert(gk_support *s, const u64 *d_keys, const u32 *d_cnt, u64 n, bool checked, bool *overflow) {
+    gk_ctx *ctx = s->ctx;
+    if (overflow) *overflow = false;
+    if (n == 0) return GK_OK;
+    unsigned long long h[4];
+    if (int rc = support_counters(s, h)) return rc;
+    if (int rc = support_reserve(s, h[0] + n)) return rc;
+    s->host_valid = false;
+    if (checked) hipLaunchKernelGGL(k_sup_add_list_checked, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, d_keys, d_cnt, n, sup_view(s));
+    else hipLaunchKernelGGL(k_sup_add_list, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, d_keys, d_cnt, n, sup_view(s));
+    GK_HIP(ctx, hipGetLastError());
+    unsigned long long f[2] = {0, 0};                          // [3] table full, [4] a count wrapped
+    GK_HIP(ctx, hipMemcpyAsync(f, s->d_ctr + 3, 16, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (f[0]) return fail(ctx, GK_E_CAPACITY, "support_insert: the support table filled up (internal sizing error)");
+    if (overflow) *overflow = f[1] != 0;
+    return GK_OK;
+}
+
+int graph_edge_canon(gk_graph *g, u32 **d_canon, u32 **d_inv, u64 *nlive, u64 *content_fp) {
+    gk_ctx *ctx = g->ctx;
+    *d_canon = *d_inv = nullptr;
+    *nlive = 0; *content_fp = 0;
+    const u64 ne = g->v.n_edges;
+    Tmp tmp(ctx);
+    u64 *d_k = nullptr, *d_k2 = nullptr;
+    u32 *d_id = nullptr, *d_id2 = nullptr, *d_flag = nullptr, h_flag = 0;
+    unsigned long long *d_out = nullptr, h_out[2] = {0, 0};
+    void *d_temp = nullptr;
+    size_t temp_bytes = 0;
+    hipError_t e = tmp.get(&d_k, ne);
+    if (e == hipSuccess) e = tmp.get(&d_k2, ne);
+    if (e == hipSuccess) e = tmp.get(&d_id, ne);
+    if (e == hipSuccess) e = tmp.get(&d_id2, ne);
+    if (e == hipSuccess) e = tmp.get(&d_flag, 1);
+    if (e == hipSuccess) e = tmp.get(&d_out, 2);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, 16, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 4, ctx->stream);
+    if (e == hipSuccess && ne) e = rocprim::radix_sort_pairs(nullptr, temp_bytes, d_k, d_k2, d_id, d_id2, (size_t)ne, 0, 64, ctx->stream);
+    if (e == hipSuccess) e = tmp.get((uint8_t **)&d_temp, temp_bytes);
+    if (e != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon: scratch");
+    if (ne) {
+        hipLaunchKernelGGL(k_edge_content, dim3(ggrid(ctx, ne)), dim3(BLOCK), 0, ctx->stream, g->v, d_k, d_id, d_out);
+        GK_HIP(ctx, hipGetLastError());
+        GK_HIP(ctx, rocprim::radix_sort_pairs(d_temp, temp_bytes, d_k, d_k2, d_id, d_id2, (size_t)ne, 0, 64, ctx->stream));
+    }
+    GK_HIP(ctx, hipMemcpyAsync(h_out, d_out, 16, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    u32 *canon = nullptr, *inv = nullptr;
+    e = hipMalloc((void **)&canon, std::max<u64>(ne, 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&inv, std::max<u64>(h_out[0], 1) * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(canon, 0xff, std::max<u64>(ne, 1) * 4, ctx->stream);
+    if (e != hipSuccess) {
+        if (canon) (void)hipFree(canon);
+        if (inv) (void)hipFree(inv);
+        return hip_fail(ctx, e, "graph_edge_canon: maps");
+    }
+    if (h_out[0]) hipLaunchKernelGGL(k_edge_canon, dim3(ggrid(ctx, h_out[0])), dim3(BLOCK), 0, ctx->stream, d_k2, d_id2, (u64)h_out[0], canon, inv, d_flag);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess || h_flag) {
+        (void)hipFree(canon); (void)hipFree(inv);
+        return e != hipSuccess ? hip_fail(ctx, e, "graph_edge_canon")
+                               : fail(ctx, GK_E_STATE, "two live edges share a start k-mer and a first base (a node split made copies): their support cannot be summed by content");
+    }
+    *d_canon = canon; *d_inv = inv;
+    *nlive = h_out[0];
+    *content_fp = h_out[1] + mix64(h_out[0] ^ 0x6c697665ULL);
+    return GK_OK;
+}
+
+int support_keys_uncanon(gk_ctx *ctx, u64 *d_keys, u64 n, const u32 *d_inv, u64 nlive) {
+    if (n == 0) return GK_OK;
+    Tmp tmp(ctx);
+    u32 *d_bad = nullptr, h_bad = 0;
+    GK_HIP(ctx, tmp.get(&d_bad, 1));
+    GK_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(k_sup_uncanon, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, d_keys, n, d_inv, nlive, d_bad);
+    GK_HIP(ctx, hipGetLastError());
+    GK_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (h_bad) return fail(ctx, GK_E_STATE, "support_keys_uncanon: a pair outside the canonical edge numbering");
+    return GK_OK;
+}
+
+int support_adopt(gk_support *s, gk_support *t, u64 bad, u64 walked) {
+    gk_ctx *ctx = s->ctx;
+    GK_HIP(ctx, hipStreamSynchronize(t->ctx->stream));
+    std::swap(s->d_keys, t->d_keys); std::swap(s->d_cnt, t->d_cnt); std::swap(s->cap, t->cap); std::swap(s->d_ctr, t->d_ctr);
+    s->host_valid = false; t->host_valid = false;              // (the split and gk_support_export read the host copy: it is stale now)
+    const unsigned long long c[2] = {bad, walked}, z[5] = {0, 0, 0, 0, 0};
+    GK_HIP(ctx, hipMemcpyAsync(s->d_ctr + 3, z, 40, hipMemcpyHostToDevice, ctx->stream));
+    GK_HIP(ctx, hipMemcpyAsync(s->d_ctr + 1, c, 16, hipMemcpyHostToDevice, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return GK_OK;
+}
+}  // namespace gk
+
+namespace {
 
 // the counts as a host map (the split reads them by key)
 int support_to_host(gk_support *s) {
@@ -668,6 +955,91 @@ int gk_support_export(const gk_support *s, uint32_t *e1, uint32_t *e2, uint32_t 
     if (s->paths.size() > cap) return fail(s->ctx, GK_E_CAPACITY, "gk_support_export: need room for " + std::to_string(s->paths.size()) + " pairs");
     u64 i = 0;
     for (const auto &kv : s->paths) { e1[i] = (u32)(kv.first >> 32); e2[i] = (u32)kv.first; count[i] = kv.second; i++; }
+    return GK_OK;
+}
+
+int gk_support_merge(gk_support *dst, const gk_support *src) {
+    if (!dst || !src) return fail(dst ? dst->ctx : nullptr, GK_E_INVALID, "gk_support_merge: null support handle");
+    gk_ctx *ctx = dst->ctx;
+    if (dst == src) return fail(ctx, GK_E_INVALID, "gk_support_merge: dst and src are the same support");
+    if (src->ctx->device != ctx->device) return fail(ctx, GK_E_INVALID, "gk_support_merge: the two supports live on different devices");
+    GK_HIP(ctx, hipSetDevice(ctx->device));
+    GK_HIP(ctx, hipStreamSynchronize(src->ctx->stream));
+    unsigned long long hs[4], hd[4];
+    if (int rc = support_counters(src, hs)) return rc;
+    if (int rc = support_counters(dst, hd)) return rc;
+    // would a count wrap?  decided before dst is touched: a refused merge leaves it as it was
+    if (src->cap && dst->cap && hs[0]) {
+        Tmp tmp(ctx);
+        u32 *d_wrap = nullptr, h_wrap = 0;
+        GK_HIP(ctx, tmp.get(&d_wrap, 1));
+        GK_HIP(ctx, hipMemsetAsync(d_wrap, 0, 4, ctx->stream));
+        hipLaunchKernelGGL(k_sup_check_merge, dim3(ggrid(ctx, src->cap)), dim3(BLOCK), 0, ctx->stream, src->d_keys, src->d_cnt, src->cap, sup_view(dst), d_wrap);
+        GK_HIP(ctx, hipGetLastError());
+        GK_HIP(ctx, hipMemcpyAsync(&h_wrap, d_wrap, 4, hipMemcpyDeviceToHost, ctx->stream));
+        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (h_wrap) return fail(ctx, GK_E_CAPACITY, "gk_support_merge: a count would pass 2^32-1; nothing was added");
+    }
+    if (src->cap && hs[0]) {
+        if (int rc = support_reserve(dst, hd[0] + hs[0])) return rc;
+        dst->host_valid = false;
+        hipLaunchKernelGGL(k_sup_rehash, dim3(ggrid(ctx, src->cap)), dim3(BLOCK), 0, ctx->stream, src->d_keys, src->d_cnt, src->cap, sup_view(dst));
+        GK_HIP(ctx, hipGetLastError());
+    }
+    unsigned long long cur[4];
+    if (int rc = support_counters(dst, cur)) return rc;
+    if (cur[3]) return fail(ctx, GK_E_CAPACITY, "gk_support_merge: the support table filled up (internal sizing error)");
+    cur[1] += hs[1]; cur[2] += hs[2];
+    GK_HIP(ctx, hipMemcpyAsync(dst->d_ctr + 1, cur + 1, 16, hipMemcpyHostToDevice, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return GK_OK;
+}
+
+int gk_support_add(gk_support *s, const uint32_t *e1, const uint32_t *e2, const uint32_t *count, uint64_t n, uint64_t bad_pairs,
+                   uint64_t walked_orientations) {
+    if (!s) return fail(nullptr, GK_E_INVALID, "null support handle");
+    gk_ctx *ctx = s->ctx;
+    if (n && (!e1 || !e2 || !count)) return fail(ctx, GK_E_INVALID, "gk_support_add: null argument");
+    GK_HIP(ctx, hipSetDevice(ctx->device));
+    // the list goes into a support of its own (duplicates add up there, checked), which is then merged: s is only written
+    // once nothing can wrap
+    gk_support *t = nullptr;
+    if (int rc = gk_support_create(ctx, &t)) return rc;
+    std::unique_ptr<gk_support, void (*)(gk_support *)> own(t, gk_support_destroy);
+    if (n) {
+        std::vector<u64> keys(n);
+        for (u64 i = 0; i < n; i++) keys[i] = ((u64)e1[i] << 32) | e2[i];
+        Tmp tmp(ctx);
+        u64 *d_k = nullptr;
+        u32 *d_c = nullptr;
+        hipError_t e = tmp.get(&d_k, n);
+        if (e == hipSuccess) e = tmp.get(&d_c, n);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_k, keys.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_c, count, n * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, "gk_support_add: upload");
+        bool wrapped = false;
+        if (int rc = support_insert(t, d_k, d_c, n, true, &wrapped)) return rc;
+        if (wrapped) return fail(ctx, GK_E_CAPACITY, "gk_support_add: a count of the list would pass 2^32-1; nothing was added");
+    }
+    const unsigned long long c[2] = {bad_pairs, walked_orientations};
+    GK_HIP(ctx, hipMemcpyAsync(t->d_ctr + 1, c, 16, hipMemcpyHostToDevice, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return gk_support_merge(s, t);
+}
+
+int gk_graph_id_fingerprint(gk_graph *g, uint64_t *fp) {
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    if (!fp) return fail(ctx, GK_E_INVALID, "gk_graph_id_fingerprint: null argument");
+    Tmp tmp(ctx);
+    unsigned long long *d = nullptr, h = 0;
+    GK_HIP(ctx, tmp.get(&d, 1));
+    GK_HIP(ctx, hipMemsetAsync(d, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(k_graph_id_fingerprint, dim3(ggrid(ctx, std::max<u64>(std::max(g->v.n_nodes, g->v.n_edges), 1))), dim3(BLOCK), 0, ctx->stream, g->v, d);
+    GK_HIP(ctx, hipGetLastError());
+    GK_HIP(ctx, hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *fp = h + mix64(mix64(g->v.n_nodes ^ 0x626f756e6473ULL) ^ (g->v.n_edges + 0x9e3779b97f4a7c15ULL));     // and the id bounds
     return GK_OK;
 }
 

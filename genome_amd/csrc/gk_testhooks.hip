@@ -53,6 +53,7 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
     else if (n == "target_load_pct") ctx->hook_target_load_pct = (int)value;
     else if (n == "cc_find") ctx->hook_cc_find = (int)value;
     else if (n == "test_dist_fail_classify") ctx->hook_dist_fail_classify = (int)value;
+    else if (n == "test_dist_fail_reduce") ctx->hook_dist_fail_reduce = (int)value;
     else if (n == "test_dist_fail_exchange") ctx->hook_dist_fail = value > 0 ? -(int)value : (int)value;
     else if (n == "test_max_nb2") ctx->hook_max_nb2 = (int)std::max<int64_t>(0, value);
     else if (n == "min_lnb1") {

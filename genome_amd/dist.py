@@ -71,6 +71,15 @@ class HipDist:
         L.check(L.lib().gk_dist_allreduce_f64(self.h, v.ctypes.data_as(C.POINTER(C.c_double)), len(v), 1 if op == "max" else 0), self.ctx.h)
         return v
 
+    def reduce_support(self, graph, support):
+        """COLLECTIVE (gk_dist_reduce_support): every rank's `support` (its share of the pairs walked on its replica `graph`)
+        becomes the sum over all ranks, in this rank's own edge ids.  The replicas may number differently but must hold the same
+        edges (refused on every rank with GK_E_STATE otherwise, or after a node split); on any
+        failure every rank raises and every support is unchanged.  `graph` / `support` may be None on a rank that cannot take
+        part: it still joins the agreement, and every rank raises."""
+        L.check(L.lib().gk_dist_reduce_support(self.h, graph.h if graph is not None else None,
+                                               support.h if support is not None else None), self.ctx.h)
+
     def last_ms(self):
         ms = (C.c_float * 4)()
         L.check(L.lib().gk_dist_last_ms(self.h, ms), self.ctx.h)

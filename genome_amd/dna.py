@@ -57,3 +57,37 @@ def reads_to_bin(reads) -> bytes:
 def unpack_2bit(buf: np.ndarray, nbases: int) -> str:
     """Edge sequences come back as 2-bit codes, 4 per byte, LSB first."""
     return "".join(BASES[(int(buf[i // 4]) >> (2 * (i % 4))) & 3] for i in range(nbases))
+
+
+def bin_pair_offsets(bin_bytes, npairs: int) -> np.ndarray:
+    """Byte offsets of pairs 0..npairs in a `.bin` stream of mate records ([len:u8][ceil(len/4) bytes] each, two per pair):
+    entry i is where pair i starts, entry npairs where the last one ends.  ValueError if the stream ends inside a record."""
+    buf = bytes(bin_bytes) if not isinstance(bin_bytes, (bytes, bytearray)) else bin_bytes
+    if npairs and len(buf):
+        # a stream of equal-length records (what a sequencer's run and the generators give): the offsets are arithmetic, and
+        # one vectorised look at the length bytes confirms it
+        stride = 1 + (buf[0] + 3) // 4
+        if len(buf) >= 2 * npairs * stride:
+            lens = np.frombuffer(buf, np.uint8, count=2 * npairs * stride)[::stride]
+            if (lens == buf[0]).all():
+                return np.arange(npairs + 1, dtype=np.int64) * (2 * stride)
+    out = np.zeros(npairs + 1, np.int64)
+    pos = 0
+    for i in range(npairs):
+        out[i] = pos
+        for _ in range(2):
+            if pos >= len(buf):
+                raise ValueError(f"the stream ends inside pair {i}")
+            pos += 1 + (buf[pos] + 3) // 4
+            if pos > len(buf):
+                raise ValueError(f"the stream ends inside pair {i}")
+    out[npairs] = pos
+    return out
+
+
+def bin_pairs(bin_bytes, a: int, b: int) -> bytes:
+    """Pairs [a, b) of a `.bin` stream of mate records, as a stream of their own (a rank's share for walkPairs)."""
+    if not 0 <= a <= b:
+        raise ValueError("need 0 <= a <= b")
+    off = bin_pair_offsets(bin_bytes, b)
+    return bytes(bin_bytes[int(off[a]):int(off[b])])

@@ -149,6 +149,13 @@ class HipGraph:
         L.check(L.lib().gk_graph_id_bounds(self.h, C.byref(a), C.byref(b)), self.ctx.h)
         return a.value, b.value
 
+    def idFingerprint(self) -> int:
+        """an id-exact fingerprint (live nodes and edges WITH their ids, and the id bounds): equal on two replicas iff their ids
+        mean the same nodes and edges — what gk_dist_reduce_support checks before it adds supports keyed by edge ids"""
+        fp = C.c_uint64()
+        L.check(L.lib().gk_graph_id_fingerprint(self.h, C.byref(fp)), self.ctx.h)
+        return fp.value
+
     def removeEdgesById(self, edge_ids) -> int:             # toRemove.foreach(id => graph.removeEdge(graph.getEdge(id)))  :316
         ids = np.ascontiguousarray(edge_ids, np.uint32)
         rm = C.c_uint64()
@@ -269,4 +276,15 @@ class Support:
         got = C.c_uint64()
         L.check(L.lib().gk_support_export(self.h, L.ptr(e1, C.c_uint32), L.ptr(e2, C.c_uint32), L.ptr(cnt, C.c_uint32), n, C.byref(got)), self.ctx.h)
         return e1, e2, cnt
+
+    def add(self, e1, e2, cnt, bad: int = 0, walked: int = 0):
+        """add (e1, e2, count) triples (duplicates add up) and the two counters; GK_E_CAPACITY, and nothing added, if a count
+        would pass 2^32-1.  items() of one support added into an empty one reproduces it."""
+        e1, e2, cnt = (np.ascontiguousarray(a, np.uint32) for a in (e1, e2, cnt))
+        assert len(e1) == len(e2) == len(cnt)
+        L.check(L.lib().gk_support_add(self.h, L.ptr(e1, C.c_uint32), L.ptr(e2, C.c_uint32), L.ptr(cnt, C.c_uint32), len(e1), bad, walked), self.ctx.h)
+
+    def merge(self, other: "Support"):
+        """self += other on the device (same device); other is unchanged.  Same overflow rule as add()."""
+        L.check(L.lib().gk_support_merge(self.h, other.h), self.ctx.h)
 

@@ -285,6 +285,14 @@ class Support {
         check(gk_support_size(h_, &a, &b, &c), ctx_.handle());
         return {a, b, c};
     }
+    // add (e1, e2, count) triples (duplicates add up) and the two counters; throws (nothing added) if a count would pass 2^32-1
+    void add(const std::vector<uint32_t> &e1, const std::vector<uint32_t> &e2, const std::vector<uint32_t> &count, uint64_t badPairs = 0,
+             uint64_t walked = 0) {
+        if (e1.size() != e2.size() || e1.size() != count.size()) throw GkError(GK_E_INVALID, "Support::add: the three lists differ in length");
+        check(gk_support_add(h_, e1.data(), e2.data(), count.data(), e1.size(), badPairs, walked), ctx_.handle());
+    }
+    // *this += other on the device (the supports of two walks on one GPU); other is unchanged
+    void merge(const Support &other) { check(gk_support_merge(h_, other.h_), ctx_.handle()); }
 
   private:
     Context &ctx_;

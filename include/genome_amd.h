@@ -302,6 +302,20 @@ int gk_dist_gather_map(gk_dist *d, gk_map *local, gk_map **full);
 int gk_dist_gather_classified_map(gk_dist *d, gk_map *local, gk_map **full);
 /* neighbour lookups this rank has asked of other ranks in classified gathers since the handle was created */
 int gk_dist_classify_queries(gk_dist *d, uint64_t *n);
+/* The paired-end support over the ranks (GraphSimplifier.scala:172-186, 209-248: the driver sums the WalkingActors' counters
+ * into one pathsMap).  Every rank holds a replica of the graph and has walked ITS share of the pairs into `sup`; afterwards
+ * every rank's sup holds the sum over all ranks: every (e1, e2) count, bad pairs and walked orientations added up, the
+ * distinct-pair count recomputed, keyed by THIS rank's edge ids.  The replicas need not number their edges alike: the pairs
+ * travel in a canonical numbering (live edges ordered by (start k-mer, first base)), so the replicas must hold the same edges —
+ * a fresh build or a retained one, before any node split (a split makes copies that share a start k-mer: GK_E_STATE).  Before
+ * any payload moves the ranks agree on every rank's status and on equal content fingerprints of g; after the owners' merge
+ * on "no count passed 2^32-1", and after the rebuild once more, before anything is swapped in.  If any of this fails on any
+ * rank, every rank returns an error (GK_E_STATE for replicas that differ, GK_E_CAPACITY for an overflow), every sup is left
+ * unchanged and no rank is left waiting in a receive.  Pairs go to an owner rank by a hash of the canonical (e1, e2): one
+ * all-to-all of 12-byte records, the owners merge, then every owner's shard goes to every rank.  world <= 64 (gk_dist_create).
+ * world == 1: only the checks run.  COLLECTIVE. */
+typedef struct gk_support gk_support;
+int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup);
 
 /* ---- Graph: S/data/graph/Graph.scala ------------------------------------------------------- */
 /* Graph.buildGraph(k, kmersFreq) (:269-382): degree classification of every live key through
@@ -355,6 +369,11 @@ int gk_graph_replace_start(gk_graph *g, uint32_t edge_id, uint32_t new_start_nod
 int gk_graph_replace_end(gk_graph *g, uint32_t edge_id, uint32_t new_end_node);
 /* ids run from 0 to these bounds (dead nodes / edges keep theirs) */
 int gk_graph_id_bounds(gk_graph *g, uint64_t *node_ids, uint64_t *edge_ids);
+/* An id-exact fingerprint of the graph: a sum mod 2^64 over the live nodes (id, k-mer) and the live edges (id, start id, end id,
+ * first base, length), each mixed through a 64-bit hash, plus the id bounds.  Two graphs share it iff (up to hash collisions)
+ * their ids mean the same nodes and edges.  gk_graph_checksum is content-only and cannot tell that.  Note: two builds of one
+ * table need not number alike (ids follow table slot order, output ranges come from atomic cursors). */
+int gk_graph_id_fingerprint(gk_graph *g, uint64_t *fp);
 /* MapGraph.removeEdge (:191-195) by edge id (each id once, as the reference's `toRemove` Set, GraphSimplifier.scala:270,316) */
 int gk_graph_remove_edges_by_id(gk_graph *g, const uint32_t *edge_ids, uint64_t n, uint64_t *removed);
 
@@ -369,6 +388,13 @@ int gk_support_size(const gk_support *s, uint64_t *pairs, uint64_t *bad_pairs, u
  * walks, merge of the per-thread counts} */
 int gk_support_last_ms(const gk_support *s, float *ms5);
 int gk_support_export(const gk_support *s, uint32_t *e1, uint32_t *e2, uint32_t *count, uint64_t cap, uint64_t *n);   /* unordered */
+/* Add n (e1, e2, count) triples and the two counters into s; duplicates in the list add up.  Export, then add into an empty
+ * support, reproduces the support.  A count that would pass 2^32-1 fails with GK_E_CAPACITY, and s is then unchanged. */
+int gk_support_add(gk_support *s, const uint32_t *e1, const uint32_t *e2, const uint32_t *count, uint64_t n, uint64_t bad_pairs,
+                   uint64_t walked_orientations);
+/* dst += src on the device (both supports on the same device; dst != src): every (e1, e2) count, bad pairs and walked
+ * orientations.  src is unchanged.  Same overflow rule as gk_support_add. */
+int gk_support_merge(gk_support *dst, const gk_support *src);
 /* :213-247 for the first `npairs` pairs of a `.bin` stream (two records per pair; pairs with a mate shorter than k are
  * skipped, :213).  `positions` = gk_graph_position_map of THIS graph in its current state (GK_E_STATE otherwise).  For each
  * pair the four getAll (:214-217) run as one batch on the device; `annotate` (:192-206) drops an orientation whose mates lie

@@ -32,7 +32,8 @@ extern "C" {
  * path halving only / no path writes / start node only), "target_load_pct" (load factor new tables are sized for, percent;
  * 0 = 65), and the failure injections of the exchange: "test_dist_small_send" (a send region far too small: re-routed in
  * place), "test_dist_fail_exchange" (this rank's next exchange fails locally with the given code), "test_dist_fail_classify"
- * (this rank cannot stage the queries of its next classified gather). */
+ * (this rank cannot stage the queries of its next classified gather), "test_dist_fail_reduce" (this rank fails the owner merge of
+ * its next gk_dist_reduce_support, after the records were exchanged). */
 int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value);
 
 /* TEST transport: the ranks are threads of ONE process on ONE device; sends, receives and reductions go through a hub in the
