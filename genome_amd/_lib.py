@@ -104,6 +104,7 @@ SIGNATURES = {
     "gk_dist_barrier": (C.c_int, [vp]),
     "gk_dist_allreduce_f64": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int, C.c_int]),
     "gk_dist_count_reads_dev": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_int, u64p, u64p]),
+    "gk_dist_count_reads": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint64, u64p, u64p]),
     "gk_dist_route_begin": (C.c_int, [vp, C.c_int, vp, C.c_uint64, C.c_int]),
     "gk_dist_count_routed": (C.c_int, [vp, vp, u64p, u64p]),
     "gk_dist_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),

@@ -53,6 +53,7 @@ struct gk_dist {
     // routes that were begun and not yet counted: at most three, first in, first out
     struct Route {
         int k = 0, read_len = 0; const void *records = nullptr; gk::u64 nreads = 0;
+        const uint32_t *offsets = nullptr; gk::u64 windows = 0;     // offset framing (a ragged host stream): record r at offsets[r]
         // settled (owner thread): the routing kernel has finished, a region that was too small has been routed again, and
         // this rank's verdict on its own half of the exchange is in local_rc — what it will tell its peers
         bool settled = false;
@@ -66,6 +67,11 @@ struct gk_dist {
         std::string error_text;
     };
     Route route[NROUTE];
+    // gk_dist_count_reads: one staging area (records) and one offset table per batch it keeps in flight — a begun batch's records
+    // live until its gk_dist_count_routed returns; kept between calls, released by gk_dist_destroy
+    uint8_t *d_stage[NROUTE] = {nullptr, nullptr, nullptr};
+    uint32_t *d_stage_offs[NROUTE] = {nullptr, nullptr, nullptr};
+    gk::u64 stage_bytes[NROUTE] = {0, 0, 0}, stage_offs_bytes[NROUTE] = {0, 0, 0};
     int head = 0, npending = 0;                      // route[head] is the oldest; the next route goes to (head + npending) % NROUTE
     gk::u64 nexchanged = 0;                              // exchanges posted so far: the next one receives into d_recv[nexchanged & 1]
     unsigned long long *d_route_cnt = nullptr;       // [NROUTE][SKM_COUNT_WORDS] counters of the routing kernels on the second stream

@@ -245,6 +245,7 @@ void gk_dist_destroy(gk_dist *d) {
     if (d->ctx && d->ctx->copy_stream) (void)hipStreamSynchronize(d->ctx->copy_stream);
     for (int i = 0; i < gk_dist::NROUTE; i++) if (d->d_sendbuf[i]) (void)hipFree(d->d_sendbuf[i]);
     for (int i = 0; i < 2; i++) if (d->d_recv[i]) (void)hipFree(d->d_recv[i]);
+    for (int i = 0; i < gk_dist::NROUTE; i++) { if (d->d_stage[i]) (void)hipFree(d->d_stage[i]); if (d->d_stage_offs[i]) (void)hipFree(d->d_stage_offs[i]); }
     for (int i = 0; i < gk_dist::NROUTE; i++) if (d->route_done[i]) (void)hipEventDestroy(d->route_done[i]);
     for (int i = 0; i < gk_dist::NROUTE; i++) if (d->exch_done[i]) (void)hipEventDestroy(d->exch_done[i]);
     if (d->join) (void)hipEventDestroy(d->join);
@@ -319,17 +320,32 @@ static u64 route_want_records(int k, int P, u64 nreads, int read_len) {
     const double per_read = std::max(2.0, (double)nk / std::max(1.0, (k - 9) / 2.0)) * 1.5 + 1.0;
     return std::max<u64>((u64)1024 * P, (u64)((double)nreads * per_read) / P * P);
 }
+// the same for a ragged batch, from the window total its host walk counted (not nreads x the longest read's windows)
+static u64 route_want_records_ragged(int k, int P, u64 nreads, u64 windows) {
+    const double runs = std::max(2.0 * (double)nreads, (double)windows / std::max(1.0, (k - 9) / 2.0));
+    return std::max<u64>((u64)1024 * P, (u64)(runs * 1.5 + (double)nreads) / P * P);
+}
+// launch (or re-launch) route slot b's kernel on the context's second stream, in its batch's framing
+static int route_launch(gk_dist *d, int b) {
+    gk_ctx *ctx = d->ctx;
+    const gk_dist::Route &rt = d->route[b];
+    unsigned long long *d_rc = d->d_route_cnt + b * SKM_COUNT_WORDS, *h_rc = d->h_route_cnt + b * SKM_COUNT_WORDS;
+    ctx->copy_other_pending = true;
+    if (rt.offsets) return skm_route_launch(ctx, ctx->copy_stream, d_rc, h_rc, rt.k, rt.records, rt.offsets, rt.nreads, rt.windows, d->world, d->d_sendbuf[b], d->send_cap[b]);
+    return skm_route_launch(ctx, ctx->copy_stream, d_rc, h_rc, rt.k, rt.records, rt.nreads, rt.read_len, d->world, d->d_sendbuf[b], d->send_cap[b]);
+}
+static bool route_has_windows(const gk_dist::Route &rt) { return rt.nreads && (rt.offsets ? rt.windows > 0 : rt.read_len >= rt.k); }
 
-// Route this rank's reads for a later gk_dist_count_routed on the context's second stream and return at once: the routing
-// kernel (0.6 ms per 10^6 reads, issue-bound) then overlaps whatever the main stream is doing — in a streaming loop, the
-// owner pipeline of an earlier batch.  The records buffer must stay valid until the batch's gk_dist_count_routed returns.
-int gk_dist_route_begin(gk_dist *d, int k, const void *dev_records, uint64_t nreads, int read_len) {
-    if (int rc = dist_check(d)) return rc;
+// Begin a route: fixed stride (offsets == nullptr), or the offset framing of a host-walked ragged batch.  carry_rc != 0: this rank
+// has already failed this batch (its records could not be staged) — the batch is begun empty, carrying the failure, and its
+// gk_dist_count_routed tells every rank, which all drop it together.
+static int route_begin_impl(gk_dist *d, int k, const void *dev_records, const uint32_t *dev_offsets, uint64_t nreads, int read_len, uint64_t windows,
+                            int carry_rc = GK_OK, const std::string &carry_err = std::string()) {
     gk_ctx *ctx = d->ctx;
     constexpr int NR = gk_dist::NROUTE;
     drain_garbage(d);
     if (d->npending >= NR) return fail(ctx, GK_E_STATE, "gk_dist_route_begin: three routes are already waiting (gk_dist_count_routed consumes one)");
-    if (!dev_records && nreads) return fail(ctx, GK_E_INVALID, "gk_dist_route_begin: null records");
+    if (!dev_records && nreads && !carry_rc) return fail(ctx, GK_E_INVALID, "gk_dist_route_begin: null records");
     if (read_len < 0 || read_len > 255) return fail(ctx, GK_E_FORMAT, "read_len must be 0..255 (one length byte per record)");
     if (!k_supported(k)) return fail(ctx, GK_E_UNSUPPORTED_K, "k=" + std::to_string(k) + " unsupported");
     const int P = d->world, slot = gk_skm_slot_bytes(k);
@@ -344,7 +360,7 @@ int gk_dist_route_begin(gk_dist *d, int k, const void *dev_records, uint64_t nre
     }
     const int b = (d->head + d->npending) % NR;
     // (the buffer's previous batch was counted before this slot could come round again: its records have left)
-    u64 want = std::max(route_want_records(k, P, nreads, read_len), d->send_cap[b]);
+    u64 want = std::max(dev_offsets ? route_want_records_ragged(k, P, nreads, windows) : route_want_records(k, P, nreads, read_len), d->send_cap[b]);
     if (ctx->hook_dist_small_send > 0) {      // test hook: THIS route gets a send buffer of so many records — the in-place re-route must repair it
         GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
         if (d->d_sendbuf[b]) { GK_HIP(ctx, hipFree(d->d_sendbuf[b])); d->d_sendbuf[b] = nullptr; d->send_cap[b] = 0; }
@@ -354,16 +370,25 @@ int gk_dist_route_begin(gk_dist *d, int k, const void *dev_records, uint64_t nre
     gk_dist::Route &rt = d->route[b];
     rt = gk_dist::Route();
     rt.k = k; rt.read_len = read_len; rt.records = dev_records; rt.nreads = nreads;
+    rt.offsets = dev_offsets; rt.windows = windows;
     // A failure from here on is THIS RANK'S ALONE, and its peers are going to exchange this batch: the batch is begun all the
     // same, carrying the failure, and gk_dist_count_routed tells everybody (status word of the counts exchange).
-    int rc = dist_grow(ctx, &d->d_sendbuf[b], &d->send_cap[b], want, slot);
-    ctx->copy_other_pending = true;
-    if (!rc) rc = skm_route_launch(ctx, ctx->copy_stream, d->d_route_cnt + b * SKM_COUNT_WORDS, d->h_route_cnt + b * SKM_COUNT_WORDS, k, dev_records, nreads,
-                                   read_len, P, d->d_sendbuf[b], d->send_cap[b]);
-    if (rc) { rt.settled = true; rt.local_rc = rc; rt.local_err = ctx->err; (void)hipGetLastError(); }
+    int rc = carry_rc;
+    if (rc) { rt.records = nullptr; rt.offsets = nullptr; rt.nreads = 0; rt.windows = 0; }
+    if (!rc) rc = dist_grow(ctx, &d->d_sendbuf[b], &d->send_cap[b], want, slot);
+    if (!rc) rc = route_launch(d, b);
+    if (rc) { rt.settled = true; rt.local_rc = rc; rt.local_err = carry_rc ? carry_err : ctx->err; (void)hipGetLastError(); }
     GK_HIP(ctx, hipEventRecord(d->route_done[b], ctx->copy_stream));
     d->npending++;
     return GK_OK;
+}
+
+// Route this rank's reads for a later gk_dist_count_routed on the context's second stream and return at once: the routing
+// kernel (0.6 ms per 10^6 reads, issue-bound) then overlaps whatever the main stream is doing — in a streaming loop, the
+// owner pipeline of an earlier batch.  The records buffer must stay valid until the batch's gk_dist_count_routed returns.
+int gk_dist_route_begin(gk_dist *d, int k, const void *dev_records, uint64_t nreads, int read_len) {
+    if (int rc = dist_check(d)) return rc;
+    return route_begin_impl(d, k, dev_records, nullptr, nreads, read_len, 0);
 }
 
 // Owner thread: wait for route slot b's kernel, take the route again (bigger, in place) while a region was too small, and
@@ -373,20 +398,19 @@ static void route_settle(gk_dist *d, int b, float *ms) {
     gk_dist::Route &rt = d->route[b];
     if (rt.settled) return;
     const double t0 = now_ms();
-    const int k = rt.k, P = d->world, slot = d->slot;
-    unsigned long long *d_rc = d->d_route_cnt + b * SKM_COUNT_WORDS, *h_rc = d->h_route_cnt + b * SKM_COUNT_WORDS;
+    const int P = d->world, slot = d->slot;
+    const unsigned long long *h_rc = d->h_route_cnt + b * SKM_COUNT_WORDS;
     int rrc = GK_OK;
     hipError_t e = hipEventSynchronize(d->route_done[b]);            // this route only: later ones may already be queued behind it
     if (e != hipSuccess) rrc = hip_fail(ctx, e, "gk_dist: waiting for the route");
-    if (!rrc) rrc = skm_route_finish(ctx, h_rc, rt.nreads && rt.read_len >= k, P, d->send_cap[b], rt.recs, rt.kmers);
+    if (!rrc) rrc = skm_route_finish(ctx, h_rc, route_has_windows(rt), P, d->send_cap[b], rt.recs, rt.kmers);
     for (int attempt = 0; rrc == GK_E_CAPACITY && attempt < 4; attempt++) {       // a region was too small: route again, in place, bigger
         u64 worst = 0;
         for (int p = 0; p < P; p++) worst = std::max<u64>(worst, rt.recs[p]);
         const u64 want = std::max<u64>(d->send_cap[b] * 2, (worst + worst / 8 + 1024) * P);
         if ((e = hipStreamSynchronize(ctx->copy_stream)) != hipSuccess) { rrc = hip_fail(ctx, e, "gk_dist: re-route"); break; }   // (later routes share the stream)
         if ((rrc = dist_grow(ctx, &d->d_sendbuf[b], &d->send_cap[b], want, slot)) != GK_OK) break;
-        ctx->copy_other_pending = true;
-        if ((rrc = skm_route_launch(ctx, ctx->copy_stream, d_rc, h_rc, k, rt.records, rt.nreads, rt.read_len, P, d->d_sendbuf[b], d->send_cap[b])) != GK_OK) break;
+        if ((rrc = route_launch(d, b)) != GK_OK) break;
         if ((e = hipStreamSynchronize(ctx->copy_stream)) != hipSuccess) { rrc = hip_fail(ctx, e, "gk_dist: re-route"); break; }
         rrc = skm_route_finish(ctx, h_rc, true, P, d->send_cap[b], rt.recs, rt.kmers);
     }
@@ -559,6 +583,117 @@ int gk_dist_count_reads_dev(gk_dist *d, gk_map *local, const void *dev_records, 
     if (!local || local->ctx != d->ctx) return fail(d->ctx, GK_E_INVALID, "gk_dist_count_reads_dev: the local map must live on the handle's context");
     if (int rc = gk_dist_route_begin(d, local->k, dev_records, nreads, read_len)) return rc;
     return gk_dist_count_routed(d, local, occurrences_sent, occurrences_owned);
+}
+
+// FreqFilter.add over this rank's HOST `.bin` stream (ragged or not), every k-mer counted by its owner.
+//   1. the whole stream's framing is walked on the host and cut into chunks by gk_map_count_reads' rules (map_cut_chunk)
+//      before anything moves;
+//   2. ONE all-gather of (status | chunk count): a malformed stream anywhere -> GK_E_FORMAT on every rank, nothing moved, every
+//      `local` untouched; else every rank runs max(chunk count) rounds — a rank out of chunks routes empty batches — so that all
+//      of them issue the same sequence of transport operations;
+//   3. the rounds stream through route_begin / count_routed three batches deep: chunk i+1 (and i+2) is uploaded and routed on
+//      the context's second stream while chunk i is exchanged and counted.  A run of equal-length records takes the fixed-stride
+//      route, a ragged chunk the offset-framed one (its offset table travels with it).
+// A rank that fails a round after streaming began (an exchange dropped by agreement, a HIP error) begins its remaining batches
+// empty and carrying the failure: its peers learn it from the status word of the next counts exchange, every rank goes through
+// every round without a payload, and every rank returns an error.  `local` then holds an unspecified subset of the counts.
+int gk_dist_count_reads(gk_dist *d, gk_map *local, const uint8_t *bin, size_t nbytes, uint64_t nreads, uint64_t *occurrences_sent,
+                        uint64_t *occurrences_owned) {
+    if (int rc = dist_check(d)) return rc;
+    gk_ctx *ctx = d->ctx;
+    constexpr int NR = gk_dist::NROUTE;
+    if (occurrences_sent) *occurrences_sent = 0;
+    if (occurrences_owned) *occurrences_owned = 0;
+    drain_garbage(d);
+    // ---- 1. this rank's verdict on its own stream (a failure here is announced in step 2, never returned before it)
+    int my_rc = GK_OK;
+    std::vector<BinChunk> chunks;            // (a run of equal-length records carries no offset table)
+    if (!local || local->ctx != ctx) my_rc = fail(ctx, GK_E_INVALID, "gk_dist_count_reads: the local map must live on the handle's context");
+    else if (!bin && nreads) my_rc = fail(ctx, GK_E_INVALID, "gk_dist_count_reads: null stream");
+    else if (d->npending) my_rc = fail(ctx, GK_E_STATE, "gk_dist_count_reads: routes begun with gk_dist_route_begin are still waiting");
+    else if (!k_supported(local->k)) my_rc = fail(ctx, GK_E_UNSUPPORTED_K, "k=" + std::to_string(local->k) + " unsupported");
+    size_t pos = 0;
+    u64 r = 0;
+    while (!my_rc && r < nreads) {
+        int err = 0;
+        BinChunk c = map_cut_chunk(local, bin, nbytes, nreads, pos, r, true, &err);
+        if (err) {
+            my_rc = fail(ctx, GK_E_FORMAT, err == 1 ? "truncated .bin stream: record " + std::to_string(c.r_begin + c.offs.size()) + " starts past the end"
+                                                    : "truncated .bin stream inside record " + std::to_string(c.r_begin + c.offs.size()));
+            break;
+        }
+        if (!c.valid) break;
+        pos += c.bytes; r += c.reads;
+        if (c.uniform && c.first_len >= 0 && !ctx->hook_host_ragged) { c.offs.clear(); c.offs.shrink_to_fit(); }
+        else if (c.offs.empty()) {        // (host_ragged: a run of equal-length records goes the offset-framed way too)
+            const u32 rb = 1 + (u32)(c.first_len + 3) / 4;
+            c.offs.resize(c.reads + 1);
+            for (u64 i = 0; i <= c.reads; i++) c.offs[i] = (u32)(i * rb);
+        }
+        chunks.push_back(std::move(c));
+    }
+    const std::string my_err = my_rc ? ctx->err : std::string();
+    // ---- 2. every rank's status and chunk count, in one collective
+    if (int rc = dist_quiesce(d)) return rc;
+    constexpr unsigned long long BAD = 1ull << 63;
+    const unsigned long long word = my_rc ? BAD | (unsigned long long)(-(long long)my_rc) : (unsigned long long)chunks.size();
+    GK_HIP(ctx, hipMemcpyAsync(d->d_cnt + 2 * 64, &word, 8, hipMemcpyHostToDevice, ctx->stream));
+    GK_NCCL(ctx, xAllGather(d, d->d_cnt + 2 * 64, d->d_cnt, 1, ncclUint64, ctx->stream));
+    GK_HIP(ctx, hipMemcpyAsync(d->h_cnt, d->d_cnt, (size_t)d->world * 8, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    u64 rounds = 0;
+    int bad = -1, malformed = -1;
+    for (int p = 0; p < d->world; p++) {
+        const unsigned long long w = d->h_cnt[p];
+        if (!(w & BAD)) { rounds = std::max<u64>(rounds, w); continue; }
+        if (bad < 0) bad = p;
+        if (malformed < 0 && -(long long)(w & ~BAD) == GK_E_FORMAT) malformed = p;
+    }
+    if (malformed >= 0)
+        return my_rc == GK_E_FORMAT ? fail(ctx, GK_E_FORMAT, my_err)
+                                    : fail(ctx, GK_E_FORMAT, "the .bin stream of rank " + std::to_string(malformed) + " is malformed: no rank counted anything");
+    if (my_rc) return fail(ctx, my_rc, my_err);
+    if (bad >= 0) return fail(ctx, GK_E_COMM, "rank " + std::to_string(bad) + " could not start its count: no rank counted anything");
+    // ---- 3. the rounds
+    const int k = local->k;
+    int failed = GK_OK;
+    std::string failed_err;
+    auto grow = [&](void **buf, u64 *have, u64 want) -> int {
+        if (*have >= want && *buf) return GK_OK;
+        if (*buf) GK_HIP(ctx, hipFree(*buf));
+        *buf = nullptr; *have = 0;
+        GK_HIP(ctx, hipMalloc(buf, want));
+        *have = want;
+        return GK_OK;
+    };
+    auto begin = [&](u64 i) -> int {
+        const int s = (int)(i % NR);      // (batch i - 3 used this area: it was counted, its route has finished)
+        if (failed || i >= chunks.size()) return route_begin_impl(d, k, nullptr, nullptr, 0, 0, 0, failed, failed_err);
+        const BinChunk &c = chunks[i];
+        const bool ragged = !c.offs.empty();
+        int rc = grow((void **)&d->d_stage[s], &d->stage_bytes[s], c.bytes + 64);
+        if (!rc && ragged) rc = grow((void **)&d->d_stage_offs[s], &d->stage_offs_bytes[s], c.offs.size() * sizeof(u32));
+        hipError_t e = hipSuccess;
+        if (!rc) e = hipMemcpyAsync(d->d_stage[s], bin + c.begin, c.bytes, hipMemcpyHostToDevice, ctx->copy_stream);
+        if (!rc && ragged && e == hipSuccess) e = hipMemcpyAsync(d->d_stage_offs[s], c.offs.data(), c.offs.size() * sizeof(u32), hipMemcpyHostToDevice, ctx->copy_stream);
+        if (!rc && e != hipSuccess) rc = hip_fail(ctx, e, "gk_dist_count_reads: staging upload");
+        if (rc) return route_begin_impl(d, k, nullptr, nullptr, 0, 0, 0, rc, ctx->err);
+        if (!ragged) return route_begin_impl(d, k, d->d_stage[s], nullptr, c.reads, c.first_len, 0);
+        return route_begin_impl(d, k, d->d_stage[s], d->d_stage_offs[s], c.reads, 255, c.occ);
+    };
+    u64 begun = 0, sent = 0, owned = 0;
+    for (; begun < std::min<u64>(rounds, NR); begun++) { if (int rc = begin(begun)) return rc; }
+    for (u64 i = 0; i < rounds; i++) {
+        uint64_t s1 = 0, o1 = 0;
+        const int rc = gk_dist_count_routed(d, local, &s1, &o1);
+        if (rc && !failed) { failed = rc; failed_err = ctx->err; }
+        sent += s1; owned += o1;
+        if (begun < rounds) { if (int rc2 = begin(begun++)) return rc2; }
+    }
+    if (failed) return fail(ctx, failed, failed_err + " (gk_dist_count_reads: the local map holds an unspecified part of the counts)");
+    if (occurrences_sent) *occurrences_sent = sent;
+    if (occurrences_owned) *occurrences_owned = owned;
+    return GK_OK;
 }
 
 int gk_dist_last_ms(gk_dist *d, float *ms4) {

@@ -7,6 +7,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "../../include/genome_amd.h"
 #include "gk_device.h"
@@ -259,6 +260,15 @@ constexpr int PART_NOT_UNIFORM = 2;      // ReadSrc::verify_uniform failed: walk
 struct PartPlan { bool estimate = false; bool fine_exact = false; bool check_canon = false; double grow_ahead = 1.0; };
 int part_count(gk_map *m, PartScratch **pps, const ReadSrc &src, const uint64_t *d_keys, uint64_t nkeys_in, uint64_t nkeys_bound,
                bool from_empty, const PartPlan &plan);
+// one chunk of a host `.bin` stream, cut by gk_map_count_reads' rules (gk_table.hip: map_cut_chunk)
+struct BinChunk {
+    size_t begin = 0, bytes = 0;
+    uint64_t r_begin = 0, reads = 0, occ = 0;
+    int first_len = -1;
+    bool uniform = true, unverified = false, valid = false;
+    std::vector<uint32_t> offs;          // record offsets from `begin` and the end (empty for a run of equal-length records)
+};
+BinChunk map_cut_chunk(gk_map *m, const uint8_t *bin, size_t nbytes, uint64_t nreads, size_t pos, uint64_t r, bool walk, int *err);
 int map_fire_prefetch(gk_map *m, hipEvent_t after);   // issue the armed host -> staging uploads on the copy stream behind `after` (nullptr: at once)
 int map_ensure_sample(gk_map *m);                    // allocate the distinct-key sample set on first use
 // if the table cannot take `new_distinct` more keys, grow it (rehash, or plain re-allocation from empty) for `size_for` more
@@ -269,6 +279,10 @@ int ctx_check_format(gk_ctx *ctx);                   // GK_E_FORMAT (and reset) 
 constexpr int SKM_COUNT_WORDS = 2 * 64 + 1;
 int skm_route_launch(gk_ctx *ctx, hipStream_t st, unsigned long long *d_counts, unsigned long long *h_counts, int k, const void *dev_records,
                      uint64_t nreads, int read_len, int P, void *dev_out, uint64_t out_cap_records);
+// the same over a ragged stream: record r spans [dev_offsets[r], dev_offsets[r + 1]) of dev_records (a framing the host has walked),
+// `windows` = the k-mer windows of all nreads records (what the send regions are sized from)
+int skm_route_launch(gk_ctx *ctx, hipStream_t st, unsigned long long *d_counts, unsigned long long *h_counts, int k, const void *dev_records,
+                     const uint32_t *dev_offsets, uint64_t nreads, uint64_t windows, int P, void *dev_out, uint64_t out_cap_records);
 int skm_route_finish(gk_ctx *ctx, const unsigned long long *h_counts, bool launched, int P, uint64_t out_cap_records, uint64_t *rec_counts_host,
                      uint64_t *kmer_counts_host);
 // lanes per read in the window loops: 64 for reads, 32/16 for short records (super-k-mers)

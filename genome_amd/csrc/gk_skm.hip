@@ -98,11 +98,16 @@ __device__ __forceinline__ void write_record(const u32 *tile, u32 bit, int nbase
 // alternating from window to window — not something hashed minimizers do on real reads) is redone in
 // groups of 16 reads, which always fit (16 x 254 windows).
 static constexpr int DESC_CAP = 4096;
-template <int SLOT>
-__global__ __launch_bounds__(BLOCK) void k_skm_route(const uint8_t *__restrict__ rec, u64 nreads, u32 stride, int k, int P,
+//
+// Two framings, chosen at compile time (OFFS): fixed stride (record r at r * stride), or an offset table walked on the host
+// (record r at offsets[r], offsets[nreads] = the end: a ragged `.bin` stream).  The offset form copies the tile's 65 offsets
+// into LDS once per tile; the fixed-stride instantiation compiles that away.
+template <int SLOT, bool OFFS>
+__global__ __launch_bounds__(BLOCK) void k_skm_route(const uint8_t *__restrict__ rec, const u32 *__restrict__ offsets, u64 nreads, u32 stride, int k, int P,
                                                      WindowLimits lim, u64 region_cap /* records per owner region */, unsigned long long *cursors,
                                                      unsigned long long *kmer_counts, u32 *overflow, uint8_t *__restrict__ out) {
     __shared__ __attribute__((aligned(16))) u32 tile[TILE_WORDS];
+    __shared__ u32 toff[OFFS ? TILE_READS + 1 : 1];       // offset framing: the tile's record offsets (read r at toff[r])
     __shared__ u32 strips[(BLOCK / 64) * MAX_POS], strips2[(BLOCK / 64) * MAX_POS];
     __shared__ u32 desc[DESC_CAP];            // r (6 bits) | first window (8) << 6 | run length (8) << 14 | owner (6) << 22
     __shared__ u32 hist[MAX_PARTS], t_kmer[MAX_PARTS], h_kmer[MAX_PARTS];
@@ -118,7 +123,15 @@ __global__ __launch_bounds__(BLOCK) void k_skm_route(const uint8_t *__restrict__
         const int nr = (int)min((u64)TILE_READS, nreads - r0);
         __syncthreads();
         GK_TICK(4);
-        const u64 a0 = stage_tile(tile, rec, r0 * stride, (r0 + nr) * stride);
+        u64 a0;
+        if constexpr (OFFS) {
+            if (threadIdx.x <= (u32)nr) toff[threadIdx.x] = offsets[r0 + threadIdx.x];
+            a0 = stage_tile(tile, rec, offsets[r0], offsets[r0 + nr]);
+        } else {
+            a0 = stage_tile(tile, rec, r0 * stride, (r0 + nr) * stride);
+        }
+        // byte offset of the tile's read r in LDS
+        auto rec_at = [&](int r) -> u32 { if constexpr (OFFS) return (u32)((u64)toff[r] - a0); else return (u32)((r0 + r) * stride - a0); };
         const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
         u32 *strip = strips + wave * MAX_POS, *strip2 = strips2 + wave * MAX_POS;
         int gsz = TILE_READS, g0 = 0;
@@ -131,7 +144,7 @@ __global__ __launch_bounds__(BLOCK) void k_skm_route(const uint8_t *__restrict__
             GK_TICK(0);
             // ---- phase 1
             for (int r = g0 + wave; r < g1; r += BLOCK / 64) {
-                const u32 ro = (u32)((r0 + r) * stride - a0);
+                const u32 ro = rec_at(r);
                 const int len = record_len(tb, ro, lim), nk = len - k + 1, nm = len - m + 1;
                 const u32 bit0 = (ro + 1) * 8;
                 __builtin_amdgcn_wave_barrier();
@@ -212,7 +225,7 @@ __global__ __launch_bounds__(BLOCK) void k_skm_route(const uint8_t *__restrict__
                 const u32 dsc = desc[i];
                 const int r = g0 + (int)(dsc & 63u), p = (int)((dsc >> 6) & 255u), rl = (int)((dsc >> 14) & 255u), o = (int)(dsc >> 22);
                 if (base[o] == ~0ull) continue;
-                const u32 ro = (u32)((r0 + r) * stride - a0);
+                const u32 ro = rec_at(r);
                 const int nrec = (rl + rmax - 1) / rmax;
                 const u64 slot0 = base[o] + atomicAdd(&hist[o], (u32)nrec);
                 for (int c = 0; c < nrec; c++) {
@@ -234,15 +247,17 @@ namespace gk {
 // The routing kernel, launched on `st` with its counters in d_counts (SKM_COUNT_WORDS words: cursors, k-mer counts, overflow)
 // and their copy-back to h_counts queued behind it; nothing is waited for.  skm_route_finish reads h_counts once the stream
 // has been synchronised.  (gk_dist routes batch i+1 on a second stream while the owner pipeline of batch i runs.)
-int skm_route_launch(gk_ctx *ctx, hipStream_t st, unsigned long long *d_counts, unsigned long long *h_counts, int k, const void *dev_records,
-                     uint64_t nreads, int read_len, int P, void *dev_out, uint64_t out_cap_records) {
+// (fixed stride: every record is 1 + ceil(read_len / 4) bytes; offset framing: record r spans [offsets[r], offsets[r + 1]) —
+// a table the host built while walking the stream's framing — and `windows` is the total the walk counted)
+static int skm_route_go(gk_ctx *ctx, hipStream_t st, unsigned long long *d_counts, unsigned long long *h_counts, int k, const void *dev_records,
+                        const u32 *dev_offsets, uint64_t nreads, int read_len, uint64_t windows, int P, void *dev_out, uint64_t out_cap_records) {
     if (!k_supported(k)) return fail(ctx, GK_E_UNSUPPORTED_K, "k=" + std::to_string(k) + " unsupported");
     if (P < 1 || P > MAX_PARTS) return fail(ctx, GK_E_INVALID, "P must be 1.." + std::to_string(MAX_PARTS));
     if (!dev_records && nreads) return fail(ctx, GK_E_INVALID, "null argument");
     if (read_len < 0 || read_len > 255) return fail(ctx, GK_E_FORMAT, "read_len must be 0..255");
     GK_HIP(ctx, hipSetDevice(ctx->device));
     for (int i = 0; i < SKM_COUNT_WORDS; i++) h_counts[i] = 0;
-    const u64 nk = read_len >= k ? (u64)(read_len - k + 1) : 0;
+    const u64 nk = dev_offsets ? windows : read_len >= k ? (u64)(read_len - k + 1) : 0;
     if (nreads == 0 || nk == 0) return GK_OK;
     if (!dev_out) return fail(ctx, GK_E_INVALID, "null record buffer");
     const u64 region_cap = out_cap_records / (u64)P;
@@ -255,15 +270,25 @@ int skm_route_launch(gk_ctx *ctx, hipStream_t st, unsigned long long *d_counts, 
     // the last counter word: [0] a region overflowed, [1] a record's length byte exceeded read_len (clamped).  Both travel back
     // with the counts, so whoever finishes the route — on any thread — needs no other stream and no shared flag word.
     u32 *d_overflow = reinterpret_cast<u32 *>(d_counts + 2 * MAX_PARTS);
-    if (skm_slot_bytes(k) == 16)
-        hipLaunchKernelGGL(k_skm_route<16>, dim3(grid), dim3(BLOCK), 0, st, rec, nreads, stride, k, P, WindowLimits{read_len, d_overflow + 1}, region_cap, d_counts,
-                           d_counts + MAX_PARTS, d_overflow, (uint8_t *)dev_out);
-    else
-        hipLaunchKernelGGL(k_skm_route<32>, dim3(grid), dim3(BLOCK), 0, st, rec, nreads, stride, k, P, WindowLimits{read_len, d_overflow + 1}, region_cap, d_counts,
-                           d_counts + MAX_PARTS, d_overflow, (uint8_t *)dev_out);
+    // (offset framing: the host has walked it, every length byte is what the offsets say — the bound is the format's own 255)
+    const WindowLimits lim{dev_offsets ? 255 : read_len, d_overflow + 1};
+#define GK_SKM_GO(SLOT, OFFS) hipLaunchKernelGGL((k_skm_route<SLOT, OFFS>), dim3(grid), dim3(BLOCK), 0, st, rec, dev_offsets, nreads, stride, k, P, lim, \
+                                                 region_cap, d_counts, d_counts + MAX_PARTS, d_overflow, (uint8_t *)dev_out)
+    if (skm_slot_bytes(k) == 16) { if (dev_offsets) GK_SKM_GO(16, true); else GK_SKM_GO(16, false); }
+    else { if (dev_offsets) GK_SKM_GO(32, true); else GK_SKM_GO(32, false); }
+#undef GK_SKM_GO
     GK_HIP(ctx, hipGetLastError());
     GK_HIP(ctx, hipMemcpyAsync(h_counts, d_counts, SKM_COUNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     return GK_OK;
+}
+int skm_route_launch(gk_ctx *ctx, hipStream_t st, unsigned long long *d_counts, unsigned long long *h_counts, int k, const void *dev_records,
+                     uint64_t nreads, int read_len, int P, void *dev_out, uint64_t out_cap_records) {
+    return skm_route_go(ctx, st, d_counts, h_counts, k, dev_records, nullptr, nreads, read_len, 0, P, dev_out, out_cap_records);
+}
+int skm_route_launch(gk_ctx *ctx, hipStream_t st, unsigned long long *d_counts, unsigned long long *h_counts, int k, const void *dev_records,
+                     const uint32_t *dev_offsets, uint64_t nreads, uint64_t windows, int P, void *dev_out, uint64_t out_cap_records) {
+    if (!dev_offsets && nreads) return fail(ctx, GK_E_INVALID, "null offset table");
+    return skm_route_go(ctx, st, d_counts, h_counts, k, dev_records, dev_offsets, nreads, 255, windows, P, dev_out, out_cap_records);
 }
 int skm_route_finish(gk_ctx *ctx, const unsigned long long *h, bool launched, int P, uint64_t out_cap_records, uint64_t *rec_counts_host,
                      uint64_t *kmer_counts_host) {

@@ -1394,6 +1394,73 @@ int gk_map_prefetch_reads(gk_map *m, const uint8_t *bin, size_t nbytes, uint64_t
     }
 }
 
+}  // extern "C"
+namespace gk {
+// The chunk of a host `.bin` stream that starts at (byte pos, record r): gk_map_count_reads' rules — bounded in bytes by the
+// staging area (max_stage) and in windows by what one insert of `m` takes; a long run of equal-length records becomes a chunk
+// of its own without an offset table.  walk = false lets a stream that looks like one sequencing run go unwalked (its length
+// bytes are then checked on the device: unverified).  *err: 1 = a record starts past the end, 2 = the stream ends inside one.
+BinChunk map_cut_chunk(gk_map *m, const uint8_t *bin, size_t nbytes, uint64_t nreads, size_t pos, uint64_t r, bool walk, int *err) {
+    gk_ctx *ctx = m->ctx;
+    BinChunk c;
+    c.begin = pos; c.r_begin = r;
+    if (r >= nreads) return c;
+    const size_t chunk_begin = pos;
+    u64 occ = 0;
+    // windows per chunk: what the table has room for on the direct path; one partitioned batch's key scratch otherwise
+    const u64 occ_limit = std::max<u64>(reads_per_launch(m, 1), use_partitioned(m, part_batch_keys(m)) ? part_batch_keys(m) : 0);
+    bool fast_prefix = false;
+    // Fast prefix: a run of equal-length records (one sequencing run) is recognised by comparing one byte per
+    // record, with no offset table built; it becomes a chunk of its own when it is long enough to be worth it.
+    if (pos < nbytes) {
+        const int len0 = bin[pos];
+        const size_t rb0 = 1 + (size_t)(len0 + 3) / 4;
+        const u64 nk0 = len0 >= m->k ? (u64)(len0 - m->k + 1) : 0;
+        u64 cap = std::min<u64>(nreads - r, (nbytes - pos) / rb0);
+        // (A short FIRST chunk — its upload cannot hide behind anything — was tried and lost: 128 MiB first, C3 from host memory
+        //  129 ms against 107-116 with equal chunks: one more batch, i.e. one more pass over the table, costs more than the
+        //  2 ms of exposed upload it saves; profiles/r03/c3_host_fed_variants.txt)
+        const size_t stage_cap = max_stage(ctx);
+        cap = std::min<u64>(cap, std::max<u64>(1, stage_cap / rb0));
+        if (nk0) cap = std::min<u64>(cap, std::max<u64>(1, occ_limit / nk0));
+        const uint8_t *p0 = bin + pos;
+        u64 run = 0;
+        // What is left is EXACTLY (reads left) records of this length: one sequencing run, almost surely.  Then the
+        // host does not walk a million length bytes (~1 ms per 39 MB: a third of the whole insert) — the L1 scatter
+        // checks them on the device as it goes, and gives the chunk back if one differs (PART_NOT_UNIFORM).
+        const bool looks_uniform = !walk && !ctx->hook_host_ragged && !ctx->hook_part_exact && nk0 && (nbytes - pos) == (size_t)(nreads - r) * rb0 &&
+                                   cap >= 4096 && use_partitioned(m, cap * nk0) && nk0 * (u64)m->W <= (u64)5632;
+        if (looks_uniform) { run = cap; c.unverified = true; }
+        while (run < cap && p0[run * rb0] == (uint8_t)len0) run++;
+        if (run >= 4096 || (run == nreads - r && run > 0)) {
+            fast_prefix = true;
+            c.first_len = len0;
+            pos += run * rb0;
+            occ = run * nk0;
+            r += run;
+        } else c.unverified = false;
+    }
+    while (!fast_prefix && r < nreads) {
+        if (pos >= nbytes) { *err = 1; return c; }
+        int len = bin[pos];
+        if (c.first_len < 0) c.first_len = len; else if (len != c.first_len) c.uniform = false;
+        size_t rb = 1 + (size_t)(len + 3) / 4;
+        if (pos + rb > nbytes) { *err = 2; return c; }
+        u64 nk = len >= m->k ? (u64)(len - m->k + 1) : 0;
+        if (r > c.r_begin && (pos + rb - chunk_begin > max_stage(ctx) || occ + nk > occ_limit)) break;
+        c.offs.push_back((u32)(pos - chunk_begin));
+        pos += rb;
+        occ += nk;
+        r++;
+    }
+    if (!c.offs.empty()) c.offs.push_back((u32)(pos - chunk_begin));
+    c.bytes = pos - chunk_begin; c.reads = r - c.r_begin; c.occ = occ;
+    c.valid = c.reads > 0;
+    return c;
+}
+}  // namespace gk
+extern "C" {
+
 int gk_map_count_reads(gk_map *m, const uint8_t *bin, size_t nbytes, uint64_t nreads, uint64_t *occurrences) {
     if (int rc = check_map_lazy(m)) return rc;
     gk_ctx *ctx = m->ctx;
@@ -1404,71 +1471,8 @@ int gk_map_count_reads(gk_map *m, const uint8_t *bin, size_t nbytes, uint64_t nr
     if (int rc = reset_occ_counter(m)) return rc;
     // Walk the record framing once on the host (one length byte per record, PairedEndData.scala:24-31),
     // cutting the stream into launches bounded in bytes (staging area) and in windows (load limit, key scratch).
-    struct Chunk {
-        size_t begin = 0, bytes = 0;
-        u64 r_begin = 0, reads = 0, occ = 0;
-        int first_len = -1;
-        bool uniform = true, unverified = false, valid = false;
-        std::vector<u32> offs;
-    };
-    // the chunk that starts at (pos, r); GK_E_FORMAT through *err
-    auto cut = [&](size_t pos, u64 r, bool walk, int *err) {
-        Chunk c;
-        c.begin = pos; c.r_begin = r;
-        if (r >= nreads) return c;
-        const size_t chunk_begin = pos;
-        u64 occ = 0;
-        // windows per chunk: what the table has room for on the direct path; one partitioned batch's key scratch otherwise
-        const u64 occ_limit = std::max<u64>(reads_per_launch(m, 1), use_partitioned(m, part_batch_keys(m)) ? part_batch_keys(m) : 0);
-        bool fast_prefix = false;
-        // Fast prefix: a run of equal-length records (one sequencing run) is recognised by comparing one byte per
-        // record, with no offset table built; it becomes a chunk of its own when it is long enough to be worth it.
-        if (pos < nbytes) {
-            const int len0 = bin[pos];
-            const size_t rb0 = 1 + (size_t)(len0 + 3) / 4;
-            const u64 nk0 = len0 >= m->k ? (u64)(len0 - m->k + 1) : 0;
-            u64 cap = std::min<u64>(nreads - r, (nbytes - pos) / rb0);
-            // (A short FIRST chunk — its upload cannot hide behind anything — was tried and lost: 128 MiB first, C3 from host memory
-            //  129 ms against 107-116 with equal chunks: one more batch, i.e. one more pass over the table, costs more than the
-            //  2 ms of exposed upload it saves; profiles/r03/c3_host_fed_variants.txt)
-            const size_t stage_cap = max_stage(ctx);
-            cap = std::min<u64>(cap, std::max<u64>(1, stage_cap / rb0));
-            if (nk0) cap = std::min<u64>(cap, std::max<u64>(1, occ_limit / nk0));
-            const uint8_t *p0 = bin + pos;
-            u64 run = 0;
-            // What is left is EXACTLY (reads left) records of this length: one sequencing run, almost surely.  Then the
-            // host does not walk a million length bytes (~1 ms per 39 MB: a third of the whole insert) — the L1 scatter
-            // checks them on the device as it goes, and gives the chunk back if one differs (PART_NOT_UNIFORM).
-            const bool looks_uniform = !walk && !ctx->hook_host_ragged && !ctx->hook_part_exact && nk0 && (nbytes - pos) == (size_t)(nreads - r) * rb0 &&
-                                       cap >= 4096 && use_partitioned(m, cap * nk0) && nk0 * (u64)m->W <= (u64)5632;
-            if (looks_uniform) { run = cap; c.unverified = true; }
-            while (run < cap && p0[run * rb0] == (uint8_t)len0) run++;
-            if (run >= 4096 || (run == nreads - r && run > 0)) {
-                fast_prefix = true;
-                c.first_len = len0;
-                pos += run * rb0;
-                occ = run * nk0;
-                r += run;
-            } else c.unverified = false;
-        }
-        while (!fast_prefix && r < nreads) {
-            if (pos >= nbytes) { *err = 1; return c; }
-            int len = bin[pos];
-            if (c.first_len < 0) c.first_len = len; else if (len != c.first_len) c.uniform = false;
-            size_t rb = 1 + (size_t)(len + 3) / 4;
-            if (pos + rb > nbytes) { *err = 2; return c; }
-            u64 nk = len >= m->k ? (u64)(len - m->k + 1) : 0;
-            if (r > c.r_begin && (pos + rb - chunk_begin > max_stage(ctx) || occ + nk > occ_limit)) break;
-            c.offs.push_back((u32)(pos - chunk_begin));
-            pos += rb;
-            occ += nk;
-            r++;
-        }
-        if (!c.offs.empty()) c.offs.push_back((u32)(pos - chunk_begin));
-        c.bytes = pos - chunk_begin; c.reads = r - c.r_begin; c.occ = occ;
-        c.valid = c.reads > 0;
-        return c;
-    };
+    using Chunk = BinChunk;
+    auto cut = [&](size_t pos, u64 r, bool walk, int *err) { return map_cut_chunk(m, bin, nbytes, nreads, pos, r, walk, err); };
     auto format_error = [&](int err, const Chunk &c) {
         return fail(ctx, GK_E_FORMAT, err == 1 ? "truncated .bin stream: record " + std::to_string(c.r_begin + c.reads) + " starts past the end"
                                                 : "truncated .bin stream inside record " + std::to_string(c.r_begin + c.reads));

@@ -102,6 +102,17 @@ class DistDNAMap:
         L.check(L.lib().gk_dist_count_reads_dev(self.dist.h, self.local.h, d_records, nreads, read_len, C.byref(sent), C.byref(owned)), self.ctx.h)
         return sent.value, owned.value
 
+    def count_reads(self, bin_bytes, nreads: int):
+        """FreqFilter.add over this rank's share of the reads as a host `.bin` stream (ragged mates allowed; any length, 0 included)
+        -> (windows sent, windows this rank counted as owner).  COLLECTIVE: a malformed stream on any rank raises GK_E_FORMAT on
+        every rank with every local map unchanged; a failure after streaming began raises on every rank and leaves the local map
+        with an unspecified part of the counts (clear it)."""
+        buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)
+        sent, owned = C.c_uint64(), C.c_uint64()
+        L.check(L.lib().gk_dist_count_reads(self.dist.h, self.local.h, L.ptr(buf, C.c_uint8) if buf.size else None, buf.size, nreads,
+                                            C.byref(sent), C.byref(owned)), self.ctx.h)
+        return sent.value, owned.value
+
     def route_begin(self, d_records: int, nreads: int, read_len: int):
         """First half of count_reads_dev, asynchronous: route the batch on the second stream.  Call it for batch i+1 before
         count_routed() of batch i and the routing kernel hides behind the owner pipeline; with batch i+2 begun as well (three

@@ -96,6 +96,26 @@ struct PairedEndData {
     std::vector<uint8_t> bin;
 };
 
+// Sharing the pairs out over N ranks: rank `rank` of `world` takes the pairs [n * rank / world, n * (rank + 1) / world) of the
+// first n = min(takeFirst, count) — the same range for the count and for the walks.
+inline std::pair<uint64_t, uint64_t> pairShare(uint64_t count, uint64_t takeFirst, int rank, int world) {
+    if (world < 1 || rank < 0 || rank >= world) throw GkError(GK_E_INVALID, "pairShare: need 0 <= rank < world");
+    const unsigned __int128 n = std::min(count, takeFirst);
+    return {(uint64_t)(n * (unsigned)rank / (unsigned)world), (uint64_t)(n * (unsigned)(rank + 1) / (unsigned)world)};
+}
+// byte range [first, end) of pairs [firstPair, endPair) of a `.bin` stream of mate records (two per pair), by walking its framing
+inline std::pair<size_t, size_t> pairBytes(const PairedEndData &data, uint64_t firstPair, uint64_t endPair) {
+    if (firstPair > endPair) throw GkError(GK_E_INVALID, "pairBytes: firstPair > endPair");
+    size_t pos = 0, first = 0;
+    for (uint64_t rec = 0; rec < 2 * endPair; rec++) {
+        if (rec == 2 * firstPair) first = pos;
+        if (pos >= data.bin.size()) throw GkError(GK_E_FORMAT, "the stream ends before pair " + std::to_string(rec / 2));
+        pos += 1 + ((size_t)data.bin[pos] + 3) / 4;
+        if (pos > data.bin.size()) throw GkError(GK_E_FORMAT, "the stream ends inside pair " + std::to_string(rec / 2));
+    }
+    return {firstPair == endPair ? pos : first, pos};
+}
+
 // the two closures the hot path passes to DNAMap
 struct PlusOne {};                 // `_ + 1`            FreqFilter.scala:33
 struct ValueLessThan { int rounds; };   // `(k, v) => v < rounds`   FreqFilter.scala:55
@@ -176,6 +196,8 @@ class DNAMap {
 // with PartitionedDNAMap::uniqueId() and hands it to the others through whatever channel the host program has.
 // Every member that moves data is COLLECTIVE.  Owner of a k-mer = strand-symmetric minimizer hash mod world (gk_owner_of),
 // not `hashCode mod P` (:60-63): the partition function is unobservable in results and keeps x and rc(x) together.
+class Graph;
+class Support;
 class PartitionedDNAMap {
   public:
     static std::vector<uint8_t> uniqueId() {
@@ -199,6 +221,14 @@ class PartitionedDNAMap {
     std::pair<uint64_t, uint64_t> countReadsDev(const void *devRecords, uint64_t nreads, int readLen) {
         uint64_t sent = 0, owned = 0;
         check(gk_dist_count_reads_dev(d_, local_.handle(), devRecords, nreads, readLen, &sent, &owned), ctx_.handle());
+        return {sent, owned};
+    }
+    // FreqFilter.add over pairs [firstPair, endPair) of a host `.bin` stream (ragged mates allowed): chunked, uploaded and routed
+    // inside the library (gk_dist_count_reads).  A malformed stream on any rank throws GK_E_FORMAT on every rank, nothing counted.
+    std::pair<uint64_t, uint64_t> countReads(const PairedEndData &data, uint64_t firstPair, uint64_t endPair) {
+        const auto [b0, b1] = pairBytes(data, firstPair, endPair);
+        uint64_t sent = 0, owned = 0;
+        check(gk_dist_count_reads(d_, local_.handle(), data.bin.data() + b0, b1 - b0, 2 * (endPair - firstPair), &sent, &owned), ctx_.handle());
         return {sent, owned};
     }
     // the same in two halves for a streaming loop: routeBegin(batch i+1), and routeBegin(batch i+2) for the exchange to run
@@ -225,6 +255,8 @@ class PartitionedDNAMap {
         return DNAMap(ctx_, local_.k(), full);
     }
     void barrier() { check(gk_dist_barrier(d_), ctx_.handle()); }
+    // every rank's support (its share of the pairs walked on its replica) becomes the sum over all ranks (gk_dist_reduce_support)
+    void reduceSupport(Graph &graph, Support &support);
 
   private:
     Context &ctx_;
@@ -254,6 +286,15 @@ inline DNAMap extractFilteredKmers(Context &ctx, const PairedEndData &data, int 
     }
     kmersFreq.deleteAll(ValueLessThan{rounds});
     return kmersFreq;
+}
+// the same over N ranks: this rank counts its share of the first min(takeFirst, count) pairs (pairShare) into its partition and
+// filters it; every partition then holds its owned k-mers seen at least `rounds` times -> (windows sent, windows counted as owner)
+inline std::pair<uint64_t, uint64_t> extractFilteredKmers(PartitionedDNAMap &kmersFreq, const PairedEndData &data, int rounds,
+                                                          uint64_t takeFirst = UINT64_MAX) {
+    const auto [a, b] = pairShare(data.count, takeFirst, kmersFreq.rank(), kmersFreq.world());
+    const auto occ = kmersFreq.countReads(data, a, b);
+    kmersFreq.deleteAll(ValueLessThan{rounds});
+    return occ;
 }
 }  // namespace FreqFilter
 
@@ -358,6 +399,14 @@ class Graph {
         check(gk_graph_walk_pairs(h_, positions.handle(), support.handle(), data.bin.data(), data.bin.size(), std::min<uint64_t>(data.count, takeFirst),
                                   rangeLo, rangeHi), ctx_.handle());
     }
+    // the same over pairs [firstPair, endPair) only (one rank's share)
+    void walkPairs(PositionMap &positions, Support &support, const PairedEndData &data, uint64_t firstPair, uint64_t endPair, int rangeLo, int rangeHi) {
+        if (endPair <= firstPair) return;
+        const auto [b0, b1] = pairBytes(data, firstPair, endPair);
+        check(gk_graph_walk_pairs(h_, positions.handle(), support.handle(), data.bin.data() + b0, b1 - b0, endPair - firstPair, rangeLo, rangeHi),
+              ctx_.handle());
+    }
+    gk_graph *handle() const { return h_; }
     // :272-316 -> (edges removed, nodes added); simplifyGraph() is the next call (:318)
     std::pair<uint64_t, uint64_t> splitBySupport(const Support &support, int cutoff) {
         uint64_t rm = 0, nn = 0;
@@ -425,5 +474,9 @@ class Graph {
     int k_;
     gk_graph *h_ = nullptr;
 };
+
+inline void PartitionedDNAMap::reduceSupport(Graph &graph, Support &support) {
+    check(gk_dist_reduce_support(d_, graph.handle(), support.handle()), ctx_.handle());
+}
 
 }  // namespace genome

@@ -10,21 +10,57 @@
 //   map, the pairs' walks with range LO to HI (the reference: 180 to 250, :146), node split at genome.cutoff = CUTOFF,
 //   removeEdge, simplifyGraph; its counters join the JSON;
 //   --out writes <prefix>.nodes.txt, .edges.txt, .contigs (GraphSimplifier.scala:338-347) and .dot (Graph.scala:74-88)
+//   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Rank 0 writes the
+//   communicator id to PATH (a file that must not exist yet: written aside, then renamed), the others wait for it (2 minutes at
+//   most).  Each rank counts its contiguous share of the pairs into its partition (gk_dist_count_reads), the partitions are
+//   filtered and gathered into a replica of the graph on every rank, and with --walk-pairs each rank walks its share of the
+//   pairs and the supports are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus occurrences_sent,
+//   occurrences_owned — rank 0's — and world) and writes --out.  (RCCL may print a banner line to stdout before the JSON line.)
 //
 // Build: g++ -std=c++17 -O2 -I include genome_amd/host/graph_builder.cpp -L genome_amd -lgenome_amd
 //        -Wl,-rpath,'$ORIGIN/..' -o genome_amd/host/graph_builder
+#include <unistd.h>
+
+#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <iostream>
 #include <iterator>
+#include <memory>
+#include <thread>
 
 #include "genome.hpp"
+
+// the communicator id through a file: rank 0 writes it aside and renames it into place, the others wait for it
+static std::vector<uint8_t> shareId(int rank, const std::string &path) {
+    if (rank == 0) {
+        std::vector<uint8_t> id = genome::PartitionedDNAMap::uniqueId();
+        const std::string tmp = path + ".tmp" + std::to_string(getpid());
+        {
+            std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
+            f.write((const char *)id.data(), (std::streamsize)id.size());
+            if (!f) throw std::runtime_error("cannot write " + tmp);
+        }
+        if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + path);
+        return id;
+    }
+    const auto until = std::chrono::steady_clock::now() + std::chrono::seconds(120);
+    for (;;) {
+        std::ifstream f(path, std::ios::binary);
+        if (f) {
+            std::vector<uint8_t> id((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+            if (id.size() == 128) return id;
+        }
+        if (std::chrono::steady_clock::now() > until) throw std::runtime_error("no communicator id in " + path + " after 120 s");
+        std::this_thread::sleep_for(std::chrono::milliseconds(20));
+    }
+}
 
 int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--walk-pairs CUTOFF LO HI] [--out prefix]\n", argv[0]);
+                             "[--walk-pairs CUTOFF LO HI] [--out prefix] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string infile = argv[1];
@@ -36,7 +72,8 @@ int main(int argc, char **argv) {
     uint64_t prefilter = 0;                       // expected distinct k-mers; 0 = no singleton pre-filter
     bool retain = true, simplify = false;
     int walkCutoff = -1, walkLo = 180, walkHi = 250;
-    std::string out;
+    std::string out, idFile;
+    int world = 0, rank = 0;                      // world 0: one GPU, no communicator
     for (int i = 4; i < argc; i++) {
         if (!std::strcmp(argv[i], "--rounds") && i + 1 < argc) rounds = std::stoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--take-first") && i + 1 < argc) takeFirst = std::stoull(argv[++i]);
@@ -45,16 +82,43 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--simplify")) simplify = true;
         else if (!std::strcmp(argv[i], "--walk-pairs") && i + 3 < argc) { walkCutoff = std::stoi(argv[++i]); walkLo = std::stoi(argv[++i]); walkHi = std::stoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
+        else if (!std::strcmp(argv[i], "--world") && i + 1 < argc) world = std::stoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) rank = std::stoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--id-file") && i + 1 < argc) idFile = argv[++i];
         else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+    }
+    if (world && (world < 1 || rank < 0 || rank >= world || idFile.empty())) {
+        std::fprintf(stderr, "--world W needs --rank R (0 <= R < W) and --id-file PATH\n");
+        return 2;
+    }
+    if (world && prefilter) {
+        std::fprintf(stderr, "--prefilter runs on one GPU only (not with --world)\n");
+        return 2;
     }
     try {
         std::ifstream f(infile, std::ios::binary);
         if (!f) throw std::runtime_error("cannot open " + infile);
         data.bin.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-        genome::Context ctx(0);
-        auto kmersFreq = genome::FreqFilter::extractFilteredKmers(ctx, data, k, rounds, takeFirst, 0, prefilter);      // :32
-        const uint64_t good = kmersFreq.size();                                                          // :34
-        auto graph = genome::Graph::buildGraph(k, kmersFreq);                                            // :36
+        int device = 0;
+        if (world) {
+            const int ndev = gk_device_count();
+            if (ndev < 1) throw genome::GkError(GK_E_NODEVICE, "no GPU");
+            device = rank % ndev;
+        }
+        genome::Context ctx(device);
+        std::unique_ptr<genome::PartitionedDNAMap> pm;
+        uint64_t sent = 0, owned = 0, good = 0;
+        std::unique_ptr<genome::DNAMap> kmersFreq;
+        if (world) {
+            pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, idFile));
+            std::tie(sent, owned) = genome::FreqFilter::extractFilteredKmers(*pm, data, rounds, takeFirst);           // :32 over N ranks
+            good = pm->size();                                                                                          // :34
+            kmersFreq = std::make_unique<genome::DNAMap>(pm->gathered(true));
+        } else {
+            kmersFreq = std::make_unique<genome::DNAMap>(genome::FreqFilter::extractFilteredKmers(ctx, data, k, rounds, takeFirst, 0, prefilter));   // :32
+            good = kmersFreq->size();                                                                                  // :34
+        }
+        auto graph = genome::Graph::buildGraph(k, *kmersFreq);                                           // :36
         auto [nodes, edges, totalLen] = graph.counts();                                                  // :39
         // :41-47 the two component histograms, on the graph as built (the reference computes them before retain)
         auto [hist, hist2] = graph.componentHistograms();
@@ -66,12 +130,20 @@ int main(int argc, char **argv) {
         if (walkCutoff >= 0) {
             auto graphMap = graph.getGraphMap();                                                         // GraphSimplifier.scala:188
             genome::Support support(ctx);
-            graph.walkPairs(graphMap, support, data, takeFirst, walkLo, walkHi);                         // :213-263
+            if (world) {                                                                                 // this rank's pairs, then the sum over the ranks
+                const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
+                graph.walkPairs(graphMap, support, data, a, b, walkLo, walkHi);
+                pm->reduceSupport(graph, support);                                                       // (before any node split)
+            } else {
+                graph.walkPairs(graphMap, support, data, takeFirst, walkLo, walkHi);                     // :213-263
+            }
             std::tie(supPairs, badPairs, walked) = support.sizes();                                      // :266 "Bad pairs"
             std::tie(removedEdges, newNodes) = graph.splitBySupport(support, walkCutoff);                // :272-316
             graph.simplifyGraph();                                                                       // :318
         }
         auto [n2, e2, l2] = graph.counts();
+        if (pm) pm->barrier();
+        if (rank != 0) return 0;
         std::printf("{\"k\":%d,\"rounds\":%d,\"good_kmers\":%llu,\"graph_nodes\":%llu,\"graph_edges\":%llu,"
                     "\"total_edges_length\":%llu,\"components\":%llu,\"max_component_size\":%llu,"
                     "\"retained_nodes\":%llu,\"retained_edges\":%llu,\"retained_edges_length\":%llu,",
@@ -89,7 +161,8 @@ int main(int argc, char **argv) {
             std::printf("]%s", tail);
         };
         dump("components_histogram", hist, ",");          // GraphBuilder.scala:42 "Components histogram"
-        dump("components_histogram_2", hist2, "}\n");     // :47 "Components histogram 2"
+        dump("components_histogram_2", hist2, world ? "," : "}\n");     // :47 "Components histogram 2"
+        if (world) std::printf("\"occurrences_sent\":%llu,\"occurrences_owned\":%llu,\"world\":%d}\n", (unsigned long long)sent, (unsigned long long)owned, world);
         if (!out.empty()) {                                                                              // :56 (Kryo file there)
             std::ofstream nf(out + ".nodes.txt"), ef(out + ".edges.txt");
             for (const auto &n : graph.getNodes()) nf << n.toString() << "\n";

@@ -269,6 +269,20 @@ int gk_dist_allreduce_f64(gk_dist *d, double *values, int n, int op_max);
  * *occurrences_sent = windows of this rank's reads, *occurrences_owned = windows this rank counted (sums over ranks agree). */
 int gk_dist_count_reads_dev(gk_dist *d, gk_map *local, const void *dev_records, uint64_t nreads, int read_len,
                             uint64_t *occurrences_sent, uint64_t *occurrences_owned);
+/* FreqFilter.add over THIS rank's share of the reads as a HOST `.bin` stream ([len:u8][ceil(len/4) bytes] per record, lengths
+ * 0..255 and ragged — what Convert2bin writes), every k-mer counted by its owner rank.  Ranks may pass streams of any length,
+ * nreads == 0 included.  The stream is cut into chunks by gk_map_count_reads' rules (bounded staging; a run of equal-length
+ * records takes the fixed-stride route, a ragged chunk an offset-framed one) and streamed through route_begin / count_routed
+ * three batches deep, with the upload of the next chunks on the context's second stream.  Every rank walks its whole stream's
+ * framing before anything is exchanged: a truncated or malformed stream on ANY rank returns GK_E_FORMAT on EVERY rank, nothing
+ * moves and every `local` is unchanged.  A rank with fewer chunks routes empty batches, so that every rank issues the same
+ * operations.  A failure after streaming began (an exchange dropped, a HIP error on one rank) returns an error on every rank and
+ * leaves nobody waiting; `local` then holds an UNSPECIFIED subset of the counts and must be cleared (gk_map_clear) before
+ * reuse.  Needs no routes begun with gk_dist_route_begin outstanding (GK_E_STATE on this rank, GK_E_COMM on the others).  The
+ * staging areas (one per batch in flight) stay on the handle until gk_dist_destroy and count in gk_ctx_mem_stats.
+ * *occurrences_sent = windows of this rank's stream, *occurrences_owned = windows this rank counted (sums over ranks agree). */
+int gk_dist_count_reads(gk_dist *d, gk_map *local, const uint8_t *bin_host, size_t nbytes, uint64_t nreads,
+                        uint64_t *occurrences_sent, uint64_t *occurrences_owned);
 /* The same in two halves, for a streaming loop: gk_dist_route_begin launches the routing of a batch on the context's second
  * stream and returns at once; gk_dist_count_routed waits for it, exchanges and counts.  Calling route_begin for batch i+1
  * BEFORE count_routed for batch i overlaps the routing kernel with the owner pipeline; with route_begin for batch i+2 before
