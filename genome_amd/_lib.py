@@ -156,6 +156,10 @@ SIGNATURES = {
     "gk_graph_export_nodes": (C.c_int, [vp, u64p, u64p, C.c_uint64, u64p]),
     "gk_graph_export_edges": (C.c_int, [vp, u64p, u64p, u64p, u64p, i64p, i64p, C.c_uint64, u64p, u8p, C.c_uint64, u64p]),
     "gk_graph_out_order": (C.c_int, [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gk_graph_save": (C.c_int, [vp, C.c_char_p]),
+    "gk_graph_load": (C.c_int, [vp, C.c_char_p, C.POINTER(vp)]),
+    "gk_graph_k": (C.c_int, [vp]),
+    "gk_graph_io_stats": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "gk_synth_reads_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
     "gk_prefilter_create": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp)]),
     "gk_prefilter_destroy": (None, [vp]),

@@ -1590,7 +1590,7 @@ static void graph_free_arrays(gk_graph *g) {
     v = GraphView{};
 }
 
-static int graph_alloc_nodes(gk_graph *g, u64 n) {
+int graph_alloc_nodes(gk_graph *g, u64 n) {
     gk_ctx *ctx = g->ctx;
     GraphView &v = g->v;
     const u64 c = std::max<u64>(n, 1);
@@ -1604,7 +1604,7 @@ static int graph_alloc_nodes(gk_graph *g, u64 n) {
     g->node_cap = c;
     return GK_OK;
 }
-static int graph_alloc_edges(gk_graph *g, u64 n) {
+int graph_alloc_edges(gk_graph *g, u64 n) {
     gk_ctx *ctx = g->ctx;
     GraphView &v = g->v;
     const u64 c = std::max<u64>(n, 1);

@@ -76,6 +76,7 @@ struct gk_ctx {
     double ref_copy_tbps = 5.9, ref_cas_gps = 26.7;        // (measured by these kernels in run 6 of round 3: 5.91 TB/s, 26.66 G/s)
     std::string err;
     int hook_dist_fail_reduce = 0;   // test hook: this context's next gk_dist_reduce_support fails its owner merge, after the records have been exchanged
+    float graph_io_ms[4] = {0, 0, 0, 0};   // the last gk_graph_save / gk_graph_load on this context: file I/O, copies, kernels, whole call
 };
 
 namespace gk {

@@ -13,7 +13,9 @@ count and for the walks alike:
      (gk_dist_reduce_support, which refuses replicas with split nodes: it comes before splitBySupport), splitBySupport,
      simplifyGraph.
 
-Every step that moves data is collective: all ranks must call build_graph with the same arguments."""
+simplify_graph is GraphSimplifier's own stage from a graph file (gk_graph_save / gk_graph_load): every rank loads the same file
+and runs step 5.  Every step that moves data is collective: all ranks must call build_graph (or simplify_graph) with the same
+arguments."""
 from __future__ import annotations
 
 import numpy as np
@@ -21,7 +23,7 @@ import numpy as np
 from . import dna
 from .dist import DistDNAMap, HipDist
 from .freqfilter import PairedEndData
-from .graph import HipGraph, Support, buildGraph
+from .graph import HipGraph, Support, buildGraph, loadGraph
 
 
 def pair_share(npairs: int, world: int, rank: int, take_first: int | None = None) -> tuple[int, int]:
@@ -33,14 +35,39 @@ def pair_share(npairs: int, world: int, rank: int, take_first: int | None = None
     return n * rank // world, n * (rank + 1) // world
 
 
+def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs) -> dict:
+    """GraphSimplifier.scala:188-318 on this rank's replica `g`: getGraphMap, walkPairs over the rank's `npairs` pairs in `share`,
+    the supports summed over the ranks (before any node split), splitBySupport at the cutoff, simplifyGraph -> the walk_pairs
+    counters."""
+    cutoff, lo, hi = walk_pairs
+    vm = g.getGraphMap()                                                    # :188
+    sup = Support(hd.ctx)
+    try:
+        if npairs > 0:
+            g.walkPairs(vm, sup, share, npairs, lo, hi)                     # :213-263, this rank's pairs
+        hd.reduce_support(g, sup)                                           # every rank's walks summed, before any split
+        sup_pairs, bad, walked = sup.sizes()                                # :266
+        removed, new_nodes = g.splitBySupport(sup, cutoff)                  # :272-316
+        g.simplifyGraph()                                                   # :318
+    finally:
+        sup.close()
+        vm.close()
+    return {"supported_edge_pairs": sup_pairs, "bad_pairs": bad, "orientations_walked": walked, "removed_edges": removed,
+            "new_nodes": new_nodes}
+
+
+def _rank_share(hd: HipDist, data: PairedEndData, take_first: int | None):
+    a, b = pair_share(data.count, hd.world, hd.rank, take_first)
+    off = dna.bin_pair_offsets(data.bin, b)
+    return a, b, np.frombuffer(data.bin, np.uint8)[int(off[a]):int(off[b])]
+
+
 def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds: int = 3, take_first: int | None = None, retain: bool = True,
                 simplify: bool = False, walk_pairs=None, classified: bool = True) -> tuple[HipGraph, dict]:
     """One rank's part of the N-rank GraphBuilder (+ GraphSimplifier pairs stage) -> (this rank's graph replica, stats).
     `stats` holds graph_builder's JSON keys (the walk_pairs object only with walk_pairs) plus occurrences_sent,
     occurrences_owned (this rank's windows) and world.  The caller closes the graph."""
-    a, b = pair_share(data.count, hd.world, hd.rank, take_first)
-    off = dna.bin_pair_offsets(data.bin, b)
-    share = np.frombuffer(data.bin, np.uint8)[int(off[a]):int(off[b])]
+    a, b, share = _rank_share(hd, data, take_first)
     pm = DistDNAMap(hd, k)
     try:
         sent, owned = pm.count_reads(share, 2 * (b - a))                   # FreqFilter.scala:44-48
@@ -64,21 +91,7 @@ def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds: int = 3, take_
             g.simplifyGraph()
         walk = None
         if walk_pairs is not None:
-            cutoff, lo, hi = walk_pairs
-            vm = g.getGraphMap()                                            # :188
-            sup = Support(hd.ctx)
-            try:
-                if b > a:
-                    g.walkPairs(vm, sup, share, b - a, lo, hi)              # :213-263, this rank's pairs
-                hd.reduce_support(g, sup)                                   # every rank's walks summed, before any split
-                sup_pairs, bad, walked = sup.sizes()                        # :266
-                removed, new_nodes = g.splitBySupport(sup, cutoff)          # :272-316
-                g.simplifyGraph()                                           # :318
-            finally:
-                sup.close()
-                vm.close()
-            walk = {"supported_edge_pairs": sup_pairs, "bad_pairs": bad, "orientations_walked": walked, "removed_edges": removed,
-                    "new_nodes": new_nodes}
+            walk = _pairs_stage(hd, g, share, b - a, walk_pairs)
         n2, e2, l2 = g.counts()
     except BaseException:
         g.close()
@@ -90,4 +103,29 @@ def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds: int = 3, take_
     stats["components_histogram"] = [list(x) for x in hist]
     stats["components_histogram_2"] = [list(x) for x in hist2]
     stats.update({"occurrences_sent": sent, "occurrences_owned": owned, "world": hd.world})
+    return g, stats
+
+
+def simplify_graph(hd: HipDist, graph_path, data: PairedEndData, cutoff: int, lo: int = 180, hi: int = 250,
+                   take_first: int | None = None) -> tuple[HipGraph, dict]:
+    """One rank's part of GraphSimplifier.startup (S/scripts/GraphSimplifier.scala:152-318) over N ranks: every rank loads the
+    same graph file (:152-153, so the replicas are identical, ids included), then walks its own share of the pairs and the
+    supports are summed over the ranks before the split, as in build_graph's pairs stage.  The range defaults to the
+    reference's 180 to 250 (:146).  -> (this rank's graph, stats): k, the live counts before and after, the walk_pairs object,
+    components_histogram_2 and max_component_size of the final graph (:320-331), and world.  COLLECTIVE.  The caller closes
+    the graph."""
+    g = loadGraph(hd.ctx, graph_path)
+    try:
+        a, b, share = _rank_share(hd, data, take_first)
+        n1, e1, l1 = g.counts()
+        walk = _pairs_stage(hd, g, share, b - a, (cutoff, lo, hi))
+        n2, e2, l2 = g.counts()
+        sizes, _ = g.componentStats()
+        _, hist2 = g.componentHistograms()
+    except BaseException:
+        g.close()
+        raise
+    stats = {"k": g.k, "nodes": n1, "edges": e1, "edges_length": l1, "walk_pairs": walk, "simplified_nodes": n2, "simplified_edges": e2,
+             "simplified_edges_length": l2, "components_histogram_2": [list(x) for x in hist2],
+             "max_component_size": int(sizes.max()) if len(sizes) else 0, "world": hd.world}
     return g, stats

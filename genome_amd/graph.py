@@ -5,6 +5,7 @@ canonical serialisation used for parity.
 from __future__ import annotations
 
 import ctypes as C
+import os
 import sys
 
 import numpy as np
@@ -201,6 +202,13 @@ class HipGraph:
         L.check(L.lib().gk_graph_out_order(self.h, lo, hi, arr, C.byref(cnt)), self.ctx.h)
         return None if cnt.value < 0 else [arr[i] for i in range(cnt.value)]
 
+    # ---- the graph file (include/genome_amd.h, version 1) -------------------------------------------------------------
+    def save(self, path):
+        """MapGraph.write (Graph.scala:232-261): the live nodes and edges with their ids; written aside, then renamed onto path."""
+        if not self.h:
+            raise ValueError("graph is closed")
+        L.check(L.lib().gk_graph_save(self.h, os.fsencode(path)), self.ctx.h)
+
     def canonical(self):
         """(sorted node strings, edges (start, end, seq) sorted by (start k-mer, first base))."""
         k = self.k
@@ -233,6 +241,27 @@ def buildGraph(k: int, kmersFreq) -> HipGraph:
         if own is not None:
             own.close()
     return HipGraph(kmersFreq.ctx, k, h)
+
+
+def loadGraph(ctx, path) -> HipGraph:
+    """Graph(file) (Graph.scala:384-390) with GraphSimplifier's checks of the loaded graph (GraphSimplifier.scala:157-169): the
+    saved ids, out-edge orders and checksums; k comes from the file (:153).  GkError GK_E_FORMAT for a malformed or corrupt file."""
+    if not ctx.h:
+        raise ValueError("context is closed")
+    h = L.vp()
+    L.check(L.lib().gk_graph_load(ctx.h, os.fsencode(path), C.byref(h)), ctx.h)
+    k = L.lib().gk_graph_k(h)
+    if k < 0:
+        L.lib().gk_graph_destroy(h)
+        L.check(k, ctx.h)
+    return HipGraph(ctx, k, h)
+
+
+def graphIoStats(ctx) -> dict:
+    """wall ms of the last save / load on `ctx`: file I/O, waits for host<->device copies, device kernels, the whole call"""
+    arr = (C.c_float * 4)()
+    L.check(L.lib().gk_graph_io_stats(ctx.h, arr), ctx.h)
+    return dict(zip(("file_io", "copies", "kernels", "total"), (float(x) for x in arr)))
 
 
 class Support:

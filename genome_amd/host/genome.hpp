@@ -355,6 +355,17 @@ class Graph {
         check(gk_graph_build(kmersFreq.handle(), &g.h_), kmersFreq.context().handle());
         return g;
     }
+    // Graph(file) (Graph.scala:384-390) with GraphSimplifier's checks of the loaded graph (GraphSimplifier.scala:157-169); k comes
+    // from the file (:153).  A malformed or corrupt file throws GK_E_FORMAT.
+    static Graph load(Context &ctx, const std::string &path) {
+        Graph g(ctx, 0);
+        check(gk_graph_load(ctx.handle(), path.c_str(), &g.h_), ctx.handle());
+        g.k_ = gk_graph_k(g.h_);
+        return g;
+    }
+    // MapGraph.write (Graph.scala:232-261): the live nodes and edges with their ids, written aside and renamed onto path
+    void save(const std::string &path) const { check(gk_graph_save(h_, path.c_str()), ctx_.handle()); }
+    int k() const { return k_; }
     ~Graph() { gk_graph_destroy(h_); }
     Graph(Graph &&o) noexcept : ctx_(o.ctx_), k_(o.k_), h_(o.h_) { o.h_ = nullptr; }
     Graph(const Graph &) = delete;

@@ -4,12 +4,13 @@
 // The reference logs its counters through akka Logging (:34-53); here they are one JSON object.
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
-//                 [--walk-pairs CUTOFF LO HI] [--out prefix]
+//                 [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH]
 //   --simplify runs removeBubbles + simplifyGraph (GraphSimplifier.scala:317-318) before writing;
 //   --walk-pairs runs GraphSimplifier.startup's paired-end stage on the graph GraphBuilder hands over (:188-318): position
 //   map, the pairs' walks with range LO to HI (the reference: 180 to 250, :146), node split at genome.cutoff = CUTOFF,
 //   removeEdge, simplifyGraph; its counters join the JSON;
 //   --out writes <prefix>.nodes.txt, .edges.txt, .contigs (GraphSimplifier.scala:338-347) and .dot (Graph.scala:74-88)
+//   --save-graph writes the same graph as a graph file (gk_graph_save; GraphBuilder.scala:55-56) for graph_simplifier
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Rank 0 writes the
 //   communicator id to PATH (a file that must not exist yet: written aside, then renamed), the others wait for it (2 minutes at
 //   most).  Each rank counts its contiguous share of the pairs into its partition (gk_dist_count_reads), the partitions are
@@ -31,36 +32,12 @@
 #include <thread>
 
 #include "genome.hpp"
-
-// the communicator id through a file: rank 0 writes it aside and renames it into place, the others wait for it
-static std::vector<uint8_t> shareId(int rank, const std::string &path) {
-    if (rank == 0) {
-        std::vector<uint8_t> id = genome::PartitionedDNAMap::uniqueId();
-        const std::string tmp = path + ".tmp" + std::to_string(getpid());
-        {
-            std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
-            f.write((const char *)id.data(), (std::streamsize)id.size());
-            if (!f) throw std::runtime_error("cannot write " + tmp);
-        }
-        if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + path);
-        return id;
-    }
-    const auto until = std::chrono::steady_clock::now() + std::chrono::seconds(120);
-    for (;;) {
-        std::ifstream f(path, std::ios::binary);
-        if (f) {
-            std::vector<uint8_t> id((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-            if (id.size() == 128) return id;
-        }
-        if (std::chrono::steady_clock::now() > until) throw std::runtime_error("no communicator id in " + path + " after 120 s");
-        std::this_thread::sleep_for(std::chrono::milliseconds(20));
-    }
-}
+#include "rank_id.hpp"
 
 int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--walk-pairs CUTOFF LO HI] [--out prefix] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string infile = argv[1];
@@ -72,7 +49,7 @@ int main(int argc, char **argv) {
     uint64_t prefilter = 0;                       // expected distinct k-mers; 0 = no singleton pre-filter
     bool retain = true, simplify = false;
     int walkCutoff = -1, walkLo = 180, walkHi = 250;
-    std::string out, idFile;
+    std::string out, idFile, saveGraph;
     int world = 0, rank = 0;                      // world 0: one GPU, no communicator
     for (int i = 4; i < argc; i++) {
         if (!std::strcmp(argv[i], "--rounds") && i + 1 < argc) rounds = std::stoi(argv[++i]);
@@ -82,6 +59,7 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--simplify")) simplify = true;
         else if (!std::strcmp(argv[i], "--walk-pairs") && i + 3 < argc) { walkCutoff = std::stoi(argv[++i]); walkLo = std::stoi(argv[++i]); walkHi = std::stoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
+        else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
         else if (!std::strcmp(argv[i], "--world") && i + 1 < argc) world = std::stoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) rank = std::stoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--id-file") && i + 1 < argc) idFile = argv[++i];
@@ -163,7 +141,8 @@ int main(int argc, char **argv) {
         dump("components_histogram", hist, ",");          // GraphBuilder.scala:42 "Components histogram"
         dump("components_histogram_2", hist2, world ? "," : "}\n");     // :47 "Components histogram 2"
         if (world) std::printf("\"occurrences_sent\":%llu,\"occurrences_owned\":%llu,\"world\":%d}\n", (unsigned long long)sent, (unsigned long long)owned, world);
-        if (!out.empty()) {                                                                              // :56 (Kryo file there)
+        if (!saveGraph.empty()) graph.save(saveGraph);                                                   // :55-56 (a Kryo file there)
+        if (!out.empty()) {
             std::ofstream nf(out + ".nodes.txt"), ef(out + ".edges.txt");
             for (const auto &n : graph.getNodes()) nf << n.toString() << "\n";
             for (const auto &e : graph.getEdges()) ef << e.start.toString() << " " << e.end.toString() << " " << e.seq << "\n";

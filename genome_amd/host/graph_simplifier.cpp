@@ -1,0 +1,117 @@
+// graph_simplifier.cpp — C++ twin of GraphSimplifier.startup (S/scripts/GraphSimplifier.scala:140-352) over genome.hpp: loads
+// the graph file graph_builder --save-graph wrote (:152-153, with the checks of :157-169), walks the read pairs over it, splits
+// its nodes by the pairs' support and simplifies it.  The reference logs its counters (:266, :320-331); here they are one JSON
+// object.
+//
+//   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI] [--take-first N]
+//                    [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]
+//   k comes from the graph (:153); the range defaults to the reference's 180 to 250 (:146), the cutoff is genome.cutoff.
+//   The stage: getGraphMap (:188), walkPairs over the first N pairs (:213-263), splitBySupport (:272-316), simplifyGraph (:318).
+//   --out writes graph_builder's <prefix>.nodes.txt, .edges.txt, .contigs (:338-347) and .dot; --save-graph writes the final
+//   graph as a graph file (the reference's graphFile, :352).
+//   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
+//   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
+//   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
+//
+// Build: g++ -std=c++17 -O2 -I include genome_amd/host/graph_simplifier.cpp -L genome_amd -lgenome_amd
+//        -Wl,-rpath,'$ORIGIN/..' -o genome_amd/host/graph_simplifier
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <iterator>
+#include <memory>
+
+#include "genome.hpp"
+#include "rank_id.hpp"
+
+int main(int argc, char **argv) {
+    if (argc < 4) {
+        std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI] [--take-first N] [--out prefix] "
+                             "[--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
+        return 2;
+    }
+    const std::string graphFile = argv[1], infile = argv[2];
+    genome::PairedEndData data;
+    data.count = std::stoull(argv[3]);
+    int cutoff = -1, rangeLo = 180, rangeHi = 250;          // GraphSimplifier.scala:146
+    uint64_t takeFirst = UINT64_MAX;
+    std::string out, saveGraph, idFile;
+    int world = 0, rank = 0;
+    for (int i = 4; i < argc; i++) {
+        if (!std::strcmp(argv[i], "--cutoff") && i + 1 < argc) cutoff = std::stoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--range") && i + 2 < argc) { rangeLo = std::stoi(argv[++i]); rangeHi = std::stoi(argv[++i]); }
+        else if (!std::strcmp(argv[i], "--take-first") && i + 1 < argc) takeFirst = std::stoull(argv[++i]);
+        else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
+        else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
+        else if (!std::strcmp(argv[i], "--world") && i + 1 < argc) world = std::stoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) rank = std::stoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--id-file") && i + 1 < argc) idFile = argv[++i];
+        else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+    }
+    if (cutoff < 0) {
+        std::fprintf(stderr, "--cutoff C is required\n");
+        return 2;
+    }
+    if (world && (world < 1 || rank < 0 || rank >= world || idFile.empty())) {
+        std::fprintf(stderr, "--world W needs --rank R (0 <= R < W) and --id-file PATH\n");
+        return 2;
+    }
+    try {
+        std::ifstream f(infile, std::ios::binary);
+        if (!f) throw std::runtime_error("cannot open " + infile);
+        data.bin.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        int device = 0;
+        if (world) {
+            const int ndev = gk_device_count();
+            if (ndev < 1) throw genome::GkError(GK_E_NODEVICE, "no GPU");
+            device = rank % ndev;
+        }
+        genome::Context ctx(device);
+        auto graph = genome::Graph::load(ctx, graphFile);                                                // :152-153, :157-169
+        const int k = graph.k();
+        std::unique_ptr<genome::PartitionedDNAMap> pm;
+        if (world) pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, idFile));
+        auto [n1, e1, l1] = graph.counts();
+        auto graphMap = graph.getGraphMap();                                                             // :188
+        genome::Support support(ctx);
+        if (world) {                                                                                     // this rank's pairs, then the sum over the ranks
+            const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
+            graph.walkPairs(graphMap, support, data, a, b, rangeLo, rangeHi);
+            pm->reduceSupport(graph, support);                                                           // (before any node split)
+        } else {
+            graph.walkPairs(graphMap, support, data, takeFirst, rangeLo, rangeHi);                       // :213-263
+        }
+        auto [supPairs, badPairs, walked] = support.sizes();                                             // :266 "Bad pairs"
+        auto [removedEdges, newNodes] = graph.splitBySupport(support, cutoff);                           // :272-316
+        graph.simplifyGraph();                                                                           // :318
+        auto [n2, e2, l2] = graph.counts();
+        auto [hist, hist2] = graph.componentHistograms();                                                // :320-331
+        if (pm) pm->barrier();
+        if (rank != 0) return 0;
+        std::printf("{\"k\":%d,\"nodes\":%llu,\"edges\":%llu,\"edges_length\":%llu,"
+                    "\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},"
+                    "\"simplified_nodes\":%llu,\"simplified_edges\":%llu,\"simplified_edges_length\":%llu,\"components_histogram_2\":[",
+                    k, (unsigned long long)n1, (unsigned long long)e1, (unsigned long long)l1, (unsigned long long)supPairs,
+                    (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges, (unsigned long long)newNodes,
+                    (unsigned long long)n2, (unsigned long long)e2, (unsigned long long)l2);
+        bool first = true;
+        for (const auto &p : hist2) { std::printf("%s[%llu,%llu]", first ? "" : ",", (unsigned long long)p.first, (unsigned long long)p.second); first = false; }
+        std::printf("],\"max_component_size\":%llu", (unsigned long long)(hist.empty() ? 0 : hist.rbegin()->first));
+        if (world) std::printf(",\"world\":%d", world);
+        std::printf("}\n");
+        if (!saveGraph.empty()) graph.save(saveGraph);                                                   // :352 graphFile
+        if (!out.empty()) {
+            std::ofstream nf(out + ".nodes.txt"), ef(out + ".edges.txt");
+            for (const auto &n : graph.getNodes()) nf << n.toString() << "\n";
+            for (const auto &e : graph.getEdges()) ef << e.start.toString() << " " << e.end.toString() << " " << e.seq << "\n";
+            std::ofstream cf(out + ".contigs"), df(out + ".dot");
+            graph.writeContigs(cf);                                                                      // :338-347
+            graph.writeDot(df);
+        }
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "graph_simplifier: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}

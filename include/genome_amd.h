@@ -46,7 +46,7 @@ typedef enum {
     GK_E_CAPACITY = -4,       /* table could not grow / export buffer too small */
     GK_E_HIP = -5,            /* HIP runtime error (message has the hipError string) */
     GK_E_NODEVICE = -6,       /* no usable gfx950 device */
-    GK_E_FORMAT = -7,         /* malformed `.bin` read stream */
+    GK_E_FORMAT = -7,         /* malformed `.bin` read stream, or a malformed / corrupt graph file (gk_graph_load) */
     GK_E_STATE = -8,          /* operation not valid in the handle's current state */
     GK_E_COMM = -9            /* RCCL missing or a collective failed (message has the RCCL error string) */
 } gk_status;
@@ -390,6 +390,38 @@ int gk_graph_id_bounds(gk_graph *g, uint64_t *node_ids, uint64_t *edge_ids);
 int gk_graph_id_fingerprint(gk_graph *g, uint64_t *fp);
 /* MapGraph.removeEdge (:191-195) by edge id (each id once, as the reference's `toRemove` Set, GraphSimplifier.scala:270,316) */
 int gk_graph_remove_edges_by_id(gk_graph *g, const uint32_t *edge_ids, uint64_t n, uint64_t *removed);
+
+/* ---- the graph file: MapGraph.write (Graph.scala:232-261) / Graph(file) (:384-390) --------------------------------------
+ * The stage boundary between GraphBuilder (GraphBuilder.scala:55-56) and GraphSimplifier (GraphSimplifier.scala:152-153).
+ * This project's own format (the reference's is Kryo).  Version 1, every value little-endian.  Header, 128 bytes:
+ *     0  8  magic "GKGRAPH\0"             32  8  live nodes stored (Nn)          72  8  gk_graph_id_fingerprint
+ *     8  4  version = 1                   40  8  live edges stored (Ne)          80 48  zero
+ *    12  4  k (2..31 or 34..64)           48  8  pool bytes (P)
+ *    16  8  node id bound                 56 16  gk_graph_checksum (nodes, edges)
+ *    24  8  edge id bound (both bounds < 2^32-1: 0xffffffff stays "none")
+ * Then these arrays, each starting on an 8-byte boundary (zero padding after an odd count of u32):
+ *    node ids u32[Nn] (strictly ascending); node k-mers lo u64[Nn] and, for k >= 34 only, hi u64[Nn] (gk_graph_export_nodes'
+ *    encoding); node out-order u32[Nn] (count in bits 0..2, i-th base in bits 4+2i..5+2i); edge ids u32[Ne] (strictly
+ *    ascending); edge start node u32[Ne]; edge end node u32[Ne]; edge length u64[Ne]; the pool: for each edge in file order
+ *    ceil(len/4) bytes of 2-bit codes packed LSB-first (gk_graph_export_edges' packing), the unused high bits of an edge's last
+ *    byte zero.  The file ends where the pool ends.  An edge's first base is the first code of its sequence; in-degrees and the
+ *    out-edge table are not stored (the load rebuilds them from the edges).
+ * gk_graph_save writes the live nodes and edges only, in ascending id order (the pool compacted in that order): two saves of
+ * one graph give the same bytes, and so does a save of its load.  It writes path + ".tmp" and renames it onto path: a failed
+ * save leaves nothing at path.  A path that cannot be opened or written: GK_E_INVALID with the errno text.
+ * gk_graph_load gives a graph with the saved ids, id bounds, out-edge insertion orders, in-degrees, gk_graph_checksum and
+ * gk_graph_id_fingerprint (dead ids stay dead; gk_graph_build_stats reads zeros).  Its checks (after GraphSimplifier.scala:
+ * 157-169): ids ascending and in bounds; every edge's start and end live nodes, its length >= 1; one edge per (start node,
+ * first base); out-orders that list exactly the bases with an out-edge; pool size = sum of ceil(len/4) and zero padding bits;
+ * the last k bases of (start k-mer ++ sequence) = the end node's k-mer; then the recomputed checksum and id fingerprint =
+ * the header's.  Any failure: GK_E_FORMAT (GK_E_INVALID if the file cannot be opened or read), *out stays NULL and
+ * everything the call allocated is freed. */
+int gk_graph_save(gk_graph *g, const char *path);                  /* MapGraph.write, Graph.scala:232-248 */
+int gk_graph_load(gk_ctx *ctx, const char *path, gk_graph **out);  /* Graph(file), Graph.scala:384-390 + GraphSimplifier.scala:157-169 */
+int gk_graph_k(const gk_graph *g);                                 /* GraphSimplifier.scala:153: k comes from the graph (< 0: error) */
+/* wall ms of the last gk_graph_save / gk_graph_load on this context: {file I/O, waits for host<->device copies, device kernels
+ * (each phase ends in a sync), the whole call} */
+int gk_graph_io_stats(gk_ctx *ctx, float *ms4);
 
 /* ---- paired-end walking: GraphSimplifier.startup (S/scripts/GraphSimplifier.scala:188-318) ------------------------------
  * gk_support = the reference's pathsMap (:209: (edge id, edge id) -> number of read pairs whose walk passes through the two
