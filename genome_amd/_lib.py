@@ -160,6 +160,12 @@ SIGNATURES = {
     "gk_graph_load": (C.c_int, [vp, C.c_char_p, C.POINTER(vp)]),
     "gk_graph_k": (C.c_int, [vp]),
     "gk_graph_io_stats": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "gk_fastq_create": (C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "gk_fastq_destroy": (None, [vp]),
+    "gk_fastq_convert": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "gk_fastq_count": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, u64p]),
+    "gk_fastq_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
+    "gk_fastq_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "gk_synth_reads_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
     "gk_prefilter_create": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp)]),
     "gk_prefilter_destroy": (None, [vp]),

@@ -57,6 +57,7 @@ struct gk_ctx {
     int hook_p4_grid = -1;           // over-provisioned fine level: P4 workgroups per CU (-1: 4, or 2 of the 1024-thread form)
     int hook_p4_wide = -1;           // exact fine level, 8-byte keys: -1 auto (by nb2), 0 sort 4096 keys at a time, 1 sort 8192 (1024 threads)
     int hook_fine_exact = -1;        // -1 auto, 0 never unless forced by the data path, 1 always (A/B of the two fine levels)
+    int64_t hook_fastq_chunk = 0;    // test hook: text bytes per device chunk of gk_fastq_convert / gk_fastq_count (0: 128 MiB)
     // Block pool (gk::pool_malloc / pool_free): the big device buffers — tables, key scratch, graph arrays — are handed back
     // here instead of hipFree and reused by size.  hipMalloc / hipFree of multi-GB blocks cost milliseconds to seconds on this
     // platform and freed VRAM is scrubbed in the background on the copy engines: a second count over the same map paid 20 ms of
@@ -271,6 +272,11 @@ struct BinChunk {
 };
 BinChunk map_cut_chunk(gk_map *m, const uint8_t *bin, size_t nbytes, uint64_t nreads, size_t pos, uint64_t r, bool walk, int *err);
 int map_fire_prefetch(gk_map *m, hipEvent_t after);   // issue the armed host -> staging uploads on the copy stream behind `after` (nullptr: at once)
+// the FASTQ count path (gk_fastq.hip): begin, framed device batches of at most map_window_limit windows each, end
+int map_count_begin(gk_map *m);
+uint64_t map_window_limit(gk_map *m);
+int map_count_framed_dev(gk_map *m, const uint8_t *d_rec, const uint32_t *d_off, uint64_t nrec, uint64_t windows, double grow_ahead);
+int map_count_end(gk_map *m, uint64_t *occurrences);
 int map_ensure_sample(gk_map *m);                    // allocate the distinct-key sample set on first use
 // if the table cannot take `new_distinct` more keys, grow it (rehash, or plain re-allocation from empty) for `size_for` more
 int map_make_room(gk_map *m, uint64_t new_distinct, uint64_t size_for, bool from_empty, bool keep_lnb1 = false);

@@ -2039,3 +2039,35 @@ int gk_map_last_count_kernel(gk_map *m, float *ms, uint64_t *occurrences) {
 }
 
 }  // extern "C"
+
+namespace gk {
+// Device-resident ragged `.bin` records that a kernel produced (gk_fastq.hip): one call = begin, any number of framed batches, end.
+int map_count_begin(gk_map *m) {
+    if (int rc = check_map_lazy(m)) return rc;
+    reset_call_stats(m);
+    return reset_occ_counter(m);
+}
+// the most windows one insert may take: map_cut_chunk's occ_limit
+uint64_t map_window_limit(gk_map *m) {
+    return std::max<u64>(reads_per_launch(m, 1), use_partitioned(m, part_batch_keys(m)) ? part_batch_keys(m) : 0);
+}
+// records [0, nrec) at d_rec + d_off[r] (nrec + 1 offsets), `windows` k-mer windows in all (<= map_window_limit)
+int map_count_framed_dev(gk_map *m, const uint8_t *d_rec, const uint32_t *d_off, uint64_t nrec, uint64_t windows, double grow_ahead) {
+    if (!nrec) return GK_OK;
+    ReadSrc src;
+    src.rec = d_rec;
+    src.off = d_off;
+    src.nreads = nrec;
+    src.max_len = 255;
+    const int rc = insert_batch(m, src, nullptr, 0, windows, false, grow_ahead);
+    return rc > 0 ? fail(m->ctx, GK_E_STATE, "map_count_framed_dev: unexpected insert outcome " + std::to_string(rc)) : rc;
+}
+int map_count_end(gk_map *m, uint64_t *occurrences) {
+    uint64_t occ = 0;
+    if (int rc = read_occ_counter(m, &occ)) return rc;
+    m->last_count_occ = occ;
+    m->total_occurrences += occ;
+    if (occurrences) *occurrences = occ;
+    return GK_OK;
+}
+}  // namespace gk

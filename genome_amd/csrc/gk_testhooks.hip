@@ -70,6 +70,7 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
     else if (n == "test_pairs_small_sets") ctx->hook_pairs_small_sets = (int)value;
     else if (n == "filter_classic") ctx->hook_filter_classic = (int)value;
     else if (n == "graph_load_pct") ctx->hook_graph_load_pct = (int)value;
+    else if (n == "test_fastq_chunk") ctx->hook_fastq_chunk = (int64_t)std::max<int64_t>(0, value);
     else if (n == "fine_exact") ctx->hook_fine_exact = value < 0 ? -1 : value != 0;
     else return fail(ctx, GK_E_INVALID, "gk_ctx_set_option: unknown option '" + n + "'");
     return GK_OK;

@@ -256,6 +256,12 @@ class HipDNAMap:
         L.check(L.lib().gk_map_count_reads(self.h, L.ptr(buf, C.c_uint8), buf.size, nreads, C.byref(occ)), self.ctx.h)
         return occ.value
 
+    def count_fastq(self, path_or_bytes, split_at: int = 36):
+        """FreqFilter.add over FASTQ text parsed on the device (a path, `.gz` included, or the text's bytes): the same table as
+        count_reads of its Convert2bin stream.  -> (pairs, occurrences)"""
+        from .fastq import count_fastq
+        return count_fastq(self, path_or_bytes, split_at)
+
     def prefetch_reads(self, bin_bytes, nreads: int):
         """start the upload of a (pinned) `.bin` stream's head; the next count_reads of the same buffer finds it on the device"""
         buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)

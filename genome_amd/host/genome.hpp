@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <functional>
 #include <map>
 #include <optional>
@@ -94,7 +95,67 @@ struct PairedEndData {
     uint64_t count = 0;
     int insert = 0;
     std::vector<uint8_t> bin;
+    // Convert2bin (S/scripts/Convert2bin.scala) on the GPU straight into memory: the `.bin` stream and the pair count of a FASTQ
+    // file (plain text; splitAt = Convert2bin's n, 0 = interleaved).  Defined after FastqReader.
+    static PairedEndData fromFastq(Context &ctx, const std::string &path, int splitAt = 36);
 };
+
+// gk_fastq: FASTQ text -> `.bin` records on the GPU, fed in pieces of any size (the rules: include/genome_amd.h, "FASTQ")
+class FastqReader {
+  public:
+    struct Stats { uint64_t pairs = 0, shortPairs = 0, kmers = 0, textBytes = 0, carriedBytes = 0; };
+    explicit FastqReader(Context &ctx, int splitAt = 36, int kStats = 23, uint64_t maxPairs = 0) : ctx_(ctx.handle()) {
+        check(gk_fastq_create(ctx_, splitAt, kStats, maxPairs, &h_), ctx_);
+    }
+    ~FastqReader() { gk_fastq_destroy(h_); }
+    FastqReader(const FastqReader &) = delete;
+    FastqReader &operator=(const FastqReader &) = delete;
+    // appends the records of every pair this piece completes to `out` (last: the input ends with this piece)
+    void convert(const char *text, size_t n, bool last, std::vector<uint8_t> &out) {
+        const size_t old = out.size(), cap = stats().carriedBytes + n;
+        out.resize(old + cap);
+        size_t w = 0;
+        const int rc = gk_fastq_convert(h_, text, n, last ? 1 : 0, out.data() + old, cap, &w);
+        out.resize(old + w);
+        check(rc, ctx_);
+    }
+    Stats stats() const {
+        Stats s;
+        check(gk_fastq_stats(h_, &s.pairs, &s.shortPairs, &s.kmers, &s.textBytes, &s.carriedBytes), ctx_);
+        return s;
+    }
+    gk_fastq *handle() const { return h_; }
+
+  private:
+    gk_ctx *ctx_ = nullptr;
+    gk_fastq *h_ = nullptr;
+};
+
+// the file's bytes in pieces of `piece` bytes, each handed to f(data, n, last)
+template <class F>
+inline void forEachPiece(const std::string &path, size_t piece, F f) {
+    FILE *fp = std::fopen(path.c_str(), "rb");
+    if (!fp) throw GkError(GK_E_INVALID, "cannot open " + path);
+    std::vector<char> a(piece), b(piece);
+    size_t na = std::fread(a.data(), 1, piece, fp);
+    for (;;) {
+        const size_t nb = na == piece ? std::fread(b.data(), 1, piece, fp) : 0;
+        if (std::ferror(fp)) { std::fclose(fp); throw GkError(GK_E_INVALID, "cannot read " + path); }
+        try { f(a.data(), na, nb == 0); } catch (...) { std::fclose(fp); throw; }
+        if (nb == 0) break;
+        a.swap(b);
+        na = nb;
+    }
+    std::fclose(fp);
+}
+
+inline PairedEndData PairedEndData::fromFastq(Context &ctx, const std::string &path, int splitAt) {
+    PairedEndData d;
+    FastqReader rd(ctx, splitAt);
+    forEachPiece(path, 64u << 20, [&](const char *p, size_t n, bool last) { rd.convert(p, n, last, d.bin); });
+    d.count = rd.stats().pairs;
+    return d;
+}
 
 // Sharing the pairs out over N ranks: rank `rank` of `world` takes the pairs [n * rank / world, n * (rank + 1) / world) of the
 // first n = min(takeFirst, count) — the same range for the count and for the walks.

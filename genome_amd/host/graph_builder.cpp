@@ -5,6 +5,9 @@
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
 //                 [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH]
+//   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
+//   --fastq converts the FASTQ file on the GPU first (Convert2bin, gk_fastq; --split N = its n, default 36) and takes the pair
+//   count from the conversion; the flow is then the same.  Not with --world (exit 2): convert2bin the file first.
 //   --simplify runs removeBubbles + simplifyGraph (GraphSimplifier.scala:317-318) before writing;
 //   --walk-pairs runs GraphSimplifier.startup's paired-end stage on the graph GraphBuilder hands over (:188-318): position
 //   map, the pairs' walks with range LO to HI (the reference: 180 to 250, :146), node split at genome.cutoff = CUTOFF,
@@ -29,12 +32,44 @@
 #include <iostream>
 #include <iterator>
 #include <memory>
+#include <string>
+#include <vector>
 #include <thread>
 
 #include "genome.hpp"
 #include "rank_id.hpp"
 
+// The --fastq forms: take the FASTQ path and the split options out of argv, and leave the `.bin` form's argv in `args`
+// (the reads file and pair count are filled in after the conversion).  at = argv index of "--fastq"; -> 0, or 2 for a usage error.
+static int fastqArgs(int argc, char **argv, int at, std::string *fastq, int *split, std::vector<char *> *args) {
+    static char empty[] = "", zero[] = "0";
+    if (at + 1 >= argc) return 2;
+    *fastq = argv[at + 1];
+    for (int i = 0; i < argc; i++) {
+        if (i == at) { args->push_back(empty); args->push_back(zero); i++; continue; }
+        if (!std::strcmp(argv[i], "--split") && i + 1 < argc) { *split = std::stoi(argv[++i]); if (*split < 1) return 2; continue; }
+        if (!std::strcmp(argv[i], "--interleaved")) { *split = 0; continue; }
+        if (!std::strcmp(argv[i], "--world")) return 2;      // N-rank ingestion of FASTQ is not supported: convert first
+        args->push_back(argv[i]);
+    }
+    args->push_back(nullptr);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    std::string fastq;
+    int split = 36;
+    std::vector<char *> fargs;
+    const int fastq_at = argc >= 2 && !std::strcmp(argv[1], "--fastq") ? 1 : 0;
+    if (fastq_at) {
+        if (fastqArgs(argc, argv, fastq_at, &fastq, &split, &fargs)) {
+            std::fprintf(stderr, "usage: %s --fastq <reads.fastq> <k> [--split N | --interleaved] [options of the .bin form]\n"
+                                 "       (--fastq takes --split N or --interleaved; it does not run with --world: convert2bin first)\n", argv[0]);
+            return 2;
+        }
+        argc = (int)fargs.size() - 1;
+        argv = fargs.data();
+    }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
                              "[--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
@@ -74,9 +109,11 @@ int main(int argc, char **argv) {
         return 2;
     }
     try {
-        std::ifstream f(infile, std::ios::binary);
-        if (!f) throw std::runtime_error("cannot open " + infile);
-        data.bin.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        if (fastq.empty()) {
+            std::ifstream f(infile, std::ios::binary);
+            if (!f) throw std::runtime_error("cannot open " + infile);
+            data.bin.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        }
         int device = 0;
         if (world) {
             const int ndev = gk_device_count();
@@ -84,6 +121,7 @@ int main(int argc, char **argv) {
             device = rank % ndev;
         }
         genome::Context ctx(device);
+        if (!fastq.empty()) data = genome::PairedEndData::fromFastq(ctx, fastq, split);     // the pair count comes from the conversion
         std::unique_ptr<genome::PartitionedDNAMap> pm;
         uint64_t sent = 0, owned = 0, good = 0;
         std::unique_ptr<genome::DNAMap> kmersFreq;

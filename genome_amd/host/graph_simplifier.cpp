@@ -5,6 +5,8 @@
 //
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI] [--take-first N]
 //                    [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]
+//   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
+//   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
 //   k comes from the graph (:153); the range defaults to the reference's 180 to 250 (:146), the cutoff is genome.cutoff.
 //   The stage: getGraphMap (:188), walkPairs over the first N pairs (:213-263), splitBySupport (:272-316), simplifyGraph (:318).
 //   --out writes graph_builder's <prefix>.nodes.txt, .edges.txt, .contigs (:338-347) and .dot; --save-graph writes the final
@@ -21,11 +23,43 @@
 #include <iostream>
 #include <iterator>
 #include <memory>
+#include <string>
+#include <vector>
 
 #include "genome.hpp"
 #include "rank_id.hpp"
 
+// The --fastq forms: take the FASTQ path and the split options out of argv, and leave the `.bin` form's argv in `args`
+// (the reads file and pair count are filled in after the conversion).  at = argv index of "--fastq"; -> 0, or 2 for a usage error.
+static int fastqArgs(int argc, char **argv, int at, std::string *fastq, int *split, std::vector<char *> *args) {
+    static char empty[] = "", zero[] = "0";
+    if (at + 1 >= argc) return 2;
+    *fastq = argv[at + 1];
+    for (int i = 0; i < argc; i++) {
+        if (i == at) { args->push_back(empty); args->push_back(zero); i++; continue; }
+        if (!std::strcmp(argv[i], "--split") && i + 1 < argc) { *split = std::stoi(argv[++i]); if (*split < 1) return 2; continue; }
+        if (!std::strcmp(argv[i], "--interleaved")) { *split = 0; continue; }
+        if (!std::strcmp(argv[i], "--world")) return 2;      // N-rank ingestion of FASTQ is not supported: convert first
+        args->push_back(argv[i]);
+    }
+    args->push_back(nullptr);
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    std::string fastq;
+    int split = 36;
+    std::vector<char *> fargs;
+    const int fastq_at = argc >= 3 && !std::strcmp(argv[2], "--fastq") ? 2 : 0;
+    if (fastq_at) {
+        if (fastqArgs(argc, argv, fastq_at, &fastq, &split, &fargs)) {
+            std::fprintf(stderr, "usage: %s <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [options of the .bin form]\n"
+                                 "       (--fastq takes --split N or --interleaved; it does not run with --world: convert2bin first)\n", argv[0]);
+            return 2;
+        }
+        argc = (int)fargs.size() - 1;
+        argv = fargs.data();
+    }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI] [--take-first N] [--out prefix] "
                              "[--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
@@ -58,9 +92,11 @@ int main(int argc, char **argv) {
         return 2;
     }
     try {
-        std::ifstream f(infile, std::ios::binary);
-        if (!f) throw std::runtime_error("cannot open " + infile);
-        data.bin.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        if (fastq.empty()) {
+            std::ifstream f(infile, std::ios::binary);
+            if (!f) throw std::runtime_error("cannot open " + infile);
+            data.bin.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+        }
         int device = 0;
         if (world) {
             const int ndev = gk_device_count();
@@ -68,6 +104,7 @@ int main(int argc, char **argv) {
             device = rank % ndev;
         }
         genome::Context ctx(device);
+        if (!fastq.empty()) data = genome::PairedEndData::fromFastq(ctx, fastq, split);     // the pair count comes from the conversion
         auto graph = genome::Graph::load(ctx, graphFile);                                                // :152-153, :157-169
         const int k = graph.k();
         std::unique_ptr<genome::PartitionedDNAMap> pm;

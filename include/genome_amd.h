@@ -46,7 +46,7 @@ typedef enum {
     GK_E_CAPACITY = -4,       /* table could not grow / export buffer too small */
     GK_E_HIP = -5,            /* HIP runtime error (message has the hipError string) */
     GK_E_NODEVICE = -6,       /* no usable gfx950 device */
-    GK_E_FORMAT = -7,         /* malformed `.bin` read stream, or a malformed / corrupt graph file (gk_graph_load) */
+    GK_E_FORMAT = -7,         /* malformed `.bin` read stream or FASTQ text, or a malformed / corrupt graph file (gk_graph_load) */
     GK_E_STATE = -8,          /* operation not valid in the handle's current state */
     GK_E_COMM = -9            /* RCCL missing or a collective failed (message has the RCCL error string) */
 } gk_status;
@@ -56,6 +56,7 @@ typedef struct gk_map gk_map;       /* one ArrayDNAMap[Int] partition, resident 
 typedef struct gk_graph gk_graph;   /* a MapGraph, resident in HBM */
 typedef struct gk_prefilter gk_prefilter;   /* exact two-pass singleton pre-filter (2-bit counters) */
 typedef struct gk_dist gk_dist;     /* one rank of a PartitionedDNAMap spread over the GPUs of a node (RCCL communicator) */
+typedef struct gk_fastq gk_fastq;   /* a FASTQ -> `.bin` conversion in progress (Convert2bin, S/scripts/Convert2bin.scala) */
 
 /* ---- context ---------------------------------------------------------------------------- */
 int gk_device_count(void);                       /* number of HIP devices, 0 if none / no runtime */
@@ -487,6 +488,61 @@ int gk_map_count_reads_prefiltered_dev(gk_map *m, gk_prefilter *pf, const void *
                                        uint64_t *occurrences, uint64_t *admitted);
 /* counters in state "once" / "twice or more", buckets in total, windows fed to pass 1 (any may be NULL) */
 int gk_prefilter_stats(gk_prefilter *pf, uint64_t *buckets, uint64_t *seen_once, uint64_t *seen_twice_or_more, uint64_t *windows_added);
+
+/* ---- FASTQ -> `.bin`: Convert2bin (S/scripts/Convert2bin.scala:25-87), parsed on the device ------------------------------
+ * The rules (the output is byte-identical to what Convert2bin writes to <out>.bin):
+ *   - Lines are Java BufferedReader.readLine lines: a line ends at '\n', at '\r', or at "\r\n" (one terminator, also when it is
+ *     split between two pieces of input).  A non-empty unterminated tail at the end of the input is a line; an input that ends
+ *     right after a terminator has no further line.
+ *   - Records are 4 consecutive lines: header, sequence, separator, quality (:51-73).  Header and separator are not inspected.
+ *   - split_at >= 1 (the reference's n = 36): the sequence line and the quality line are each split at split_at characters
+ *     (splitAt, :59, :61); a line shorter than that gives an empty second half.  Mate 1 is the first halves, mate 2 the second.
+ *     split_at = 0 (interleaved): each record is one whole mate; records 2i and 2i+1 form pair i.
+ *   - A mate's length (filtered, :40-49) = min(sequence half's length, quality half's length, index of the half's first
+ *     character that is not one of the UPPERCASE A, G, C, T).  'N' and lowercase end a mate; quality values are otherwise ignored.
+ *   - Output per mate: [len:u8] then ceil(len/4) bytes of 2-bit codes A0 G1 C2 T3 packed LSB-first (:35-38); mate 1 before
+ *     mate 2, one pair per record (per two records, interleaved).
+ *   - Statistics (:32-47, :85-87): pairs = pairs emitted; kmers = sum of len - k_stats + 1 over the mates with len >= k_stats
+ *     (the reference's k = 23); short_pairs = pairs with a mate shorter than k_stats.
+ *   - End of input: a trailing lone header line is ignored (Convert2bin stops when the sequence readLine returns null); a
+ *     trailing record of 2 or 3 lines is GK_E_FORMAT (the reference crashes on the null quality line).
+ * Deliberate deviations from the reference, each GK_E_FORMAT instead of silent garbage: a mate longer than 255 (the reference
+ * writes length.toByte, which wraps); a byte >= 0x80 in a sequence or quality line (the reference splits at characters of the
+ * platform charset; this converter is ASCII only); a single record of more than 64 MiB of text; an odd number of records at the
+ * end of interleaved input.  Every such message names the 0-based record number ("FASTQ record N: ...", gk_last_error).
+ * The PairedEndData descriptor (:83) is not written: the pair count is reported (gk_fastq_stats) and the tools take it. */
+/* split_at >= 1: Convert2bin's n; 0: interleaved.  k_stats in 1..255 (the `kmers` / `short_pairs` statistics).
+ * max_pairs: stop emitting after that many pairs (0 = all; later records are still parsed for errors and counted as text
+ * only) - GraphBuilder's genome.takeFirst.  Device memory comes from the context's block pool (gk_ctx_mem_stats) and is released
+ * by gk_fastq_destroy. */
+int gk_fastq_create(gk_ctx *ctx, int split_at, int k_stats, uint64_t max_pairs, gk_fastq **out);
+void gk_fastq_destroy(gk_fastq *fq);
+/* Parse the next piece of text (last != 0: the input ends with it; later calls are GK_E_STATE).  An incomplete trailing record
+ * is kept in the handle ("carried") and completed by the next call.  Appends the .bin records of every completed pair to
+ * bin_out, *bin_bytes = bytes appended.  `text` may be pageable or pinned (gk_host_alloc / gk_host_register; pageable text is
+ * staged through pinned buffers).  Long calls are cut into device chunks; the next chunk's upload runs on the context's copy
+ * stream beside this chunk's kernels.
+ * BOUND: what one call writes never exceeds (bytes carried in) + nbytes, so a bin_cap below that is GK_E_CAPACITY before
+ * anything is consumed (the handle is unchanged: retry with a larger buffer).  Proof: the records a call completes lie in the
+ * carried bytes and the new text, and no two overlap.  A completed record has at least 3 terminator bytes (its header, sequence
+ * and separator lines are followed by a line) besides its sequence line of S characters.  Its mates have lengths l1 + l2 <= S
+ * (l1 <= the first half, l2 <= the second half; one mate of l <= S when interleaved), and a mate writes 1 + ceil(l/4) <= 1 + l
+ * bytes: at most 2 + S < S + 3 bytes per record.
+ * After any other error the handle refuses further calls with GK_E_STATE; after GK_E_FORMAT bin_out holds every pair before
+ * the bad record and nothing past the last good pair (*bin_bytes says how much). */
+int gk_fastq_convert(gk_fastq *fq, const char *text, size_t nbytes, int last, uint8_t *bin_out, size_t bin_cap, size_t *bin_bytes);
+/* The same parse, but the mates are counted into m (k = gk_map_k(m), same context) straight from device memory (FreqFilter.add,
+ * as gk_map_count_reads), with no .bin crossing to the host.  The table afterwards equals, bit for bit, the one
+ * gk_map_count_reads of the converted stream gives; *occurrences = windows counted by this call.  Inserts are cut into batches
+ * of at most the map's window limit from a device prefix sum of windows per mate.  On an error the promise is
+ * gk_map_count_reads' for a truncated stream: the pairs before the bad record, or chunks of them, may already be counted. */
+int gk_fastq_count(gk_fastq *fq, gk_map *m, const char *text, size_t nbytes, int last, uint64_t *occurrences);
+/* pairs, short_pairs, kmers (so far), text bytes consumed, bytes carried now (any may be NULL).  The carried count is what lets a
+ * caller size the next bin_out: carried + nbytes. */
+int gk_fastq_stats(const gk_fastq *fq, uint64_t *pairs, uint64_t *short_pairs, uint64_t *kmers, uint64_t *text_bytes,
+                   uint64_t *carried_bytes);
+/* wall ms of the last call: {host staging + upload, parse kernels, download or count, whole call} */
+int gk_fastq_last_ms(const gk_fastq *fq, float *ms4);
 
 /* ---- synthetic reads (bench / tests) ---------------------------------------- */
 /* Fill dev_records with nreads fixed-length `.bin` records generated on device, bit-identical to
