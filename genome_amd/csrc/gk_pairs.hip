@@ -1122,6 +1122,7 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
             if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_walk_pairs: keys");
         }
     }
+    sup->last_orientations = nq / 2; sup->last_overflow = 0;           // (what gk_test_support_last_walk reports: two orientations per cut pair)
     if (nq == 0) return GK_OK;
     const double t_keys = now();
     // ---- the four getAll of every pair as ONE batch, results left in HBM as CSR

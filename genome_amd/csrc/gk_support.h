@@ -22,6 +22,7 @@ struct gk_support {
     bool host_valid = false;
     float last_ms[5] = {0, 0, 0, 0, 0};        // last gk_graph_walk_pairs: keys from the stream, getAll batch, in-edge lists + checks, walks, overflow walks on the host
     gk::u64 last_overflow = 0;                 // orientations of the last call that went to the host walker
+    gk::u64 last_orientations = 0;             // orientations the last call handed to the walk stage (device kernel or, under "pairs_host", the host walker)
 };
 
 namespace gk {

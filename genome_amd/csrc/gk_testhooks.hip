@@ -1,6 +1,7 @@
 // gk_testhooks.hip — what ONLY the test build of the library has (libgenome_amd_test.so = the product's objects + this one):
 //   * gk_ctx_set_option and the environment switches read at gk_ctx_create: A/B switches of the kernels, test hooks that stage
 //     the large-table paths on small tables or inject failures;
+//   * gk_test_support_last_walk: which walker (device kernel / host fallback) did the orientations of the last gk_graph_walk_pairs;
 //   * gk_dist_create_loopback: a transport whose ranks are threads of ONE process on ONE device, so that gk_dist_* runs with
 //     world > 1 on a one-GPU box (RCCL refuses two ranks on one device).
 // The product library (libgenome_amd.so) links none of this; its header is include/genome_amd.h, this file's is
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "gk_dist.h"
+#include "gk_support.h"
 #include "../../include/genome_amd_test.h"
 
 using namespace gk;
@@ -83,6 +85,12 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
     return GK_OK;
 }
 
+int gk_test_support_last_walk(const gk_support *s, uint64_t *orientations, uint64_t *overflowed) {
+    if (!s) return fail(nullptr, GK_E_INVALID, "gk_test_support_last_walk: null support handle");
+    if (orientations) *orientations = s->last_orientations;
+    if (overflowed) *overflowed = s->last_overflow;
+    return GK_OK;
+}
 
 }  // extern "C"
 

@@ -299,6 +299,13 @@ class Support:
         L.check(L.lib().gk_support_last_ms(self.h, arr), self.ctx.h)
         return dict(zip(("keys", "lookup", "snapshot", "walks", "merge"), (float(x) for x in arr)))
 
+    def last_walk(self):
+        """-> (pair orientations the last walkPairs into this support handed to the walk stage, those of them that outgrew the
+        device's sets and were walked on the host).  A test hook: GkError on the product library."""
+        a, b = C.c_uint64(), C.c_uint64()
+        L.check(L.test_hook("gk_test_support_last_walk")(self.h, C.byref(a), C.byref(b)), self.ctx.h)
+        return a.value, b.value
+
     def items(self):
         n = self.sizes()[0]
         e1, e2, cnt = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)

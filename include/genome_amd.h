@@ -453,8 +453,9 @@ int gk_support_merge(gk_support *dst, const gk_support *src);
  * skipped, :213).  `positions` = gk_graph_position_map of THIS graph in its current state (GK_E_STATE otherwise).  For each
  * pair the four getAll (:214-217) run as one batch on the device; `annotate` (:192-206) drops an orientation whose mates lie
  * on one edge at a distance inside [range_lo, range_hi]; every (pos1, pos2) is walked as WalkingActor does (:78-125:
- * reachable set bounded by range_hi, paths whose length puts the mates range_lo..range_hi apart) on host threads, over a
- * snapshot of the graph's edge arrays; the edge pairs on successful paths are counted once per pair orientation.  The
+ * reachable set bounded by range_hi, paths whose length puts the mates range_lo..range_hi apart) by a device kernel, one wave per pair
+ * orientation with its sets in LDS; an orientation whose sets outgrow the LDS is walked by host threads over a snapshot of the
+ * graph's edge arrays instead (exact either way); the edge pairs on successful paths are counted once per pair orientation.  The
  * reference's range is 180 to 250 (:146). */
 int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const uint8_t *bin, size_t nbytes, uint64_t npairs, int range_lo,
                         int range_hi);

@@ -38,6 +38,12 @@ extern "C" {
  * its next gk_dist_reduce_support, after the records were exchanged). */
 int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value);
 
+/* Which walker produced the last gk_graph_walk_pairs into `s`: *orientations = pair orientations handed to the walk stage (two per
+ * pair whose mates both hold k bases), *overflowed = those of them whose sets outgrew the wave's LDS on the device and were walked
+ * by the host walker instead (0 under "pairs_host" = 1, where the host walks all of them by choice).  Two host integers the call
+ * leaves in the support; either pointer may be null.  A call that cut no pair leaves (0, 0). */
+int gk_test_support_last_walk(const gk_support *s, uint64_t *orientations, uint64_t *overflowed);
+
 /* TEST transport: the ranks are threads of ONE process on ONE device; sends, receives and reductions go through a hub in the
  * library (device-to-device copies matched pairwise in posting order) instead of RCCL, which refuses two ranks on one GPU.  Every
  * rank passes the same 128 id bytes (any) and its own context; calls block until the peers have posted the matching operation

@@ -102,18 +102,18 @@ def read_shares(nreads, world):
     return [(nreads * r // world, nreads * (r + 1) // world) for r in range(world)]
 
 
-def rank_graph(c, hd, k, binb, nreads, rank, world, classified, retain, other_layout=False):
+def rank_graph(c, hd, k, binb, nreads, rank, world, classified, retain, other_layout=False, read_len=READ_LEN):
     """this rank's reads counted through the partitioned map, filtered, gathered, built (and its largest component kept).
     other_layout: the gather still runs (it is collective), but the replica is built from all reads counted on this rank's own
     context in a table of another capacity — another slot layout, hence (in general) other ids."""
     a, b = read_shares(nreads, world)[rank]
-    stride = 1 + (READ_LEN + 3) // 4
+    stride = 1 + (read_len + 3) // 4
     rec = np.frombuffer(binb, np.uint8)[a * stride:b * stride]
     d = c.alloc(max(rec.size, 1) + 64)
     if rec.size:
         c.upload(d, np.ascontiguousarray(rec))
     pm = DistDNAMap(hd, k, 1 << 10)
-    pm.count_reads_dev(d, b - a, READ_LEN)
+    pm.count_reads_dev(d, b - a, read_len)
     pm.deleteAll_lt(2)
     full = pm.gathered(classified=classified)
     if other_layout:
@@ -236,9 +236,19 @@ def test_id_fingerprint_sees_ids_and_liveness(ctx):
 
 # ---- N ranks ----------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("world,k,seed,rng,classified", [(2, 21, 1, (60, 95), True), (3, 31, 3, (50, 85), False), (8, 35, 4, (50, 80), True)])
+# make_pairs' knobs of the rows at the reference's range: 150-base mates with 0.5 % errors over an 8 kbp genome, inserts whose walk
+# distance (insert - k) lies inside 180..250 (test_pairs_shapes_gpu.py's fixture); the other rows keep make_pairs' defaults
+def wide_fixture(k, rng):
+    return dict(glen=8000, nrep=4, L=150, npairs=6000, err=0.005, ins=(k + 185, k + 245)) if rng == (180, 250) else {}
+
+
+@pytest.mark.parametrize("world,k,seed,rng,classified", [(2, 21, 1, (60, 95), True), (3, 31, 3, (50, 85), False), (8, 35, 4, (50, 80), True),
+                                                         (2, 55, 5, (180, 250), True), (3, 64, 6, (180, 250), False)])
 def test_reduce_over_ranks_equals_one_rank_and_the_oracle(world, k, seed, rng, classified):
-    reads = make_pairs(seed, k)
+    fx = wide_fixture(k, rng)
+    reads = make_pairs(seed, k, **fx)
+    read_len = fx.get("L", READ_LEN)
+    assert {len(r) for r in reads} == {read_len}
     binb = dna.reads_to_bin(reads)
     nreads, npairs = len(reads), len(reads) // 2
     # one rank, all pairs
@@ -268,7 +278,7 @@ def test_reduce_over_ranks_equals_one_rank_and_the_oracle(world, k, seed, rng, c
     assert shares[world // 2][0] == shares[world // 2][1] and len({b - a for a, b in shares}) > 1
 
     def body(rank, c, hd):
-        full, g = rank_graph(c, hd, k, binb, nreads, rank, world, classified, retain=True, other_layout=rank % 2 == 1)
+        full, g = rank_graph(c, hd, k, binb, nreads, rank, world, classified, retain=True, other_layout=rank % 2 == 1, read_len=read_len)
         vm = g.getGraphMap()
         s_all = walk_share(c, g, vm, binb, (0, npairs), rng)   # one walk of every pair on THIS replica: the by-id reference
         one = snapshot(s_all)

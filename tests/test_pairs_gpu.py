@@ -7,7 +7,6 @@ Edge ids are arbitrary on both sides: support counts are compared after translat
 both edges — unique on a freshly built graph.  The graphs after split + removeEdge + simplifyGraph are compared as canonical
 node / edge lists (copies of a node share a sequence: lists, not sets)."""
 import random
-from collections import Counter
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ from genome_amd.dnamap import Context, HipDNAMap
 from genome_amd.graph import Support, buildGraph
 from oracle import oracle as O
 from oracle import pyref as R
+from pairs_ref import gpu_canonical, gpu_support_by_content, make_pairs, oracle_canonical, oracle_support_by_content  # noqa: F401 (other modules import them from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,69 +26,6 @@ def ctx():
     c = Context(0)
     yield c
     c.close()
-
-
-def make_pairs(seed, k, glen=2400, nrep=3, L=40, npairs=5000, ins=(80, 100), err=0.0):
-    """A random genome in which `nrep` k-mers occur twice in different contexts (a node with two in- and two out-edges each,
-    which only read pairs can resolve), and read pairs of insert size `ins` from both strands."""
-    rnd = random.Random(seed)
-    g = [rnd.choice("AGCT") for _ in range(glen)]
-    for _ in range(nrep):
-        a = rnd.randrange(100, glen // 2 - 100)
-        b = rnd.randrange(glen // 2 + 100, glen - 100)
-        g[b:b + k] = g[a:a + k]
-    g = "".join(g)
-    reads = []
-    for _ in range(npairs):
-        ins_len = rnd.randint(*ins)
-        s = rnd.randrange(0, glen - ins_len)
-        frag = g[s:s + ins_len]
-        if rnd.random() < 0.5:
-            frag = R.rev_comp(frag)
-        m1, m2 = frag[:L], R.rev_comp(frag)[:L]
-        if err:
-            m1 = "".join(c if rnd.random() >= err else rnd.choice([x for x in "AGCT" if x != c]) for c in m1)
-            m2 = "".join(c if rnd.random() >= err else rnd.choice([x for x in "AGCT" if x != c]) for c in m2)
-        reads += [m1, m2]
-    return reads
-
-
-def oracle_canonical(og):
-    k = og.k
-    nlo, nhi = og.nodes()
-    nodes = sorted(dna.unpack(int(a), int(b), k) for a, b in zip(nlo, nhi))
-    e = og.edges()
-    edges = []
-    for i in range(len(e["len"])):
-        seq = synth.bases_to_str(e["bases"][e["off"][i]:e["off"][i] + e["len"][i]])
-        edges.append((dna.unpack(int(e["slo"][i]), int(e["shi"][i]), k), dna.unpack(int(e["elo"][i]), int(e["ehi"][i]), k), seq))
-    return nodes, sorted(edges)
-
-
-def gpu_canonical(g):
-    nodes, edges = g.canonical()
-    return sorted(nodes), sorted(edges)
-
-
-def gpu_support_by_content(g, k, sup):
-    e1, e2, cnt = sup.items()
-    ids = sorted(set(e1.tolist()) | set(e2.tolist()))
-    if not ids:
-        return Counter()
-    info = g.edgesById(ids)
-    nid = sorted({int(x) for x in info["start"]})
-    ninfo = g.nodesById(nid)
-    nkmer = {n: dna.unpack(int(ninfo["lo"][j]), int(ninfo["hi"][j]), k) for j, n in enumerate(nid)}
-    key = {e: (nkmer[int(info["start"][j])], int(info["first"][j])) for j, e in enumerate(ids)}
-    return Counter({(key[int(a)], key[int(b)]): int(c) for a, b, c in zip(e1, e2, cnt)})
-
-
-def oracle_support_by_content(og, k, osup):
-    e1, e2, cnt = osup.items()
-    def key(e):
-        info = og.edge_info(int(e))
-        return (dna.unpack(*og.node_seq(info["start"]), k), info["first"])
-    return Counter({(key(a), key(b)): int(c) for a, b, c in zip(e1, e2, cnt)})
 
 
 @pytest.mark.parametrize("k,seed,err,rng", [(21, 1, 0.0, (60, 95)), (21, 2, 0.004, (55, 90)), (31, 3, 0.0, (50, 85)), (35, 4, 0.0, (50, 80))])

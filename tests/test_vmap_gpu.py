@@ -138,7 +138,7 @@ def _oracle_positions(og, k, calls, idx):
     return out
 
 
-@pytest.mark.parametrize("k,seed", [(11, 1), (31, 2), (35, 3), (63, 4)])
+@pytest.mark.parametrize("k,seed", [(11, 1), (31, 2), (35, 3), (63, 4), (64, 5)])
 @pytest.mark.parametrize("simplified", [False, True])
 def test_get_graph_map_vs_oracle(ctx, k, seed, simplified):
     m, ref, g, og = _graph_pair(ctx, k, seed)
