@@ -132,7 +132,7 @@ static void drain_garbage(gk_dist *d) {
     gk_ctx *ctx = d->ctx;
     std::vector<void *> g;
     { std::lock_guard<std::mutex> lk(d->wmu); g.swap(d->garbage); }
-    for (void *p : g) (void)hipFree(p);
+    for (void *p : g) (void)pool_free(ctx, p);
 }
 
 static thread_local const gk_dist *tl_dist = nullptr;       // whose transport explains an error code (set by dist_check)
@@ -199,9 +199,9 @@ int dist_create_common(gk_ctx *ctx, int rank, int world, gk_dist **out) {
     *out = nullptr;
     gk_dist *d = new gk_dist();
     d->ctx = ctx; d->rank = rank; d->world = world;
-    hipError_t e = hipMalloc((void **)&d->d_cnt, 8 * 64 * sizeof(unsigned long long));
+    hipError_t e = pool_malloc(ctx, &d->d_cnt, 8 * 64 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipHostMalloc((void **)&d->h_cnt, 8 * 64 * sizeof(unsigned long long), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void **)&d->d_route_cnt, gk_dist::NROUTE * SKM_COUNT_WORDS * sizeof(unsigned long long));
+    if (e == hipSuccess) e = pool_malloc(ctx, &d->d_route_cnt, gk_dist::NROUTE * SKM_COUNT_WORDS * sizeof(unsigned long long));
     for (int i = 0; i < gk_dist::NROUTE && e == hipSuccess; i++) e = hipEventCreateWithFlags(&d->route_done[i], hipEventDisableTiming);
     for (int i = 0; i < gk_dist::NROUTE && e == hipSuccess; i++) e = hipEventCreateWithFlags(&d->exch_done[i], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&d->join, hipEventDisableTiming);
@@ -243,16 +243,16 @@ void gk_dist_destroy(gk_dist *d) {
     if (d->comm_stream) (void)hipStreamSynchronize(d->comm_stream);
     if (d->xport && d->xport->close) d->xport->close(d);
     if (d->ctx && d->ctx->copy_stream) (void)hipStreamSynchronize(d->ctx->copy_stream);
-    for (int i = 0; i < gk_dist::NROUTE; i++) if (d->d_sendbuf[i]) (void)hipFree(d->d_sendbuf[i]);
-    for (int i = 0; i < 2; i++) if (d->d_recv[i]) (void)hipFree(d->d_recv[i]);
-    for (int i = 0; i < gk_dist::NROUTE; i++) { if (d->d_stage[i]) (void)hipFree(d->d_stage[i]); if (d->d_stage_offs[i]) (void)hipFree(d->d_stage_offs[i]); }
+    for (int i = 0; i < gk_dist::NROUTE; i++) (void)pool_free(ctx, d->d_sendbuf[i]);
+    for (int i = 0; i < 2; i++) (void)pool_free(ctx, d->d_recv[i]);
+    for (int i = 0; i < gk_dist::NROUTE; i++) { (void)pool_free(ctx, d->d_stage[i]); (void)pool_free(ctx, d->d_stage_offs[i]); }
     for (int i = 0; i < gk_dist::NROUTE; i++) if (d->route_done[i]) (void)hipEventDestroy(d->route_done[i]);
     for (int i = 0; i < gk_dist::NROUTE; i++) if (d->exch_done[i]) (void)hipEventDestroy(d->exch_done[i]);
     if (d->join) (void)hipEventDestroy(d->join);
     if (d->comm_stream) (void)hipStreamDestroy(d->comm_stream);
-    if (d->d_route_cnt) (void)hipFree(d->d_route_cnt);
+    (void)pool_free(ctx, d->d_route_cnt);
     if (d->h_route_cnt) (void)hipHostFree(d->h_route_cnt);
-    if (d->d_cnt) (void)hipFree(d->d_cnt);
+    (void)pool_free(ctx, d->d_cnt);
     if (d->h_cnt) (void)hipHostFree(d->h_cnt);
     delete d;
 }
@@ -306,9 +306,9 @@ int gk_dist_size(gk_dist *d, gk_map *local, uint64_t *total) {
 
 static int dist_grow(gk_ctx *ctx, uint8_t **buf, u64 *have, u64 want_records, int slot) {
     if (*have >= want_records && *buf) return GK_OK;
-    if (*buf) { GK_HIP(ctx, hipStreamSynchronize(ctx->stream)); GK_HIP(ctx, hipFree(*buf)); }
+    if (*buf) { GK_HIP(ctx, hipStreamSynchronize(ctx->stream)); GK_HIP(ctx, pool_free(ctx, *buf)); }
     *buf = nullptr; *have = 0;
-    GK_HIP(ctx, hipMalloc((void **)buf, std::max<u64>(want_records, 1) * (u64)slot + 64));
+    GK_HIP(ctx, pool_malloc(ctx, buf, std::max<u64>(want_records, 1) * (u64)slot + 64));
     *have = want_records;
     return GK_OK;
 }
@@ -354,8 +354,8 @@ static int route_begin_impl(gk_dist *d, int k, const void *dev_records, const ui
         GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
         GK_HIP(ctx, hipStreamSynchronize(d->comm_stream));
-        for (int i = 0; i < NR; i++) { if (d->d_sendbuf[i]) GK_HIP(ctx, hipFree(d->d_sendbuf[i])); d->d_sendbuf[i] = nullptr; d->send_cap[i] = 0; }
-        for (int i = 0; i < 2; i++) { if (d->d_recv[i]) GK_HIP(ctx, hipFree(d->d_recv[i])); d->d_recv[i] = nullptr; d->recv_records[i] = 0; }
+        for (int i = 0; i < NR; i++) { if (d->d_sendbuf[i]) GK_HIP(ctx, pool_free(ctx, d->d_sendbuf[i])); d->d_sendbuf[i] = nullptr; d->send_cap[i] = 0; }
+        for (int i = 0; i < 2; i++) { if (d->d_recv[i]) GK_HIP(ctx, pool_free(ctx, d->d_recv[i])); d->d_recv[i] = nullptr; d->recv_records[i] = 0; }
         d->slot = slot;
     }
     const int b = (d->head + d->npending) % NR;
@@ -363,7 +363,7 @@ static int route_begin_impl(gk_dist *d, int k, const void *dev_records, const ui
     u64 want = std::max(dev_offsets ? route_want_records_ragged(k, P, nreads, windows) : route_want_records(k, P, nreads, read_len), d->send_cap[b]);
     if (ctx->hook_dist_small_send > 0) {      // test hook: THIS route gets a send buffer of so many records — the in-place re-route must repair it
         GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-        if (d->d_sendbuf[b]) { GK_HIP(ctx, hipFree(d->d_sendbuf[b])); d->d_sendbuf[b] = nullptr; d->send_cap[b] = 0; }
+        if (d->d_sendbuf[b]) { GK_HIP(ctx, pool_free(ctx, d->d_sendbuf[b])); d->d_sendbuf[b] = nullptr; d->send_cap[b] = 0; }
         want = (u64)std::max(ctx->hook_dist_small_send, P);
         ctx->hook_dist_small_send = 0;
     }
@@ -482,7 +482,7 @@ static int dist_exchange(gk_dist *d, int b, float *ms) {
     if (nrec_in > d->recv_records[rb] || !d->d_recv[rb]) {
         const u64 want = std::max<u64>(nrec_in + nrec_in / 8, 1024);
         uint8_t *nb = nullptr;
-        e = hipMalloc((void **)&nb, want * (u64)slot + 64);                         // (the pool: a mutex, no stream is waited for)
+        e = pool_malloc(ctx, &nb, want * (u64)slot + 64);                         // (the pool: a mutex, no stream is waited for)
         if (e == hipSuccess) {
             if (d->d_recv[rb]) { std::lock_guard<std::mutex> lk(d->wmu); d->garbage.push_back(d->d_recv[rb]); }
             d->d_recv[rb] = nb; d->recv_records[rb] = want;
@@ -660,9 +660,9 @@ int gk_dist_count_reads(gk_dist *d, gk_map *local, const uint8_t *bin, size_t nb
     std::string failed_err;
     auto grow = [&](void **buf, u64 *have, u64 want) -> int {
         if (*have >= want && *buf) return GK_OK;
-        if (*buf) GK_HIP(ctx, hipFree(*buf));
+        if (*buf) GK_HIP(ctx, pool_free(ctx, *buf));
         *buf = nullptr; *have = 0;
-        GK_HIP(ctx, hipMalloc(buf, want));
+        GK_HIP(ctx, pool_malloc(ctx, buf, want));
         *have = want;
         return GK_OK;
     };
@@ -759,9 +759,8 @@ static int dist_gather(gk_dist *d, gk_map *local, gk_map **full, bool classify) 
     // every rank's chunk holds at most CHS keys: the receive staging is allocated ONCE, before anything is agreed — no allocation,
     // hence no local failure, between a chunk's size exchange and its sends and receives
     const u64 recv_cap = std::max<u64>(std::min<u64>(total, (u64)P * CHS), 1);
-    auto done = [&](int code) {
-        for (void *p : {(void *)d_send_k, (void *)d_send_c, (void *)d_recv_k, (void *)d_recv_c, (void *)d_cur, (void *)d_send_m, (void *)d_recv_m, (void *)d_dc,
-                        (void *)d_qk, (void *)d_qref, (void *)d_rk, (void *)d_ans_in, (void *)d_ans_out}) if (p) (void)hipFree(p);
+    DevScratch tmp(ctx);
+    auto done = [&](int code) {          // a failed gather leaves no table behind
         if (code != GK_OK && m) { gk_map_destroy(m); m = nullptr; }
         return code;
     };
@@ -771,14 +770,14 @@ static int dist_gather(gk_dist *d, gk_map *local, gk_map **full, bool classify) 
     if (!my_rc) { my_rc = map_create_for_graph(ctx, local->k, total, &m); if (my_rc) my_err = ctx->err; }
     const u64 send_cap = std::min<u64>(CHS, local->capacity);
     if (!my_rc) {
-        hipError_t e = hipMalloc((void **)&d_send_k, std::max<u64>(send_cap, 1) * 8 * W);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_send_c, std::max<u64>(send_cap, 1) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_cur, 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_recv_k, recv_cap * 8 * W);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_recv_c, recv_cap * 4);
-        if (e == hipSuccess && classify) e = hipMalloc((void **)&d_send_m, std::max<u64>(send_cap, 1));
-        if (e == hipSuccess && classify) e = hipMalloc((void **)&d_recv_m, recv_cap);
-        if (e == hipSuccess && classify) e = hipMalloc((void **)&d_dc, 5 * 64 * 8);
+        hipError_t e = tmp.get(&d_send_k, std::max<u64>(send_cap, 1) * W);
+        if (e == hipSuccess) e = tmp.get(&d_send_c, send_cap);
+        if (e == hipSuccess) e = tmp.get(&d_cur, 1);
+        if (e == hipSuccess) e = tmp.get(&d_recv_k, recv_cap * W);
+        if (e == hipSuccess) e = tmp.get(&d_recv_c, recv_cap);
+        if (e == hipSuccess && classify) e = tmp.get(&d_send_m, send_cap);
+        if (e == hipSuccess && classify) e = tmp.get(&d_recv_m, recv_cap);
+        if (e == hipSuccess && classify) e = tmp.get(&d_dc, 5 * 64);
         if (e != hipSuccess) { my_rc = hip_fail(ctx, e, "gk_dist_gather_map: staging"); my_err = ctx->err; }
     }
 #define HIPD(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return done(hip_fail(ctx, e__, #call)); } while (0)
@@ -829,18 +828,18 @@ static int dist_gather(gk_dist *d, gk_map *local, gk_map **full, bool classify) 
                 my_err = ctx->err;
             }
             if (!my_rc && nq_out > q_out_cap) {
-                for (void *q : {(void *)d_qk, (void *)d_qref, (void *)d_ans_in}) if (q) (void)hipFree(q);
-                d_qk = d_qref = nullptr; d_ans_in = nullptr; q_out_cap = 0;
-                hipError_t e = hipMalloc((void **)&d_qk, nq_out * 8 * W);
-                if (e == hipSuccess) e = hipMalloc((void **)&d_qref, nq_out * 8);
-                if (e == hipSuccess) e = hipMalloc((void **)&d_ans_in, nq_out);
+                tmp.release(d_qk); tmp.release(d_qref); tmp.release(d_ans_in);
+                q_out_cap = 0;
+                hipError_t e = tmp.get(&d_qk, nq_out * W);
+                if (e == hipSuccess) e = tmp.get(&d_qref, nq_out);
+                if (e == hipSuccess) e = tmp.get(&d_ans_in, nq_out);
                 if (e != hipSuccess) { my_rc = hip_fail(ctx, e, "gk_dist_gather_map: query staging"); my_err = ctx->err; } else q_out_cap = nq_out;
             }
             if (!my_rc && nq_in > q_in_cap) {
-                for (void *q : {(void *)d_rk, (void *)d_ans_out}) if (q) (void)hipFree(q);
-                d_rk = nullptr; d_ans_out = nullptr; q_in_cap = 0;
-                hipError_t e = hipMalloc((void **)&d_rk, nq_in * 8 * W);
-                if (e == hipSuccess) e = hipMalloc((void **)&d_ans_out, nq_in);
+                tmp.release(d_rk); tmp.release(d_ans_out);
+                q_in_cap = 0;
+                hipError_t e = tmp.get(&d_rk, nq_in * W);
+                if (e == hipSuccess) e = tmp.get(&d_ans_out, nq_in);
                 if (e != hipSuccess) { my_rc = hip_fail(ctx, e, "gk_dist_gather_map: query staging"); my_err = ctx->err; } else q_in_cap = nq_in;
             }
             {
@@ -980,19 +979,6 @@ int gk_dist_classify_queries(gk_dist *d, uint64_t *n) {
 // Every allocation is made in front of the agreement that covers it, and nothing is allocated between an agreement and the
 // payload it guards.
 namespace {
-struct DevBufs {          // device staging of one call, freed together.  hipMalloc / hipFree here ARE the context's block pool
-                          // (gk_internal.h maps them to pool_malloc / pool_free by macro, hence the ctx member): no device-wide sync
-    gk_ctx *ctx;
-    std::vector<void *> p;
-    explicit DevBufs(gk_ctx *c) : ctx(c) {}
-    ~DevBufs() { for (void *q : p) (void)hipFree(q); }
-    template <class T> bool get(T **out, u64 n) {
-        *out = nullptr;
-        if (hipMalloc((void **)out, std::max<u64>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        p.push_back(*out);
-        return true;
-    }
-};
 struct SupHandle {        // a temporary support table on the handle's context
     gk_support *s = nullptr;
     ~SupHandle() { if (s) gk_support_destroy(s); }
@@ -1050,7 +1036,7 @@ extern "C" int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup) 
     // ---- 1. status and the replicas' content.  The replicas need not number their edges alike (a build numbers in table slot
     //      order, with atomic output cursors): the pairs travel in the CANONICAL numbering of graph_edge_canon — live edges
     //      ordered by (start k-mer, first base) — which is the same on every replica that holds the same edges.
-    DevBufs buf(ctx);
+    DevScratch buf(ctx);
     u64 fp = 0, nlive = 0;
     u32 *d_canon = nullptr, *d_inv = nullptr;
     unsigned long long ctr[4] = {0, 0, 0, 0};
@@ -1058,9 +1044,7 @@ extern "C" int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup) 
     else if (check_graph(g) != GK_OK) local(GK_E_INVALID);
     else if (g->ctx != ctx || sup->ctx != ctx) local(fail(ctx, GK_E_INVALID, std::string(who) + "the graph and the support must live on the handle's context"));
     if (!my_rc) {
-        local(graph_edge_canon(g, &d_canon, &d_inv, &nlive, &fp));
-        if (d_canon) buf.p.push_back(d_canon);
-        if (d_inv) buf.p.push_back(d_inv);
+        local(graph_edge_canon(g, buf, &d_canon, &d_inv, &nlive, &fp));
     }
     if (!my_rc) local(support_counters(sup, ctr));
     std::vector<unsigned long long> st(P), fps(P);
@@ -1079,7 +1063,7 @@ extern "C" int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup) 
     u32 *d_sc = nullptr, *d_rc = nullptr, *d_ac = nullptr;
     std::vector<u64> region(P + 1, 0);
     const u64 mine = ctr[0];
-    if (!buf.get(&d_sk, mine) || !buf.get(&d_sc, mine)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(mine) + " pairs"));
+    if (buf.get(&d_sk, mine) != hipSuccess || buf.get(&d_sc, mine) != hipSuccess) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(mine) + " pairs"));
     if (!my_rc) local(support_bucket(sup, P, d_sk, d_sc, mine, region.data(), d_canon, g->v.n_edges));
     std::vector<unsigned long long> out(P), in(P);
     for (int p = 0; p < P; p++) out[p] = my_rc ? ~0ull : region[p + 1] - region[p];
@@ -1093,7 +1077,7 @@ extern "C" int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup) 
     }
     if (my_rc) return give_up("");                                // (unreachable: this rank sent ~0 to itself)
     // ---- 3. room for the arrivals and the shard table
-    if (!buf.get(&d_rk, nin) || !buf.get(&d_rc, nin)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(nin) + " arriving pairs"));
+    if (buf.get(&d_rk, nin) != hipSuccess || buf.get(&d_rc, nin) != hipSuccess) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(nin) + " arriving pairs"));
     if (!my_rc) local(gk_support_create(ctx, &shard.s));
     if (!my_rc) local(support_reserve(shard.s, nin));
     {
@@ -1135,7 +1119,7 @@ extern "C" int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup) 
     std::vector<u64> soff(P + 1, 0);
     for (int p = 0; p < P; p++) { soff[p] = total; total += ssz[p]; }
     // ---- 6. room for every shard and the new table
-    if (!buf.get(&d_ak, total) || !buf.get(&d_ac, total)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(total) + " pairs"));
+    if (buf.get(&d_ak, total) != hipSuccess || buf.get(&d_ac, total) != hipSuccess) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(total) + " pairs"));
     if (!my_rc) local(gk_support_create(ctx, &fresh.s));
     if (!my_rc) local(support_reserve(fresh.s, total));
     {

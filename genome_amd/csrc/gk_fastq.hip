@@ -322,10 +322,10 @@ template <class T>
 int fq_grow(gk_ctx *ctx, T **p, size_t *cap, size_t want) {
     if (*cap >= want && *p) return GK_OK;
     want = std::max(want, *cap + *cap / 2);
-    if (*p) GK_HIP(ctx, hipFree(*p));
+    if (*p) GK_HIP(ctx, pool_free(ctx, *p));
     *p = nullptr;
     *cap = 0;
-    GK_HIP(ctx, hipMalloc(p, want * sizeof(T)));
+    GK_HIP(ctx, pool_malloc(ctx, p, want * sizeof(T)));
     *cap = want;
     return GK_OK;
 }
@@ -338,10 +338,10 @@ int fq_mates(gk_fastq *fq, size_t want) {
     u32 **a32[] = {&fq->d_mlen, &fq->d_mstart, &fq->d_bytes, &fq->d_win, &fq->d_off32};
     unsigned long long **a64[] = {&fq->d_off64, &fq->d_wpre};
     fq->mate_cap = 0;
-    for (u32 **p : a32) { if (*p) GK_HIP(ctx, hipFree(*p)); *p = nullptr; }
-    for (unsigned long long **p : a64) { if (*p) GK_HIP(ctx, hipFree(*p)); *p = nullptr; }
-    for (u32 **p : a32) GK_HIP(ctx, hipMalloc(p, want * sizeof(u32)));
-    for (unsigned long long **p : a64) GK_HIP(ctx, hipMalloc(p, want * sizeof(unsigned long long)));
+    for (u32 **p : a32) { if (*p) GK_HIP(ctx, pool_free(ctx, *p)); *p = nullptr; }
+    for (unsigned long long **p : a64) { if (*p) GK_HIP(ctx, pool_free(ctx, *p)); *p = nullptr; }
+    for (u32 **p : a32) GK_HIP(ctx, pool_malloc(ctx, p, want * sizeof(u32)));
+    for (unsigned long long **p : a64) GK_HIP(ctx, pool_malloc(ctx, p, want * sizeof(unsigned long long)));
     fq->mate_cap = want;
     return GK_OK;
 }
@@ -357,10 +357,10 @@ int fq_text_buffer(gk_fastq *fq, int b, u64 carry, u64 slice, bool keep) {
     const u64 sl = std::max<u64>(fq->slice_cap[b], slice);
     GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
     uint8_t *nbuf = nullptr;
-    GK_HIP(ctx, hipMalloc(&nbuf, head + sl + 64));
+    GK_HIP(ctx, pool_malloc(ctx, &nbuf, head + sl + 64));
     if (keep && carry && fq->buf[b])
         GK_HIP(ctx, hipMemcpyAsync(nbuf + head - carry, fq->buf[b] + fq->head[b] - carry, carry, hipMemcpyDeviceToDevice, ctx->stream));
-    if (fq->buf[b]) GK_HIP(ctx, hipFree(fq->buf[b]));       // (waits for the context's streams: the move has landed)
+    if (fq->buf[b]) GK_HIP(ctx, pool_free(ctx, fq->buf[b]));       // (waits for the context's streams: the move has landed)
     fq->buf[b] = nbuf; fq->head[b] = head; fq->slice_cap[b] = sl; fq->pf_src[b] = nullptr;
     return GK_OK;
 }
@@ -580,8 +580,8 @@ int gk_fastq_create(gk_ctx *ctx, int split_at, int k_stats, uint64_t max_pairs, 
         e = hipEventCreate(&fq->up0[i]);
         if (e == hipSuccess) e = hipEventCreate(&fq->up1[i]);
     }
-    if (e == hipSuccess) e = hipMalloc(&fq->d_plan, sizeof(FqPlan));
-    if (e == hipSuccess) e = hipMalloc(&fq->d_sum, sizeof(FqSum));
+    if (e == hipSuccess) e = pool_malloc(ctx, &fq->d_plan, sizeof(FqPlan));
+    if (e == hipSuccess) e = pool_malloc(ctx, &fq->d_sum, sizeof(FqSum));
     if (e == hipSuccess) e = hipHostMalloc((void **)&fq->h, sizeof(FqHost), 0);
     if (e != hipSuccess) { const int rc = hip_fail(ctx, e, "gk_fastq_create"); gk_fastq_destroy(fq); return rc; }
     *out = fq;
@@ -595,7 +595,7 @@ void gk_fastq_destroy(gk_fastq *fq) {
     (void)hipStreamSynchronize(ctx->stream);
     void *dev[] = {fq->buf[0], fq->buf[1], fq->d_tile_cnt, fq->d_tile_off, fq->d_scan, fq->d_E, fq->d_mlen, fq->d_mstart, fq->d_bytes, fq->d_win,
                    fq->d_off32, fq->d_off64, fq->d_wpre, fq->d_cut, fq->d_out, fq->d_plan, fq->d_sum};
-    for (void *p : dev) if (p) (void)hipFree(p);
+    for (void *p : dev) (void)pool_free(ctx, p);
     for (int i = 0; i < 2; i++) {
         if (fq->h_stage[i]) (void)hipHostFree(fq->h_stage[i]);
         if (fq->up0[i]) (void)hipEventDestroy(fq->up0[i]);

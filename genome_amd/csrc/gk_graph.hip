@@ -1535,11 +1535,11 @@ int ggrid(const gk_ctx *ctx, u64 items) {
 
 template <class T> static hipError_t dev_grow(gk_ctx *ctx, T **p, u64 old_n, u64 new_n, hipStream_t st) {
     T *np_ = nullptr;
-    hipError_t e = hipMalloc((void **)&np_, std::max<u64>(new_n, 1) * sizeof(T));
+    hipError_t e = pool_malloc(ctx, &np_, std::max<u64>(new_n, 1) * sizeof(T));
     if (e != hipSuccess) return e;
     if (*p && old_n) e = hipMemcpyAsync(np_, *p, old_n * sizeof(T), hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (*p) (void)hipFree(*p);
+    (void)pool_free(ctx, *p);
     *p = np_;
     return e;
 }
@@ -1585,7 +1585,7 @@ static void edge_view(GraphView &v, char *blob, const EdgeCarve &k) {
 static void graph_free_arrays(gk_graph *g) {
     gk_ctx *ctx = g->ctx;
     GraphView &v = g->v;
-    for (void *p : {g->node_blob, g->edge_blob, (void *)v.pool, (void *)v.nidx}) if (p) (void)hipFree(p);
+    for (void *p : {g->node_blob, g->edge_blob, (void *)v.pool, (void *)v.nidx}) (void)pool_free(ctx, p);
     g->node_blob = g->edge_blob = nullptr;
     v = GraphView{};
 }
@@ -1595,7 +1595,7 @@ int graph_alloc_nodes(gk_graph *g, u64 n) {
     GraphView &v = g->v;
     const u64 c = std::max<u64>(n, 1);
     const NodeCarve k = node_carve(c);
-    GK_HIP(ctx, hipMalloc(&g->node_blob, k.total));
+    GK_HIP(ctx, pool_malloc(ctx, &g->node_blob, k.total));
     node_view(v, (char *)g->node_blob, k);
     // out_edge <- NONE (0xff..), out_order / in_deg / alive <- 0: two memsets over the two contiguous stretches
     GK_HIP(ctx, hipMemsetAsync(v.out_edge, 0xff, c * 16, ctx->stream));
@@ -1609,7 +1609,7 @@ int graph_alloc_edges(gk_graph *g, u64 n) {
     GraphView &v = g->v;
     const u64 c = std::max<u64>(n, 1);
     const EdgeCarve k = edge_carve(c);
-    GK_HIP(ctx, hipMalloc(&g->edge_blob, k.total));
+    GK_HIP(ctx, pool_malloc(ctx, &g->edge_blob, k.total));
     edge_view(v, (char *)g->edge_blob, k);
     GK_HIP(ctx, hipMemsetAsync(v.e_alive, 0, c, ctx->stream));
     v.n_edges = n;
@@ -1623,7 +1623,7 @@ static int graph_grow_edges(gk_graph *g, u64 new_n) {
     const u64 old = v.n_edges;
     const EdgeCarve k = edge_carve(new_n);
     void *blob = nullptr;
-    GK_HIP(ctx, hipMalloc(&blob, k.total));
+    GK_HIP(ctx, pool_malloc(ctx, &blob, k.total));
     GraphView nv = v;
     edge_view(nv, (char *)blob, k);
     hipError_t e = hipMemsetAsync(nv.e_alive, 0, new_n, ctx->stream);
@@ -1636,8 +1636,8 @@ static int graph_grow_edges(gk_graph *g, u64 new_n) {
         if (e == hipSuccess) e = hipMemcpyAsync(nv.e_first, v.e_first, old, hipMemcpyDeviceToDevice, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(blob); return hip_fail(ctx, e, "graph: growing the edge arrays"); }
-    (void)hipFree(g->edge_blob);
+    if (e != hipSuccess) { (void)pool_free(ctx, blob); return hip_fail(ctx, e, "graph: growing the edge arrays"); }
+    (void)pool_free(ctx, g->edge_blob);
     g->edge_blob = blob;
     v = nv;
     g->edge_cap = new_n;
@@ -1648,7 +1648,8 @@ int graph_refresh_counts(gk_graph *g) {
     gk_ctx *ctx = g->ctx;
     g->epoch++;                  // (every edit of the graph ends here or in a point edit)
     unsigned long long *d = nullptr, h[3] = {0, 0, 0};
-    GK_HIP(ctx, hipMalloc((void **)&d, 24));
+    DevScratch tmp(ctx);
+    GK_HIP(ctx, tmp.get(&d, 3));
     hipError_t e = hipMemsetAsync(d, 0, 24, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_count_live, dim3(ggrid(ctx, std::max(g->v.n_nodes, g->v.n_edges))), dim3(BLOCK), 0, ctx->stream, g->v, d);
@@ -1656,7 +1657,6 @@ int graph_refresh_counts(gk_graph *g) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(ctx, e, "graph_refresh_counts");
     g->live_nodes = h[0]; g->live_edges = h[1]; g->live_len = h[2];
     return GK_OK;
@@ -1665,9 +1665,9 @@ int graph_refresh_counts(gk_graph *g) {
 int graph_build_index(gk_graph *g) {
     gk_ctx *ctx = g->ctx;
     GraphView &v = g->v;
-    if (v.nidx) { GK_HIP(ctx, hipFree(v.nidx)); v.nidx = nullptr; }
+    if (v.nidx) { GK_HIP(ctx, pool_free(ctx, v.nidx)); v.nidx = nullptr; }
     const u64 cap = pow2ceil(std::max<u64>(16, 2 * v.n_nodes + 2));
-    GK_HIP(ctx, hipMalloc((void **)&v.nidx, cap * 4));
+    GK_HIP(ctx, pool_malloc(ctx, &v.nidx, cap * 4));
     GK_HIP(ctx, hipMemsetAsync(v.nidx, 0xff, cap * 4, ctx->stream));
     v.nidx_mask = cap - 1;
     if (v.n_nodes) {
@@ -1690,24 +1690,18 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
     u64 *tslots = nullptr;
     unsigned long long *termbits = nullptr;  // one bit per slot of the table the build reads: a terminal k-mer lives there (k_classify / k_finish_masks -> k_collect_bits)
     int rc = GK_OK;
-    hipError_t e = hipMalloc((void **)&d_cnt, 8 * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_err, 16);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&d_cnt, 8);
+    if (e == hipSuccess) e = tmp.get(&d_err, 4);
     // (a bucketed table's slot count need not be a multiple of 64: k_classify writes every word with word * 64 < tcap, the last
     //  one with zeroes above tcap — one word per STARTED group of 64 slots, here and in k_collect_bits below)
     const u64 nwords = (tcap + 63) / 64;
-    if (e == hipSuccess) e = hipMalloc((void **)&termbits, std::max<u64>(nwords, 1) * 8);
+    if (e == hipSuccess) e = tmp.get(&termbits, nwords);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, 64, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, 16, ctx->stream);
     unsigned long long h_cnt[8] = {0};
     u32 h_err = 0;
-    auto done = [&](int code) {
-        if (d_cnt) (void)hipFree(d_cnt);
-        if (d_err) (void)hipFree(d_err);
-        if (tslots) (void)hipFree(tslots);
-        if (termbits) (void)hipFree(termbits);
-        return code;
-    };
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: alloc"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: alloc");
     auto t_prev = std::chrono::steady_clock::now();
     auto lap = [&](int i) {
         const auto now = std::chrono::steady_clock::now();
@@ -1726,33 +1720,33 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: classify"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: classify");
     lap(0);
     const u64 nT = h_cnt[0];
-    if (2 * nT >= (u64)NONE) return done(fail(ctx, GK_E_CAPACITY, "more than 2^32 graph nodes"));        // (also: j < 2^31 fits AUX_NODE | j)
+    if (2 * nT >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, "more than 2^32 graph nodes");        // (also: j < 2^31 fits AUX_NODE | j)
     // 2. terminal slots -> nodes (both strands) and edge stubs
-    e = hipMalloc((void **)&tslots, std::max<u64>(nT, 1) * 8);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: alloc nodes"));
+    e = tmp.get(&tslots, nT);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: alloc nodes");
     hipLaunchKernelGGL(k_collect_bits, dim3(ggrid(ctx, nwords + 1)), dim3(BLOCK), 0, ctx->stream, termbits, nwords, tslots, &d_cnt[1]);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 24, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: collect"));
-    if (h_cnt[1] != nT) return done(fail(ctx, GK_E_STATE, "terminal count mismatch"));
-    (void)hipFree(termbits); termbits = nullptr;                 // (an eighth of a byte per slot: gone before the graph arrays exist)
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: collect");
+    if (h_cnt[1] != nT) return fail(ctx, GK_E_STATE, "terminal count mismatch");
+    tmp.release(termbits);                 // (an eighth of a byte per slot: gone before the graph arrays exist)
     const u64 nE = h_cnt[2];
-    if (nE >= (u64)NONE) return done(fail(ctx, GK_E_CAPACITY, "more than 2^32 graph edges"));
-    if ((rc = graph_alloc_nodes(g, 2 * nT)) != GK_OK) return done(rc);
-    if ((rc = graph_alloc_edges(g, nE)) != GK_OK) return done(rc);
+    if (nE >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, "more than 2^32 graph edges");
+    if ((rc = graph_alloc_nodes(g, 2 * nT)) != GK_OK) return rc;
+    if ((rc = graph_alloc_edges(g, nE)) != GK_OK) return rc;
     g->v.k = k;
     if (nT) {
         hipLaunchKernelGGL((k_make_nodes<W, TT>), dim3(ggrid(ctx, nT)), dim3(BLOCK), 0, ctx->stream, t, k, tslots, nT, g->v, &d_cnt[3]);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 32, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: make_nodes"));
+        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: make_nodes");
         // every edge slot the walk will visit must have been written by k_make_nodes
-        if (h_cnt[3] != nE) return done(fail(ctx, GK_E_STATE, "edge stub count mismatch: " + std::to_string(h_cnt[3]) + " vs " + std::to_string(nE)));
+        if (h_cnt[3] != nE) return fail(ctx, GK_E_STATE, "edge stub count mismatch: " + std::to_string(h_cnt[3]) + " vs " + std::to_string(nE));
     }
     lap(1);
     // 3. unitigs: measure, reserve the sequence pool, emit.  One lane per edge walking base by base
@@ -1764,20 +1758,16 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
         u32 *chunk_tot = nullptr;
         u64 *chunk_base = nullptr;
         ulonglong2 *stage = nullptr;           // queue-fed walk: the first WALK_BUF bases of every edge, 32 bytes each
-        auto pj_free = [&]() {
-            for (void *p : {(void *)st, (void *)rb, (void *)chunk_tot, (void *)chunk_base, (void *)stage}) if (p) (void)hipFree(p);
-            st = nullptr; rb = nullptr; chunk_tot = nullptr; chunk_base = nullptr; stage = nullptr;
-        };
         if (use_pj) {
             // what is alive here besides the table: 16 B per live key (st) + 0.25 B per slot (rb) — DESIGN.md section 6
             const u64 nstates = 2 * m->size, nblk = (tcap + 63) / 64, nchunks = (nblk + RANK_CHUNK - 1) / RANK_CHUNK;
-            if (nstates >= PJ_MAX_STATES) return done(fail(ctx, GK_E_CAPACITY, "more than 2^33 k-mers: beyond the pointer-jumping state's index"));
-            e = hipMalloc((void **)&rb, nblk * sizeof(RankBlk));
-            if (e == hipSuccess) e = hipMalloc((void **)&chunk_tot, nchunks * 4);
-            if (e == hipSuccess) e = hipMalloc((void **)&chunk_base, (nchunks + 1) * 8);
-            if (e == hipSuccess) e = hipMalloc((void **)&st, std::max<u64>(nstates, 1) * 8);
+            if (nstates >= PJ_MAX_STATES) return fail(ctx, GK_E_CAPACITY, "more than 2^33 k-mers: beyond the pointer-jumping state's index");
+            e = tmp.get(&rb, nblk);
+            if (e == hipSuccess) e = tmp.get(&chunk_tot, nchunks);
+            if (e == hipSuccess) e = tmp.get(&chunk_base, nchunks + 1);
+            if (e == hipSuccess) e = tmp.get(&st, nstates);
             if (e == hipSuccess) e = hipMemsetAsync(st, 0xff, std::max<u64>(nstates, 1) * 8, ctx->stream);         // PJ_UNREG
-            if (e != hipSuccess) { pj_free(); return done(hip_fail(ctx, e, "gk_graph_build: pointer-jumping arrays")); }
+            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: pointer-jumping arrays");
             hipLaunchKernelGGL((k_rank_masks<W, TT>), dim3((int)std::min<u64>(nchunks, (u64)ctx->cu_count * 8)), dim3(BLOCK), 0, ctx->stream, t, rb, nblk, chunk_tot, nchunks);
             hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, ctx->stream, chunk_tot, chunk_base, nchunks);
             hipLaunchKernelGGL(k_rank_fill, dim3((int)std::min<u64>(nchunks, (u64)ctx->cu_count * 8)), dim3(RANK_CHUNK), 0, ctx->stream, rb, nblk, chunk_base, nchunks);
@@ -1785,8 +1775,8 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
             e = hipGetLastError();
             if (e == hipSuccess) e = hipMemcpyAsync(&ranked, chunk_base + nchunks, 8, hipMemcpyDeviceToHost, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) { pj_free(); return done(hip_fail(ctx, e, "gk_graph_build: slot ranks")); }
-            if (ranked != m->size) { pj_free(); return done(fail(ctx, GK_E_STATE, "live slots (" + std::to_string(ranked) + ") differ from the map's size (" + std::to_string(m->size) + ")")); }
+            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: slot ranks");
+            if (ranked != m->size) return fail(ctx, GK_E_STATE, "live slots (" + std::to_string(ranked) + ") differ from the map's size (" + std::to_string(m->size) + ")");
             hipLaunchKernelGGL((k_pj_init<W, TT>), dim3(ggrid(ctx, tcap)), dim3(BLOCK), 0, ctx->stream, t, k, rb, st);
             e = hipGetLastError();
             // a chain of n k-mers is resolved after ceil(log2 n) rounds; what still moves then is an all-(1,1) cycle (Graph.scala:375)
@@ -1799,22 +1789,22 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
                 hipLaunchKernelGGL(k_pj_round, dim3(ggrid(ctx, nstates)), dim3(BLOCK), 0, ctx->stream, st, nstates, d_err + 1);
                 e = hipMemcpyAsync(flags, d_err + 1, 8, hipMemcpyDeviceToHost, ctx->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-                if (e == hipSuccess && flags[1]) { pj_free(); return done(fail(ctx, GK_E_STATE, "pointer jumping met an unregistered successor (code " + std::to_string(flags[1]) + ")")); }
+                if (e == hipSuccess && flags[1]) return fail(ctx, GK_E_STATE, "pointer jumping met an unregistered successor (code " + std::to_string(flags[1]) + ")");
                 if (!flags[0]) break;
             }
-            if (e != hipSuccess) { pj_free(); return done(hip_fail(ctx, e, "gk_graph_build: pj rounds")); }
+            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: pj rounds");
             hipLaunchKernelGGL((k_pj_edges<W, TT>), dim3(ggrid(ctx, nE)), dim3(BLOCK), 0, ctx->stream, t, k, g->v, rb, st, d_err);
         } else {
             // every oriented interior k-mer lies on exactly one edge: sum of lengths <= edges + 2 x live keys, and every edge
             // rounds up to a byte — the pool can be allocated before the walk, so the walk can write as it goes
             g->pool_cap = ((nE + 2 * m->size) / 4 + nE + 16) / 4 * 4;
-            e = hipMalloc((void **)&g->v.pool, g->pool_cap);
-            if (e != hipSuccess) { pj_free(); return done(hip_fail(ctx, e, "gk_graph_build: pool")); }
+            e = pool_malloc(ctx, &g->v.pool, g->pool_cap);
+            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: pool");
             if (ctx->hook_walk_queue == 0)        // ("graph_walk_queue": 0 = one edge per lane, the round-1 form; A/B)
                 hipLaunchKernelGGL((k_walk<W, TT>), dim3(ggrid(ctx, nE)), dim3(BLOCK), 0, ctx->stream, t, k, g->v, 0, tcap + 1, &d_cnt[4], &d_cnt[6], d_err);
             else {
-                e = hipMalloc((void **)&stage, std::max<u64>(nE, 1) * 32);
-                if (e != hipSuccess) { pj_free(); return done(hip_fail(ctx, e, "gk_graph_build: edge staging")); }
+                e = tmp.get(&stage, 2 * nE);
+                if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: edge staging");
                 const int gq = (int)std::min<u64>((nE + 4 * BLOCK - 1) / (4 * BLOCK), (u64)ctx->cu_count * 8);
                 hipLaunchKernelGGL((k_walk_q<W, TT>), dim3(std::max(gq, 1)), dim3(BLOCK), 0, ctx->stream, t, k, g->v, tcap + 1, &d_cnt[7], stage, &d_cnt[6], d_err);
                 hipLaunchKernelGGL(k_place_edges, dim3(ggrid(ctx, nE / 8 + 1)), dim3(BLOCK), 0, ctx->stream, g->v, stage, &d_cnt[4]);
@@ -1831,17 +1821,16 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
         if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 56, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { pj_free(); return done(hip_fail(ctx, e, "gk_graph_build: walk")); }
-        if (h_err) { pj_free(); return done(fail(ctx, GK_E_STATE, "unitig construction failed (code " + std::to_string(h_err) +
-                                    "): the table changed since classification or is inconsistent")); }
+        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: walk");
+        if (h_err) return fail(ctx, GK_E_STATE, "unitig construction failed (code " + std::to_string(h_err) +
+                               "): the table changed since classification or is inconsistent");
         g->pool_used = h_cnt[4];
         if (use_pj) {
             g->pool_cap = (std::max<u64>(g->pool_used, 1) + 7) / 4 * 4;        // whole 32-bit words (k_pj_emit ORs words)
-            e = hipMalloc((void **)&g->v.pool, g->pool_cap);
-            if (e != hipSuccess) { pj_free(); return done(hip_fail(ctx, e, "gk_graph_build: pool")); }
+            e = pool_malloc(ctx, &g->v.pool, g->pool_cap);
+            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: pool");
         } else if (g->pool_used > g->pool_cap) {
-            pj_free();
-            return done(fail(ctx, GK_E_STATE, "edge sequences need " + std::to_string(g->pool_used) + " bytes, bound was " + std::to_string(g->pool_cap)));
+            return fail(ctx, GK_E_STATE, "edge sequences need " + std::to_string(g->pool_used) + " bytes, bound was " + std::to_string(g->pool_cap));
         }
         lap(3);
         if (use_pj) {
@@ -1856,13 +1845,13 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        pj_free();
-        if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: emit"));
-        if (h_err) return done(fail(ctx, GK_E_STATE, "unitig emission failed (code " + std::to_string(h_err) + ")"));
+        tmp.release(st); tmp.release(rb); tmp.release(chunk_tot); tmp.release(chunk_base); tmp.release(stage);      // (not at scope exit: graph_refresh_counts follows)
+        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: emit");
+        if (h_err) return fail(ctx, GK_E_STATE, "unitig emission failed (code " + std::to_string(h_err) + ")");
         lap(4);
     } else {
-        e = hipMalloc((void **)&g->v.pool, 1);
-        if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: pool"));
+        e = pool_malloc(ctx, &g->v.pool, 1);
+        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: pool");
         g->pool_cap = 1;
     }
     // (the k-mer -> node index serves point queries and by-k-mer edits only — GraphBuilder's own flow, components, the export and
@@ -1871,7 +1860,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
     rc = graph_refresh_counts(g);
     g->walked_bases = g->live_len;
     lap(5);
-    return done(rc);
+    return rc;
 }
 
 template <int W> __global__ __launch_bounds__(BLOCK) void k_mb_clear(Slot<W> *slots, u64 n) {
@@ -1935,26 +1924,23 @@ template <int W> static int graph_build_entry(gk_map *m, gk_graph *g, bool masks
     unsigned long long *d_off = nullptr, total = 0;
     u64 *d_sums = nullptr;
     Slot<W> *slots = nullptr;
-    auto done = [&](int code) {
-        for (void *p : {(void *)d_cnt, (void *)d_bucket, (void *)d_err, (void *)d_off, (void *)d_sums, (void *)slots}) if (p) (void)hipFree(p);
-        return code;
-    };
-    hipError_t e = hipMalloc((void **)&d_cnt, (u64)nb * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_bucket, m->capacity * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_off, ((u64)nb + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_sums, ((u64)nb / SCAN_CHUNK + 2) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_err, 4);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&d_cnt, nb);
+    if (e == hipSuccess) e = tmp.get(&d_bucket, m->capacity);
+    if (e == hipSuccess) e = tmp.get(&d_off, (u64)nb + 1);
+    if (e == hipSuccess) e = tmp.get(&d_sums, (u64)nb / SCAN_CHUNK + 2);
+    if (e == hipSuccess) e = tmp.get(&d_err, 1);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (u64)nb * 4, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, 4, ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: bucketed table"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: bucketed table");
     hipLaunchKernelGGL(k_mb_count<W>, dim3(ggrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, t, m->k, nb, d_cnt, d_bucket);
     hipLaunchKernelGGL(k_mb_sizes, dim3(ggrid(ctx, nb)), dim3(BLOCK), 0, ctx->stream, d_cnt, nb);
     e = scan_counts(ctx, d_cnt, nb, d_off, d_sums);
     if (e == hipSuccess) e = hipMemcpyAsync(&total, d_off + nb, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: bucket regions"));
-    e = hipMalloc((void **)&slots, total * sizeof(Slot<W>));
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: bucketed table"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: bucket regions");
+    e = tmp.get(&slots, total);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: bucketed table");
     hipLaunchKernelGGL(k_mb_clear<W>, dim3(ggrid(ctx, total / 4 + 1)), dim3(BLOCK), 0, ctx->stream, slots, (u64)total);
     MbTable<W> mt{slots, reinterpret_cast<const u64 *>(d_off), nb, m->dirty ? 1u : 0u, (u64)total};
     hipLaunchKernelGGL(k_mb_fill<W>, dim3(ggrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, t, d_bucket, mt, d_err);
@@ -1962,13 +1948,13 @@ template <int W> static int graph_build_entry(gk_map *m, gk_graph *g, bool masks
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_build: filling the bucketed table"));
-    if (h_err) return done(fail(ctx, GK_E_STATE, "gk_graph_build: a bucket region filled up (internal sizing error)"));
-    (void)hipFree(d_bucket); d_bucket = nullptr;
-    (void)hipFree(d_cnt); d_cnt = nullptr;
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: filling the bucketed table");
+    if (h_err) return fail(ctx, GK_E_STATE, "gk_graph_build: a bucket region filled up (internal sizing error)");
+    tmp.release(d_bucket);
+    tmp.release(d_cnt);
     g->mbt_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     g->mbt_slots = total;
-    return done(graph_build_impl<W, MbTable<W>>(m, g, mt));
+    return graph_build_impl<W, MbTable<W>>(m, g, mt);
 }
 
 int check_graph(const gk_graph *g) {
@@ -2031,22 +2017,15 @@ int gk_graph_simplify(gk_graph *g) {
     uint8_t *cls = nullptr;
     unsigned long long *d_cnt = nullptr, h_cnt[3] = {0, 0, 0};
     LongPiece *long_pieces = nullptr;
-    auto done = [&](int code) {
-        if (in_single) (void)hipFree(in_single);
-        if (merged_key) (void)hipFree(merged_key);
-        if (cls) (void)hipFree(cls);
-        if (d_cnt) (void)hipFree(d_cnt);
-        if (long_pieces) (void)hipFree(long_pieces);
-        return code;
-    };
-    hipError_t e = hipMalloc((void **)&in_single, v.n_nodes * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&merged_key, v.n_nodes * 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&cls, v.n_nodes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cnt, 24);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&in_single, v.n_nodes);
+    if (e == hipSuccess) e = tmp.get(&merged_key, v.n_nodes * 4);
+    if (e == hipSuccess) e = tmp.get(&cls, v.n_nodes);
+    if (e == hipSuccess) e = tmp.get(&d_cnt, 3);
     if (e == hipSuccess) e = hipMemsetAsync(in_single, 0xff, v.n_nodes * 4, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(merged_key, 0xff, v.n_nodes * 16, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, 24, ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_simplify: alloc"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: alloc");
     const int gn = ggrid(ctx, v.n_nodes), ge = ggrid(ctx, std::max<u64>(v.n_edges, 1));
     hipLaunchKernelGGL(k_in_single, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, in_single);
     hipLaunchKernelGGL(k_node_class, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, in_single, cls);
@@ -2055,21 +2034,21 @@ int gk_graph_simplify(gk_graph *g) {
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 24, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_simplify: count"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: count");
     if (h_cnt[0]) {
-        if (old_edges + h_cnt[0] >= (u64)NONE) return done(fail(ctx, GK_E_CAPACITY, "more than 2^32 graph edges"));
-        if (int rc = graph_grow_edges(g, old_edges + h_cnt[0])) return done(rc);
+        if (old_edges + h_cnt[0] >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, "more than 2^32 graph edges");
+        if (int rc = graph_grow_edges(g, old_edges + h_cnt[0])) return rc;
         if (old_pool + h_cnt[1] + 8 > g->pool_cap) {             // (+8: k_copy_long ORs whole 32-bit words, the last one may reach past the last byte)
             e = dev_grow(ctx, &v.pool, old_pool, old_pool + h_cnt[1] + 8, ctx->stream);
-            if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_simplify: pool"));
+            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: pool");
             g->pool_cap = old_pool + h_cnt[1] + 8;
         }
         e = hipMemsetAsync(d_cnt, 0, 24, ctx->stream);
         if (e == hipSuccess && h_cnt[2]) {                       // long pieces are ORed into their place: it starts as zeroes
-            e = hipMalloc((void **)&long_pieces, h_cnt[2] * sizeof(LongPiece));
+            e = tmp.get(&long_pieces, h_cnt[2]);
             if (e == hipSuccess) e = hipMemsetAsync(v.pool + old_pool, 0, h_cnt[1], ctx->stream);
         }
-        if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_simplify"));
+        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify");
         hipLaunchKernelGGL(k_chain, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, cls, 1, old_edges, old_pool, d_cnt, merged_key, long_pieces);
         if (h_cnt[2]) hipLaunchKernelGGL(k_copy_long, dim3((unsigned)h_cnt[2]), dim3(BLOCK), 0, ctx->stream, v, long_pieces);
         v.n_edges = old_edges + h_cnt[0];
@@ -2078,8 +2057,8 @@ int gk_graph_simplify(gk_graph *g) {
     hipLaunchKernelGGL(k_simplify_finish, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, cls, merged_key);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_simplify: finish"));
-    return done(graph_refresh_counts(g));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: finish");
+    return graph_refresh_counts(g);
 }
 
 int gk_graph_remove_bubbles(gk_graph *g) {
@@ -2102,10 +2081,11 @@ int gk_graph_remove_edges(gk_graph *g, const uint64_t *start_lo, const uint64_t 
     u64 *d_lo = nullptr, *d_hi = nullptr;
     uint8_t *d_b = nullptr;
     unsigned long long *d_rm = nullptr, h_rm = 0;
-    hipError_t e = hipMalloc((void **)&d_lo, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_hi, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_b, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_rm, 8);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&d_lo, n);
+    if (e == hipSuccess) e = tmp.get(&d_hi, n);
+    if (e == hipSuccess) e = tmp.get(&d_b, n);
+    if (e == hipSuccess) e = tmp.get(&d_rm, 1);
     if (e == hipSuccess) e = hipMemcpyAsync(d_lo, start_lo, n * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = start_hi ? hipMemcpyAsync(d_hi, start_hi, n * 8, hipMemcpyHostToDevice, ctx->stream)
                                       : hipMemsetAsync(d_hi, 0, n * 8, ctx->stream);
@@ -2118,7 +2098,6 @@ int gk_graph_remove_edges(gk_graph *g, const uint64_t *start_lo, const uint64_t 
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_rm, d_rm, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_lo); (void)hipFree(d_hi); (void)hipFree(d_b); (void)hipFree(d_rm);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_remove_edges");
     if (removed) *removed = h_rm;
     return graph_refresh_counts(g);
@@ -2174,20 +2153,16 @@ int dclass_apply(gk_map *m, const u64 *d_qref, const uint8_t *d_ans, u64 n) {
 }  // namespace gk
 
 // Graph.components (Graph.scala:54-72): label every live node with its component's root (min-label hooking + pointer
-// jumping) and count nodes per root.  *parent / *size are hipMalloc'ed here ([n_nodes] each); the caller frees them.
-static int graph_components(gk_graph *g, u32 **parent_out, u32 **size_out, u64 *ncomp) {
+// jumping) and count nodes per root.  *parent / *size ([n_nodes] each) come from the caller's `tmp` and live as long as it does.
+static int graph_components(gk_graph *g, DevScratch &tmp, u32 **parent_out, u32 **size_out, u64 *ncomp) {
     gk_ctx *ctx = g->ctx;
     GraphView &v = g->v;
     u32 *parent = nullptr, *size = nullptr;
     unsigned long long *d_ncomp = nullptr;
-    auto bail = [&](int code) {
-        for (void *p : {(void *)parent, (void *)size, (void *)d_ncomp}) if (p) (void)hipFree(p);
-        return code;
-    };
-    hipError_t e = hipMalloc((void **)&parent, std::max<u64>(v.n_nodes, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&size, std::max<u64>(v.n_nodes, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_ncomp, 8);
-    if (e != hipSuccess) return bail(hip_fail(ctx, e, "graph components: alloc"));
+    hipError_t e = tmp.get(&parent, v.n_nodes);
+    if (e == hipSuccess) e = tmp.get(&size, v.n_nodes);
+    if (e == hipSuccess) e = tmp.get(&d_ncomp, 1);
+    if (e != hipSuccess) return hip_fail(ctx, e, "graph components: alloc");
     const int gn = ggrid(ctx, std::max<u64>(v.n_nodes, 1)), ge = ggrid(ctx, std::max<u64>(v.n_edges, 1));
     hipLaunchKernelGGL(k_cc_init, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, parent);
     if (ctx->hook_cc_find == 1) hipLaunchKernelGGL(k_cc_link<1>, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, parent);
@@ -2195,7 +2170,7 @@ static int graph_components(gk_graph *g, u32 **parent_out, u32 **size_out, u64 *
     else if (ctx->hook_cc_find == 2) hipLaunchKernelGGL(k_cc_link<2>, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, parent);
     else hipLaunchKernelGGL(k_cc_link<0>, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, parent);
     e = hipGetLastError();
-    if (e != hipSuccess) return bail(hip_fail(ctx, e, "graph components: hooking"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "graph components: hooking");
     unsigned long long h = 0;
     e = hipMemsetAsync(size, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_ncomp, 0, 8, ctx->stream);
@@ -2205,8 +2180,8 @@ static int graph_components(gk_graph *g, u32 **parent_out, u32 **size_out, u64 *
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h, d_ncomp, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return bail(hip_fail(ctx, e, "graph components: sizes"));
-    (void)hipFree(d_ncomp);
+    if (e != hipSuccess) return hip_fail(ctx, e, "graph components: sizes");
+    tmp.release(d_ncomp);
     *parent_out = parent; *size_out = size; *ncomp = h;
     return GK_OK;
 }
@@ -2223,23 +2198,17 @@ int gk_graph_retain_largest(gk_graph *g, uint64_t *kept_nodes, uint64_t *compone
     u32 *parent = nullptr, *size = nullptr, *d_u32 = nullptr;       // d_u32: [0] unused [1] best [2] winner
     unsigned long long *d_u64 = nullptr;                            // [0] unused [1] min hi [2] min lo
     u64 ncomp = 0;
-    if (int rc = graph_components(g, &parent, &size, &ncomp)) return rc;
-    auto done = [&](int code) {
-        if (parent) (void)hipFree(parent);
-        if (size) (void)hipFree(size);
-        if (d_u32) (void)hipFree(d_u32);
-        if (d_u64) (void)hipFree(d_u64);
-        return code;
-    };
-    hipError_t e = hipMalloc((void **)&d_u32, 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_u64, 24);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_retain_largest: alloc"));
+    DevScratch tmp(ctx);
+    if (int rc = graph_components(g, tmp, &parent, &size, &ncomp)) return rc;
+    hipError_t e = tmp.get(&d_u32, 4);
+    if (e == hipSuccess) e = tmp.get(&d_u64, 3);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest: alloc");
     const int gn = ggrid(ctx, v.n_nodes);
     unsigned long long h64[3] = {0, ~0ull, ~0ull};
     u32 h32[3] = {0, 0, NONE};
     e = hipMemcpyAsync(d_u64, h64, 24, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_u32, h32, 12, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_retain_largest"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest");
     // max size -> smallest k-mer among the components of that size -> its root -> retain: four dependent steps, no host in between
     hipLaunchKernelGGL(k_cc_max, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, size, &d_u32[1]);
     for (int stage = 0; stage < 3; stage++)
@@ -2248,12 +2217,12 @@ int gk_graph_retain_largest(gk_graph *g, uint64_t *kept_nodes, uint64_t *compone
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h32, d_u32, 12, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_retain_largest: retain"));
-    if (h32[2] == NONE) return done(fail(ctx, GK_E_STATE, "no component selected"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest: retain");
+    if (h32[2] == NONE) return fail(ctx, GK_E_STATE, "no component selected");
     if (components) *components = ncomp;
     int rc = graph_refresh_counts(g);
     if (rc == GK_OK && kept_nodes) *kept_nodes = g->live_nodes;
-    return done(rc);
+    return rc;
 }
 
 int gk_graph_component_stats(gk_graph *g, uint32_t *nodes_per_component, uint64_t *edge_len_per_component, uint64_t cap, uint64_t *n) {
@@ -2265,36 +2234,34 @@ int gk_graph_component_stats(gk_graph *g, uint32_t *nodes_per_component, uint64_
     u32 *parent = nullptr, *size = nullptr, *d_nodes = nullptr;
     unsigned long long *len = nullptr, *d_len = nullptr, *d_cur = nullptr;
     u64 ncomp = 0;
-    if (int rc = graph_components(g, &parent, &size, &ncomp)) return rc;
-    auto done = [&](int code) {
-        for (void *p : {(void *)parent, (void *)size, (void *)d_nodes, (void *)len, (void *)d_len, (void *)d_cur}) if (p) (void)hipFree(p);
-        return code;
-    };
+    DevScratch tmp(ctx);
+    if (int rc = graph_components(g, tmp, &parent, &size, &ncomp)) return rc;
     if (n) *n = ncomp;
-    if (ncomp > cap) return done(fail(ctx, GK_E_CAPACITY, "component buffer too small: need " + std::to_string(ncomp)));
-    if (!nodes_per_component || !edge_len_per_component) return done(fail(ctx, GK_E_INVALID, "null component buffer"));
-    hipError_t e = hipMalloc((void **)&len, v.n_nodes * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_nodes, ncomp * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_len, ncomp * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cur, 8);
+    if (ncomp > cap) return fail(ctx, GK_E_CAPACITY, "component buffer too small: need " + std::to_string(ncomp));
+    if (!nodes_per_component || !edge_len_per_component) return fail(ctx, GK_E_INVALID, "null component buffer");
+    hipError_t e = tmp.get(&len, v.n_nodes);
+    if (e == hipSuccess) e = tmp.get(&d_nodes, ncomp);
+    if (e == hipSuccess) e = tmp.get(&d_len, ncomp);
+    if (e == hipSuccess) e = tmp.get(&d_cur, 1);
     if (e == hipSuccess) e = hipMemsetAsync(len, 0, v.n_nodes * 8, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 8, ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_component_stats: alloc"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_component_stats: alloc");
     hipLaunchKernelGGL(k_cc_edge_len, dim3(ggrid(ctx, std::max<u64>(v.n_edges, 1))), dim3(BLOCK), 0, ctx->stream, v, parent, len);
     hipLaunchKernelGGL(k_cc_collect, dim3(ggrid(ctx, v.n_nodes)), dim3(BLOCK), 0, ctx->stream, v, parent, size, len, d_nodes, d_len, d_cur);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(nodes_per_component, d_nodes, ncomp * 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(edge_len_per_component, d_len, ncomp * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_component_stats"));
-    return done(GK_OK);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_component_stats");
+    return GK_OK;
 }
 
 int gk_graph_checksum(gk_graph *g, uint64_t *nodes_checksum, uint64_t *edges_checksum) {
     if (int rc = check_graph(g)) return rc;
     gk_ctx *ctx = g->ctx;
     unsigned long long *d = nullptr, h[2] = {0, 0};
-    GK_HIP(ctx, hipMalloc((void **)&d, 16));
+    DevScratch tmp(ctx);
+    GK_HIP(ctx, tmp.get(&d, 2));
     hipError_t e = hipMemsetAsync(d, 0, 16, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_graph_checksum, dim3(ggrid(ctx, std::max<u64>(std::max(g->v.n_nodes, g->v.n_edges), 1))), dim3(BLOCK), 0, ctx->stream, g->v, d);
@@ -2302,7 +2269,6 @@ int gk_graph_checksum(gk_graph *g, uint64_t *nodes_checksum, uint64_t *edges_che
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_checksum");
     if (nodes_checksum) *nodes_checksum = h[0];
     if (edges_checksum) *edges_checksum = h[1];
@@ -2340,9 +2306,10 @@ int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap,
     const u64 cnt = g->live_nodes;
     u64 *d_lo = nullptr, *d_hi = nullptr;
     unsigned long long *d_cur = nullptr;
-    hipError_t e = hipMalloc((void **)&d_lo, cnt * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_hi, cnt * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cur, 8);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&d_lo, cnt);
+    if (e == hipSuccess) e = tmp.get(&d_hi, cnt);
+    if (e == hipSuccess) e = tmp.get(&d_cur, 1);
     if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 8, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_export_nodes, dim3(ggrid(ctx, g->v.n_nodes)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_cur);
@@ -2351,7 +2318,6 @@ int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap,
     if (e == hipSuccess) e = hipMemcpyAsync(lo, d_lo, cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && hi) e = hipMemcpyAsync(hi, d_hi, cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_lo); (void)hipFree(d_hi); (void)hipFree(d_cur);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_export_nodes");
     return GK_OK;
 }
@@ -2374,12 +2340,13 @@ int gk_graph_export_edges(gk_graph *g, uint64_t *start_lo, uint64_t *start_hi, u
     i64 *d_len = nullptr, *d_off = nullptr;
     uint8_t *d_seq = nullptr;
     unsigned long long *d_cur = nullptr, h_cur[2] = {0, 0};
+    DevScratch tmp(ctx);
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipMalloc((void **)&d_k[i], cnt * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_len, cnt * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_off, cnt * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_seq, max_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cur, 16);
+    for (int i = 0; i < 4 && e == hipSuccess; i++) e = tmp.get(&d_k[i], cnt);
+    if (e == hipSuccess) e = tmp.get(&d_len, cnt);
+    if (e == hipSuccess) e = tmp.get(&d_off, cnt);
+    if (e == hipSuccess) e = tmp.get(&d_seq, max_bytes);
+    if (e == hipSuccess) e = tmp.get(&d_cur, 2);
     if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 16, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_export_edges, dim3(ggrid(ctx, g->v.n_edges)), dim3(BLOCK), 0, ctx->stream, g->v, d_k[0], d_k[1], d_k[2],
@@ -2395,8 +2362,6 @@ int gk_graph_export_edges(gk_graph *g, uint64_t *start_lo, uint64_t *start_hi, u
     if (e == hipSuccess) e = hipMemcpyAsync(seq_off, d_off, cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess && h_cur[1]) e = hipMemcpy(seq2bit, d_seq, h_cur[1], hipMemcpyDeviceToHost);
-    for (int i = 0; i < 4; i++) (void)hipFree(d_k[i]);
-    (void)hipFree(d_len); (void)hipFree(d_off); (void)hipFree(d_seq); (void)hipFree(d_cur);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_export_edges");
     if (h_cur[0] != cnt) return fail(ctx, GK_E_STATE, "edge export count mismatch");
     if (seq_bytes) *seq_bytes = h_cur[1];
@@ -2409,13 +2374,13 @@ int gk_graph_out_order(gk_graph *g, uint64_t lo, uint64_t hi, int *bases4, int *
     if (!bases4 || !count) return fail(ctx, GK_E_INVALID, "null argument");
     if (int rc = graph_ensure_index(g)) return rc;
     int *d = nullptr, h[5] = {-1, 0, 0, 0, 0};
-    GK_HIP(ctx, hipMalloc((void **)&d, 20));
+    DevScratch tmp(ctx);
+    GK_HIP(ctx, tmp.get(&d, 5));
     if (g->W == 1) hipLaunchKernelGGL(k_out_order<1>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, d);
     else hipLaunchKernelGGL(k_out_order<2>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, d);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h, d, 20, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_out_order");
     *count = h[0];
     for (int i = 0; i < 4; i++) bases4[i] = i < h[0] ? h[1 + i] : 0;
@@ -2430,7 +2395,7 @@ int graph_grow_nodes(gk_graph *g, u64 new_cap) {
     const u64 old = v.n_nodes;
     const NodeCarve k = node_carve(new_cap);
     void *blob = nullptr;
-    GK_HIP(ctx, hipMalloc(&blob, k.total));
+    GK_HIP(ctx, pool_malloc(ctx, &blob, k.total));
     GraphView nv = v;
     node_view(nv, (char *)blob, k);
     hipError_t e = hipMemsetAsync(nv.node_alive, 0, new_cap, ctx->stream);
@@ -2443,8 +2408,8 @@ int graph_grow_nodes(gk_graph *g, u64 new_cap) {
         if (e == hipSuccess) e = hipMemcpyAsync(nv.in_deg, v.in_deg, old * 4, hipMemcpyDeviceToDevice, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(blob); return hip_fail(ctx, e, "graph: growing the node arrays"); }
-    (void)hipFree(g->node_blob);
+    if (e != hipSuccess) { (void)pool_free(ctx, blob); return hip_fail(ctx, e, "graph: growing the node arrays"); }
+    (void)pool_free(ctx, g->node_blob);
     g->node_blob = blob;
     v = nv;
     g->node_cap = new_cap;
@@ -2463,28 +2428,25 @@ int gk_graph_position_map(gk_graph *g, gk_vmap *vm, uint64_t *entries) {
     GraphView &v = g->v;
     unsigned long long *first = nullptr, *d_cur = nullptr, h_cur[2] = {0, 0};
     u64 *lo = nullptr, *hi = nullptr, *val = nullptr;
-    auto done = [&](int code) {
-        for (void *p : {(void *)first, (void *)d_cur, (void *)lo, (void *)hi, (void *)val}) if (p) (void)hipFree(p);
-        return code;
-    };
-    hipError_t e = hipMalloc((void **)&first, std::max<u64>(v.n_edges, 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cur, 16);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&first, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&d_cur, 2);
     if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 16, ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_position_map: alloc"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: alloc");
     if (v.n_edges) hipLaunchKernelGGL(k_pos_reserve, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, first, &d_cur[0]);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_cur, d_cur, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_position_map: reserve"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: reserve");
     // the reference's own check, printed side by side at :117: size == sum of edge lengths + nodes - edges
     const u64 total = g->live_nodes + h_cur[0];
-    if (h_cur[0] != g->live_len - g->live_edges) return done(fail(ctx, GK_E_STATE, "gk_graph_position_map: interior k-mer count does not match the graph's counters"));
-    if (total == 0) return done(GK_OK);
-    e = hipMalloc((void **)&lo, total * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&hi, total * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&val, total * 8);
+    if (h_cur[0] != g->live_len - g->live_edges) return fail(ctx, GK_E_STATE, "gk_graph_position_map: interior k-mer count does not match the graph's counters");
+    if (total == 0) return GK_OK;
+    e = tmp.get(&lo, total);
+    if (e == hipSuccess) e = tmp.get(&hi, total);
+    if (e == hipSuccess) e = tmp.get(&val, total);
     if (e == hipSuccess && g->W == 1) e = hipMemsetAsync(hi, 0, total * 8, ctx->stream);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_position_map: entries"));
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: entries");
     hipLaunchKernelGGL(k_pos_nodes, dim3(ggrid(ctx, std::max<u64>(v.n_nodes, 1))), dim3(BLOCK), 0, ctx->stream, v, lo, hi, val, &d_cur[1]);
     if (v.n_edges) {
         if (g->W == 1) {
@@ -2496,10 +2458,10 @@ int gk_graph_position_map(gk_graph *g, gk_vmap *vm, uint64_t *entries) {
         }
     }
     e = hipGetLastError();
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_graph_position_map: fill"));
-    if (int rc = vmap_put_new_dev(vm, lo, hi, val, total)) return done(rc);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: fill");
+    if (int rc = vmap_put_new_dev(vm, lo, hi, val, total)) return rc;
     if (entries) *entries = total;
-    return done(GK_OK);
+    return GK_OK;
 }
 
 // first live node holding this k-mer (NONE = 0xffffffff if there is none) and, if base is 0..3, its out-edge for that first base
@@ -2508,13 +2470,13 @@ int gk_graph_node_lookup(gk_graph *g, uint64_t lo, uint64_t hi, int base, uint32
     gk_ctx *ctx = g->ctx;
     if (int rc = graph_ensure_index(g)) return rc;
     u32 *d = nullptr, h[2] = {NONE, NONE};
-    GK_HIP(ctx, hipMalloc((void **)&d, 8));
+    DevScratch tmp(ctx);
+    GK_HIP(ctx, tmp.get(&d, 2));
     if (g->W == 1) hipLaunchKernelGGL(k_node_lookup<1>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, base, d);
     else hipLaunchKernelGGL(k_node_lookup<2>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, base, d);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h, d, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_node_lookup");
     if (node_id) *node_id = h[0];
     if (edge_id) *edge_id = h[1];
@@ -2554,13 +2516,13 @@ static int graph_point_edit(gk_graph *g, bool start, uint32_t edge_id, uint32_t 
     gk_ctx *ctx = g->ctx;
     g->epoch++;
     int *d = nullptr, h = 1;
-    GK_HIP(ctx, hipMalloc((void **)&d, 4));
+    DevScratch tmp(ctx);
+    GK_HIP(ctx, tmp.get(&d, 1));
     if (start) hipLaunchKernelGGL(k_replace_start, dim3(1), dim3(1), 0, ctx->stream, g->v, edge_id, node_id, d);
     else hipLaunchKernelGGL(k_replace_end, dim3(1), dim3(1), 0, ctx->stream, g->v, edge_id, node_id, d);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return hip_fail(ctx, e, "graph edit");
     if (h) return fail(ctx, GK_E_INVALID, std::string(start ? "gk_graph_replace_start" : "gk_graph_replace_end") + ": no such live edge / node");
     return GK_OK;
@@ -2576,12 +2538,13 @@ int gk_graph_nodes_by_id(gk_graph *g, const uint32_t *ids, uint64_t n, uint64_t 
     u32 *d_ids = nullptr, *d_in = nullptr, *d_out = nullptr;
     u64 *d_lo = nullptr, *d_hi = nullptr;
     uint8_t *d_al = nullptr;
-    hipError_t e = hipMalloc((void **)&d_ids, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_in, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_lo, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_hi, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_al, n);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&d_ids, n);
+    if (e == hipSuccess) e = tmp.get(&d_in, n);
+    if (e == hipSuccess) e = tmp.get(&d_out, n);
+    if (e == hipSuccess) e = tmp.get(&d_lo, n);
+    if (e == hipSuccess) e = tmp.get(&d_hi, n);
+    if (e == hipSuccess) e = tmp.get(&d_al, n);
     if (e == hipSuccess) e = hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_nodes_by_id, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_ids, n, d_lo, d_hi, d_al, d_in, d_out);
@@ -2593,7 +2556,6 @@ int gk_graph_nodes_by_id(gk_graph *g, const uint32_t *ids, uint64_t n, uint64_t 
     if (e == hipSuccess) e = hipMemcpyAsync(in_deg, d_in, n * 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out_deg, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    for (void *p : {(void *)d_ids, (void *)d_in, (void *)d_out, (void *)d_lo, (void *)d_hi, (void *)d_al}) if (p) (void)hipFree(p);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_nodes_by_id");
     return GK_OK;
 }
@@ -2606,12 +2568,13 @@ int gk_graph_edges_by_id(gk_graph *g, const uint32_t *ids, uint64_t n, uint32_t 
     u32 *d_ids = nullptr, *d_s = nullptr, *d_e = nullptr;
     u64 *d_len = nullptr;
     uint8_t *d_f = nullptr, *d_al = nullptr;
-    hipError_t e = hipMalloc((void **)&d_ids, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_s, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_e, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_len, n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_f, n);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_al, n);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&d_ids, n);
+    if (e == hipSuccess) e = tmp.get(&d_s, n);
+    if (e == hipSuccess) e = tmp.get(&d_e, n);
+    if (e == hipSuccess) e = tmp.get(&d_len, n);
+    if (e == hipSuccess) e = tmp.get(&d_f, n);
+    if (e == hipSuccess) e = tmp.get(&d_al, n);
     if (e == hipSuccess) e = hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_edges_by_id, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_ids, n, d_s, d_e, d_len, d_f, d_al);
@@ -2623,7 +2586,6 @@ int gk_graph_edges_by_id(gk_graph *g, const uint32_t *ids, uint64_t n, uint32_t 
     if (e == hipSuccess) e = hipMemcpyAsync(first_base, d_f, n, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(alive, d_al, n, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    for (void *p : {(void *)d_ids, (void *)d_s, (void *)d_e, (void *)d_len, (void *)d_f, (void *)d_al}) if (p) (void)hipFree(p);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edges_by_id");
     return GK_OK;
 }

@@ -92,18 +92,6 @@ void header_encode(const Header &h, uint8_t *b) {
     put64(b + 56, h.cs_nodes); put64(b + 64, h.cs_edges); put64(b + 72, h.fp);
 }
 
-struct Tmp {      // device arrays of one call, freed together
-    gk_ctx *ctx;
-    std::vector<void *> ptrs;
-    explicit Tmp(gk_ctx *c) : ctx(c) {}
-    ~Tmp() { for (void *p : ptrs) if (p) (void)hipFree(p); }
-    template <class T> hipError_t get(T **p, u64 n) {
-        hipError_t e = hipMalloc((void **)p, std::max<u64>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
 // two pinned staging buffers and their "copy done" events
 struct Stage {
     gk_ctx *ctx;
@@ -304,7 +292,7 @@ int graph_save_impl(gk_graph *g, const std::string &path, const std::string &tmp
     if (int rc = gk_graph_checksum(g, &h.cs_nodes, &h.cs_edges)) return rc;
     if (int rc = gk_graph_id_fingerprint(g, &h.fp)) return rc;
     // live flags -> ranks (record slots) and pool offsets
-    Tmp tmp_(ctx);
+    DevScratch tmp_(ctx);
     const u64 nn = v.n_nodes, ne = v.n_edges;
     u32 *nlive = nullptr, *elive = nullptr, *ebytes = nullptr;
     unsigned long long *nrank = nullptr, *erank = nullptr, *poff = nullptr;
@@ -438,10 +426,10 @@ int graph_load_impl(gk_ctx *ctx, const std::string &path, gk_graph *g, float *ms
     // the pool: whole 32-bit words and 8 bytes of slack (k_copy_long / k_pj_emit OR whole words), zeroed
     g->pool_used = h.pool_bytes;
     g->pool_cap = (h.pool_bytes + 8 + 3) / 4 * 4;
-    GK_HIP(ctx, hipMalloc((void **)&v.pool, g->pool_cap));
+    GK_HIP(ctx, pool_malloc(ctx, &v.pool, g->pool_cap));
     GK_HIP(ctx, hipMemsetAsync(v.pool, 0, g->pool_cap, ctx->stream));
     // records -> scratch, pool -> v.pool: chunk c + 1 is read while chunk c uploads
-    Tmp tmp_(ctx);
+    DevScratch tmp_(ctx);
     const u64 rec_bytes = L.pool - GIO_HEADER, body = L.end - GIO_HEADER;
     uint8_t *d_rec = nullptr;
     GK_HIP(ctx, tmp_.get(&d_rec, rec_bytes + 8));

@@ -110,12 +110,38 @@ int stage_source(gk_ctx *ctx, const ReadSrc &src);      // upload a host-fed sou
 namespace gk {
 struct PartScratch;
 // pooled device memory of a context (blocks of 1 MiB and more; smaller requests go straight to hipMalloc).  pool_free waits
-// for the context's two streams first, like the hipFree it replaces.  hipErrorOutOfMemory only after the pool was emptied.
+// for the context's streams first, like the hipFree it replaces.  hipErrorOutOfMemory only after the pool was emptied.
+// Every device allocation of the library is made here, by name: outside these three functions nothing calls the runtime's
+// hipMalloc / hipFree (a site that did would work, and pay milliseconds to seconds for every large block).
 hipError_t pool_malloc(gk_ctx *ctx, void **p, size_t bytes);
 hipError_t pool_free(gk_ctx *ctx, void *p);
 void pool_release(gk_ctx *ctx);                              // hipFree everything parked
 size_t mem_available(gk_ctx *ctx);                           // free + parked, or what the caller's budget leaves
 double graph_table_load(gk_ctx *ctx, int k, uint64_t keys);  // load factor of a table the graph phase will read
+template <class T> inline hipError_t pool_malloc(gk_ctx *ctx, T **p, size_t bytes) { return pool_malloc(ctx, (void **)p, bytes); }
+
+// Device buffers of one call: whatever get() handed out is freed when the owner goes out of scope, on every return path.
+// release() frees one buffer early (the pool's peak depends on where that happens), take() hands one over to a longer-lived
+// owner.  pool_free waits for the context's streams, so a scope must not end while another stream's work still reads a buffer.
+struct __attribute__((visibility("hidden"))) DevScratch {      // (internal: its instantiations are not exported)
+    gk_ctx *ctx;
+    std::vector<void *> ptrs;
+    explicit DevScratch(gk_ctx *c) : ctx(c) {}
+    DevScratch(const DevScratch &) = delete;
+    DevScratch &operator=(const DevScratch &) = delete;
+    ~DevScratch() { for (void *p : ptrs) (void)pool_free(ctx, p); }
+    template <class T> hipError_t get(T **p, uint64_t n) {      // n elements (at least one); *p == nullptr on failure
+        const hipError_t e = pool_malloc(ctx, p, (n ? n : 1) * sizeof(T));
+        if (e == hipSuccess) ptrs.push_back(*p);
+        else { *p = nullptr; (void)hipGetLastError(); }
+        return e;
+    }
+    template <class T> T *take(T *p) {                          // forget p without freeing it
+        for (size_t i = 0; i < ptrs.size(); i++) if (ptrs[i] == p) { ptrs.erase(ptrs.begin() + i); break; }
+        return p;
+    }
+    template <class T> void release(T *&p) { (void)pool_free(ctx, take(p)); p = nullptr; }
+};
 }
 
 struct gk_map {
@@ -330,11 +356,3 @@ void part_scratch_free(gk_ctx *ctx, PartScratch *ps);
 #define GK_TICK(i) do {} while (0)
 #define GK_TFLUSH(base) do {} while (0)
 #endif
-
-// Inside the library every device allocation goes through the context's block pool: the HIP names are redirected here, and a
-// translation unit that really means the runtime's own writes (hipMalloc)(...) / (hipFree)(...).  Needs `ctx` in scope.
-#ifndef GK_NO_POOL_REDIRECT
-#define hipMalloc(p, n) gk::pool_malloc(ctx, (void **)(p), (size_t)(n))
-#define hipFree(p) gk::pool_free(ctx, (void *)(p))
-#endif
-

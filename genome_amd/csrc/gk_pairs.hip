@@ -17,7 +17,7 @@
 // orientation goes to an overflow list and the host walker (the round-2 form, kept below) does it — exact either way.
 // Round 2 ran ALL walks on <= 16 host threads over a snapshot: 1.0-1.5e7 pairs/s, ten times everything before it at C3.
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>          // (first: gk_internal.h maps hipMalloc / hipFree onto the context's block pool by macro)
+#include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -703,18 +703,6 @@ inline void revcomp_host(u64 lo, u64 hi, int k, u64 &rlo, u64 &rhi) {
 
 
 namespace {
-struct Tmp {      // device arrays of one call, freed together
-    gk_ctx *ctx;
-    std::vector<void *> ptrs;
-    explicit Tmp(gk_ctx *c) : ctx(c) {}
-    ~Tmp() { for (void *p : ptrs) if (p) (void)hipFree(p); }
-    template <class T> hipError_t get(T **p, u64 n) {
-        hipError_t e = hipMalloc((void **)p, std::max<u64>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
 SupView sup_view(const gk_support *s) { return SupView{s->d_keys, s->d_cnt, s->cap - 1, s->d_ctr}; }
 }  // namespace
 
@@ -725,11 +713,11 @@ int support_reserve(gk_support *s, u64 want) {
     if (s->cap >= need) return GK_OK;
     u64 *nk = nullptr;
     u32 *nc = nullptr;
-    hipError_t e = hipMalloc((void **)&nk, need * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&nc, need * 4);
+    hipError_t e = pool_malloc(ctx, &nk, need * 8);
+    if (e == hipSuccess) e = pool_malloc(ctx, &nc, need * 4);
     if (e == hipSuccess) e = hipMemsetAsync(nk, 0xff, need * 8, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(nc, 0, need * 4, ctx->stream);
-    if (e != hipSuccess) { if (nk) (void)hipFree(nk); if (nc) (void)hipFree(nc); return hip_fail(ctx, e, "gk_support: table"); }
+    if (e != hipSuccess) { (void)pool_free(ctx, nk); (void)pool_free(ctx, nc); return hip_fail(ctx, e, "gk_support: table"); }
     if (s->cap) {
         unsigned long long distinct = 0;
         GK_HIP(ctx, hipMemcpyAsync(&distinct, s->d_ctr, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -738,7 +726,7 @@ int support_reserve(gk_support *s, u64 want) {
         hipLaunchKernelGGL(k_sup_rehash, dim3(ggrid(ctx, s->cap)), dim3(BLOCK), 0, ctx->stream, s->d_keys, s->d_cnt, s->cap, SupView{nk, nc, need - 1, s->d_ctr});
         GK_HIP(ctx, hipGetLastError());
         GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(s->d_keys); (void)hipFree(s->d_cnt);
+        (void)pool_free(ctx, s->d_keys); (void)pool_free(ctx, s->d_cnt);
         (void)distinct;
     }
     s->d_keys = nk; s->d_cnt = nc; s->cap = need;
@@ -758,7 +746,7 @@ int support_bucket(gk_support *s, int P, u64 *d_keys, u32 *d_cnt, u64 room, u64 
     for (int p = 0; p <= P; p++) region[p] = 0;
     if (s->cap == 0) return GK_OK;
     const u64 nwg = (u64)ggrid(ctx, s->cap), chunk = (s->cap + nwg - 1) / nwg, n = nwg * (u64)P;
-    Tmp tmp(ctx);
+    DevScratch tmp(ctx);
     u32 *d_counts = nullptr;
     unsigned long long *d_off = nullptr, *d_region = nullptr;
     u64 *d_sums = nullptr;
@@ -810,12 +798,12 @@ int support_insert(gk_support *s, const u64 *d_keys, const u32 *d_cnt, u64 n, bo
     return GK_OK;
 }
 
-int graph_edge_canon(gk_graph *g, u32 **d_canon, u32 **d_inv, u64 *nlive, u64 *content_fp) {
+int graph_edge_canon(gk_graph *g, DevScratch &keep, u32 **d_canon, u32 **d_inv, u64 *nlive, u64 *content_fp) {
     gk_ctx *ctx = g->ctx;
     *d_canon = *d_inv = nullptr;
     *nlive = 0; *content_fp = 0;
     const u64 ne = g->v.n_edges;
-    Tmp tmp(ctx);
+    DevScratch tmp(ctx);
     u64 *d_k = nullptr, *d_k2 = nullptr;
     u32 *d_id = nullptr, *d_id2 = nullptr, *d_flag = nullptr, h_flag = 0;
     unsigned long long *d_out = nullptr, h_out[2] = {0, 0};
@@ -840,23 +828,16 @@ int graph_edge_canon(gk_graph *g, u32 **d_canon, u32 **d_inv, u64 *nlive, u64 *c
     GK_HIP(ctx, hipMemcpyAsync(h_out, d_out, 16, hipMemcpyDeviceToHost, ctx->stream));
     GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     u32 *canon = nullptr, *inv = nullptr;
-    e = hipMalloc((void **)&canon, std::max<u64>(ne, 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&inv, std::max<u64>(h_out[0], 1) * 4);
+    e = keep.get(&canon, ne);
+    if (e == hipSuccess) e = keep.get(&inv, h_out[0]);
     if (e == hipSuccess) e = hipMemsetAsync(canon, 0xff, std::max<u64>(ne, 1) * 4, ctx->stream);
-    if (e != hipSuccess) {
-        if (canon) (void)hipFree(canon);
-        if (inv) (void)hipFree(inv);
-        return hip_fail(ctx, e, "graph_edge_canon: maps");
-    }
+    if (e != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon: maps");
     if (h_out[0]) hipLaunchKernelGGL(k_edge_canon, dim3(ggrid(ctx, h_out[0])), dim3(BLOCK), 0, ctx->stream, d_k2, d_id2, (u64)h_out[0], canon, inv, d_flag);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess || h_flag) {
-        (void)hipFree(canon); (void)hipFree(inv);
-        return e != hipSuccess ? hip_fail(ctx, e, "graph_edge_canon")
-                               : fail(ctx, GK_E_STATE, "two live edges share a start k-mer and a first base (a node split made copies): their support cannot be summed by content");
-    }
+    if (e != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon");
+    if (h_flag) return fail(ctx, GK_E_STATE, "two live edges share a start k-mer and a first base (a node split made copies): their support cannot be summed by content");
     *d_canon = canon; *d_inv = inv;
     *nlive = h_out[0];
     *content_fp = h_out[1] + mix64(h_out[0] ^ 0x6c697665ULL);
@@ -865,7 +846,7 @@ int graph_edge_canon(gk_graph *g, u32 **d_canon, u32 **d_inv, u64 *nlive, u64 *c
 
 int support_keys_uncanon(gk_ctx *ctx, u64 *d_keys, u64 n, const u32 *d_inv, u64 nlive) {
     if (n == 0) return GK_OK;
-    Tmp tmp(ctx);
+    DevScratch tmp(ctx);
     u32 *d_bad = nullptr, h_bad = 0;
     GK_HIP(ctx, tmp.get(&d_bad, 1));
     GK_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
@@ -918,7 +899,7 @@ int gk_support_create(gk_ctx *ctx, gk_support **out) {
     GK_HIP(ctx, hipSetDevice(ctx->device));
     gk_support *s = new gk_support();
     s->ctx = ctx;
-    hipError_t e = hipMalloc((void **)&s->d_ctr, 64);
+    hipError_t e = pool_malloc(ctx, &s->d_ctr, 64);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_ctr, 0, 64, ctx->stream);
     if (e != hipSuccess) { delete s; return hip_fail(ctx, e, "gk_support_create"); }
     *out = s;
@@ -929,9 +910,9 @@ void gk_support_destroy(gk_support *s) {
     gk_ctx *ctx = s->ctx;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (s->d_keys) (void)hipFree(s->d_keys);
-    if (s->d_cnt) (void)hipFree(s->d_cnt);
-    if (s->d_ctr) (void)hipFree(s->d_ctr);
+    (void)pool_free(ctx, s->d_keys);
+    (void)pool_free(ctx, s->d_cnt);
+    (void)pool_free(ctx, s->d_ctr);
     delete s;
 }
 int gk_support_size(const gk_support *s, uint64_t *pairs, uint64_t *bad_pairs, uint64_t *walked) {
@@ -970,7 +951,7 @@ int gk_support_merge(gk_support *dst, const gk_support *src) {
     if (int rc = support_counters(dst, hd)) return rc;
     // would a count wrap?  decided before dst is touched: a refused merge leaves it as it was
     if (src->cap && dst->cap && hs[0]) {
-        Tmp tmp(ctx);
+        DevScratch tmp(ctx);
         u32 *d_wrap = nullptr, h_wrap = 0;
         GK_HIP(ctx, tmp.get(&d_wrap, 1));
         GK_HIP(ctx, hipMemsetAsync(d_wrap, 0, 4, ctx->stream));
@@ -1009,7 +990,7 @@ int gk_support_add(gk_support *s, const uint32_t *e1, const uint32_t *e2, const 
     if (n) {
         std::vector<u64> keys(n);
         for (u64 i = 0; i < n; i++) keys[i] = ((u64)e1[i] << 32) | e2[i];
-        Tmp tmp(ctx);
+        DevScratch tmp(ctx);
         u64 *d_k = nullptr;
         u32 *d_c = nullptr;
         hipError_t e = tmp.get(&d_k, n);
@@ -1031,7 +1012,7 @@ int gk_graph_id_fingerprint(gk_graph *g, uint64_t *fp) {
     if (int rc = check_graph(g)) return rc;
     gk_ctx *ctx = g->ctx;
     if (!fp) return fail(ctx, GK_E_INVALID, "gk_graph_id_fingerprint: null argument");
-    Tmp tmp(ctx);
+    DevScratch tmp(ctx);
     unsigned long long *d = nullptr, h = 0;
     GK_HIP(ctx, tmp.get(&d, 1));
     GK_HIP(ctx, hipMemsetAsync(d, 0, 8, ctx->stream));
@@ -1062,7 +1043,7 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
     const int k = g->k, W = g->W;
     auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double t_begin = now();
-    Tmp tmp(ctx);
+    DevScratch tmp(ctx);
     // ---- the pairs whose mates both hold k bases (:213), their four keys.  A stream of equal-length records (what a
     //      sequencer's run is) goes to the device as it is and is cut there; a ragged one is walked here.
     u64 *d_lo = nullptr, *d_hi = nullptr;
@@ -1341,8 +1322,9 @@ int gk_graph_remove_edges_by_id(gk_graph *g, const uint32_t *edge_ids, uint64_t 
     ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
     u32 *d_e = nullptr;
     unsigned long long *d_rm = nullptr, h_rm = 0;
-    hipError_t e = hipMalloc((void **)&d_e, ids.size() * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_rm, 8);
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&d_e, ids.size());
+    if (e == hipSuccess) e = tmp.get(&d_rm, 1);
     if (e == hipSuccess) e = hipMemcpyAsync(d_e, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_rm, 0, 8, ctx->stream);
     if (e == hipSuccess) {
@@ -1351,7 +1333,6 @@ int gk_graph_remove_edges_by_id(gk_graph *g, const uint32_t *edge_ids, uint64_t 
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_rm, d_rm, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_e); (void)hipFree(d_rm);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_remove_edges_by_id");
     if (removed) *removed = h_rm;
     return graph_refresh_counts(g);
@@ -1417,9 +1398,10 @@ int gk_graph_split_by_support(gk_graph *g, const gk_support *sup, int cutoff, ui
         if (v.n_nodes + nnew > g->node_cap) { if (int rc = graph_grow_nodes(g, std::max<u64>(g->node_cap * 2, v.n_nodes + nnew))) return rc; }
         u32 *d_src = nullptr, *d_a = nullptr, *d_b = nullptr;
         const u64 nmv = std::max<u64>(end_edge.size(), start_edge.size());
-        hipError_t e = hipMalloc((void **)&d_src, nnew * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_a, std::max<u64>(nmv, 1) * 4);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_b, std::max<u64>(nmv, 1) * 4);
+        DevScratch tmp(ctx);
+        hipError_t e = tmp.get(&d_src, nnew);
+        if (e == hipSuccess) e = tmp.get(&d_a, nmv);
+        if (e == hipSuccess) e = tmp.get(&d_b, nmv);
         if (e == hipSuccess) e = hipMemcpyAsync(d_src, new_src.data(), nnew * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_add_nodes, dim3(ggrid(ctx, nnew)), dim3(BLOCK), 0, ctx->stream, v, first_new, d_src, nnew);
@@ -1438,7 +1420,6 @@ int gk_graph_split_by_support(gk_graph *g, const gk_support *sup, int cutoff, ui
             if (e == hipSuccess) { hipLaunchKernelGGL(k_move_starts, dim3(ggrid(ctx, start_edge.size())), dim3(BLOCK), 0, ctx->stream, v, d_a, d_b, (u64)start_edge.size()); e = hipGetLastError(); }
         }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_src); (void)hipFree(d_a); (void)hipFree(d_b);
         if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_split_by_support");
         g->index_ready = false;                                // several nodes share a sequence now: the next point query rebuilds the index with all of them
     }

@@ -1283,9 +1283,9 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 static int grow_buf(gk_ctx *ctx, u64 **buf, u64 *have, u64 want, int W) {
     if (*have >= want) return GK_OK;
-    if (*buf) GK_HIP(ctx, hipFree(*buf));
+    if (*buf) GK_HIP(ctx, pool_free(ctx, *buf));
     *buf = nullptr; *have = 0;
-    hipError_t e = hipMalloc((void **)buf, std::max<u64>(want, 1) * 8 * W);
+    hipError_t e = pool_malloc(ctx, buf, std::max<u64>(want, 1) * 8 * W);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(ctx, GK_E_CAPACITY, "partitioned insert: cannot allocate " + std::to_string(want * 8 * W) + " bytes of key scratch: " + hipGetErrorString(e));
@@ -1295,9 +1295,9 @@ static int grow_buf(gk_ctx *ctx, u64 **buf, u64 *have, u64 want, int W) {
 }
 static int grow_raw(gk_ctx *ctx, void **buf, size_t *have, size_t want) {
     if (*have >= want) return GK_OK;
-    if (*buf) GK_HIP(ctx, hipFree(*buf));
+    if (*buf) GK_HIP(ctx, pool_free(ctx, *buf));
     *buf = nullptr; *have = 0;
-    GK_HIP(ctx, hipMalloc(buf, std::max<size_t>(want, 256)));
+    GK_HIP(ctx, pool_malloc(ctx, buf, std::max<size_t>(want, 256)));
     *have = want;
     return GK_OK;
 }
@@ -1321,7 +1321,7 @@ static int part_prepare_l1(gk_map *m, PartScratch *ps, u64 nkeys, bool op1, Part
     arr->n_failed = (u32 *)(b + o_nf); arr->nspill = (unsigned long long *)(b + o_nsp); arr->overflow = (u32 *)(b + o_ovf);
     arr->hist2 = nullptr; arr->fine_base = nullptr; arr->cursor2 = nullptr; arr->failed = nullptr; arr->rmat = nullptr;
     if (ps->W != m->W) {     // key width changed: drop the buffers
-        for (u64 **bp : {&ps->bufA, &ps->bufB, &ps->spill}) { if (*bp) GK_HIP(ctx, hipFree(*bp)); *bp = nullptr; }
+        for (u64 **bp : {&ps->bufA, &ps->bufB, &ps->spill}) { if (*bp) GK_HIP(ctx, pool_free(ctx, *bp)); *bp = nullptr; }
         ps->bufA_keys = ps->bufB_keys = ps->spill_keys = 0;
         ps->W = m->W;
     }
@@ -1380,9 +1380,9 @@ static int part_prepare_fine(gk_map *m, PartScratch *ps, u64 nkeys, bool op2, Pa
         const u64 max_ranges = (nkeys / TILE2 + MAXB1 + 1) / arr->range_chunks + MAXB1 + 1;
         const u64 words = max_ranges * m->nb2;
         if (ps->rmat_words < words) {
-            if (ps->rmat) GK_HIP(ctx, hipFree(ps->rmat));
+            if (ps->rmat) GK_HIP(ctx, pool_free(ctx, ps->rmat));
             ps->rmat = nullptr; ps->rmat_words = 0;
-            GK_HIP(ctx, hipMalloc((void **)&ps->rmat, words * 4));
+            GK_HIP(ctx, pool_malloc(ctx, &ps->rmat, words * 4));
             ps->rmat_words = words;
         }
         arr->rmat = ps->rmat;
@@ -1393,7 +1393,7 @@ static int part_prepare_fine(gk_map *m, PartScratch *ps, u64 nkeys, bool op2, Pa
 void part_scratch_free(gk_ctx *ctx, PartScratch *ps) {
     if (!ps) return;
     for (void *p : {ps->blob, ps->fblob, (void *)ps->rmat, (void *)ps->bufA, (void *)ps->bufB, (void *)ps->spill})
-        if (p) (void)hipFree(p);
+        (void)pool_free(ctx, p);
     delete ps;
 }
 

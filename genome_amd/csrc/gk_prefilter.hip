@@ -169,9 +169,9 @@ int pf_select_and_insert(gk_prefilter *pf, gk_map *m, const uint8_t *d_rec, u64 
                          u64 max_windows_per_read, u64 *admitted_total, int max_len = 255) {
     gk_ctx *ctx = pf->ctx;
     if (pf->keybuf_keys < max_windows) {
-        if (pf->keybuf) GK_HIP(ctx, hipFree(pf->keybuf));
+        if (pf->keybuf) GK_HIP(ctx, pool_free(ctx, pf->keybuf));
         pf->keybuf = nullptr; pf->keybuf_keys = 0;
-        GK_HIP(ctx, hipMalloc((void **)&pf->keybuf, std::max<u64>(max_windows, 1) * 8 * pf->W));
+        GK_HIP(ctx, pool_malloc(ctx, &pf->keybuf, std::max<u64>(max_windows, 1) * 8 * pf->W));
         pf->keybuf_keys = max_windows;
     }
     GK_HIP(ctx, hipMemsetAsync(pf->d_cursor, 0, 8, ctx->stream));                     // admitted
@@ -202,15 +202,15 @@ int pf_select_and_insert(gk_prefilter *pf, gk_map *m, const uint8_t *d_rec, u64 
 int pf_ensure_stage(gk_prefilter *pf, size_t bytes, size_t noffs) {
     gk_ctx *ctx = pf->ctx;
     if (pf->stage_bytes < bytes + 64) {
-        if (pf->d_stage) GK_HIP(ctx, hipFree(pf->d_stage));
+        if (pf->d_stage) GK_HIP(ctx, pool_free(ctx, pf->d_stage));
         pf->d_stage = nullptr; pf->stage_bytes = 0;
-        GK_HIP(ctx, hipMalloc(&pf->d_stage, bytes + 64));
+        GK_HIP(ctx, pool_malloc(ctx, &pf->d_stage, bytes + 64));
         pf->stage_bytes = bytes + 64;
     }
     if (pf->offsets_bytes < noffs * sizeof(u32)) {
-        if (pf->d_offsets) GK_HIP(ctx, hipFree(pf->d_offsets));
+        if (pf->d_offsets) GK_HIP(ctx, pool_free(ctx, pf->d_offsets));
         pf->d_offsets = nullptr; pf->offsets_bytes = 0;
-        GK_HIP(ctx, hipMalloc((void **)&pf->d_offsets, noffs * sizeof(u32)));
+        GK_HIP(ctx, pool_malloc(ctx, &pf->d_offsets, noffs * sizeof(u32)));
         pf->offsets_bytes = noffs * sizeof(u32);
     }
     return GK_OK;
@@ -289,10 +289,10 @@ int gk_prefilter_create(gk_ctx *ctx, int k, uint64_t expected_distinct, gk_prefi
     // another k-mer with probability ~ 1 - exp(-1/4) = 22 %
     pf->nbuckets = std::max<u64>(expected_distinct, 1ull << 16) * 4;
     pf->nwords = (pf->nbuckets + 15) / 16;
-    hipError_t e = hipMalloc((void **)&pf->words, pf->nwords * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&pf->d_cursor, 4 * sizeof(unsigned long long));
+    hipError_t e = pool_malloc(ctx, &pf->words, pf->nwords * 4);
+    if (e == hipSuccess) e = pool_malloc(ctx, &pf->d_cursor, 4 * sizeof(unsigned long long));
     if (e != hipSuccess) {
-        if (pf->words) (void)hipFree(pf->words);
+        (void)pool_free(ctx, pf->words);
         delete pf;
         (void)hipGetLastError();
         return fail(ctx, GK_E_CAPACITY, "gk_prefilter_create: " + std::string(hipGetErrorString(e)) + " for " + std::to_string(pf->nwords * 4) + " bytes");
@@ -311,11 +311,11 @@ void gk_prefilter_destroy(gk_prefilter *pf) {
     if (!pf) return;
     gk_ctx *ctx = pf->ctx;
     if (pf->ctx) (void)hipSetDevice(pf->ctx->device);
-    if (pf->words) (void)hipFree(pf->words);
-    if (pf->keybuf) (void)hipFree(pf->keybuf);
-    if (pf->d_cursor) (void)hipFree(pf->d_cursor);
-    if (pf->d_stage) (void)hipFree(pf->d_stage);
-    if (pf->d_offsets) (void)hipFree(pf->d_offsets);
+    (void)pool_free(ctx, pf->words);
+    (void)pool_free(ctx, pf->keybuf);
+    (void)pool_free(ctx, pf->d_cursor);
+    (void)pool_free(ctx, pf->d_stage);
+    (void)pool_free(ctx, pf->d_offsets);
     delete pf;
 }
 

@@ -168,7 +168,8 @@ int gk_shard_reads_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_t nre
     const int W = words_for_k(k);
     const u32 stride = 1 + (read_len + 3) / 4;
     unsigned long long *d_cnt = nullptr;
-    GK_HIP(ctx, hipMalloc((void **)&d_cnt, 2 * MAX_PARTS * sizeof(unsigned long long)));
+    DevScratch tmp(ctx);
+    GK_HIP(ctx, tmp.get(&d_cnt, 2 * MAX_PARTS));
     hipError_t e = hipMemsetAsync(d_cnt, 0, 2 * MAX_PARTS * sizeof(unsigned long long), ctx->stream);
     const u64 ntiles = (nreads + TILE_READS - 1) / TILE_READS;
     const int grid = (int)std::min<u64>(ntiles, (u64)ctx->cu_count * 8);
@@ -192,7 +193,6 @@ int gk_shard_reads_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_t nre
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_cnt);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_shard_reads_dev");
     return ctx_check_format(ctx);
 }

@@ -316,7 +316,7 @@ int gk_shard_superkmers_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_
                             void *dev_out, uint64_t out_cap_records, uint64_t *rec_counts_host, uint64_t *kmer_counts_host) {
     if (!ctx) return fail(nullptr, GK_E_INVALID, "null ctx");
     if (!rec_counts_host || !kmer_counts_host) return fail(ctx, GK_E_INVALID, "null argument");
-    if (!ctx->skm_counts) GK_HIP(ctx, hipMalloc(&ctx->skm_counts, SKM_COUNT_WORDS * sizeof(unsigned long long)));
+    if (!ctx->skm_counts) GK_HIP(ctx, pool_malloc(ctx, &ctx->skm_counts, SKM_COUNT_WORDS * sizeof(unsigned long long)));
     unsigned long long h[SKM_COUNT_WORDS];
     if (int rc = skm_route_launch(ctx, ctx->stream, (unsigned long long *)ctx->skm_counts, h, k, dev_records, nreads, read_len, P, dev_out, out_cap_records)) return rc;
     GK_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -38,10 +38,10 @@ int support_counters(const gk_support *s, unsigned long long *h4);
 int support_bucket(gk_support *s, int P, u64 *d_keys, u32 *d_cnt, u64 room, u64 *region, const u32 *canon = nullptr, u64 nmap = 0);
 // The canonical edge numbering of a replica: live edges ordered by (a 64-bit hash of) their content key, (start k-mer, first
 // base) — the same on every replica that holds the same edges, whatever ids its build gave them.  *d_canon [n_edges]: local id ->
-// canonical (0xffffffff dead), *d_inv [*nlive]: canonical -> local id; both from the context's pool (hipFree them).
+// canonical (0xffffffff dead), *d_inv [*nlive]: canonical -> local id; both belong to `keep`, the caller's owner.
 // *content_fp: equal on two replicas iff they hold the same live edges (start and end k-mer, first base, length).  GK_E_STATE if
 // two live edges share a content key (a node split made copies that share a k-mer).  The sort is rocPRIM's radix sort.
-int graph_edge_canon(gk_graph *g, u32 **d_canon, u32 **d_inv, u64 *nlive, u64 *content_fp);
+int graph_edge_canon(gk_graph *g, DevScratch &keep, u32 **d_canon, u32 **d_inv, u64 *nlive, u64 *content_fp);
 // canonical pair keys back to the local numbering, in place
 int support_keys_uncanon(gk_ctx *ctx, u64 *d_keys, u64 n, const u32 *d_inv, u64 nlive);
 // insert n records into s (reserved here for distinct + n).  checked: a count that passes 2^32-1 sets *overflow (the table

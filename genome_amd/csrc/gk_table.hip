@@ -431,7 +431,7 @@ static void launch_clear(gk_ctx *ctx, int W, int layout, void *slots, uint64_t c
     else hipLaunchKernelGGL(k_clear<CSlot>, dim3(grid), dim3(BLOCK), 0, ctx->stream, (CSlot *)slots, cap);
 }
 static int alloc_table(gk_ctx *ctx, int W, int layout, uint64_t cap, void **out) {
-    GK_HIP(ctx, hipMalloc(out, cap * slot_bytes(W, layout)));
+    GK_HIP(ctx, pool_malloc(ctx, out, cap * slot_bytes(W, layout)));
     launch_clear(ctx, W, layout, *out, cap);
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
@@ -459,7 +459,7 @@ static constexpr size_t POOL_MIN_BLOCK = 1u << 20;
 hipError_t pool_malloc(gk_ctx *ctx, void **p, size_t bytes) {
     *p = nullptr;
     std::lock_guard<std::recursive_mutex> lock(ctx->pool_mu);
-    if (bytes < POOL_MIN_BLOCK) return (hipMalloc)(p, bytes ? bytes : 1);
+    if (bytes < POOL_MIN_BLOCK) return hipMalloc(p, bytes ? bytes : 1);
     // best fit, but never a block more than half again as big as asked for (a 12 GB table must not sit in a 50 GB block)
     auto it = ctx->pool_free_blocks.lower_bound(bytes);
     if (it != ctx->pool_free_blocks.end() && it->first <= bytes + bytes / 2) {
@@ -471,11 +471,11 @@ hipError_t pool_malloc(gk_ctx *ctx, void **p, size_t bytes) {
         ctx->pool_hits++;
         return hipSuccess;
     }
-    hipError_t e = (hipMalloc)(p, bytes);
+    hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess && !ctx->pool_free_blocks.empty()) {         // out of memory with blocks parked: give them back, once
         (void)hipGetLastError();
         pool_release(ctx);
-        e = (hipMalloc)(p, bytes);
+        e = hipMalloc(p, bytes);
     }
     if (e == hipSuccess) {
         ctx->pool_sizes[*p] = bytes;
@@ -489,7 +489,7 @@ hipError_t pool_free(gk_ctx *ctx, void *p) {
     if (!p) return hipSuccess;
     std::lock_guard<std::recursive_mutex> lock(ctx->pool_mu);
     auto it = ctx->pool_sizes.find(p);
-    if (it == ctx->pool_sizes.end()) return (hipFree)(p);
+    if (it == ctx->pool_sizes.end()) return hipFree(p);
     const size_t bytes = it->second;
     ctx->pool_live -= std::min(ctx->pool_live, bytes);
     // (hipFree waits for the device; a parked block may be handed out again at once, so wait for this context's work here:
@@ -505,7 +505,7 @@ hipError_t pool_free(gk_ctx *ctx, void *p) {
     if (e == hipSuccess && ctx->aux_stream) e = hipStreamSynchronize(ctx->aux_stream);
     if (e != hipSuccess || ctx->pool_held + bytes > ctx->pool_limit) {
         ctx->pool_sizes.erase(it);
-        const hipError_t e2 = (hipFree)(p);
+        const hipError_t e2 = hipFree(p);
         return e != hipSuccess ? e : e2;
     }
     ctx->pool_free_blocks.emplace(bytes, p);
@@ -542,7 +542,7 @@ double graph_table_load(gk_ctx *ctx, int k, uint64_t keys) {
 }
 void pool_release(gk_ctx *ctx) {
     std::lock_guard<std::recursive_mutex> lock(ctx->pool_mu);
-    for (auto &b : ctx->pool_free_blocks) { ctx->pool_sizes.erase(b.second); (void)(hipFree)(b.second); }
+    for (auto &b : ctx->pool_free_blocks) { ctx->pool_sizes.erase(b.second); (void)hipFree(b.second); }
     ctx->pool_free_blocks.clear();
     ctx->pool_held = 0;
 }
@@ -608,18 +608,18 @@ static int map_grow_to(gk_map *m, uint64_t want_slots, bool rehash, bool keep_ln
     }
     void *nslots = nullptr;
     if (!rehash) {
-        hipError_t e = hipMalloc(&nslots, ncap * map_slot_bytes(m));
+        hipError_t e = pool_malloc(ctx, &nslots, ncap * map_slot_bytes(m));
         if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, GK_E_CAPACITY, "cannot grow table to " + std::to_string(ncap) + " slots: " + hipGetErrorString(e)); }
     } else {
         int rc = alloc_table(ctx, m->W, m->layout, ncap, &nslots);
-        if (rc) { if (nslots) (void)hipFree(nslots); return fail(ctx, GK_E_CAPACITY, "cannot grow table to " + std::to_string(ncap) + " slots: " + ctx->err); }
+        if (rc) { (void)pool_free(ctx, nslots); return fail(ctx, GK_E_CAPACITY, "cannot grow table to " + std::to_string(ncap) + " slots: " + ctx->err); }
         launch_rehash(m, m->layout, nslots, nnb2, nlnb1);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { (void)hipFree(nslots); return hip_fail(ctx, e, "table rehash"); }
-        if (int rc2 = map_sync_counters(m)) { (void)hipFree(nslots); return rc2; }      // rehash error flag: the old table stays
+        if (e != hipSuccess) { (void)pool_free(ctx, nslots); return hip_fail(ctx, e, "table rehash"); }
+        if (int rc2 = map_sync_counters(m)) { (void)pool_free(ctx, nslots); return rc2; }      // rehash error flag: the old table stays
     }
-    GK_HIP(ctx, hipFree(m->slots));
+    GK_HIP(ctx, pool_free(ctx, m->slots));
     m->slots = nslots;
     m->capacity = ncap;
     m->nb2 = nnb2;
@@ -653,7 +653,7 @@ static constexpr uint64_t SAMPLE_SLOTS = 1ull << 23;      // 64 MB: 4 M sample k
 int map_ensure_sample(gk_map *m) {
     if (m->d_sample) return GK_OK;
     gk_ctx *ctx = m->ctx;
-    GK_HIP(ctx, hipMalloc((void **)&m->d_sample, SAMPLE_SLOTS * 8));
+    GK_HIP(ctx, pool_malloc(ctx, &m->d_sample, SAMPLE_SLOTS * 8));
     GK_HIP(ctx, hipMemsetAsync(m->d_sample, 0xff, SAMPLE_SLOTS * 8, ctx->stream));
     m->sample_mask = SAMPLE_SLOTS - 1;
     return GK_OK;
@@ -715,7 +715,7 @@ int gk_ctx_create(int device, gk_ctx **out) {
     for (int i = 0; i < 16 && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ctx->cev[i], hipEventDisableTiming);
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->d_flags, 64);
+    if (e == hipSuccess) e = pool_malloc(ctx, &ctx->d_flags, 64);
     if (e == hipSuccess) e = hipMemset(ctx->d_flags, 0, 64);
     if (e != hipSuccess) {
         int rc = hip_fail(nullptr, e, "gk_ctx_create");
@@ -739,8 +739,8 @@ void gk_ctx_destroy(gk_ctx *ctx) {
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
     gk::pool_release(ctx);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    if (ctx->skm_counts) (void)hipFree(ctx->skm_counts);
-    if (ctx->d_flags) (void)hipFree(ctx->d_flags);
+    (void)pool_free(ctx, ctx->skm_counts);
+    (void)pool_free(ctx, ctx->d_flags);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (int i = 0; i < 6; i++) if (ctx->pev[i]) (void)hipEventDestroy(ctx->pev[i]);
@@ -826,12 +826,12 @@ int gk_host_unregister(gk_ctx *ctx, void *host_ptr) {
 int gk_dev_alloc(gk_ctx *ctx, size_t nbytes, void **dev_ptr) {
     if (!ctx || !dev_ptr) return fail(ctx, GK_E_INVALID, "gk_dev_alloc: null argument");
     GK_HIP(ctx, hipSetDevice(ctx->device));
-    GK_HIP(ctx, hipMalloc(dev_ptr, nbytes ? nbytes : 1));
+    GK_HIP(ctx, pool_malloc(ctx, dev_ptr, nbytes ? nbytes : 1));
     return GK_OK;
 }
 int gk_dev_free(gk_ctx *ctx, void *dev_ptr) {
     if (!ctx) return fail(ctx, GK_E_INVALID, "null ctx");
-    if (dev_ptr) GK_HIP(ctx, hipFree(dev_ptr));
+    if (dev_ptr) GK_HIP(ctx, pool_free(ctx, dev_ptr));
     return GK_OK;
 }
 int gk_dev_upload(gk_ctx *ctx, void *dev_dst, const void *host_src, size_t nbytes) {
@@ -871,8 +871,9 @@ int gk_dev_stream_bench(gk_ctx *ctx, size_t nbytes, int reps, double *gbps3) {
     GK_HIP(ctx, hipSetDevice(ctx->device));
     const u64 n = nbytes / 16;
     uint4 *a = nullptr, *b = nullptr;
-    GK_HIP(ctx, hipMalloc((void **)&a, n * 16));
-    if (hipError_t e = hipMalloc((void **)&b, n * 16); e != hipSuccess) { (void)hipFree(a); return hip_fail(ctx, e, "gk_dev_stream_bench"); }
+    DevScratch tmp(ctx);
+    GK_HIP(ctx, tmp.get(&a, n));
+    if (hipError_t e = tmp.get(&b, n); e != hipSuccess) return hip_fail(ctx, e, "gk_dev_stream_bench");
     const int grid = (int)std::min<u64>((n + 255) / 256, (u64)ctx->cu_count * 8);
     auto timed = [&](int which, double bytes_per_rep, double *out) -> int {
         for (int r = -1; r < reps; r++) {          // (one untimed launch first)
@@ -894,7 +895,6 @@ int gk_dev_stream_bench(gk_ctx *ctx, size_t nbytes, int reps, double *gbps3) {
     if (!rc) rc = timed(1, 16.0 * (double)n, &gbps3[1]);
     if (!rc) rc = timed(2, 16.0 * (double)n, &gbps3[2]);
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(a); (void)hipFree(b);
     return rc;
 }
 
@@ -917,20 +917,20 @@ int gk_map_create(gk_ctx *ctx, int k, uint64_t capacity_hint, gk_map **out) {
     int rc = GK_OK;
     {
         m->layout = LAYOUT_COUNT;        // (8-byte keys: 12-byte count slots; the graph phase's 16-byte layout is what deleteAll / the gather build)
-        hipError_t ea = hipMalloc(&m->slots, m->capacity * map_slot_bytes(m));
+        hipError_t ea = pool_malloc(ctx, &m->slots, m->capacity * map_slot_bytes(m));
         if (ea != hipSuccess) rc = hip_fail(ctx, ea, "gk_map_create: table");
         m->pending_clear = true;
     }
     if (rc == GK_OK) {
-        hipError_t e = hipMalloc((void **)&m->d_ctr, sizeof(Counters));
+        hipError_t e = pool_malloc(ctx, &m->d_ctr, sizeof(Counters));
         if (e == hipSuccess) e = hipHostMalloc((void **)&m->h_status, 256, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMemsetAsync(m->d_ctr, 0, sizeof(Counters), ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = hip_fail(ctx, e, "gk_map_create");
     }
     if (rc != GK_OK) {
-        if (m->slots) (void)hipFree(m->slots);
-        if (m->d_ctr) (void)hipFree(m->d_ctr);
+        (void)pool_free(ctx, m->slots);
+        (void)pool_free(ctx, m->d_ctr);
         if (m->h_status) (void)hipHostFree(m->h_status);
         delete m;
         return rc == GK_E_HIP ? fail(ctx, GK_E_CAPACITY, "cannot allocate table: " + ctx->err) : rc;
@@ -952,14 +952,14 @@ void gk_map_destroy(gk_map *m) {
     gk_ctx *ctx = m->ctx;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    if (m->slots) (void)hipFree(m->slots);
-    if (m->d_ctr) (void)hipFree(m->d_ctr);
+    (void)pool_free(ctx, m->slots);
+    (void)pool_free(ctx, m->d_ctr);
     if (m->h_status) (void)hipHostFree(m->h_status);
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);       // (a prefetch may be on its way)
-    for (int i = 0; i < 2; i++) { if (m->stage[i].d) (void)hipFree(m->stage[i].d); if (m->stage[i].ev) (void)hipEventDestroy(m->stage[i].ev); }
-    if (m->d_offsets) (void)hipFree(m->d_offsets);
-    if (m->d_sample) (void)hipFree(m->d_sample);
-    if (m->d_scratch) (void)hipFree(m->d_scratch);
+    for (int i = 0; i < 2; i++) { (void)pool_free(ctx, m->stage[i].d); if (m->stage[i].ev) (void)hipEventDestroy(m->stage[i].ev); }
+    (void)pool_free(ctx, m->d_offsets);
+    (void)pool_free(ctx, m->d_sample);
+    (void)pool_free(ctx, m->d_scratch);
     part_scratch_free(ctx, m->part);
     delete m;
 }
@@ -1074,7 +1074,8 @@ static const PathCost &path_cost(gk_ctx *ctx) {
     ctx->cost_state = 2;                                           // (whatever happens below, measure once)
     constexpr u64 N16 = (64u << 20) / 16, NCAS = 1u << 23;           // 64 MiB copied, 8 M CAS into a 64 MiB table
     uint4 *a = nullptr, *b = nullptr;
-    if (hipMalloc((void **)&a, N16 * 16) != hipSuccess || hipMalloc((void **)&b, N16 * 16) != hipSuccess) { (void)hipGetLastError(); if (a) (void)hipFree(a); return REF; }
+    DevScratch tmp(ctx);
+    if (tmp.get(&a, N16) != hipSuccess || tmp.get(&b, N16) != hipSuccess) return REF;
     const int grid = ctx->cu_count * 8;
     float ms_copy = 0, ms_cas = 0;
     hipError_t e = hipMemsetAsync(a, 0xff, N16 * 16, ctx->stream);
@@ -1090,7 +1091,6 @@ static const PathCost &path_cost(gk_ctx *ctx) {
     if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
     if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
     if (e == hipSuccess) e = hipEventElapsedTime(&ms_cas, ctx->ev0, ctx->ev1);
-    (void)hipFree(a); (void)hipFree(b);
     if (e != hipSuccess || ms_copy <= 0 || ms_cas <= 0) { (void)hipGetLastError(); return REF; }
     const double copy_tbps = 2.0 * N16 * 16 / (ms_copy * 1e-3) / 1e12, cas_gps = NCAS / (ms_cas * 1e-3) / 1e9;
     // (a 64 MiB working set partly lives in the 256 MB Infinity Cache: the RATIOS to the reference box are what is used, and they are
@@ -1336,10 +1336,10 @@ static int stage_reserve(gk_map *m, int slot, size_t bytes) {
     if (st.cap >= bytes) return GK_OK;
     if (st.d) {
         GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));        // (an upload into this area may be in flight: pool_free does not wait for those)
-        GK_HIP(ctx, hipFree(st.d));
+        GK_HIP(ctx, pool_free(ctx, st.d));
     }
     st.d = nullptr; st.cap = 0;
-    GK_HIP(ctx, hipMalloc(&st.d, bytes));
+    GK_HIP(ctx, pool_malloc(ctx, &st.d, bytes));
     st.cap = bytes;
     return GK_OK;
 }
@@ -1512,10 +1512,10 @@ int gk_map_count_reads(gk_map *m, const uint8_t *bin, size_t nbytes, uint64_t nr
         if (err) return format_error(err, nxt);
         if (nxt.valid && ctx->hook_host_prefetch != 0) { if (int rc = stage_prefetch_arm(m, bin + nxt.begin, nxt.bytes, m->stage_cur)) return rc; }
         if (m->offsets_bytes < cur.offs.size() * sizeof(u32)) {
-            if (m->d_offsets) GK_HIP(ctx, hipFree(m->d_offsets));
+            if (m->d_offsets) GK_HIP(ctx, pool_free(ctx, m->d_offsets));
             m->d_offsets = nullptr;
             m->offsets_bytes = 0;
-            GK_HIP(ctx, hipMalloc(&m->d_offsets, cur.offs.size() * sizeof(u32)));
+            GK_HIP(ctx, pool_malloc(ctx, &m->d_offsets, cur.offs.size() * sizeof(u32)));
             m->offsets_bytes = cur.offs.size() * sizeof(u32);
         }
         // the records stay in host memory for now: the consumer uploads them (ReadSrc::host) — unless they are on their way already
@@ -1622,10 +1622,10 @@ int map_create_for_graph(gk_ctx *ctx, int k, uint64_t keys, gk_map **out) {
     if (int rc = gk_map_create(ctx, k, hint, out)) return rc;
     gk_map *m = *out;
     if (m->W == 1) {            // the graph layout (16-byte slots with the annotation word): the table was allocated for 12-byte slots
-        GK_HIP(ctx, hipFree(m->slots));
+        GK_HIP(ctx, pool_free(ctx, m->slots));
         m->slots = nullptr;
         m->layout = LAYOUT_GRAPH;
-        hipError_t e = hipMalloc(&m->slots, m->capacity * map_slot_bytes(m));
+        hipError_t e = pool_malloc(ctx, &m->slots, m->capacity * map_slot_bytes(m));
         if (e != hipSuccess) { const int rc = hip_fail(ctx, e, "gk_map_create_for_graph: table"); gk_map_destroy(m); *out = nullptr; return rc == GK_E_HIP ? fail(ctx, GK_E_CAPACITY, "cannot allocate table: " + ctx->err) : rc; }
     }
     return GK_OK;
@@ -1678,10 +1678,10 @@ namespace gk {
 void *map_scratch(gk_map *m, size_t bytes) {
     if (m->scratch_bytes >= bytes) return m->d_scratch;
     gk_ctx *ctx = m->ctx;
-    if (m->d_scratch) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(m->d_scratch); }
+    if (m->d_scratch) { (void)hipStreamSynchronize(ctx->stream); (void)pool_free(ctx, m->d_scratch); }
     m->d_scratch = nullptr; m->scratch_bytes = 0;
     const size_t want = std::max<size_t>(bytes + bytes / 4, 1 << 16);
-    hipError_t e = hipMalloc(&m->d_scratch, want);
+    hipError_t e = pool_malloc(ctx, &m->d_scratch, want);
     if (e != hipSuccess) { (void)hipGetLastError(); (void)fail(ctx, GK_E_CAPACITY, std::string("scratch allocation failed: ") + hipGetErrorString(e)); return nullptr; }
     m->scratch_bytes = want;
     return m->d_scratch;
@@ -1733,19 +1733,19 @@ int gk_map_add_map(gk_map *dst, gk_map *src) {
     u64 *d_keys = nullptr;
     i32 *d_cnt = nullptr;
     unsigned long long *d_cur = nullptr;
-    auto done = [&](int code) { for (void *p : {(void *)d_keys, (void *)d_cnt, (void *)d_cur}) if (p) (void)hipFree(p); return code; };
-    hipError_t e = hipMalloc((void **)&d_keys, cap * 8 * dst->W);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cnt, cap * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cur, 8);
-    if (e != hipSuccess) return done(hip_fail(ctx, e, "gk_map_add_map: staging"));
+    DevScratch tmp(ctx);
+    hipError_t e = tmp.get(&d_keys, cap * dst->W);
+    if (e == hipSuccess) e = tmp.get(&d_cnt, cap);
+    if (e == hipSuccess) e = tmp.get(&d_cur, 1);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_map_add_map: staging");
     for (u64 s0 = 0; s0 < src->capacity; s0 += CHS) {
         uint64_t n = 0;
-        if (int rc = map_export_range_dev(src, s0, s0 + CHS, d_keys, d_cnt, d_cur, &n)) return done(rc);
-        if (n) { if (int rc = add_keys_dev(dst, d_keys, d_cnt, n, src->dirty)) return done(rc); }
+        if (int rc = map_export_range_dev(src, s0, s0 + CHS, d_keys, d_cnt, d_cur, &n)) return rc;
+        if (n) { if (int rc = add_keys_dev(dst, d_keys, d_cnt, n, src->dirty)) return rc; }
     }
     if (src->dirty) dst->dirty = true;
     GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return done(GK_OK);
+    return GK_OK;
 }
 
 // replace the table by one sized for its live keys (after deleteAll: the reference rescales too, ArrayDNAMap.scala:214)
@@ -1758,13 +1758,13 @@ static int map_compact(gk_map *m) {
     plan_segments(m->W, (uint64_t)((double)m->size / graph_load) + 1, &nnb2, &nlnb1, &ncap, (uint32_t)ctx->hook_min_lnb1);
     if (ncap > m->capacity) { nnb2 = m->nb2; nlnb1 = m->lnb1; ncap = m->capacity; }
     void *nslots = nullptr;
-    if (alloc_table(ctx, m->W, LAYOUT_GRAPH, ncap, &nslots) != GK_OK) { if (nslots) (void)hipFree(nslots); return GK_OK; }   // keep tombstones if memory is short
+    if (alloc_table(ctx, m->W, LAYOUT_GRAPH, ncap, &nslots) != GK_OK) { (void)pool_free(ctx, nslots); return GK_OK; }   // keep tombstones if memory is short
     launch_rehash(m, LAYOUT_GRAPH, nslots, nnb2, nlnb1);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(nslots); return hip_fail(ctx, e, "table compaction"); }
-    if (int rc = map_sync_counters(m)) { (void)hipFree(nslots); return rc; }       // a failed rehash leaves the old table in place
-    GK_HIP(ctx, hipFree(m->slots));
+    if (e != hipSuccess) { (void)pool_free(ctx, nslots); return hip_fail(ctx, e, "table compaction"); }
+    if (int rc = map_sync_counters(m)) { (void)pool_free(ctx, nslots); return rc; }       // a failed rehash leaves the old table in place
+    GK_HIP(ctx, pool_free(ctx, m->slots));
     m->slots = nslots;
     m->capacity = ncap;
     m->nb2 = nnb2;
@@ -1794,7 +1794,7 @@ static int streaming_rebuild(gk_map *m, uint32_t nnb2, uint32_t nlnb1, uint64_t 
     unsigned long long h_kept = 0;
     GK_HIP(ctx, hipMemsetAsync(&m->d_ctr->rebuild_kept, 0, 8, ctx->stream));
     void *nslots = nullptr;
-    if (hipMalloc(&nslots, ncap * slot_bytes(m->W, new_layout)) != hipSuccess) { (void)hipGetLastError(); return GK_OK; }    // (every slot is written below: no clear)
+    if (pool_malloc(ctx, &nslots, ncap * slot_bytes(m->W, new_layout)) != hipSuccess) { (void)hipGetLastError(); return GK_OK; }    // (every slot is written below: no clear)
     const int gc = (int)std::min<u64>((u64)nnb2 << nlnb1, (u64)ctx->cu_count * 16);
     hipError_t e = hipSuccess;
     if (m->W == 2) e = launch_compact<2, Slot<2>, Slot<2>>(m, nslots, nnb2, nlnb1, rounds, gc);
@@ -1805,16 +1805,16 @@ static int streaming_rebuild(gk_map *m, uint32_t nnb2, uint32_t nlnb1, uint64_t 
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(&h_kept, &m->d_ctr->rebuild_kept, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(nslots); return hip_fail(ctx, e, "streaming table rebuild"); }
+    if (e != hipSuccess) { (void)pool_free(ctx, nslots); return hip_fail(ctx, e, "streaming table rebuild"); }
     const u64 kept = h_kept;
     if (int rc = map_sync_counters(m)) {                   // a segment of the new table filled up (a sizing error): the old table stays
-        (void)hipFree(nslots);
+        (void)pool_free(ctx, nslots);
         return rc;
     }
     unsigned long long sz = kept;
     GK_HIP(ctx, hipMemcpyAsync(&m->d_ctr->size, &sz, sizeof(sz), hipMemcpyHostToDevice, ctx->stream));
     GK_HIP(ctx, hipStreamSynchronize(ctx->stream));         // (`sz` is a stack variable)
-    GK_HIP(ctx, hipFree(m->slots));
+    GK_HIP(ctx, pool_free(ctx, m->slots));
     m->slots = nslots;
     m->capacity = ncap;
     m->nb2 = nnb2;
@@ -1904,13 +1904,13 @@ int map_to_graph_layout(gk_map *m) {
     }
     // (another L1 fan-out, or no memory for the streaming form's second table... the rehash form needs one too)
     void *nslots = nullptr;
-    if (alloc_table(ctx, m->W, LAYOUT_GRAPH, ncap, &nslots) != GK_OK) { if (nslots) (void)hipFree(nslots); return fail(ctx, GK_E_CAPACITY, "cannot rebuild the table in the graph layout: " + ctx->err); }
+    if (alloc_table(ctx, m->W, LAYOUT_GRAPH, ncap, &nslots) != GK_OK) { (void)pool_free(ctx, nslots); return fail(ctx, GK_E_CAPACITY, "cannot rebuild the table in the graph layout: " + ctx->err); }
     launch_rehash(m, LAYOUT_GRAPH, nslots, nnb2, nlnb1);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(nslots); return hip_fail(ctx, e, "table rebuild (graph layout)"); }
-    if (int rc = map_sync_counters(m)) { (void)hipFree(nslots); return rc; }
-    GK_HIP(ctx, hipFree(m->slots));
+    if (e != hipSuccess) { (void)pool_free(ctx, nslots); return hip_fail(ctx, e, "table rebuild (graph layout)"); }
+    if (int rc = map_sync_counters(m)) { (void)pool_free(ctx, nslots); return rc; }
+    GK_HIP(ctx, pool_free(ctx, m->slots));
     m->slots = nslots; m->capacity = ncap; m->nb2 = nnb2; m->lnb1 = nlnb1; m->tombstones = 0; m->layout = LAYOUT_GRAPH;
     return GK_OK;
 }
@@ -1991,9 +1991,9 @@ int gk_map_trim(gk_map *m) {
     gk_ctx *ctx = m->ctx;
     GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-    for (int i = 0; i < 2; i++) { m->stage[i].valid = m->stage[i].armed = false; if (m->stage[i].d) { (void)hipFree(m->stage[i].d); m->stage[i].d = nullptr; m->stage[i].cap = 0; } }
-    if (m->d_offsets) { (void)hipFree(m->d_offsets); m->d_offsets = nullptr; m->offsets_bytes = 0; }
-    if (m->d_scratch) { (void)hipFree(m->d_scratch); m->d_scratch = nullptr; m->scratch_bytes = 0; }
+    for (int i = 0; i < 2; i++) { m->stage[i].valid = m->stage[i].armed = false; if (m->stage[i].d) { (void)pool_free(ctx, m->stage[i].d); m->stage[i].d = nullptr; m->stage[i].cap = 0; } }
+    if (m->d_offsets) { (void)pool_free(ctx, m->d_offsets); m->d_offsets = nullptr; m->offsets_bytes = 0; }
+    if (m->d_scratch) { (void)pool_free(ctx, m->d_scratch); m->d_scratch = nullptr; m->scratch_bytes = 0; }
     part_scratch_free(ctx, m->part);
     m->part = nullptr;
     pool_release(ctx);                  // "release" means back to the device, not parked in the context's pool

@@ -188,7 +188,7 @@ int vm_check(const gk_vmap *m) {
 }
 
 int vm_alloc_table(gk_ctx *ctx, int W, u64 cap, void **out) {
-    hipError_t e = hipMalloc(out, cap * slot_bytes(W));
+    hipError_t e = pool_malloc(ctx, out, cap * slot_bytes(W));
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, GK_E_CAPACITY, std::string("value map: cannot allocate table: ") + hipGetErrorString(e)); }
     if (W == 1) hipLaunchKernelGGL(k_vm_clear<1>, dim3(vgrid(ctx, cap / 4)), dim3(BLOCK), 0, ctx->stream, (Slot<1> *)*out, cap);
     else hipLaunchKernelGGL(k_vm_clear<2>, dim3(vgrid(ctx, cap / 4)), dim3(BLOCK), 0, ctx->stream, (Slot<2> *)*out, cap);
@@ -222,7 +222,7 @@ int vm_reserve(gk_vmap *m, u64 extra) {
     uint64_t ncap;
     plan_segments(m->W, std::max<u64>((u64)((double)(m->size + extra) / target) + 1, m->capacity + m->capacity / 2), &nnb2, &nlnb1, &ncap);
     void *nslots = nullptr;
-    if (int rc = vm_alloc_table(ctx, m->W, ncap, &nslots)) { if (nslots) (void)hipFree(nslots); return rc; }
+    if (int rc = vm_alloc_table(ctx, m->W, ncap, &nslots)) { (void)pool_free(ctx, nslots); return rc; }
     if (m->W == 1)
         hipLaunchKernelGGL(k_vm_rehash<1>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<1> *)m->slots, m->capacity,
                            Table<1>{(Slot<1> *)nslots, nnb2, nlnb1, 0u}, m->d_ctr);
@@ -230,9 +230,9 @@ int vm_reserve(gk_vmap *m, u64 extra) {
         hipLaunchKernelGGL(k_vm_rehash<2>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<2> *)m->slots, m->capacity,
                            Table<2>{(Slot<2> *)nslots, nnb2, nlnb1, m->k == 64 ? 1u : 0u}, m->d_ctr);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { (void)hipFree(nslots); return hip_fail(ctx, e, "value map rehash"); }
-    if (int rc = vm_sync(m)) { (void)hipFree(nslots); return rc; }          // a failed rehash leaves the old table in place
-    GK_HIP(ctx, hipFree(m->slots));
+    if (e != hipSuccess) { (void)pool_free(ctx, nslots); return hip_fail(ctx, e, "value map rehash"); }
+    if (int rc = vm_sync(m)) { (void)pool_free(ctx, nslots); return rc; }          // a failed rehash leaves the old table in place
+    GK_HIP(ctx, pool_free(ctx, m->slots));
     m->slots = nslots; m->capacity = ncap; m->nb2 = nnb2; m->lnb1 = nlnb1;
     return GK_OK;
 }
@@ -246,18 +246,6 @@ int vm_check_keys(const gk_vmap *m, const uint64_t *lo, const uint64_t *hi, uint
     }
     return GK_OK;
 }
-
-struct DevBuf {      // a few device arrays for one call, freed together
-    gk_ctx *ctx;
-    explicit DevBuf(gk_ctx *c) : ctx(c) {}
-    std::vector<void *> ptrs;
-    ~DevBuf() { for (void *p : ptrs) if (p) (void)hipFree(p); }
-    template <class T> hipError_t get(T **p, u64 n) {
-        hipError_t e = hipMalloc((void **)p, std::max<u64>(n, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
 
 }  // namespace
 
@@ -300,14 +288,14 @@ int gk_vmap_create(gk_ctx *ctx, int k, uint64_t capacity_hint, gk_vmap **out) {
     plan_segments(m->W, (uint64_t)((double)std::max<uint64_t>(capacity_hint, 1024) / (k == 64 ? 0.35 : 0.5)) + 1, &m->nb2, &m->lnb1, &m->capacity);
     int rc = vm_alloc_table(ctx, m->W, m->capacity, &m->slots);
     if (rc == GK_OK) {
-        hipError_t e = hipMalloc((void **)&m->d_ctr, 16);
+        hipError_t e = pool_malloc(ctx, &m->d_ctr, 16);
         if (e == hipSuccess) e = hipMemsetAsync(m->d_ctr, 0, 16, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) rc = hip_fail(ctx, e, "gk_vmap_create");
     }
     if (rc != GK_OK) {
-        if (m->slots) (void)hipFree(m->slots);
-        if (m->d_ctr) (void)hipFree(m->d_ctr);
+        (void)pool_free(ctx, m->slots);
+        (void)pool_free(ctx, m->d_ctr);
         delete m;
         return rc;
     }
@@ -320,8 +308,8 @@ void gk_vmap_destroy(gk_vmap *m) {
     gk_ctx *ctx = m->ctx;
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->stream);
-    if (m->slots) (void)hipFree(m->slots);
-    if (m->d_ctr) (void)hipFree(m->d_ctr);
+    (void)pool_free(ctx, m->slots);
+    (void)pool_free(ctx, m->d_ctr);
     delete m;
 }
 
@@ -340,7 +328,7 @@ int gk_vmap_put_new_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, co
     if (n == 0) return GK_OK;
     if (!values) return fail(ctx, GK_E_INVALID, "null value array");
     if (int rc = vm_check_keys(m, lo, hi, n)) return rc;
-    DevBuf b(ctx);
+    DevScratch b(ctx);
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_val = nullptr;
     hipError_t e = b.get(&d_lo, n);
     if (e == hipSuccess && m->W == 2) e = b.get(&d_hi, n);
@@ -360,7 +348,7 @@ int gk_vmap_update_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, con
     if (!values) return fail(ctx, GK_E_INVALID, "null value array");
     if (int rc = vm_check_keys(m, lo, hi, n)) return rc;
     if (int rc = vm_reserve(m, n)) return rc;
-    DevBuf b(ctx);
+    DevScratch b(ctx);
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_val = nullptr, *d_slot = nullptr;
     u32 *d_win = nullptr;
     hipError_t e = b.get(&d_lo, n);
@@ -394,7 +382,7 @@ int gk_vmap_get_all_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, ui
     offsets_out[0] = 0;
     if (n == 0) return GK_OK;
     if (int rc = vm_check_keys(m, lo, hi, n)) return rc;
-    DevBuf b(ctx);
+    DevScratch b(ctx);
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_out = nullptr;
     u32 *d_cnt = nullptr;
     unsigned long long *d_off = nullptr;
@@ -436,7 +424,7 @@ int gk_vmap_get_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, uint64
     if (n == 0) return GK_OK;
     if (!values_out) return fail(ctx, GK_E_INVALID, "null value buffer");
     if (int rc = vm_check_keys(m, lo, hi, n)) return rc;
-    DevBuf b(ctx);
+    DevScratch b(ctx);
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_out = nullptr;
     u32 *d_cnt = nullptr;
     unsigned long long *d_off = nullptr;
@@ -474,7 +462,7 @@ int gk_vmap_export(gk_vmap *m, uint64_t *lo, uint64_t *hi, uint64_t *values, uin
     if (m->size > cap) return fail(ctx, GK_E_CAPACITY, "export buffer too small: need " + std::to_string(m->size));
     if (m->size == 0) return GK_OK;
     if (!lo || !values || (m->W == 2 && !hi)) return fail(ctx, GK_E_INVALID, "null export buffer");
-    DevBuf b(ctx);
+    DevScratch b(ctx);
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_val = nullptr;
     unsigned long long *d_cur = nullptr;
     const u64 cnt = m->size;
