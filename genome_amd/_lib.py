@@ -166,6 +166,13 @@ SIGNATURES = {
     "gk_fastq_count": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, u64p]),
     "gk_fastq_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p]),
     "gk_fastq_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "gk_fasta_check_create": (C.c_int, [vp, vp, C.c_int, C.c_uint64, C.POINTER(vp)]),
+    "gk_fasta_check_destroy": (None, [vp]),
+    "gk_fasta_check_feed": (C.c_int, [vp, vp, C.c_size_t, C.c_int]),
+    "gk_fasta_check_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
+    "gk_fasta_check_missing": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p, C.c_uint64, u64p]),
+    "gk_fasta_check_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "gk_graph_contig_stats": (C.c_int, [vp, C.c_uint64, u64p, u64p, u64p, u64p, u64p]),
     "gk_synth_reads_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
     "gk_prefilter_create": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp)]),
     "gk_prefilter_destroy": (None, [vp]),

@@ -1,0 +1,101 @@
+"""CheckGraph (S/scripts/CheckGraph.scala) on the GPU: the contig statistics of a graph and every k-window of a reference FASTA
+looked up in its position map.
+
+The rules of the FASTA check and its deviations from the reference are stated in include/genome_amd.h ("FASTA check").
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+from . import _lib as L
+from .fastq import _text, iter_pieces
+
+COUNTERS = ("lines", "records", "bases", "valid_bases", "windows", "found", "missing", "covered_bases", "short_lines")
+
+
+class FastaCheck:
+    """A FASTA check in progress (gk_fasta_check): feed the text in pieces of any size, the last one with last=True.
+
+    vmap: the position map to look the windows up in (Graph.getGraphMap); k is the map's.  per_line: windows never cross a line
+    end (the reference's literal rule); otherwise the sequence lines of a record are joined.  max_missing: how many not-found
+    windows to keep, the first ones in stream order."""
+
+    def __init__(self, ctx, vmap, per_line: bool = False, max_missing: int = 0):
+        if not ctx.h:
+            raise ValueError("context is closed")
+        self.ctx, self.vmap, self.k = ctx, vmap, vmap.k
+        self.h = L.vp()
+        L.check(L.lib().gk_fasta_check_create(ctx.h, vmap.h, 1 if per_line else 0, int(max_missing), C.byref(self.h)), ctx.h)
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:               # (a handle that outlived its context is dropped, not followed)
+                L.lib().gk_fasta_check_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _handle(self):
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the FASTA check is closed")
+        return self.h
+
+    def feed(self, text, last: bool = False):
+        buf = _text(text)
+        L.check(L.lib().gk_fasta_check_feed(self._handle(), buf.ctypes.data if buf.size else None, buf.size, 1 if last else 0), self.ctx.h)
+
+    def stats(self) -> dict:
+        v = [C.c_uint64() for _ in COUNTERS]
+        L.check(L.lib().gk_fasta_check_stats(self._handle(), *[C.byref(x) for x in v]), self.ctx.h)
+        return dict(zip(COUNTERS, (x.value for x in v)))
+
+    def missing(self) -> list:
+        """[(byte offset of the window's first base, its 0-based line, its 0-based column, lo, hi)], in stream order"""
+        n = C.c_uint64()
+        L.check(L.lib().gk_fasta_check_missing(self._handle(), None, None, None, None, None, 0, C.byref(n)), self.ctx.h)
+        a = [np.zeros(max(n.value, 1), np.uint64) for _ in range(5)]
+        L.check(L.lib().gk_fasta_check_missing(self._handle(), *[L.ptr(x, C.c_uint64) for x in a], n.value, C.byref(n)), self.ctx.h)
+        return [tuple(int(x[i]) for x in a) for i in range(n.value)]
+
+    def last_ms(self) -> dict:
+        out = (C.c_float * 4)()
+        L.check(L.lib().gk_fasta_check_last_ms(self._handle(), out), self.ctx.h)
+        return dict(zip(("upload", "parse", "lookup", "total"), (float(x) for x in out)))
+
+
+def check_graph(graph, fasta, longer_than: int = 200, per_line: bool = False, max_missing: int = 0, piece_bytes: int = 256 << 20) -> dict:
+    """CheckGraph.startup for a graph and a FASTA file (a path, `.gz` read with the standard library) or its bytes: one dict with
+    k, the contig statistics (:37-41), the check's counters (:48-55), the coverage and, with max_missing, the missing list."""
+    out = {"k": graph.k, "longer_than": int(longer_than), "per_line": bool(per_line)}
+    out["contigs"] = graph.contigStats(longer_than)
+    vm = graph.getGraphMap()
+    try:
+        with FastaCheck(graph.ctx, vm, per_line, max_missing) as fc:
+            if isinstance(fasta, (str, os.PathLike)):
+                for piece, last in iter_pieces(fasta, piece_bytes):
+                    fc.feed(piece, last=last)
+            else:
+                fc.feed(fasta, last=True)
+            st = fc.stats()
+            out.update(st)
+            out["coverage"] = st["covered_bases"] / st["valid_bases"] if st["valid_bases"] else 0.0
+            out["missing_list"] = [{"offset": o, "line": ln, "column": c, "lo": lo, "hi": hi} for o, ln, c, lo, hi in fc.missing()]
+    finally:
+        vm.close()
+    return out

@@ -20,13 +20,10 @@
 #include <cstring>
 #include <string>
 
-#include "gk_scan.h"
-#include "gk_tile.h"
+#include "gk_text.h"
 
 namespace {
 
-constexpr u32 FQ_TILE = 16384;                          // text bytes per workgroup of the line-end passes
-constexpr u32 FQ_BLOCK = 256;
 constexpr u64 FQ_MAX_RECORD = 64ull << 20;              // one record's text at most (a deliberate limit; GK_E_FORMAT beyond)
 constexpr u64 FQ_SLICE_DEFAULT = 128ull << 20;          // text bytes uploaded per device chunk
 constexpr u64 FQ_HEAD_MIN = 1ull << 20;                 // room in front of a slice for the carried tail (grows on demand)
@@ -62,58 +59,8 @@ struct FqHost {                  // pinned landing area of the per-chunk reads
     unsigned long long out_bytes, windows;
 };
 
-__device__ __forceinline__ u64 umin(u64 a, u64 b) { return a < b ? a : b; }
 __device__ __forceinline__ bool fq_acgt(u32 c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 __device__ __forceinline__ u32 fq_code(u32 c) { return c == 'G' ? 1u : c == 'C' ? 2u : c == 'T' ? 3u : 0u; }     // A0 G1 C2 T3
-
-// first byte of line j: 0, or past line j-1's terminator ("\r\n" is one; E == n marks an unterminated last line)
-__device__ __forceinline__ u64 fq_line_start(const uint8_t *__restrict__ T, u64 n, const u32 *__restrict__ E, u64 j) {
-    if (j == 0) return 0;
-    const u64 e = E[j - 1];
-    if (e >= n) return n;
-    return e + ((T[e] == '\r' && e + 1 < n && T[e + 1] == '\n') ? 2 : 1);
-}
-
-// pass 0: terminators per tile; pass 1: their positions at tile_off[tile].  A terminator is the byte a line ends at: '\r', or
-// '\n' not preceded by '\r' (Java BufferedReader.readLine).  The byte before the tile comes along for that look-back.
-template <int PASS>
-__global__ __launch_bounds__(FQ_BLOCK) void k_fq_terms(const uint8_t *__restrict__ T, u64 n, u32 *__restrict__ tile_cnt,
-                                                        const unsigned long long *__restrict__ tile_off, u32 *__restrict__ E) {
-    __shared__ u32 s_tile[(FQ_TILE + 64) / 4];
-    __shared__ u32 s_wcnt[FQ_BLOCK / 64];
-    const u64 g0 = (u64)blockIdx.x * FQ_TILE, g1 = umin(n, g0 + FQ_TILE);
-    const u64 a0 = stage_tile(s_tile, T, g0 ? g0 - 1 : 0, g1);
-    __syncthreads();
-    const uint8_t *tb = reinterpret_cast<const uint8_t *>(s_tile);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr u32 PER_WAVE = FQ_TILE / (FQ_BLOCK / 64);
-    const u64 w0 = g0 + (u64)wave * PER_WAVE;
-    auto is_term = [&](u64 x) -> bool {
-        if (x >= g1) return false;
-        const u32 c = tb[x - a0];
-        return c == '\r' || (c == '\n' && !(x > 0 && tb[x - 1 - a0] == '\r'));
-    };
-    u32 cnt = 0;
-    for (u32 s = 0; s < PER_WAVE; s += 64) cnt += (u32)__popcll(__ballot(is_term(w0 + s + lane)));
-    if (PASS == 0) {
-        if (lane == 0) s_wcnt[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_wcnt[0] + s_wcnt[1] + s_wcnt[2] + s_wcnt[3];
-        return;
-    }
-    if (lane == 0) s_wcnt[wave] = cnt;
-    __syncthreads();
-    u64 o = tile_off[blockIdx.x];
-    for (int w = 0; w < wave; w++) o += s_wcnt[w];
-    const unsigned long long below = (1ull << lane) - 1ull;
-    for (u32 s = 0; s < PER_WAVE; s += 64) {
-        const u64 x = w0 + s + lane;
-        const bool t = is_term(x);
-        const unsigned long long mask = __ballot(t);
-        if (t) E[o + (u64)__popcll(mask & below)] = (u32)x;
-        o += (u64)__popcll(mask);
-    }
-}
 
 // one lane: which records the chunk completes and emits, and the end-of-input rules (Convert2bin.scala:51-73)
 __global__ void k_fq_plan(const uint8_t *__restrict__ T, u64 n, u32 *__restrict__ E, u64 terms, int last, int interleaved, u64 rec_base,

@@ -1527,6 +1527,39 @@ __global__ void k_nidx_insert(GraphView g, u32 n, u64 h) {
 // =============================================================================================
 // host side
 // =============================================================================================
+// ---- contig statistics (CheckGraph.scala:37-41): one reduction, then a radix select over the 64-bit lengths by histogram passes ----
+// out: [0] count, [1] sum, [2] max over the live edges longer than `longer_than`
+__global__ __launch_bounds__(BLOCK) void k_contig_reduce(GraphView g, u64 longer_than, unsigned long long *out) {
+    unsigned long long c = 0, s = 0, m = 0;
+    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK) {
+        const u64 len = g.e_len[e];
+        if (g.e_alive[e] && len > longer_than) { c++; s += len; m = len > m ? len : m; }
+    }
+    for (int d = 32; d; d >>= 1) {
+        c += __shfl_down(c, d); s += __shfl_down(s, d);
+        const unsigned long long o = __shfl_down(m, d);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & 63) == 0 && c) { atomicAdd(&out[0], c); atomicAdd(&out[1], s); atomicMax(&out[2], m); }
+}
+// one level of both selects: the byte at `shift` of the lengths whose higher bits equal a prefix.  hist[0..255] counts the lengths
+// under the median's prefix (a plain rank), hist[256..511] sums the lengths under the N50's prefix (a length-weighted rank).
+__global__ __launch_bounds__(BLOCK) void k_contig_hist(GraphView g, u64 longer_than, int shift, u64 prefix_med, u64 prefix_n50, unsigned long long *hist) {
+    __shared__ unsigned long long s_h[512];
+    for (int i = threadIdx.x; i < 512; i += BLOCK) s_h[i] = 0;
+    __syncthreads();
+    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK) {
+        const u64 len = g.e_len[e];
+        if (!g.e_alive[e] || len <= longer_than) continue;
+        const u64 above = shift >= 56 ? 0 : len >> (shift + 8);
+        const u32 b = (u32)(len >> shift) & 255u;
+        if (above == prefix_med) atomicAdd(&s_h[b], 1ull);
+        if (above == prefix_n50) atomicAdd(&s_h[256 + b], (unsigned long long)len);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 512; i += BLOCK) if (s_h[i]) atomicAdd(&hist[i], s_h[i]);
+}
+
 int ggrid(const gk_ctx *ctx, u64 items) {
     u64 blocks = (items + BLOCK - 1) / BLOCK;
     if (blocks < 1) blocks = 1;
@@ -2005,6 +2038,49 @@ int gk_graph_counts(gk_graph *g, uint64_t *nodes, uint64_t *edges, uint64_t *tot
     if (nodes) *nodes = g->live_nodes;
     if (edges) *edges = g->live_edges;
     if (total_edge_len) *total_edge_len = g->live_len;
+    return GK_OK;
+}
+
+int gk_graph_contig_stats(gk_graph *g, uint64_t longer_than, uint64_t *count, uint64_t *sum, uint64_t *median, uint64_t *n50, uint64_t *max) {
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    uint64_t *outs[5] = {count, sum, median, n50, max};
+    for (uint64_t *o : outs) if (o) *o = 0;
+    if (g->v.n_edges == 0) return GK_OK;
+    DevScratch tmp(ctx);
+    unsigned long long *d = nullptr, h[512];                 // d: [0..2] the reduction, [8..519] one level's histograms
+    GK_HIP(ctx, tmp.get(&d, 8 + 512));
+    GK_HIP(ctx, hipMemsetAsync(d, 0, 64, ctx->stream));
+    const int grid = ggrid(ctx, g->v.n_edges);
+    hipLaunchKernelGGL(k_contig_reduce, dim3(grid), dim3(BLOCK), 0, ctx->stream, g->v, (u64)longer_than, d);
+    GK_HIP(ctx, hipGetLastError());
+    GK_HIP(ctx, hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const u64 cnt = h[0], total = h[1], mx = h[2];
+    if (cnt == 0) return GK_OK;
+    // sorted[count / 2] ascending; and, lengths descending, the first at which the running sum reaches half the total (rounded up)
+    u64 rank = cnt / 2, acc = 0, pm = 0, pn = 0;
+    const u64 half = total / 2 + (total & 1);
+    int shift = 56;
+    while (shift > 0 && (mx >> shift) == 0) shift -= 8;      // (the bytes above the maximum's top byte are zero in every length)
+    for (; shift >= 0; shift -= 8) {
+        GK_HIP(ctx, hipMemsetAsync(d + 8, 0, 512 * 8, ctx->stream));
+        hipLaunchKernelGGL(k_contig_hist, dim3(grid), dim3(BLOCK), 0, ctx->stream, g->v, (u64)longer_than, shift, pm, pn, d + 8);
+        GK_HIP(ctx, hipGetLastError());
+        GK_HIP(ctx, hipMemcpyAsync(h, d + 8, 512 * 8, hipMemcpyDeviceToHost, ctx->stream));
+        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        int bm = -1, bn = -1;
+        for (int b = 0; b < 256 && bm < 0; b++) { if (rank < h[b]) bm = b; else rank -= h[b]; }
+        for (int b = 255; b >= 0 && bn < 0; b--) { if (acc + h[256 + b] >= half) bn = b; else acc += h[256 + b]; }
+        if (bm < 0 || bn < 0) return fail(ctx, GK_E_STATE, "gk_graph_contig_stats: the select lost its rank (the graph changed under the call?)");
+        pm = (pm << 8) | (u64)bm;
+        pn = (pn << 8) | (u64)bn;
+    }
+    if (count) *count = cnt;
+    if (sum) *sum = total;
+    if (median) *median = pm;
+    if (n50) *n50 = pn;
+    if (max) *max = mx;
     return GK_OK;
 }
 

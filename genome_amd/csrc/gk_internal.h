@@ -58,6 +58,7 @@ struct gk_ctx {
     int hook_p4_wide = -1;           // exact fine level, 8-byte keys: -1 auto (by nb2), 0 sort 4096 keys at a time, 1 sort 8192 (1024 threads)
     int hook_fine_exact = -1;        // -1 auto, 0 never unless forced by the data path, 1 always (A/B of the two fine levels)
     int64_t hook_fastq_chunk = 0;    // test hook: text bytes per device chunk of gk_fastq_convert / gk_fastq_count (0: 128 MiB)
+                                     // and per device slice of gk_fasta_check_feed (0: 64 MiB)
     // Block pool (gk::pool_malloc / pool_free): the big device buffers — tables, key scratch, graph arrays — are handed back
     // here instead of hipFree and reused by size.  hipMalloc / hipFree of multi-GB blocks cost milliseconds to seconds on this
     // platform and freed VRAM is scrubbed in the background on the copy engines: a second count over the same map paid 20 ms of

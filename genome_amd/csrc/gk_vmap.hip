@@ -263,6 +263,8 @@ int vmap_put_new_dev(gk_vmap *m, const uint64_t *d_lo, const uint64_t *d_hi, con
 }
 int vmap_k(const gk_vmap *m) { return m->k; }
 gk_ctx *vmap_ctx(const gk_vmap *m) { return m->ctx; }
+// the table's geometry, for a kernel of another translation unit that probes it (gk_fasta.hip); tagged and the slot width follow from k
+void vmap_table(const gk_vmap *m, void **slots, uint32_t *nb2, uint32_t *lnb1) { *slots = m->slots; *nb2 = m->nb2; *lnb1 = m->lnb1; }
 // getAll for keys already in HBM, results left in HBM (the paired-end stage, gk_pairs.hip): pass 0 counts into d_cnt[n]; the
 // caller turns the counts into CSR offsets d_off[n + 1] and allocates d_out; pass 1 fills.  Stream-ordered, nothing is waited for.
 int vmap_get_all_dev(gk_vmap *m, const uint64_t *d_lo, const uint64_t *d_hi, uint64_t n, const unsigned long long *d_off, uint32_t *d_cnt, uint64_t *d_out) {

@@ -41,6 +41,15 @@ class HipGraph:
         L.check(L.lib().gk_graph_counts(self.h, C.byref(n), C.byref(e), C.byref(ln)), self.ctx.h)
         return n.value, e.value, ln.value
 
+    def contigStats(self, longer_than: int = 200) -> dict:
+        """CheckGraph.scala:37-41 over the live edges longer than `longer_than`: count, summed length, median (= sorted[count/2],
+        the reference's "N50"), the real N50 and the maximum; all 0 when there is none.  Computed on the device."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        v = [C.c_uint64() for _ in range(5)]
+        L.check(L.lib().gk_graph_contig_stats(self.h, int(longer_than), *[C.byref(x) for x in v]), self.ctx.h)
+        return dict(zip(("count", "sum", "median", "n50", "max"), (x.value for x in v)))
+
     def simplifyGraph(self):                       # Graph.scala:211-230
         L.check(L.lib().gk_graph_simplify(self.h), self.ctx.h)
 

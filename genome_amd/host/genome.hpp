@@ -374,6 +374,39 @@ class PositionMap {
     gk_vmap *h_ = nullptr;
 };
 
+// gk_fasta_check: every k-window of a FASTA text looked up in a position map, fed in pieces of any size (the rules:
+// include/genome_amd.h, "FASTA check")
+class FastaCheck {
+  public:
+    struct Stats { uint64_t lines = 0, records = 0, bases = 0, validBases = 0, windows = 0, found = 0, missing = 0, coveredBases = 0, shortLines = 0; };
+    struct Missing { uint64_t offset, line, column, lo, hi; };
+    FastaCheck(Context &ctx, PositionMap &positions, bool perLine = false, uint64_t maxMissing = 0) : ctx_(ctx.handle()) {
+        check(gk_fasta_check_create(ctx_, positions.handle(), perLine ? 1 : 0, maxMissing, &h_), ctx_);
+    }
+    ~FastaCheck() { gk_fasta_check_destroy(h_); }
+    FastaCheck(const FastaCheck &) = delete;
+    FastaCheck &operator=(const FastaCheck &) = delete;
+    void feed(const char *text, size_t n, bool last) { check(gk_fasta_check_feed(h_, text, n, last ? 1 : 0), ctx_); }
+    Stats stats() const {
+        Stats s;
+        check(gk_fasta_check_stats(h_, &s.lines, &s.records, &s.bases, &s.validBases, &s.windows, &s.found, &s.missing, &s.coveredBases, &s.shortLines), ctx_);
+        return s;
+    }
+    std::vector<Missing> missing() const {                                          // the first maxMissing not-found windows, in stream order
+        uint64_t n = 0;
+        check(gk_fasta_check_missing(h_, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n), ctx_);
+        std::vector<uint64_t> a(5 * n);
+        if (n) check(gk_fasta_check_missing(h_, a.data(), a.data() + n, a.data() + 2 * n, a.data() + 3 * n, a.data() + 4 * n, n, &n), ctx_);
+        std::vector<Missing> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = Missing{a[i], a[n + i], a[2 * n + i], a[3 * n + i], a[4 * n + i]};
+        return out;
+    }
+
+  private:
+    gk_ctx *ctx_ = nullptr;
+    gk_fasta_check *h_ = nullptr;
+};
+
 // pathsMap + badPairs of GraphSimplifier.scala:209-211
 class Support {
   public:
@@ -484,6 +517,14 @@ class Graph {
         uint64_t rm = 0, nn = 0;
         check(gk_graph_split_by_support(h_, support.handle(), cutoff, &rm, &nn), ctx_.handle());
         return {rm, nn};
+    }
+    // CheckGraph.scala:37-41 over the live edges longer than longerThan: count, summed length, median (sorted[count / 2], the
+    // reference's "N50"), the real N50, the maximum; computed on the device
+    struct ContigStats { uint64_t count = 0, sum = 0, median = 0, n50 = 0, max = 0; };
+    ContigStats contigStats(uint64_t longerThan = 200) const {
+        ContigStats c;
+        check(gk_graph_contig_stats(h_, longerThan, &c.count, &c.sum, &c.median, &c.n50, &c.max), ctx_.handle());
+        return c;
     }
     std::tuple<uint64_t, uint64_t, uint64_t> counts() const {
         uint64_t n = 0, e = 0, l = 0;

@@ -347,6 +347,11 @@ int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup);
 int gk_graph_build(gk_map *m, gk_graph **out);
 void gk_graph_destroy(gk_graph *g);
 int gk_graph_counts(gk_graph *g, uint64_t *nodes, uint64_t *edges, uint64_t *total_edge_len); /* live */
+/* CheckGraph.scala:37-41 over the live edges with length > longer_than (the reference: 200).  median = sorted[count/2], which is
+ * what the reference logs as "N50"; n50 = the real one: lengths descending, the first length at which twice the running sum
+ * reaches the total.  count == 0: everything 0.  Both strands' edges are counted, as in the reference.  One reduction and a radix
+ * select by histogram passes on the device: the lengths are neither downloaded nor sorted. */
+int gk_graph_contig_stats(gk_graph *g, uint64_t longer_than, uint64_t *count, uint64_t *sum, uint64_t *median, uint64_t *n50, uint64_t *max);
 int gk_graph_simplify(gk_graph *g);          /* MapGraph.simplifyGraph :211-230 */
 int gk_graph_remove_bubbles(gk_graph *g);    /* Graph.removeBubbles :125-149 */
 /* MapGraph.removeEdge :191-195 for the edges leaving start[i] with first base base[i] */
@@ -551,6 +556,51 @@ int gk_fastq_stats(const gk_fastq *fq, uint64_t *pairs, uint64_t *short_pairs, u
                    uint64_t *carried_bytes);
 /* wall ms of the last call: {host staging + upload, parse kernels, download or count, whole call} */
 int gk_fastq_last_ms(const gk_fastq *fq, float *ms4);
+
+/* ---- FASTA check: the k-window loop of CheckGraph (S/scripts/CheckGraph.scala:48-55), on the device ----------------------
+ * Every k-window of a reference FASTA is looked up in a position map (normally gk_graph_position_map of the graph under test);
+ * k = gk_vmap_k of that map.  The text is fed in pieces of any size, as for the FASTQ parser.  The rules:
+ *   - Lines are readLine lines exactly as in the FASTQ section: a line ends at '\n', at '\r', or at "\r\n" (one terminator, also
+ *     when it is split between two feeds).  A non-empty unterminated tail at the end of the input is a line.  `lines` counts them.
+ *   - A line whose first character is '>' is a header (:48).  A header starts a new record; sequence lines before the first
+ *     header belong to record 0.  `records` = headers, plus one if a sequence character precedes the first header.
+ *   - Every character of every other line is a sequence character (`bases`).  It is valid only if it is an UPPERCASE A, G, C or T
+ *     (Base.fromChar, :49; `valid_bases`).  'N', lowercase and bytes >= 0x80 are invalid; they are not an error.
+ *   - A window is k consecutive sequence characters, all valid, inside one line (per_line != 0: the reference's literal rule,
+ *     line.sliding(k)) or inside one record (per_line == 0: the record's sequence lines are joined, so windows cross line ends
+ *     but never a header).  `windows` counts them.  A window is looked up as it reads, not canonicalised (getGraphMap stores
+ *     node.seq and the k-mers along every edge as they are, and the graph holds both strands).  The lookup is `contains` (:51):
+ *     the first slot of the probe sequence that holds the key, as gk_vmap_get_batch.  found + missing == windows.
+ *   - `covered_bases` = sequence characters that lie inside at least one found window.  covered_bases / valid_bases is the
+ *     "coverage" figure quoted for the reference.
+ *   - `short_lines` = non-header lines of 1..k-1 characters.  DEVIATION: the reference's sliding(k) yields such a line whole and
+ *     logs it as "Not found"; here it has no window (in either mode's own terms) and is counted in short_lines, whatever its
+ *     characters.
+ *   - The missing list holds the first max_missing not-found windows in stream order (an ordered compaction: the same list on
+ *     every run and for every way of cutting the input into feeds).  Each entry: the byte offset of the window's first base in
+ *     the whole input, that base's 0-based line and 0-based column, and the k-mer (base i at bits 2i of lo, then hi).
+ *     DEVIATION: the reference logs line.length; a line can outlast a feed, so line and column are reported instead.
+ *   - No text is kept between feeds (an unwrapped chromosome on one line needs no buffering): the handle carries the last k-1
+ *     sequence codes and the line state.  Long feeds are cut into device slices; the next slice's upload runs on the context's
+ *     copy stream beside the current slice's kernels.
+ * Errors: a null handle is GK_E_INVALID; a feed after last != 0 is GK_E_STATE; after any other error the handle refuses further
+ * feeds with GK_E_STATE.  Device memory comes from the context's block pool (gk_ctx_mem_stats): each feed's buffers are returned
+ * when the feed returns, the rest by gk_fasta_check_destroy.  The position map must outlive the handle and not change under it. */
+typedef struct gk_fasta_check gk_fasta_check;
+/* positions: any gk_vmap of this context.  max_missing: how many not-found windows to keep (0 = none). */
+int gk_fasta_check_create(gk_ctx *ctx, gk_vmap *positions, int per_line, uint64_t max_missing, gk_fasta_check **out);
+void gk_fasta_check_destroy(gk_fasta_check *fc);
+/* the next piece of text (pageable or pinned); last != 0: the input ends with it */
+int gk_fasta_check_feed(gk_fasta_check *fc, const char *text, size_t nbytes, int last);
+/* the counters so far (any may be NULL).  Windows that start in the last k-1 sequence characters fed so far are evaluated by
+ * the next feed, and an unterminated last line is counted when the input ends: the figures are final after last != 0. */
+int gk_fasta_check_stats(const gk_fasta_check *fc, uint64_t *lines, uint64_t *records, uint64_t *bases, uint64_t *valid_bases,
+                         uint64_t *windows, uint64_t *found, uint64_t *missing, uint64_t *covered_bases, uint64_t *short_lines);
+/* the missing list: *n = entries held (<= max_missing); the first min(*n, cap) are written (any array may be NULL) */
+int gk_fasta_check_missing(const gk_fasta_check *fc, uint64_t *text_offset, uint64_t *line, uint64_t *column,
+                           uint64_t *lo, uint64_t *hi, uint64_t cap, uint64_t *n);
+/* wall ms of the last feed: {host staging + upload, parse kernels, lookup kernels, whole call} */
+int gk_fasta_check_last_ms(const gk_fasta_check *fc, float *ms4);
 
 /* ---- synthetic reads (bench / tests) ---------------------------------------- */
 /* Fill dev_records with nreads fixed-length `.bin` records generated on device, bit-identical to
