@@ -789,8 +789,7 @@ static int dist_gather(gk_dist *d, gk_map *local, gk_map **full, bool classify) 
             if (!my_rc) {
                 my_rc = dclass_count(local, d->rank, P, c * CHS, (c + 1) * CHS, d_dc + 2 * 64);
                 if (!my_rc) {
-                    hipError_t e = hipMemcpyAsync(h_send, d_dc + 2 * 64, P * 8, hipMemcpyDeviceToHost, ctx->stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+                    const hipError_t e = read_back(ctx, h_send, d_dc + 2 * 64, P);
                     if (e != hipSuccess) my_rc = hip_fail(ctx, e, "gk_dist_gather_map: classify counts");
                 }
                 if (my_rc) my_err = ctx->err;

@@ -327,16 +327,6 @@ __global__ void k_fa_finish(FaState *st, int k) {
     st->nc = 0;
 }
 
-using clk = std::chrono::steady_clock;
-double ms_since(clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); }
-
-bool fa_is_pinned(const void *p) {
-    unsigned int flags = 0;
-    const bool ok = hipHostGetFlags(&flags, const_cast<void *>(p)) == hipSuccess;
-    if (!ok) (void)hipGetLastError();
-    return ok;
-}
-
 }  // namespace
 
 struct gk_fasta_check {
@@ -353,9 +343,7 @@ struct gk_fasta_check {
     unsigned long long *d_miss = nullptr;     // five arrays of miss_cap entries: offset, line, column, lo, hi
     u64 miss_cap = 0;
     unsigned long long *h = nullptr;          // pinned: [0..13] FaState's counters, [14] terminators, [15] kept characters
-    uint8_t *h_stage[2] = {nullptr, nullptr}; // pinned staging of pageable text
-    u64 h_stage_cap = 0;
-    hipEvent_t up0[2] = {nullptr, nullptr}, up1[2] = {nullptr, nullptr};
+    TextUpload up;                            // the copy-stream upload of a slice (gk_text.h)
     float ms[4] = {0, 0, 0, 0};
 };
 
@@ -395,30 +383,6 @@ FaCut fa_cut(const char *text, u64 nbytes, u64 pos, bool prev_cr, u64 slice_max)
     return FaCut{pos, std::min<u64>(nbytes - pos, slice_max)};
 }
 
-// text [src, src + bytes) -> d_dst on the copy stream (pageable text goes through a pinned staging buffer first)
-int fa_upload(gk_fasta_check *fc, int b, uint8_t *d_dst, const char *src, u64 bytes, bool pinned, double *host_ms) {
-    gk_ctx *ctx = fc->ctx;
-    const void *from = src;
-    if (!pinned) {
-        if (fc->h_stage_cap < bytes) {
-            FA_HIP(fc, hipStreamSynchronize(ctx->copy_stream));
-            for (int i = 0; i < 2; i++) { if (fc->h_stage[i]) (void)hipHostFree(fc->h_stage[i]); fc->h_stage[i] = nullptr; }
-            fc->h_stage_cap = 0;
-            const u64 cap = pow2ceil(std::max<u64>(bytes, 4096));
-            for (int i = 0; i < 2; i++) FA_HIP(fc, hipHostMalloc((void **)&fc->h_stage[i], cap, 0));
-            fc->h_stage_cap = cap;
-        }
-        const auto t0 = clk::now();
-        memcpy(fc->h_stage[b], src, bytes);
-        *host_ms += ms_since(t0);
-        from = fc->h_stage[b];
-    }
-    FA_HIP(fc, hipEventRecord(fc->up0[b], ctx->copy_stream));
-    FA_HIP(fc, hipMemcpyAsync(d_dst, from, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-    FA_HIP(fc, hipEventRecord(fc->up1[b], ctx->copy_stream));
-    return GK_OK;
-}
-
 template <class T> T *fa_carve(uint8_t *&at, u64 n) {
     T *p = reinterpret_cast<T *>(at);
     at += (n * sizeof(T) + 255) & ~255ull;
@@ -429,7 +393,7 @@ int fa_run(gk_fasta_check *fc, const char *text, u64 nbytes) {
     gk_ctx *ctx = fc->ctx;
     const int k = fc->k;
     double up_ms = 0, parse_ms = 0, look_ms = 0;
-    const bool pinned = fa_is_pinned(text);
+    const bool pinned = TextUpload::is_pinned(text);
     const u64 slice_max = fa_slice_max(fc);
     const bool want_pos = fc->max_missing > 0;
     // every buffer of the call in one pooled block, carved (sizes for the largest slice)
@@ -471,44 +435,36 @@ int fa_run(gk_fasta_check *fc, const char *text, u64 nbytes) {
     void *slots = nullptr;
     uint32_t nb2 = 1, lnb1 = 0;
     vmap_table(fc->vm, &slots, &nb2, &lnb1);
-    auto kstart = [&]() { return hipEventRecord(ctx->ev0, ctx->stream); };
-    auto kend = [&](double *acc) -> int {
-        GK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        GK_HIP(ctx, hipEventSynchronize(ctx->ev1));
-        float t = 0;
-        GK_HIP(ctx, hipEventElapsedTime(&t, ctx->ev0, ctx->ev1));
-        *acc += t;
-        return GK_OK;
-    };
+    const TimedSection kt{ctx};
     int rc = GK_OK;
     int b = 0;
     FaCut cut = fa_cut(text, nbytes, 0, fc->prev_cr, slice_max);
     bool uploaded = false;                                           // the current slice is already on its way into tb[b]
     while (cut.len) {
         const u64 n = cut.len;
-        if (!uploaded) { if ((rc = fa_upload(fc, b, tb[b], text + cut.begin, n, pinned, &up_ms))) return rc; }
-        FA_HIP(fc, hipStreamWaitEvent(ctx->stream, fc->up1[b], 0));
+        if (!uploaded) { if ((rc = fc->up.upload(ctx, b, tb[b], text + cut.begin, n, pinned, &up_ms))) { fc->failed = true; return rc; } }
+        FA_HIP(fc, hipStreamWaitEvent(ctx->stream, fc->up.up1[b], 0));
         const uint8_t *T = tb[b];
         const u64 slice_off = fc->text_off + cut.begin;              // offset of T[0] in the whole input (text_off: before this call)
         const u64 ntiles = (n + FQ_TILE - 1) / FQ_TILE;
         // ---- line ends
-        FA_HIP(fc, kstart());
+        FA_HIP(fc, kt.start());
         hipLaunchKernelGGL((k_fq_terms<0>), dim3((unsigned)ntiles), dim3(FQ_BLOCK), 0, ctx->stream, T, n, tile_cnt, nullptr, nullptr);
         FA_HIP(fc, hipGetLastError());
         FA_HIP(fc, scan_counts(ctx, tile_cnt, ntiles, tile_off, scan));
         FA_HIP(fc, hipMemcpyAsync(&fc->h[14], tile_off + ntiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = kend(&parse_ms))) { fc->failed = true; return rc; }
+        if ((rc = kt.end(&parse_ms))) { fc->failed = true; return rc; }
         const u64 terms = fc->h[14];
         {
             float t = 0;
-            FA_HIP(fc, hipEventElapsedTime(&t, fc->up0[b], fc->up1[b]));
+            FA_HIP(fc, hipEventElapsedTime(&t, fc->up.up0[b], fc->up.up1[b]));
             up_ms += t;
         }
         if (terms > n) return fa_fail(fc, GK_E_STATE, "gk_fasta_check: more line ends than characters (internal error)");
         u32 *E = eblk;
         if (!E) FA_HIP(fc, tmp.get(&E, terms + 2));
         // ---- squeeze
-        FA_HIP(fc, kstart());
+        FA_HIP(fc, kt.start());
         hipLaunchKernelGGL((k_fq_terms<1>), dim3((unsigned)ntiles), dim3(FQ_BLOCK), 0, ctx->stream, T, n, nullptr, tile_off, E);
         hipLaunchKernelGGL((k_fa_squeeze<0>), dim3((unsigned)ntiles), dim3(FQ_BLOCK), 0, ctx->stream, T, n, slice_off, E, tile_off, fc->per_line, fc->d_st,
                            wave_kept, nullptr, nullptr, nullptr);
@@ -517,16 +473,16 @@ int fa_run(gk_fasta_check *fc, const char *text, u64 nbytes) {
         FA_HIP(fc, hipMemcpyAsync(&fc->h[15], kept_off + ntiles * FA_WAVES, 8, hipMemcpyDeviceToHost, ctx->stream));
         // (the next slice goes up on the copy stream beside the rest of this one: the other text buffer is free)
         const FaCut next = fa_cut(text, nbytes, cut.begin + n, false, slice_max);
-        if (next.len) { if ((rc = fa_upload(fc, 1 - b, tb[1 - b], text + next.begin, next.len, pinned, &up_ms))) return rc; }
-        if ((rc = kend(&parse_ms))) { fc->failed = true; return rc; }
+        if (next.len) { if ((rc = fc->up.upload(ctx, 1 - b, tb[1 - b], text + next.begin, next.len, pinned, &up_ms))) { fc->failed = true; return rc; } }
+        if ((rc = kt.end(&parse_ms))) { fc->failed = true; return rc; }
         const u64 m = fc->h[15];
         if (m > n) return fa_fail(fc, GK_E_STATE, "gk_fasta_check: more codes than characters (internal error)");
-        FA_HIP(fc, kstart());
+        FA_HIP(fc, kt.start());
         hipLaunchKernelGGL((k_fa_squeeze<1>), dim3((unsigned)ntiles), dim3(FQ_BLOCK), 0, ctx->stream, T, n, slice_off, E, tile_off, fc->per_line, fc->d_st,
                            nullptr, kept_off, codes + FA_HEAD, src);
         if (terms) hipLaunchKernelGGL(k_fa_short, dim3((unsigned)((terms + FQ_BLOCK - 1) / FQ_BLOCK)), dim3(FQ_BLOCK), 0, ctx->stream, T, n, E, terms, k, fc->d_st);
         FA_HIP(fc, hipGetLastError());
-        if ((rc = kend(&parse_ms))) { fc->failed = true; return rc; }
+        if ((rc = kt.end(&parse_ms))) { fc->failed = true; return rc; }
         // ---- windows
         const u32 nc = fc->nc;
         const u64 Ltot = nc + m, P = Ltot >= (u64)k ? Ltot - k + 1 : 0;
@@ -534,28 +490,24 @@ int fa_run(gk_fasta_check *fc, const char *text, u64 nbytes) {
         const u32 nc_new = (u32)std::min<u64>((u64)k - 1, Ltot);
         FaSlice sl{T, n, slice_off, E, terms, codes + FA_HEAD - nc, Ltot, P, src};
         const u64 w_before = fc->h[5], f_before = fc->h[6];
-        FA_HIP(fc, kstart());
+        FA_HIP(fc, kt.start());
         if (nc) hipLaunchKernelGGL(k_fa_put_carry, dim3(1), dim3(64), 0, ctx->stream, fc->d_st, codes, nc);
         if (P) {
             const unsigned grid = (unsigned)((nshort + 255) / 256);
-            if (fc->W == 1)
-                hipLaunchKernelGGL(k_fa_windows<1>, dim3(grid), dim3(256), 0, ctx->stream, Table<1>{(Slot<1> *)slots, nb2, lnb1, 0u, 0u}, k, sl.S, Ltot, P,
-                                   (uint16_t *)wb, (uint16_t *)fb, nshort, fc->d_st);
-            else
-                hipLaunchKernelGGL(k_fa_windows<2>, dim3(grid), dim3(256), 0, ctx->stream, Table<2>{(Slot<2> *)slots, nb2, lnb1, k == 64 ? 1u : 0u, 0u}, k, sl.S,
-                                   Ltot, P, (uint16_t *)wb, (uint16_t *)fb, nshort, fc->d_st);
+            GK_BY_W(fc->W, hipLaunchKernelGGL(k_fa_windows<W>, dim3(grid), dim3(256), 0, ctx->stream, Table<W>{(Slot<W> *)slots, nb2, lnb1, k == 64 ? 1u : 0u, 0u}, k, sl.S,
+                                              Ltot, P, (uint16_t *)wb, (uint16_t *)fb, nshort, fc->d_st));
         }
         if (nC) hipLaunchKernelGGL(k_fa_cover, dim3((unsigned)std::min<u64>((nC + 255) / 256, 4096)), dim3(256), 0, ctx->stream, fb, nF, nC, P, k, cb, fc->d_st);
         FA_HIP(fc, hipGetLastError());
         FA_HIP(fc, hipMemcpyAsync(fc->h, fc->d_st, FA_STATE_HOST, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = kend(&look_ms))) { fc->failed = true; return rc; }
+        if ((rc = kt.end(&look_ms))) { fc->failed = true; return rc; }
         // ---- the first not-found windows, in stream order
         const u64 miss_now = (fc->h[5] - w_before) - (fc->h[6] - f_before);
         u64 appended = 0;
         if (want_pos && miss_now && fc->have < fc->max_missing) {
             appended = std::min<u64>(miss_now, fc->max_missing - fc->have);
             if ((rc = fa_miss_reserve(fc, fc->have + appended))) return rc;
-            FA_HIP(fc, kstart());
+            FA_HIP(fc, kt.start());
             const unsigned grid = (unsigned)std::min<u64>((nF + 255) / 256, 4096);
             hipLaunchKernelGGL(k_fa_miss_count, dim3(grid), dim3(256), 0, ctx->stream, wb, fb, nF, mcnt);
             FA_HIP(fc, hipGetLastError());
@@ -564,12 +516,12 @@ int fa_run(gk_fasta_check *fc, const char *text, u64 nbytes) {
             hipLaunchKernelGGL(k_fa_miss_emit, dim3(grid), dim3(256), 0, ctx->stream, sl, fc->d_st, nc, k, wb, fb, nF, moff, fc->have, fc->max_missing, fc->d_miss,
                                fc->d_miss + mc, fc->d_miss + 2 * mc, fc->d_miss + 3 * mc, fc->d_miss + 4 * mc);
             FA_HIP(fc, hipGetLastError());
-            if ((rc = kend(&look_ms))) { fc->failed = true; return rc; }
+            if ((rc = kt.end(&look_ms))) { fc->failed = true; return rc; }
         }
-        FA_HIP(fc, kstart());
+        FA_HIP(fc, kt.start());
         hipLaunchKernelGGL(k_fa_carry, dim3(1), dim3(64), 0, ctx->stream, sl, fc->d_st, nc, nc_new, cb, appended);
         FA_HIP(fc, hipGetLastError());
-        if ((rc = kend(&look_ms))) { fc->failed = true; return rc; }
+        if ((rc = kt.end(&look_ms))) { fc->failed = true; return rc; }
         fc->nc = nc_new;
         fc->have += appended;
         if (!eblk) tmp.release(E);
@@ -597,11 +549,7 @@ int gk_fasta_check_create(gk_ctx *ctx, gk_vmap *positions, int per_line, uint64_
     gk_fasta_check *fc = new gk_fasta_check;
     fc->ctx = ctx; fc->vm = positions; fc->k = vmap_k(positions); fc->W = words_for_k(fc->k);
     fc->per_line = per_line ? 1 : 0; fc->max_missing = max_missing;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        e = hipEventCreate(&fc->up0[i]);
-        if (e == hipSuccess) e = hipEventCreate(&fc->up1[i]);
-    }
+    hipError_t e = fc->up.create();
     if (e == hipSuccess) e = pool_malloc(ctx, &fc->d_st, sizeof(FaState));
     if (e == hipSuccess) e = hipHostMalloc((void **)&fc->h, 16 * 8, 0);
     if (e == hipSuccess) {
@@ -625,11 +573,7 @@ void gk_fasta_check_destroy(gk_fasta_check *fc) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)pool_free(ctx, fc->d_st);
     (void)pool_free(ctx, fc->d_miss);
-    for (int i = 0; i < 2; i++) {
-        if (fc->h_stage[i]) (void)hipHostFree(fc->h_stage[i]);
-        if (fc->up0[i]) (void)hipEventDestroy(fc->up0[i]);
-        if (fc->up1[i]) (void)hipEventDestroy(fc->up1[i]);
-    }
+    fc->up.destroy();
     if (fc->h) (void)hipHostFree(fc->h);
     delete fc;
 }
@@ -650,8 +594,7 @@ int gk_fasta_check_feed(gk_fasta_check *fc, const char *text, size_t nbytes, int
         fc->finished = true;
         fc->nc = 0;
     }
-    FA_HIP(fc, hipMemcpyAsync(fc->h, fc->d_st, FA_STATE_HOST, hipMemcpyDeviceToHost, ctx->stream));
-    FA_HIP(fc, hipStreamSynchronize(ctx->stream));
+    FA_HIP(fc, read_back(ctx, {{fc->h, fc->d_st, FA_STATE_HOST}}));
     fc->ms[3] = (float)ms_since(t_call);
     return GK_OK;
 }
@@ -680,10 +623,9 @@ int gk_fasta_check_missing(const gk_fasta_check *fc, uint64_t *text_offset, uint
     const u64 take = std::min<u64>(fc->have, cap);
     if (!take) return GK_OK;
     GK_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t *dst[5] = {text_offset, line, column, lo, hi};
-    for (int a = 0; a < 5; a++)
-        if (dst[a]) GK_HIP(ctx, hipMemcpyAsync(dst[a], fc->d_miss + a * fc->miss_cap, take * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const unsigned long long *d = fc->d_miss;
+    const u64 mc = fc->miss_cap, nb = take * 8;
+    GK_HIP(ctx, read_back(ctx, {{text_offset, d, nb}, {line, d + mc, nb}, {column, d + 2 * mc, nb}, {lo, d + 3 * mc, nb}, {hi, d + 4 * mc, nb}}));
     return GK_OK;
 }
 

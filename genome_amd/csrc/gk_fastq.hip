@@ -223,8 +223,6 @@ __global__ void k_fq_cut(const unsigned long long *__restrict__ wpre, u64 nm, u6
     cut[2 * j + 1] = wpre[b];
 }
 
-using clk = std::chrono::steady_clock;
-double ms_since(clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); }
 
 }  // namespace
 
@@ -241,10 +239,8 @@ struct gk_fastq {
     // the slice already on its way into buf[b] (prefetched by the previous chunk of the same call)
     const char *pf_src[2] = {nullptr, nullptr};
     u64 pf_bytes[2] = {0, 0};
-    hipEvent_t up0[2] = {nullptr, nullptr}, up1[2] = {nullptr, nullptr};
+    TextUpload up;                                // the copy-stream upload into buf[b] (gk_text.h)
     bool up_timed[2] = {false, false};
-    uint8_t *h_stage[2] = {nullptr, nullptr};     // pinned staging of pageable text
-    u64 h_stage_cap = 0;
     // parse scratch (pooled, grown on demand)
     u32 *d_tile_cnt = nullptr; size_t tile_cap = 0;
     unsigned long long *d_tile_off = nullptr; size_t tile_off_cap = 0;
@@ -312,29 +308,12 @@ int fq_text_buffer(gk_fastq *fq, int b, u64 carry, u64 slice, bool keep) {
     return GK_OK;
 }
 
-// text [src, src + bytes) -> buf[b] + head[b], on the copy stream (pageable text goes through a pinned staging buffer first)
-int fq_upload(gk_fastq *fq, int b, const char *src, u64 bytes, bool pinned, double *host_ms) {
-    gk_ctx *ctx = fq->ctx;
+// text [src, src + bytes) on its way to buf[b] + head[b], and remembered: the chunk that wants exactly this slice finds it there
+int fq_prefetch(gk_fastq *fq, int b, const char *src, u64 bytes, bool pinned, double *host_ms) {
     fq->pf_src[b] = src; fq->pf_bytes[b] = bytes;
     fq->up_timed[b] = false;
     if (!bytes) return GK_OK;
-    const void *from = src;
-    if (!pinned) {
-        if (fq->h_stage_cap < bytes) {
-            GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-            for (int i = 0; i < 2; i++) { if (fq->h_stage[i]) (void)hipHostFree(fq->h_stage[i]); fq->h_stage[i] = nullptr; }
-            fq->h_stage_cap = 0;
-            for (int i = 0; i < 2; i++) GK_HIP(ctx, hipHostMalloc((void **)&fq->h_stage[i], bytes, 0));
-            fq->h_stage_cap = bytes;
-        }
-        const auto t0 = clk::now();
-        memcpy(fq->h_stage[b], src, bytes);
-        *host_ms += ms_since(t0);
-        from = fq->h_stage[b];
-    }
-    GK_HIP(ctx, hipEventRecord(fq->up0[b], ctx->copy_stream));
-    GK_HIP(ctx, hipMemcpyAsync(fq->buf[b] + fq->head[b], from, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-    GK_HIP(ctx, hipEventRecord(fq->up1[b], ctx->copy_stream));
+    if (int rc = fq->up.upload(fq->ctx, b, fq->buf[b] + fq->head[b], src, bytes, pinned, host_ms)) return rc;
     fq->up_timed[b] = true;
     return GK_OK;
 }
@@ -344,43 +323,28 @@ int fq_fail(gk_fastq *fq, int code, const std::string &msg) {
     return fail(fq->ctx, code, msg);
 }
 
-bool fq_is_pinned(const void *p) {
-    unsigned int flags = 0;
-    const bool ok = hipHostGetFlags(&flags, const_cast<void *>(p)) == hipSuccess;
-    if (!ok) (void)hipGetLastError();
-    return ok;
-}
-
 // the shared body of gk_fastq_convert / gk_fastq_count: every completed pair goes to `sink` (host buffer or map)
 int fq_run(gk_fastq *fq, const char *text, size_t nbytes, int last, uint8_t *bin_out, size_t *bin_bytes, gk_map *m, uint64_t *occ_out) {
     gk_ctx *ctx = fq->ctx;
     const auto t_call = clk::now();
     double up_ms = 0, kern_ms = 0, sink_ms = 0;
-    const bool pinned = nbytes && fq_is_pinned(text);
+    const bool pinned = nbytes && TextUpload::is_pinned(text);
     const u64 slice_max = fq_slice(fq);
     u64 pos = 0;
     size_t written = 0;
     int rc = GK_OK;
     if (m) { if ((rc = map_count_begin(m))) return fq_fail(fq, rc, ctx->err); }
-    auto kstart = [&]() { return hipEventRecord(ctx->ev0, ctx->stream); };
-    auto kend = [&]() -> int {
-        GK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-        GK_HIP(ctx, hipEventSynchronize(ctx->ev1));
-        float t = 0;
-        GK_HIP(ctx, hipEventElapsedTime(&t, ctx->ev0, ctx->ev1));
-        kern_ms += t;
-        return GK_OK;
-    };
+    const TimedSection kt{ctx};
     do {
         const u64 slice = std::min<u64>(nbytes - pos, slice_max);
         const bool is_last = last && pos + slice == nbytes;
         const int b = fq->cur;
         if ((rc = fq_text_buffer(fq, b, fq->carry, slice, true))) return fq_fail(fq, rc, ctx->err);
         if (!(fq->pf_src[b] == text + pos && fq->pf_bytes[b] == slice)) {
-            if ((rc = fq_upload(fq, b, text + pos, slice, pinned, &up_ms))) return fq_fail(fq, rc, ctx->err);
+            if ((rc = fq_prefetch(fq, b, text + pos, slice, pinned, &up_ms))) return fq_fail(fq, rc, ctx->err);
         }
         fq->pf_src[b] = nullptr;
-        if (fq->up_timed[b]) GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, fq->up1[b], 0));
+        if (fq->up_timed[b]) GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, fq->up.up1[b], 0));
         const u64 n = fq->carry + slice;
         const uint8_t *T = fq->buf[b] + fq->head[b] - fq->carry;
         // ---- line ends
@@ -388,32 +352,32 @@ int fq_run(gk_fastq *fq, const char *text, size_t nbytes, int last, uint8_t *bin
         if ((rc = fq_grow(ctx, &fq->d_tile_cnt, &fq->tile_cap, ntiles + 1)) || (rc = fq_grow(ctx, &fq->d_tile_off, &fq->tile_off_cap, ntiles + 2)) ||
             (rc = fq_grow(ctx, &fq->d_scan, &fq->scan_cap, (size_t)(n / (2 * SCAN_CHUNK) + 4))))
             return fq_fail(fq, rc, ctx->err);
-        GK_HIP(ctx, kstart());
+        GK_HIP(ctx, kt.start());
         if (ntiles) hipLaunchKernelGGL((k_fq_terms<0>), dim3((unsigned)ntiles), dim3(FQ_BLOCK), 0, ctx->stream, T, n, fq->d_tile_cnt, nullptr, nullptr);
         GK_HIP(ctx, hipGetLastError());
         GK_HIP(ctx, scan_counts(ctx, fq->d_tile_cnt, ntiles, fq->d_tile_off, fq->d_scan));
         GK_HIP(ctx, hipMemcpyAsync(&fq->h->terms, fq->d_tile_off + ntiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = kend())) return fq_fail(fq, rc, ctx->err);
+        if ((rc = kt.end(&kern_ms))) return fq_fail(fq, rc, ctx->err);
         const u64 terms = fq->h->terms;
         if (fq->up_timed[b]) {
             float t = 0;
-            GK_HIP(ctx, hipEventElapsedTime(&t, fq->up0[b], fq->up1[b]));
+            GK_HIP(ctx, hipEventElapsedTime(&t, fq->up.up0[b], fq->up.up1[b]));
             up_ms += t;
             fq->up_timed[b] = false;
         }
         // (the next slice of this call goes up beside the rest of this chunk: its buffer is free, its head region is written last)
         const u64 next_pos = pos + slice, next_slice = std::min<u64>(nbytes - next_pos, slice_max);
         if ((rc = fq_grow(ctx, &fq->d_E, &fq->e_cap, terms + 2))) return fq_fail(fq, rc, ctx->err);
-        GK_HIP(ctx, kstart());
+        GK_HIP(ctx, kt.start());
         if (ntiles) hipLaunchKernelGGL((k_fq_terms<1>), dim3((unsigned)ntiles), dim3(FQ_BLOCK), 0, ctx->stream, T, n, nullptr, fq->d_tile_off, fq->d_E);
         hipLaunchKernelGGL(k_fq_plan, dim3(1), dim3(1), 0, ctx->stream, T, n, fq->d_E, terms, is_last ? 1 : 0, fq->split_at ? 0 : 1, fq->records,
                            fq->d_plan, fq->d_sum);
         GK_HIP(ctx, hipGetLastError());
         GK_HIP(ctx, hipMemcpyAsync(&fq->h->plan, fq->d_plan, sizeof(FqPlan), hipMemcpyDeviceToHost, ctx->stream));
         if (next_slice && fq->buf[1 - b] && fq->slice_cap[1 - b] >= next_slice) {
-            if ((rc = fq_upload(fq, 1 - b, text + next_pos, next_slice, pinned, &up_ms))) return fq_fail(fq, rc, ctx->err);
+            if ((rc = fq_prefetch(fq, 1 - b, text + next_pos, next_slice, pinned, &up_ms))) return fq_fail(fq, rc, ctx->err);
         }
-        if ((rc = kend())) return fq_fail(fq, rc, ctx->err);
+        if ((rc = kt.end(&kern_ms))) return fq_fail(fq, rc, ctx->err);
         const FqPlan plan = fq->h->plan;
         // ---- records, pairs, offsets, pack
         const u64 npairs = fq->split_at ? plan.recs_emit : plan.recs_emit / 2;
@@ -423,7 +387,7 @@ int fq_run(gk_fastq *fq, const char *text, size_t nbytes, int last, uint8_t *bin
         if ((rc = fq_grow(ctx, &fq->d_scan, &fq->scan_cap, (size_t)(nm / SCAN_CHUNK + 4)))) return fq_fail(fq, rc, ctx->err);
         // output: never more bytes than the chunk's text (header comment of gk_fastq_convert)
         if ((rc = fq_grow(ctx, &fq->d_out, &fq->out_cap, (size_t)n + 64))) return fq_fail(fq, rc, ctx->err);
-        GK_HIP(ctx, kstart());
+        GK_HIP(ctx, kt.start());
         if (plan.recs)
             hipLaunchKernelGGL(k_fq_records, dim3((unsigned)((plan.recs + 3) / 4)), dim3(FQ_BLOCK), 0, ctx->stream, T, n, fq->d_E, plan.recs, fq->split_at,
                                fq->records, fq->d_mlen, fq->d_mstart, fq->d_sum);
@@ -441,7 +405,7 @@ int fq_run(gk_fastq *fq, const char *text, size_t nbytes, int last, uint8_t *bin
         GK_HIP(ctx, hipMemcpyAsync(&fq->h->sum, fq->d_sum, sizeof(FqSum), hipMemcpyDeviceToHost, ctx->stream));
         GK_HIP(ctx, hipMemcpyAsync(&fq->h->out_bytes, fq->d_off64 + nm, 8, hipMemcpyDeviceToHost, ctx->stream));
         if (m) GK_HIP(ctx, hipMemcpyAsync(&fq->h->windows, fq->d_wpre + nm, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if ((rc = kend())) return fq_fail(fq, rc, ctx->err);
+        if ((rc = kt.end(&kern_ms))) return fq_fail(fq, rc, ctx->err);
         const FqSum sum = fq->h->sum;
         const u64 out_bytes = fq->h->out_bytes;
         // ---- the completed pairs to their sink (pairs after the first bad record emitted nothing: a prefix of the mates)
@@ -461,10 +425,8 @@ int fq_run(gk_fastq *fq, const char *text, size_t nbytes, int last, uint8_t *bin
                 const u64 per = limit - 255, nb = (windows + per - 1) / per;
                 if ((rc = fq_grow(ctx, &fq->d_cut, &fq->cut_cap, 2 * (nb + 1)))) return fq_fail(fq, rc, ctx->err);
                 hipLaunchKernelGGL(k_fq_cut, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, ctx->stream, fq->d_wpre, good_mates, per, nb, fq->d_cut);
-                GK_HIP(ctx, hipGetLastError());
                 std::vector<unsigned long long> cut(2 * (nb + 1));
-                GK_HIP(ctx, hipMemcpyAsync(cut.data(), fq->d_cut, cut.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-                GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                GK_HIP(ctx, read_back(ctx, cut.data(), fq->d_cut, cut.size()));
                 for (u64 j = 0; j < nb; j++) {
                     const u64 b0 = cut[2 * j], b1 = cut[2 * j + 2];
                     if (b1 <= b0) continue;
@@ -522,11 +484,7 @@ int gk_fastq_create(gk_ctx *ctx, int split_at, int k_stats, uint64_t max_pairs, 
     GK_HIP(ctx, hipSetDevice(ctx->device));
     gk_fastq *fq = new gk_fastq;
     fq->ctx = ctx; fq->split_at = split_at; fq->k_stats = k_stats; fq->max_pairs = max_pairs;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        e = hipEventCreate(&fq->up0[i]);
-        if (e == hipSuccess) e = hipEventCreate(&fq->up1[i]);
-    }
+    hipError_t e = fq->up.create();
     if (e == hipSuccess) e = pool_malloc(ctx, &fq->d_plan, sizeof(FqPlan));
     if (e == hipSuccess) e = pool_malloc(ctx, &fq->d_sum, sizeof(FqSum));
     if (e == hipSuccess) e = hipHostMalloc((void **)&fq->h, sizeof(FqHost), 0);
@@ -543,11 +501,7 @@ void gk_fastq_destroy(gk_fastq *fq) {
     void *dev[] = {fq->buf[0], fq->buf[1], fq->d_tile_cnt, fq->d_tile_off, fq->d_scan, fq->d_E, fq->d_mlen, fq->d_mstart, fq->d_bytes, fq->d_win,
                    fq->d_off32, fq->d_off64, fq->d_wpre, fq->d_cut, fq->d_out, fq->d_plan, fq->d_sum};
     for (void *p : dev) (void)pool_free(ctx, p);
-    for (int i = 0; i < 2; i++) {
-        if (fq->h_stage[i]) (void)hipHostFree(fq->h_stage[i]);
-        if (fq->up0[i]) (void)hipEventDestroy(fq->up0[i]);
-        if (fq->up1[i]) (void)hipEventDestroy(fq->up1[i]);
-    }
+    fq->up.destroy();
     if (fq->h) (void)hipHostFree(fq->h);
     delete fq;
 }

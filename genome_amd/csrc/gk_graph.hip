@@ -1686,10 +1686,8 @@ int graph_refresh_counts(gk_graph *g) {
     hipError_t e = hipMemsetAsync(d, 0, 24, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_count_live, dim3(ggrid(ctx, std::max(g->v.n_nodes, g->v.n_edges))), dim3(BLOCK), 0, ctx->stream, g->v, d);
-        e = hipGetLastError();
+        e = read_back(ctx, h, d, 3);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "graph_refresh_counts");
     g->live_nodes = h[0]; g->live_edges = h[1]; g->live_len = h[2];
     return GK_OK;
@@ -1704,8 +1702,7 @@ int graph_build_index(gk_graph *g) {
     GK_HIP(ctx, hipMemsetAsync(v.nidx, 0xff, cap * 4, ctx->stream));
     v.nidx_mask = cap - 1;
     if (v.n_nodes) {
-        if (g->W == 1) hipLaunchKernelGGL(k_build_nidx<1>, dim3(ggrid(ctx, v.n_nodes)), dim3(BLOCK), 0, ctx->stream, v);
-        else hipLaunchKernelGGL(k_build_nidx<2>, dim3(ggrid(ctx, v.n_nodes)), dim3(BLOCK), 0, ctx->stream, v);
+        GK_BY_W(g->W, hipLaunchKernelGGL(k_build_nidx<W>, dim3(ggrid(ctx, v.n_nodes)), dim3(BLOCK), 0, ctx->stream, v));
         GK_HIP(ctx, hipGetLastError());
     }
     GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1750,10 +1747,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
     }
     if (!from_masks) hipLaunchKernelGGL((k_classify<W, TT>), dim3(ggrid(ctx, tcap)), dim3(BLOCK), 0, ctx->stream, t, k, &d_cnt[0], termbits);
     g->used_masks = from_masks ? 1 : 0;
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: classify");
+    if ((e = read_back(ctx, h_cnt, d_cnt, 1)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: classify");
     lap(0);
     const u64 nT = h_cnt[0];
     if (2 * nT >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, "more than 2^32 graph nodes");        // (also: j < 2^31 fits AUX_NODE | j)
@@ -1761,10 +1755,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
     e = tmp.get(&tslots, nT);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: alloc nodes");
     hipLaunchKernelGGL(k_collect_bits, dim3(ggrid(ctx, nwords + 1)), dim3(BLOCK), 0, ctx->stream, termbits, nwords, tslots, &d_cnt[1]);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 24, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: collect");
+    if ((e = read_back(ctx, h_cnt, d_cnt, 3)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: collect");
     if (h_cnt[1] != nT) return fail(ctx, GK_E_STATE, "terminal count mismatch");
     tmp.release(termbits);                 // (an eighth of a byte per slot: gone before the graph arrays exist)
     const u64 nE = h_cnt[2];
@@ -1774,10 +1765,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
     g->v.k = k;
     if (nT) {
         hipLaunchKernelGGL((k_make_nodes<W, TT>), dim3(ggrid(ctx, nT)), dim3(BLOCK), 0, ctx->stream, t, k, tslots, nT, g->v, &d_cnt[3]);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 32, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: make_nodes");
+        if ((e = read_back(ctx, h_cnt, d_cnt, 4)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: make_nodes");
         // every edge slot the walk will visit must have been written by k_make_nodes
         if (h_cnt[3] != nE) return fail(ctx, GK_E_STATE, "edge stub count mismatch: " + std::to_string(h_cnt[3]) + " vs " + std::to_string(nE));
     }
@@ -1805,10 +1793,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
             hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, ctx->stream, chunk_tot, chunk_base, nchunks);
             hipLaunchKernelGGL(k_rank_fill, dim3((int)std::min<u64>(nchunks, (u64)ctx->cu_count * 8)), dim3(RANK_CHUNK), 0, ctx->stream, rb, nblk, chunk_base, nchunks);
             unsigned long long ranked = 0;
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(&ranked, chunk_base + nchunks, 8, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: slot ranks");
+            if ((e = read_back(ctx, &ranked, chunk_base + nchunks)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: slot ranks");
             if (ranked != m->size) return fail(ctx, GK_E_STATE, "live slots (" + std::to_string(ranked) + ") differ from the map's size (" + std::to_string(m->size) + ")");
             hipLaunchKernelGGL((k_pj_init<W, TT>), dim3(ggrid(ctx, tcap)), dim3(BLOCK), 0, ctx->stream, t, k, rb, st);
             e = hipGetLastError();
@@ -1820,8 +1805,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
                 e = hipMemsetAsync(d_err + 1, 0, 8, ctx->stream);      // (d_err has 4 words: [0] the build's error, [1] moved, [2] round error)
                 if (e != hipSuccess) break;
                 hipLaunchKernelGGL(k_pj_round, dim3(ggrid(ctx, nstates)), dim3(BLOCK), 0, ctx->stream, st, nstates, d_err + 1);
-                e = hipMemcpyAsync(flags, d_err + 1, 8, hipMemcpyDeviceToHost, ctx->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+                e = read_back(ctx, flags, d_err + 1, 2);
                 if (e == hipSuccess && flags[1]) return fail(ctx, GK_E_STATE, "pointer jumping met an unregistered successor (code " + std::to_string(flags[1]) + ")");
                 if (!flags[0]) break;
             }
@@ -1847,13 +1831,8 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         lap(2);
         g->used_pj = use_pj ? 1 : 0;
-        if (e == hipSuccess && use_pj) {
-            hipLaunchKernelGGL(k_reserve_pool, dim3(ggrid(ctx, nE)), dim3(BLOCK), 0, ctx->stream, g->v, (u64)0, &d_cnt[4]);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 56, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess && use_pj) hipLaunchKernelGGL(k_reserve_pool, dim3(ggrid(ctx, nE)), dim3(BLOCK), 0, ctx->stream, g->v, (u64)0, &d_cnt[4]);
+        if (e == hipSuccess) e = read_back(ctx, {{h_cnt, d_cnt, 56}, {&h_err, d_err, 4}});
         if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: walk");
         if (h_err) return fail(ctx, GK_E_STATE, "unitig construction failed (code " + std::to_string(h_err) +
                                "): the table changed since classification or is inconsistent");
@@ -1870,14 +1849,15 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
             e = hipMemsetAsync(g->v.pool, 0, g->pool_cap, ctx->stream);
             if (e == hipSuccess) {
                 hipLaunchKernelGGL((k_pj_emit<W, TT>), dim3(ggrid(ctx, std::max<u64>(tcap, nE))), dim3(BLOCK), 0, ctx->stream, t, k, g->v, rb, st, d_err);
+                e = read_back(ctx, &h_err, d_err);
+            }
+        } else {
+            if (h_cnt[6]) {          // edges longer than the walk's register buffer: second walk, emitting
+                hipLaunchKernelGGL((k_walk<W, TT>), dim3(ggrid(ctx, nE)), dim3(BLOCK), 0, ctx->stream, t, k, g->v, 1, tcap + 1, &d_cnt[4], &d_cnt[6], d_err);
                 e = hipGetLastError();
             }
-            if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream);
-        } else if (h_cnt[6]) {       // edges longer than the walk's register buffer: second walk, emitting
-            hipLaunchKernelGGL((k_walk<W, TT>), dim3(ggrid(ctx, nE)), dim3(BLOCK), 0, ctx->stream, t, k, g->v, 1, tcap + 1, &d_cnt[4], &d_cnt[6], d_err);
-            e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         tmp.release(st); tmp.release(rb); tmp.release(chunk_tot); tmp.release(chunk_base); tmp.release(stage);      // (not at scope exit: graph_refresh_counts follows)
         if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: emit");
         if (h_err) return fail(ctx, GK_E_STATE, "unitig emission failed (code " + std::to_string(h_err) + ")");
@@ -1969,8 +1949,7 @@ template <int W> static int graph_build_entry(gk_map *m, gk_graph *g, bool masks
     hipLaunchKernelGGL(k_mb_count<W>, dim3(ggrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, t, m->k, nb, d_cnt, d_bucket);
     hipLaunchKernelGGL(k_mb_sizes, dim3(ggrid(ctx, nb)), dim3(BLOCK), 0, ctx->stream, d_cnt, nb);
     e = scan_counts(ctx, d_cnt, nb, d_off, d_sums);
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, d_off + nb, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = read_back(ctx, &total, d_off + nb);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: bucket regions");
     e = tmp.get(&slots, total);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: bucketed table");
@@ -1978,10 +1957,7 @@ template <int W> static int graph_build_entry(gk_map *m, gk_graph *g, bool masks
     MbTable<W> mt{slots, reinterpret_cast<const u64 *>(d_off), nb, m->dirty ? 1u : 0u, (u64)total};
     hipLaunchKernelGGL(k_mb_fill<W>, dim3(ggrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, t, d_bucket, mt, d_err);
     u32 h_err = 0;
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: filling the bucketed table");
+    if ((e = read_back(ctx, &h_err, d_err)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: filling the bucketed table");
     if (h_err) return fail(ctx, GK_E_STATE, "gk_graph_build: a bucket region filled up (internal sizing error)");
     tmp.release(d_bucket);
     tmp.release(d_cnt);
@@ -2053,9 +2029,7 @@ int gk_graph_contig_stats(gk_graph *g, uint64_t longer_than, uint64_t *count, ui
     GK_HIP(ctx, hipMemsetAsync(d, 0, 64, ctx->stream));
     const int grid = ggrid(ctx, g->v.n_edges);
     hipLaunchKernelGGL(k_contig_reduce, dim3(grid), dim3(BLOCK), 0, ctx->stream, g->v, (u64)longer_than, d);
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipMemcpyAsync(h, d, 24, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, h, d, 3));
     const u64 cnt = h[0], total = h[1], mx = h[2];
     if (cnt == 0) return GK_OK;
     // sorted[count / 2] ascending; and, lengths descending, the first at which the running sum reaches half the total (rounded up)
@@ -2066,9 +2040,7 @@ int gk_graph_contig_stats(gk_graph *g, uint64_t longer_than, uint64_t *count, ui
     for (; shift >= 0; shift -= 8) {
         GK_HIP(ctx, hipMemsetAsync(d + 8, 0, 512 * 8, ctx->stream));
         hipLaunchKernelGGL(k_contig_hist, dim3(grid), dim3(BLOCK), 0, ctx->stream, g->v, (u64)longer_than, shift, pm, pn, d + 8);
-        GK_HIP(ctx, hipGetLastError());
-        GK_HIP(ctx, hipMemcpyAsync(h, d + 8, 512 * 8, hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GK_HIP(ctx, read_back(ctx, h, d + 8, 512));
         int bm = -1, bn = -1;
         for (int b = 0; b < 256 && bm < 0; b++) { if (rank < h[b]) bm = b; else rank -= h[b]; }
         for (int b = 255; b >= 0 && bn < 0; b--) { if (acc + h[256 + b] >= half) bn = b; else acc += h[256 + b]; }
@@ -2107,10 +2079,7 @@ int gk_graph_simplify(gk_graph *g) {
     hipLaunchKernelGGL(k_node_class, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, in_single, cls);
     const u64 old_edges = v.n_edges, old_pool = g->pool_used;
     hipLaunchKernelGGL(k_chain, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, cls, 0, old_edges, old_pool, d_cnt, merged_key, (LongPiece *)nullptr);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 24, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: count");
+    if ((e = read_back(ctx, h_cnt, d_cnt, 3)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: count");
     if (h_cnt[0]) {
         if (old_edges + h_cnt[0] >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, "more than 2^32 graph edges");
         if (int rc = graph_grow_edges(g, old_edges + h_cnt[0])) return rc;
@@ -2168,12 +2137,9 @@ int gk_graph_remove_edges(gk_graph *g, const uint64_t *start_lo, const uint64_t 
     if (e == hipSuccess) e = hipMemcpyAsync(d_b, base, n, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_rm, 0, 8, ctx->stream);
     if (e == hipSuccess) {
-        if (g->W == 1) hipLaunchKernelGGL(k_remove_edges<1>, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_b, n, d_rm);
-        else hipLaunchKernelGGL(k_remove_edges<2>, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_b, n, d_rm);
-        e = hipGetLastError();
+        GK_BY_W(g->W, hipLaunchKernelGGL(k_remove_edges<W>, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_b, n, d_rm));
+        e = read_back(ctx, &h_rm, d_rm);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_rm, d_rm, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_remove_edges");
     if (removed) *removed = h_rm;
     return graph_refresh_counts(g);
@@ -2193,8 +2159,7 @@ int dclass_count(gk_map *m, int rank, int P, u64 s0, u64 s1, unsigned long long 
     if (s1 > m->capacity) s1 = m->capacity;
     if (s0 >= s1) return GK_OK;
     const int grid = ggrid(ctx, s1 - s0);
-    if (m->W == 1) hipLaunchKernelGGL((k_dc_scan<1, false>), dim3(grid), dim3(BLOCK), 0, ctx->stream, graph_table_of<1>(m), m->k, rank, P, s0, s1, d_cnt, nullptr, nullptr, nullptr);
-    else hipLaunchKernelGGL((k_dc_scan<2, false>), dim3(grid), dim3(BLOCK), 0, ctx->stream, graph_table_of<2>(m), m->k, rank, P, s0, s1, d_cnt, nullptr, nullptr, nullptr);
+    GK_BY_W(m->W, hipLaunchKernelGGL((k_dc_scan<W, false>), dim3(grid), dim3(BLOCK), 0, ctx->stream, graph_table_of<W>(m), m->k, rank, P, s0, s1, d_cnt, nullptr, nullptr, nullptr));
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
 }
@@ -2205,24 +2170,21 @@ int dclass_fill(gk_map *m, int rank, int P, u64 s0, u64 s1, const unsigned long 
     if (s1 > m->capacity) s1 = m->capacity;
     if (s0 >= s1) return GK_OK;
     const int grid = ggrid(ctx, s1 - s0);
-    if (m->W == 1) hipLaunchKernelGGL((k_dc_scan<1, true>), dim3(grid), dim3(BLOCK), 0, ctx->stream, graph_table_of<1>(m), m->k, rank, P, s0, s1, d_cur, d_off, d_qkeys, d_qref);
-    else hipLaunchKernelGGL((k_dc_scan<2, true>), dim3(grid), dim3(BLOCK), 0, ctx->stream, graph_table_of<2>(m), m->k, rank, P, s0, s1, d_cur, d_off, d_qkeys, d_qref);
+    GK_BY_W(m->W, hipLaunchKernelGGL((k_dc_scan<W, true>), dim3(grid), dim3(BLOCK), 0, ctx->stream, graph_table_of<W>(m), m->k, rank, P, s0, s1, d_cur, d_off, d_qkeys, d_qref));
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
 }
 int dclass_answer(gk_map *m, const u64 *d_keys, u64 n, uint8_t *d_ans) {
     gk_ctx *ctx = m->ctx;
     if (!n) return GK_OK;
-    if (m->W == 1) hipLaunchKernelGGL((k_dc_answer<1>), dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, graph_table_of<1>(m), m->k, d_keys, n, d_ans);
-    else hipLaunchKernelGGL((k_dc_answer<2>), dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, graph_table_of<2>(m), m->k, d_keys, n, d_ans);
+    GK_BY_W(m->W, hipLaunchKernelGGL((k_dc_answer<W>), dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, graph_table_of<W>(m), m->k, d_keys, n, d_ans));
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
 }
 int dclass_apply(gk_map *m, const u64 *d_qref, const uint8_t *d_ans, u64 n) {
     gk_ctx *ctx = m->ctx;
     if (!n) return GK_OK;
-    if (m->W == 1) hipLaunchKernelGGL((k_dc_apply<1>), dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, graph_table_of<1>(m), d_qref, d_ans, n);
-    else hipLaunchKernelGGL((k_dc_apply<2>), dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, graph_table_of<2>(m), d_qref, d_ans, n);
+    GK_BY_W(m->W, hipLaunchKernelGGL((k_dc_apply<W>), dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, graph_table_of<W>(m), d_qref, d_ans, n));
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
 }
@@ -2252,10 +2214,8 @@ static int graph_components(gk_graph *g, DevScratch &tmp, u32 **parent_out, u32 
     if (e == hipSuccess) e = hipMemsetAsync(d_ncomp, 0, 8, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_cc_sizes, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, parent, size, d_ncomp);
-        e = hipGetLastError();
+        e = read_back(ctx, &h, d_ncomp);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_ncomp, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "graph components: sizes");
     tmp.release(d_ncomp);
     *parent_out = parent; *size_out = size; *ncomp = h;
@@ -2290,10 +2250,7 @@ int gk_graph_retain_largest(gk_graph *g, uint64_t *kept_nodes, uint64_t *compone
     for (int stage = 0; stage < 3; stage++)
         hipLaunchKernelGGL(k_cc_pick, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, parent, size, &d_u32[1], stage, &d_u64[1], &d_u32[2]);
     hipLaunchKernelGGL(k_retain, dim3(ggrid(ctx, std::max(v.n_nodes, v.n_edges))), dim3(BLOCK), 0, ctx->stream, v, parent, &d_u32[2]);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h32, d_u32, 12, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest: retain");
+    if ((e = read_back(ctx, h32, d_u32, 3)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest: retain");
     if (h32[2] == NONE) return fail(ctx, GK_E_STATE, "no component selected");
     if (components) *components = ncomp;
     int rc = graph_refresh_counts(g);
@@ -2324,10 +2281,7 @@ int gk_graph_component_stats(gk_graph *g, uint32_t *nodes_per_component, uint64_
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_component_stats: alloc");
     hipLaunchKernelGGL(k_cc_edge_len, dim3(ggrid(ctx, std::max<u64>(v.n_edges, 1))), dim3(BLOCK), 0, ctx->stream, v, parent, len);
     hipLaunchKernelGGL(k_cc_collect, dim3(ggrid(ctx, v.n_nodes)), dim3(BLOCK), 0, ctx->stream, v, parent, size, len, d_nodes, d_len, d_cur);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(nodes_per_component, d_nodes, ncomp * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(edge_len_per_component, d_len, ncomp * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    e = read_back(ctx, {{nodes_per_component, d_nodes, ncomp * 4}, {edge_len_per_component, d_len, ncomp * 8}});
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_component_stats");
     return GK_OK;
 }
@@ -2341,10 +2295,8 @@ int gk_graph_checksum(gk_graph *g, uint64_t *nodes_checksum, uint64_t *edges_che
     hipError_t e = hipMemsetAsync(d, 0, 16, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_graph_checksum, dim3(ggrid(ctx, std::max<u64>(std::max(g->v.n_nodes, g->v.n_edges), 1))), dim3(BLOCK), 0, ctx->stream, g->v, d);
-        e = hipGetLastError();
+        e = read_back(ctx, h, d, 2);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_checksum");
     if (nodes_checksum) *nodes_checksum = h[0];
     if (edges_checksum) *edges_checksum = h[1];
@@ -2389,11 +2341,8 @@ int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap,
     if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 8, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_export_nodes, dim3(ggrid(ctx, g->v.n_nodes)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_cur);
-        e = hipGetLastError();
+        e = read_back(ctx, {{lo, d_lo, cnt * 8}, {hi, d_hi, cnt * 8}});
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(lo, d_lo, cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && hi) e = hipMemcpyAsync(hi, d_hi, cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_export_nodes");
     return GK_OK;
 }
@@ -2427,16 +2376,9 @@ int gk_graph_export_edges(gk_graph *g, uint64_t *start_lo, uint64_t *start_hi, u
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_export_edges, dim3(ggrid(ctx, g->v.n_edges)), dim3(BLOCK), 0, ctx->stream, g->v, d_k[0], d_k[1], d_k[2],
                            d_k[3], d_len, d_off, d_seq, d_cur);
-        e = hipGetLastError();
+        e = read_back(ctx, {{h_cur, d_cur, 16}, {start_lo, d_k[0], cnt * 8}, {start_hi, d_k[1], cnt * 8}, {end_lo, d_k[2], cnt * 8},
+                            {end_hi, d_k[3], cnt * 8}, {len, d_len, cnt * 8}, {seq_off, d_off, cnt * 8}});
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cur, d_cur, 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(start_lo, d_k[0], cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && start_hi) e = hipMemcpyAsync(start_hi, d_k[1], cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(end_lo, d_k[2], cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && end_hi) e = hipMemcpyAsync(end_hi, d_k[3], cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(len, d_len, cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(seq_off, d_off, cnt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess && h_cur[1]) e = hipMemcpy(seq2bit, d_seq, h_cur[1], hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_export_edges");
     if (h_cur[0] != cnt) return fail(ctx, GK_E_STATE, "edge export count mismatch");
@@ -2452,11 +2394,8 @@ int gk_graph_out_order(gk_graph *g, uint64_t lo, uint64_t hi, int *bases4, int *
     int *d = nullptr, h[5] = {-1, 0, 0, 0, 0};
     DevScratch tmp(ctx);
     GK_HIP(ctx, tmp.get(&d, 5));
-    if (g->W == 1) hipLaunchKernelGGL(k_out_order<1>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, d);
-    else hipLaunchKernelGGL(k_out_order<2>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, 20, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    GK_BY_W(g->W, hipLaunchKernelGGL(k_out_order<W>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, d));
+    const hipError_t e = read_back(ctx, h, d, 5);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_out_order");
     *count = h[0];
     for (int i = 0; i < 4; i++) bases4[i] = i < h[0] ? h[1 + i] : 0;
@@ -2510,10 +2449,7 @@ int gk_graph_position_map(gk_graph *g, gk_vmap *vm, uint64_t *entries) {
     if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 16, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: alloc");
     if (v.n_edges) hipLaunchKernelGGL(k_pos_reserve, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, first, &d_cur[0]);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cur, d_cur, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: reserve");
+    if ((e = read_back(ctx, h_cur, d_cur, 1)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: reserve");
     // the reference's own check, printed side by side at :117: size == sum of edge lengths + nodes - edges
     const u64 total = g->live_nodes + h_cur[0];
     if (h_cur[0] != g->live_len - g->live_edges) return fail(ctx, GK_E_STATE, "gk_graph_position_map: interior k-mer count does not match the graph's counters");
@@ -2525,13 +2461,9 @@ int gk_graph_position_map(gk_graph *g, gk_vmap *vm, uint64_t *entries) {
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: entries");
     hipLaunchKernelGGL(k_pos_nodes, dim3(ggrid(ctx, std::max<u64>(v.n_nodes, 1))), dim3(BLOCK), 0, ctx->stream, v, lo, hi, val, &d_cur[1]);
     if (v.n_edges) {
-        if (g->W == 1) {
-            hipLaunchKernelGGL(k_pos_fill<1>, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val);
-            hipLaunchKernelGGL(k_pos_fill_long<1>, dim3((int)std::min<u64>(v.n_edges, (u64)ctx->cu_count * 8)), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val);
-        } else {
-            hipLaunchKernelGGL(k_pos_fill<2>, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val);
-            hipLaunchKernelGGL(k_pos_fill_long<2>, dim3((int)std::min<u64>(v.n_edges, (u64)ctx->cu_count * 8)), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val);
-        }
+        GK_BY_W(g->W,
+            hipLaunchKernelGGL(k_pos_fill<W>, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val);
+            hipLaunchKernelGGL(k_pos_fill_long<W>, dim3((int)std::min<u64>(v.n_edges, (u64)ctx->cu_count * 8)), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val));
     }
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: fill");
@@ -2548,11 +2480,8 @@ int gk_graph_node_lookup(gk_graph *g, uint64_t lo, uint64_t hi, int base, uint32
     u32 *d = nullptr, h[2] = {NONE, NONE};
     DevScratch tmp(ctx);
     GK_HIP(ctx, tmp.get(&d, 2));
-    if (g->W == 1) hipLaunchKernelGGL(k_node_lookup<1>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, base, d);
-    else hipLaunchKernelGGL(k_node_lookup<2>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, base, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h, d, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    GK_BY_W(g->W, hipLaunchKernelGGL(k_node_lookup<W>, dim3(1), dim3(1), 0, ctx->stream, g->v, lo, hi, base, d));
+    const hipError_t e = read_back(ctx, h, d, 2);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_node_lookup");
     if (node_id) *node_id = h[0];
     if (edge_id) *edge_id = h[1];
@@ -2596,9 +2525,7 @@ static int graph_point_edit(gk_graph *g, bool start, uint32_t edge_id, uint32_t 
     GK_HIP(ctx, tmp.get(&d, 1));
     if (start) hipLaunchKernelGGL(k_replace_start, dim3(1), dim3(1), 0, ctx->stream, g->v, edge_id, node_id, d);
     else hipLaunchKernelGGL(k_replace_end, dim3(1), dim3(1), 0, ctx->stream, g->v, edge_id, node_id, d);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = read_back(ctx, &h, d);
     if (e != hipSuccess) return hip_fail(ctx, e, "graph edit");
     if (h) return fail(ctx, GK_E_INVALID, std::string(start ? "gk_graph_replace_start" : "gk_graph_replace_end") + ": no such live edge / node");
     return GK_OK;
@@ -2624,14 +2551,8 @@ int gk_graph_nodes_by_id(gk_graph *g, const uint32_t *ids, uint64_t n, uint64_t 
     if (e == hipSuccess) e = hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_nodes_by_id, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_ids, n, d_lo, d_hi, d_al, d_in, d_out);
-        e = hipGetLastError();
+        e = read_back(ctx, {{lo, d_lo, n * 8}, {hi, d_hi, n * 8}, {alive, d_al, n}, {in_deg, d_in, n * 4}, {out_deg, d_out, n * 4}});
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(lo, d_lo, n * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hi, d_hi, n * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(alive, d_al, n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(in_deg, d_in, n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_deg, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_nodes_by_id");
     return GK_OK;
 }
@@ -2654,14 +2575,8 @@ int gk_graph_edges_by_id(gk_graph *g, const uint32_t *ids, uint64_t n, uint32_t 
     if (e == hipSuccess) e = hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_edges_by_id, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_ids, n, d_s, d_e, d_len, d_f, d_al);
-        e = hipGetLastError();
+        e = read_back(ctx, {{start_node, d_s, n * 4}, {end_node, d_e, n * 4}, {len, d_len, n * 8}, {first_base, d_f, n}, {alive, d_al, n}});
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(start_node, d_s, n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(end_node, d_e, n * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(len, d_len, n * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(first_base, d_f, n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(alive, d_al, n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edges_by_id");
     return GK_OK;
 }

@@ -312,10 +312,7 @@ int graph_save_impl(gk_graph *g, const std::string &path, const std::string &tmp
     GK_HIP(ctx, scan_counts(ctx, elive, ne, erank, sums));
     GK_HIP(ctx, scan_counts(ctx, ebytes, ne, poff, sums));
     unsigned long long tot[3] = {0, 0, 0};
-    GK_HIP(ctx, hipMemcpyAsync(&tot[0], nrank + nn, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipMemcpyAsync(&tot[1], erank + ne, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipMemcpyAsync(&tot[2], poff + ne, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, {{&tot[0], nrank + nn, 8}, {&tot[1], erank + ne, 8}, {&tot[2], poff + ne, 8}}));
     h.nodes = tot[0]; h.edges = tot[1]; h.pool_bytes = tot[2];
     if (h.nodes != g->live_nodes || h.edges != g->live_edges) return fail(ctx, GK_E_STATE, "gk_graph_save: live counts disagree with the graph's");
     const Layout L = gio_layout(g->k, h.nodes, h.edges, h.pool_bytes);
@@ -487,9 +484,7 @@ int graph_load_impl(gk_ctx *ctx, const std::string &path, gk_graph *g, float *ms
     GK_HIP(ctx, scan_counts(ctx, nbytes, h.edges, poff, sums));
     u32 hflags = 0;
     unsigned long long pool_sum = 0;
-    GK_HIP(ctx, hipMemcpyAsync(&hflags, flags, 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipMemcpyAsync(&pool_sum, poff + h.edges, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, {{&hflags, flags, 4}, {&pool_sum, poff + h.edges, 8}}));
     if (hflags) return bad(gio_flag_text(hflags));
     if (pool_sum != h.pool_bytes)
         return bad("pool of " + std::to_string(h.pool_bytes) + " bytes, the edge lengths need " + std::to_string(pool_sum));
@@ -501,8 +496,7 @@ int graph_load_impl(gk_ctx *ctx, const std::string &path, gk_graph *g, float *ms
         hipLaunchKernelGGL(k_gio_load_orders, dim3(ggrid(ctx, h.nodes)), dim3(BLOCK), 0, ctx->stream, v, ids, h.nodes, flags);
         GK_HIP(ctx, hipGetLastError());
     }
-    GK_HIP(ctx, hipMemcpyAsync(&hflags, flags, 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, &hflags, flags));
     if (hflags) return bad(gio_flag_text(hflags));
     if (int rc = graph_refresh_counts(g)) return rc;
     g->index_ready = false;                   // (built on the first point query, as after a build)

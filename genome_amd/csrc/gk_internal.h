@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -143,6 +144,19 @@ struct __attribute__((visibility("hidden"))) DevScratch {      // (internal: its
     }
     template <class T> void release(T *&p) { (void)pool_free(ctx, take(p)); p = nullptr; }
 };
+
+// The end of a step whose result the host needs: check the launches so far, copy device -> host on ctx->stream in the order
+// given (a null destination skips its copy), wait for the stream ONCE.  Returns the first error.  The destinations stay what
+// the caller made them (pageable or pinned).
+struct D2H { void *dst; const void *src; size_t bytes; };
+static inline hipError_t read_back(gk_ctx *ctx, std::initializer_list<D2H> copies) {
+    hipError_t e = hipGetLastError();
+    for (const D2H &c : copies)
+        if (e == hipSuccess && c.dst) e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e;
+}
+template <class T> static inline hipError_t read_back(gk_ctx *ctx, T *h, const void *d, size_t n = 1) { return read_back(ctx, {{h, d, n * sizeof(T)}}); }
 }
 
 struct gk_map {
@@ -262,6 +276,12 @@ inline size_t map_slot_bytes(const gk_map *m) { return slot_bytes(m->W, m->layou
         if ((m_)->W == 2) { constexpr int W = 2; using S = gk::Slot<2>; (void)W; __VA_ARGS__; }          \
         else if ((m_)->layout == gk::LAYOUT_GRAPH) { constexpr int W = 1; using S = gk::Slot<1>; (void)W; __VA_ARGS__; } \
         else { constexpr int W = 1; using S = gk::CSlot; (void)W; __VA_ARGS__; }                         \
+    } while (0)
+// run BODY with `W` (constexpr int) bound to a key width of 1 or 2 words: graphs, value maps, key lists (no slot type involved)
+#define GK_BY_W(w_, ...)                                                                                 \
+    do {                                                                                                 \
+        if ((w_) == 1) { constexpr int W = 1; (void)W; __VA_ARGS__; }                                    \
+        else { constexpr int W = 2; (void)W; __VA_ARGS__; }                                              \
     } while (0)
 
 // table ops used across translation units

@@ -720,8 +720,7 @@ int support_reserve(gk_support *s, u64 want) {
     if (e != hipSuccess) { (void)pool_free(ctx, nk); (void)pool_free(ctx, nc); return hip_fail(ctx, e, "gk_support: table"); }
     if (s->cap) {
         unsigned long long distinct = 0;
-        GK_HIP(ctx, hipMemcpyAsync(&distinct, s->d_ctr, 8, hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GK_HIP(ctx, read_back(ctx, &distinct, s->d_ctr));
         GK_HIP(ctx, hipMemsetAsync(s->d_ctr, 0, 8, ctx->stream));                   // (the rehash counts the distinct pairs again)
         hipLaunchKernelGGL(k_sup_rehash, dim3(ggrid(ctx, s->cap)), dim3(BLOCK), 0, ctx->stream, s->d_keys, s->d_cnt, s->cap, SupView{nk, nc, need - 1, s->d_ctr});
         GK_HIP(ctx, hipGetLastError());
@@ -735,8 +734,7 @@ int support_reserve(gk_support *s, u64 want) {
 
 int support_counters(const gk_support *s, unsigned long long *h4) {
     gk_ctx *ctx = s->ctx;
-    GK_HIP(ctx, hipMemcpyAsync(h4, s->d_ctr, 32, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, h4, s->d_ctr, 4));
     return GK_OK;
 }
 
@@ -762,11 +760,8 @@ int support_bucket(gk_support *s, int P, u64 *d_keys, u32 *d_cnt, u64 room, u64 
     GK_HIP(ctx, hipGetLastError());
     GK_HIP(ctx, scan_counts(ctx, d_counts, n, d_off, d_sums));
     hipLaunchKernelGGL(k_sup_regions, dim3(1), dim3(64), 0, ctx->stream, d_off, nwg, (u32)P, d_region);
-    GK_HIP(ctx, hipGetLastError());
     std::vector<unsigned long long> h(P + 1);
-    GK_HIP(ctx, hipMemcpyAsync(h.data(), d_region, (P + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, {{h.data(), d_region, (size_t)(P + 1) * 8}, {&h_bad, d_bad, 4}}));
     if (h_bad) return fail(ctx, GK_E_STATE, "the support names an edge that is not a live edge of this graph");
     if (h[P] > room) return fail(ctx, GK_E_STATE, "support_bucket: " + std::to_string(h[P]) + " live slots, room for " + std::to_string(room));
     if (h[P]) {
@@ -789,10 +784,8 @@ int support_insert(gk_support *s, const u64 *d_keys, const u32 *d_cnt, u64 n, bo
     s->host_valid = false;
     if (checked) hipLaunchKernelGGL(k_sup_add_list_checked, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, d_keys, d_cnt, n, sup_view(s));
     else hipLaunchKernelGGL(k_sup_add_list, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, d_keys, d_cnt, n, sup_view(s));
-    GK_HIP(ctx, hipGetLastError());
     unsigned long long f[2] = {0, 0};                          // [3] table full, [4] a count wrapped
-    GK_HIP(ctx, hipMemcpyAsync(f, s->d_ctr + 3, 16, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, f, s->d_ctr + 3, 2));
     if (f[0]) return fail(ctx, GK_E_CAPACITY, "support_insert: the support table filled up (internal sizing error)");
     if (overflow) *overflow = f[1] != 0;
     return GK_OK;
@@ -825,18 +818,14 @@ int graph_edge_canon(gk_graph *g, DevScratch &keep, u32 **d_canon, u32 **d_inv, 
         GK_HIP(ctx, hipGetLastError());
         GK_HIP(ctx, rocprim::radix_sort_pairs(d_temp, temp_bytes, d_k, d_k2, d_id, d_id2, (size_t)ne, 0, 64, ctx->stream));
     }
-    GK_HIP(ctx, hipMemcpyAsync(h_out, d_out, 16, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, h_out, d_out, 2));
     u32 *canon = nullptr, *inv = nullptr;
     e = keep.get(&canon, ne);
     if (e == hipSuccess) e = keep.get(&inv, h_out[0]);
     if (e == hipSuccess) e = hipMemsetAsync(canon, 0xff, std::max<u64>(ne, 1) * 4, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon: maps");
     if (h_out[0]) hipLaunchKernelGGL(k_edge_canon, dim3(ggrid(ctx, h_out[0])), dim3(BLOCK), 0, ctx->stream, d_k2, d_id2, (u64)h_out[0], canon, inv, d_flag);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon");
+    if ((e = read_back(ctx, &h_flag, d_flag)) != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon");
     if (h_flag) return fail(ctx, GK_E_STATE, "two live edges share a start k-mer and a first base (a node split made copies): their support cannot be summed by content");
     *d_canon = canon; *d_inv = inv;
     *nlive = h_out[0];
@@ -851,9 +840,7 @@ int support_keys_uncanon(gk_ctx *ctx, u64 *d_keys, u64 n, const u32 *d_inv, u64 
     GK_HIP(ctx, tmp.get(&d_bad, 1));
     GK_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, ctx->stream));
     hipLaunchKernelGGL(k_sup_uncanon, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, d_keys, n, d_inv, nlive, d_bad);
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, &h_bad, d_bad));
     if (h_bad) return fail(ctx, GK_E_STATE, "support_keys_uncanon: a pair outside the canonical edge numbering");
     return GK_OK;
 }
@@ -881,9 +868,7 @@ int support_to_host(gk_support *s) {
     if (s->cap) {
         std::vector<u64> k(s->cap);
         std::vector<u32> c(s->cap);
-        GK_HIP(ctx, hipMemcpyAsync(k.data(), s->d_keys, s->cap * 8, hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipMemcpyAsync(c.data(), s->d_cnt, s->cap * 4, hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GK_HIP(ctx, read_back(ctx, {{k.data(), s->d_keys, s->cap * 8}, {c.data(), s->d_cnt, s->cap * 4}}));
         for (u64 i = 0; i < s->cap; i++) if (k[i] != SUP_EMPTY) s->paths.emplace(k[i], c[i]);
     }
     s->host_valid = true;
@@ -956,9 +941,7 @@ int gk_support_merge(gk_support *dst, const gk_support *src) {
         GK_HIP(ctx, tmp.get(&d_wrap, 1));
         GK_HIP(ctx, hipMemsetAsync(d_wrap, 0, 4, ctx->stream));
         hipLaunchKernelGGL(k_sup_check_merge, dim3(ggrid(ctx, src->cap)), dim3(BLOCK), 0, ctx->stream, src->d_keys, src->d_cnt, src->cap, sup_view(dst), d_wrap);
-        GK_HIP(ctx, hipGetLastError());
-        GK_HIP(ctx, hipMemcpyAsync(&h_wrap, d_wrap, 4, hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GK_HIP(ctx, read_back(ctx, &h_wrap, d_wrap));
         if (h_wrap) return fail(ctx, GK_E_CAPACITY, "gk_support_merge: a count would pass 2^32-1; nothing was added");
     }
     if (src->cap && hs[0]) {
@@ -1017,9 +1000,7 @@ int gk_graph_id_fingerprint(gk_graph *g, uint64_t *fp) {
     GK_HIP(ctx, tmp.get(&d, 1));
     GK_HIP(ctx, hipMemsetAsync(d, 0, 8, ctx->stream));
     hipLaunchKernelGGL(k_graph_id_fingerprint, dim3(ggrid(ctx, std::max<u64>(std::max(g->v.n_nodes, g->v.n_edges), 1))), dim3(BLOCK), 0, ctx->stream, g->v, d);
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, &h, d));
     *fp = h + mix64(mix64(g->v.n_nodes ^ 0x626f756e6473ULL) ^ (g->v.n_edges + 0x9e3779b97f4a7c15ULL));     // and the id bounds
     return GK_OK;
 }
@@ -1062,11 +1043,8 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
             if (e == hipSuccess) e = hipMemsetAsync(d_rag, 0, 4, ctx->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(d_bin, bin, 2 * npairs * rb, hipMemcpyHostToDevice, ctx->stream);
             if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_walk_pairs: upload");
-            if (W == 1) hipLaunchKernelGGL(k_pair_keys<1>, dim3(ggrid(ctx, npairs)), dim3(BLOCK), 0, ctx->stream, d_bin, npairs, (u32)rb, l0, k, d_lo, d_hi, d_rag);
-            else hipLaunchKernelGGL(k_pair_keys<2>, dim3(ggrid(ctx, npairs)), dim3(BLOCK), 0, ctx->stream, d_bin, npairs, (u32)rb, l0, k, d_lo, d_hi, d_rag);
-            GK_HIP(ctx, hipGetLastError());
-            GK_HIP(ctx, hipMemcpyAsync(&h_rag, d_rag, 4, hipMemcpyDeviceToHost, ctx->stream));
-            GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            GK_BY_W(g->W, hipLaunchKernelGGL(k_pair_keys<W>, dim3(ggrid(ctx, npairs)), dim3(BLOCK), 0, ctx->stream, d_bin, npairs, (u32)rb, l0, k, d_lo, d_hi, d_rag));
+            GK_HIP(ctx, read_back(ctx, &h_rag, d_rag));
             if (!h_rag) { cut = true; nq = 4 * npairs; }
         }
     }
@@ -1118,8 +1096,7 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
         if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_walk_pairs: lookup arrays");
         if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, nullptr, d_cnt, nullptr)) return rc;
         GK_HIP(ctx, scan_counts(ctx, d_cnt, nq, d_off, d_sums));
-        GK_HIP(ctx, hipMemcpyAsync(&total, d_off + nq, 8, hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GK_HIP(ctx, read_back(ctx, &total, d_off + nq));
         GK_HIP(ctx, tmp.get(&d_vals, total));
         if (total) { if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, d_off, d_cnt, d_vals)) return rc; }
     }
@@ -1150,8 +1127,7 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
         if (v.n_edges) hipLaunchKernelGGL(k_in_fill, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, d_in_off, d_in_cnt, d_in_list);
         GK_HIP(ctx, hipGetLastError());
     }
-    GK_HIP(ctx, hipMemcpyAsync(h_flag, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, h_flag, d_flag, 1));
     if (h_flag[0]) return fail(ctx, GK_E_STATE, "gk_graph_walk_pairs: the position map does not belong to this graph (rebuild it after edits)");
     const double t_snap = now();
     // ---- the walks: one wave per pair orientation (two per pair: (f1, f2) and (f3, f4)  :219)
@@ -1168,9 +1144,7 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
                            ctx->hook_pairs_small_sets > 0 ? WalkArgs{k, range_lo, range_hi, 6u, 10u, 3u}       // (test: most walks outgrow their sets -> host walker)
                                                           : WalkArgs{k, range_lo, range_hi, W_RMAX, W_QCAP, W_PMAX},
                            sup_view(sup), d_ov, ov_cap, d_flag + 1);
-        GK_HIP(ctx, hipGetLastError());
-        GK_HIP(ctx, hipMemcpyAsync(h_flag + 1, d_flag + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        GK_HIP(ctx, read_back(ctx, h_flag + 1, d_flag + 1, 1));
     }
     const double t_walks = now();
     // ---- what the device could not hold (or everything, under the A/B switch): the host walker over a snapshot
@@ -1329,10 +1303,8 @@ int gk_graph_remove_edges_by_id(gk_graph *g, const uint32_t *edge_ids, uint64_t 
     if (e == hipSuccess) e = hipMemsetAsync(d_rm, 0, 8, ctx->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_remove_edges_by_id, dim3(ggrid(ctx, ids.size())), dim3(BLOCK), 0, ctx->stream, g->v, d_e, (u64)ids.size(), d_rm);
-        e = hipGetLastError();
+        e = read_back(ctx, &h_rm, d_rm);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_rm, d_rm, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_remove_edges_by_id");
     if (removed) *removed = h_rm;
     return graph_refresh_counts(g);

@@ -156,10 +156,7 @@ int pf_launch_add(gk_prefilter *pf, const uint8_t *d_rec, u64 nreads, const u32 
     gk_ctx *ctx = pf->ctx;
     const u64 ntiles = (nreads + TILE_READS - 1) / TILE_READS;
     const int grid = (int)std::min<u64>(std::max<u64>(ntiles, 1), (u64)ctx->cu_count * 8);
-    if (pf->W == 1)
-        hipLaunchKernelGGL(k_pf_add<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, d_rec, nreads, d_off, stride, pf->k, WindowLimits{max_len, ctx->d_flags}, pf->words, pf->nbuckets, pf->d_cursor + 1);
-    else
-        hipLaunchKernelGGL(k_pf_add<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, d_rec, nreads, d_off, stride, pf->k, WindowLimits{max_len, ctx->d_flags}, pf->words, pf->nbuckets, pf->d_cursor + 1);
+    GK_BY_W(pf->W, hipLaunchKernelGGL(k_pf_add<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, d_rec, nreads, d_off, stride, pf->k, WindowLimits{max_len, ctx->d_flags}, pf->words, pf->nbuckets, pf->d_cursor + 1));
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
 }
@@ -182,16 +179,10 @@ int pf_select_and_insert(gk_prefilter *pf, gk_map *m, const uint8_t *d_rec, u64 
     const u64 ntiles = (nreads + rs - 1) / rs;
     const int grid = (int)std::min<u64>(std::max<u64>(ntiles, 1), (u64)ctx->cu_count * 8);
     const size_t lds = (size_t)rs * per_read * 8 * pf->W;
-    if (pf->W == 1)
-        hipLaunchKernelGGL(k_pf_select<1>, dim3(grid), dim3(BLOCK), lds, ctx->stream, d_rec, nreads, d_off, stride, pf->k, WindowLimits{max_len, ctx->d_flags}, rs, pf->words, pf->nbuckets,
-                           pf->keybuf, pf->keybuf_keys, pf->d_cursor, d_ovf);
-    else
-        hipLaunchKernelGGL(k_pf_select<2>, dim3(grid), dim3(BLOCK), lds, ctx->stream, d_rec, nreads, d_off, stride, pf->k, WindowLimits{max_len, ctx->d_flags}, rs, pf->words, pf->nbuckets,
-                           pf->keybuf, pf->keybuf_keys, pf->d_cursor, d_ovf);
-    GK_HIP(ctx, hipGetLastError());
+    GK_BY_W(pf->W, hipLaunchKernelGGL(k_pf_select<W>, dim3(grid), dim3(BLOCK), lds, ctx->stream, d_rec, nreads, d_off, stride, pf->k, WindowLimits{max_len, ctx->d_flags}, rs, pf->words, pf->nbuckets,
+                                      pf->keybuf, pf->keybuf_keys, pf->d_cursor, d_ovf));
     unsigned long long h[3] = {0, 0, 0};
-    GK_HIP(ctx, hipMemcpyAsync(h, pf->d_cursor, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, h, pf->d_cursor, 3));
     if ((u32)h[2]) return fail(ctx, GK_E_CAPACITY, "prefilter: admitted keys exceed the key buffer (internal sizing error)");
     if (int rc = ctx_check_format(ctx)) return rc;
     *admitted_total += h[0];
@@ -396,10 +387,8 @@ int gk_prefilter_stats(gk_prefilter *pf, uint64_t *buckets, uint64_t *seen_once,
     GK_HIP(ctx, hipMemsetAsync(pf->d_cursor + 2, 0, 16, ctx->stream));
     const int grid = (int)std::min<u64>(std::max<u64>((pf->nwords + BLOCK - 1) / BLOCK, 1), (u64)ctx->cu_count * 8);
     hipLaunchKernelGGL(k_pf_stats, dim3(grid), dim3(BLOCK), 0, ctx->stream, pf->words, pf->nwords, pf->d_cursor + 2);
-    GK_HIP(ctx, hipGetLastError());
     unsigned long long h[2] = {0, 0};
-    GK_HIP(ctx, hipMemcpyAsync(h, pf->d_cursor + 2, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, h, pf->d_cursor + 2, 2));
     if (buckets) *buckets = pf->nbuckets;
     if (seen_once) *seen_once = h[0];
     if (seen_twice_or_more) *seen_twice_or_more = h[1];

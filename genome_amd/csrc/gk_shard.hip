@@ -145,9 +145,7 @@ int gk_map_count_foreign(gk_map *m, int P, int p, uint64_t *foreign) {
     const int grid = (int)std::min<u64>(std::max<u64>((m->capacity + BLOCK - 1) / BLOCK, 1), (u64)ctx->cu_count * 8);
     GK_BY_SLOT(m, hipLaunchKernelGGL((k_count_foreign<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream,
                                      Table<W, S>{(S *)m->slots, m->nb2, m->lnb1, m->k == 64 ? 1u : 0u}, m->k, P, p, d));
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, &h, d));
     *foreign = h;
     return GK_OK;
 }
@@ -165,7 +163,6 @@ int gk_shard_reads_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_t nre
     if (nreads == 0 || nk == 0) return GK_OK;
     if (nreads * nk > keys_cap) return fail(ctx, GK_E_CAPACITY, "keys_cap too small: need " + std::to_string(nreads * nk));
     if (!dev_keys_out) return fail(ctx, GK_E_INVALID, "null key buffer");
-    const int W = words_for_k(k);
     const u32 stride = 1 + (read_len + 3) / 4;
     unsigned long long *d_cnt = nullptr;
     DevScratch tmp(ctx);
@@ -174,22 +171,18 @@ int gk_shard_reads_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_t nre
     const u64 ntiles = (nreads + TILE_READS - 1) / TILE_READS;
     const int grid = (int)std::min<u64>(ntiles, (u64)ctx->cu_count * 8);
     const uint8_t *rec = (const uint8_t *)dev_records;
-    if (e == hipSuccess) {
-        if (W == 1) hipLaunchKernelGGL(k_shard_count<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, rec, nreads, stride, k, P, WindowLimits{read_len, ctx->d_flags}, d_cnt);
-        else hipLaunchKernelGGL(k_shard_count<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, rec, nreads, stride, k, P, WindowLimits{read_len, ctx->d_flags}, d_cnt);
-        e = hipGetLastError();
-    }
     unsigned long long h_cnt[MAX_PARTS], h_cur[MAX_PARTS];
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, P * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) {
+        GK_BY_W(words_for_k(k), hipLaunchKernelGGL(k_shard_count<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, rec, nreads, stride, k, P, WindowLimits{read_len, ctx->d_flags}, d_cnt));
+        e = read_back(ctx, h_cnt, d_cnt, P);
+    }
     if (e == hipSuccess) {
         unsigned long long acc = 0;
         for (int p = 0; p < P; p++) { h_cur[p] = acc; acc += h_cnt[p]; counts_host[p] = h_cnt[p]; }
         e = hipMemcpyAsync(d_cnt + MAX_PARTS, h_cur, P * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
     }
     if (e == hipSuccess) {
-        if (W == 1) hipLaunchKernelGGL(k_shard_scatter<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, rec, nreads, stride, k, P, WindowLimits{read_len, nullptr}, d_cnt + MAX_PARTS, (u64 *)dev_keys_out);
-        else hipLaunchKernelGGL(k_shard_scatter<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, rec, nreads, stride, k, P, WindowLimits{read_len, nullptr}, d_cnt + MAX_PARTS, (u64 *)dev_keys_out);
+        GK_BY_W(words_for_k(k), hipLaunchKernelGGL(k_shard_scatter<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, rec, nreads, stride, k, P, WindowLimits{read_len, nullptr}, d_cnt + MAX_PARTS, (u64 *)dev_keys_out));
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);

@@ -575,8 +575,7 @@ int stage_source(gk_ctx *ctx, const ReadSrc &src) {
 
 int ctx_check_format(gk_ctx *ctx) {
     u32 f = 0;
-    GK_HIP(ctx, hipMemcpyAsync(&f, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, &f, ctx->d_flags));
     if (!f) return GK_OK;
     GK_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, 4, ctx->stream));
     return fail(ctx, GK_E_FORMAT, "a device record's length byte exceeds the declared read length");
@@ -1589,8 +1588,7 @@ int map_add_unique_keys_dev(gk_map *m, const uint64_t *d_keys, const int32_t *d_
     if (m->W == 1 && m->layout != LAYOUT_GRAPH) return fail(ctx, GK_E_STATE, "map_add_unique_keys_dev: count-layout table");
     if (int rc = map_reserve(m, n)) return rc;
     const int grid = grid_for(ctx, n, BLOCK);
-    if (m->W == 1) hipLaunchKernelGGL((k_add_unique<1>), dim3(grid), dim3(BLOCK), 0, ctx->stream, d_keys, d_counts, d_masks, n, table_of<1, Slot<1>>(m), m->d_ctr);
-    else hipLaunchKernelGGL((k_add_unique<2>), dim3(grid), dim3(BLOCK), 0, ctx->stream, d_keys, d_counts, d_masks, n, table_of<2, Slot<2>>(m), m->d_ctr);
+    GK_BY_W(m->W, hipLaunchKernelGGL((k_add_unique<W>), dim3(grid), dim3(BLOCK), 0, ctx->stream, d_keys, d_counts, d_masks, n, table_of<W, Slot<W>>(m), m->d_ctr));
     GK_HIP(ctx, hipGetLastError());
     return map_sync_counters(m);
 }
@@ -1606,10 +1604,8 @@ int map_export_range_dev(gk_map *m, uint64_t s0, uint64_t s1, uint64_t *d_keys, 
     const int grid = grid_for(ctx, s1 - s0, BLOCK);
     GK_BY_SLOT(m, hipLaunchKernelGGL((k_export_packed<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, (const S *)m->slots + s0, s1 - s0, s0, m->k == 64 ? 1u : 0u, d_keys,
                                      d_cnt, d_cursor, d_masks));
-    GK_HIP(ctx, hipGetLastError());
     unsigned long long n = 0;
-    GK_HIP(ctx, hipMemcpyAsync(&n, d_cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, &n, d_cursor));
     *n_out = n;
     return GK_OK;
 }
@@ -1802,9 +1798,7 @@ static int streaming_rebuild(gk_map *m, uint32_t nnb2, uint32_t nlnb1, uint64_t 
     else if (m->layout == LAYOUT_GRAPH) e = launch_compact<1, Slot<1>, CSlot>(m, nslots, nnb2, nlnb1, rounds, gc);
     else if (new_layout == LAYOUT_GRAPH) e = launch_compact<1, CSlot, Slot<1>>(m, nslots, nnb2, nlnb1, rounds, gc);
     else e = launch_compact<1, CSlot, CSlot>(m, nslots, nnb2, nlnb1, rounds, gc);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&h_kept, &m->d_ctr->rebuild_kept, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = read_back(ctx, &h_kept, &m->d_ctr->rebuild_kept);
     if (e != hipSuccess) { (void)pool_free(ctx, nslots); return hip_fail(ctx, e, "streaming table rebuild"); }
     const u64 kept = h_kept;
     if (int rc = map_sync_counters(m)) {                   // a segment of the new table filled up (a sizing error): the old table stays
@@ -1841,9 +1835,7 @@ static int filter_compact_streaming(gk_map *m, int32_t rounds, bool *done) {
     const u32 every = nseg >= 4096 ? 16u : 1u;
     const int gs = (int)std::min<u64>((nseg + every - 1) / every, (u64)ctx->cu_count * 8);
     GK_BY_SLOT(m, hipLaunchKernelGGL((k_count_ge_sample<W, S>), dim3(gs), dim3(BLOCK), 0, ctx->stream, (const S *)m->slots, nseg, every, rounds, d2));
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipMemcpyAsync(h2, d2, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, h2, d2, 1));
     const u64 est = (u64)((double)h2[0] * every * 1.03) + 1024;
     // 2. the new table's geometry (same rule as map_compact)
     const double graph_load = graph_table_load(ctx, m->k, est);
@@ -1870,10 +1862,8 @@ int gk_map_filter_lt(gk_map *m, int32_t rounds) {
     GK_HIP(ctx, hipMemsetAsync(d_removed, 0, sizeof(unsigned long long), ctx->stream));
     int grid = grid_for(ctx, m->capacity, BLOCK * 4);
     GK_BY_SLOT(m, hipLaunchKernelGGL(k_filter_lt<S>, dim3(grid), dim3(BLOCK), 0, ctx->stream, (S *)m->slots, m->capacity, rounds, d_removed));
-    GK_HIP(ctx, hipGetLastError());
     unsigned long long removed = 0;
-    GK_HIP(ctx, hipMemcpyAsync(&removed, d_removed, sizeof(removed), hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, &removed, d_removed));
     m->size -= removed;
     m->tombstones += removed;
     unsigned long long sz = m->size;
@@ -1933,10 +1923,7 @@ int gk_map_get_batch(gk_map *m, const uint64_t *lo, const uint64_t *hi, uint64_t
     if (d_hi) GK_HIP(ctx, hipMemcpyAsync(d_hi, hi, n * 8, hipMemcpyHostToDevice, ctx->stream));
     int grid = grid_for(ctx, n, BLOCK);
     GK_BY_SLOT(m, hipLaunchKernelGGL((k_get<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, d_lo, d_hi, n, table_of<W, S>(m), d_cnt, d_found));
-    GK_HIP(ctx, hipGetLastError());
-    if (counts_out) GK_HIP(ctx, hipMemcpyAsync(counts_out, d_cnt, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (found_out) GK_HIP(ctx, hipMemcpyAsync(found_out, d_found, n, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, {{counts_out, d_cnt, n * 4}, {found_out, d_found, n}}));
     return GK_OK;
 }
 
@@ -1957,13 +1944,8 @@ int gk_map_export(gk_map *m, uint64_t *lo, uint64_t *hi, int32_t *counts, uint64
     GK_HIP(ctx, hipMemsetAsync(d_cursor, 0, 8, ctx->stream));
     int grid = grid_for(ctx, m->capacity, BLOCK);
     GK_BY_SLOT(m, hipLaunchKernelGGL((k_export<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, (const S *)m->slots, m->capacity, m->k == 64 ? 1u : 0u, d_lo, d_hi, d_cnt, d_cursor));
-    GK_HIP(ctx, hipGetLastError());
     unsigned long long written = 0;
-    GK_HIP(ctx, hipMemcpyAsync(&written, d_cursor, 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipMemcpyAsync(lo, d_lo, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (hi) GK_HIP(ctx, hipMemcpyAsync(hi, d_hi, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipMemcpyAsync(counts, d_cnt, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, {{&written, d_cursor, 8}, {lo, d_lo, cnt * 8}, {hi, d_hi, cnt * 8}, {counts, d_cnt, cnt * 4}}));
     if (written != cnt) return fail(ctx, GK_E_STATE, "export wrote " + std::to_string(written) + " entries, size says " + std::to_string(cnt));
     return GK_OK;
 }
@@ -1976,9 +1958,7 @@ int gk_map_verify(gk_map *m, uint64_t *live, uint64_t *bad_slots, uint64_t *sum_
     GK_HIP(ctx, hipMemsetAsync(d, 0, 32, ctx->stream));
     int grid = grid_for(ctx, m->capacity, BLOCK);
     GK_BY_SLOT(m, hipLaunchKernelGGL((k_verify<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, table_of<W, S>(m), d));
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipMemcpyAsync(h, d, 32, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, h, d, 4));
     if (live) *live = h[0];
     if (bad_slots) *bad_slots = h[1];
     if (sum_counts) *sum_counts = h[2];

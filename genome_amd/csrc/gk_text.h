@@ -1,6 +1,11 @@
-// gk_text.h — line ends of a text tile on the device, shared by the FASTQ parser (gk_fastq.hip) and the FASTA check (gk_fasta.hip):
+// gk_text.h — what the FASTQ parser (gk_fastq.hip) and the FASTA check (gk_fasta.hip) share.  Device: line ends of a text tile —
 // the terminator passes over 16 KiB tiles staged in LDS, and the start of line j from the terminator array they write.
+// Host: the slice upload on the copy stream (TextUpload) and the event-timed section of kernels (TimedSection).
 #pragma once
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
 
 #include "gk_scan.h"
 #include "gk_tile.h"
@@ -60,5 +65,76 @@ __global__ __launch_bounds__(FQ_BLOCK) void k_fq_terms(const uint8_t *__restrict
         o += (u64)__popcll(mask);
     }
 }
+
+// ---- host half ----------------------------------------------------------------------------------------------------------------
+using clk = std::chrono::steady_clock;
+double ms_since(clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); }
+
+// Uploads of text slices into the two device buffers of a stage: on the copy stream, between the event pair up0[b] / up1[b]
+// (the consumer waits for up1[b] and reads the pair's time).  Pageable text goes through one of two pinned staging buffers,
+// grown on demand to a power of two.
+struct TextUpload {
+    hipEvent_t up0[2] = {nullptr, nullptr}, up1[2] = {nullptr, nullptr};
+    uint8_t *h_stage[2] = {nullptr, nullptr};
+    u64 h_stage_cap = 0;
+
+    hipError_t create() {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 2 && e == hipSuccess; i++) {
+            e = hipEventCreate(&up0[i]);
+            if (e == hipSuccess) e = hipEventCreate(&up1[i]);
+        }
+        return e;
+    }
+    void destroy() {
+        for (int i = 0; i < 2; i++) {
+            if (h_stage[i]) (void)hipHostFree(h_stage[i]);
+            if (up0[i]) (void)hipEventDestroy(up0[i]);
+            if (up1[i]) (void)hipEventDestroy(up1[i]);
+        }
+    }
+    static bool is_pinned(const void *p) {
+        unsigned int flags = 0;
+        const bool ok = hipHostGetFlags(&flags, const_cast<void *>(p)) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        return ok;
+    }
+    // text [src, src + bytes) -> d_dst; *host_ms grows by the time of the host's copy into the staging buffer
+    int upload(gk_ctx *ctx, int b, void *d_dst, const char *src, u64 bytes, bool pinned, double *host_ms) {
+        const void *from = src;
+        if (!pinned) {
+            if (h_stage_cap < bytes) {
+                GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+                for (int i = 0; i < 2; i++) { if (h_stage[i]) (void)hipHostFree(h_stage[i]); h_stage[i] = nullptr; }
+                h_stage_cap = 0;
+                const u64 cap = pow2ceil(std::max<u64>(bytes, 4096));
+                for (int i = 0; i < 2; i++) GK_HIP(ctx, hipHostMalloc((void **)&h_stage[i], cap, 0));
+                h_stage_cap = cap;
+            }
+            const auto t0 = clk::now();
+            memcpy(h_stage[b], src, bytes);
+            *host_ms += ms_since(t0);
+            from = h_stage[b];
+        }
+        GK_HIP(ctx, hipEventRecord(up0[b], ctx->copy_stream));
+        GK_HIP(ctx, hipMemcpyAsync(d_dst, from, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+        GK_HIP(ctx, hipEventRecord(up1[b], ctx->copy_stream));
+        return GK_OK;
+    }
+};
+
+// A section of work on ctx->stream between the context's event pair: end() waits for it and adds its time to *acc_ms.
+struct TimedSection {
+    gk_ctx *ctx;
+    hipError_t start() const { return hipEventRecord(ctx->ev0, ctx->stream); }
+    int end(double *acc_ms) const {
+        GK_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        GK_HIP(ctx, hipEventSynchronize(ctx->ev1));
+        float t = 0;
+        GK_HIP(ctx, hipEventElapsedTime(&t, ctx->ev0, ctx->ev1));
+        *acc_ms += t;
+        return GK_OK;
+    }
+};
 
 }  // namespace

@@ -190,16 +190,14 @@ int vm_check(const gk_vmap *m) {
 int vm_alloc_table(gk_ctx *ctx, int W, u64 cap, void **out) {
     hipError_t e = pool_malloc(ctx, out, cap * slot_bytes(W));
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, GK_E_CAPACITY, std::string("value map: cannot allocate table: ") + hipGetErrorString(e)); }
-    if (W == 1) hipLaunchKernelGGL(k_vm_clear<1>, dim3(vgrid(ctx, cap / 4)), dim3(BLOCK), 0, ctx->stream, (Slot<1> *)*out, cap);
-    else hipLaunchKernelGGL(k_vm_clear<2>, dim3(vgrid(ctx, cap / 4)), dim3(BLOCK), 0, ctx->stream, (Slot<2> *)*out, cap);
+    GK_BY_W(W, hipLaunchKernelGGL(k_vm_clear<W>, dim3(vgrid(ctx, cap / 4)), dim3(BLOCK), 0, ctx->stream, (Slot<W> *)*out, cap));
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
 }
 
 int vm_sync(gk_vmap *m) {
     unsigned long long h[2] = {0, 0};
-    GK_HIP(m->ctx, hipMemcpyAsync(h, m->d_ctr, 16, hipMemcpyDeviceToHost, m->ctx->stream));
-    GK_HIP(m->ctx, hipStreamSynchronize(m->ctx->stream));
+    GK_HIP(m->ctx, read_back(m->ctx, h, m->d_ctr, 2));
     m->size = h[0];
     if (h[1]) {
         GK_HIP(m->ctx, hipMemsetAsync(m->d_ctr + 1, 0, 8, m->ctx->stream));
@@ -223,12 +221,8 @@ int vm_reserve(gk_vmap *m, u64 extra) {
     plan_segments(m->W, std::max<u64>((u64)((double)(m->size + extra) / target) + 1, m->capacity + m->capacity / 2), &nnb2, &nlnb1, &ncap);
     void *nslots = nullptr;
     if (int rc = vm_alloc_table(ctx, m->W, ncap, &nslots)) { (void)pool_free(ctx, nslots); return rc; }
-    if (m->W == 1)
-        hipLaunchKernelGGL(k_vm_rehash<1>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<1> *)m->slots, m->capacity,
-                           Table<1>{(Slot<1> *)nslots, nnb2, nlnb1, 0u}, m->d_ctr);
-    else
-        hipLaunchKernelGGL(k_vm_rehash<2>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<2> *)m->slots, m->capacity,
-                           Table<2>{(Slot<2> *)nslots, nnb2, nlnb1, m->k == 64 ? 1u : 0u}, m->d_ctr);
+    GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_rehash<W>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<W> *)m->slots, m->capacity,
+                                     Table<W>{(Slot<W> *)nslots, nnb2, nlnb1, m->k == 64 ? 1u : 0u}, m->d_ctr));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { (void)pool_free(ctx, nslots); return hip_fail(ctx, e, "value map rehash"); }
     if (int rc = vm_sync(m)) { (void)pool_free(ctx, nslots); return rc; }          // a failed rehash leaves the old table in place
@@ -255,8 +249,7 @@ int vmap_put_new_dev(gk_vmap *m, const uint64_t *d_lo, const uint64_t *d_hi, con
     if (int rc = vm_reserve(m, n)) return rc;
     gk_ctx *ctx = m->ctx;
     if (n) {
-        if (m->W == 1) hipLaunchKernelGGL(k_vm_put_new<1>, dim3(vgrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, vtable<1>(m), d_lo, d_hi, d_val, n, m->d_ctr);
-        else hipLaunchKernelGGL(k_vm_put_new<2>, dim3(vgrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, vtable<2>(m), d_lo, d_hi, d_val, n, m->d_ctr);
+        GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_put_new<W>, dim3(vgrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, d_val, n, m->d_ctr));
         GK_HIP(ctx, hipGetLastError());
     }
     return vm_sync(m);
@@ -271,8 +264,7 @@ int vmap_get_all_dev(gk_vmap *m, const uint64_t *d_lo, const uint64_t *d_hi, uin
     gk_ctx *ctx = m->ctx;
     if (n == 0) return GK_OK;
     const int grid = vgrid(ctx, n);
-    if (m->W == 1) hipLaunchKernelGGL(k_vm_get_all<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<1>(m), d_lo, d_hi, n, 0xffffffffu, d_off, d_cnt, d_out);
-    else hipLaunchKernelGGL(k_vm_get_all<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<2>(m), d_lo, d_hi, n, 0xffffffffu, d_off, d_cnt, d_out);
+    GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_get_all<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, n, 0xffffffffu, d_off, d_cnt, d_out));
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
 }
@@ -364,13 +356,9 @@ int gk_vmap_update_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, con
     if (e == hipSuccess) e = hipMemcpyAsync(d_val, values, n * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_update_batch");
     const int grid = vgrid(ctx, n);
-    if (m->W == 1) {
-        hipLaunchKernelGGL(k_vm_find_or_claim<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<1>(m), d_lo, d_hi, n, d_slot, d_win, m->d_ctr);
-        hipLaunchKernelGGL(k_vm_store_last<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<1>(m), d_val, n, d_slot, d_win);
-    } else {
-        hipLaunchKernelGGL(k_vm_find_or_claim<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<2>(m), d_lo, d_hi, n, d_slot, d_win, m->d_ctr);
-        hipLaunchKernelGGL(k_vm_store_last<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<2>(m), d_val, n, d_slot, d_win);
-    }
+    GK_BY_W(m->W,
+        hipLaunchKernelGGL(k_vm_find_or_claim<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, n, d_slot, d_win, m->d_ctr);
+        hipLaunchKernelGGL(k_vm_store_last<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_val, n, d_slot, d_win));
     GK_HIP(ctx, hipGetLastError());
     return vm_sync(m);
 }
@@ -397,12 +385,9 @@ int gk_vmap_get_all_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, ui
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_get_all_batch");
     const int grid = vgrid(ctx, n);
     const u32 nolimit = 0xffffffffu;
-    if (m->W == 1) hipLaunchKernelGGL(k_vm_get_all<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<1>(m), d_lo, d_hi, n, nolimit, nullptr, d_cnt, nullptr);
-    else hipLaunchKernelGGL(k_vm_get_all<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<2>(m), d_lo, d_hi, n, nolimit, nullptr, d_cnt, nullptr);
-    GK_HIP(ctx, hipGetLastError());
+    GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_get_all<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, n, nolimit, nullptr, d_cnt, nullptr));
     std::vector<u32> cnt(n);
-    GK_HIP(ctx, hipMemcpyAsync(cnt.data(), d_cnt, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, cnt.data(), d_cnt, n));
     for (uint64_t i = 0; i < n; i++) offsets_out[i + 1] = offsets_out[i] + cnt[i];
     const uint64_t tot = offsets_out[n];
     if (total) *total = tot;
@@ -412,11 +397,8 @@ int gk_vmap_get_all_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, ui
     e = b.get(&d_out, tot);
     if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets_out, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_get_all_batch");
-    if (m->W == 1) hipLaunchKernelGGL(k_vm_get_all<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<1>(m), d_lo, d_hi, n, nolimit, d_off, d_cnt, d_out);
-    else hipLaunchKernelGGL(k_vm_get_all<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<2>(m), d_lo, d_hi, n, nolimit, d_off, d_cnt, d_out);
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipMemcpyAsync(values_out, d_out, tot * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_get_all<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, n, nolimit, d_off, d_cnt, d_out));
+    GK_HIP(ctx, read_back(ctx, values_out, d_out, tot));
     return GK_OK;
 }
 
@@ -444,15 +426,10 @@ int gk_vmap_get_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, uint64
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_get_batch");
     const int grid = vgrid(ctx, n);
     // apply (ArrayDNAMap.scala:90-101) = the first slot of the probe sequence that holds the key: getAll cut off at one
-    for (int pass = 0; pass < 2; pass++) {
-        if (m->W == 1) hipLaunchKernelGGL(k_vm_get_all<1>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<1>(m), d_lo, d_hi, n, 1u, d_off, d_cnt, pass ? d_out : nullptr);
-        else hipLaunchKernelGGL(k_vm_get_all<2>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<2>(m), d_lo, d_hi, n, 1u, d_off, d_cnt, pass ? d_out : nullptr);
-    }
-    GK_HIP(ctx, hipGetLastError());
+    for (int pass = 0; pass < 2; pass++)
+        GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_get_all<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, n, 1u, d_off, d_cnt, pass ? d_out : nullptr));
     std::vector<u32> cnt(n);
-    GK_HIP(ctx, hipMemcpyAsync(cnt.data(), d_cnt, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipMemcpyAsync(values_out, d_out, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_HIP(ctx, read_back(ctx, {{cnt.data(), d_cnt, n * 4}, {values_out, d_out, n * 8}}));
     if (found_out) for (uint64_t i = 0; i < n; i++) found_out[i] = cnt[i] ? 1 : 0;
     return GK_OK;
 }
@@ -474,13 +451,8 @@ int gk_vmap_export(gk_vmap *m, uint64_t *lo, uint64_t *hi, uint64_t *values, uin
     if (e == hipSuccess) e = b.get(&d_cur, 1);
     if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 8, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_export");
-    if (m->W == 1) hipLaunchKernelGGL(k_vm_export<1>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<1> *)m->slots, m->capacity, 0u, d_lo, d_hi, d_val, d_cur);
-    else hipLaunchKernelGGL(k_vm_export<2>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<2> *)m->slots, m->capacity, m->k == 64 ? 1u : 0u, d_lo, d_hi, d_val, d_cur);
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipMemcpyAsync(lo, d_lo, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (hi) GK_HIP(ctx, hipMemcpyAsync(hi, d_hi, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipMemcpyAsync(values, d_val, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_export<W>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<W> *)m->slots, m->capacity, m->k == 64 ? 1u : 0u, d_lo, d_hi, d_val, d_cur));
+    GK_HIP(ctx, read_back(ctx, {{lo, d_lo, cnt * 8}, {hi, d_hi, cnt * 8}, {values, d_val, cnt * 8}}));
     return GK_OK;
 }
 
