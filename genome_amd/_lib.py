@@ -59,6 +59,9 @@ SIGNATURES = {
     "gk_ctx_set_mem_budget": (C.c_int, [vp, C.c_uint64]),
     "gk_map_add_map": (C.c_int, [vp, vp]),
     "gk_map_verify": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+    "gk_map_spectrum": (C.c_int, [vp, u64p, C.c_uint32, u64p, u64p, u32p]),
+    "gk_spectrum_cutoff": (C.c_int, [u64p, C.c_uint32, C.c_uint32, u32p, u32p, u64p]),
+    "gk_dist_spectrum": (C.c_int, [vp, vp, u64p, C.c_uint32, u64p, u64p, u32p]),
     "gk_map_set_max_batch_keys": (C.c_int, [vp, C.c_uint64]),
     "gk_map_trim": (C.c_int, [vp]),
     "gk_host_alloc": (C.c_int, [vp, C.c_size_t, C.POINTER(vp)]),

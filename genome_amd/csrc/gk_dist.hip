@@ -304,6 +304,49 @@ int gk_dist_size(gk_dist *d, gk_map *local, uint64_t *total) {
     return GK_OK;
 }
 
+// The spectrum of the whole map on every rank.  The status round comes FIRST, on the handle's own words (they exist whatever
+// fails here): a rank that could not take its spectrum, or has no room for the histogram, says so beside its largest count, and
+// the histogram is only reduced once every rank is known to hold one.  The results are read without a launch check in between
+// (a check could fail one rank in a round the others passed).
+int gk_dist_spectrum(gk_dist *d, gk_map *local, uint64_t *hist, uint32_t bins, uint64_t *distinct, uint64_t *occurrences, uint32_t *max_count) {
+    if (int rc = dist_check(d)) return rc;
+    gk_ctx *ctx = d->ctx;
+    const char *who = "gk_dist_spectrum: ";
+    if (!hist) return fail(ctx, GK_E_INVALID, std::string(who) + "hist is NULL");
+    if (bins < 2 || bins > (1u << 20)) return fail(ctx, GK_E_INVALID, std::string(who) + "bins must be 2 .. 1<<20");
+    if (int rc = dist_quiesce(d)) return rc;
+    int my_rc = GK_OK;
+    std::string my_err;
+    auto local_rc = [&](int rc) { if (rc != GK_OK && my_rc == GK_OK) { my_rc = rc; my_err = ctx->err; } };
+    std::vector<unsigned long long> h((size_t)bins + 2, 0ull);       // hist, distinct, occurrences
+    uint32_t mx = 0;
+    if (!local) local_rc(fail(ctx, GK_E_INVALID, std::string(who) + "null map"));
+    else if (local->ctx != ctx) local_rc(fail(ctx, GK_E_INVALID, std::string(who) + "the map must live on the handle's context"));
+    else {
+        static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "one histogram type");
+        local_rc(gk_map_spectrum(local, reinterpret_cast<uint64_t *>(h.data()), bins, reinterpret_cast<uint64_t *>(&h[bins]),
+                                 reinterpret_cast<uint64_t *>(&h[(size_t)bins + 1]), &mx));
+    }
+    DevScratch buf(ctx);
+    unsigned long long *d_h = nullptr;
+    if (buf.get(&d_h, h.size()) != hipSuccess) local_rc(fail(ctx, GK_E_HIP, std::string(who) + "no room for the histogram"));
+    unsigned long long w[2] = {mx, my_rc ? 1ull : 0ull};
+    GK_HIP(ctx, hipMemcpyAsync(d->d_cnt, w, 16, hipMemcpyHostToDevice, ctx->stream));
+    GK_NCCL(ctx, xAllReduce(d, d->d_cnt, d->d_cnt + 2, 2, XP_UINT64, XP_MAX, ctx->stream));
+    GK_HIP(ctx, hipMemcpyAsync(w, d->d_cnt + 2, 16, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (w[1]) return my_rc ? fail(ctx, my_rc, my_err) : fail(ctx, GK_E_COMM, std::string(who) + "a rank could not take the spectrum of its partition; every rank gave up");
+    GK_HIP(ctx, hipMemcpyAsync(d_h, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    GK_NCCL(ctx, xAllReduce(d, d_h, d_h, h.size(), XP_UINT64, XP_SUM, ctx->stream));
+    GK_HIP(ctx, hipMemcpyAsync(h.data(), d_h, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t b = 0; b < bins; b++) hist[b] = h[b];
+    if (distinct) *distinct = h[bins];
+    if (occurrences) *occurrences = h[(size_t)bins + 1];
+    if (max_count) *max_count = (uint32_t)w[0];
+    return GK_OK;
+}
+
 static int dist_grow(gk_ctx *ctx, uint8_t **buf, u64 *have, u64 want_records, int slot) {
     if (*have >= want_records && *buf) return GK_OK;
     if (*buf) { GK_HIP(ctx, hipStreamSynchronize(ctx->stream)); GK_HIP(ctx, pool_free(ctx, *buf)); }

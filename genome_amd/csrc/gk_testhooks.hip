@@ -112,8 +112,9 @@ struct LoopHub {
     // reductions / gathers: one at a time, every rank contributes
     unsigned long long gen = 0;
     int arrived = 0;
-    double contrib[64][32];
-    double result[64 * 32];
+    std::vector<double> contrib[64];                      // (any length: a spectrum reduces a histogram)
+    std::vector<double> result;
+    bool result_ok = true;                                // false: the ranks disagreed about the length (RCCL would hang): every rank gets an error
     std::vector<hipEvent_t> events;                       // every event the transport made; destroyed with the hub
     ~LoopHub() { for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e); }
 };
@@ -197,17 +198,20 @@ int loop_group_end(gk_dist *d) {
 }
 static int loop_collective(gk_dist *d, const void *in, void *out, size_t n, int dt, int op, bool gather, hipStream_t st) {
     LoopHub &h = *static_cast<LoopState *>(d->xstate.get())->hub;
-    if (n > 32 || (gather && n != 1)) return 3;
-    double mine[32];
-    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(mine, in, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return 3;
-    double res[64 * 32];
+    if (n < 1 || (gather && n != 1)) return 3;
+    std::vector<double> mine(n);
+    if (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(mine.data(), in, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return 3;
     size_t nres = gather ? (size_t)h.world : n;
+    std::vector<double> res(nres);
     {
         std::unique_lock<std::mutex> lk(h.mu);
         const unsigned long long gen = h.gen;
-        memcpy(h.contrib[d->rank], mine, n * 8);
+        h.contrib[d->rank] = mine;
         if (++h.arrived == h.world) {
-            for (size_t i = 0; i < nres; i++) {
+            h.result.assign(nres, 0.0);
+            h.result_ok = true;
+            for (int r = 0; r < h.world; r++) h.result_ok = h.result_ok && h.contrib[r].size() == n;
+            for (size_t i = 0; i < nres && h.result_ok; i++) {
                 if (gather) { memcpy(&h.result[i], &h.contrib[i][0], 8); continue; }
                 if (dt == XP_FLOAT64) {
                     double acc = h.contrib[0][i];
@@ -225,13 +229,14 @@ static int loop_collective(gk_dist *d, const void *in, void *out, size_t n, int 
         } else {
             h.cv.wait(lk, [&]() { return h.gen != gen; });
         }
-        memcpy(res, h.result, nres * 8);
+        if (!h.result_ok || h.result.size() != nres) return 3;
+        memcpy(res.data(), h.result.data(), nres * 8);
     }
-    return hipMemcpyAsync(out, res, nres * 8, hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? XP_SUCCESS : 3;
+    return hipMemcpyAsync(out, res.data(), nres * 8, hipMemcpyHostToDevice, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess ? XP_SUCCESS : 3;
 }
 int loop_all_reduce(gk_dist *d, const void *in, void *out, size_t n, int dt, int op, hipStream_t st) { return loop_collective(d, in, out, n, dt, op, false, st); }
 int loop_all_gather(gk_dist *d, const void *in, void *out, size_t n, int dt, hipStream_t st) { return loop_collective(d, in, out, n, dt, XP_SUM, true, st); }
-std::string loop_error_text(int) { return "transport error (loopback: a send and its receive differ in size, or a HIP call failed)"; }
+std::string loop_error_text(int) { return "transport error (loopback: a send and its receive differ in size, the ranks of a reduction differ in length, or a HIP call failed)"; }
 void loop_close(gk_dist *d) { d->xstate.reset(); }
 const Transport LOOP_TRANSPORT = {loop_group_start, loop_send, loop_recv, loop_group_end, loop_all_reduce, loop_all_gather, loop_error_text, loop_close};
 }  // namespace

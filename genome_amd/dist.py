@@ -130,6 +130,15 @@ class DistDNAMap:
         L.check(L.lib().gk_dist_size(self.dist.h, self.local.h, C.byref(n)), self.ctx.h)
         return n.value
 
+    def spectrum(self, bins: int = 4096) -> dict:
+        """The count spectrum of the WHOLE map on every rank (gk_dist_spectrum; HipDNAMap.spectrum's keys).  COLLECTIVE: a rank
+        whose local pass fails still takes part, and every rank raises."""
+        hist = np.zeros(bins, np.uint64)
+        n, occ, mx = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        L.check(L.lib().gk_dist_spectrum(self.dist.h, self.local.h if self.local is not None else None, L.ptr(hist, C.c_uint64), bins,
+                                         C.byref(n), C.byref(occ), C.byref(mx)), self.ctx.h)
+        return {"hist": hist, "distinct": n.value, "occurrences": occ.value, "max_count": mx.value}
+
     def deleteAll_lt(self, rounds: int):                      # :49-51 — local on every rank
         self.local.deleteAll_lt(rounds)
 

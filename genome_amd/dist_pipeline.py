@@ -22,7 +22,7 @@ import numpy as np
 
 from . import dna
 from .dist import DistDNAMap, HipDist
-from .freqfilter import PairedEndData
+from .freqfilter import PairedEndData, auto_rounds
 from .graph import HipGraph, Support, buildGraph, loadGraph
 
 
@@ -62,15 +62,21 @@ def _rank_share(hd: HipDist, data: PairedEndData, take_first: int | None):
     return a, b, np.frombuffer(data.bin, np.uint8)[int(off[a]):int(off[b])]
 
 
-def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds: int = 3, take_first: int | None = None, retain: bool = True,
+def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds=3, take_first: int | None = None, retain: bool = True,
                 simplify: bool = False, walk_pairs=None, classified: bool = True) -> tuple[HipGraph, dict]:
     """One rank's part of the N-rank GraphBuilder (+ GraphSimplifier pairs stage) -> (this rank's graph replica, stats).
     `stats` holds graph_builder's JSON keys (the walk_pairs object only with walk_pairs) plus occurrences_sent,
-    occurrences_owned (this rank's windows) and world.  The caller closes the graph."""
+    occurrences_owned (this rank's windows) and world.  rounds = "auto": the cutoff is the valley of the REDUCED count spectrum
+    (gk_dist_spectrum: every rank filters alike), 3 when it has none; `stats` then also holds rounds_auto, valley, peak and
+    genome_size_estimate, and "rounds" is the number used.  The caller closes the graph."""
+    auto = None
     a, b, share = _rank_share(hd, data, take_first)
     pm = DistDNAMap(hd, k)
     try:
         sent, owned = pm.count_reads(share, 2 * (b - a))                   # FreqFilter.scala:44-48
+        if rounds == "auto":
+            auto = auto_rounds(pm)
+            rounds = auto["rounds"]
         pm.deleteAll_lt(rounds)                                             # :55
         good = pm.size()                                                    # GraphBuilder.scala:34
         full = pm.gathered(classified=classified)
@@ -100,6 +106,8 @@ def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds: int = 3, take_
              "components": comps, "max_component_size": kept, "retained_nodes": n2, "retained_edges": e2, "retained_edges_length": l2}
     if walk is not None:
         stats["walk_pairs"] = walk
+    if auto is not None:
+        stats.update({key: auto[key] for key in ("rounds_auto", "valley", "peak", "genome_size_estimate")})
     stats["components_histogram"] = [list(x) for x in hist]
     stats["components_histogram_2"] = [list(x) for x in hist2]
     stats.update({"occurrences_sent": sent, "occurrences_owned": owned, "world": hd.world})

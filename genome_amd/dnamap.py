@@ -290,6 +290,14 @@ class HipDNAMap:
         L.check(L.lib().gk_map_verify(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), self.ctx.h)
         return a.value, b.value, c.value, d.value
 
+    def spectrum(self, bins: int = 4096) -> dict:
+        """The count spectrum, taken on the device (gk_map_spectrum): "hist" (uint64[bins]: hist[c] = keys seen exactly c times,
+        the last bin = keys seen bins-1 times and more), "distinct", "occurrences", "max_count".  The table is not changed."""
+        hist = np.zeros(bins, np.uint64)
+        n, occ, mx = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        L.check(L.lib().gk_map_spectrum(self.h, L.ptr(hist, C.c_uint64), bins, C.byref(n), C.byref(occ), C.byref(mx)), self.ctx.h)
+        return {"hist": hist, "distinct": n.value, "occurrences": occ.value, "max_count": mx.value}
+
     def trim(self):
         """Release the scratch kept between calls (gk_map_trim)."""
         L.check(L.lib().gk_map_trim(self.h), self.ctx.h)

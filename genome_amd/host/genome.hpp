@@ -181,6 +181,21 @@ inline std::pair<size_t, size_t> pairBytes(const PairedEndData &data, uint64_t f
 struct PlusOne {};                 // `_ + 1`            FreqFilter.scala:33
 struct ValueLessThan { int rounds; };   // `(k, v) => v < rounds`   FreqFilter.scala:55
 
+// A k-mer count spectrum (gk_map_spectrum / gk_dist_spectrum) and the deleteAll cutoff it suggests (gk_spectrum_cutoff: pure host
+// code).  valley == 0: the spectrum has no valley — callers fall back to the reference's rounds = 3 (GraphBuilder.scala:30).
+struct Spectrum {
+    std::vector<uint64_t> hist;
+    uint64_t distinct = 0, occurrences = 0;
+    uint32_t maxCount = 0;
+};
+struct SpectrumCutoff { uint32_t valley = 0, peak = 0; uint64_t genomeSize = 0; };
+// minCount: 1 normally; 2 for a table counted through the singleton pre-filter, whose bin 1 is incomplete by construction
+inline SpectrumCutoff spectrumCutoff(const std::vector<uint64_t> &hist, uint32_t minCount = 1) {
+    SpectrumCutoff c;
+    check(gk_spectrum_cutoff(hist.data(), (uint32_t)hist.size(), minCount, &c.valley, &c.peak, &c.genomeSize), nullptr);
+    return c;
+}
+
 // trait DNAMap[Int] over one HBM-resident partition (ArrayDNAMap.scala:49-60, 62-243)
 class DNAMap {
   public:
@@ -234,6 +249,14 @@ class DNAMap {
         uint64_t occ = 0;
         check(gk_map_count_reads(h_, bin, nbytes, nreads, &occ), ctx_.handle());
         return occ;
+    }
+    // the count spectrum, taken on the device (gk_map_spectrum): hist[c] = keys seen exactly c times, the last bin = keys seen
+    // bins - 1 times and more; the table is not changed
+    Spectrum spectrum(uint32_t bins = 4096) const {
+        Spectrum s;
+        s.hist.assign(bins, 0);
+        check(gk_map_spectrum(h_, s.hist.data(), bins, &s.distinct, &s.occurrences, &s.maxCount), ctx_.handle());
+        return s;
     }
     // the table's invariants and an order-independent content checksum (gk_map_verify)
     struct Verify { uint64_t live, bad, sumCounts, checksum; };
@@ -307,6 +330,13 @@ class PartitionedDNAMap {
         check(gk_dist_size(d_, local_.handle(), &n), ctx_.handle());
         return n;
     }
+    // the count spectrum of the WHOLE map on every rank (gk_dist_spectrum): collective
+    Spectrum spectrum(uint32_t bins = 4096) {
+        Spectrum s;
+        s.hist.assign(bins, 0);
+        check(gk_dist_spectrum(d_, local_.handle(), s.hist.data(), bins, &s.distinct, &s.occurrences, &s.maxCount), ctx_.handle());
+        return s;
+    }
     void deleteAll(ValueLessThan p) { local_.deleteAll(p); }      // :49-51 — every partition filters its own keys
     // every partition's keys in one table on this rank: what Graph.buildGraph needs.  classified: the keys' owners
     // classify them first (Graph.scala:320-329 on every partition, :55-58) and the degree masks travel with the keys
@@ -326,16 +356,38 @@ class PartitionedDNAMap {
 };
 
 namespace FreqFilter {
+// Asking extractFilteredKmers for more than a number: autoRounds = take the cutoff from the count spectrum of the counted table
+// (its valley; 3 when there is none) instead of `rounds`; wantSpectrum = take the spectrum although `rounds` is used.  Filled
+// in on return: the spectrum before deleteAll, the cutoff it suggests, the rounds used, and autoFound (asked for auto and the
+// spectrum had a valley).  Without a Chosen, or with both flags false, nothing changes and no spectrum is taken.
+struct Chosen {
+    bool autoRounds = false, wantSpectrum = false;
+    Spectrum spectrum;
+    SpectrumCutoff cutoff;
+    bool autoFound = false;
+    int rounds = 0;
+};
+template <class Map> inline int chooseRounds(Map &kmersFreq, int rounds, uint32_t minCount, Chosen *chosen) {
+    if (!chosen || !(chosen->autoRounds || chosen->wantSpectrum)) return rounds;
+    chosen->spectrum = kmersFreq.spectrum();
+    chosen->cutoff = spectrumCutoff(chosen->spectrum.hist, minCount);
+    chosen->autoFound = chosen->autoRounds && chosen->cutoff.valley != 0;
+    if (chosen->autoRounds) rounds = chosen->autoFound ? (int)chosen->cutoff.valley : 3;
+    chosen->rounds = rounds;
+    return rounds;
+}
 // FreqFilter.extractFilteredKmers(data, k, rounds) (FreqFilter.scala:25-58); `takeFirst` is
 // genome.takeFirst (:40, :44)
 // prefilterDistinct > 0 (rounds >= 2 only): the exact two-pass singleton pre-filter sized for that many
 // distinct k-mers runs first (include/genome_amd.h); same result, k-mers seen once take no table slot
+// chosen->autoRounds: the cutoff is the valley of the table's count spectrum (chooseRounds; min_count = 2 behind the pre-filter)
 inline DNAMap extractFilteredKmers(Context &ctx, const PairedEndData &data, int k, int rounds,
-                                   uint64_t takeFirst = UINT64_MAX, uint64_t capacityHint = 0, uint64_t prefilterDistinct = 0) {
+                                   uint64_t takeFirst = UINT64_MAX, uint64_t capacityHint = 0, uint64_t prefilterDistinct = 0,
+                                   Chosen *chosen = nullptr) {
     DNAMap kmersFreq(ctx, k, capacityHint);
     const uint64_t pairs = std::min<uint64_t>(data.count, takeFirst);
     if (prefilterDistinct) {
-        if (rounds < 2) throw GkError(GK_E_INVALID, "the singleton pre-filter needs rounds >= 2");
+        if (rounds < 2 && !(chosen && chosen->autoRounds)) throw GkError(GK_E_INVALID, "the singleton pre-filter needs rounds >= 2");
         gk_prefilter *pf = nullptr;
         check(gk_prefilter_create(ctx.handle(), k, prefilterDistinct, &pf), ctx.handle());
         int rc = gk_prefilter_add_reads(pf, data.bin.data(), data.bin.size(), 2 * pairs);
@@ -345,15 +397,19 @@ inline DNAMap extractFilteredKmers(Context &ctx, const PairedEndData &data, int 
     } else {
         kmersFreq.countReads(data.bin.data(), data.bin.size(), 2 * pairs);
     }
+    rounds = chooseRounds(kmersFreq, rounds, prefilterDistinct ? 2 : 1, chosen);
+    if (prefilterDistinct && rounds < 2) rounds = 2;       // (auto only: a number below 2 was refused above)
     kmersFreq.deleteAll(ValueLessThan{rounds});
     return kmersFreq;
 }
 // the same over N ranks: this rank counts its share of the first min(takeFirst, count) pairs (pairShare) into its partition and
 // filters it; every partition then holds its owned k-mers seen at least `rounds` times -> (windows sent, windows counted as owner)
+// (chosen->autoRounds: the valley of the REDUCED spectrum, so that every rank filters alike)
 inline std::pair<uint64_t, uint64_t> extractFilteredKmers(PartitionedDNAMap &kmersFreq, const PairedEndData &data, int rounds,
-                                                          uint64_t takeFirst = UINT64_MAX) {
+                                                          uint64_t takeFirst = UINT64_MAX, Chosen *chosen = nullptr) {
     const auto [a, b] = pairShare(data.count, takeFirst, kmersFreq.rank(), kmersFreq.world());
     const auto occ = kmersFreq.countReads(data, a, b);
+    rounds = chooseRounds(kmersFreq, rounds, 1, chosen);
     kmersFreq.deleteAll(ValueLessThan{rounds});
     return occ;
 }

@@ -3,11 +3,16 @@
 // builds the de Bruijn graph, keeps the largest component, and writes the graph as text.
 // The reference logs its counters through akka Logging (:34-53); here they are one JSON object.
 //
-//   graph_builder <reads.bin> <pairs> <k> [--rounds 3] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
+//   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
 //                 [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
 //   --fastq converts the FASTQ file on the GPU first (Convert2bin, gk_fastq; --split N = its n, default 36) and takes the pair
 //   count from the conversion; the flow is then the same.  Not with --world (exit 2): convert2bin the file first.
+//   --rounds auto takes the k-mer count spectrum of the counted table on the GPU (gk_map_spectrum; over --world the spectrum reduced
+//   over the ranks, so that every rank filters alike) and uses its valley as the cutoff (gk_spectrum_cutoff; behind --prefilter
+//   with min_count = 2); a spectrum without a valley falls back to the reference's 3 and the JSON says "rounds_auto":false.
+//   --spectrum PATH writes that spectrum as one `count<TAB>keys` line per non-empty bin, the overflow bin as `>=N` (rank 0).
+//   With either flag the JSON gains "rounds_auto", "valley", "peak" and "genome_size_estimate"; "rounds" is the number used.
 //   --simplify runs removeBubbles + simplifyGraph (GraphSimplifier.scala:317-318) before writing;
 //   --walk-pairs runs GraphSimplifier.startup's paired-end stage on the graph GraphBuilder hands over (:188-318): position
 //   map, the pairs' walks with range LO to HI (the reference: 180 to 250, :146), node split at genome.cutoff = CUTOFF,
@@ -71,7 +76,7 @@ int main(int argc, char **argv) {
         argv = fargs.data();
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
+        std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
                              "[--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
@@ -80,14 +85,19 @@ int main(int argc, char **argv) {
     data.count = std::stoull(argv[2]);
     const int k = std::stoi(argv[3]);
     int rounds = 3;                               // GraphBuilder.scala:30
+    bool autoRounds = false;                      // --rounds auto
     uint64_t takeFirst = UINT64_MAX;              // genome.takeFirst
     uint64_t prefilter = 0;                       // expected distinct k-mers; 0 = no singleton pre-filter
     bool retain = true, simplify = false;
     int walkCutoff = -1, walkLo = 180, walkHi = 250;
-    std::string out, idFile, saveGraph;
+    std::string out, idFile, saveGraph, spectrumPath;
     int world = 0, rank = 0;                      // world 0: one GPU, no communicator
     for (int i = 4; i < argc; i++) {
-        if (!std::strcmp(argv[i], "--rounds") && i + 1 < argc) rounds = std::stoi(argv[++i]);
+        if (!std::strcmp(argv[i], "--rounds") && i + 1 < argc) {
+            if (!std::strcmp(argv[++i], "auto")) autoRounds = true;   // chosen from the spectrum
+            else { autoRounds = false; rounds = std::stoi(argv[i]); }
+        }
+        else if (!std::strcmp(argv[i], "--spectrum") && i + 1 < argc) spectrumPath = argv[++i];
         else if (!std::strcmp(argv[i], "--take-first") && i + 1 < argc) takeFirst = std::stoull(argv[++i]);
         else if (!std::strcmp(argv[i], "--prefilter") && i + 1 < argc) prefilter = std::stoull(argv[++i]);
         else if (!std::strcmp(argv[i], "--no-retain")) retain = false;
@@ -125,14 +135,26 @@ int main(int argc, char **argv) {
         std::unique_ptr<genome::PartitionedDNAMap> pm;
         uint64_t sent = 0, owned = 0, good = 0;
         std::unique_ptr<genome::DNAMap> kmersFreq;
+        genome::FreqFilter::Chosen chosen;
+        chosen.autoRounds = autoRounds;
+        chosen.wantSpectrum = !spectrumPath.empty();
+        const bool withSpectrum = chosen.autoRounds || chosen.wantSpectrum;
         if (world) {
             pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, idFile));
-            std::tie(sent, owned) = genome::FreqFilter::extractFilteredKmers(*pm, data, rounds, takeFirst);           // :32 over N ranks
+            std::tie(sent, owned) = genome::FreqFilter::extractFilteredKmers(*pm, data, rounds, takeFirst, &chosen);  // :32 over N ranks
             good = pm->size();                                                                                          // :34
             kmersFreq = std::make_unique<genome::DNAMap>(pm->gathered(true));
         } else {
-            kmersFreq = std::make_unique<genome::DNAMap>(genome::FreqFilter::extractFilteredKmers(ctx, data, k, rounds, takeFirst, 0, prefilter));   // :32
+            kmersFreq = std::make_unique<genome::DNAMap>(genome::FreqFilter::extractFilteredKmers(ctx, data, k, rounds, takeFirst, 0, prefilter, &chosen));   // :32
             good = kmersFreq->size();                                                                                  // :34
+        }
+        if (withSpectrum) rounds = chosen.rounds;
+        if (rank == 0 && !spectrumPath.empty()) {
+            std::ofstream sf(spectrumPath);
+            const auto &h = chosen.spectrum.hist;
+            for (size_t c = 1; c + 1 < h.size(); c++) if (h[c]) sf << c << "\t" << h[c] << "\n";
+            if (h.back()) sf << ">=" << h.size() - 1 << "\t" << h.back() << "\n";
+            if (!sf) throw std::runtime_error("cannot write " + spectrumPath);
         }
         auto graph = genome::Graph::buildGraph(k, *kmersFreq);                                           // :36
         auto [nodes, edges, totalLen] = graph.counts();                                                  // :39
@@ -166,6 +188,9 @@ int main(int argc, char **argv) {
                     k, rounds, (unsigned long long)good, (unsigned long long)nodes, (unsigned long long)edges,
                     (unsigned long long)totalLen, (unsigned long long)comps, (unsigned long long)kept,
                     (unsigned long long)n2, (unsigned long long)e2, (unsigned long long)l2);
+        if (withSpectrum)
+            std::printf("\"rounds_auto\":%s,\"valley\":%u,\"peak\":%u,\"genome_size_estimate\":%llu,", chosen.autoFound ? "true" : "false",
+                        chosen.cutoff.valley, chosen.cutoff.peak, (unsigned long long)chosen.cutoff.genomeSize);
         if (walkCutoff >= 0)
             std::printf("\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},",
                         (unsigned long long)supPairs, (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges,

@@ -162,6 +162,14 @@ class PartitionedDNAMap:
         tot[3] &= (1 << 64) - 1
         return tuple(tot)
 
+    def spectrum(self, bins: int = 4096) -> dict:
+        """The count spectrum of the whole map (HipDNAMap.spectrum): the partitions are disjoint by owner, so their histograms,
+        key counts and occurrences add up and the largest count is the largest of theirs."""
+        parts = [p.spectrum(bins) for p in self.parts]
+        return {"hist": np.sum([s["hist"] for s in parts], axis=0, dtype=np.uint64),
+                "distinct": sum(s["distinct"] for s in parts), "occurrences": sum(s["occurrences"] for s in parts),
+                "max_count": max(s["max_count"] for s in parts)}
+
     def count_reads_dev_keys(self, d_records: int, nreads: int, read_len: int) -> int:
         """extract + canonicalise + bucket 8/16-B keys by owner on the device, then owner-side inserts."""
         nk = max(0, read_len - self.k + 1)

@@ -121,6 +121,26 @@ int gk_map_slots(gk_map *m, uint64_t *slots);              /* current table capa
  * agree — whatever their sizes, slot orders and insert histories (partitions of one table ADD UP: the checksum of a
  * PartitionedDNAMap is the sum of its partitions' checksums mod 2^64).  Any may be NULL. */
 int gk_map_verify(gk_map *m, uint64_t *live, uint64_t *bad_slots, uint64_t *sum_counts, uint64_t *checksum);
+/* The count spectrum of the table: how many distinct k-mers occur exactly c times (what any k-mer counter reports: the coverage
+ * peak, the error valley, a genome-size estimate).  One streaming pass over the slots on the device; nothing but the histogram
+ * crosses to the host.  No reference counterpart: GraphBuilder.scala:30 hardcodes the cutoff this exists to choose.
+ *   hist[0] = 0;  hist[c] = live keys with count exactly c, 1 <= c <= bins-2;  hist[bins-1] = live keys with count >= bins-1 (the
+ *   overflow bin).  `hist` holds `bins` entries, 2 <= bins <= 1<<20 (GK_E_INVALID otherwise, and for a NULL hist).
+ *   *distinct (== gk_map_size), *occurrences (== gk_map_verify's sum_counts) and *max_count (the largest count; 0 for an empty
+ *   map) are exact whatever `bins` is; any of the three may be NULL.
+ * The table is not changed.  A new or cleared map gives all zeros without its slots being read. */
+int gk_map_spectrum(gk_map *m, uint64_t *hist, uint32_t bins, uint64_t *distinct, uint64_t *occurrences, uint32_t *max_count);
+/* The deleteAll cutoff a spectrum suggests.  Pure host code: no context, runs without a GPU.  Only c in [min_count, bins-2] is
+ * looked at, never the overflow bin:
+ *   1. r = the smallest c in the range with hist[c] < hist[c+1] (c+1 <= bins-2).  None: GK_OK with *valley = *peak = 0 and
+ *      *genome_size = 0 — "no valley" (callers then fall back to the reference's 3 and say so).
+ *   2. *peak = the c > r with the largest hist[c]; on a tie the smallest c.
+ *   3. *valley = the c in [min_count, *peak] with the smallest hist[c]; on a tie the smallest c.
+ *   4. *genome_size = floor(sum over c = *valley .. bins-2 of c * hist[c] / *peak).
+ * Use rounds = *valley: gk_map_filter_lt(*valley) keeps the counts >= *valley.  min_count is 1 normally, and 2 for a table counted
+ * through the singleton pre-filter (gk_map_count_reads_prefiltered), whose bin 1 is incomplete by construction; 0 is
+ * GK_E_INVALID, as are a NULL hist and bins outside 2 .. 1<<20.  Any out-pointer may be NULL. */
+int gk_spectrum_cutoff(const uint64_t *hist, uint32_t bins, uint32_t min_count, uint32_t *valley, uint32_t *peak, uint64_t *genome_size);
 /* Upper bound on the k-mer windows one partitioned insert batch holds when a call brings more windows than the
  * table has room for (the batch's key scratch is ~17 x W bytes per window); 0 = default (64 GiB of keys per buffer or as much scratch as the table itself holds, half of the free HBM at most). */
 int gk_map_set_max_batch_keys(gk_map *m, uint64_t keys);
@@ -307,6 +327,14 @@ int gk_dist_count_routed(gk_dist *d, gk_map *local, uint64_t *occurrences_sent, 
 /* wall ms of the last gk_dist_count_routed on this rank: {waiting for the route, exchange, owner count, total} */
 int gk_dist_last_ms(gk_dist *d, float *ms4);
 int gk_dist_size(gk_dist *d, gk_map *local, uint64_t *total);         /* PartitionedDNAMap.size (:31): sum over the partitions */
+/* The spectrum of the WHOLE PartitionedDNAMap on every rank (gk_map_spectrum's outputs and rules; `bins` the same on every rank):
+ * each rank takes the spectrum of its partition; the partitions are disjoint by owner, so the sum over the ranks of hist, distinct
+ * and occurrences and the maximum of max_count are the whole map's.  COLLECTIVE: two all-reduces (uint64 max: largest count and a
+ * status word; uint64 sum: the rest).  A rank whose local pass failed (a NULL `local` or one of another context included)
+ * still takes part and says so in the status word: every rank then returns an error, nobody waits, and the handle stays usable.
+ * That covers failures of the local pass only: a NULL `d` or `hist`, or bad `bins`, is GK_E_INVALID on the rank that passes it, before
+ * the collective, like a wrong argument of any other gk_dist_* call (the other ranks would wait). */
+int gk_dist_spectrum(gk_dist *d, gk_map *local, uint64_t *hist, uint32_t bins, uint64_t *distinct, uint64_t *occurrences, uint32_t *max_count);
 /* deleteAll / filter_lt, stats, export are LOCAL: call gk_map_filter_lt etc. on `local` on every rank (:49-51 scatter, no data moves). */
 /* The whole k-mer set on every rank, for Graph.buildGraph (the unitig walk crosses partitions arbitrarily):
  * all-gather of every partition's live (key, count), device to device and in bounded chunks (staging <= 0.7 GB to send, world x
