@@ -1,0 +1,309 @@
+// gk_coverage.hip — how often the k-mers of an edge were seen (the count table's multiplicities carried up to the graph), and
+// the removal of dead-end tips decided from those numbers.
+//
+// Reference: none.  Graph.buildGraph (S/data/graph/Graph.scala:269-382) drops the counts once `contains` has been answered, and
+// the reference has no tip removal.  The rules of the two entry points are this project's own and
+// stated in include/genome_amd.h; tests/tips_ref.py restates them.
+//
+// Roofline: one independent random table probe per k-mer of every live edge (total edge length + live edges of them) and
+// nothing else of size: the random-load rate of HBM, as the unitig walk — whose probes depend on each other, these do not.
+#include <algorithm>
+
+#include "gk_graph.h"
+#include "gk_scan.h"
+
+// ---------------------------------------------------------------------------------------------
+// windows of start.seq ++ edge.seq without a per-base loop per window
+// ---------------------------------------------------------------------------------------------
+// n <= 32 bases from base i0 of a 2-bit sequence (4 bases per byte, LSB first).  Touches only bytes that hold a base asked for.
+__device__ __forceinline__ u64 pool_bits(const uint8_t *__restrict__ p, u64 i0, int n) {
+    if (n <= 0) return 0;
+    const u64 b0 = i0 >> 2;
+    const int sh = (int)(i0 & 3) * 2, nb = (int)(((i0 + (u64)n + 3) >> 2) - b0);      // 1 .. 9 bytes
+    u64 lo = 0, hi = 0;
+    for (int j = 0; j < nb && j < 8; j++) lo |= (u64)p[b0 + j] << (8 * j);
+    if (nb > 8) hi = p[b0 + 8];
+    const u64 r = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+    return r & low_mask(2 * n);
+}
+// n <= 32 bases from base i0 of the path (the start node's k bases, then the edge's)
+__device__ __forceinline__ u64 path_bits(Kmer<2> node, const uint8_t *__restrict__ seq, int k, u64 i0, int n) {
+    if (i0 >= (u64)k) return pool_bits(seq, i0 - (u64)k, n);
+    const int m = min(n, k - (int)i0);                       // of them from the node
+    const u64 a = window_bits(node, 2 * (int)i0) & low_mask(2 * m);
+    return m == n ? a : a | (pool_bits(seq, 0, n - m) << (2 * m));
+}
+template <int W> __device__ __forceinline__ Kmer<W> window_at(Kmer<2> node, const uint8_t *__restrict__ seq, int k, u64 d) {
+    if constexpr (W == 1) return Kmer<1>{path_bits(node, seq, k, d, k)};
+    else return Kmer<2>{path_bits(node, seq, k, d, 32), path_bits(node, seq, k, d + 32, k - 32)};
+}
+
+// The count of one window.  Its hash-rule orientation (canonical, gk_device.h) is where a table filled by the rule holds it.
+// Where the rule cannot tell the strands apart (equal hashes), and in a table that took verbatim keys (Table::both, as
+// k_classify), the other orientation may be stored too: the two counts add up.  A palindrome is one key.
+template <int W, class S>
+__device__ __forceinline__ u32 window_count(const Table<W, S> &t, Kmer<W> x, Kmer<W> rc) {
+    const i32 hx = ref_hash(x), hr = ref_hash(rc);
+    const bool fwd = hx < hr;
+    i64 s = table_find(t, fwd ? x : rc);
+    u32 c = s >= 0 ? slot_count(&t.slots[s]) : 0u;
+    if ((t.both || hx == hr) && !(x == rc)) {
+        s = table_find(t, fwd ? rc : x);
+        if (s >= 0) c += slot_count(&t.slots[s]);
+    }
+    return c;
+}
+
+// sum / min / max / missing over a run of windows, rolled: the forward window takes the next base at its end, the reverse
+// complement its complement at the front; the bases come out of the pool one byte per four steps
+struct CovAcc {
+    u64 sum = 0;
+    u32 mn = ~0u, mx = 0, miss = 0;
+    __device__ __forceinline__ void add(u32 c) { sum += c; mn = min(mn, c); mx = max(mx, c); miss += c == 0u; }
+    __device__ __forceinline__ void merge(u64 s, u32 a, u32 b, u32 m) { sum += s; mn = min(mn, a); mx = max(mx, b); miss += m; }
+};
+template <int W, class S>
+__device__ __forceinline__ void cover_run(const Table<W, S> &t, Kmer<2> node, const uint8_t *__restrict__ seq, int k, u64 d0, u64 d1, CovAcc &acc) {
+    Kmer<W> x = window_at<W>(node, seq, k, d0), rc = revcomp(x, k);
+    acc.add(window_count(t, x, rc));
+    u32 byte = (d0 & 3) ? seq[d0 >> 2] : 0u;                 // the window at distance d + 1 ends with base d of the edge
+    for (u64 d = d0; d + 1 < d1; d++) {
+        if ((d & 3) == 0) byte = seq[d >> 2];
+        const int b = (int)(byte >> ((d & 3) * 2)) & 3;
+        x = append_base(x, b, k);
+        rc = prepend_base(3 - b, rc, k);
+        acc.add(window_count(t, x, rc));
+    }
+}
+
+// Per-edge results, indexed by edge id; written for the live edges (`want` == nullptr) or the live edges marked in `want`.
+struct EdgeCov { u64 *sum; u32 *mn, *mx, *miss; };
+static constexpr u64 COV_SHORT = 64;      // windows one lane walks alone
+static constexpr u64 COV_RUN = 16;        // consecutive windows per lane and pass of the long form
+
+// short edges (<= COV_SHORT windows): one lane per edge, no atomics
+template <int W, class S>
+__global__ __launch_bounds__(BLOCK) void k_cov_short(GraphView g, Table<W, S> t, const uint8_t *__restrict__ want, EdgeCov out) {
+    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK) {
+        if (!g.e_alive[e] || (want && !want[e])) continue;
+        const u64 nwin = g.e_len[e] + 1;
+        if (nwin > COV_SHORT) continue;
+        const u32 s = g.e_start[e];
+        CovAcc acc;
+        cover_run<W, S>(t, Kmer<2>{g.node_lo[s], W == 2 ? g.node_hi[s] : 0ull}, g.pool + g.e_off[e], g.k, 0, nwin, acc);
+        out.sum[e] = acc.sum; out.mn[e] = acc.mn; out.mx[e] = acc.mx; out.miss[e] = acc.miss;
+    }
+}
+// long edges: one workgroup per edge at a time; a pass is BLOCK runs of COV_RUN consecutive windows, lane t the t-th.  The partial
+// results meet by wave shuffle, then through one LDS step; lane 0 writes.
+template <int W, class S>
+__global__ __launch_bounds__(BLOCK) void k_cov_long(GraphView g, Table<W, S> t, const uint8_t *__restrict__ want, EdgeCov out) {
+    __shared__ u64 s_sum[BLOCK / 64];
+    __shared__ u32 s_mn[BLOCK / 64], s_mx[BLOCK / 64], s_miss[BLOCK / 64];
+    for (u64 e = blockIdx.x; e < g.n_edges; e += gridDim.x) {            // (uniform over the workgroup: the barriers below are safe)
+        if (!g.e_alive[e] || (want && !want[e])) continue;
+        const u64 nwin = g.e_len[e] + 1;
+        if (nwin <= COV_SHORT) continue;
+        const u32 s = g.e_start[e];
+        const Kmer<2> node{g.node_lo[s], W == 2 ? g.node_hi[s] : 0ull};
+        const uint8_t *seq = g.pool + g.e_off[e];
+        CovAcc acc;
+        for (u64 d0 = (u64)threadIdx.x * COV_RUN; d0 < nwin; d0 += (u64)BLOCK * COV_RUN)
+            cover_run<W, S>(t, node, seq, g.k, d0, min(d0 + COV_RUN, nwin), acc);
+        for (int d = 32; d; d >>= 1)
+            acc.merge(__shfl_down(acc.sum, d), __shfl_down(acc.mn, d), __shfl_down(acc.mx, d), __shfl_down(acc.miss, d));
+        const int wave = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) { s_sum[wave] = acc.sum; s_mn[wave] = acc.mn; s_mx[wave] = acc.mx; s_miss[wave] = acc.miss; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < BLOCK / 64; w++) acc.merge(s_sum[w], s_mn[w], s_mx[w], s_miss[w]);
+            out.sum[e] = acc.sum; out.mn[e] = acc.mn; out.mx[e] = acc.mx; out.miss[e] = acc.miss;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_cov_want(const u32 *__restrict__ ids, u64 n, u64 n_edges, uint8_t *want) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK)
+        if (ids[i] < n_edges) want[ids[i]] = 1;
+}
+// the answers in the order asked; a dead or out-of-range id reads zeros.  missing[0] += the windows not held, once per wave.
+__global__ __launch_bounds__(BLOCK) void k_cov_gather(GraphView g, EdgeCov cov, const u32 *__restrict__ ids, u64 n, u64 *kmers, u64 *sum, u32 *mn, u32 *mx,
+                                                      unsigned long long *missing) {
+    const u64 stride = (u64)gridDim.x * BLOCK;
+    for (u64 i0 = (u64)blockIdx.x * BLOCK; i0 < n; i0 += stride) {       // (uniform over the wave: every lane takes the shuffles)
+        const u64 i = i0 + threadIdx.x;
+        unsigned long long m = 0;
+        if (i < n) {
+            const u32 e = ids[i];
+            const bool ok = e < g.n_edges && g.e_alive[e];
+            kmers[i] = ok ? g.e_len[e] + 1 : 0;
+            sum[i] = ok ? cov.sum[e] : 0;
+            mn[i] = ok ? cov.mn[e] : 0;
+            mx[i] = ok ? cov.mx[e] : 0;
+            m = ok ? cov.miss[e] : 0;
+        }
+        for (int d = 32; d; d >>= 1) m += __shfl_down(m, d);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(missing, m);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// tips (the rule: include/genome_amd.h, gk_graph_clip_tips)
+// ---------------------------------------------------------------------------------------------
+// mean coverage of a strictly below that of b: sum_a * kmers_b < sum_b * kmers_a as 128-bit integers
+__device__ __forceinline__ bool cov_weaker(u64 sum_a, u64 kmers_a, u64 sum_b, u64 kmers_b) {
+    const u64 lh = __umul64hi(sum_a, kmers_b), ll = sum_a * kmers_b, rh = __umul64hi(sum_b, kmers_a), rl = sum_b * kmers_a;
+    return lh != rh ? lh < rh : ll < rl;
+}
+// one lane per edge, from the graph as it is (nothing is written but `mark`): flags[0] = a live edge has a window the table
+// does not hold
+__global__ __launch_bounds__(BLOCK) void k_tip_mark(GraphView g, EdgeCov cov, const unsigned long long *__restrict__ in_off, const u32 *__restrict__ in_list,
+                                                    u64 max_len, uint8_t *mark, u32 *flags) {
+    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK) {
+        mark[e] = 0;
+        if (!g.e_alive[e]) continue;
+        if (cov.miss[e]) flags[0] = 1u;
+        const u64 len = g.e_len[e];
+        if (len > max_len) continue;
+        const u32 u = g.e_start[e], v = g.e_end[e];
+        const u32 out_u = (u32)order_count(g.out_order[u]), out_v = (u32)order_count(g.out_order[v]);
+        const u64 in_u = in_off[u + 1] - in_off[u], in_v = in_off[v + 1] - in_off[v];
+        const u64 sum_e = cov.sum[e], kmers_e = len + 1;
+        bool weaker = false;
+        if (out_v == 0 && in_v == 1 && out_u >= 2) {                     // out-tip: against the other out-edges of u
+            for (int b = 0; b < 4; b++) {
+                const u32 f = g.out_edge[(u64)u * 4 + b];
+                if (f != NONE && f != (u32)e && g.e_alive[f]) weaker |= cov_weaker(sum_e, kmers_e, cov.sum[f], g.e_len[f] + 1);
+            }
+        } else if (in_u == 0 && out_u == 1 && in_v >= 2) {               // in-tip: against the other in-edges of v
+            for (u64 j = in_off[v]; j < in_off[v + 1]; j++) {
+                const u32 f = in_list[j];
+                if (f != (u32)e) weaker |= cov_weaker(sum_e, kmers_e, cov.sum[f], g.e_len[f] + 1);
+            }
+        }
+        if (weaker) mark[e] = 1;
+    }
+}
+// ... applied at once — unless the marking found the map wanting: then the graph stays as it was
+__global__ __launch_bounds__(BLOCK) void k_tip_apply(GraphView g, const uint8_t *__restrict__ mark, const u32 *__restrict__ flags, unsigned long long *removed) {
+    if (flags[0]) return;
+    const u64 stride = (u64)gridDim.x * BLOCK;
+    for (u64 e0 = (u64)blockIdx.x * BLOCK; e0 < g.n_edges; e0 += stride) {
+        const u64 e = e0 + threadIdx.x;
+        const bool rm = e < g.n_edges && mark[e];
+        if (rm) graph_remove_edge(g, (u32)e);
+        const unsigned long long votes = __ballot(rm);
+        if ((threadIdx.x & 63) == 0 && votes) atomicAdd(removed, (unsigned long long)__popcll(votes));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+static int check_counts(const gk_graph *g, gk_map *counts, const char *who) {
+    if (!counts || !counts->ctx) return fail(g->ctx, GK_E_INVALID, std::string(who) + ": null map handle");
+    if (counts->ctx != g->ctx) return fail(g->ctx, GK_E_INVALID, std::string(who) + ": the map belongs to another context");
+    if (counts->k != g->k) return fail(g->ctx, GK_E_INVALID, std::string(who) + ": the map's k is not the graph's");
+    return map_materialize(counts);                          // (a new or cleared map: empty slots, not void bytes)
+}
+
+// the coverage of every live edge (`want` == nullptr) or of the marked ones into arrays owned by `tmp`; stream-ordered, no sync
+static int coverage_pass(gk_graph *g, gk_map *counts, DevScratch &tmp, const uint8_t *want, EdgeCov *cov) {
+    gk_ctx *ctx = g->ctx;
+    const GraphView &v = g->v;
+    hipError_t e = tmp.get(&cov->sum, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&cov->mn, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&cov->mx, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&cov->miss, v.n_edges);
+    if (e != hipSuccess) return hip_fail(ctx, e, "edge coverage: per-edge results");
+    if (v.n_edges == 0) return GK_OK;
+    const int long_grid = (int)std::min<u64>(v.n_edges, (u64)ctx->cu_count * 8);
+    GK_BY_SLOT(counts, {
+        const Table<W, S> t{reinterpret_cast<S *>(counts->slots), counts->nb2, counts->lnb1, counts->k == 64 ? 1u : 0u, counts->dirty ? 1u : 0u};
+        hipLaunchKernelGGL((k_cov_short<W, S>), dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, t, want, *cov);
+        hipLaunchKernelGGL((k_cov_long<W, S>), dim3(long_grid), dim3(BLOCK), 0, ctx->stream, v, t, want, *cov);
+    });
+    GK_HIP(ctx, hipGetLastError());
+    return GK_OK;
+}
+
+extern "C" {
+
+int gk_graph_edge_coverage(gk_graph *g, gk_map *counts, const uint32_t *edge_ids, uint64_t n, uint64_t *kmers, uint64_t *sum,
+                           uint32_t *min_count, uint32_t *max_count, uint64_t *missing) {
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    if (int rc = check_counts(g, counts, "gk_graph_edge_coverage")) return rc;
+    if (missing) *missing = 0;
+    if (n == 0) return GK_OK;
+    if (!edge_ids) return fail(ctx, GK_E_INVALID, "gk_graph_edge_coverage: edge_ids is NULL");
+    const GraphView &v = g->v;
+    DevScratch tmp(ctx);
+    u32 *d_ids = nullptr, *d_mn = nullptr, *d_mx = nullptr;
+    u64 *d_kmers = nullptr, *d_sum = nullptr;
+    uint8_t *d_want = nullptr;
+    unsigned long long *d_missing = nullptr, h_missing = 0;
+    hipError_t e = tmp.get(&d_ids, n);
+    if (e == hipSuccess) e = tmp.get(&d_kmers, n);
+    if (e == hipSuccess) e = tmp.get(&d_sum, n);
+    if (e == hipSuccess) e = tmp.get(&d_mn, n);
+    if (e == hipSuccess) e = tmp.get(&d_mx, n);
+    if (e == hipSuccess) e = tmp.get(&d_want, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&d_missing, 1);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_ids, edge_ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_want, 0, std::max<u64>(v.n_edges, 1), ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_missing, 0, 8, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edge_coverage");
+    hipLaunchKernelGGL(k_cov_want, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, d_ids, (u64)n, v.n_edges, d_want);
+    EdgeCov cov{};
+    if (int rc = coverage_pass(g, counts, tmp, d_want, &cov)) return rc;
+    hipLaunchKernelGGL(k_cov_gather, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, v, cov, d_ids, (u64)n, d_kmers, d_sum, d_mn, d_mx, d_missing);
+    e = read_back(ctx, {{kmers, d_kmers, (size_t)n * 8}, {sum, d_sum, (size_t)n * 8}, {min_count, d_mn, (size_t)n * 4}, {max_count, d_mx, (size_t)n * 4},
+                        {&h_missing, d_missing, 8}});
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edge_coverage");
+    if (missing) *missing = h_missing;
+    return GK_OK;
+}
+
+int gk_graph_clip_tips(gk_graph *g, gk_map *counts, uint64_t max_len, uint64_t *removed_edges) {
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    if (int rc = check_counts(g, counts, "gk_graph_clip_tips")) return rc;
+    if (removed_edges) *removed_edges = 0;
+    const GraphView &v = g->v;
+    if (max_len == 0 || v.n_edges == 0) return GK_OK;
+    DevScratch tmp(ctx);
+    EdgeCov cov{};
+    if (int rc = coverage_pass(g, counts, tmp, nullptr, &cov)) return rc;
+    // the in-edge lists of the graph as it is
+    unsigned long long *d_in_off = nullptr, *d_removed = nullptr, h_removed = 0;
+    u32 *d_in_cnt = nullptr, *d_in_list = nullptr, *d_flags = nullptr, h_flags = 0;
+    u64 *d_sums = nullptr;
+    uint8_t *d_mark = nullptr;
+    hipError_t e = tmp.get(&d_in_off, v.n_nodes + 1);
+    if (e == hipSuccess) e = tmp.get(&d_in_cnt, v.n_nodes);
+    if (e == hipSuccess) e = tmp.get(&d_in_list, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&d_sums, v.n_nodes / SCAN_CHUNK + 2);
+    if (e == hipSuccess) e = tmp.get(&d_mark, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&d_flags, 1);
+    if (e == hipSuccess) e = tmp.get(&d_removed, 1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_in_cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 4, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, 8, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_clip_tips: in-edge lists");
+    const int grid = ggrid(ctx, v.n_edges);
+    hipLaunchKernelGGL(k_in_count, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, d_in_cnt);
+    GK_HIP(ctx, scan_counts(ctx, d_in_cnt, v.n_nodes, d_in_off, d_sums));
+    GK_HIP(ctx, hipMemsetAsync(d_in_cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream));
+    hipLaunchKernelGGL(k_in_fill, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, d_in_off, d_in_cnt, d_in_list);
+    hipLaunchKernelGGL(k_tip_mark, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, cov, d_in_off, d_in_list, (u64)max_len, d_mark, d_flags);
+    // the decision is complete before anything is applied, and a map that is not this graph's leaves the graph as it was
+    hipLaunchKernelGGL(k_tip_apply, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, d_mark, d_flags, d_removed);
+    GK_HIP(ctx, read_back(ctx, {{&h_flags, d_flags, 4}, {&h_removed, d_removed, 8}}));
+    if (h_flags) return fail(ctx, GK_E_STATE, "gk_graph_clip_tips: the map does not hold every k-mer of the graph (not the table it was built from?)");
+    if (removed_edges) *removed_edges = h_removed;
+    return graph_refresh_counts(g);
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gk_internal.h"
+#include "gk_tile.h"
 
 using namespace gk;
 
@@ -81,6 +82,24 @@ __device__ __forceinline__ u32 order_remove(u32 o, int b) {
 }
 __device__ __forceinline__ u32 rev4(u32 m) { return ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3); }
 __device__ __forceinline__ int pool_get(const uint8_t *pool, u64 off, u64 i) { return (pool[off + (i >> 2)] >> ((i & 3) * 2)) & 3; }
+
+// MapGraph.removeEdge (Graph.scala:191-195) of a live edge, safe beside other lanes removing other edges: the start node's
+// out-edge slot and insertion order, the edge itself, the end node's in-degree (k_remove_edges_by_id, k_tip_apply)
+__device__ __forceinline__ void graph_remove_edge(const GraphView &g, u32 e) {
+    const u32 v = g.e_start[e];
+    const int b = g.e_first[e];
+    if (atomicCAS(&g.out_edge[(u64)v * 4 + b], e, NONE) == e) {
+        u32 seen = g.out_order[v], prev;
+        do { prev = seen; seen = atomicCAS(&g.out_order[v], prev, order_remove(prev, b)); } while (seen != prev);
+    }
+    g.e_alive[e] = 0;
+    atomicSub(&g.in_deg[g.e_end[e]], 1u);
+}
+
+// in-edge lists (Node.inEdgeIds) as CSR by end node (gk_pairs.hip): cnt[v] += 1 per live edge ending at v; then, with `off` the
+// exclusive scan of those counts and `cursor` zeroed, list[off[v] ..] = the ids of those edges (order unspecified)
+__global__ __launch_bounds__(BLOCK) void k_in_count(GraphView g, u32 *cnt);
+__global__ __launch_bounds__(BLOCK) void k_in_fill(GraphView g, const unsigned long long *off, u32 *cursor, u32 *list);
 
 
 // host-side helpers of gk_graph.hip that the paired-end stage (gk_pairs.hip) uses

@@ -245,7 +245,7 @@ __global__ __launch_bounds__(BLOCK) void k_pair_keys(const uint8_t *__restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// in-edge lists (Node.inEdgeIds) as CSR by end node, built on the device
+// in-edge lists (Node.inEdgeIds) as CSR by end node, built on the device (declared in gk_graph.h: the tip rule reads them too)
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void k_in_count(GraphView g, u32 *cnt) {
     for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK)
@@ -1271,14 +1271,7 @@ __global__ __launch_bounds__(BLOCK) void k_remove_edges_by_id(GraphView g, const
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
         const u32 e = edge[i];                               // MapGraph.removeEdge :191-195
         if (e >= g.n_edges || !g.e_alive[e]) continue;
-        const u32 v = g.e_start[e];
-        const int b = g.e_first[e];
-        if (atomicCAS(&g.out_edge[(u64)v * 4 + b], e, NONE) == e) {
-            u32 seen = g.out_order[v], prev;
-            do { prev = seen; seen = atomicCAS(&g.out_order[v], prev, order_remove(prev, b)); } while (seen != prev);
-        }
-        g.e_alive[e] = 0;
-        atomicSub(&g.in_deg[g.e_end[e]], 1u);
+        graph_remove_edge(g, e);
         atomicAdd(removed, 1ull);
     }
 }

@@ -172,6 +172,27 @@ class HipGraph:
         L.check(L.lib().gk_graph_remove_edges_by_id(self.h, L.ptr(ids, C.c_uint32), len(ids), C.byref(rm)), self.ctx.h)
         return rm.value
 
+    # ---- edge coverage and tips (this project's own rules: include/genome_amd.h) ---------------------------------------
+    def edgeCoverage(self, counts: HipDNAMap, edge_ids=None) -> dict:
+        """How often the k-mers of the edges were seen, from the count table `counts` (the one the graph was built from, or any
+        table of this k): per id `kmers` (= len + 1 windows, both end nodes included), `sum`, `min`, `max` of their counts (zeros
+        for a dead or out-of-range id), and `missing` = windows `counts` does not hold.  Default: every id below idBounds()."""
+        ids = np.arange(self.idBounds()[1], dtype=np.uint32) if edge_ids is None else np.ascontiguousarray(edge_ids, np.uint32)
+        n = len(ids)
+        kmers, total = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        mn, mx = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        missing = C.c_uint64()
+        L.check(L.lib().gk_graph_edge_coverage(self.h, counts.h, L.ptr(ids, C.c_uint32), n, L.ptr(kmers, C.c_uint64), L.ptr(total, C.c_uint64),
+                                               L.ptr(mn, C.c_uint32), L.ptr(mx, C.c_uint32), C.byref(missing)), self.ctx.h)
+        return {"ids": ids, "kmers": kmers, "sum": total, "min": mn, "max": mx, "missing": missing.value}
+
+    def clipTips(self, counts: HipDNAMap, max_len=None) -> int:
+        """One round of tip removal: dead-end edges of at most `max_len` bases (default 2k) beside an edge of strictly higher mean
+        coverage -> the number removed.  Call simplifyGraph() next.  GkError GK_E_STATE if `counts` is not this graph's table."""
+        rm = C.c_uint64()
+        L.check(L.lib().gk_graph_clip_tips(self.h, counts.h, 2 * self.k if max_len is None else int(max_len), C.byref(rm)), self.ctx.h)
+        return rm.value
+
     def walkPairs(self, positions, support: "Support", bin_bytes, npairs: int, range_lo: int = 180, range_hi: int = 250):
         """:213-247: the pairs' positions through `positions` (getGraphMap of this graph as it is now), annotate, the bounded
         walks; the supported (edge, edge) pairs are counted in `support`."""

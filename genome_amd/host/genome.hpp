@@ -574,6 +574,31 @@ class Graph {
         check(gk_graph_split_by_support(h_, support.handle(), cutoff, &rm, &nn), ctx_.handle());
         return {rm, nn};
     }
+    // Edge coverage (this project's own rule, include/genome_amd.h): per id the number of k-mers (len + 1 windows), the sum, minimum
+    // and maximum of their counts in `counts`; zeros for a dead or out-of-range id.  Default: every id below the edge id bound.
+    struct EdgeCoverage { std::vector<uint32_t> ids; std::vector<uint64_t> kmers, sum; std::vector<uint32_t> min, max; uint64_t missing = 0; };
+    EdgeCoverage edgeCoverage(const DNAMap &counts) const {
+        uint64_t nodeIds = 0, edgeIds = 0;
+        check(gk_graph_id_bounds(h_, &nodeIds, &edgeIds), ctx_.handle());
+        std::vector<uint32_t> ids(edgeIds);
+        for (uint64_t i = 0; i < edgeIds; i++) ids[i] = (uint32_t)i;
+        return edgeCoverage(counts, ids);
+    }
+    EdgeCoverage edgeCoverage(const DNAMap &counts, const std::vector<uint32_t> &ids) const {
+        EdgeCoverage c;
+        c.ids = ids;
+        const size_t n = ids.size();
+        c.kmers.resize(n); c.sum.resize(n); c.min.resize(n); c.max.resize(n);
+        check(gk_graph_edge_coverage(h_, counts.handle(), ids.data(), n, c.kmers.data(), c.sum.data(), c.min.data(), c.max.data(), &c.missing), ctx_.handle());
+        return c;
+    }
+    // One round of tip removal (include/genome_amd.h): dead-end edges of at most maxLen bases (0 = the default, 2k) beside an edge
+    // of strictly higher mean coverage -> edges removed; simplifyGraph() is the next call.  GK_E_STATE if `counts` is not this graph's.
+    uint64_t clipTips(const DNAMap &counts, uint64_t maxLen = 0) {
+        uint64_t removed = 0;
+        check(gk_graph_clip_tips(h_, counts.handle(), maxLen ? maxLen : 2 * (uint64_t)k_, &removed), ctx_.handle());
+        return removed;
+    }
     // CheckGraph.scala:37-41 over the live edges longer than longerThan: count, summed length, median (sorted[count / 2], the
     // reference's "N50"), the real N50, the maximum; computed on the device
     struct ContigStats { uint64_t count = 0, sum = 0, median = 0, n50 = 0, max = 0; };

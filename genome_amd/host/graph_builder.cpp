@@ -4,7 +4,7 @@
 // The reference logs its counters through akka Logging (:34-53); here they are one JSON object.
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
-//                 [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH]
+//                 [--clip-tips [MAXLEN|auto]] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
 //   --fastq converts the FASTQ file on the GPU first (Convert2bin, gk_fastq; --split N = its n, default 36) and takes the pair
 //   count from the conversion; the flow is then the same.  Not with --world (exit 2): convert2bin the file first.
@@ -13,6 +13,11 @@
 //   with min_count = 2); a spectrum without a valley falls back to the reference's 3 and the JSON says "rounds_auto":false.
 //   --spectrum PATH writes that spectrum as one `count<TAB>keys` line per non-empty bin, the overflow bin as `>=N` (rank 0).
 //   With either flag the JSON gains "rounds_auto", "valley", "peak" and "genome_size_estimate"; "rounds" is the number used.
+//   --clip-tips removes dead-end tips by edge coverage (gk_graph_clip_tips: this project's own rule, the reference has none) after
+//   the retain and before --simplify's two steps: clip, then simplifyGraph, repeated until a round removes nothing, 8 rounds at
+//   most; MAXLEN = the longest edge a tip may be (auto, the default: 2k).  The JSON gains "clip_tips":{"max_len","removed":[per round]}.
+//   --edge-coverage, with --out, writes <prefix>.coverage.txt: per live edge of the final graph, ascending ids, one line
+//   `edge id, len, kmers, sum, min, max` (gk_graph_edge_coverage).  Neither runs with --world (exit 2).
 //   --simplify runs removeBubbles + simplifyGraph (GraphSimplifier.scala:317-318) before writing;
 //   --walk-pairs runs GraphSimplifier.startup's paired-end stage on the graph GraphBuilder hands over (:188-318): position
 //   map, the pairs' walks with range LO to HI (the reference: 180 to 250, :146), node split at genome.cutoff = CUTOFF,
@@ -77,7 +82,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--clip-tips [MAXLEN|auto]] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string infile = argv[1];
@@ -89,6 +94,8 @@ int main(int argc, char **argv) {
     uint64_t takeFirst = UINT64_MAX;              // genome.takeFirst
     uint64_t prefilter = 0;                       // expected distinct k-mers; 0 = no singleton pre-filter
     bool retain = true, simplify = false;
+    bool clipTips = false, edgeCoverage = false;
+    uint64_t tipMaxLen = 0;                       // 0 = auto: 2k
     int walkCutoff = -1, walkLo = 180, walkHi = 250;
     std::string out, idFile, saveGraph, spectrumPath;
     int world = 0, rank = 0;                      // world 0: one GPU, no communicator
@@ -102,6 +109,12 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--prefilter") && i + 1 < argc) prefilter = std::stoull(argv[++i]);
         else if (!std::strcmp(argv[i], "--no-retain")) retain = false;
         else if (!std::strcmp(argv[i], "--simplify")) simplify = true;
+        else if (!std::strcmp(argv[i], "--clip-tips")) {
+            clipTips = true;
+            if (i + 1 < argc && !std::strcmp(argv[i + 1], "auto")) i++;
+            else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') tipMaxLen = std::stoull(argv[++i]);
+        }
+        else if (!std::strcmp(argv[i], "--edge-coverage")) edgeCoverage = true;
         else if (!std::strcmp(argv[i], "--walk-pairs") && i + 3 < argc) { walkCutoff = std::stoi(argv[++i]); walkLo = std::stoi(argv[++i]); walkHi = std::stoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
@@ -118,6 +131,11 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--prefilter runs on one GPU only (not with --world)\n");
         return 2;
     }
+    if (world && (clipTips || edgeCoverage)) {
+        std::fprintf(stderr, "--clip-tips and --edge-coverage run on one GPU only (not with --world)\n");
+        return 2;
+    }
+    if (clipTips && !tipMaxLen) tipMaxLen = 2 * (uint64_t)k;
     try {
         if (fastq.empty()) {
             std::ifstream f(infile, std::ios::binary);
@@ -162,6 +180,13 @@ int main(int argc, char **argv) {
         auto [hist, hist2] = graph.componentHistograms();
         uint64_t kept = nodes, comps = 0;
         if (retain) std::tie(kept, comps) = graph.retainLargestComponent();                              // :52-54
+        // --clip-tips: clip, then simplifyGraph, until a round removes nothing (the counts are the table the graph was built from)
+        std::vector<uint64_t> tipsRemoved;
+        while (clipTips && tipsRemoved.size() < 8) {
+            tipsRemoved.push_back(graph.clipTips(*kmersFreq, tipMaxLen));
+            if (!tipsRemoved.back()) break;
+            graph.simplifyGraph();
+        }
         // --simplify = GraphSimplifier.scala:317-318, applied to the graph GraphBuilder hands over (i.e. after retain)
         if (simplify) { graph.removeBubbles(); graph.simplifyGraph(); }
         uint64_t supPairs = 0, badPairs = 0, walked = 0, removedEdges = 0, newNodes = 0;
@@ -191,6 +216,11 @@ int main(int argc, char **argv) {
         if (withSpectrum)
             std::printf("\"rounds_auto\":%s,\"valley\":%u,\"peak\":%u,\"genome_size_estimate\":%llu,", chosen.autoFound ? "true" : "false",
                         chosen.cutoff.valley, chosen.cutoff.peak, (unsigned long long)chosen.cutoff.genomeSize);
+        if (clipTips) {
+            std::printf("\"clip_tips\":{\"max_len\":%llu,\"removed\":[", (unsigned long long)tipMaxLen);
+            for (size_t i = 0; i < tipsRemoved.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)tipsRemoved[i]);
+            std::printf("]},");
+        }
         if (walkCutoff >= 0)
             std::printf("\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},",
                         (unsigned long long)supPairs, (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges,
@@ -212,6 +242,12 @@ int main(int argc, char **argv) {
             std::ofstream cf(out + ".contigs"), df(out + ".dot");
             graph.writeContigs(cf);
             graph.writeDot(df);
+            if (edgeCoverage) {
+                std::ofstream vf(out + ".coverage.txt");
+                const auto c = graph.edgeCoverage(*kmersFreq);
+                for (size_t i = 0; i < c.ids.size(); i++)
+                    if (c.kmers[i]) vf << c.ids[i] << " " << c.kmers[i] - 1 << " " << c.kmers[i] << " " << c.sum[i] << " " << c.min[i] << " " << c.max[i] << "\n";
+            }
         }
     } catch (const std::exception &e) {
         std::fprintf(stderr, "graph_builder: %s\n", e.what());

@@ -432,6 +432,33 @@ int gk_graph_id_fingerprint(gk_graph *g, uint64_t *fp);
 /* MapGraph.removeEdge (:191-195) by edge id (each id once, as the reference's `toRemove` Set, GraphSimplifier.scala:270,316) */
 int gk_graph_remove_edges_by_id(gk_graph *g, const uint32_t *edge_ids, uint64_t n, uint64_t *removed);
 
+/* ---- edge coverage and tips: this project's own rules (the reference keeps no counts past buildGraph and removes no tips) ----
+ * Coverage.  A live edge of `len` bases leaving the start node S has len + 1 k-mers: the windows of S ++ seq at distances
+ * 0 .. len, both end nodes included — the strand-symmetric choice: an edge and its reverse-complement twin read the same numbers.
+ * The count of a window is what `counts` holds for its hash-rule orientation (FreqFilter.scala:31-32), 0 if it holds none; where
+ * the rule cannot tell the strands apart (equal hashes, the k-mer not its own reverse complement) and in a table that took
+ * verbatim keys in either orientation, the counts of both stored orientations add up.  Per id asked for, in the order asked:
+ * kmers[i] = len + 1, sum[i] = the sum of the counts, min_count[i] / max_count[i] over the same windows; a dead or out-of-range id
+ * gives zeros.  *missing = the windows with no entry in `counts`, summed over the ids asked for (an id asked twice counts twice).
+ * Any output pointer may be NULL.  `counts` may be any k-mer table of the graph's k on the graph's context, in either slot layout —
+ * the table the graph was built from (the build leaves its counts alone), or one counted afresh for a loaded graph; a table of
+ * another k or context, or a NULL handle: GK_E_INVALID.  Nothing is attached to the graph: the call is valid on a graph in any
+ * state (merged edges, node copies), and neither the graph, its file format, checksum nor id fingerprint change. */
+int gk_graph_edge_coverage(gk_graph *g, gk_map *counts, const uint32_t *edge_ids, uint64_t n, uint64_t *kmers, uint64_t *sum,
+                           uint32_t *min_count, uint32_t *max_count, uint64_t *missing);
+/* Tips.  One round, decided entirely from the graph's state at entry and then applied at once (the result depends neither on
+ * scheduling nor on id order).  A live edge e (start u, end v, len bases, mean coverage sum_e / kmers_e as above) is removed iff
+ *   len <= max_len, and a competitor f exists with STRICTLY higher mean coverage, and one of
+ *   out-tip: v has out-degree 0 and in-degree 1, and u has out-degree >= 2; competitors are the other live out-edges of u;
+ *   in-tip:  u has in-degree 0 and out-degree 1, and v has in-degree >= 2; competitors are the other live in-edges of v.
+ * "e below f" is sum_e * kmers_f < sum_f * kmers_e, compared exactly as 128-bit integers; no floating point.  So: ties remove
+ * nothing; an isolated short contig is kept; two tips at one junction beside a stronger third edge both go; the twin of an
+ * out-tip is an in-tip with the same numbers, so a strand-closed edge set stays strand-closed.  Removal is MapGraph.removeEdge
+ * (:191-195); nodes stay — the isolated dead ends and the junctions left with one way in and one way out are what the caller's
+ * next simplifyGraph removes and merges.  *removed_edges = edges removed.  max_len == 0 removes nothing.  If any window of any
+ * live edge is missing from `counts` the map is not this graph's: GK_E_STATE, and the graph is untouched.  Handles as above. */
+int gk_graph_clip_tips(gk_graph *g, gk_map *counts, uint64_t max_len, uint64_t *removed_edges);
+
 /* ---- the graph file: MapGraph.write (Graph.scala:232-261) / Graph(file) (:384-390) --------------------------------------
  * The stage boundary between GraphBuilder (GraphBuilder.scala:55-56) and GraphSimplifier (GraphSimplifier.scala:152-153).
  * This project's own format (the reference's is Kryo).  Version 1, every value little-endian.  Header, 128 bytes:
