@@ -38,22 +38,6 @@ template <int W> __device__ __forceinline__ Kmer<W> window_at(Kmer<2> node, cons
     else return Kmer<2>{path_bits(node, seq, k, d, 32), path_bits(node, seq, k, d + 32, k - 32)};
 }
 
-// The count of one window.  Its hash-rule orientation (canonical, gk_device.h) is where a table filled by the rule holds it.
-// Where the rule cannot tell the strands apart (equal hashes), and in a table that took verbatim keys (Table::both, as
-// k_classify), the other orientation may be stored too: the two counts add up.  A palindrome is one key.
-template <int W, class S>
-__device__ __forceinline__ u32 window_count(const Table<W, S> &t, Kmer<W> x, Kmer<W> rc) {
-    const i32 hx = ref_hash(x), hr = ref_hash(rc);
-    const bool fwd = hx < hr;
-    i64 s = table_find(t, fwd ? x : rc);
-    u32 c = s >= 0 ? slot_count(&t.slots[s]) : 0u;
-    if ((t.both || hx == hr) && !(x == rc)) {
-        s = table_find(t, fwd ? rc : x);
-        if (s >= 0) c += slot_count(&t.slots[s]);
-    }
-    return c;
-}
-
 // sum / min / max / missing over a run of windows, rolled: the forward window takes the next base at its end, the reverse
 // complement its complement at the front; the bases come out of the pool one byte per four steps
 struct CovAcc {

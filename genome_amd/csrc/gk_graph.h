@@ -1,5 +1,6 @@
 // gk_graph.h — the device-side view of a MapGraph (S/data/graph/Graph.scala:153-209) and the host handle, shared by
-// gk_graph.hip (build, structural edits) and gk_pairs.hip (the paired-end stage).
+// gk_graph.hip (build, structural edits), gk_pairs.hip (the paired-end stage) and the readers of a count table (gk_coverage.hip,
+// gk_correct.hip: window_count).
 #pragma once
 
 #include <memory>
@@ -94,6 +95,22 @@ __device__ __forceinline__ void graph_remove_edge(const GraphView &g, u32 e) {
     }
     g.e_alive[e] = 0;
     atomicSub(&g.in_deg[g.e_end[e]], 1u);
+}
+
+// The count of one window.  Its hash-rule orientation (canonical, gk_device.h) is where a table filled by the rule holds it.
+// Where the rule cannot tell the strands apart (equal hashes), and in a table that took verbatim keys (Table::both, as
+// k_classify), the other orientation may be stored too: the two counts add up.  A palindrome is one key.
+template <int W, class S>
+__device__ __forceinline__ u32 window_count(const Table<W, S> &t, Kmer<W> x, Kmer<W> rc) {
+    const i32 hx = ref_hash(x), hr = ref_hash(rc);
+    const bool fwd = hx < hr;
+    i64 s = table_find(t, fwd ? x : rc);
+    u32 c = s >= 0 ? slot_count(&t.slots[s]) : 0u;
+    if ((t.both || hx == hr) && !(x == rc)) {
+        s = table_find(t, fwd ? rc : x);
+        if (s >= 0) c += slot_count(&t.slots[s]);
+    }
+    return c;
 }
 
 // in-edge lists (Node.inEdgeIds) as CSR by end node (gk_pairs.hip): cnt[v] += 1 per live edge ending at v; then, with `off` the

@@ -131,6 +131,10 @@ def _keys(k: int, keys):
     return lo, hi
 
 
+# the GK_CORRECT_* indices of gk_reads_correct's statistics, in order
+CORRECT_STATS = ("reads", "short", "windows", "weak_windows", "weak_runs", "corrected", "ambiguous", "unresolved", "skipped", "reads_changed")
+
+
 class HipDNAMap:
     """`ArrayDNAMap[Int]` resident in HBM (one partition)."""
 
@@ -276,6 +280,35 @@ class HipDNAMap:
         occ = C.c_uint64()
         L.check(L.lib().gk_map_count_superkmers_dev(self.h, d_records, nrecords, kmers_total, C.byref(occ)), self.ctx.h)
         return occ.value
+
+    # ---- spectral read correction (gk_reads_correct: this project's own rule, include/genome_amd.h) --------------------------
+    def _solid(self, solid) -> dict:
+        """solid = "auto": the valley of this table's count spectrum (gk_spectrum_cutoff), or freqfilter.DEFAULT_ROUNDS when the
+        spectrum has none -- and the dict says which ("solid_auto")."""
+        if solid != "auto":
+            return {"solid": int(solid)}
+        from .freqfilter import auto_rounds
+        a = auto_rounds(self)
+        return {"solid": a["rounds"], "solid_auto": a["rounds_auto"], "valley": a["valley"], "peak": a["peak"]}
+
+    def correct_reads(self, bin_bytes, nreads: int, solid=3):
+        """Replace the bases of a `.bin` stream that lie under a run of weak k-mers (count < solid in this table) where exactly one
+        replacement makes the run solid -> (corrected stream as bytes, stats dict named as CORRECT_STATS).  The map is not changed."""
+        buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)
+        info = self._solid(solid)
+        out = np.empty(buf.size, np.uint8)
+        st = np.zeros(len(CORRECT_STATS), np.uint64)
+        L.check(L.lib().gk_reads_correct(self.h, L.ptr(buf, C.c_uint8), buf.size, nreads, info["solid"], L.ptr(out, C.c_uint8),
+                                         L.ptr(st, C.c_uint64)), self.ctx.h)
+        return out.tobytes(), dict(zip(CORRECT_STATS, (int(x) for x in st)), **info)
+
+    def correct_reads_dev(self, d_records: int, nreads: int, read_len: int, solid=3, d_out: int | None = None) -> dict:
+        """The same over records resident in HBM at stride 1 + ceil(read_len / 4), written to d_out (default: in place) -> stats dict"""
+        info = self._solid(solid)
+        st = np.zeros(len(CORRECT_STATS), np.uint64)
+        L.check(L.lib().gk_reads_correct_dev(self.h, d_records, nreads, read_len, info["solid"], d_records if d_out is None else d_out,
+                                             L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(CORRECT_STATS, (int(x) for x in st)), **info)
 
     def clear(self):
         L.check(L.lib().gk_map_clear(self.h), self.ctx.h)

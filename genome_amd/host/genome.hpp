@@ -258,6 +258,27 @@ class DNAMap {
         check(gk_map_spectrum(h_, s.hist.data(), bins, &s.distinct, &s.occurrences, &s.maxCount), ctx_.handle());
         return s;
     }
+    // spectral read correction (gk_reads_correct: this project's own rule, include/genome_amd.h): the bases of `bin` under a run of
+    // weak k-mers (count < solid in this table) are replaced where exactly one replacement makes the run solid.  `out` holds
+    // nbytes and may be `bin`.  The table is not changed.
+    struct CorrectStats {
+        uint64_t v[GK_CORRECT_NSTATS] = {};
+        uint64_t operator[](int i) const { return v[i]; }
+        // {"reads": .., "short": .., ...} in the order of the GK_CORRECT_* indices
+        std::string json() const {
+            static const char *names[GK_CORRECT_NSTATS] = {"reads", "short", "windows", "weak_windows", "weak_runs", "corrected", "ambiguous", "unresolved",
+                                                           "skipped", "reads_changed"};
+            std::string s = "{";
+            for (int i = 0; i < GK_CORRECT_NSTATS; i++) s += std::string(i ? ", \"" : "\"") + names[i] + "\": " + std::to_string(v[i]);
+            return s + "}";
+        }
+    };
+    CorrectStats correctReads(const uint8_t *bin, size_t nbytes, uint64_t nreads, uint32_t solid, uint8_t *out) const {
+        CorrectStats st;
+        check(gk_reads_correct(h_, bin, nbytes, nreads, solid, out, st.v), ctx_.handle());
+        return st;
+    }
+    void clear() { check(gk_map_clear(h_), ctx_.handle()); }       // back to an empty table of the same capacity
     // the table's invariants and an order-independent content checksum (gk_map_verify)
     struct Verify { uint64_t live, bad, sumCounts, checksum; };
     Verify verify() const {

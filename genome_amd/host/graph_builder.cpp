@@ -4,7 +4,7 @@
 // The reference logs its counters through akka Logging (:34-53); here they are one JSON object.
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
-//                 [--clip-tips [MAXLEN|auto]] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH]
+//                 [--clip-tips [MAXLEN|auto]] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--correct N|auto]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
 //   --fastq converts the FASTQ file on the GPU first (Convert2bin, gk_fastq; --split N = its n, default 36) and takes the pair
 //   count from the conversion; the flow is then the same.  Not with --world (exit 2): convert2bin the file first.
@@ -18,6 +18,10 @@
 //   most; MAXLEN = the longest edge a tip may be (auto, the default: 2k).  The JSON gains "clip_tips":{"max_len","removed":[per round]}.
 //   --edge-coverage, with --out, writes <prefix>.coverage.txt: per live edge of the final graph, ascending ids, one line
 //   `edge id, len, kmers, sum, min, max` (gk_graph_edge_coverage).  Neither runs with --world (exit 2).
+//   --correct N|auto corrects the reads before they are counted (gk_reads_correct: this project's own rule, the reference has none):
+//   count, correct the stream in host memory against that count (solid = N, or the valley of its spectrum; 3 when it has none),
+//   then count the corrected stream and go on as without the flag — --rounds auto sees the second spectrum, and --walk-pairs walks
+//   the corrected mates.  The JSON gains "correct":{"solid","solid_auto",the ten statistics}.  Not with --world (exit 2).
 //   --simplify runs removeBubbles + simplifyGraph (GraphSimplifier.scala:317-318) before writing;
 //   --walk-pairs runs GraphSimplifier.startup's paired-end stage on the graph GraphBuilder hands over (:188-318): position
 //   map, the pairs' walks with range LO to HI (the reference: 180 to 250, :146), node split at genome.cutoff = CUTOFF,
@@ -82,7 +86,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--clip-tips [MAXLEN|auto]] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--clip-tips [MAXLEN|auto]] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--correct N|auto] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string infile = argv[1];
@@ -96,6 +100,8 @@ int main(int argc, char **argv) {
     bool retain = true, simplify = false;
     bool clipTips = false, edgeCoverage = false;
     uint64_t tipMaxLen = 0;                       // 0 = auto: 2k
+    bool correct = false;                         // --correct
+    uint32_t solid = 0;                           // 0 = auto: the valley of the first count's spectrum
     int walkCutoff = -1, walkLo = 180, walkHi = 250;
     std::string out, idFile, saveGraph, spectrumPath;
     int world = 0, rank = 0;                      // world 0: one GPU, no communicator
@@ -115,6 +121,11 @@ int main(int argc, char **argv) {
             else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') tipMaxLen = std::stoull(argv[++i]);
         }
         else if (!std::strcmp(argv[i], "--edge-coverage")) edgeCoverage = true;
+        else if (!std::strcmp(argv[i], "--correct") && i + 1 < argc) {
+            correct = true;
+            if (!std::strcmp(argv[++i], "auto")) solid = 0;
+            else if ((solid = (uint32_t)std::stoul(argv[i])) == 0) { std::fprintf(stderr, "--correct N needs N >= 1 (or auto)\n"); return 2; }
+        }
         else if (!std::strcmp(argv[i], "--walk-pairs") && i + 3 < argc) { walkCutoff = std::stoi(argv[++i]); walkLo = std::stoi(argv[++i]); walkHi = std::stoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
@@ -135,6 +146,10 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--clip-tips and --edge-coverage run on one GPU only (not with --world)\n");
         return 2;
     }
+    if (world && correct) {
+        std::fprintf(stderr, "--correct runs on one GPU only (not with --world)\n");
+        return 2;
+    }
     if (clipTips && !tipMaxLen) tipMaxLen = 2 * (uint64_t)k;
     try {
         if (fastq.empty()) {
@@ -150,6 +165,21 @@ int main(int argc, char **argv) {
         }
         genome::Context ctx(device);
         if (!fastq.empty()) data = genome::PairedEndData::fromFastq(ctx, fastq, split);     // the pair count comes from the conversion
+        // --correct: a count of the reads as they are, the stream corrected against it in place, and the flow below starts over
+        genome::DNAMap::CorrectStats corrected;
+        bool solidAuto = false;
+        if (correct) {
+            const uint64_t pairs = std::min<uint64_t>(data.count, takeFirst);
+            const size_t nbytes = genome::pairBytes(data, 0, pairs).second;
+            genome::DNAMap raw(ctx, k);
+            raw.countReads(data.bin.data(), nbytes, 2 * pairs);
+            if (!solid) {
+                const uint32_t valley = genome::spectrumCutoff(raw.spectrum().hist).valley;
+                solidAuto = valley != 0;
+                solid = solidAuto ? valley : 3;
+            }
+            corrected = raw.correctReads(data.bin.data(), nbytes, 2 * pairs, solid, data.bin.data());
+        }
         std::unique_ptr<genome::PartitionedDNAMap> pm;
         uint64_t sent = 0, owned = 0, good = 0;
         std::unique_ptr<genome::DNAMap> kmersFreq;
@@ -216,6 +246,10 @@ int main(int argc, char **argv) {
         if (withSpectrum)
             std::printf("\"rounds_auto\":%s,\"valley\":%u,\"peak\":%u,\"genome_size_estimate\":%llu,", chosen.autoFound ? "true" : "false",
                         chosen.cutoff.valley, chosen.cutoff.peak, (unsigned long long)chosen.cutoff.genomeSize);
+        if (correct) {
+            std::string st = corrected.json();
+            std::printf("\"correct\":{\"solid\":%u,\"solid_auto\":%s,%s,", solid, solidAuto ? "true" : "false", st.c_str() + 1);
+        }
         if (clipTips) {
             std::printf("\"clip_tips\":{\"max_len\":%llu,\"removed\":[", (unsigned long long)tipMaxLen);
             for (size_t i = 0; i < tipsRemoved.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)tipsRemoved[i]);

@@ -170,6 +170,53 @@ int gk_map_prefetch_reads(gk_map *m, const uint8_t *bin_host, size_t nbytes, uin
  * the call then fails with GK_E_FORMAT (the map's contents are unspecified: clear it). */
 int gk_map_count_reads_dev(gk_map *m, const void *dev_records, uint64_t nreads, int read_len, uint64_t *occurrences);
 
+/* ---- spectral read correction: this project's own rule (the reference has none: GraphBuilder.scala:30 hardcodes rounds = 3 and
+ * lives with the k true k-mers that every wrong base costs) ----
+ * Inputs: `counts`, a k-mer table of some k (either slot layout, filtered or not); a threshold solid >= 1; a `.bin` record stream.
+ * The COUNT of a window is what gk_graph_edge_coverage defines: the entry of its hash-rule orientation, 0 if there is none; the two
+ * stored orientations add up on a hash tie and in a table that took verbatim keys; a palindrome is one key.  A window is SOLID iff
+ * its count >= solid, else WEAK.
+ * For each record of L bases let n = L - k + 1.  n <= 0: the record is copied unchanged and counted as short.  Otherwise
+ * s[0..n-1] are the solid flags of the windows of the INPUT record, and a weak run is a maximal [a, b] with s = 0.  Each weak run
+ * is judged on its own, from the input record only.  With m = b - a + 1:
+ *   1. Shape.  whole read (a = 0 and b = n-1): skipped;  head run (a = 0, b < n-1): needs m <= k, then p = b;  tail run (a > 0,
+ *      b = n-1): needs m <= k, then p = a + k - 1;  interior run (a > 0, b < n-1): needs m = k, then p = b;  anything else is
+ *      skipped.  In every accepted case the windows that contain base p are exactly [a, b].
+ *   2. Candidates.  Each of the three bases c != read[p] is valid iff every window of [a, b] is solid once read[p] := c.
+ *   3. Decision.  Exactly one valid c: base p becomes c (corrected).  Two or three: ambiguous, nothing changes.  None: unresolved,
+ *      nothing changes.
+ * So: runs never share a window and a correction touches only its own run's windows — the result depends neither on order nor
+ * on scheduling; every window of a corrected run is solid in the output and all other windows are unchanged; correcting the
+ * output again with the same map and `solid` changes nothing; the output has the framing of the input byte for byte (the same
+ * length bytes, the same byte count, the padding bits of a record's last byte copied as they are): only the 2-bit fields of
+ * corrected bases differ.  The map is never changed.  A new or cleared map is an empty table: every window is weak, nothing is
+ * corrected, and its slots are not read.
+ * stats (may be NULL) receives GK_CORRECT_NSTATS values, indexed by the names below; runs = corrected + ambiguous + unresolved +
+ * skipped, always.
+ * Host form: ragged streams are fine; the framing is validated on the host first, as gk_map_count_reads validates it
+ * (GK_E_FORMAT, nothing written); the stream goes through the device in chunks; bin_out holds nbytes and may be bin_host.
+ * Device form: fixed stride 1 + ceil(read_len / 4), shorter records inside the stride are fine; dev_out may be dev_records itself
+ * (in place), any other overlap is GK_E_INVALID; a length byte above read_len is clamped, never followed, and the call then
+ * fails with GK_E_FORMAT (the output is unspecified).
+ * GK_E_INVALID: solid = 0, a NULL handle, NULL buffers with nreads > 0. */
+enum {
+    GK_CORRECT_READS = 0,      /* records */
+    GK_CORRECT_SHORT = 1,      /* records shorter than k */
+    GK_CORRECT_WINDOWS = 2,    /* windows */
+    GK_CORRECT_WEAK = 3,       /* weak windows of the input */
+    GK_CORRECT_RUNS = 4,       /* weak runs */
+    GK_CORRECT_CORRECTED = 5,  /* runs with exactly one valid replacement: bases changed */
+    GK_CORRECT_AMBIGUOUS = 6,  /* runs with two or three */
+    GK_CORRECT_UNRESOLVED = 7, /* runs with none */
+    GK_CORRECT_SKIPPED = 8,    /* runs skipped for their shape */
+    GK_CORRECT_CHANGED = 9,    /* records with at least one base changed */
+    GK_CORRECT_NSTATS = 10
+};
+int gk_reads_correct(gk_map *counts, const uint8_t *bin_host, size_t nbytes, uint64_t nreads, uint32_t solid,
+                     uint8_t *bin_out, uint64_t *stats);
+int gk_reads_correct_dev(gk_map *counts, const void *dev_records, uint64_t nreads, int read_len, uint32_t solid,
+                         void *dev_out, uint64_t *stats);
+
 /* DNAMap.update(key, 1, _+1) for a batch of keys taken verbatim (no canonicalisation):
  * PartitionedDNAMap's owner-side insert (Messages.update1, ArrayDNAMap.scala:39).  Keys are
  * W = 1 (k<=32) or 2 (k>32) uint64 each.  The map notices when a verbatim key is not the hash-rule orientation of
