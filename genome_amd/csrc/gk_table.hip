@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "gk_internal.h"
+#include "gk_scan.h"
 #include "gk_tile.h"
 
 using namespace gk;
@@ -350,30 +351,38 @@ __device__ __forceinline__ u32 block_scan_flag(bool flag, u32 *total, u32 *lds4)
     return base + wprefix;
 }
 
-// Container.iterator (ArrayDNAMap.scala:175-178): compact every live (key, count) to dense arrays.
-// One atomic per 256-slot group reserves the output range; order within a group is slot order.
+// Container.iterator (ArrayDNAMap.scala:175-178): compact every live (key, count) to dense arrays IN ASCENDING SLOT INDEX (what
+// gk_map_export promises).  Two passes over the key words: k_export_count leaves the live slots of every 256-slot group, a scan
+// (gk_scan.h) turns them into each group's first output index, k_export writes the group there in slot order.
+template <class S>
+__global__ __launch_bounds__(BLOCK) void k_export_count(const S *__restrict__ slots, u64 ncap, u32 *__restrict__ gcnt) {
+    __shared__ u32 lds4[BLOCK / 64];
+    const u64 ngroups = (ncap + BLOCK - 1) / BLOCK;
+    for (u64 g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const u64 i = g * BLOCK + threadIdx.x;
+        u32 tot;
+        (void)block_scan_flag(i < ncap && slot_live(&slots[i]), &tot, lds4);
+        if (threadIdx.x == 0) gcnt[g] = tot;
+    }
+}
 template <int W, class S>
 __global__ __launch_bounds__(BLOCK) void k_export(const S *__restrict__ slots, u64 ncap, u32 tagged, u64 *lo, u64 *hi, i32 *cnt,
-                                                  unsigned long long *cursor) {
+                                                  const unsigned long long *__restrict__ goff, u64 out_cap) {
     __shared__ u32 lds4[BLOCK / 64];
-    __shared__ unsigned long long s_base;
     const u64 ngroups = (ncap + BLOCK - 1) / BLOCK;
     for (u64 g = blockIdx.x; g < ngroups; g += gridDim.x) {
         u64 i = g * BLOCK + threadIdx.x;
         bool live = i < ncap && slot_live(&slots[i]);
         u32 tot;
         u32 pos = block_scan_flag(live, &tot, lds4);
-        if (threadIdx.x == 0 && tot) s_base = atomicAdd(cursor, (unsigned long long)tot);
-        __syncthreads();
-        if (live) {
+        const u64 o = goff[g] + pos;
+        if (live && o < out_cap) {          // (o >= out_cap: the table holds more live slots than its size says; the host reports it)
             Kmer<W> key = slot_key(slots, i, tagged);
-            u64 o = s_base + pos;
             lo[o] = key.lo;
             if constexpr (W == 2) { if (hi) hi[o] = key.hi; }
             else { if (hi) hi[o] = 0; }
             cnt[o] = (i32)slot_count(&slots[i]);
         }
-        __syncthreads();
     }
 }
 
@@ -1935,17 +1944,24 @@ int gk_map_export(gk_map *m, uint64_t *lo, uint64_t *hi, int32_t *counts, uint64
     if (m->size == 0) return GK_OK;
     if (!lo || !counts || (m->W == 2 && !hi)) return fail(ctx, GK_E_INVALID, "null export buffer");
     const u64 cnt = m->size;
+    const u64 ngroups = (m->capacity + BLOCK - 1) / BLOCK;
     const size_t b8 = al256(cnt * 8), b4 = al256(cnt * 4);
-    char *base = (char *)map_scratch(m, 2 * b8 + b4 + 256);
+    const size_t bg = al256(ngroups * 4), bo = al256((ngroups + 1) * 8), bs = al256((ngroups / SCAN_CHUNK + 2) * 8);
+    char *base = (char *)map_scratch(m, 2 * b8 + b4 + bg + bo + bs);
     if (!base) return GK_E_CAPACITY;
     u64 *d_lo = (u64 *)base, *d_hi = (u64 *)(base + b8);
     i32 *d_cnt = (i32 *)(base + 2 * b8);
-    unsigned long long *d_cursor = (unsigned long long *)(base + 2 * b8 + b4);
-    GK_HIP(ctx, hipMemsetAsync(d_cursor, 0, 8, ctx->stream));
+    u32 *d_gcnt = (u32 *)(base + 2 * b8 + b4);
+    unsigned long long *d_goff = (unsigned long long *)(base + 2 * b8 + b4 + bg);
+    u64 *d_sums = (u64 *)(base + 2 * b8 + b4 + bg + bo);
     int grid = grid_for(ctx, m->capacity, BLOCK);
-    GK_BY_SLOT(m, hipLaunchKernelGGL((k_export<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, (const S *)m->slots, m->capacity, m->k == 64 ? 1u : 0u, d_lo, d_hi, d_cnt, d_cursor));
+    GK_BY_SLOT(m, hipLaunchKernelGGL((k_export_count<S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, (const S *)m->slots, m->capacity, d_gcnt));
+    GK_HIP(ctx, hipGetLastError());
+    GK_HIP(ctx, scan_counts(ctx, d_gcnt, ngroups, d_goff, d_sums));
+    GK_BY_SLOT(m, hipLaunchKernelGGL((k_export<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, (const S *)m->slots, m->capacity, m->k == 64 ? 1u : 0u, d_lo, d_hi, d_cnt, d_goff, cnt));
+    GK_HIP(ctx, hipGetLastError());
     unsigned long long written = 0;
-    GK_HIP(ctx, read_back(ctx, {{&written, d_cursor, 8}, {lo, d_lo, cnt * 8}, {hi, d_hi, cnt * 8}, {counts, d_cnt, cnt * 4}}));
+    GK_HIP(ctx, read_back(ctx, {{&written, d_goff + ngroups, 8}, {lo, d_lo, cnt * 8}, {hi, d_hi, cnt * 8}, {counts, d_cnt, cnt * 4}}));
     if (written != cnt) return fail(ctx, GK_E_STATE, "export wrote " + std::to_string(written) + " entries, size says " + std::to_string(cnt));
     return GK_OK;
 }

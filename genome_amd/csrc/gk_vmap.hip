@@ -212,6 +212,7 @@ int vm_sync(gk_vmap *m) {
 }
 
 // room for `extra` more entries (every putNew takes a slot; load kept under 0.7, sized for 0.5: multimap runs are longer than a set's)
+// (tests/test_adversarial_keys_gpu.py _vmap_slots replays this rule and gk_vmap_create's to know the table's slots: change them together)
 int vm_reserve(gk_vmap *m, u64 extra) {
     const double max_load = m->k == 64 ? 0.5 : 0.7, target = m->k == 64 ? 0.35 : 0.5;
     if ((double)(m->size + extra) <= max_load * (double)m->capacity) return GK_OK;

@@ -240,8 +240,11 @@ int gk_map_filter_lt(gk_map *m, int32_t rounds);
 int gk_map_get_batch(gk_map *m, const uint64_t *lo, const uint64_t *hi, uint64_t n, int32_t *counts_out, uint8_t *found_out);
 
 /* Container.iterator / mapReduce(identity) (ArrayDNAMap.scala:175-178, 234-241): every live
- * (key, count) in slot order (unspecified; callers sort for comparison).  If cap < live count the
- * call fails with GK_E_CAPACITY and *n holds the required size. */
+ * (key, count) in ascending slot index.  Which slot a key sits in is the table's business (its geometry, its insert
+ * history), so callers sort for comparison; what the order does promise is that two exports of an unchanged table agree and
+ * that keys come out segment by segment and, inside a segment, slot by slot: a probe chain in chain order, except that the
+ * part of it that wrapped past the segment's end comes first (tests/test_adversarial_keys_gpu.py reads positions off this).
+ * If cap < live count the call fails with GK_E_CAPACITY and *n holds the required size. */
 int gk_map_export(gk_map *m, uint64_t *lo, uint64_t *hi, int32_t *counts, uint64_t cap, uint64_t *n);
 
 /* JSON counters: capacity, size, occurrences, grows, last kernel time ... (SURVEY.md §5 metrics), and which member of each
