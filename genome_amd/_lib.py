@@ -138,6 +138,8 @@ SIGNATURES = {
     "gk_graph_remove_edges_by_id": (C.c_int, [vp, u32p, C.c_uint64, u64p]),
     "gk_graph_edge_coverage": (C.c_int, [vp, vp, u32p, C.c_uint64, u64p, u64p, u32p, u32p, u64p]),
     "gk_graph_clip_tips": (C.c_int, [vp, vp, C.c_uint64, u64p]),
+    "gk_graph_edge_distance": (C.c_int, [vp, u32p, u32p, C.c_uint64, C.c_uint32, u32p]),
+    "gk_graph_pop_bubbles": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, u64p, u64p]),
     "gk_support_create": (C.c_int, [vp, C.POINTER(vp)]),
     "gk_support_destroy": (None, [vp]),
     "gk_support_size": (C.c_int, [vp, u64p, u64p, u64p]),

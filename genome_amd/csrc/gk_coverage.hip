@@ -3,7 +3,10 @@
 //
 // Reference: none.  Graph.buildGraph (S/data/graph/Graph.scala:269-382) drops the counts once `contains` has been answered, and
 // the reference has no tip removal.  The rules of the two entry points are this project's own and
-// stated in include/genome_amd.h; tests/tips_ref.py restates them.
+// stated in include/genome_amd.h; tests/tips_ref.py restates them.  So are the two that remove bubbles by the same numbers
+// (gk_graph_edge_distance: a thresholded, banded edit distance of two edges, one wave per pair; gk_graph_pop_bubbles: the weaker of
+// two similar parallel edges goes; restated in tests/bubbles_ref.py) — gk_graph_remove_bubbles, the reference's own unfinished
+// rule (Graph.scala:121-149), stays in gk_graph.hip as it is.
 //
 // Roofline: one independent random table probe per k-mer of every live edge (total edge length + live edges of them) and
 // nothing else of size: the random-load rate of HBM, as the unitig walk — whose probes depend on each other, these do not.
@@ -183,6 +186,123 @@ __global__ __launch_bounds__(BLOCK) void k_tip_apply(GraphView g, const uint8_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// bubbles (the rules: include/genome_amd.h, gk_graph_edge_distance and gk_graph_pop_bubbles)
+// ---------------------------------------------------------------------------------------------
+static constexpr u32 DIST_MAX_DIFF = 31;                 // a band of 2 * 31 + 1 = 63 diagonals: one wave, lane 63 the wall beside it
+static constexpr u32 DIST_INVALID = 0xffffffffu;
+
+// bases s .. s + 31 of a sequence of n bases as 32 2-bit codes; s may be negative and s + 32 may pass n: those read as 0, and no
+// byte outside the sequence is touched
+__device__ __forceinline__ u64 seq_chunk(const uint8_t *__restrict__ seq, i64 s, u64 n) {
+    const i64 lo = s > 0 ? s : 0, hi = s + 32 < (i64)n ? s + 32 : (i64)n;
+    return hi > lo ? pool_bits(seq, (u64)lo, (int)(hi - lo)) << (2 * (int)(lo - s)) : 0ull;
+}
+
+// min(Levenshtein(a, b), D + 1) by one wave, for |m - n| <= D <= 31; every lane of the wave must call it (the shuffles take all
+// 64) and every lane gets the answer.  Lane d owns diagonal o = d - D of the matrix: in row i the cell (i, i + o).  The rows
+// advance in lock-step:
+//   the diagonal neighbour (i-1, j-1) is the lane's own last value, the upper one (i-1, j) lane d + 1's last value, and the
+//   left one (i, j-1) lane d - 1's value of THIS row: cur[d] = min over e <= d of (t[e] + d - e), t = min(diagonal, upper) —
+//   a prefix minimum in log2(band) shuffle steps.
+// Every value is capped at D + 1, which is also what a cell outside the matrix or the band holds: an alignment of cost <= D
+// never leaves |i - j| <= D, so the cap changes no value <= D.  Row i reads base i - 1 of a (the same for every lane) and base
+// i - 1 + o of b; both come 32 at a time, at the same rows and the same bit position, so a substitution is one XOR.
+// The wave leaves as soon as a whole row is over D (the minimum of a row never falls).
+__device__ __forceinline__ u32 wave_banded_distance(const uint8_t *__restrict__ a, u64 m, const uint8_t *__restrict__ b, u64 n, u32 D) {
+    const u32 lane = threadIdx.x & 63u, cap = D + 1;
+    const i64 o = (i64)lane - (i64)D;
+    const bool band = lane <= 2 * D;
+    u32 cur = band && o >= 0 && (u64)o <= n ? (u32)o : cap;              // row 0 (o <= D < cap)
+    u64 abits = 0, bbits = 0;
+    for (u64 i = 1; i <= m; i++) {                                       // (uniform over the wave)
+        const u64 r = i - 1;
+        if ((r & 31) == 0) {
+            abits = pool_bits(a, r, (int)(m - r < 32 ? m - r : 32));
+            bbits = band ? seq_chunk(b, (i64)r + o, n) : 0ull;
+        }
+        const u32 sub = ((abits ^ bbits) >> (2 * (int)(r & 31)) & 3) != 0;
+        const u32 up = __shfl_down(cur, 1);                              // (lane 63 reads itself: it is never in the band)
+        const i64 j = (i64)i + o;
+        const bool cell = band && j >= 0 && (u64)j <= n;
+        u32 t = cell ? min(min(cur + sub, up + 1), cap) : cap;
+        for (u32 s = 1; s <= 2 * D; s <<= 1) {
+            const u32 left = __shfl_up(t, s);
+            if (lane >= s) t = min(t, left + s);
+        }
+        cur = cell ? t : cap;
+        if (!__any(cur <= D)) return cap;
+    }
+    return __shfl(cur, (int)((i64)D + (i64)n - (i64)m));
+}
+
+// one wave per pair of edge ids
+__global__ __launch_bounds__(BLOCK) void k_edge_distance(GraphView g, const u32 *__restrict__ e1, const u32 *__restrict__ e2, u64 n, u32 D, u32 *__restrict__ dist) {
+    const u64 waves = (u64)gridDim.x * (BLOCK / 64);
+    for (u64 p = (u64)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); p < n; p += waves) {      // (uniform over the wave)
+        const u32 e = __builtin_amdgcn_readfirstlane(e1[p]), f = __builtin_amdgcn_readfirstlane(e2[p]);
+        u32 d;
+        if (e >= g.n_edges || f >= g.n_edges || !g.e_alive[e] || !g.e_alive[f]) d = DIST_INVALID;
+        else if (e == f) d = 0;
+        else {
+            const u64 m = g.e_len[e], l = g.e_len[f];
+            d = (m > l ? m - l : l - m) > D ? D + 1 : wave_banded_distance(g.pool + g.e_off[e], m, g.pool + g.e_off[f], l, D);
+        }
+        if ((threadIdx.x & 63) == 0) dist[p] = d;
+    }
+}
+
+// the unordered pairs among the live out-edges of node u that share their end node, both of at most max_len bases: 6 at most
+template <class F> __device__ __forceinline__ u32 parallel_pairs(const GraphView &g, u64 u, u64 max_len, F &&emit) {
+    u32 ids[4];
+    for (int b = 0; b < 4; b++) {
+        const u32 f = g.out_edge[u * 4 + b];
+        ids[b] = f != NONE && g.e_alive[f] && g.e_len[f] <= max_len ? f : NONE;
+    }
+    u32 cnt = 0;
+    for (int a = 0; a < 3; a++)
+        for (int b = a + 1; b < 4; b++)
+            if (ids[a] != NONE && ids[b] != NONE && g.e_end[ids[a]] == g.e_end[ids[b]]) emit(cnt++, ids[a], ids[b]);
+    return cnt;
+}
+// one lane per node: the number of its candidate pairs, then (with `off` the exclusive scan of those) the pairs themselves and
+// want[e] = 1 for their edges (an edge leaves one node: one lane writes its byte)
+__global__ __launch_bounds__(BLOCK) void k_bubble_count(GraphView g, u64 max_len, u32 *__restrict__ cnt) {
+    for (u64 u = (u64)blockIdx.x * BLOCK + threadIdx.x; u < g.n_nodes; u += (u64)gridDim.x * BLOCK)
+        cnt[u] = g.node_alive[u] && order_count(g.out_order[u]) >= 2 ? parallel_pairs(g, u, max_len, [](u32, u32, u32) {}) : 0u;
+}
+__global__ __launch_bounds__(BLOCK) void k_bubble_pairs(GraphView g, u64 max_len, const u32 *__restrict__ cnt, const unsigned long long *__restrict__ off,
+                                                        u32 *__restrict__ pe, u32 *__restrict__ pf, uint8_t *__restrict__ want) {
+    for (u64 u = (u64)blockIdx.x * BLOCK + threadIdx.x; u < g.n_nodes; u += (u64)gridDim.x * BLOCK) {
+        if (!cnt[u]) continue;
+        const u64 at = off[u];
+        parallel_pairs(g, u, max_len, [&](u32 i, u32 e, u32 f) { pe[at + i] = e; pf[at + i] = f; want[e] = 1; want[f] = 1; });
+    }
+}
+// one lane per candidate pair, from the graph as it is (nothing is written but `mark`, zeroed before): the weaker edge of a pair
+// within D goes.  flags[0] = a candidate edge has a window the table does not hold; *compared += the pairs whose lengths let the
+// distance be computed.
+__global__ __launch_bounds__(BLOCK) void k_bubble_mark(GraphView g, EdgeCov cov, const u32 *__restrict__ pe, const u32 *__restrict__ pf, const u32 *__restrict__ dist,
+                                                       u64 npairs, u32 D, uint8_t *mark, u32 *flags, unsigned long long *compared) {
+    const u64 stride = (u64)gridDim.x * BLOCK;
+    for (u64 p0 = (u64)blockIdx.x * BLOCK; p0 < npairs; p0 += stride) {  // (uniform over the wave: every lane takes the ballot)
+        const u64 p = p0 + threadIdx.x;
+        bool within = false;
+        if (p < npairs) {
+            const u32 e = pe[p], f = pf[p];
+            if (cov.miss[e] | cov.miss[f]) flags[0] = 1u;
+            const u64 le = g.e_len[e], lf = g.e_len[f];
+            within = (le > lf ? le - lf : lf - le) <= D;
+            if (dist[p] <= D) {
+                if (cov_weaker(cov.sum[e], le + 1, cov.sum[f], lf + 1)) mark[e] = 1;
+                else if (cov_weaker(cov.sum[f], lf + 1, cov.sum[e], le + 1)) mark[f] = 1;
+            }
+        }
+        const unsigned long long votes = __ballot(within);
+        if ((threadIdx.x & 63) == 0 && votes) atomicAdd(compared, (unsigned long long)__popcll(votes));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 static int check_counts(const gk_graph *g, gk_map *counts, const char *who) {
@@ -287,6 +407,79 @@ int gk_graph_clip_tips(gk_graph *g, gk_map *counts, uint64_t max_len, uint64_t *
     GK_HIP(ctx, read_back(ctx, {{&h_flags, d_flags, 4}, {&h_removed, d_removed, 8}}));
     if (h_flags) return fail(ctx, GK_E_STATE, "gk_graph_clip_tips: the map does not hold every k-mer of the graph (not the table it was built from?)");
     if (removed_edges) *removed_edges = h_removed;
+    return graph_refresh_counts(g);
+}
+
+int gk_graph_edge_distance(gk_graph *g, const uint32_t *e1, const uint32_t *e2, uint64_t n, uint32_t max_diff, uint32_t *dist) {
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    if (max_diff > DIST_MAX_DIFF) return fail(ctx, GK_E_INVALID, "gk_graph_edge_distance: max_diff is at most 31 (a band of 63 diagonals, one wave)");
+    if (n == 0) return GK_OK;
+    if (!e1 || !e2) return fail(ctx, GK_E_INVALID, "gk_graph_edge_distance: an id array is NULL");
+    DevScratch tmp(ctx);
+    u32 *d_e1 = nullptr, *d_e2 = nullptr, *d_dist = nullptr;
+    hipError_t e = tmp.get(&d_e1, n);
+    if (e == hipSuccess) e = tmp.get(&d_e2, n);
+    if (e == hipSuccess) e = tmp.get(&d_dist, n);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_e1, e1, n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_e2, e2, n * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edge_distance");
+    hipLaunchKernelGGL(k_edge_distance, dim3(ggrid(ctx, n * 64)), dim3(BLOCK), 0, ctx->stream, g->v, d_e1, d_e2, (u64)n, (u32)max_diff, d_dist);
+    GK_HIP(ctx, read_back(ctx, {{dist, d_dist, (size_t)n * 4}}));
+    return GK_OK;
+}
+
+int gk_graph_pop_bubbles(gk_graph *g, gk_map *counts, uint64_t max_len, uint32_t max_diff, uint64_t *removed_edges, uint64_t *pairs_compared) {
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    if (int rc = check_counts(g, counts, "gk_graph_pop_bubbles")) return rc;
+    if (max_diff > DIST_MAX_DIFF) return fail(ctx, GK_E_INVALID, "gk_graph_pop_bubbles: max_diff is at most 31 (a band of 63 diagonals, one wave)");
+    if (removed_edges) *removed_edges = 0;
+    if (pairs_compared) *pairs_compared = 0;
+    const GraphView &v = g->v;
+    if (max_len == 0 || v.n_edges == 0 || v.n_nodes == 0) return GK_OK;
+    DevScratch tmp(ctx);
+    // the candidate pairs: counted per node, scanned, written
+    unsigned long long *d_off = nullptr, *d_removed = nullptr, *d_compared = nullptr, h_pairs = 0, h_removed = 0, h_compared = 0;
+    u32 *d_cnt = nullptr, *d_pe = nullptr, *d_pf = nullptr, *d_dist = nullptr, *d_flags = nullptr, h_flags = 0;
+    u64 *d_sums = nullptr;
+    uint8_t *d_want = nullptr, *d_mark = nullptr;
+    hipError_t e = tmp.get(&d_cnt, v.n_nodes);
+    if (e == hipSuccess) e = tmp.get(&d_off, v.n_nodes + 1);
+    if (e == hipSuccess) e = tmp.get(&d_sums, v.n_nodes / SCAN_CHUNK + 2);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_pop_bubbles: candidate counts");
+    const int ngrid = ggrid(ctx, v.n_nodes);
+    hipLaunchKernelGGL(k_bubble_count, dim3(ngrid), dim3(BLOCK), 0, ctx->stream, v, (u64)max_len, d_cnt);
+    GK_HIP(ctx, scan_counts(ctx, d_cnt, v.n_nodes, d_off, d_sums));
+    GK_HIP(ctx, read_back(ctx, &h_pairs, d_off + v.n_nodes));
+    if (h_pairs == 0) return GK_OK;
+    e = tmp.get(&d_pe, h_pairs);
+    if (e == hipSuccess) e = tmp.get(&d_pf, h_pairs);
+    if (e == hipSuccess) e = tmp.get(&d_dist, h_pairs);
+    if (e == hipSuccess) e = tmp.get(&d_want, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&d_mark, v.n_edges);
+    if (e == hipSuccess) e = tmp.get(&d_flags, 1);
+    if (e == hipSuccess) e = tmp.get(&d_removed, 1);
+    if (e == hipSuccess) e = tmp.get(&d_compared, 1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_want, 0, v.n_edges, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_mark, 0, v.n_edges, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 4, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, 8, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_compared, 0, 8, ctx->stream);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_pop_bubbles: candidate pairs");
+    hipLaunchKernelGGL(k_bubble_pairs, dim3(ngrid), dim3(BLOCK), 0, ctx->stream, v, (u64)max_len, d_cnt, d_off, d_pe, d_pf, d_want);
+    // coverage of the edges in some bubble only, and the distance of every pair
+    EdgeCov cov{};
+    if (int rc = coverage_pass(g, counts, tmp, d_want, &cov)) return rc;
+    hipLaunchKernelGGL(k_edge_distance, dim3(ggrid(ctx, h_pairs * 64)), dim3(BLOCK), 0, ctx->stream, v, d_pe, d_pf, (u64)h_pairs, (u32)max_diff, d_dist);
+    // the decision is complete before anything is applied, and a map that is not this graph's leaves the graph as it was
+    hipLaunchKernelGGL(k_bubble_mark, dim3(ggrid(ctx, h_pairs)), dim3(BLOCK), 0, ctx->stream, v, cov, d_pe, d_pf, d_dist, (u64)h_pairs, (u32)max_diff, d_mark, d_flags,
+                       d_compared);
+    hipLaunchKernelGGL(k_tip_apply, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, d_mark, d_flags, d_removed);
+    GK_HIP(ctx, read_back(ctx, {{&h_flags, d_flags, 4}, {&h_removed, d_removed, 8}, {&h_compared, d_compared, 8}}));
+    if (h_flags) return fail(ctx, GK_E_STATE, "gk_graph_pop_bubbles: the map does not hold every k-mer of the candidate edges (not the table the graph was built from?)");
+    if (removed_edges) *removed_edges = h_removed;
+    if (pairs_compared) *pairs_compared = h_compared;
     return graph_refresh_counts(g);
 }
 

@@ -193,6 +193,25 @@ class HipGraph:
         L.check(L.lib().gk_graph_clip_tips(self.h, counts.h, 2 * self.k if max_len is None else int(max_len), C.byref(rm)), self.ctx.h)
         return rm.value
 
+    def edgeDistance(self, e1, e2, max_diff: int) -> np.ndarray:
+        """Per pair of edge ids min(Levenshtein distance of the two edges' sequences, max_diff + 1), as uint32; 0xffffffff where
+        an id is dead or out of range.  max_diff is at most 31 (GkError GK_E_INVALID beyond)."""
+        e1, e2 = np.ascontiguousarray(e1, np.uint32), np.ascontiguousarray(e2, np.uint32)
+        assert e1.shape == e2.shape and e1.ndim == 1
+        dist = np.zeros(len(e1), np.uint32)
+        L.check(L.lib().gk_graph_edge_distance(self.h, L.ptr(e1, C.c_uint32), L.ptr(e2, C.c_uint32), len(e1), int(max_diff), L.ptr(dist, C.c_uint32)), self.ctx.h)
+        return dist
+
+    def popBubbles(self, counts: HipDNAMap, max_len=None, max_diff=None):
+        """One round of bubble removal: of two parallel edges (same start and end node) of at most `max_len` bases (default 2k)
+        within edit distance `max_diff` (default 3, the reference's commented-out `maxerrors`), the one of strictly lower mean
+        coverage goes -> (edges removed, pairs compared).  Call simplifyGraph() next.  GkError GK_E_STATE if `counts` is not this
+        graph's table."""
+        rm, pairs = C.c_uint64(), C.c_uint64()
+        L.check(L.lib().gk_graph_pop_bubbles(self.h, counts.h, 2 * self.k if max_len is None else int(max_len), 3 if max_diff is None else int(max_diff),
+                                             C.byref(rm), C.byref(pairs)), self.ctx.h)
+        return rm.value, pairs.value
+
     def walkPairs(self, positions, support: "Support", bin_bytes, npairs: int, range_lo: int = 180, range_hi: int = 250):
         """:213-247: the pairs' positions through `positions` (getGraphMap of this graph as it is now), annotate, the bounded
         walks; the supported (edge, edge) pairs are counted in `support`."""

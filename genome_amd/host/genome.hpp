@@ -620,6 +620,22 @@ class Graph {
         check(gk_graph_clip_tips(h_, counts.handle(), maxLen ? maxLen : 2 * (uint64_t)k_, &removed), ctx_.handle());
         return removed;
     }
+    // Per pair of edge ids min(Levenshtein distance of the two edges' sequences, maxDiff + 1); 0xffffffff for a dead or
+    // out-of-range id; maxDiff <= 31 (include/genome_amd.h)
+    std::vector<uint32_t> edgeDistance(const std::vector<uint32_t> &e1, const std::vector<uint32_t> &e2, uint32_t maxDiff) const {
+        if (e1.size() != e2.size()) throw GkError(GK_E_INVALID, "edgeDistance: the id lists differ in length");
+        std::vector<uint32_t> dist(e1.size());
+        check(gk_graph_edge_distance(h_, e1.data(), e2.data(), e1.size(), maxDiff, dist.data()), ctx_.handle());
+        return dist;
+    }
+    // One round of bubble removal (include/genome_amd.h): of two parallel edges of at most maxLen bases (0 = the default, 2k)
+    // within edit distance maxDiff (default 3, the reference's commented-out maxerrors) the one of strictly lower mean coverage
+    // goes -> (edges removed, pairs compared); simplifyGraph() is the next call.  GK_E_STATE if `counts` is not this graph's.
+    std::pair<uint64_t, uint64_t> popBubbles(const DNAMap &counts, uint64_t maxLen = 0, uint32_t maxDiff = 3) {
+        uint64_t removed = 0, pairs = 0;
+        check(gk_graph_pop_bubbles(h_, counts.handle(), maxLen ? maxLen : 2 * (uint64_t)k_, maxDiff, &removed, &pairs), ctx_.handle());
+        return {removed, pairs};
+    }
     // CheckGraph.scala:37-41 over the live edges longer than longerThan: count, summed length, median (sorted[count / 2], the
     // reference's "N50"), the real N50, the maximum; computed on the device
     struct ContigStats { uint64_t count = 0, sum = 0, median = 0, n50 = 0, max = 0; };

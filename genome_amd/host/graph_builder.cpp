@@ -4,7 +4,8 @@
 // The reference logs its counters through akka Logging (:34-53); here they are one JSON object.
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
-//                 [--clip-tips [MAXLEN|auto]] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--correct N|auto]
+//                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI]
+//                 [--out prefix] [--save-graph PATH] [--correct N|auto]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
 //   --fastq converts the FASTQ file on the GPU first (Convert2bin, gk_fastq; --split N = its n, default 36) and takes the pair
 //   count from the conversion; the flow is then the same.  Not with --world (exit 2): convert2bin the file first.
@@ -18,6 +19,11 @@
 //   most; MAXLEN = the longest edge a tip may be (auto, the default: 2k).  The JSON gains "clip_tips":{"max_len","removed":[per round]}.
 //   --edge-coverage, with --out, writes <prefix>.coverage.txt: per live edge of the final graph, ascending ids, one line
 //   `edge id, len, kmers, sum, min, max` (gk_graph_edge_coverage).  Neither runs with --world (exit 2).
+//   --pop-bubbles removes the weaker of two similar parallel edges (gk_graph_pop_bubbles: this project's own rule; --simplify's
+//   removeBubbles is the reference's and stays) in the same rounds: clip if asked, pop if asked, then simplifyGraph, until a
+//   round removes nothing, 8 rounds at most.  MAXDIFF = the edit distance two branches may be apart (auto, the default: 3, at most
+//   31); --bubble-max-len N = the longest edge a branch may be (default 2k).  The JSON gains
+//   "pop_bubbles":{"max_len","max_diff","removed":[per round],"pairs":[per round]}.  Not with --world (exit 2).
 //   --correct N|auto corrects the reads before they are counted (gk_reads_correct: this project's own rule, the reference has none):
 //   count, correct the stream in host memory against that count (solid = N, or the valley of its spectrum; 3 when it has none),
 //   then count the corrected stream and go on as without the flag — --rounds auto sees the second spectrum, and --walk-pairs walks
@@ -86,7 +92,8 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--clip-tips [MAXLEN|auto]] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] [--correct N|auto] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] "
+                             "[--correct N|auto] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string infile = argv[1];
@@ -100,6 +107,9 @@ int main(int argc, char **argv) {
     bool retain = true, simplify = false;
     bool clipTips = false, edgeCoverage = false;
     uint64_t tipMaxLen = 0;                       // 0 = auto: 2k
+    bool popBubbles = false;
+    uint32_t bubbleMaxDiff = 3;                   // auto: the reference's commented-out maxerrors (Graph.scala:121-123)
+    uint64_t bubbleMaxLen = 0;                    // 0 = auto: 2k
     bool correct = false;                         // --correct
     uint32_t solid = 0;                           // 0 = auto: the valley of the first count's spectrum
     int walkCutoff = -1, walkLo = 180, walkHi = 250;
@@ -120,6 +130,12 @@ int main(int argc, char **argv) {
             if (i + 1 < argc && !std::strcmp(argv[i + 1], "auto")) i++;
             else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') tipMaxLen = std::stoull(argv[++i]);
         }
+        else if (!std::strcmp(argv[i], "--pop-bubbles")) {
+            popBubbles = true;
+            if (i + 1 < argc && !std::strcmp(argv[i + 1], "auto")) i++;
+            else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') bubbleMaxDiff = (uint32_t)std::stoul(argv[++i]);
+        }
+        else if (!std::strcmp(argv[i], "--bubble-max-len") && i + 1 < argc) bubbleMaxLen = std::stoull(argv[++i]);
         else if (!std::strcmp(argv[i], "--edge-coverage")) edgeCoverage = true;
         else if (!std::strcmp(argv[i], "--correct") && i + 1 < argc) {
             correct = true;
@@ -150,7 +166,16 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--correct runs on one GPU only (not with --world)\n");
         return 2;
     }
+    if (world && popBubbles) {
+        std::fprintf(stderr, "--pop-bubbles runs on one GPU only (not with --world)\n");
+        return 2;
+    }
+    if (popBubbles && bubbleMaxDiff > 31) {
+        std::fprintf(stderr, "--pop-bubbles MAXDIFF is at most 31\n");
+        return 2;
+    }
     if (clipTips && !tipMaxLen) tipMaxLen = 2 * (uint64_t)k;
+    if (popBubbles && !bubbleMaxLen) bubbleMaxLen = 2 * (uint64_t)k;
     try {
         if (fastq.empty()) {
             std::ifstream f(infile, std::ios::binary);
@@ -210,11 +235,18 @@ int main(int argc, char **argv) {
         auto [hist, hist2] = graph.componentHistograms();
         uint64_t kept = nodes, comps = 0;
         if (retain) std::tie(kept, comps) = graph.retainLargestComponent();                              // :52-54
-        // --clip-tips: clip, then simplifyGraph, until a round removes nothing (the counts are the table the graph was built from)
-        std::vector<uint64_t> tipsRemoved;
-        while (clipTips && tipsRemoved.size() < 8) {
-            tipsRemoved.push_back(graph.clipTips(*kmersFreq, tipMaxLen));
-            if (!tipsRemoved.back()) break;
+        // --clip-tips / --pop-bubbles: clip, pop, then simplifyGraph, until a round removes nothing (the counts are the table the
+        // graph was built from)
+        std::vector<uint64_t> tipsRemoved, bubblesRemoved, bubblePairs;
+        for (int round = 0; (clipTips || popBubbles) && round < 8; round++) {
+            uint64_t gone = 0;
+            if (clipTips) { tipsRemoved.push_back(graph.clipTips(*kmersFreq, tipMaxLen)); gone += tipsRemoved.back(); }
+            if (popBubbles) {
+                const auto [removed, pairs] = graph.popBubbles(*kmersFreq, bubbleMaxLen, bubbleMaxDiff);
+                bubblesRemoved.push_back(removed); bubblePairs.push_back(pairs);
+                gone += removed;
+            }
+            if (!gone) break;
             graph.simplifyGraph();
         }
         // --simplify = GraphSimplifier.scala:317-318, applied to the graph GraphBuilder hands over (i.e. after retain)
@@ -253,6 +285,13 @@ int main(int argc, char **argv) {
         if (clipTips) {
             std::printf("\"clip_tips\":{\"max_len\":%llu,\"removed\":[", (unsigned long long)tipMaxLen);
             for (size_t i = 0; i < tipsRemoved.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)tipsRemoved[i]);
+            std::printf("]},");
+        }
+        if (popBubbles) {
+            std::printf("\"pop_bubbles\":{\"max_len\":%llu,\"max_diff\":%u,\"removed\":[", (unsigned long long)bubbleMaxLen, bubbleMaxDiff);
+            for (size_t i = 0; i < bubblesRemoved.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)bubblesRemoved[i]);
+            std::printf("],\"pairs\":[");
+            for (size_t i = 0; i < bubblePairs.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)bubblePairs[i]);
             std::printf("]},");
         }
         if (walkCutoff >= 0)

@@ -508,6 +508,35 @@ int gk_graph_edge_coverage(gk_graph *g, gk_map *counts, const uint32_t *edge_ids
  * next simplifyGraph removes and merges.  *removed_edges = edges removed.  max_len == 0 removes nothing.  If any window of any
  * live edge is missing from `counts` the map is not this graph's: GK_E_STATE, and the graph is untouched.  Handles as above. */
 int gk_graph_clip_tips(gk_graph *g, gk_map *counts, uint64_t max_len, uint64_t *removed_edges);
+/* Distance.  dist[i] = min(Levenshtein(seq(e1[i]), seq(e2[i])), max_diff + 1): substitution, insertion and deletion cost 1
+ * each, and seq is the edge's own bases, the ones after the start k-mer (gk_graph_export_edges' sequence).  Exact within the
+ * band: an alignment of cost <= max_diff never leaves |i - j| <= max_diff, so nothing else is looked at; lengths that differ by
+ * more than max_diff give max_diff + 1 without any comparison.  e1[i] == e2[i] (live) gives 0; a dead or out-of-range id on either
+ * side gives 0xffffffff.  max_diff > 31: GK_E_INVALID (a band of 2 * max_diff + 1 <= 63 diagonals is one wave of the device).
+ * n == 0 is GK_OK.  The graph is not changed.
+ * Strand symmetry rests on this: two edges with the same start node share the prefix start.seq of their paths start.seq ++ seq,
+ * two with the same end node the suffix end.seq; the Levenshtein distance does not change when a common prefix or suffix is
+ * stripped, nor when both strings are reversed and complemented.  So for parallel edges the distance of the sequences IS the
+ * distance of the paths, and the distance of their reverse-complement twins' sequences. */
+int gk_graph_edge_distance(gk_graph *g, const uint32_t *e1, const uint32_t *e2, uint64_t n, uint32_t max_diff, uint32_t *dist);
+/* Bubbles.  One round, decided entirely from the graph's state at entry and then applied at once, as the tips are.  Two live
+ * edges are PARALLEL when they have the same start node and the same end node, by node id (the copies a node split leaves are
+ * different nodes; the self-loops at one node are parallel to each other).  A live edge e is removed iff some other live edge f
+ *   is parallel to e, and len_e <= max_len and len_f <= max_len, and distance(e, f) <= max_diff (as above), and
+ *   e is STRICTLY below f in mean coverage: sum_e * kmers_f < sum_f * kmers_e, the 128-bit comparison of the tips over the same
+ *   len + 1 windows.
+ * So: ties remove nothing; the strongest edge of any group of similar parallel edges always survives; with e < f < g in coverage,
+ * d(e,f) <= max_diff, d(f,g) <= max_diff and d(e,g) > max_diff, e and f both go; two edges that are each other's twins tie and
+ * stay; the twins of a parallel pair are a parallel pair with the same coverages and the same distance, so a strand-closed edge
+ * set stays strand-closed.  Removal is MapGraph.removeEdge (:191-195); nodes stay for the caller's next simplifyGraph.  max_len
+ * == 0 removes nothing, and neither does max_diff == 0 (the out-edges of one node differ in their first base: their distance is
+ * >= 1).  *removed_edges = edges removed.  *pairs_compared = the unordered pairs of live parallel edges within max_len whose
+ * distance was computed: a pair whose lengths differ by more than max_diff does not count.  max_diff > 31: GK_E_INVALID.
+ * Coverage is computed for the CANDIDATE edges only: those with a parallel edge, both within max_len.  If a window of a candidate
+ * edge is missing from `counts` the map is not this graph's: GK_E_STATE, and the graph is untouched.  Handles as above.
+ * gk_graph_remove_bubbles — the reference's rule: lengths within a fifth, no sequences, no coverage — is a different entry
+ * point and unchanged. */
+int gk_graph_pop_bubbles(gk_graph *g, gk_map *counts, uint64_t max_len, uint32_t max_diff, uint64_t *removed_edges, uint64_t *pairs_compared);
 
 /* ---- the graph file: MapGraph.write (Graph.scala:232-261) / Graph(file) (:384-390) --------------------------------------
  * The stage boundary between GraphBuilder (GraphBuilder.scala:55-56) and GraphSimplifier (GraphSimplifier.scala:152-153).
