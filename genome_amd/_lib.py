@@ -198,6 +198,7 @@ TEST_SIGNATURES = {
     "gk_ctx_set_option": (C.c_int, [vp, C.c_char_p, C.c_int64]),
     "gk_dist_create_loopback": (C.c_int, [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]),
     "gk_test_support_last_walk": (C.c_int, [vp, u64p, u64p]),
+    "gk_test_grid_cap_uses": (C.c_int, [vp, u64p]),
 }
 TEST_LIB_PATH = os.path.join(_HERE, "libgenome_amd_test.so")
 

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(BLOCK) void k_correct_reads(Table<W, S> t, int k, u
 static int correct_launch(gk_map *counts, const ReadSrc &src, uint8_t *d_out, u32 solid, u32 *d_bad, unsigned long long *d_stats) {
     gk_ctx *ctx = counts->ctx;
     const u64 ntiles = (src.nreads + TILE_READS - 1) / TILE_READS;
-    const int grid = (int)std::min<u64>(ntiles, (u64)ctx->cu_count * 8);
+    const int grid = (int)std::min<u64>(ntiles, grid_cap(ctx));
     const WindowLimits lim{src.max_len, d_bad};
     // a new or cleared map is an empty table whose slots hold void bytes: every window is weak, and the slots are not read
     const u32 empty = counts->pending_clear ? 1u : 0u;

@@ -322,7 +322,7 @@ static int coverage_pass(gk_graph *g, gk_map *counts, DevScratch &tmp, const uin
     if (e == hipSuccess) e = tmp.get(&cov->miss, v.n_edges);
     if (e != hipSuccess) return hip_fail(ctx, e, "edge coverage: per-edge results");
     if (v.n_edges == 0) return GK_OK;
-    const int long_grid = (int)std::min<u64>(v.n_edges, (u64)ctx->cu_count * 8);
+    const int long_grid = (int)std::min<u64>(v.n_edges, grid_cap(ctx));
     GK_BY_SLOT(counts, {
         const Table<W, S> t{reinterpret_cast<S *>(counts->slots), counts->nb2, counts->lnb1, counts->k == 64 ? 1u : 0u, counts->dirty ? 1u : 0u};
         hipLaunchKernelGGL((k_cov_short<W, S>), dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, t, want, *cov);

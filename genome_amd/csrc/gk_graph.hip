@@ -1563,7 +1563,7 @@ __global__ __launch_bounds__(BLOCK) void k_contig_hist(GraphView g, u64 longer_t
 int ggrid(const gk_ctx *ctx, u64 items) {
     u64 blocks = (items + BLOCK - 1) / BLOCK;
     if (blocks < 1) blocks = 1;
-    return (int)std::min<u64>(blocks, (u64)ctx->cu_count * 8);
+    return (int)std::min<u64>(blocks, grid_cap(ctx));
 }
 
 template <class T> static hipError_t dev_grow(gk_ctx *ctx, T **p, u64 old_n, u64 new_n, hipStream_t st) {
@@ -1789,9 +1789,9 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
             if (e == hipSuccess) e = tmp.get(&st, nstates);
             if (e == hipSuccess) e = hipMemsetAsync(st, 0xff, std::max<u64>(nstates, 1) * 8, ctx->stream);         // PJ_UNREG
             if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: pointer-jumping arrays");
-            hipLaunchKernelGGL((k_rank_masks<W, TT>), dim3((int)std::min<u64>(nchunks, (u64)ctx->cu_count * 8)), dim3(BLOCK), 0, ctx->stream, t, rb, nblk, chunk_tot, nchunks);
+            hipLaunchKernelGGL((k_rank_masks<W, TT>), dim3((int)std::min<u64>(nchunks, grid_cap(ctx))), dim3(BLOCK), 0, ctx->stream, t, rb, nblk, chunk_tot, nchunks);
             hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, ctx->stream, chunk_tot, chunk_base, nchunks);
-            hipLaunchKernelGGL(k_rank_fill, dim3((int)std::min<u64>(nchunks, (u64)ctx->cu_count * 8)), dim3(RANK_CHUNK), 0, ctx->stream, rb, nblk, chunk_base, nchunks);
+            hipLaunchKernelGGL(k_rank_fill, dim3((int)std::min<u64>(nchunks, grid_cap(ctx))), dim3(RANK_CHUNK), 0, ctx->stream, rb, nblk, chunk_base, nchunks);
             unsigned long long ranked = 0;
             if ((e = read_back(ctx, &ranked, chunk_base + nchunks)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: slot ranks");
             if (ranked != m->size) return fail(ctx, GK_E_STATE, "live slots (" + std::to_string(ranked) + ") differ from the map's size (" + std::to_string(m->size) + ")");
@@ -1822,7 +1822,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
             else {
                 e = tmp.get(&stage, 2 * nE);
                 if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: edge staging");
-                const int gq = (int)std::min<u64>((nE + 4 * BLOCK - 1) / (4 * BLOCK), (u64)ctx->cu_count * 8);
+                const int gq = (int)std::min<u64>((nE + 4 * BLOCK - 1) / (4 * BLOCK), grid_cap(ctx));
                 hipLaunchKernelGGL((k_walk_q<W, TT>), dim3(std::max(gq, 1)), dim3(BLOCK), 0, ctx->stream, t, k, g->v, tcap + 1, &d_cnt[7], stage, &d_cnt[6], d_err);
                 hipLaunchKernelGGL(k_place_edges, dim3(ggrid(ctx, nE / 8 + 1)), dim3(BLOCK), 0, ctx->stream, g->v, stage, &d_cnt[4]);
             }
@@ -2463,7 +2463,7 @@ int gk_graph_position_map(gk_graph *g, gk_vmap *vm, uint64_t *entries) {
     if (v.n_edges) {
         GK_BY_W(g->W,
             hipLaunchKernelGGL(k_pos_fill<W>, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val);
-            hipLaunchKernelGGL(k_pos_fill_long<W>, dim3((int)std::min<u64>(v.n_edges, (u64)ctx->cu_count * 8)), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val));
+            hipLaunchKernelGGL(k_pos_fill_long<W>, dim3((int)std::min<u64>(v.n_edges, grid_cap(ctx))), dim3(BLOCK), 0, ctx->stream, v, g->k, first, g->live_nodes, lo, hi, val));
     }
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: fill");

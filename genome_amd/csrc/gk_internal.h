@@ -80,7 +80,16 @@ struct gk_ctx {
     std::string err;
     int hook_dist_fail_reduce = 0;   // test hook: this context's next gk_dist_reduce_support fails its owner merge, after the records have been exchanged
     float graph_io_ms[4] = {0, 0, 0, 0};   // the last gk_graph_save / gk_graph_load on this context: file I/O, copies, kernels, whole call
+    int hook_max_grid = 0;           // test hook: the grid-stride launches of the graph phase, the value maps, the spectrum and the read correction get at
+                                     // most this many workgroups (0: cu_count * 8), so that a small input makes every workgroup take several trips
+    mutable uint64_t hook_max_grid_uses = 0;   // ... and how many launches were sized under it (gk_test_grid_cap_uses: the switch's echo)
 };
+// most workgroups of a grid-stride launch: 8 resident 256-thread workgroups per CU, or what the test hook says
+inline uint64_t grid_cap(const gk_ctx *ctx) {
+    if (ctx->hook_max_grid <= 0) return (uint64_t)ctx->cu_count * 8;
+    ctx->hook_max_grid_uses++;
+    return (uint64_t)ctx->hook_max_grid;
+}
 
 namespace gk {
 // A stream of `.bin` records resident in HBM (PairedEndData.scala:20-36): fixed stride (off == nullptr) or an offset

@@ -1139,7 +1139,7 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
     const u32 ov_cap = (u32)std::min<u64>(norient, 1u << 22);
     GK_HIP(ctx, tmp.get(&d_ov, ov_cap));
     if (!host_only) {
-        const int grid = (int)std::min<u64>((norient + BLOCK / 64 - 1) / (BLOCK / 64), (u64)ctx->cu_count * 16);
+        const int grid = (int)std::min<u64>((norient + BLOCK / 64 - 1) / (BLOCK / 64), 2 * grid_cap(ctx));
         hipLaunchKernelGGL(k_walk_pairs, dim3(std::max(grid, 1)), dim3(BLOCK), 0, ctx->stream, v, d_in_off, d_in_list, d_off, d_vals, norient,
                            ctx->hook_pairs_small_sets > 0 ? WalkArgs{k, range_lo, range_hi, 6u, 10u, 3u}       // (test: most walks outgrow their sets -> host walker)
                                                           : WalkArgs{k, range_lo, range_hi, W_RMAX, W_QCAP, W_PMAX},

@@ -86,7 +86,7 @@ int gk_map_spectrum(gk_map *m, uint64_t *hist, uint32_t bins, uint64_t *distinct
         GK_HIP(ctx, hipMemsetAsync(d, 0, ((size_t)bins + 3) * 8, ctx->stream));
         const u64 per_block = (u64)BLOCK * SPEC_UNROLL;
         u64 blocks = (m->capacity + per_block - 1) / per_block;
-        const u64 cap_blocks = (u64)ctx->cu_count * 8;   // grid-stride; the LDS histogram lets five be resident per CU
+        const u64 cap_blocks = grid_cap(ctx);             // grid-stride; the LDS histogram lets five be resident per CU
         const int grid = (int)(blocks < 1 ? 1 : blocks < cap_blocks ? blocks : cap_blocks);
         GK_BY_SLOT(m, hipLaunchKernelGGL((k_spectrum<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, (const S *)m->slots, m->capacity, bins, d, d + bins));
         GK_HIP(ctx, hipGetLastError());

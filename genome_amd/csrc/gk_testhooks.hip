@@ -1,6 +1,7 @@
 // gk_testhooks.hip — what ONLY the test build of the library has (libgenome_amd_test.so = the product's objects + this one):
 //   * gk_ctx_set_option and the environment switches read at gk_ctx_create: A/B switches of the kernels, test hooks that stage
 //     the large-table paths on small tables or inject failures;
+//   * gk_test_grid_cap_uses: how many launches "test_max_grid" has sized on a context (the switch's echo);
 //   * gk_test_support_last_walk: which walker (device kernel / host fallback) did the orientations of the last gk_graph_walk_pairs;
 //   * gk_dist_create_loopback: a transport whose ranks are threads of ONE process on ONE device, so that gk_dist_* runs with
 //     world > 1 on a one-GPU box (RCCL refuses two ranks on one device).
@@ -80,8 +81,18 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
         ctx->hook_graph_load_pct = value > 0 ? (int)value : -1;
     }
     else if (n == "test_fastq_chunk") ctx->hook_fastq_chunk = (int64_t)std::max<int64_t>(0, value);
+    else if (n == "test_max_grid") {
+        if (value < 0) return fail(ctx, GK_E_INVALID, "test_max_grid: 0 off, else the most workgroups of a grid-stride launch");
+        ctx->hook_max_grid = (int)std::min<int64_t>(value, 1 << 30);
+    }
     else if (n == "fine_exact") ctx->hook_fine_exact = value < 0 ? -1 : value != 0;
     else return fail(ctx, GK_E_INVALID, "gk_ctx_set_option: unknown option '" + n + "'");
+    return GK_OK;
+}
+
+int gk_test_grid_cap_uses(const gk_ctx *ctx, uint64_t *uses) {
+    if (!ctx || !uses) return fail(ctx, GK_E_INVALID, "gk_test_grid_cap_uses: null argument");
+    *uses = ctx->hook_max_grid_uses;
     return GK_OK;
 }
 

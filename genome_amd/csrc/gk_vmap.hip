@@ -178,7 +178,7 @@ __global__ __launch_bounds__(BLOCK) void k_vm_export(const Slot<W> *__restrict__
 
 namespace {
 
-int vgrid(const gk_ctx *ctx, u64 items) { return (int)std::min<u64>(std::max<u64>((items + BLOCK - 1) / BLOCK, 1), (u64)ctx->cu_count * 8); }
+int vgrid(const gk_ctx *ctx, u64 items) { return (int)std::min<u64>(std::max<u64>((items + BLOCK - 1) / BLOCK, 1), grid_cap(ctx)); }
 
 int vm_check(const gk_vmap *m) {
     if (!m || !m->ctx) return fail(nullptr, GK_E_INVALID, "null value-map handle");

@@ -41,6 +41,12 @@ class Context:
         """Test / A-B switches (include/genome_amd_test.h: gk_ctx_set_option; the TEST build of the library only)."""
         L.check(L.test_hook("gk_ctx_set_option")(self.h, name.encode(), int(value)), self.h)
 
+    def grid_cap_uses(self) -> int:
+        """Launches on this context that "test_max_grid" has sized so far (a test hook: GkError on the product library)."""
+        n = C.c_uint64()
+        L.check(L.test_hook("gk_test_grid_cap_uses")(self.h, C.byref(n)), self.h)
+        return n.value
+
     def sync(self):
         """Wait for everything queued on the context's stream."""
         L.check(L.lib().gk_ctx_sync(self.h), self.h)

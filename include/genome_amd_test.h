@@ -35,8 +35,19 @@ extern "C" {
  * same range and refusal; 0 or -1 = chosen by free memory; at k = 64 a value above 45 means 45, the tagged table's densest step),
  * and the failure injections of the exchange: "test_dist_small_send" (a send region far too small: re-routed in place), "test_dist_fail_exchange" (this rank's next exchange fails locally with the given code), "test_dist_fail_classify"
  * (this rank cannot stage the queries of its next classified gather), "test_dist_fail_reduce" (this rank fails the owner merge of
- * its next gk_dist_reduce_support, after the records were exchanged). */
+ * its next gk_dist_reduce_support, after the records were exchanged).
+ * "test_max_grid" (0: off; a positive value: every grid-stride launch of the graph phase — build, simplify, components,
+ * coverage, tips, bubbles, distance, export, the graph file, the position map, the paired-end stage —, of the value maps, the
+ * spectrum and the read correction gets at most that many workgroups, the pair walks twice as many, instead of 8 (16) per CU; a
+ * negative value is GK_E_INVALID): a graph the oracle can follow then makes every workgroup take several trips through its loop,
+ * and one workgroup sees more component roots than its LDS table holds.  The insert pipeline's grids follow the table's geometry
+ * and are not capped.  The list of capped kernels is in DESIGN.md section 5. */
 int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value);
+
+/* The echo of "test_max_grid": *uses = the launches on this context whose grid was bounded by the switch's value instead of by
+ * 8 workgroups per CU, since the context was created (every capped launch site asks once per launch; nothing is counted while the
+ * switch is 0).  A call that is meant to run under the cap and leaves the number as it was did not consult it. */
+int gk_test_grid_cap_uses(const gk_ctx *ctx, uint64_t *uses);
 
 /* Which walker produced the last gk_graph_walk_pairs into `s`: *orientations = pair orientations handed to the walk stage (two per
  * pair whose mates both hold k bases), *overflowed = those of them whose sets outgrew the wave's LDS on the device and were walked

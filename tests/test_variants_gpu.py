@@ -21,7 +21,8 @@ Pairs that cannot run anywhere (by the code, not by choice):
   * filter_classic = 0 at k = 64: filter_compact_streaming refuses tagged slots; asserted as "classic".
   * graph_mbt = 1 at k = 64: graph_build_entry never buckets tagged slots (`m->k != 64`); asserted as "no bucketed table".
 Taken on trust: cc_find has no echo — the four forms differ only in which parent pointers they write, never in the result, so
-the result against the oracle is the whole check.  With this module every option name of gk_testhooks.hip is set by some test.
+the result against the oracle is the whole check.  With this module every option name of gk_testhooks.hip is set by some test
+("test_max_grid", the cap of the graph phase's launch grids, by tests/test_small_grid_gpu.py through forced() below).
 """
 import os
 import random
@@ -44,7 +45,7 @@ pytestmark = pytest.mark.gpu
 # gk_internal.h: -1 for the tri-states, cc_find 3, graph_mbt_keys 256, 0 otherwise
 DEFAULTS = {"p4_wide": -1, "p4_direct": -1, "p2_wide": -1, "p2_sorted": -1, "p45_stripes": -1, "p4_grid": -1, "p24_pieces": -1,
             "fine_exact": -1, "filter_classic": -1, "graph_load_pct": -1, "graph_mbt": -1, "graph_mbt_keys": 256, "cc_find": 3,
-            "part_exact": 0, "host_ragged": 0, "min_lnb1": 0, "target_load_pct": 0, "test_no_reserve": 0}
+            "part_exact": 0, "host_ragged": 0, "min_lnb1": 0, "target_load_pct": 0, "test_no_reserve": 0, "test_max_grid": 0}
 
 KS = (21, 31, 35, 55, 64)
 

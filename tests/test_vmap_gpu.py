@@ -144,6 +144,12 @@ def test_get_graph_map_vs_oracle(ctx, k, seed, simplified):
     m, ref, g, og = _graph_pair(ctx, k, seed)
     if simplified:                                   # longer edges: interior k-mers at distances up to hundreds
         g.removeBubbles(); og.remove_bubbles(); g.simplifyGraph(); og.simplify()
+    check_graph_map(g, og, k, seed)
+    g.close(); m.close()
+
+
+def check_graph_map(g, og, k, seed):
+    """g.getGraphMap() against the oracle's putNew sequence for the same graph (also used by tests/test_small_grid_gpu.py)"""
     vm = g.getGraphMap()
     calls = og.graph_map_calls()
     n, e, ln = g.counts()
@@ -165,7 +171,7 @@ def test_get_graph_map_vs_oracle(ctx, k, seed, simplified):
     nlo, nhi = g.getNodes()
     _, found = vm.apply_batch((nlo, nhi))
     assert found.all()
-    vm.close(); g.close(); m.close()
+    vm.close()
 
 
 @pytest.mark.parametrize("k,seed", [(15, 5), (31, 6), (47, 7)])
