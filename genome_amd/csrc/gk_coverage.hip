@@ -382,25 +382,16 @@ int gk_graph_clip_tips(gk_graph *g, gk_map *counts, uint64_t max_len, uint64_t *
     if (int rc = coverage_pass(g, counts, tmp, nullptr, &cov)) return rc;
     // the in-edge lists of the graph as it is
     unsigned long long *d_in_off = nullptr, *d_removed = nullptr, h_removed = 0;
-    u32 *d_in_cnt = nullptr, *d_in_list = nullptr, *d_flags = nullptr, h_flags = 0;
-    u64 *d_sums = nullptr;
+    u32 *d_in_list = nullptr, *d_flags = nullptr, h_flags = 0;
     uint8_t *d_mark = nullptr;
-    hipError_t e = tmp.get(&d_in_off, v.n_nodes + 1);
-    if (e == hipSuccess) e = tmp.get(&d_in_cnt, v.n_nodes);
-    if (e == hipSuccess) e = tmp.get(&d_in_list, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&d_sums, v.n_nodes / SCAN_CHUNK + 2);
-    if (e == hipSuccess) e = tmp.get(&d_mark, v.n_edges);
+    hipError_t e = tmp.get(&d_mark, v.n_edges);
     if (e == hipSuccess) e = tmp.get(&d_flags, 1);
     if (e == hipSuccess) e = tmp.get(&d_removed, 1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_in_cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 4, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, 8, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_clip_tips: in-edge lists");
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_clip_tips: marks");
+    if (int rc = graph_in_lists(g, tmp, "gk_graph_clip_tips", &d_in_off, &d_in_list)) return rc;
     const int grid = ggrid(ctx, v.n_edges);
-    hipLaunchKernelGGL(k_in_count, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, d_in_cnt);
-    GK_HIP(ctx, scan_counts(ctx, d_in_cnt, v.n_nodes, d_in_off, d_sums));
-    GK_HIP(ctx, hipMemsetAsync(d_in_cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream));
-    hipLaunchKernelGGL(k_in_fill, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, d_in_off, d_in_cnt, d_in_list);
     hipLaunchKernelGGL(k_tip_mark, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, cov, d_in_off, d_in_list, (u64)max_len, d_mark, d_flags);
     // the decision is complete before anything is applied, and a map that is not this graph's leaves the graph as it was
     hipLaunchKernelGGL(k_tip_apply, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, d_mark, d_flags, d_removed);
@@ -442,15 +433,13 @@ int gk_graph_pop_bubbles(gk_graph *g, gk_map *counts, uint64_t max_len, uint32_t
     // the candidate pairs: counted per node, scanned, written
     unsigned long long *d_off = nullptr, *d_removed = nullptr, *d_compared = nullptr, h_pairs = 0, h_removed = 0, h_compared = 0;
     u32 *d_cnt = nullptr, *d_pe = nullptr, *d_pf = nullptr, *d_dist = nullptr, *d_flags = nullptr, h_flags = 0;
-    u64 *d_sums = nullptr;
     uint8_t *d_want = nullptr, *d_mark = nullptr;
     hipError_t e = tmp.get(&d_cnt, v.n_nodes);
     if (e == hipSuccess) e = tmp.get(&d_off, v.n_nodes + 1);
-    if (e == hipSuccess) e = tmp.get(&d_sums, v.n_nodes / SCAN_CHUNK + 2);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_pop_bubbles: candidate counts");
     const int ngrid = ggrid(ctx, v.n_nodes);
     hipLaunchKernelGGL(k_bubble_count, dim3(ngrid), dim3(BLOCK), 0, ctx->stream, v, (u64)max_len, d_cnt);
-    GK_HIP(ctx, scan_counts(ctx, d_cnt, v.n_nodes, d_off, d_sums));
+    GK_HIP(ctx, scan_counts(ctx, tmp, d_cnt, v.n_nodes, d_off));
     GK_HIP(ctx, read_back(ctx, &h_pairs, d_off + v.n_nodes));
     if (h_pairs == 0) return GK_OK;
     e = tmp.get(&d_pe, h_pairs);

@@ -1,6 +1,7 @@
-// gk_graph.h — the device-side view of a MapGraph (S/data/graph/Graph.scala:153-209) and the host handle, shared by
-// gk_graph.hip (build, structural edits), gk_pairs.hip (the paired-end stage) and the readers of a count table (gk_coverage.hip,
-// gk_correct.hip: window_count).
+// gk_graph.h — the device-side view of a MapGraph (S/data/graph/Graph.scala:153-209), the host handle and the block-wide device
+// helpers, shared by gk_graph.hip (the build from a k-mer table), gk_graph_ops.hip (everything on a built graph: the arrays,
+// structural edits, in-edge lists), gk_pairs.hip (the paired-end stage), gk_graphio.hip (the graph file) and the readers of a
+// count table (gk_coverage.hip, gk_correct.hip: window_count).
 #pragma once
 
 #include <memory>
@@ -83,6 +84,44 @@ __device__ __forceinline__ u32 order_remove(u32 o, int b) {
 }
 __device__ __forceinline__ u32 rev4(u32 m) { return ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3); }
 __device__ __forceinline__ int pool_get(const uint8_t *pool, u64 off, u64 i) { return (pool[off + (i >> 2)] >> ((i & 3) * 2)) & 3; }
+template <int W> __device__ __forceinline__ Kmer<W> node_kmer(const GraphView &g, u64 n);
+template <> __device__ __forceinline__ Kmer<1> node_kmer<1>(const GraphView &g, u64 n) { return Kmer<1>{g.node_lo[n]}; }
+template <> __device__ __forceinline__ Kmer<2> node_kmer<2>(const GraphView &g, u64 n) { return Kmer<2>{g.node_lo[n], g.node_hi[n]}; }
+__device__ __forceinline__ u32 wave_incl_scan(u32 v) {
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) {
+        u32 t = __shfl_up(v, d);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+// block-wide exclusive scan of small per-thread counts; *total = block sum
+__device__ __forceinline__ u32 block_excl_scan(u32 v, u32 *total, u32 *lds4) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u32 inc = wave_incl_scan(v);
+    __syncthreads();
+    if (lane == 63) lds4[wave] = inc;
+    __syncthreads();
+    u32 base = 0, tot = 0;
+    for (int w = 0; w < BLOCK / 64; ++w) {
+        u32 c = lds4[w];
+        if (w < wave) base += c;
+        tot += c;
+    }
+    *total = tot;
+    return base + inc - v;
+}
+// reserve `v` units per thread from a global cursor with ONE atomic per block; returns this
+// thread's first unit
+__device__ __forceinline__ u64 block_reserve(u32 v, unsigned long long *cursor, u32 *lds4, unsigned long long *s_base) {
+    u32 tot;
+    u32 pre = block_excl_scan(v, &tot, lds4);
+    if (threadIdx.x == 0) *s_base = tot ? atomicAdd(cursor, (unsigned long long)tot) : 0ull;
+    __syncthreads();
+    u64 r = *s_base + pre;
+    __syncthreads();
+    return r;
+}
 
 // MapGraph.removeEdge (Graph.scala:191-195) of a live edge, safe beside other lanes removing other edges: the start node's
 // out-edge slot and insertion order, the edge itself, the end node's in-degree (k_remove_edges_by_id, k_tip_apply)
@@ -113,13 +152,7 @@ __device__ __forceinline__ u32 window_count(const Table<W, S> &t, Kmer<W> x, Kme
     return c;
 }
 
-// in-edge lists (Node.inEdgeIds) as CSR by end node (gk_pairs.hip): cnt[v] += 1 per live edge ending at v; then, with `off` the
-// exclusive scan of those counts and `cursor` zeroed, list[off[v] ..] = the ids of those edges (order unspecified)
-__global__ __launch_bounds__(BLOCK) void k_in_count(GraphView g, u32 *cnt);
-__global__ __launch_bounds__(BLOCK) void k_in_fill(GraphView g, const unsigned long long *off, u32 *cursor, u32 *list);
-
-
-// host-side helpers of gk_graph.hip that the paired-end stage (gk_pairs.hip) uses
+// host-side helpers of gk_graph_ops.hip that the build, the paired-end stage, the tip rule and the graph file use
 int check_graph(const gk_graph *g);
 int ggrid(const gk_ctx *ctx, u64 items);                  // grid of BLOCK-thread workgroups for `items` work items
 int graph_refresh_counts(gk_graph *g);                    // live nodes / edges / bases; bumps the graph's epoch
@@ -129,3 +162,6 @@ int graph_grow_nodes(gk_graph *g, u64 new_cap);
 // the node / edge arrays of a graph without any (ids 0..n-1, none alive, out_edge NONE, out_order / in_deg 0): the build and gk_graph_load
 int graph_alloc_nodes(gk_graph *g, u64 n);
 int graph_alloc_edges(gk_graph *g, u64 n);
+// Node.inEdgeIds as CSR by end node of the graph as it is now: (*off)[v] .. (*off)[v+1] index *list; both live in `tmp`.
+// Stream-ordered, no synchronisation; `who` names the entry point in the error text.  (Not exported, like DevScratch.)
+__attribute__((visibility("hidden"))) int graph_in_lists(gk_graph *g, DevScratch &tmp, const char *who, unsigned long long **off, u32 **list);

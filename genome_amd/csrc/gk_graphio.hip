@@ -296,21 +296,19 @@ int graph_save_impl(gk_graph *g, const std::string &path, const std::string &tmp
     const u64 nn = v.n_nodes, ne = v.n_edges;
     u32 *nlive = nullptr, *elive = nullptr, *ebytes = nullptr;
     unsigned long long *nrank = nullptr, *erank = nullptr, *poff = nullptr;
-    u64 *sums = nullptr;
     GK_HIP(ctx, tmp_.get(&nlive, nn));
     GK_HIP(ctx, tmp_.get(&elive, ne));
     GK_HIP(ctx, tmp_.get(&ebytes, ne));
     GK_HIP(ctx, tmp_.get(&nrank, nn + 1));
     GK_HIP(ctx, tmp_.get(&erank, ne + 1));
     GK_HIP(ctx, tmp_.get(&poff, ne + 1));
-    GK_HIP(ctx, tmp_.get(&sums, std::max(nn, ne) / SCAN_CHUNK + 2));
     if (nn || ne) {
         hipLaunchKernelGGL(k_gio_save_flags, dim3(ggrid(ctx, std::max(nn, ne))), dim3(BLOCK), 0, ctx->stream, v, nlive, elive, ebytes);
         GK_HIP(ctx, hipGetLastError());
     }
-    GK_HIP(ctx, scan_counts(ctx, nlive, nn, nrank, sums));      // (stream-ordered: one scratch serves the three scans)
-    GK_HIP(ctx, scan_counts(ctx, elive, ne, erank, sums));
-    GK_HIP(ctx, scan_counts(ctx, ebytes, ne, poff, sums));
+    GK_HIP(ctx, scan_counts(ctx, tmp_, nlive, nn, nrank));      // (each scan holds its own few KB of scratch until this call returns)
+    GK_HIP(ctx, scan_counts(ctx, tmp_, elive, ne, erank));
+    GK_HIP(ctx, scan_counts(ctx, tmp_, ebytes, ne, poff));
     unsigned long long tot[3] = {0, 0, 0};
     GK_HIP(ctx, read_back(ctx, {{&tot[0], nrank + nn, 8}, {&tot[1], erank + ne, 8}, {&tot[2], poff + ne, 8}}));
     h.nodes = tot[0]; h.edges = tot[1]; h.pool_bytes = tot[2];
@@ -465,11 +463,9 @@ int graph_load_impl(gk_ctx *ctx, const std::string &path, gk_graph *g, float *ms
     const u32 *ids = (const u32 *)at(L.ids), *eid = (const u32 *)at(L.eid);
     u32 *flags = nullptr, *nbytes = nullptr;
     unsigned long long *poff = nullptr;
-    u64 *sums = nullptr;
     GK_HIP(ctx, tmp_.get(&flags, 1));
     GK_HIP(ctx, tmp_.get(&nbytes, h.edges));
     GK_HIP(ctx, tmp_.get(&poff, h.edges + 1));
-    GK_HIP(ctx, tmp_.get(&sums, h.edges / SCAN_CHUNK + 2));
     GK_HIP(ctx, hipMemsetAsync(flags, 0, 4, ctx->stream));
     if (h.nodes) {
         hipLaunchKernelGGL(k_gio_load_nodes, dim3(ggrid(ctx, h.nodes)), dim3(BLOCK), 0, ctx->stream, v, ids, (const u64 *)at(L.lo),
@@ -481,7 +477,7 @@ int graph_load_impl(gk_ctx *ctx, const std::string &path, gk_graph *g, float *ms
                            (const u32 *)at(L.een), (const u64 *)at(L.elen), h.edges, nbytes, flags);
         GK_HIP(ctx, hipGetLastError());
     }
-    GK_HIP(ctx, scan_counts(ctx, nbytes, h.edges, poff, sums));
+    GK_HIP(ctx, scan_counts(ctx, tmp_, nbytes, h.edges, poff));
     u32 hflags = 0;
     unsigned long long pool_sum = 0;
     GK_HIP(ctx, read_back(ctx, {{&hflags, flags, 4}, {&pool_sum, poff + h.edges, 8}}));

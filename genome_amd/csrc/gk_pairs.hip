@@ -244,17 +244,6 @@ __global__ __launch_bounds__(BLOCK) void k_pair_keys(const uint8_t *__restrict__
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// in-edge lists (Node.inEdgeIds) as CSR by end node, built on the device (declared in gk_graph.h: the tip rule reads them too)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_in_count(GraphView g, u32 *cnt) {
-    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK)
-        if (g.e_alive[e]) atomicAdd(&cnt[g.e_end[e]], 1u);
-}
-__global__ __launch_bounds__(BLOCK) void k_in_fill(GraphView g, const unsigned long long *off, u32 *cursor, u32 *list) {
-    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK)
-        if (g.e_alive[e]) { const u32 v = g.e_end[e]; list[off[v] + atomicAdd(&cursor[v], 1u)] = (u32)e; }
-}
 // a position must name something of THIS graph (gk_graph_walk_pairs: GK_E_STATE otherwise)
 __global__ __launch_bounds__(BLOCK) void k_check_positions(GraphView g, const u64 *vals, u64 n, u32 *bad) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
@@ -747,18 +736,16 @@ int support_bucket(gk_support *s, int P, u64 *d_keys, u32 *d_cnt, u64 room, u64 
     DevScratch tmp(ctx);
     u32 *d_counts = nullptr;
     unsigned long long *d_off = nullptr, *d_region = nullptr;
-    u64 *d_sums = nullptr;
     u32 *d_bad = nullptr, h_bad = 0;
     hipError_t e = tmp.get(&d_counts, n);
     if (e == hipSuccess) e = tmp.get(&d_off, n + 1);
-    if (e == hipSuccess) e = tmp.get(&d_sums, n / SCAN_CHUNK + 2);
     if (e == hipSuccess) e = tmp.get(&d_region, (u64)P + 1);
     if (e == hipSuccess) e = tmp.get(&d_bad, 1);
     if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 4, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "support_bucket: scratch");
     hipLaunchKernelGGL(k_sup_bucket_count, dim3((unsigned)nwg), dim3(BLOCK), 0, ctx->stream, s->d_keys, s->cap, chunk, (u32)P, canon, nmap, d_counts, d_bad);
     GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, scan_counts(ctx, d_counts, n, d_off, d_sums));
+    GK_HIP(ctx, scan_counts(ctx, tmp, d_counts, n, d_off));
     hipLaunchKernelGGL(k_sup_regions, dim3(1), dim3(64), 0, ctx->stream, d_off, nwg, (u32)P, d_region);
     std::vector<unsigned long long> h(P + 1);
     GK_HIP(ctx, read_back(ctx, {{h.data(), d_region, (size_t)(P + 1) * 8}, {&h_bad, d_bad, 4}}));
@@ -1087,15 +1074,14 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
     // ---- the four getAll of every pair as ONE batch, results left in HBM as CSR
     u32 *d_cnt = nullptr;
     unsigned long long *d_off = nullptr;
-    u64 *d_sums = nullptr, *d_vals = nullptr;
+    u64 *d_vals = nullptr;
     unsigned long long total = 0;
     {
         hipError_t e = tmp.get(&d_cnt, nq);
         if (e == hipSuccess) e = tmp.get(&d_off, nq + 1);
-        if (e == hipSuccess) e = tmp.get(&d_sums, nq / SCAN_CHUNK + 2);
         if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_walk_pairs: lookup arrays");
         if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, nullptr, d_cnt, nullptr)) return rc;
-        GK_HIP(ctx, scan_counts(ctx, d_cnt, nq, d_off, d_sums));
+        GK_HIP(ctx, scan_counts(ctx, tmp, d_cnt, nq, d_off));
         GK_HIP(ctx, read_back(ctx, &total, d_off + nq));
         GK_HIP(ctx, tmp.get(&d_vals, total));
         if (total) { if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, d_off, d_cnt, d_vals)) return rc; }
@@ -1112,21 +1098,8 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
         GK_HIP(ctx, hipGetLastError());
     }
     unsigned long long *d_in_off = nullptr;
-    u32 *d_in_cnt = nullptr, *d_in_list = nullptr;
-    u64 *d_sums2 = nullptr;
-    {
-        hipError_t e = tmp.get(&d_in_off, v.n_nodes + 1);
-        if (e == hipSuccess) e = tmp.get(&d_in_cnt, v.n_nodes);
-        if (e == hipSuccess) e = tmp.get(&d_in_list, v.n_edges);
-        if (e == hipSuccess) e = tmp.get(&d_sums2, v.n_nodes / SCAN_CHUNK + 2);
-        if (e == hipSuccess) e = hipMemsetAsync(d_in_cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_walk_pairs: in-edge lists");
-        if (v.n_edges) hipLaunchKernelGGL(k_in_count, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, d_in_cnt);
-        GK_HIP(ctx, scan_counts(ctx, d_in_cnt, v.n_nodes, d_in_off, d_sums2));
-        GK_HIP(ctx, hipMemsetAsync(d_in_cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream));
-        if (v.n_edges) hipLaunchKernelGGL(k_in_fill, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, d_in_off, d_in_cnt, d_in_list);
-        GK_HIP(ctx, hipGetLastError());
-    }
+    u32 *d_in_list = nullptr;
+    if (int rc = graph_in_lists(g, tmp, "gk_graph_walk_pairs", &d_in_off, &d_in_list)) return rc;
     GK_HIP(ctx, read_back(ctx, h_flag, d_flag, 1));
     if (h_flag[0]) return fail(ctx, GK_E_STATE, "gk_graph_walk_pairs: the position map does not belong to this graph (rebuild it after edits)");
     const double t_snap = now();

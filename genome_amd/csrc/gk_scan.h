@@ -1,14 +1,12 @@
-// gk_scan.h — exclusive scan of u32 counts into u64 offsets on the device (three small kernels); shared by the paired-end stage
-// (CSR of the getAll batch, in-edge lists) and the graph build (bucket regions of the minimizer-bucketed table).
+// gk_scan.h — exclusive scan of u32 counts into u64 offsets on the device (three small kernels); shared by the graph files (in-edge
+// lists, bucket regions of the minimizer-bucketed table, candidate pairs, the graph file's ranks), the paired-end stage (CSR of the
+// getAll batch), the table export and the FASTQ / FASTA parsers.  A caller with a DevScratch passes it and gets the scratch from it.
 #pragma once
 
 #include "gk_internal.h"
 
 using namespace gk;
 
-// ---------------------------------------------------------------------------------------------
-// small device utilities: exclusive scan of u32 counts into u64 offsets (n + 1 entries)
-// ---------------------------------------------------------------------------------------------
 static constexpr u32 SCAN_CHUNK = 4096;
 static __global__ __launch_bounds__(256) void k_scan_sums(const u32 *__restrict__ in, u64 n, u64 *__restrict__ sums) {
     __shared__ u64 s_w[4];
@@ -61,4 +59,9 @@ static hipError_t scan_counts(gk_ctx *ctx, const u32 *d_in, u64 n, unsigned long
     hipLaunchKernelGGL(k_scan_fill, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream, d_in, n, d_sums, nchunks, d_out);
     return hipGetLastError();
 }
-
+// the same, its scratch taken from `tmp` (it lives as long as `tmp` does)
+static hipError_t scan_counts(gk_ctx *ctx, DevScratch &tmp, const u32 *d_in, u64 n, unsigned long long *d_out) {
+    u64 *d_sums = nullptr;
+    const hipError_t e = tmp.get(&d_sums, n / SCAN_CHUNK + 2);
+    return e != hipSuccess ? e : scan_counts(ctx, d_in, n, d_out, d_sums);
+}

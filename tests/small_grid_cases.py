@@ -16,7 +16,7 @@ from oracle import pyref as R
 
 import bubbles_planted as P
 
-# gk_tile.h: threads per workgroup of every grid-stride kernel; gk_scan.h: elements per workgroup of scan_counts; gk_graph.hip:
+# gk_tile.h: threads per workgroup of every grid-stride kernel; gk_scan.h: elements per workgroup of scan_counts; gk_graph_ops.hip:
 # entries of a workgroup's LDS component table (CcTable) — a root that finds 16 probed entries taken goes straight to memory
 BLOCK = 256
 SCAN_CHUNK = 4096

@@ -38,7 +38,7 @@ import test_pairs_gpu as pairs_cases
 import test_spectrum_gpu as spectrum_cases
 import test_vmap_gpu as vmap_cases
 import tips_ref as T
-from small_grid_cases import BLOCK, CC_TAB, SCAN_CHUNK      # gk_tile.h (through gk_internal.h), gk_graph.hip, gk_scan.h
+from small_grid_cases import BLOCK, CC_TAB, SCAN_CHUNK      # gk_tile.h (through gk_internal.h), gk_graph_ops.hip, gk_scan.h
 from test_fuzz_gpu import _oracle_graph
 from test_graph_file_gpu import same_graph
 from test_variants_gpu import ctx, forced  # noqa: F401 (the module-scoped context fixture)
