@@ -347,6 +347,42 @@ int gk_dist_spectrum(gk_dist *d, gk_map *local, uint64_t *hist, uint32_t bins, u
     return GK_OK;
 }
 
+// The fragment-length histogram of every rank's pairs on every rank: gk_dist_spectrum's shape.  The status round comes first, on
+// the handle's own words; the histogram and the classes travel as one array once every rank is known to hold them.
+int gk_dist_pair_distances(gk_dist *d, gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbytes, uint64_t npairs, uint32_t bins, uint64_t *hist,
+                           uint64_t *classes) {
+    if (int rc = dist_check(d)) return rc;
+    gk_ctx *ctx = d->ctx;
+    const char *who = "gk_dist_pair_distances: ";
+    if (!hist || !classes) return fail(ctx, GK_E_INVALID, std::string(who) + "hist or classes is NULL");
+    if (bins < 2 || bins > 65536) return fail(ctx, GK_E_INVALID, std::string(who) + "bins must be 2 .. 65536");
+    if (int rc = dist_quiesce(d)) return rc;
+    int my_rc = GK_OK;
+    std::string my_err;
+    auto local_rc = [&](int rc) { if (rc != GK_OK && my_rc == GK_OK) { my_rc = rc; my_err = ctx->err; } };
+    std::vector<unsigned long long> h((size_t)bins + 9, 0ull);       // hist, then the nine classes
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "one histogram type");
+    if (!g) local_rc(fail(ctx, GK_E_INVALID, std::string(who) + "null graph"));
+    else if (!positions) local_rc(fail(ctx, GK_E_INVALID, std::string(who) + "null position map"));
+    else local_rc(gk_graph_pair_distances(g, positions, bin, nbytes, npairs, bins, reinterpret_cast<uint64_t *>(h.data()), reinterpret_cast<uint64_t *>(&h[bins])));
+    DevScratch buf(ctx);
+    unsigned long long *d_h = nullptr;
+    if (buf.get(&d_h, h.size()) != hipSuccess) local_rc(fail(ctx, GK_E_HIP, std::string(who) + "no room for the histogram"));
+    unsigned long long w = my_rc ? 1ull : 0ull;
+    GK_HIP(ctx, hipMemcpyAsync(d->d_cnt, &w, 8, hipMemcpyHostToDevice, ctx->stream));
+    GK_NCCL(ctx, xAllReduce(d, d->d_cnt, d->d_cnt + 2, 1, XP_UINT64, XP_MAX, ctx->stream));
+    GK_HIP(ctx, hipMemcpyAsync(&w, d->d_cnt + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (w) return my_rc ? fail(ctx, my_rc, my_err) : fail(ctx, GK_E_COMM, std::string(who) + "a rank could not take the distances of its pairs; every rank gave up");
+    GK_HIP(ctx, hipMemcpyAsync(d_h, h.data(), h.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    GK_NCCL(ctx, xAllReduce(d, d_h, d_h, h.size(), XP_UINT64, XP_SUM, ctx->stream));
+    GK_HIP(ctx, hipMemcpyAsync(h.data(), d_h, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t b = 0; b < bins; b++) hist[b] = h[b];
+    for (int c = 0; c < 9; c++) classes[c] = h[(size_t)bins + c];
+    return GK_OK;
+}
+
 static int dist_grow(gk_ctx *ctx, uint8_t **buf, u64 *have, u64 want_records, int slot) {
     if (*have >= want_records && *buf) return GK_OK;
     if (*buf) { GK_HIP(ctx, hipStreamSynchronize(ctx->stream)); GK_HIP(ctx, pool_free(ctx, *buf)); }

@@ -165,3 +165,23 @@ int graph_alloc_edges(gk_graph *g, u64 n);
 // Node.inEdgeIds as CSR by end node of the graph as it is now: (*off)[v] .. (*off)[v+1] index *list; both live in `tmp`.
 // Stream-ordered, no synchronisation; `who` names the entry point in the error text.  (Not exported, like DevScratch.)
 __attribute__((visibility("hidden"))) int graph_in_lists(gk_graph *g, DevScratch &tmp, const char *who, unsigned long long **off, u32 **list);
+
+// The front end every paired-end entry point shares (gk_pairs.hip; GraphSimplifier.scala:213-217): the pairs whose mates both
+// hold k bases are cut from the `.bin` stream (a fixed-stride stream on the device by k_pair_keys, a ragged one on the host),
+// their four getAll run as ONE batch whose results stay in HBM as CSR, and k_check_positions is queued behind it.  Key 4p + q
+// of cut pair p: q = 0 p1.take(k), 1 p2.take(k).revComplement, 2 p2.take(k), 3 p1.take(k).revComplement — orientation o of
+// the batch reads the runs 2o (P1) and 2o + 1 (P2).  Everything lives in `tmp`.  pairs_front returns with the lookups done
+// (t_keys / t_lookup: monotonic ms at the end of the cut and of the batch) and the check still in flight, so that a caller can
+// queue more work before pairs_front_checked waits for it: GK_E_STATE if a position names nothing live in this graph.
+struct PairFront {
+    u64 nq = 0;                                  // keys cut: 4 per pair that was not skipped (0: nothing else is set)
+    unsigned long long *d_off = nullptr;         // [nq + 1]
+    u64 *d_vals = nullptr;                       // [total]
+    unsigned long long total = 0;
+    u32 *d_flag = nullptr;                       // [0] raised by k_check_positions, [1] zero, the caller's
+    double t_keys = 0, t_lookup = 0;
+};
+double pairs_now();
+__attribute__((visibility("hidden"))) int pairs_front(gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbytes, uint64_t npairs, const char *who,
+                                                      DevScratch &tmp, PairFront &F);
+__attribute__((visibility("hidden"))) int pairs_front_checked(gk_ctx *ctx, const PairFront &F, const char *who);

@@ -863,6 +863,108 @@ int support_to_host(gk_support *s) {
 }
 }  // namespace
 
+double pairs_now() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+
+// the shared front end of the paired-end entry points (gk_graph.h: PairFront)
+int pairs_front(gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbytes, uint64_t npairs, const char *who, DevScratch &tmp, PairFront &F) {
+    gk_ctx *ctx = g->ctx;
+    const int k = g->k, W = g->W;
+    auto now = pairs_now;
+    const std::string w = std::string(who) + ": ";
+    // ---- the pairs whose mates both hold k bases (:213), their four keys.  A stream of equal-length records (what a
+    //      sequencer's run is) goes to the device as it is and is cut there; a ragged one is walked here.
+    u64 *d_lo = nullptr, *d_hi = nullptr;
+    u64 nq = 0;
+    bool cut = false;
+    if (npairs && nbytes && bin[0] >= k) {
+        const int l0 = bin[0];
+        const size_t rb = 1 + (size_t)(l0 + 3) / 4;
+        if (nbytes >= 2 * npairs * rb) {
+            uint8_t *d_bin = nullptr;
+            u32 *d_rag = nullptr, h_rag = 0;
+            hipError_t e = tmp.get(&d_bin, 2 * npairs * rb + 16);
+            if (e == hipSuccess) e = tmp.get(&d_lo, 4 * npairs);
+            if (e == hipSuccess && W == 2) e = tmp.get(&d_hi, 4 * npairs);
+            if (e == hipSuccess) e = tmp.get(&d_rag, 1);
+            if (e == hipSuccess) e = hipMemsetAsync(d_rag, 0, 4, ctx->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_bin, bin, 2 * npairs * rb, hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) return hip_fail(ctx, e, (w + "upload").c_str());
+            GK_BY_W(g->W, hipLaunchKernelGGL(k_pair_keys<W>, dim3(ggrid(ctx, npairs)), dim3(BLOCK), 0, ctx->stream, d_bin, npairs, (u32)rb, l0, k, d_lo, d_hi, d_rag));
+            GK_HIP(ctx, read_back(ctx, &h_rag, d_rag));
+            if (!h_rag) { cut = true; nq = 4 * npairs; }
+        }
+    }
+    if (!cut) {
+        std::vector<u64> klo, khi;
+        klo.reserve((size_t)std::min<uint64_t>(npairs, nbytes / 2) * 4); khi.reserve(klo.capacity());
+        size_t pos = 0;
+        for (uint64_t p = 0; p < npairs && pos < nbytes; p++) {
+            const uint8_t *r1 = bin + pos;
+            const int l1 = r1[0];
+            pos += 1 + (size_t)(l1 + 3) / 4;
+            if (pos >= nbytes) return fail(ctx, GK_E_FORMAT, w + "the stream ends inside a pair");
+            const uint8_t *r2 = bin + pos;
+            const int l2 = r2[0];
+            pos += 1 + (size_t)(l2 + 3) / 4;
+            if (pos > nbytes) return fail(ctx, GK_E_FORMAT, w + "the stream ends inside a record");
+            if (l1 < k || l2 < k) continue;
+            u64 alo, ahi, blo, bhi, ralo, rahi, rblo, rbhi;
+            first_kmer(r1 + 1, (size_t)(l1 + 3) / 4, k, alo, ahi); first_kmer(r2 + 1, (size_t)(l2 + 3) / 4, k, blo, bhi);
+            revcomp_host(alo, ahi, k, ralo, rahi); revcomp_host(blo, bhi, k, rblo, rbhi);
+            // f1 = getAll(p1.take(k)), f2 = getAll(p2.take(k).revComplement), f3 = getAll(p2.take(k)), f4 = getAll(p1.take(k).revComplement)
+            const u64 lo4[4] = {alo, rblo, blo, ralo}, hi4[4] = {ahi, rbhi, bhi, rahi};
+            klo.insert(klo.end(), lo4, lo4 + 4);
+            khi.insert(khi.end(), hi4, hi4 + 4);
+        }
+        nq = klo.size();
+        if (nq) {
+            d_lo = d_hi = nullptr;
+            hipError_t e = tmp.get(&d_lo, nq);
+            if (e == hipSuccess && W == 2) e = tmp.get(&d_hi, nq);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_lo, klo.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream);
+            if (e == hipSuccess && d_hi) e = hipMemcpyAsync(d_hi, khi.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (klo / khi die with this scope)
+            if (e != hipSuccess) return hip_fail(ctx, e, (w + "keys").c_str());
+        }
+    }
+    F.nq = nq;
+    if (nq == 0) return GK_OK;
+    F.t_keys = now();
+    // ---- the four getAll of every pair as ONE batch, results left in HBM as CSR
+    u32 *d_cnt = nullptr;
+    unsigned long long *d_off = nullptr;
+    u64 *d_vals = nullptr;
+    unsigned long long total = 0;
+    {
+        hipError_t e = tmp.get(&d_cnt, nq);
+        if (e == hipSuccess) e = tmp.get(&d_off, nq + 1);
+        if (e != hipSuccess) return hip_fail(ctx, e, (w + "lookup arrays").c_str());
+        if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, nullptr, d_cnt, nullptr)) return rc;
+        GK_HIP(ctx, scan_counts(ctx, tmp, d_cnt, nq, d_off));
+        GK_HIP(ctx, read_back(ctx, &total, d_off + nq));
+        GK_HIP(ctx, tmp.get(&d_vals, total));
+        if (total) { if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, d_off, d_cnt, d_vals)) return rc; }
+    }
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    F.t_lookup = now();
+    // ---- a position must name something of THIS graph
+    GK_HIP(ctx, tmp.get(&F.d_flag, 2));
+    GK_HIP(ctx, hipMemsetAsync(F.d_flag, 0, 8, ctx->stream));
+    if (total) {
+        hipLaunchKernelGGL(k_check_positions, dim3(ggrid(ctx, total)), dim3(BLOCK), 0, ctx->stream, g->v, d_vals, (u64)total, F.d_flag);
+        GK_HIP(ctx, hipGetLastError());
+    }
+    F.d_off = d_off; F.d_vals = d_vals; F.total = total;
+    return GK_OK;
+}
+
+int pairs_front_checked(gk_ctx *ctx, const PairFront &F, const char *who) {
+    u32 bad = 0;
+    GK_HIP(ctx, read_back(ctx, &bad, F.d_flag, 1));
+    if (bad) return fail(ctx, GK_E_STATE, std::string(who) + ": the position map does not belong to this graph (rebuild it after edits)");
+    return GK_OK;
+}
+
 extern "C" {
 
 int gk_support_create(gk_ctx *ctx, gk_support **out) {
@@ -1008,100 +1110,26 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
     if (vmap_ctx(positions) != ctx || sup->ctx != ctx) return fail(ctx, GK_E_INVALID, "gk_graph_walk_pairs: the position map and the support must live on the graph's context");
     if (vmap_k(positions) != g->k) return fail(ctx, GK_E_KLEN, "gk_graph_walk_pairs: the position map has another k");
     if (range_lo < 0 || range_hi < range_lo || range_hi > 65535) return fail(ctx, GK_E_INVALID, "gk_graph_walk_pairs: range must satisfy 0 <= lo <= hi <= 65535");
-    const int k = g->k, W = g->W;
-    auto now = []() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
+    const int k = g->k;
+    auto now = pairs_now;
     const double t_begin = now();
     DevScratch tmp(ctx);
-    // ---- the pairs whose mates both hold k bases (:213), their four keys.  A stream of equal-length records (what a
-    //      sequencer's run is) goes to the device as it is and is cut there; a ragged one is walked here.
-    u64 *d_lo = nullptr, *d_hi = nullptr;
-    u64 nq = 0;
-    bool cut = false;
-    if (npairs && nbytes && bin[0] >= k) {
-        const int l0 = bin[0];
-        const size_t rb = 1 + (size_t)(l0 + 3) / 4;
-        if (nbytes >= 2 * npairs * rb) {
-            uint8_t *d_bin = nullptr;
-            u32 *d_rag = nullptr, h_rag = 0;
-            hipError_t e = tmp.get(&d_bin, 2 * npairs * rb + 16);
-            if (e == hipSuccess) e = tmp.get(&d_lo, 4 * npairs);
-            if (e == hipSuccess && W == 2) e = tmp.get(&d_hi, 4 * npairs);
-            if (e == hipSuccess) e = tmp.get(&d_rag, 1);
-            if (e == hipSuccess) e = hipMemsetAsync(d_rag, 0, 4, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_bin, bin, 2 * npairs * rb, hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_walk_pairs: upload");
-            GK_BY_W(g->W, hipLaunchKernelGGL(k_pair_keys<W>, dim3(ggrid(ctx, npairs)), dim3(BLOCK), 0, ctx->stream, d_bin, npairs, (u32)rb, l0, k, d_lo, d_hi, d_rag));
-            GK_HIP(ctx, read_back(ctx, &h_rag, d_rag));
-            if (!h_rag) { cut = true; nq = 4 * npairs; }
-        }
-    }
-    if (!cut) {
-        std::vector<u64> klo, khi;
-        klo.reserve((size_t)std::min<uint64_t>(npairs, nbytes / 2) * 4); khi.reserve(klo.capacity());
-        size_t pos = 0;
-        for (uint64_t p = 0; p < npairs && pos < nbytes; p++) {
-            const uint8_t *r1 = bin + pos;
-            const int l1 = r1[0];
-            pos += 1 + (size_t)(l1 + 3) / 4;
-            if (pos >= nbytes) return fail(ctx, GK_E_FORMAT, "gk_graph_walk_pairs: the stream ends inside a pair");
-            const uint8_t *r2 = bin + pos;
-            const int l2 = r2[0];
-            pos += 1 + (size_t)(l2 + 3) / 4;
-            if (pos > nbytes) return fail(ctx, GK_E_FORMAT, "gk_graph_walk_pairs: the stream ends inside a record");
-            if (l1 < k || l2 < k) continue;
-            u64 alo, ahi, blo, bhi, ralo, rahi, rblo, rbhi;
-            first_kmer(r1 + 1, (size_t)(l1 + 3) / 4, k, alo, ahi); first_kmer(r2 + 1, (size_t)(l2 + 3) / 4, k, blo, bhi);
-            revcomp_host(alo, ahi, k, ralo, rahi); revcomp_host(blo, bhi, k, rblo, rbhi);
-            // f1 = getAll(p1.take(k)), f2 = getAll(p2.take(k).revComplement), f3 = getAll(p2.take(k)), f4 = getAll(p1.take(k).revComplement)
-            const u64 lo4[4] = {alo, rblo, blo, ralo}, hi4[4] = {ahi, rbhi, bhi, rahi};
-            klo.insert(klo.end(), lo4, lo4 + 4);
-            khi.insert(khi.end(), hi4, hi4 + 4);
-        }
-        nq = klo.size();
-        if (nq) {
-            d_lo = d_hi = nullptr;
-            hipError_t e = tmp.get(&d_lo, nq);
-            if (e == hipSuccess && W == 2) e = tmp.get(&d_hi, nq);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_lo, klo.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess && d_hi) e = hipMemcpyAsync(d_hi, khi.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (klo / khi die with this scope)
-            if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_walk_pairs: keys");
-        }
-    }
+    PairFront F;
+    if (int rc = pairs_front(g, positions, bin, nbytes, npairs, "gk_graph_walk_pairs", tmp, F)) return rc;
+    const u64 nq = F.nq;
     sup->last_orientations = nq / 2; sup->last_overflow = 0;           // (what gk_test_support_last_walk reports: two orientations per cut pair)
     if (nq == 0) return GK_OK;
-    const double t_keys = now();
-    // ---- the four getAll of every pair as ONE batch, results left in HBM as CSR
-    u32 *d_cnt = nullptr;
-    unsigned long long *d_off = nullptr;
-    u64 *d_vals = nullptr;
-    unsigned long long total = 0;
-    {
-        hipError_t e = tmp.get(&d_cnt, nq);
-        if (e == hipSuccess) e = tmp.get(&d_off, nq + 1);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_walk_pairs: lookup arrays");
-        if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, nullptr, d_cnt, nullptr)) return rc;
-        GK_HIP(ctx, scan_counts(ctx, tmp, d_cnt, nq, d_off));
-        GK_HIP(ctx, read_back(ctx, &total, d_off + nq));
-        GK_HIP(ctx, tmp.get(&d_vals, total));
-        if (total) { if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, d_off, d_cnt, d_vals)) return rc; }
-    }
-    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const double t_lookup = now();
-    // ---- a position must name something of THIS graph; the in-edge lists of its current state
+    const double t_keys = F.t_keys, t_lookup = F.t_lookup;
+    unsigned long long *d_off = F.d_off;
+    u64 *d_vals = F.d_vals;
+    const unsigned long long total = F.total;
+    // ---- the in-edge lists of the graph's current state, beside the position check the front end has queued
     const GraphView &v = g->v;
-    u32 *d_flag = nullptr, h_flag[2] = {0, 0};                 // [0] bad position, [1] overflow count
-    GK_HIP(ctx, tmp.get(&d_flag, 2));
-    GK_HIP(ctx, hipMemsetAsync(d_flag, 0, 8, ctx->stream));
-    if (total) {
-        hipLaunchKernelGGL(k_check_positions, dim3(ggrid(ctx, total)), dim3(BLOCK), 0, ctx->stream, v, d_vals, (u64)total, d_flag);
-        GK_HIP(ctx, hipGetLastError());
-    }
+    u32 *d_flag = F.d_flag, h_flag[2] = {0, 0};                // [0] bad position, [1] overflow count
     unsigned long long *d_in_off = nullptr;
     u32 *d_in_list = nullptr;
     if (int rc = graph_in_lists(g, tmp, "gk_graph_walk_pairs", &d_in_off, &d_in_list)) return rc;
-    GK_HIP(ctx, read_back(ctx, h_flag, d_flag, 1));
-    if (h_flag[0]) return fail(ctx, GK_E_STATE, "gk_graph_walk_pairs: the position map does not belong to this graph (rebuild it after edits)");
+    if (int rc = pairs_front_checked(ctx, F, "gk_graph_walk_pairs")) return rc;
     const double t_snap = now();
     // ---- the walks: one wave per pair orientation (two per pair: (f1, f2) and (f3, f4)  :219)
     const u64 norient = nq / 2;

@@ -80,6 +80,18 @@ class HipDist:
         L.check(L.lib().gk_dist_reduce_support(self.h, graph.h if graph is not None else None,
                                                support.h if support is not None else None), self.ctx.h)
 
+    def pair_distances(self, graph, positions, bin_bytes, npairs: int, bins: int = 4096):
+        """COLLECTIVE (gk_dist_pair_distances): HipGraph.pairDistances of this rank's share of the pairs on its replica, summed
+        over the ranks -> (hist, classes) of ALL pairs on every rank.  `graph` / `positions` may be None on a rank that cannot
+        take part: it still joins the agreement, and every rank raises."""
+        from .graph import PAIR_CLASSES
+        buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)
+        hist, cls = np.zeros(max(int(bins), 1), np.uint64), np.zeros(len(PAIR_CLASSES), np.uint64)
+        L.check(L.lib().gk_dist_pair_distances(self.h, graph.h if graph is not None else None, positions.h if positions is not None else None,
+                                               L.ptr(buf, C.c_uint8) if buf.size else None, buf.size, npairs, int(bins),
+                                               L.ptr(hist, C.c_uint64), L.ptr(cls, C.c_uint64)), self.ctx.h)
+        return hist, dict(zip(PAIR_CLASSES, (int(x) for x in cls)))
+
     def last_ms(self):
         ms = (C.c_float * 4)()
         L.check(L.lib().gk_dist_last_ms(self.h, ms), self.ctx.h)

@@ -23,7 +23,7 @@ import numpy as np
 from . import dna
 from .dist import DistDNAMap, HipDist
 from .freqfilter import PairedEndData, auto_rounds
-from .graph import HipGraph, Support, buildGraph, loadGraph
+from .graph import REFERENCE_RANGE, HipGraph, Support, buildGraph, insertRange, loadGraph
 
 
 def pair_share(npairs: int, world: int, rank: int, take_first: int | None = None) -> tuple[int, int]:
@@ -35,14 +35,34 @@ def pair_share(npairs: int, world: int, rank: int, take_first: int | None = None
     return n * rank // world, n * (rank + 1) // world
 
 
-def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs) -> dict:
+def estimate_range(hd: HipDist, g: HipGraph, vm, share, npairs: int, max_insert: int = 4095, trim: int = 25,
+                   min_observations: int = 1000) -> dict:
+    """The range of the walks measured from the pairs themselves (include/genome_amd.h, "the insert range"): every rank's share
+    through gk_dist_pair_distances (bins = max_insert + 1), gk_insert_range over the summed histogram — the same on every rank.
+    -> {"lo", "hi", "median" (None without an estimate), "estimated", "classes", "hist", "max_insert", "trim"}; without an
+    estimate lo / hi are the reference's 180 / 250 and "estimated" is False.  COLLECTIVE."""
+    hist, classes = hd.pair_distances(g, vm, share, npairs, bins=max_insert + 1)
+    est = insertRange(hist, trim, min_observations)
+    lo, hi, median = est if est is not None else (*REFERENCE_RANGE, None)
+    return {"lo": lo, "hi": hi, "median": median, "estimated": est is not None, "classes": classes, "hist": hist, "max_insert": max_insert,
+            "trim": trim}
+
+
+def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs, auto_args=None) -> dict:
     """GraphSimplifier.scala:188-318 on this rank's replica `g`: getGraphMap, walkPairs over the rank's `npairs` pairs in `share`,
     the supports summed over the ranks (before any node split), splitBySupport at the cutoff, simplifyGraph -> the walk_pairs
-    counters."""
+    counters.  lo == "auto": the range is estimated first, from the same pairs (estimate_range with `auto_args`); the counters
+    then hold "insert_range" (estimate_range's result without its histogram)."""
     cutoff, lo, hi = walk_pairs
     vm = g.getGraphMap()                                                    # :188
     sup = Support(hd.ctx)
+    auto = None
     try:
+        if isinstance(lo, str):
+            if lo != "auto":
+                raise ValueError("the range is two numbers, or lo = \"auto\"")
+            auto = estimate_range(hd, g, vm, share, npairs, **(auto_args or {}))
+            lo, hi = auto["lo"], auto["hi"]
         if npairs > 0:
             g.walkPairs(vm, sup, share, npairs, lo, hi)                     # :213-263, this rank's pairs
         hd.reduce_support(g, sup)                                           # every rank's walks summed, before any split
@@ -52,8 +72,11 @@ def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs) -> di
     finally:
         sup.close()
         vm.close()
-    return {"supported_edge_pairs": sup_pairs, "bad_pairs": bad, "orientations_walked": walked, "removed_edges": removed,
-            "new_nodes": new_nodes}
+    out = {"supported_edge_pairs": sup_pairs, "bad_pairs": bad, "orientations_walked": walked, "removed_edges": removed,
+           "new_nodes": new_nodes}
+    if auto is not None:
+        out["insert_range"] = {key: auto[key] for key in auto if key != "hist"}
+    return out
 
 
 def _rank_share(hd: HipDist, data: PairedEndData, take_first: int | None):
@@ -63,12 +86,14 @@ def _rank_share(hd: HipDist, data: PairedEndData, take_first: int | None):
 
 
 def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds=3, take_first: int | None = None, retain: bool = True,
-                simplify: bool = False, walk_pairs=None, classified: bool = True) -> tuple[HipGraph, dict]:
+                simplify: bool = False, walk_pairs=None, classified: bool = True, auto_range=None) -> tuple[HipGraph, dict]:
     """One rank's part of the N-rank GraphBuilder (+ GraphSimplifier pairs stage) -> (this rank's graph replica, stats).
     `stats` holds graph_builder's JSON keys (the walk_pairs object only with walk_pairs) plus occurrences_sent,
     occurrences_owned (this rank's windows) and world.  rounds = "auto": the cutoff is the valley of the REDUCED count spectrum
     (gk_dist_spectrum: every rank filters alike), 3 when it has none; `stats` then also holds rounds_auto, valley, peak and
-    genome_size_estimate, and "rounds" is the number used.  The caller closes the graph."""
+    genome_size_estimate, and "rounds" is the number used.  walk_pairs = (cutoff, "auto", None): the range of the walks is
+    estimated from the pairs over all ranks (estimate_range; auto_range = its max_insert / trim / min_observations as a dict).
+    The caller closes the graph."""
     auto = None
     a, b, share = _rank_share(hd, data, take_first)
     pm = DistDNAMap(hd, k)
@@ -97,7 +122,7 @@ def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds=3, take_first: 
             g.simplifyGraph()
         walk = None
         if walk_pairs is not None:
-            walk = _pairs_stage(hd, g, share, b - a, walk_pairs)
+            walk = _pairs_stage(hd, g, share, b - a, walk_pairs, auto_range)
         n2, e2, l2 = g.counts()
     except BaseException:
         g.close()
@@ -114,19 +139,22 @@ def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds=3, take_first: 
     return g, stats
 
 
-def simplify_graph(hd: HipDist, graph_path, data: PairedEndData, cutoff: int, lo: int = 180, hi: int = 250,
-                   take_first: int | None = None) -> tuple[HipGraph, dict]:
+def simplify_graph(hd: HipDist, graph_path, data: PairedEndData, cutoff: int, lo=180, hi=250,
+                   take_first: int | None = None, max_insert: int = 4095, trim: int = 25, min_observations: int = 1000) -> tuple[HipGraph, dict]:
     """One rank's part of GraphSimplifier.startup (S/scripts/GraphSimplifier.scala:152-318) over N ranks: every rank loads the
     same graph file (:152-153, so the replicas are identical, ids included), then walks its own share of the pairs and the
     supports are summed over the ranks before the split, as in build_graph's pairs stage.  The range defaults to the
-    reference's 180 to 250 (:146).  -> (this rank's graph, stats): k, the live counts before and after, the walk_pairs object,
+    reference's 180 to 250 (:146); lo = "auto" estimates it from the same pairs over all ranks before walking (estimate_range:
+    max_insert, trim and min_observations are its knobs — choices, not measurements — and walk_pairs["insert_range"] says what
+    was found; without an estimate the walks fall back to 180 to 250).  -> (this rank's graph, stats): k, the live counts before and after, the walk_pairs object,
     components_histogram_2 and max_component_size of the final graph (:320-331), and world.  COLLECTIVE.  The caller closes
     the graph."""
     g = loadGraph(hd.ctx, graph_path)
     try:
         a, b, share = _rank_share(hd, data, take_first)
         n1, e1, l1 = g.counts()
-        walk = _pairs_stage(hd, g, share, b - a, (cutoff, lo, hi))
+        walk = _pairs_stage(hd, g, share, b - a, (cutoff, lo, hi),
+                            {"max_insert": max_insert, "trim": trim, "min_observations": min_observations})
         n2, e2, l2 = g.counts()
         sizes, _ = g.componentStats()
         _, hist2 = g.componentHistograms()

@@ -218,6 +218,21 @@ class HipGraph:
         buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)
         L.check(L.lib().gk_graph_walk_pairs(self.h, positions.h, support.h, L.ptr(buf, C.c_uint8), buf.size, npairs, range_lo, range_hi), self.ctx.h)
 
+    def pairDistances(self, positions, data, bins: int = 4096, take_first=None):
+        """The fragment lengths of the pairs whose mates' first k-mers lie on one edge (the rule: include/genome_amd.h, "the
+        insert range") -> (hist, classes): hist[D] = orientations counted at fragment length D (uint64[bins]; bins - 1 is the
+        largest length looked for, and part of the rule), classes = {name: orientations} over PAIR_CLASSES.  `data`: a
+        PairedEndData (its first `take_first` pairs), or (bin bytes, npairs).  Neither the graph nor `positions` (getGraphMap
+        of this graph as it is now) changes."""
+        bin_bytes, npairs = (data.bin, data.count) if hasattr(data, "bin") else data
+        if take_first is not None:
+            npairs = max(0, min(int(take_first), npairs))
+        buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)
+        hist, cls = np.zeros(max(int(bins), 1), np.uint64), np.zeros(len(PAIR_CLASSES), np.uint64)
+        L.check(L.lib().gk_graph_pair_distances(self.h, positions.h, L.ptr(buf, C.c_uint8) if buf.size else None, buf.size, npairs, int(bins),
+                                                L.ptr(hist, C.c_uint64), L.ptr(cls, C.c_uint64)), self.ctx.h)
+        return hist, dict(zip(PAIR_CLASSES, (int(x) for x in cls)))
+
     def splitBySupport(self, support: "Support", cutoff: int):
         """:272-316 -> (edges removed, nodes added); call simplifyGraph() next (:318)."""
         rm, nn = C.c_uint64(), C.c_uint64()
@@ -274,6 +289,25 @@ class HipGraph:
                           dna.unpack(int(e["elo"][i]), int(e["ehi"][i]), k),
                           dna.unpack_2bit(e["seq"][o:o + (ln + 3) // 4], ln)))
         return nodes, edges
+
+
+# the classes of gk_graph_pair_distances, in the order of its `classes` array
+PAIR_CLASSES = ("orientations", "unplaced", "repetitive", "apart", "ambiguous", "reversed", "beyond", "near_end", "counted")
+# what the tools fall back to without an estimate: the reference's `180 to 250` (GraphSimplifier.scala:146)
+REFERENCE_RANGE = (180, 250)
+
+
+def insertRange(hist, trim: int = 25, min_observations: int = 1000):
+    """gk_insert_range over a pairDistances histogram -> (lo, hi, median) in bases, or None when the histogram holds fewer than
+    max(min_observations, 1) observations ("no estimate": callers fall back to REFERENCE_RANGE and say so).  lo / hi cut `trim`
+    thousandths off either tail (0: the smallest and largest length seen; at most 499).  Both defaults are choices, not
+    measurements.  Host code: no context, no GPU."""
+    h = np.ascontiguousarray(hist, np.uint64)
+    lo, hi, med = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    L.check(L.lib().gk_insert_range(L.ptr(h, C.c_uint64), len(h), int(trim), int(min_observations), C.byref(lo), C.byref(hi), C.byref(med)))
+    if sum(int(x) for x in h) < max(int(min_observations), 1):
+        return None
+    return lo.value, hi.value, med.value
 
 
 def buildGraph(k: int, kmersFreq) -> HipGraph:

@@ -369,6 +369,7 @@ class PartitionedDNAMap {
     void barrier() { check(gk_dist_barrier(d_), ctx_.handle()); }
     // every rank's support (its share of the pairs walked on its replica) becomes the sum over all ranks (gk_dist_reduce_support)
     void reduceSupport(Graph &graph, Support &support);
+    gk_dist *distHandle() const { return d_; }
 
   private:
     Context &ctx_;
@@ -588,6 +589,20 @@ class Graph {
         check(gk_graph_walk_pairs(h_, positions.handle(), support.handle(), data.bin.data() + b0, b1 - b0, endPair - firstPair, rangeLo, rangeHi),
               ctx_.handle());
     }
+    // The fragment lengths of the pairs whose mates' first k-mers lie on one edge (include/genome_amd.h, "the insert range"):
+    // hist[D] over bins = maxInsert + 1 lengths and the nine classes {orientations, unplaced, repetitive, apart, ambiguous,
+    // reversed, beyond, near_end, counted}.  pm != nullptr: pairs [firstPair, endPair) are this rank's share and the result is
+    // the sum over the ranks (COLLECTIVE).
+    struct PairDistances { std::vector<uint64_t> hist; uint64_t classes[9] = {}; };
+    static constexpr const char *pairClassNames[9] = {"orientations", "unplaced", "repetitive", "apart", "ambiguous", "reversed", "beyond", "near_end", "counted"};
+    PairDistances pairDistances(PositionMap &positions, const PairedEndData &data, uint64_t takeFirst, uint32_t bins = 4096) {
+        PairDistances r;
+        r.hist.resize(bins >= 1 ? bins : 1);
+        check(gk_graph_pair_distances(h_, positions.handle(), data.bin.data(), data.bin.size(), std::min<uint64_t>(data.count, takeFirst), bins,
+                                      r.hist.data(), r.classes), ctx_.handle());
+        return r;
+    }
+    PairDistances pairDistances(PartitionedDNAMap &pm, PositionMap &positions, const PairedEndData &data, uint64_t firstPair, uint64_t endPair, uint32_t bins = 4096);
     gk_graph *handle() const { return h_; }
     // :272-316 -> (edges removed, nodes added); simplifyGraph() is the next call (:318)
     std::pair<uint64_t, uint64_t> splitBySupport(const Support &support, int cutoff) {
@@ -705,6 +720,30 @@ class Graph {
     int k_;
     gk_graph *h_ = nullptr;
 };
+
+inline Graph::PairDistances Graph::pairDistances(PartitionedDNAMap &pm, PositionMap &positions, const PairedEndData &data, uint64_t firstPair, uint64_t endPair,
+                                                 uint32_t bins) {
+    PairDistances r;
+    r.hist.resize(bins >= 1 ? bins : 1);
+    size_t b0 = 0, b1 = 0;
+    if (endPair > firstPair) std::tie(b0, b1) = pairBytes(data, firstPair, endPair);
+    check(gk_dist_pair_distances(pm.distHandle(), h_, positions.handle(), data.bin.data() + b0, b1 - b0, endPair > firstPair ? endPair - firstPair : 0, bins,
+                                 r.hist.data(), r.classes), ctx_.handle());
+    return r;
+}
+
+// gk_insert_range over a pairDistances histogram: lo / hi cut trimPermille thousandths off either tail, median; estimated =
+// false ("no estimate", fewer than max(minObservations, 1) observations): lo / hi are then the reference's 180 / 250
+// (GraphSimplifier.scala:146).  The two defaults are choices, not measurements.  Host code: no context, no GPU.
+struct InsertRange { uint32_t lo = 180, hi = 250, median = 0; bool estimated = false; uint64_t observations = 0; };
+inline InsertRange insertRange(const std::vector<uint64_t> &hist, uint32_t trimPermille = 25, uint64_t minObservations = 1000) {
+    InsertRange r;
+    uint32_t lo = 0, hi = 0, med = 0;
+    check(gk_insert_range(hist.data(), (uint32_t)hist.size(), trimPermille, minObservations, &lo, &hi, &med), nullptr);
+    for (uint64_t c : hist) r.observations += c;
+    if (r.observations >= std::max<uint64_t>(minObservations, 1)) { r.lo = lo; r.hi = hi; r.median = med; r.estimated = true; }
+    return r;
+}
 
 inline void PartitionedDNAMap::reduceSupport(Graph &graph, Support &support) {
     check(gk_dist_reduce_support(d_, graph.handle(), support.handle()), ctx_.handle());

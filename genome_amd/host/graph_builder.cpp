@@ -4,7 +4,7 @@
 // The reference logs its counters through akka Logging (:34-53); here they are one JSON object.
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
-//                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI]
+//                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]]
 //                 [--out prefix] [--save-graph PATH] [--correct N|auto]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
 //   --fastq converts the FASTQ file on the GPU first (Convert2bin, gk_fastq; --split N = its n, default 36) and takes the pair
@@ -92,7 +92,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI] [--out prefix] [--save-graph PATH] "
+                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--out prefix] [--save-graph PATH] "
                              "[--correct N|auto] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
@@ -113,6 +113,8 @@ int main(int argc, char **argv) {
     bool correct = false;                         // --correct
     uint32_t solid = 0;                           // 0 = auto: the valley of the first count's spectrum
     int walkCutoff = -1, walkLo = 180, walkHi = 250;
+    bool walkAuto = false;                                   // --walk-pairs CUTOFF auto: the range is measured from the pairs (graph_simplifier --range auto)
+    long maxInsert = 4095;
     std::string out, idFile, saveGraph, spectrumPath;
     int world = 0, rank = 0;                      // world 0: one GPU, no communicator
     for (int i = 4; i < argc; i++) {
@@ -142,6 +144,8 @@ int main(int argc, char **argv) {
             if (!std::strcmp(argv[++i], "auto")) solid = 0;
             else if ((solid = (uint32_t)std::stoul(argv[i])) == 0) { std::fprintf(stderr, "--correct N needs N >= 1 (or auto)\n"); return 2; }
         }
+        else if (!std::strcmp(argv[i], "--walk-pairs") && i + 2 < argc && !std::strcmp(argv[i + 2], "auto")) { walkCutoff = std::stoi(argv[++i]); walkAuto = true; i++; }
+        else if (!std::strcmp(argv[i], "--max-insert") && i + 1 < argc) { maxInsert = std::stol(argv[++i]); if (maxInsert < 1 || maxInsert > 65535) { std::fprintf(stderr, "--max-insert N is 1..65535\n"); return 2; } }
         else if (!std::strcmp(argv[i], "--walk-pairs") && i + 3 < argc) { walkCutoff = std::stoi(argv[++i]); walkLo = std::stoi(argv[++i]); walkHi = std::stoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
@@ -252,8 +256,25 @@ int main(int argc, char **argv) {
         // --simplify = GraphSimplifier.scala:317-318, applied to the graph GraphBuilder hands over (i.e. after retain)
         if (simplify) { graph.removeBubbles(); graph.simplifyGraph(); }
         uint64_t supPairs = 0, badPairs = 0, walked = 0, removedEdges = 0, newNodes = 0;
+        genome::InsertRange insertEst;
         if (walkCutoff >= 0) {
             auto graphMap = graph.getGraphMap();                                                         // GraphSimplifier.scala:188
+            if (walkAuto) {                                                                              // the same pairs, before walking; over the ranks one histogram
+                genome::Graph::PairDistances dist;
+                if (world) {
+                    const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
+                    dist = graph.pairDistances(*pm, graphMap, data, a, b, (uint32_t)maxInsert + 1);
+                } else {
+                    dist = graph.pairDistances(graphMap, data, takeFirst, (uint32_t)maxInsert + 1);
+                }
+                insertEst = genome::insertRange(dist.hist);
+                walkLo = (int)insertEst.lo; walkHi = (int)insertEst.hi;
+                if (rank == 0 && insertEst.estimated)
+                    std::fprintf(stderr, "insert range %u to %u, median %u, from %llu observations\n", insertEst.lo, insertEst.hi, insertEst.median, (unsigned long long)insertEst.observations);
+                else if (rank == 0)
+                    std::fprintf(stderr, "no estimate of the insert range (%llu observations): falling back to the reference's %u to %u\n",
+                                 (unsigned long long)insertEst.observations, insertEst.lo, insertEst.hi);
+            }
             genome::Support support(ctx);
             if (world) {                                                                                 // this rank's pairs, then the sum over the ranks
                 const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
@@ -294,6 +315,9 @@ int main(int argc, char **argv) {
             for (size_t i = 0; i < bubblePairs.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)bubblePairs[i]);
             std::printf("]},");
         }
+        if (walkCutoff >= 0 && walkAuto)
+            std::printf("\"insert_range\":{\"lo\":%u,\"hi\":%u,\"estimated\":%s,\"observations\":%llu},", insertEst.lo, insertEst.hi, insertEst.estimated ? "true" : "false",
+                        (unsigned long long)insertEst.observations);
         if (walkCutoff >= 0)
             std::printf("\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},",
                         (unsigned long long)supPairs, (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges,

@@ -3,11 +3,18 @@
 // its nodes by the pairs' support and simplifies it.  The reference logs its counters (:266, :320-331); here they are one JSON
 // object.
 //
-//   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI] [--take-first N]
+//   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
+//                    [--take-first N]
 //                    [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]
 //   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
 //   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
 //   k comes from the graph (:153); the range defaults to the reference's 180 to 250 (:146), the cutoff is genome.cutoff.
+//   --range auto measures the range instead (include/genome_amd.h, "the insert range"): the fragment lengths of the pairs whose
+//   mates lie on one edge, from the same pairs in the same --take-first prefix, before walking; fragments up to --max-insert
+//   bases are looked for (default 4095; part of the rule: an edge shorter than that counts nothing, so set it little above the
+//   largest fragment expected), the range is the central 95 % of at least 1000 observations (both choices, not measurements).
+//   The JSON then holds "insert_range": lo, hi, median, estimated, observations and the nine classes; without an estimate the
+//   walks fall back to 180 to 250 and "estimated" is false.  --insert-hist writes the histogram as text lines "D count".
 //   The stage: getGraphMap (:188), walkPairs over the first N pairs (:213-263), splitBySupport (:272-316), simplifyGraph (:318).
 //   --out writes graph_builder's <prefix>.nodes.txt, .edges.txt, .contigs (:338-347) and .dot; --save-graph writes the final
 //   graph as a graph file (the reference's graphFile, :352).
@@ -61,8 +68,8 @@ int main(int argc, char **argv) {
         argv = fargs.data();
     }
     if (argc < 4) {
-        std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI] [--take-first N] [--out prefix] "
-                             "[--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
+                             "[--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -70,10 +77,15 @@ int main(int argc, char **argv) {
     data.count = std::stoull(argv[3]);
     int cutoff = -1, rangeLo = 180, rangeHi = 250;          // GraphSimplifier.scala:146
     uint64_t takeFirst = UINT64_MAX;
-    std::string out, saveGraph, idFile;
+    std::string out, saveGraph, idFile, insertHist;
     int world = 0, rank = 0;
+    bool rangeAuto = false;
+    long maxInsert = 4095;
     for (int i = 4; i < argc; i++) {
         if (!std::strcmp(argv[i], "--cutoff") && i + 1 < argc) cutoff = std::stoi(argv[++i]);
+        else if (!std::strcmp(argv[i], "--range") && i + 1 < argc && !std::strcmp(argv[i + 1], "auto")) { rangeAuto = true; i++; }
+        else if (!std::strcmp(argv[i], "--max-insert") && i + 1 < argc) maxInsert = std::stol(argv[++i]);
+        else if (!std::strcmp(argv[i], "--insert-hist") && i + 1 < argc) insertHist = argv[++i];
         else if (!std::strcmp(argv[i], "--range") && i + 2 < argc) { rangeLo = std::stoi(argv[++i]); rangeHi = std::stoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--take-first") && i + 1 < argc) takeFirst = std::stoull(argv[++i]);
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
@@ -85,6 +97,10 @@ int main(int argc, char **argv) {
     }
     if (cutoff < 0) {
         std::fprintf(stderr, "--cutoff C is required\n");
+        return 2;
+    }
+    if (maxInsert < 1 || maxInsert > 65535 || (!rangeAuto && !insertHist.empty())) {
+        std::fprintf(stderr, "--max-insert N is 1..65535; --insert-hist PATH goes with --range auto\n");
         return 2;
     }
     if (world && (world < 1 || rank < 0 || rank >= world || idFile.empty())) {
@@ -111,6 +127,28 @@ int main(int argc, char **argv) {
         if (world) pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, idFile));
         auto [n1, e1, l1] = graph.counts();
         auto graphMap = graph.getGraphMap();                                                             // :188
+        genome::Graph::PairDistances dist;
+        genome::InsertRange est;
+        if (rangeAuto) {                                                                                 // the same pairs, before walking
+            if (world) {
+                const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
+                dist = graph.pairDistances(*pm, graphMap, data, a, b, (uint32_t)maxInsert + 1);
+            } else {
+                dist = graph.pairDistances(graphMap, data, takeFirst, (uint32_t)maxInsert + 1);
+            }
+            est = genome::insertRange(dist.hist);
+            rangeLo = (int)est.lo; rangeHi = (int)est.hi;
+            if (rank == 0) {
+                if (est.estimated) std::fprintf(stderr, "insert range %u to %u, median %u, from %llu observations\n", est.lo, est.hi, est.median, (unsigned long long)est.observations);
+                else std::fprintf(stderr, "no estimate of the insert range (%llu observations): falling back to the reference's %u to %u\n",
+                                  (unsigned long long)est.observations, est.lo, est.hi);
+            }
+            if (rank == 0 && !insertHist.empty()) {
+                std::ofstream hf(insertHist);
+                for (size_t d = 0; d < dist.hist.size(); d++) if (dist.hist[d]) hf << d << " " << dist.hist[d] << "\n";
+                if (!hf) throw std::runtime_error("cannot write " + insertHist);
+            }
+        }
         genome::Support support(ctx);
         if (world) {                                                                                     // this rank's pairs, then the sum over the ranks
             const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
@@ -126,11 +164,20 @@ int main(int argc, char **argv) {
         auto [hist, hist2] = graph.componentHistograms();                                                // :320-331
         if (pm) pm->barrier();
         if (rank != 0) return 0;
+        std::string autoJson;
+        if (rangeAuto) {
+            autoJson = "\"insert_range\":{\"lo\":" + std::to_string(est.lo) + ",\"hi\":" + std::to_string(est.hi) + ",\"median\":" +
+                       (est.estimated ? std::to_string(est.median) : std::string("null")) + ",\"estimated\":" + (est.estimated ? "true" : "false") +
+                       ",\"observations\":" + std::to_string(est.observations) + ",\"max_insert\":" + std::to_string(maxInsert) + ",\"classes\":{";
+            for (int c = 0; c < 9; c++)
+                autoJson += std::string(c ? "," : "") + "\"" + genome::Graph::pairClassNames[c] + "\":" + std::to_string(dist.classes[c]);
+            autoJson += "}},";
+        }
         std::printf("{\"k\":%d,\"nodes\":%llu,\"edges\":%llu,\"edges_length\":%llu,"
                     "\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},"
-                    "\"simplified_nodes\":%llu,\"simplified_edges\":%llu,\"simplified_edges_length\":%llu,\"components_histogram_2\":[",
+                    "%s\"simplified_nodes\":%llu,\"simplified_edges\":%llu,\"simplified_edges_length\":%llu,\"components_histogram_2\":[",
                     k, (unsigned long long)n1, (unsigned long long)e1, (unsigned long long)l1, (unsigned long long)supPairs,
-                    (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges, (unsigned long long)newNodes,
+                    (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges, (unsigned long long)newNodes, autoJson.c_str(),
                     (unsigned long long)n2, (unsigned long long)e2, (unsigned long long)l2);
         bool first = true;
         for (const auto &p : hist2) { std::printf("%s[%llu,%llu]", first ? "" : ",", (unsigned long long)p.first, (unsigned long long)p.second); first = false; }

@@ -603,6 +603,61 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
  * replaceStart); out-edges that no group reached are removed.  Follow with gk_graph_simplify (:318).  Node ids: copies are
  * appended; nodes that existed when the call started are the ones visited (the reference iterates a live map: unspecified). */
 int gk_graph_split_by_support(gk_graph *g, const gk_support *sup, int cutoff, uint64_t *removed_edges, uint64_t *new_nodes);
+
+/* ---- the insert range: this project's own rule (the reference hardcodes `180 to 250`, GraphSimplifier.scala:146, with
+ * `160 to 270` commented out beside it, and measures nothing) ----
+ * Distances.  `annotate` (:192-206) computes, for a pair whose two first k-mers lie on one edge, (dist2 - dist1) + k: the length
+ * of the fragment the pair was read from.  gk_graph_pair_distances keeps those numbers.  A pair has the two orientations
+ * gk_graph_walk_pairs walks (:214-219):
+ *   orientation 0: P1 = getAll(p1.take(k)), P2 = getAll(p2.take(k).revComplement);
+ *   orientation 1: P1 = getAll(p2.take(k)), P2 = getAll(p1.take(k).revComplement);
+ * a pair with a mate shorter than k gives none (:213).  With max_dist = bins - 1, every orientation falls into exactly one
+ * class, tested in this order (integers only):
+ *   unplaced    P1 or P2 is empty;
+ *   repetitive  |P1| > 16 or |P2| > 16: the lists are not looked at (the work of one lane is bounded; a fresh graph holds a k-mer
+ *               once and never gets here, the node copies of a split can);
+ *   apart       C = the (a, b) with a in P1, b in P2, both EDGE positions with the same edge id; C is empty;
+ *   ambiguous   |C| >= 2;
+ *   reversed    for the one (a, b), on edge e: D = dist(b) - dist(a) + k, signed; D < k (b does not lie after a: what an
+ *               outward-facing mate-pair library gives.  It is reported, not interpreted);
+ *   beyond      D > max_dist;
+ *   near_end    dist(a) + max_dist - k >= len_e: had the fragment been max_dist long, its far k-mer would lie off the edge;
+ *   counted     none of the above: hist[D] += 1.
+ * near_end removes the truncation bias: an edge shows a fragment only if both its ends fit, so short fragments are seen wherever
+ * the near mate lands and long ones only far from the edge's end.  After the test every D <= max_dist is observable from exactly
+ * the same positions, and short fragments on short edges do not skew the histogram.  So `bins` is part of the rule: it should
+ * exceed the largest fragment expected by little (the tools' --max-insert), not by much — an edge shorter than bins - 1 - k
+ * counts nothing.
+ * hist = uint64[bins], 2 <= bins <= 65536: THIS call's pairs only (callers add batches).  classes = uint64[9] = {orientations,
+ * unplaced, repetitive, apart, ambiguous, reversed, beyond, near_end, counted}; element 0 is the sum of the other eight = twice
+ * the pairs that were not skipped.  Handles, stream shapes and errors are gk_graph_walk_pairs': `positions` =
+ * gk_graph_position_map of THIS graph in its current state on the graph's context (GK_E_KLEN for another k, GK_E_STATE if a
+ * position names nothing live in this graph), the first `npairs` pairs of a `.bin` stream (GK_E_FORMAT if it ends inside a
+ * pair).  Neither the graph nor the position map changes.  On the device: one lane per orientation over the getAll batch's CSR,
+ * a histogram per workgroup in LDS for D < 4096 (one global atomic per non-empty bin at the end), global atomics beyond. */
+int gk_graph_pair_distances(gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbytes, uint64_t npairs, uint32_t bins, uint64_t *hist,
+                            uint64_t *classes);
+/* The range.  Pure host code: no context, no device (gk_spectrum_cutoff's kind).  n = the sum of hist, cum(D) = hist[0] + .. +
+ * hist[D].  n < max(min_observations, 1): GK_OK with *range_lo = *range_hi = *median = 0, "no estimate" (callers fall back to
+ * the reference's 180..250 and say so: the convention of a spectrum without a valley).  Otherwise
+ *   *range_lo = the smallest D with 1000 * cum(D) >  trim_permille * n,
+ *   *range_hi = the smallest D with 1000 * cum(D) >= (1000 - trim_permille) * n,
+ *   *median   = the smallest D with    2 * cum(D) >= n,
+ * compared exactly (128-bit products).  trim_permille = 0 gives the smallest and the largest occupied bin; trim_permille > 499, a
+ * NULL hist or bins outside 2..65536: GK_E_INVALID.  Any output pointer may be NULL.  The callers' defaults, trim_permille = 25
+ * (the central 95 %) and min_observations = 1000, are choices, not measurements.  The result is in annotate's unit, fragment
+ * length; the walks of gk_graph_walk_pairs measure between the mates' first k-mers and the tools pass the range as it is, as the
+ * reference passes its `180 to 250` to both (:146, :199, :104). */
+int gk_insert_range(const uint64_t *hist, uint32_t bins, uint32_t trim_permille, uint64_t min_observations, uint32_t *range_lo, uint32_t *range_hi,
+                    uint32_t *median);
+/* gk_graph_pair_distances over the ranks: every rank passes ITS share of the pairs and its replica of the graph with that
+ * replica's position map; afterwards every rank holds the sums of hist and classes over all ranks (`bins` the same on every
+ * rank).  COLLECTIVE: two all-reduces (uint64 max: a status word; uint64 sum: hist and classes as one array).  gk_dist_spectrum's
+ * failure contract: a rank whose local pass failed (a NULL graph or position map included) still takes part and says so in the
+ * status word: every rank then returns an error, nobody waits, and the handle stays usable.  A NULL `d`, `hist` or `classes`, or
+ * bad `bins`, is GK_E_INVALID on the rank that passes it, before the collective. */
+int gk_dist_pair_distances(gk_dist *d, gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbytes, uint64_t npairs, uint32_t bins, uint64_t *hist,
+                           uint64_t *classes);
 /* live nodes, unspecified order */
 int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap, uint64_t *n);
 /* live edges, unspecified order: start/end k-mer, length in bases, and the edge sequence as 2-bit
