@@ -51,6 +51,7 @@ struct gk_ctx {
     int64_t hook_max_stage = 0;      // test hook: bytes of `.bin` records per staging area (0: 704 MiB), so that a small stream is cut into many chunks
     int hook_host_prefetch = -1;     // host-fed count: 0 = do not upload the next chunk beside the current chunk's P3 / P4 / P5 (A/B)
     int hook_pairs_host = -1;        // paired-end walks: 1 = all of them on host threads over a snapshot (the round-2 form), else one wave per pair orientation
+    int hook_thread_combine = -1;    // read threading (gk_thread.hip): 1 = equal keys of a wave's trip are combined before the atomic, else one atomic per crossing (A/B)
     int hook_pairs_small_sets = -1;  // test hook: the device walks get tiny LDS sets, so that most orientations overflow to the host walker
     int hook_graph_mbt = -1;         // gk_graph_build: 1 = classify and walk on a minimizer-bucketed copy of the table (A/B)
     int hook_graph_mbt_keys = 256;   // ... keys per bucket on average

@@ -40,19 +40,7 @@ gk_ctx *vmap_ctx(const gk_vmap *m);
 // gk_support: pathsMap (:209) + badPairs (:211) on the device
 // ---------------------------------------------------------------------------------------------
 // (SupView, gk_support: gk_support.h)
-__device__ __forceinline__ void sup_add(const SupView &s, u64 key, u32 c) {
-    u64 i = mix64(key) & s.mask;
-    for (u64 n = 0; n <= s.mask; n++) {
-        u64 cur = s.keys[i];
-        if (cur == SUP_EMPTY) {
-            cur = atomicCAS(reinterpret_cast<unsigned long long *>(&s.keys[i]), (unsigned long long)SUP_EMPTY, (unsigned long long)key);
-            if (cur == SUP_EMPTY) { atomicAdd(&s.ctr[0], 1ull); cur = key; }
-        }
-        if (cur == key) { atomicAdd(&s.cnt[i], c); return; }
-        i = (i + 1) & s.mask;
-    }
-    s.ctr[3] = 1;
-}
+// (sup_add, sup_add_checked: gk_support.h)
 __global__ __launch_bounds__(BLOCK) void k_sup_rehash(const u64 *okeys, const u32 *ocnt, u64 ocap, SupView s) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < ocap; i += (u64)gridDim.x * BLOCK)
         if (okeys[i] != SUP_EMPTY) sup_add(s, okeys[i], ocnt[i]);
@@ -62,24 +50,6 @@ __global__ __launch_bounds__(BLOCK) void k_sup_add_list(const u64 *keys, const u
 }
 
 // ---- merging supports (gk_support_add / gk_support_merge, the N-rank reduce of gk_dist.hip) ---------------------------------
-// sup_add with a check the walks do not need (one count per pair orientation cannot wrap): a u32 count that wraps raises ctr[4]
-__device__ __forceinline__ void sup_add_checked(const SupView &s, u64 key, u32 c) {
-    u64 i = mix64(key) & s.mask;
-    for (u64 n = 0; n <= s.mask; n++) {
-        u64 cur = s.keys[i];
-        if (cur == SUP_EMPTY) {
-            cur = atomicCAS(reinterpret_cast<unsigned long long *>(&s.keys[i]), (unsigned long long)SUP_EMPTY, (unsigned long long)key);
-            if (cur == SUP_EMPTY) { atomicAdd(&s.ctr[0], 1ull); cur = key; }
-        }
-        if (cur == key) {
-            const u32 old = atomicAdd(&s.cnt[i], c);
-            if (old + c < old) s.ctr[4] = 1;
-            return;
-        }
-        i = (i + 1) & s.mask;
-    }
-    s.ctr[3] = 1;
-}
 __global__ __launch_bounds__(BLOCK) void k_sup_add_list_checked(const u64 *keys, const u32 *cnt, u64 n, SupView s) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) sup_add_checked(s, keys[i], cnt[i]);
 }

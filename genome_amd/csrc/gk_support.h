@@ -26,6 +26,39 @@ struct gk_support {
 };
 
 namespace gk {
+// ---- the table's two inserts, for the kernels that count into a support (gk_pairs.hip, gk_thread.hip)
+__device__ __forceinline__ void sup_add(const SupView &s, u64 key, u32 c) {
+    u64 i = mix64(key) & s.mask;
+    for (u64 n = 0; n <= s.mask; n++) {
+        u64 cur = s.keys[i];
+        if (cur == SUP_EMPTY) {
+            cur = atomicCAS(reinterpret_cast<unsigned long long *>(&s.keys[i]), (unsigned long long)SUP_EMPTY, (unsigned long long)key);
+            if (cur == SUP_EMPTY) { atomicAdd(&s.ctr[0], 1ull); cur = key; }
+        }
+        if (cur == key) { atomicAdd(&s.cnt[i], c); return; }
+        i = (i + 1) & s.mask;
+    }
+    s.ctr[3] = 1;
+}
+// sup_add with a check the walks do not need (one count per pair orientation cannot wrap): a u32 count that wraps raises ctr[4]
+__device__ __forceinline__ void sup_add_checked(const SupView &s, u64 key, u32 c) {
+    u64 i = mix64(key) & s.mask;
+    for (u64 n = 0; n <= s.mask; n++) {
+        u64 cur = s.keys[i];
+        if (cur == SUP_EMPTY) {
+            cur = atomicCAS(reinterpret_cast<unsigned long long *>(&s.keys[i]), (unsigned long long)SUP_EMPTY, (unsigned long long)key);
+            if (cur == SUP_EMPTY) { atomicAdd(&s.ctr[0], 1ull); cur = key; }
+        }
+        if (cur == key) {
+            const u32 old = atomicAdd(&s.cnt[i], c);
+            if (old + c < old) s.ctr[4] = 1;
+            return;
+        }
+        i = (i + 1) & s.mask;
+    }
+    s.ctr[3] = 1;
+}
+
 // room for `want` distinct pairs at load <= 0.5 (a power of two of slots); contents are kept
 int support_reserve(gk_support *s, u64 want);
 // the first four counters (distinct, bad, walked, full) to the host

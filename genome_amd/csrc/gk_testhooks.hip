@@ -72,6 +72,7 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
     else if (n == "graph_mbt") ctx->hook_graph_mbt = (int)value;
     else if (n == "graph_mbt_keys") ctx->hook_graph_mbt_keys = (int)std::max<int64_t>(16, value);
     else if (n == "pairs_host") ctx->hook_pairs_host = (int)value;
+    else if (n == "thread_combine") ctx->hook_thread_combine = value < 0 ? -1 : value != 0;
     else if (n == "host_prefetch") ctx->hook_host_prefetch = (int)value;
     else if (n == "test_max_stage") ctx->hook_max_stage = (int64_t)std::max<int64_t>(0, value);
     else if (n == "test_pairs_small_sets") ctx->hook_pairs_small_sets = (int)value;

@@ -1,0 +1,339 @@
+// gk_thread.hip — reads threaded through the graph: every window of every read is looked up in the position map, and a window
+// that is a node's k-mer names the in-edge the read arrived by and the out-edge it left by: support[(in, out)] += 1.  The rule is
+// this project's own and stated in include/genome_amd.h (gk_graph_thread_reads); tests/thread_ref.py restates it.
+//
+// Reference: none.  GraphSimplifier.scala:213-217 looks at p1.take(k) and p2.take(k) of a pair and drops the rest of both mates.
+//
+// Shape: k_correct_reads' (gk_correct.hip).  A workgroup stages 64 records in LDS, a wave takes a record, its lanes take windows
+// 64 at a time.  One bit-range extraction gives window i of the read and, reverse-complemented, window n-1-i of the other strand;
+// both go to the position map (gk_vmap_probe.h), and what comes back — nothing, several positions, or the one — is left in a
+// per-wave LDS array, 2 strands x 256 windows x 8 bytes.  After a wave barrier the lanes whose window is a node read their two
+// neighbours from LDS and the node's edges from the graph arrays.
+// Bound: two random position-map probes per window (~1.3 sectors each: the HBM random-access rate, as k_fa_windows); the
+// liveness check of a position reads e_alive / e_len or node_alive at an id that is the same for the lanes along one edge; the
+// graph is otherwise touched at node windows only (out_edge, e_len, e_end), and the support table once per crossing.
+// Contention: at high coverage thousands of reads cross one node, so one counter takes thousands of atomics.  Every crossing is
+// one atomic of its own lane.  Combining the equal keys of a wave's trip first (a ballot loop over the trip's distinct keys, one
+// lane adding per key) was measured and does not pay: a wave holds ONE read, which rarely crosses one (in, out) pair twice, so
+// there is nothing to combine and the loop serialises the trip's adds — 22.5 ms against 7.6 ms where every read crosses nodes
+// (8 x 10^5 reads of a 2 kbp genome), no difference on a 4 Mbp genome (profiles/r11).  The loop stays behind the test-build
+// switch "thread_combine" = 1 as the A/B.
+#include <algorithm>
+#include <memory>
+
+#include "gk_graph.h"
+#include "gk_support.h"
+#include "gk_vmap_probe.h"
+
+namespace gk {
+void vmap_table(const gk_vmap *m, void **slots, uint32_t *nb2, uint32_t *lnb1);
+}
+
+namespace {
+
+constexpr int TH_NSTATS = 7;
+constexpr int TH_MAXW = 256;                   // windows of a record: at most 255 - k + 1 <= 254
+// what a window's lookup left, beside a position: no valid GraphPosition has these bit patterns (an edge id of 2^31 - 1)
+constexpr u64 PV_NONE = ~0ull, PV_MANY = ~0ull - 1;
+enum { TC_OFF = 0, TC_REPEATED = 1, TC_ON_EDGE = 2, TC_BROKEN = 3, TC_CROSSING = 4 };
+
+struct ThreadCounts { u32 reads, inner, cls[5]; };
+
+__device__ __forceinline__ void thread_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// getAll(w) reduced to {none, many, the position}.  The one position is untrusted (k_check_positions' test, gk_pairs.hip): one
+// that names nothing live in this graph raises *bad and counts as none, so that nothing below indexes the graph with it.
+template <int W>
+__device__ __forceinline__ u64 thread_lookup(const Table<W> &pm, const GraphView &g, Kmer<W> x, u32 *bad) {
+    u64 v = 0;
+    const u32 n = vmap_count_one(pm, x, &v);
+    if (n == 0) return PV_NONE;
+    if (n > 1) return PV_MANY;
+    const u32 id = GK_POS_ID(v);
+    const bool ok = GK_POS_IS_EDGE(v) ? (id < g.n_edges && g.e_alive[id] && (u64)GK_POS_DIST(v) < g.e_len[id])
+                                      : ((v >> 32) == 0 && id < g.n_nodes && g.node_alive[id]);
+    if (!ok) { *bad = 1u; return PV_NONE; }
+    return v;
+}
+
+// base p of strand s of the record at tile byte `ro` (s = 1: the reverse complement; complement is ^ 3)
+__device__ __forceinline__ int strand_base(const uint8_t *tb, u32 ro, int len, int s, int p) {
+    const int q = s ? len - 1 - p : p;
+    const int b = (tb[ro + 1 + (q >> 2)] >> ((q & 3) * 2)) & 3;
+    return s ? b ^ 3 : b;
+}
+
+// One record, one wave.  pos[s][i] = what window i of strand s found.
+template <int W>
+__device__ __forceinline__ void thread_record(const Table<W> &pm, const GraphView &g, const u32 *tile, u32 ro, int len, int k, u64 (*pos)[TH_MAXW],
+                                              const SupView &sup, bool combine, u32 *bad, ThreadCounts &st) {
+    const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
+    const int lane = threadIdx.x & 63;
+    if (len < k + 2) return;                                  // no inner window
+    const int n = len - k + 1;
+    const u32 bit0 = (ro + 1) * 8;
+    st.reads++;
+    st.inner += 2u * (u32)(n - 2);
+    // phase 1: both strands' positions, one lane per window of the read
+    for (int p = lane; p < n; p += 64) {
+        const Kmer<W> x = tile_kmer(tile, bit0 + 2 * p, k, (Kmer<W> *)nullptr);
+        pos[0][p] = thread_lookup(pm, g, x, bad);
+        pos[1][n - 1 - p] = thread_lookup(pm, g, revcomp(x, k), bad);
+    }
+    thread_wave_sync();
+    // phase 2: the class of every inner window of either strand (the loops are wave-uniform, a lane may have no window)
+    for (int s = 0; s < 2; s++)
+        for (int i0 = 1; i0 < n - 1; i0 += 64) {
+            const int i = i0 + lane;
+            int cls = -1;
+            u64 key = 0;
+            if (i < n - 1) {
+                const u64 P = pos[s][i];
+                if (P == PV_NONE) cls = TC_OFF;
+                else if (P == PV_MANY) cls = TC_REPEATED;
+                else if (GK_POS_IS_EDGE(P)) cls = TC_ON_EDGE;
+                else {
+                    cls = TC_BROKEN;
+                    const u32 v = (u32)P;
+                    const u64 nx = pos[s][i + 1], pv = pos[s][i - 1];
+                    // exit: the out-edge of v by the base behind the window, and the next window one step along it
+                    const u32 f = g.out_edge[(u64)v * 4 + strand_base(tb, ro, len, s, i + k)];
+                    bool ok = f != NONE && g.e_alive[f] != 0 && nx < PV_MANY;
+                    if (ok) ok = nx == (g.e_len[f] > 1 ? ((1ull << 63) | ((u64)f << 32) | 1ull) : (u64)g.e_end[f]);
+                    // entry: the previous window one step before the end of an in-edge of v, or the start node of one of length 1
+                    u32 e = NONE;
+                    if (ok && pv < PV_MANY) {
+                        if (GK_POS_IS_EDGE(pv)) {
+                            const u32 pe = GK_POS_ID(pv);
+                            if ((u64)GK_POS_DIST(pv) + 1 == g.e_len[pe] && g.e_end[pe] == v) e = pe;
+                        } else {
+                            const u32 pe = g.out_edge[(u64)(u32)pv * 4 + strand_base(tb, ro, len, s, i + k - 1)];
+                            if (pe != NONE && g.e_alive[pe] != 0 && g.e_len[pe] == 1 && g.e_end[pe] == v) e = pe;
+                        }
+                    }
+                    if (e != NONE) { cls = TC_CROSSING; key = ((u64)e << 32) | f; }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 5; c++) st.cls[c] += (u32)__popcll(__ballot(cls == c));
+            if (combine) {
+                // (A/B) equal keys of this trip as one add by the first lane that holds the key
+                unsigned long long todo = __ballot(cls == TC_CROSSING);
+                while (todo) {
+                    const int leader = __ffsll((long long)todo) - 1;
+                    const u64 k0 = (u64)__shfl((unsigned long long)key, leader);
+                    const unsigned long long same = __ballot(cls == TC_CROSSING && key == k0);
+                    if (lane == leader) sup_add_checked(sup, k0, (u32)__popcll(same));
+                    todo &= ~same;
+                }
+            } else if (cls == TC_CROSSING) sup_add_checked(sup, key, 1u);
+        }
+    thread_wave_sync();                                       // before the next record's positions land in `pos`
+}
+
+template <int W>
+__global__ __launch_bounds__(BLOCK) void k_thread_reads(Table<W> pm, GraphView g, int k, const uint8_t *rec, u64 nreads, const u32 *__restrict__ off, u32 stride,
+                                                        WindowLimits lim, SupView sup, u32 combine, u32 *bad, unsigned long long *stats) {
+    __shared__ __attribute__((aligned(16))) u32 tile[TILE_WORDS];
+    __shared__ u64 pos[BLOCK / 64][2][TH_MAXW];
+    __shared__ unsigned long long s_stats[TH_NSTATS];
+    const uint8_t *tb = reinterpret_cast<const uint8_t *>(tile);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x < TH_NSTATS) s_stats[threadIdx.x] = 0;
+    ThreadCounts st{};
+    const u64 ntiles = (nreads + TILE_READS - 1) / TILE_READS;
+    for (u64 ti = blockIdx.x; ti < ntiles; ti += gridDim.x) {                 // (uniform over the workgroup: the barriers are safe)
+        const u64 r0 = ti * TILE_READS;
+        const int nr = (int)min((u64)TILE_READS, nreads - r0);
+        const u64 gb = off ? (u64)off[r0] : r0 * stride, ge = off ? (u64)off[r0 + nr] : (r0 + nr) * stride;
+        const u64 a0 = stage_tile(tile, rec, gb, ge);
+        __syncthreads();
+        for (int r = wave; r < nr; r += BLOCK / 64) {
+            const u32 ro = (u32)((off ? (u64)off[r0 + r] : (r0 + r) * stride) - a0);
+            thread_record<W>(pm, g, tile, ro, record_len(tb, ro, lim), k, pos[wave], sup, combine != 0u, bad, st);
+        }
+        __syncthreads();                                                      // before the next tile is staged over this one
+    }
+    // the counters are wave-uniform: lane 0 of every wave adds them up in LDS, then one global atomic per counter and workgroup
+    if (lane == 0) {
+        const u32 v[TH_NSTATS] = {st.reads, st.inner, st.cls[TC_OFF], st.cls[TC_REPEATED], st.cls[TC_ON_EDGE], st.cls[TC_BROKEN], st.cls[TC_CROSSING]};
+#pragma unroll
+        for (int i = 0; i < TH_NSTATS; i++) if (v[i]) atomicAdd(&s_stats[i], (unsigned long long)v[i]);
+    }
+    __syncthreads();
+    if (threadIdx.x < TH_NSTATS && s_stats[threadIdx.x]) atomicAdd(&stats[threadIdx.x], s_stats[threadIdx.x]);
+}
+
+// the state of one call: a support of its own that the launches count into, the flags and the statistics
+struct ThreadCall {
+    gk_graph *g;
+    gk_vmap *pm;
+    gk_support *local = nullptr;
+    u32 *d_bad = nullptr;
+    unsigned long long *d_stats = nullptr;
+};
+
+SupView thread_sup_view(const gk_support *s) { return SupView{s->d_keys, s->d_cnt, s->cap - 1, s->d_ctr}; }
+
+int thread_check_args(gk_graph *g, gk_vmap *positions, gk_support *sup, uint64_t *stats7, const char *who) {
+    if (stats7) for (int i = 0; i < TH_NSTATS; i++) stats7[i] = 0;
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    const std::string w(who);
+    if (!positions || !sup) return fail(ctx, GK_E_INVALID, w + ": null argument");
+    if (vmap_ctx(positions) != ctx || sup->ctx != ctx) return fail(ctx, GK_E_INVALID, w + ": the position map and the support must live on the graph's context");
+    if (vmap_k(positions) != g->k) return fail(ctx, GK_E_KLEN, w + ": the position map has another k");
+    GK_HIP(ctx, hipSetDevice(ctx->device));
+    return GK_OK;
+}
+
+int thread_begin(ThreadCall &c, DevScratch &tmp) {
+    gk_ctx *ctx = c.g->ctx;
+    if (int rc = gk_support_create(ctx, &c.local)) return rc;
+    // a crossing is (in-edge, out-edge) of one node: at most 4 out-edges behind every edge, at most 16 pairs at every node
+    const GraphView &v = c.g->v;
+    if (int rc = support_reserve(c.local, std::min<u64>(4 * v.n_edges, 16 * v.n_nodes))) return rc;
+    GK_HIP(ctx, tmp.get(&c.d_bad, 1));
+    GK_HIP(ctx, tmp.get(&c.d_stats, TH_NSTATS));
+    GK_HIP(ctx, hipMemsetAsync(c.d_bad, 0, 4, ctx->stream));
+    GK_HIP(ctx, hipMemsetAsync(c.d_stats, 0, TH_NSTATS * 8, ctx->stream));
+    return GK_OK;
+}
+
+// one launch over records resident in HBM; stream-ordered, no sync
+int thread_launch(const ThreadCall &c, const ReadSrc &src, u32 *d_fmt) {
+    gk_ctx *ctx = c.g->ctx;
+    const u64 ntiles = (src.nreads + TILE_READS - 1) / TILE_READS;
+    const int grid = (int)std::min<u64>(ntiles, grid_cap(ctx));
+    const WindowLimits lim{src.max_len, d_fmt};
+    void *slots = nullptr;
+    uint32_t nb2 = 1, lnb1 = 0;
+    vmap_table(c.pm, &slots, &nb2, &lnb1);
+    const int k = c.g->k;
+    const u32 combine = ctx->hook_thread_combine > 0 ? 1u : 0u;
+    GK_BY_W(c.g->W, hipLaunchKernelGGL(k_thread_reads<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, Table<W>{(Slot<W> *)slots, nb2, lnb1, k == 64 ? 1u : 0u, 0u},
+                                       c.g->v, k, src.rec, (u64)src.nreads, src.off, src.stride, lim, thread_sup_view(c.local), combine, c.d_bad, c.d_stats));
+    GK_HIP(ctx, hipGetLastError());
+    return GK_OK;
+}
+
+// the end of a call whose launches are queued: the flags, then the call's counts into `sup` through gk_support_merge, which
+// refuses before it writes if a count would wrap
+int thread_end(const ThreadCall &c, gk_support *sup, bool dev_format, uint64_t *stats7, const char *who) {
+    gk_ctx *ctx = c.g->ctx;
+    const std::string w(who);
+    unsigned long long h_stats[TH_NSTATS] = {}, h_ctr[5] = {};
+    u32 h_bad = 0;
+    GK_HIP(ctx, read_back(ctx, {{h_stats, c.d_stats, sizeof(h_stats)}, {&h_bad, c.d_bad, 4}, {h_ctr, c.local->d_ctr, sizeof(h_ctr)}}));
+    if (dev_format) { if (int rc = ctx_check_format(ctx)) return rc; }
+    if (h_bad) return fail(ctx, GK_E_STATE, w + ": the position map does not belong to this graph (rebuild it after edits)");
+    if (h_ctr[3]) return fail(ctx, GK_E_CAPACITY, w + ": the support table filled up (internal sizing error)");
+    if (h_ctr[4]) return fail(ctx, GK_E_CAPACITY, w + ": a count would pass 2^32-1; nothing was added");
+    if (int rc = gk_support_merge(sup, c.local)) return rc;
+    if (stats7) for (int i = 0; i < TH_NSTATS; i++) stats7[i] = h_stats[i];
+    return GK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gk_graph_thread_reads_dev(gk_graph *g, gk_vmap *positions, gk_support *sup, const void *dev_records, uint64_t nreads, int read_len, uint64_t *stats7) {
+    if (int rc = thread_check_args(g, positions, sup, stats7, "gk_graph_thread_reads_dev")) return rc;
+    gk_ctx *ctx = g->ctx;
+    if (nreads && !dev_records) return fail(ctx, GK_E_INVALID, "gk_graph_thread_reads_dev: null records");
+    if (read_len < 0 || read_len > 255) return fail(ctx, GK_E_FORMAT, "read_len must be 0..255 (one length byte per record)");
+    if (nreads == 0) return GK_OK;
+    ThreadCall c{g, positions};
+    DevScratch tmp(ctx);
+    int rc = thread_begin(c, tmp);
+    std::unique_ptr<gk_support, void (*)(gk_support *)> own(c.local, gk_support_destroy);
+    if (rc) return rc;
+    ReadSrc src;
+    src.rec = (const uint8_t *)dev_records;
+    src.nreads = nreads;
+    src.stride = 1 + (u32)(read_len + 3) / 4;
+    src.max_len = read_len;
+    if ((rc = thread_launch(c, src, ctx->d_flags))) return rc;
+    return thread_end(c, sup, true, stats7, "gk_graph_thread_reads_dev");
+}
+
+int gk_graph_thread_reads(gk_graph *g, gk_vmap *positions, gk_support *sup, const uint8_t *bin, size_t nbytes, uint64_t nreads, uint64_t *stats7) {
+    if (int rc = thread_check_args(g, positions, sup, stats7, "gk_graph_thread_reads")) return rc;
+    gk_ctx *ctx = g->ctx;
+    if (nreads && !bin) return fail(ctx, GK_E_INVALID, "gk_graph_thread_reads: null stream");
+    if (nreads == 0) return GK_OK;
+    // the framing, walked on the host before anything is launched (gk_reads_correct's checks and messages)
+    size_t end = 0;
+    for (u64 r = 0; r < nreads; r++) {
+        if (end >= nbytes) return fail(ctx, GK_E_FORMAT, "truncated .bin stream: record " + std::to_string(r) + " starts past the end");
+        end += 1 + (size_t)(bin[end] + 3) / 4;
+        if (end > nbytes) return fail(ctx, GK_E_FORMAT, "truncated .bin stream inside record " + std::to_string(r));
+    }
+    ThreadCall c{g, positions};
+    DevScratch tmp(ctx);
+    int rc = thread_begin(c, tmp);
+    std::unique_ptr<gk_support, void (*)(gk_support *)> own(c.local, gk_support_destroy);
+    if (rc) return rc;
+    // Chunks of whole records, bounded by the staging area; two areas, so that the next chunk's upload (copy stream) runs beside
+    // this chunk's kernel (gk_reads_correct's scheme, without the way back).
+    const size_t stage_cap = ctx->hook_max_stage > 0 ? (size_t)ctx->hook_max_stage : (size_t)704 << 20;
+    struct Piece { size_t begin = 0, bytes = 0; std::vector<u32> offs; };
+    auto cut = [&](size_t pos) {
+        Piece p;
+        p.begin = pos;
+        while (pos < end) {
+            const size_t rb = 1 + (size_t)(bin[pos] + 3) / 4;
+            if (!p.offs.empty() && pos + rb - p.begin > stage_cap) break;
+            p.offs.push_back((u32)(pos - p.begin));
+            pos += rb;
+        }
+        p.offs.push_back((u32)(pos - p.begin));
+        p.bytes = pos - p.begin;
+        return p;
+    };
+    uint8_t *d_area[2] = {nullptr, nullptr};
+    u32 *d_off = nullptr;
+    size_t off_cap = 0;
+    const size_t area = std::min(stage_cap + 260, end) + 64;
+    auto run = [&]() -> int {
+        GK_HIP(ctx, tmp.get(&d_area[0], area));
+        Piece cur = cut(0);
+        GK_HIP(ctx, hipMemcpyAsync(d_area[0], bin, cur.bytes, hipMemcpyHostToDevice, ctx->stream));
+        for (int i = 0; cur.bytes; i ^= 1) {
+            Piece nxt;
+            if (cur.begin + cur.bytes < end) nxt = cut(cur.begin + cur.bytes);
+            if (cur.offs.size() > off_cap) {
+                if (d_off) tmp.release(d_off);
+                GK_HIP(ctx, tmp.get(&d_off, cur.offs.size()));
+                off_cap = cur.offs.size();
+            }
+            GK_HIP(ctx, hipMemcpyAsync(d_off, cur.offs.data(), cur.offs.size() * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+            ReadSrc src;
+            src.rec = d_area[i];
+            src.nreads = cur.offs.size() - 1;
+            src.off = d_off;
+            src.max_len = 255;                 // the host has walked this framing: every length byte is what the offsets say
+            if (int r = thread_launch(c, src, nullptr)) return r;
+            if (nxt.bytes) {
+                if (!d_area[i ^ 1]) GK_HIP(ctx, tmp.get(&d_area[i ^ 1], area));
+                GK_HIP(ctx, hipMemcpyAsync(d_area[i ^ 1], bin + nxt.begin, nxt.bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+                GK_HIP(ctx, hipEventRecord(ctx->cev[0], ctx->copy_stream));
+            }
+            // (the end of every chunk waits for the main stream: the offsets and the other area are free for the next chunk)
+            GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (nxt.bytes) GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->cev[0], 0));
+            cur = std::move(nxt);
+        }
+        return GK_OK;
+    };
+    rc = run();
+    (void)hipStreamSynchronize(ctx->copy_stream);            // (the areas go back to the pool, which does not wait for uploads)
+    if (rc) return rc;
+    return thread_end(c, sup, false, stats7, "gk_graph_thread_reads");
+}
+
+}  // extern "C"

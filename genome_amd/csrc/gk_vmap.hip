@@ -20,6 +20,7 @@
 
 #include "gk_internal.h"
 #include "gk_tile.h"
+#include "gk_vmap_probe.h"
 
 using namespace gk;
 
@@ -34,8 +35,7 @@ struct gk_vmap {
 };
 
 template <int W> static Table<W> vtable(const gk_vmap *m) { return Table<W>{reinterpret_cast<Slot<W> *>(m->slots), m->nb2, m->lnb1, m->k == 64 ? 1u : 0u}; }
-template <int W> __device__ __forceinline__ void slot_set_value(Slot<W> *s, u64 v) { s->extra = (u32)v; s->aux = (u32)(v >> 32); }
-template <int W> __device__ __forceinline__ u64 slot_value(const Slot<W> *s) { return (u64)s->extra | ((u64)s->aux << 32); }
+// (slot_value / slot_set_value, slot_has_key and the probe itself, vmap_for_each: gk_vmap_probe.h)
 
 template <int W> __global__ __launch_bounds__(BLOCK) void k_vm_clear(Slot<W> *slots, u64 n) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
@@ -67,41 +67,16 @@ __global__ __launch_bounds__(BLOCK) void k_vm_put_new(Table<W> t, const u64 *__r
     if ((threadIdx.x & 63) == 0 && claimed) atomicAdd(&ctr[0], (unsigned long long)claimed);
 }
 
-// a 128-bit key is visible only once BOTH words are in place (seg_claim_unique writes w0 then w1): a reader that meets a slot
-// whose w0 matches and whose w1 is still EMPTY is looking at an insert of ANOTHER launch phase, which these maps never overlap
-// with lookups (handles are externally synchronised), so plain loads suffice here.
-template <int W> __device__ __forceinline__ bool slot_has_key(const Slot<W> *s, Kmer<W> key, u32 tagged, u64 index) {
-    if constexpr (W == 1) return s->w0 == key.lo;
-    else {
-        const Stored<2> k = to_stored(key);
-        return s->w0 == k.w0 && s->w1 == k.w1 && (!tagged || (u32)(index & 3u) == key_tag(key));
-    }
-}
-
 // getAll (ArrayDNAMap.scala:103-113): walk the probe sequence to the first free slot, every slot holding the key contributes.
 // out == nullptr: count only.  The reference prepends as it goes (`ans ::= v`), so its list is in REVERSE probe order;
 // values are written that way too (harmless: the simplifier treats them as sets).
 template <int W>
 __global__ __launch_bounds__(BLOCK) void k_vm_get_all(Table<W> t, const u64 *__restrict__ lo, const u64 *__restrict__ hi, u64 n, u32 limit,
                                                       const unsigned long long *__restrict__ offsets, u32 *__restrict__ counts, u64 *__restrict__ out) {
-    constexpr u32 smask = (1u << SegBits<W>::value) - 1u;
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
         const Kmer<W> key = key_at<W>(lo, hi, i);
-        const u64 h = slot_hash(key);
-        const u64 base = (u64)seg_of(t, h) << SegBits<W>::value;
-        const Slot<W> *seg = t.slots + base;
-        const u32 step = t.tagged ? 4u : 1u;
-        u32 p = t.tagged ? ((seg_pos<W>(h) & ~3u) | key_tag(key)) : seg_pos<W>(h);
-        u32 found = 0;
         const u32 total = out ? counts[i] : 0u;
-        for (u32 s = 0; s <= smask && found < limit; s += step) {
-            if (seg[p].w0 == KEY_EMPTY) break;
-            if (slot_has_key(&seg[p], key, t.tagged, base + p)) {
-                if (out) out[offsets[i] + (total - 1 - found)] = slot_value(&seg[p]);
-                found++;
-            }
-            p = (p + step) & smask;
-        }
+        const u32 found = vmap_for_each(t, key, limit, [&](u64 v, u32 j) { if (out) out[offsets[i] + (total - 1 - j)] = v; });
         if (!out) counts[i] = found;
     }
 }

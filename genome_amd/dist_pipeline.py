@@ -23,7 +23,7 @@ import numpy as np
 from . import dna
 from .dist import DistDNAMap, HipDist
 from .freqfilter import PairedEndData, auto_rounds
-from .graph import REFERENCE_RANGE, HipGraph, Support, buildGraph, insertRange, loadGraph
+from .graph import REFERENCE_RANGE, THREAD_STATS, HipGraph, Support, buildGraph, insertRange, loadGraph
 
 
 def pair_share(npairs: int, world: int, rank: int, take_first: int | None = None) -> tuple[int, int]:
@@ -48,12 +48,17 @@ def estimate_range(hd: HipDist, g: HipGraph, vm, share, npairs: int, max_insert:
             "trim": trim}
 
 
-def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs, auto_args=None) -> dict:
+def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs, auto_args=None, thread_reads: bool = False, walk: bool = True) -> dict:
     """GraphSimplifier.scala:188-318 on this rank's replica `g`: getGraphMap, walkPairs over the rank's `npairs` pairs in `share`,
     the supports summed over the ranks (before any node split), splitBySupport at the cutoff, simplifyGraph -> the walk_pairs
     counters.  lo == "auto": the range is estimated first, from the same pairs (estimate_range with `auto_args`); the counters
-    then hold "insert_range" (estimate_range's result without its histogram)."""
+    then hold "insert_range" (estimate_range's result without its histogram).  thread_reads: both mates of the same pairs are
+    threaded through the graph as single reads into the same support before the reduce (HipGraph.threadReads; the counters
+    then hold "thread_reads", the seven stats summed over the ranks); walk = False skips the walks."""
     cutoff, lo, hi = walk_pairs
+    if not walk and (not thread_reads or isinstance(lo, str)):
+        raise ValueError("walk = False goes with thread_reads = True and a range given as numbers (no walk uses it)")
+    threaded = None
     vm = g.getGraphMap()                                                    # :188
     sup = Support(hd.ctx)
     auto = None
@@ -63,8 +68,12 @@ def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs, auto_
                 raise ValueError("the range is two numbers, or lo = \"auto\"")
             auto = estimate_range(hd, g, vm, share, npairs, **(auto_args or {}))
             lo, hi = auto["lo"], auto["hi"]
-        if npairs > 0:
+        if npairs > 0 and walk:
             g.walkPairs(vm, sup, share, npairs, lo, hi)                     # :213-263, this rank's pairs
+        if thread_reads:
+            mine = g.threadReads(vm, sup, (share, 2 * npairs))              # this rank's reads
+            total = hd.allreduce([float(mine[key]) for key in THREAD_STATS])
+            threaded = {key: int(v) for key, v in zip(THREAD_STATS, total)}
         hd.reduce_support(g, sup)                                           # every rank's walks summed, before any split
         sup_pairs, bad, walked = sup.sizes()                                # :266
         removed, new_nodes = g.splitBySupport(sup, cutoff)                  # :272-316
@@ -76,6 +85,8 @@ def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs, auto_
            "new_nodes": new_nodes}
     if auto is not None:
         out["insert_range"] = {key: auto[key] for key in auto if key != "hist"}
+    if threaded is not None:
+        out["thread_reads"] = threaded
     return out
 
 
@@ -140,21 +151,25 @@ def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds=3, take_first: 
 
 
 def simplify_graph(hd: HipDist, graph_path, data: PairedEndData, cutoff: int, lo=180, hi=250,
-                   take_first: int | None = None, max_insert: int = 4095, trim: int = 25, min_observations: int = 1000) -> tuple[HipGraph, dict]:
+                   take_first: int | None = None, max_insert: int = 4095, trim: int = 25, min_observations: int = 1000,
+                   thread_reads: bool = False, walk: bool = True) -> tuple[HipGraph, dict]:
     """One rank's part of GraphSimplifier.startup (S/scripts/GraphSimplifier.scala:152-318) over N ranks: every rank loads the
     same graph file (:152-153, so the replicas are identical, ids included), then walks its own share of the pairs and the
     supports are summed over the ranks before the split, as in build_graph's pairs stage.  The range defaults to the
     reference's 180 to 250 (:146); lo = "auto" estimates it from the same pairs over all ranks before walking (estimate_range:
     max_insert, trim and min_observations are its knobs — choices, not measurements — and walk_pairs["insert_range"] says what
     was found; without an estimate the walks fall back to 180 to 250).  -> (this rank's graph, stats): k, the live counts before and after, the walk_pairs object,
-    components_histogram_2 and max_component_size of the final graph (:320-331), and world.  COLLECTIVE.  The caller closes
+    components_histogram_2 and max_component_size of the final graph (:320-331), and world.  thread_reads = True threads each
+    rank's share of the reads through the graph into the same support before the reduce (this project's own rule,
+    gk_graph_thread_reads; walk_pairs["thread_reads"] holds the stats over all ranks); walk = False skips the walks, so that the
+    reads alone are the evidence.  COLLECTIVE.  The caller closes
     the graph."""
     g = loadGraph(hd.ctx, graph_path)
     try:
         a, b, share = _rank_share(hd, data, take_first)
         n1, e1, l1 = g.counts()
         walk = _pairs_stage(hd, g, share, b - a, (cutoff, lo, hi),
-                            {"max_insert": max_insert, "trim": trim, "min_observations": min_observations})
+                            {"max_insert": max_insert, "trim": trim, "min_observations": min_observations}, thread_reads, walk)
         n2, e2, l2 = g.counts()
         sizes, _ = g.componentStats()
         _, hist2 = g.componentHistograms()

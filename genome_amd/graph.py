@@ -233,6 +233,29 @@ class HipGraph:
                                                 L.ptr(hist, C.c_uint64), L.ptr(cls, C.c_uint64)), self.ctx.h)
         return hist, dict(zip(PAIR_CLASSES, (int(x) for x in cls)))
 
+    def threadReads(self, positions, support: "Support", data, take_first=None) -> dict:
+        """Every window of every read through `positions` (getGraphMap of this graph as it is now): a window that is a node's
+        k-mer, entered by an in-edge and left by an out-edge of that node, adds one to `support` for that (in, out) pair, on both
+        strands (the rule: include/genome_amd.h, gk_graph_thread_reads) -> the seven stats, named as THREAD_STATS.  `data`: a
+        PairedEndData (both mates of its first `take_first` pairs, as single reads), or (bin bytes, records) (its first
+        `take_first` records).  GkError, and `support` unchanged, on any error; the graph and `positions` never change."""
+        if hasattr(data, "bin"):
+            bin_bytes, nreads = data.bin, 2 * (data.count if take_first is None else max(0, min(int(take_first), data.count)))
+        else:
+            bin_bytes, nreads = data
+            nreads = nreads if take_first is None else max(0, min(int(take_first), nreads))
+        buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)
+        st = np.zeros(len(THREAD_STATS), np.uint64)
+        L.check(L.lib().gk_graph_thread_reads(self.h, positions.h, support.h, L.ptr(buf, C.c_uint8) if buf.size else None, buf.size, nreads,
+                                              L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(THREAD_STATS, (int(x) for x in st)))
+
+    def threadReadsDev(self, positions, support: "Support", d_records: int, nreads: int, read_len: int) -> dict:
+        """threadReads over records resident in HBM at stride 1 + ceil(read_len / 4) -> the seven stats"""
+        st = np.zeros(len(THREAD_STATS), np.uint64)
+        L.check(L.lib().gk_graph_thread_reads_dev(self.h, positions.h, support.h, d_records, nreads, read_len, L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(THREAD_STATS, (int(x) for x in st)))
+
     def splitBySupport(self, support: "Support", cutoff: int):
         """:272-316 -> (edges removed, nodes added); call simplifyGraph() next (:318)."""
         rm, nn = C.c_uint64(), C.c_uint64()
@@ -293,6 +316,8 @@ class HipGraph:
 
 # the classes of gk_graph_pair_distances, in the order of its `classes` array
 PAIR_CLASSES = ("orientations", "unplaced", "repetitive", "apart", "ambiguous", "reversed", "beyond", "near_end", "counted")
+# the statistics of gk_graph_thread_reads, in the order of its `stats7` array: inner_windows is the sum of the five after it
+THREAD_STATS = ("records", "inner_windows", "off_graph", "repeated", "on_edge", "broken", "crossings")
 # what the tools fall back to without an estimate: the reference's `180 to 250` (GraphSimplifier.scala:146)
 REFERENCE_RANGE = (180, 250)
 

@@ -589,6 +589,26 @@ class Graph {
         check(gk_graph_walk_pairs(h_, positions.handle(), support.handle(), data.bin.data() + b0, b1 - b0, endPair - firstPair, rangeLo, rangeHi),
               ctx_.handle());
     }
+    // Reads threaded through the graph (this project's own rule, include/genome_amd.h: gk_graph_thread_reads): every window of both
+    // mates of the first `takeFirst` pairs, as single reads; a window that is a node's k-mer adds one to the support of the
+    // (in-edge, out-edge) the read crossed it by.  -> {records threaded, inner windows, off_graph, repeated, on_edge, broken,
+    // crossings}.  On an error the support is unchanged.
+    struct ThreadStats { uint64_t v[7] = {}; };
+    static constexpr const char *threadStatNames[7] = {"records", "inner_windows", "off_graph", "repeated", "on_edge", "broken", "crossings"};
+    ThreadStats threadReads(PositionMap &positions, Support &support, const PairedEndData &data, uint64_t takeFirst) {
+        ThreadStats st;
+        check(gk_graph_thread_reads(h_, positions.handle(), support.handle(), data.bin.data(), data.bin.size(), 2 * std::min<uint64_t>(data.count, takeFirst),
+                                    st.v), ctx_.handle());
+        return st;
+    }
+    // the same over pairs [firstPair, endPair) only (one rank's share)
+    ThreadStats threadReads(PositionMap &positions, Support &support, const PairedEndData &data, uint64_t firstPair, uint64_t endPair) {
+        ThreadStats st;
+        if (endPair <= firstPair) return st;
+        const auto [b0, b1] = pairBytes(data, firstPair, endPair);
+        check(gk_graph_thread_reads(h_, positions.handle(), support.handle(), data.bin.data() + b0, b1 - b0, 2 * (endPair - firstPair), st.v), ctx_.handle());
+        return st;
+    }
     // The fragment lengths of the pairs whose mates' first k-mers lie on one edge (include/genome_amd.h, "the insert range"):
     // hist[D] over bins = maxInsert + 1 lengths and the nine classes {orientations, unplaced, repetitive, apart, ambiguous,
     // reversed, beyond, near_end, counted}.  pm != nullptr: pairs [firstPair, endPair) are this rank's share and the result is

@@ -4,7 +4,7 @@
 // object.
 //
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
-//                    [--take-first N]
+//                    [--take-first N] [--thread-reads [--no-pairs]]
 //                    [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]
 //   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
 //   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
@@ -15,6 +15,9 @@
 //   largest fragment expected), the range is the central 95 % of at least 1000 observations (both choices, not measurements).
 //   The JSON then holds "insert_range": lo, hi, median, estimated, observations and the nine classes; without an estimate the
 //   walks fall back to 180 to 250 and "estimated" is false.  --insert-hist writes the histogram as text lines "D count".
+//   --thread-reads threads both mates of the same pairs through the graph as single reads (include/genome_amd.h,
+//   gk_graph_thread_reads: this project's own rule) into the same support before the split; --no-pairs skips the walks, so
+//   that the reads alone are the evidence.  The JSON then holds "thread_reads": the seven stats (summed over the ranks).
 //   The stage: getGraphMap (:188), walkPairs over the first N pairs (:213-263), splitBySupport (:272-316), simplifyGraph (:318).
 //   --out writes graph_builder's <prefix>.nodes.txt, .edges.txt, .contigs (:338-347) and .dot; --save-graph writes the final
 //   graph as a graph file (the reference's graphFile, :352).
@@ -69,7 +72,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
-                             "[--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--thread-reads [--no-pairs]] [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -79,7 +82,7 @@ int main(int argc, char **argv) {
     uint64_t takeFirst = UINT64_MAX;
     std::string out, saveGraph, idFile, insertHist;
     int world = 0, rank = 0;
-    bool rangeAuto = false;
+    bool rangeAuto = false, threadReads = false, noPairs = false;
     long maxInsert = 4095;
     for (int i = 4; i < argc; i++) {
         if (!std::strcmp(argv[i], "--cutoff") && i + 1 < argc) cutoff = std::stoi(argv[++i]);
@@ -88,6 +91,8 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--insert-hist") && i + 1 < argc) insertHist = argv[++i];
         else if (!std::strcmp(argv[i], "--range") && i + 2 < argc) { rangeLo = std::stoi(argv[++i]); rangeHi = std::stoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--take-first") && i + 1 < argc) takeFirst = std::stoull(argv[++i]);
+        else if (!std::strcmp(argv[i], "--thread-reads")) threadReads = true;
+        else if (!std::strcmp(argv[i], "--no-pairs")) noPairs = true;
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
         else if (!std::strcmp(argv[i], "--world") && i + 1 < argc) world = std::stoi(argv[++i]);
@@ -101,6 +106,10 @@ int main(int argc, char **argv) {
     }
     if (maxInsert < 1 || maxInsert > 65535 || (!rangeAuto && !insertHist.empty())) {
         std::fprintf(stderr, "--max-insert N is 1..65535; --insert-hist PATH goes with --range auto\n");
+        return 2;
+    }
+    if (noPairs && (!threadReads || rangeAuto)) {
+        std::fprintf(stderr, "--no-pairs goes with --thread-reads, and not with --range auto (no walk uses the range)\n");
         return 2;
     }
     if (world && (world < 1 || rank < 0 || rank >= world || idFile.empty())) {
@@ -150,12 +159,21 @@ int main(int argc, char **argv) {
             }
         }
         genome::Support support(ctx);
+        genome::Graph::ThreadStats threaded;
         if (world) {                                                                                     // this rank's pairs, then the sum over the ranks
             const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
-            graph.walkPairs(graphMap, support, data, a, b, rangeLo, rangeHi);
+            if (!noPairs) graph.walkPairs(graphMap, support, data, a, b, rangeLo, rangeHi);
+            if (threadReads) {
+                threaded = graph.threadReads(graphMap, support, data, a, b);
+                double v[7];
+                for (int i = 0; i < 7; i++) v[i] = (double)threaded.v[i];
+                genome::check(gk_dist_allreduce_f64(pm->distHandle(), v, 7, 0), ctx.handle());
+                for (int i = 0; i < 7; i++) threaded.v[i] = (uint64_t)v[i];
+            }
             pm->reduceSupport(graph, support);                                                           // (before any node split)
         } else {
-            graph.walkPairs(graphMap, support, data, takeFirst, rangeLo, rangeHi);                       // :213-263
+            if (!noPairs) graph.walkPairs(graphMap, support, data, takeFirst, rangeLo, rangeHi);         // :213-263
+            if (threadReads) threaded = graph.threadReads(graphMap, support, data, takeFirst);
         }
         auto [supPairs, badPairs, walked] = support.sizes();                                             // :266 "Bad pairs"
         auto [removedEdges, newNodes] = graph.splitBySupport(support, cutoff);                           // :272-316
@@ -172,6 +190,11 @@ int main(int argc, char **argv) {
             for (int c = 0; c < 9; c++)
                 autoJson += std::string(c ? "," : "") + "\"" + genome::Graph::pairClassNames[c] + "\":" + std::to_string(dist.classes[c]);
             autoJson += "}},";
+        }
+        if (threadReads) {
+            autoJson += "\"thread_reads\":{";
+            for (int c = 0; c < 7; c++) autoJson += std::string(c ? "," : "") + "\"" + genome::Graph::threadStatNames[c] + "\":" + std::to_string(threaded.v[c]);
+            autoJson += "},";
         }
         std::printf("{\"k\":%d,\"nodes\":%llu,\"edges\":%llu,\"edges_length\":%llu,"
                     "\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},"

@@ -604,6 +604,47 @@ int gk_graph_walk_pairs(gk_graph *g, gk_vmap *positions, gk_support *sup, const 
  * appended; nodes that existed when the call started are the ones visited (the reference iterates a live map: unspecified). */
 int gk_graph_split_by_support(gk_graph *g, const gk_support *sup, int cutoff, uint64_t *removed_edges, uint64_t *new_nodes);
 
+/* ---- reads threaded through the graph: this project's own rule (the reference looks at p1.take(k) and p2.take(k) of a pair,
+ * GraphSimplifier.scala:213-217, and drops every other window of both mates) ----
+ * Let G be a graph of word size k, PM = gk_graph_position_map of G in its current state, and getAll(w) the positions PM holds for
+ * the k-mer w, taken as it is with no canonicalisation (as gk_graph_walk_pairs takes its keys).
+ * A record of L bases is threaded iff L >= k + 2; shorter records are skipped.  A threaded record r has two strands, s = r and
+ * s = revComplement(r).  On a strand, w_i = s[i .. i+k) for i = 0 .. L-k and P_i = getAll(w_i).  The inner windows are
+ * i = 1 .. L-k-1.  Every inner window of every strand falls into exactly one class, tested in this order:
+ *   1. off_graph  P_i is empty;
+ *   2. repeated   |P_i| >= 2 (the copies a node split leaves share a k-mer; a fresh graph never gets here);
+ *   3. on_edge    the one position is an EDGE position;
+ *   4. otherwise P_i = { Node v }.
+ *        exit:   f = out_edge(v, s[i+k]) is a live edge, |P_{i+1}| = 1, and its position is Edge(f, 1) if len_f > 1, or
+ *                Node(end(f)) if len_f = 1;
+ *        entry:  |P_{i-1}| = 1, and its position is either Edge(e, len_e - 1) with end(e) = v, or Node(u) with
+ *                e = out_edge(u, s[i+k-1]) live, len_e = 1 and end(e) = v;
+ *      broken     entry or exit fails;
+ *   5. crossing   support[(e, f)] += 1.
+ * Counts are per crossing: a read that crosses one node three times adds three (no per-read set is kept, unlike the
+ * once-per-orientation rule of the pair walk).  A read and its reverse complement give twin crossings, so a strand-closed graph
+ * gets strand-closed support.  bad_pairs and walked_orientations of the support do not move.
+ * stats7 (may be NULL) = uint64[7] = {records threaded, inner windows, off_graph, repeated, on_edge, broken, crossings}; element
+ * 1 is the sum of elements 2..6.
+ * Positions are untrusted: the one position of a window (windows 0 and L-k included: they are neighbours) whose id is out of
+ * bounds, or names a dead node or edge, or carries a distance >= len, makes the call return GK_E_STATE, as gk_graph_walk_pairs
+ * does.  The positions of a repeated window are not looked at.
+ * Stream shapes and errors are gk_reads_correct's / gk_reads_correct_dev's: a host `.bin` stream, ragged or fixed, validated on
+ * the host first (GK_E_FORMAT if it ends inside a record) and sent through the device in chunks; or a device buffer of fixed
+ * stride 1 + ceil(read_len / 4), where a length byte above read_len is clamped, never followed, and the call fails with
+ * GK_E_FORMAT.  Handle errors are gk_graph_walk_pairs': GK_E_KLEN for a position map of another k, GK_E_INVALID for NULL handles
+ * or another context.  nreads = 0 is GK_OK with zero stats.  A count that would pass 2^32-1 is GK_E_CAPACITY (gk_support_add's
+ * rule).  On ANY error sup is unchanged (the call counts into a support of its own and merges it at the end), and stats7 is
+ * zero.  Neither the graph nor the position map changes.  Over N ranks every rank threads its share into its own support and
+ * gk_dist_reduce_support sums them: there is no collective of its own.
+ * On the device: a workgroup stages 64 records in LDS, a wave takes a record, a lane a window — which is window i of one strand
+ * and, reverse-complemented, window L-k-i of the other: two position-map probes per window, the graph is read at node windows
+ * only.
+ * What it resolves: the split is per node, as the reference's is.  Reads resolve junctions and remove connections that no read
+ * spans; a repeat longer than k needs read paths over several nodes, which this call does not build. */
+int gk_graph_thread_reads(gk_graph *g, gk_vmap *positions, gk_support *sup, const uint8_t *bin, size_t nbytes, uint64_t nreads, uint64_t *stats7);
+int gk_graph_thread_reads_dev(gk_graph *g, gk_vmap *positions, gk_support *sup, const void *dev_records, uint64_t nreads, int read_len, uint64_t *stats7);
+
 /* ---- the insert range: this project's own rule (the reference hardcodes `180 to 250`, GraphSimplifier.scala:146, with
  * `160 to 270` commented out beside it, and measures nothing) ----
  * Distances.  `annotate` (:192-206) computes, for a pair whose two first k-mers lie on one edge, (dist2 - dist1) + k: the length

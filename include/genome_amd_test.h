@@ -26,7 +26,8 @@ extern "C" {
  * tables beyond 34 GB) and "test_max_nb2" (the pipeline refuses tables of more fine buckets per L1 bucket) stage the
  * large-table paths on small tables.
  * Round 3: "graph_mbt" / "graph_mbt_keys" (gk_graph_build on a minimizer-bucketed copy of the table; keys per bucket),
- * "pairs_host" (1: the paired-end walks on host threads), "test_pairs_small_sets" (tiny LDS sets: walks overflow to the host
+ * "pairs_host" (1: the paired-end walks on host threads), "thread_combine" (1: gk_graph_thread_reads combines the equal keys of
+ * a wave's trip before the atomic instead of adding every crossing with an atomic of its own), "test_pairs_small_sets" (tiny LDS sets: walks overflow to the host
  * walker), "host_prefetch" (0: a host-fed count does not upload the next chunk beside the current one), "test_max_stage" (bytes
  * per staging area of a host-fed count), "cc_find" (the components' link pass: 3 = look before the CAS, the default; 0 / 1 / 2 =
  * path halving only / no path writes / start node only), "target_load_pct" (load factor new tables are sized for, percent;
