@@ -9,6 +9,7 @@
 // written once, 16 bytes at a time; no global atomics but ten per workgroup for the statistics.
 #include <algorithm>
 
+#include "gk_binstream.h"
 #include "gk_graph.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -205,20 +206,15 @@ int gk_reads_correct_dev(gk_map *counts, const void *dev_records, uint64_t nread
     if (int rc = check_correct_args(counts, solid, stats, "gk_reads_correct_dev")) return rc;
     gk_ctx *ctx = counts->ctx;
     if (nreads && (!dev_records || !dev_out)) return fail(ctx, GK_E_INVALID, "gk_reads_correct_dev: null records");
-    if (read_len < 0 || read_len > 255) return fail(ctx, GK_E_FORMAT, "read_len must be 0..255 (one length byte per record)");
+    if (int rc = check_read_len(ctx, read_len)) return rc;
     if (nreads == 0) return GK_OK;
-    ReadSrc src;
-    src.rec = (const uint8_t *)dev_records;
-    src.nreads = nreads;
-    src.stride = 1 + (u32)(read_len + 3) / 4;
-    src.max_len = read_len;
+    const ReadSrc src = ReadSrc::fixed(dev_records, nreads, read_len);
     const uintptr_t in0 = (uintptr_t)dev_records, out0 = (uintptr_t)dev_out, span = (uintptr_t)(nreads * src.stride);
     if (in0 != out0 && in0 < out0 + span && out0 < in0 + span)
         return fail(ctx, GK_E_INVALID, "gk_reads_correct_dev: dev_out overlaps dev_records without being the same buffer");
     DevScratch tmp(ctx);
     unsigned long long *d_stats = nullptr, h_stats[GK_CORRECT_NSTATS] = {};
-    GK_HIP(ctx, tmp.get(&d_stats, GK_CORRECT_NSTATS));
-    GK_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(h_stats), ctx->stream));
+    GK_HIP(ctx, tmp.zeroed(&d_stats, GK_CORRECT_NSTATS));
     if (int rc = correct_launch(counts, src, (uint8_t *)dev_out, solid, ctx->d_flags, d_stats)) return rc;
     GK_HIP(ctx, read_back(ctx, {{h_stats, d_stats, sizeof(h_stats)}}));
     if (stats) for (int i = 0; i < GK_CORRECT_NSTATS; i++) stats[i] = h_stats[i];
@@ -229,75 +225,22 @@ int gk_reads_correct(gk_map *counts, const uint8_t *bin_host, size_t nbytes, uin
     if (int rc = check_correct_args(counts, solid, stats, "gk_reads_correct")) return rc;
     gk_ctx *ctx = counts->ctx;
     if (nreads && (!bin_host || !bin_out)) return fail(ctx, GK_E_INVALID, "gk_reads_correct: null stream");
-    // the framing, walked on the host before anything is written (gk_map_count_reads' checks and messages)
+    // the framing, walked on the host before anything is written
     size_t end = 0;
-    for (u64 r = 0; r < nreads; r++) {
-        if (end >= nbytes) return fail(ctx, GK_E_FORMAT, "truncated .bin stream: record " + std::to_string(r) + " starts past the end");
-        end += 1 + (size_t)(bin_host[end] + 3) / 4;
-        if (end > nbytes) return fail(ctx, GK_E_FORMAT, "truncated .bin stream inside record " + std::to_string(r));
-    }
-    // Chunks of whole records, bounded by the staging area; two areas, so that the next chunk's upload (copy stream) runs beside
-    // this chunk's kernel.  A chunk is corrected in place in its area and comes back to bin_out at the offset it came from.
-    const size_t stage_cap = ctx->hook_max_stage > 0 ? (size_t)ctx->hook_max_stage : (size_t)704 << 20;
-    struct Piece { size_t begin = 0, bytes = 0; std::vector<u32> offs; };
-    auto cut = [&](size_t pos) {
-        Piece c;
-        c.begin = pos;
-        while (pos < end) {
-            const size_t rb = 1 + (size_t)(bin_host[pos] + 3) / 4;
-            if (!c.offs.empty() && pos + rb - c.begin > stage_cap) break;
-            c.offs.push_back((u32)(pos - c.begin));
-            pos += rb;
-        }
-        c.offs.push_back((u32)(pos - c.begin));
-        c.bytes = pos - c.begin;
-        return c;
-    };
-    DevScratch tmp(ctx);
-    uint8_t *d_area[2] = {nullptr, nullptr};
-    u32 *d_off = nullptr;
-    unsigned long long *d_stats = nullptr, h_stats[GK_CORRECT_NSTATS] = {};
-    size_t off_cap = 0;
-    const size_t area = std::min(stage_cap + 260, end) + 64;
-    int rc = GK_OK;
-    auto run = [&]() -> int {
-        if (end == 0) return GK_OK;
-        GK_HIP(ctx, tmp.get(&d_area[0], area));
-        GK_HIP(ctx, tmp.get(&d_stats, GK_CORRECT_NSTATS));
-        GK_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(h_stats), ctx->stream));
-        Piece cur = cut(0);
-        GK_HIP(ctx, hipMemcpyAsync(d_area[0], bin_host, cur.bytes, hipMemcpyHostToDevice, ctx->stream));
-        for (int i = 0; cur.bytes; i ^= 1) {
-            Piece nxt;
-            if (cur.begin + cur.bytes < end) nxt = cut(cur.begin + cur.bytes);
-            if (cur.offs.size() > off_cap) {
-                if (d_off) tmp.release(d_off);
-                GK_HIP(ctx, tmp.get(&d_off, cur.offs.size()));
-                off_cap = cur.offs.size();
-            }
-            GK_HIP(ctx, hipMemcpyAsync(d_off, cur.offs.data(), cur.offs.size() * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-            ReadSrc src;
-            src.rec = d_area[i];
-            src.nreads = cur.offs.size() - 1;
-            src.off = d_off;
-            src.max_len = 255;                 // the host has walked this framing: every length byte is what the offsets say
-            if (int r = correct_launch(counts, src, d_area[i], solid, nullptr, d_stats)) return r;
-            if (nxt.bytes) {
-                if (!d_area[i ^ 1]) GK_HIP(ctx, tmp.get(&d_area[i ^ 1], area));
-                GK_HIP(ctx, hipMemcpyAsync(d_area[i ^ 1], bin_host + nxt.begin, nxt.bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-                GK_HIP(ctx, hipEventRecord(ctx->cev[0], ctx->copy_stream));
-            }
-            // (the end of every chunk waits for the main stream: the other area is free when the next upload is issued)
-            GK_HIP(ctx, read_back(ctx, {{bin_out + cur.begin, d_area[i], cur.bytes}}));
-            if (nxt.bytes) GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->cev[0], 0));
-            cur = std::move(nxt);
-        }
+    if (int rc = bin_walk(ctx, bin_host, nbytes, nreads, &end)) return rc;
+    unsigned long long h_stats[GK_CORRECT_NSTATS] = {};
+    if (end) {
+        DevScratch tmp(ctx);
+        unsigned long long *d_stats = nullptr;
+        GK_HIP(ctx, tmp.zeroed(&d_stats, GK_CORRECT_NSTATS));
+        // a piece is corrected in place in its staging area and comes back to bin_out at the offset it came from
+        if (int rc = bin_feed(ctx, tmp, bin_host, end, [&](const ReadSrc &src, uint8_t *d_area, const BinPiece &piece, D2H *back) {
+                *back = {bin_out + piece.begin, d_area, piece.bytes};
+                return correct_launch(counts, src, d_area, solid, nullptr, d_stats);
+            }))
+            return rc;
         GK_HIP(ctx, read_back(ctx, {{h_stats, d_stats, sizeof(h_stats)}}));
-        return GK_OK;
-    };
-    rc = run();
-    (void)hipStreamSynchronize(ctx->copy_stream);            // (the areas go back to the pool, which does not wait for uploads)
-    if (rc) return rc;
+    }
     if (bin_out != bin_host && nbytes > end) std::copy(bin_host + end, bin_host + nbytes, bin_out + end);     // bytes behind the last record
     if (stats) for (int i = 0; i < GK_CORRECT_NSTATS; i++) stats[i] = h_stats[i];
     return GK_OK;

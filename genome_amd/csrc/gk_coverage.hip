@@ -316,11 +316,11 @@ static int check_counts(const gk_graph *g, gk_map *counts, const char *who) {
 static int coverage_pass(gk_graph *g, gk_map *counts, DevScratch &tmp, const uint8_t *want, EdgeCov *cov) {
     gk_ctx *ctx = g->ctx;
     const GraphView &v = g->v;
-    hipError_t e = tmp.get(&cov->sum, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&cov->mn, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&cov->mx, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&cov->miss, v.n_edges);
-    if (e != hipSuccess) return hip_fail(ctx, e, "edge coverage: per-edge results");
+    tmp.get(&cov->sum, v.n_edges);
+    tmp.get(&cov->mn, v.n_edges);
+    tmp.get(&cov->mx, v.n_edges);
+    tmp.get(&cov->miss, v.n_edges);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "edge coverage: per-edge results");
     if (v.n_edges == 0) return GK_OK;
     const int long_grid = (int)std::min<u64>(v.n_edges, grid_cap(ctx));
     GK_BY_SLOT(counts, {
@@ -348,23 +348,20 @@ int gk_graph_edge_coverage(gk_graph *g, gk_map *counts, const uint32_t *edge_ids
     u64 *d_kmers = nullptr, *d_sum = nullptr;
     uint8_t *d_want = nullptr;
     unsigned long long *d_missing = nullptr, h_missing = 0;
-    hipError_t e = tmp.get(&d_ids, n);
-    if (e == hipSuccess) e = tmp.get(&d_kmers, n);
-    if (e == hipSuccess) e = tmp.get(&d_sum, n);
-    if (e == hipSuccess) e = tmp.get(&d_mn, n);
-    if (e == hipSuccess) e = tmp.get(&d_mx, n);
-    if (e == hipSuccess) e = tmp.get(&d_want, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&d_missing, 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ids, edge_ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_want, 0, std::max<u64>(v.n_edges, 1), ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_missing, 0, 8, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edge_coverage");
+    tmp.upload(&d_ids, edge_ids, n);
+    tmp.get(&d_kmers, n);
+    tmp.get(&d_sum, n);
+    tmp.get(&d_mn, n);
+    tmp.get(&d_mx, n);
+    tmp.zeroed(&d_want, v.n_edges);
+    tmp.zeroed(&d_missing, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_edge_coverage");
     hipLaunchKernelGGL(k_cov_want, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, d_ids, (u64)n, v.n_edges, d_want);
     EdgeCov cov{};
     if (int rc = coverage_pass(g, counts, tmp, d_want, &cov)) return rc;
     hipLaunchKernelGGL(k_cov_gather, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, v, cov, d_ids, (u64)n, d_kmers, d_sum, d_mn, d_mx, d_missing);
-    e = read_back(ctx, {{kmers, d_kmers, (size_t)n * 8}, {sum, d_sum, (size_t)n * 8}, {min_count, d_mn, (size_t)n * 4}, {max_count, d_mx, (size_t)n * 4},
-                        {&h_missing, d_missing, 8}});
+    const hipError_t e = read_back(ctx, {{kmers, d_kmers, (size_t)n * 8}, {sum, d_sum, (size_t)n * 8}, {min_count, d_mn, (size_t)n * 4},
+                                         {max_count, d_mx, (size_t)n * 4}, {&h_missing, d_missing, 8}});
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edge_coverage");
     if (missing) *missing = h_missing;
     return GK_OK;
@@ -384,12 +381,10 @@ int gk_graph_clip_tips(gk_graph *g, gk_map *counts, uint64_t max_len, uint64_t *
     unsigned long long *d_in_off = nullptr, *d_removed = nullptr, h_removed = 0;
     u32 *d_in_list = nullptr, *d_flags = nullptr, h_flags = 0;
     uint8_t *d_mark = nullptr;
-    hipError_t e = tmp.get(&d_mark, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&d_flags, 1);
-    if (e == hipSuccess) e = tmp.get(&d_removed, 1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 4, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, 8, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_clip_tips: marks");
+    tmp.get(&d_mark, v.n_edges);
+    tmp.zeroed(&d_flags, 1);
+    tmp.zeroed(&d_removed, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_clip_tips: marks");
     if (int rc = graph_in_lists(g, tmp, "gk_graph_clip_tips", &d_in_off, &d_in_list)) return rc;
     const int grid = ggrid(ctx, v.n_edges);
     hipLaunchKernelGGL(k_tip_mark, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, cov, d_in_off, d_in_list, (u64)max_len, d_mark, d_flags);
@@ -409,12 +404,10 @@ int gk_graph_edge_distance(gk_graph *g, const uint32_t *e1, const uint32_t *e2, 
     if (!e1 || !e2) return fail(ctx, GK_E_INVALID, "gk_graph_edge_distance: an id array is NULL");
     DevScratch tmp(ctx);
     u32 *d_e1 = nullptr, *d_e2 = nullptr, *d_dist = nullptr;
-    hipError_t e = tmp.get(&d_e1, n);
-    if (e == hipSuccess) e = tmp.get(&d_e2, n);
-    if (e == hipSuccess) e = tmp.get(&d_dist, n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_e1, e1, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_e2, e2, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edge_distance");
+    tmp.upload(&d_e1, e1, n);
+    tmp.upload(&d_e2, e2, n);
+    tmp.get(&d_dist, n);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_edge_distance");
     hipLaunchKernelGGL(k_edge_distance, dim3(ggrid(ctx, n * 64)), dim3(BLOCK), 0, ctx->stream, g->v, d_e1, d_e2, (u64)n, (u32)max_diff, d_dist);
     GK_HIP(ctx, read_back(ctx, {{dist, d_dist, (size_t)n * 4}}));
     return GK_OK;
@@ -434,28 +427,23 @@ int gk_graph_pop_bubbles(gk_graph *g, gk_map *counts, uint64_t max_len, uint32_t
     unsigned long long *d_off = nullptr, *d_removed = nullptr, *d_compared = nullptr, h_pairs = 0, h_removed = 0, h_compared = 0;
     u32 *d_cnt = nullptr, *d_pe = nullptr, *d_pf = nullptr, *d_dist = nullptr, *d_flags = nullptr, h_flags = 0;
     uint8_t *d_want = nullptr, *d_mark = nullptr;
-    hipError_t e = tmp.get(&d_cnt, v.n_nodes);
-    if (e == hipSuccess) e = tmp.get(&d_off, v.n_nodes + 1);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_pop_bubbles: candidate counts");
+    tmp.get(&d_cnt, v.n_nodes);
+    tmp.get(&d_off, v.n_nodes + 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_pop_bubbles: candidate counts");
     const int ngrid = ggrid(ctx, v.n_nodes);
     hipLaunchKernelGGL(k_bubble_count, dim3(ngrid), dim3(BLOCK), 0, ctx->stream, v, (u64)max_len, d_cnt);
     GK_HIP(ctx, scan_counts(ctx, tmp, d_cnt, v.n_nodes, d_off));
     GK_HIP(ctx, read_back(ctx, &h_pairs, d_off + v.n_nodes));
     if (h_pairs == 0) return GK_OK;
-    e = tmp.get(&d_pe, h_pairs);
-    if (e == hipSuccess) e = tmp.get(&d_pf, h_pairs);
-    if (e == hipSuccess) e = tmp.get(&d_dist, h_pairs);
-    if (e == hipSuccess) e = tmp.get(&d_want, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&d_mark, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&d_flags, 1);
-    if (e == hipSuccess) e = tmp.get(&d_removed, 1);
-    if (e == hipSuccess) e = tmp.get(&d_compared, 1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_want, 0, v.n_edges, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_mark, 0, v.n_edges, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 4, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, 8, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_compared, 0, 8, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_pop_bubbles: candidate pairs");
+    tmp.get(&d_pe, h_pairs);
+    tmp.get(&d_pf, h_pairs);
+    tmp.get(&d_dist, h_pairs);
+    tmp.zeroed(&d_want, v.n_edges);
+    tmp.zeroed(&d_mark, v.n_edges);
+    tmp.zeroed(&d_flags, 1);
+    tmp.zeroed(&d_removed, 1);
+    tmp.zeroed(&d_compared, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_pop_bubbles: candidate pairs");
     hipLaunchKernelGGL(k_bubble_pairs, dim3(ngrid), dim3(BLOCK), 0, ctx->stream, v, (u64)max_len, d_cnt, d_off, d_pe, d_pf, d_want);
     // coverage of the edges in some bubble only, and the distance of every pair
     EdgeCov cov{};

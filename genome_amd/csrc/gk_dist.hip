@@ -32,6 +32,7 @@
 #include <thread>
 #include <vector>
 
+#include "gk_binstream.h"
 #include "gk_dist.h"
 #include "gk_graph.h"
 #include "gk_support.h"
@@ -697,8 +698,7 @@ int gk_dist_count_reads(gk_dist *d, gk_map *local, const uint8_t *bin, size_t nb
         int err = 0;
         BinChunk c = map_cut_chunk(local, bin, nbytes, nreads, pos, r, true, &err);
         if (err) {
-            my_rc = fail(ctx, GK_E_FORMAT, err == 1 ? "truncated .bin stream: record " + std::to_string(c.r_begin + c.offs.size()) + " starts past the end"
-                                                    : "truncated .bin stream inside record " + std::to_string(c.r_begin + c.offs.size()));
+            my_rc = bin_truncated(ctx, err, c.r_begin + c.offs.size());
             break;
         }
         if (!c.valid) break;

@@ -874,16 +874,17 @@ int graph_in_lists(gk_graph *g, DevScratch &tmp, const char *who, unsigned long 
     gk_ctx *ctx = g->ctx;
     const GraphView &v = g->v;
     u32 *cnt = nullptr;                       // the counts, then (zeroed again) the fill's cursors
-    hipError_t e = tmp.get(off, v.n_nodes + 1);
-    if (e == hipSuccess) e = tmp.get(&cnt, v.n_nodes);
-    if (e == hipSuccess) e = tmp.get(list, v.n_edges);
-    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream);
-    if (e == hipSuccess && v.n_edges) hipLaunchKernelGGL(k_in_count, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, cnt);
-    if (e == hipSuccess) e = scan_counts(ctx, tmp, cnt, v.n_nodes, *off);
-    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream);
-    if (e == hipSuccess && v.n_edges) hipLaunchKernelGGL(k_in_fill, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, *off, cnt, *list);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, (std::string(who) + ": in-edge lists").c_str());
+    const std::string what = std::string(who) + ": in-edge lists";
+    tmp.get(off, v.n_nodes + 1);
+    tmp.zeroed(&cnt, v.n_nodes);
+    tmp.get(list, v.n_edges);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), what.c_str());
+    if (v.n_edges) hipLaunchKernelGGL(k_in_count, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, cnt);
+    tmp.note(scan_counts(ctx, tmp, cnt, v.n_nodes, *off));
+    tmp.note(hipMemsetAsync(cnt, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream));
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), what.c_str());
+    if (v.n_edges) hipLaunchKernelGGL(k_in_fill, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, *off, cnt, *list);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(ctx, e, what.c_str());
     return GK_OK;
 }
 
@@ -946,20 +947,22 @@ int gk_graph_simplify(gk_graph *g) {
     unsigned long long *d_cnt = nullptr, h_cnt[3] = {0, 0, 0};
     LongPiece *long_pieces = nullptr;
     DevScratch tmp(ctx);
-    hipError_t e = tmp.get(&in_single, v.n_nodes);
-    if (e == hipSuccess) e = tmp.get(&merged_key, v.n_nodes * 4);
-    if (e == hipSuccess) e = tmp.get(&cls, v.n_nodes);
-    if (e == hipSuccess) e = tmp.get(&d_cnt, 3);
-    if (e == hipSuccess) e = hipMemsetAsync(in_single, 0xff, v.n_nodes * 4, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(merged_key, 0xff, v.n_nodes * 16, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, 24, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: alloc");
+    tmp.get(&in_single, v.n_nodes);
+    tmp.get(&merged_key, v.n_nodes * 4);
+    tmp.get(&cls, v.n_nodes);
+    tmp.zeroed(&d_cnt, 3);
+    if (tmp.error() == hipSuccess) {                             // (NONE everywhere: a fill, not a zeroing)
+        tmp.note(hipMemsetAsync(in_single, 0xff, v.n_nodes * 4, ctx->stream));
+        tmp.note(hipMemsetAsync(merged_key, 0xff, v.n_nodes * 16, ctx->stream));
+    }
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_simplify: alloc");
     const int gn = ggrid(ctx, v.n_nodes), ge = ggrid(ctx, std::max<u64>(v.n_edges, 1));
     hipLaunchKernelGGL(k_in_single, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, in_single);
     hipLaunchKernelGGL(k_node_class, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, in_single, cls);
     const u64 old_edges = v.n_edges, old_pool = g->pool_used;
     hipLaunchKernelGGL(k_chain, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, cls, 0, old_edges, old_pool, d_cnt, merged_key, (LongPiece *)nullptr);
-    if ((e = read_back(ctx, h_cnt, d_cnt, 3)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: count");
+    hipError_t e = read_back(ctx, h_cnt, d_cnt, 3);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: count");
     if (h_cnt[0]) {
         if (old_edges + h_cnt[0] >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, "more than 2^32 graph edges");
         if (int rc = graph_grow_edges(g, old_edges + h_cnt[0])) return rc;
@@ -968,12 +971,12 @@ int gk_graph_simplify(gk_graph *g) {
             if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: pool");
             g->pool_cap = old_pool + h_cnt[1] + 8;
         }
-        e = hipMemsetAsync(d_cnt, 0, 24, ctx->stream);
-        if (e == hipSuccess && h_cnt[2]) {                       // long pieces are ORed into their place: it starts as zeroes
-            e = tmp.get(&long_pieces, h_cnt[2]);
-            if (e == hipSuccess) e = hipMemsetAsync(v.pool + old_pool, 0, h_cnt[1], ctx->stream);
+        tmp.note(hipMemsetAsync(d_cnt, 0, 24, ctx->stream));
+        if (h_cnt[2]) {                                          // long pieces are ORed into their place: it starts as zeroes
+            tmp.get(&long_pieces, h_cnt[2]);
+            tmp.note(hipMemsetAsync(v.pool + old_pool, 0, h_cnt[1], ctx->stream));
         }
-        if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify");
+        if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_simplify");
         hipLaunchKernelGGL(k_chain, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, cls, 1, old_edges, old_pool, d_cnt, merged_key, long_pieces);
         if (h_cnt[2]) hipLaunchKernelGGL(k_copy_long, dim3((unsigned)h_cnt[2]), dim3(BLOCK), 0, ctx->stream, v, long_pieces);
         v.n_edges = old_edges + h_cnt[0];
@@ -1007,20 +1010,14 @@ int gk_graph_remove_edges(gk_graph *g, const uint64_t *start_lo, const uint64_t 
     uint8_t *d_b = nullptr;
     unsigned long long *d_rm = nullptr, h_rm = 0;
     DevScratch tmp(ctx);
-    hipError_t e = tmp.get(&d_lo, n);
-    if (e == hipSuccess) e = tmp.get(&d_hi, n);
-    if (e == hipSuccess) e = tmp.get(&d_b, n);
-    if (e == hipSuccess) e = tmp.get(&d_rm, 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lo, start_lo, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = start_hi ? hipMemcpyAsync(d_hi, start_hi, n * 8, hipMemcpyHostToDevice, ctx->stream)
-                                      : hipMemsetAsync(d_hi, 0, n * 8, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_b, base, n, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_rm, 0, 8, ctx->stream);
-    if (e == hipSuccess) {
-        GK_BY_W(g->W, hipLaunchKernelGGL(k_remove_edges<W>, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_b, n, d_rm));
-        e = read_back(ctx, &h_rm, d_rm);
-    }
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_remove_edges");
+    tmp.upload(&d_lo, start_lo, n);
+    if (start_hi) tmp.upload(&d_hi, start_hi, n);
+    else tmp.zeroed(&d_hi, n);
+    tmp.upload(&d_b, base, n);
+    tmp.zeroed(&d_rm, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_remove_edges");
+    GK_BY_W(g->W, hipLaunchKernelGGL(k_remove_edges<W>, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_b, n, d_rm));
+    if (const hipError_t e = read_back(ctx, &h_rm, d_rm); e != hipSuccess) return hip_fail(ctx, e, "gk_graph_remove_edges");
     if (removed) *removed = h_rm;
     return graph_refresh_counts(g);
 }
@@ -1034,26 +1031,21 @@ static int graph_components(gk_graph *g, DevScratch &tmp, u32 **parent_out, u32 
     GraphView &v = g->v;
     u32 *parent = nullptr, *size = nullptr;
     unsigned long long *d_ncomp = nullptr;
-    hipError_t e = tmp.get(&parent, v.n_nodes);
-    if (e == hipSuccess) e = tmp.get(&size, v.n_nodes);
-    if (e == hipSuccess) e = tmp.get(&d_ncomp, 1);
-    if (e != hipSuccess) return hip_fail(ctx, e, "graph components: alloc");
+    tmp.get(&parent, v.n_nodes);
+    tmp.zeroed(&size, v.n_nodes);
+    tmp.zeroed(&d_ncomp, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "graph components: alloc");
     const int gn = ggrid(ctx, std::max<u64>(v.n_nodes, 1)), ge = ggrid(ctx, std::max<u64>(v.n_edges, 1));
     hipLaunchKernelGGL(k_cc_init, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, parent);
     if (ctx->hook_cc_find == 1) hipLaunchKernelGGL(k_cc_link<1>, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, parent);
     else if (ctx->hook_cc_find == 3) hipLaunchKernelGGL(k_cc_link<3>, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, parent);
     else if (ctx->hook_cc_find == 2) hipLaunchKernelGGL(k_cc_link<2>, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, parent);
     else hipLaunchKernelGGL(k_cc_link<0>, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, parent);
-    e = hipGetLastError();
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, "graph components: hooking");
     unsigned long long h = 0;
-    e = hipMemsetAsync(size, 0, std::max<u64>(v.n_nodes, 1) * 4, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_ncomp, 0, 8, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_cc_sizes, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, parent, size, d_ncomp);
-        e = read_back(ctx, &h, d_ncomp);
-    }
-    if (e != hipSuccess) return hip_fail(ctx, e, "graph components: sizes");
+    hipLaunchKernelGGL(k_cc_sizes, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, parent, size, d_ncomp);
+    if ((e = read_back(ctx, &h, d_ncomp)) != hipSuccess) return hip_fail(ctx, e, "graph components: sizes");
     tmp.release(d_ncomp);
     *parent_out = parent; *size_out = size; *ncomp = h;
     return GK_OK;
@@ -1073,21 +1065,18 @@ int gk_graph_retain_largest(gk_graph *g, uint64_t *kept_nodes, uint64_t *compone
     u64 ncomp = 0;
     DevScratch tmp(ctx);
     if (int rc = graph_components(g, tmp, &parent, &size, &ncomp)) return rc;
-    hipError_t e = tmp.get(&d_u32, 4);
-    if (e == hipSuccess) e = tmp.get(&d_u64, 3);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest: alloc");
     const int gn = ggrid(ctx, v.n_nodes);
-    unsigned long long h64[3] = {0, ~0ull, ~0ull};
+    const unsigned long long h64[3] = {0, ~0ull, ~0ull};
     u32 h32[3] = {0, 0, NONE};
-    e = hipMemcpyAsync(d_u64, h64, 24, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_u32, h32, 12, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest");
+    tmp.upload(&d_u64, h64, 3);
+    tmp.upload(&d_u32, h32, 3);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_retain_largest: alloc");
     // max size -> smallest k-mer among the components of that size -> its root -> retain: four dependent steps, no host in between
     hipLaunchKernelGGL(k_cc_max, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, size, &d_u32[1]);
     for (int stage = 0; stage < 3; stage++)
         hipLaunchKernelGGL(k_cc_pick, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, parent, size, &d_u32[1], stage, &d_u64[1], &d_u32[2]);
     hipLaunchKernelGGL(k_retain, dim3(ggrid(ctx, std::max(v.n_nodes, v.n_edges))), dim3(BLOCK), 0, ctx->stream, v, parent, &d_u32[2]);
-    if ((e = read_back(ctx, h32, d_u32, 3)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest: retain");
+    if (const hipError_t e = read_back(ctx, h32, d_u32, 3); e != hipSuccess) return hip_fail(ctx, e, "gk_graph_retain_largest: retain");
     if (h32[2] == NONE) return fail(ctx, GK_E_STATE, "no component selected");
     if (components) *components = ncomp;
     int rc = graph_refresh_counts(g);
@@ -1109,16 +1098,14 @@ int gk_graph_component_stats(gk_graph *g, uint32_t *nodes_per_component, uint64_
     if (n) *n = ncomp;
     if (ncomp > cap) return fail(ctx, GK_E_CAPACITY, "component buffer too small: need " + std::to_string(ncomp));
     if (!nodes_per_component || !edge_len_per_component) return fail(ctx, GK_E_INVALID, "null component buffer");
-    hipError_t e = tmp.get(&len, v.n_nodes);
-    if (e == hipSuccess) e = tmp.get(&d_nodes, ncomp);
-    if (e == hipSuccess) e = tmp.get(&d_len, ncomp);
-    if (e == hipSuccess) e = tmp.get(&d_cur, 1);
-    if (e == hipSuccess) e = hipMemsetAsync(len, 0, v.n_nodes * 8, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 8, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_component_stats: alloc");
+    tmp.zeroed(&len, v.n_nodes);
+    tmp.get(&d_nodes, ncomp);
+    tmp.get(&d_len, ncomp);
+    tmp.zeroed(&d_cur, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_component_stats: alloc");
     hipLaunchKernelGGL(k_cc_edge_len, dim3(ggrid(ctx, std::max<u64>(v.n_edges, 1))), dim3(BLOCK), 0, ctx->stream, v, parent, len);
     hipLaunchKernelGGL(k_cc_collect, dim3(ggrid(ctx, v.n_nodes)), dim3(BLOCK), 0, ctx->stream, v, parent, size, len, d_nodes, d_len, d_cur);
-    e = read_back(ctx, {{nodes_per_component, d_nodes, ncomp * 4}, {edge_len_per_component, d_len, ncomp * 8}});
+    const hipError_t e = read_back(ctx, {{nodes_per_component, d_nodes, ncomp * 4}, {edge_len_per_component, d_len, ncomp * 8}});
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_component_stats");
     return GK_OK;
 }
@@ -1151,15 +1138,12 @@ int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap,
     u64 *d_lo = nullptr, *d_hi = nullptr;
     unsigned long long *d_cur = nullptr;
     DevScratch tmp(ctx);
-    hipError_t e = tmp.get(&d_lo, cnt);
-    if (e == hipSuccess) e = tmp.get(&d_hi, cnt);
-    if (e == hipSuccess) e = tmp.get(&d_cur, 1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 8, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_export_nodes, dim3(ggrid(ctx, g->v.n_nodes)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_cur);
-        e = read_back(ctx, {{lo, d_lo, cnt * 8}, {hi, d_hi, cnt * 8}});
-    }
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_export_nodes");
+    tmp.get(&d_lo, cnt);
+    tmp.get(&d_hi, cnt);
+    tmp.zeroed(&d_cur, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_export_nodes");
+    hipLaunchKernelGGL(k_export_nodes, dim3(ggrid(ctx, g->v.n_nodes)), dim3(BLOCK), 0, ctx->stream, g->v, d_lo, d_hi, d_cur);
+    if (const hipError_t e = read_back(ctx, {{lo, d_lo, cnt * 8}, {hi, d_hi, cnt * 8}}); e != hipSuccess) return hip_fail(ctx, e, "gk_graph_export_nodes");
     return GK_OK;
 }
 
@@ -1182,19 +1166,15 @@ int gk_graph_export_edges(gk_graph *g, uint64_t *start_lo, uint64_t *start_hi, u
     uint8_t *d_seq = nullptr;
     unsigned long long *d_cur = nullptr, h_cur[2] = {0, 0};
     DevScratch tmp(ctx);
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 4 && e == hipSuccess; i++) e = tmp.get(&d_k[i], cnt);
-    if (e == hipSuccess) e = tmp.get(&d_len, cnt);
-    if (e == hipSuccess) e = tmp.get(&d_off, cnt);
-    if (e == hipSuccess) e = tmp.get(&d_seq, max_bytes);
-    if (e == hipSuccess) e = tmp.get(&d_cur, 2);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 16, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_export_edges, dim3(ggrid(ctx, g->v.n_edges)), dim3(BLOCK), 0, ctx->stream, g->v, d_k[0], d_k[1], d_k[2],
-                           d_k[3], d_len, d_off, d_seq, d_cur);
-        e = read_back(ctx, {{h_cur, d_cur, 16}, {start_lo, d_k[0], cnt * 8}, {start_hi, d_k[1], cnt * 8}, {end_lo, d_k[2], cnt * 8},
-                            {end_hi, d_k[3], cnt * 8}, {len, d_len, cnt * 8}, {seq_off, d_off, cnt * 8}});
-    }
+    for (int i = 0; i < 4; i++) tmp.get(&d_k[i], cnt);
+    tmp.get(&d_len, cnt);
+    tmp.get(&d_off, cnt);
+    tmp.get(&d_seq, max_bytes);
+    tmp.zeroed(&d_cur, 2);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_export_edges");
+    hipLaunchKernelGGL(k_export_edges, dim3(ggrid(ctx, g->v.n_edges)), dim3(BLOCK), 0, ctx->stream, g->v, d_k[0], d_k[1], d_k[2], d_k[3], d_len, d_off, d_seq, d_cur);
+    hipError_t e = read_back(ctx, {{h_cur, d_cur, 16}, {start_lo, d_k[0], cnt * 8}, {start_hi, d_k[1], cnt * 8}, {end_lo, d_k[2], cnt * 8},
+                                   {end_hi, d_k[3], cnt * 8}, {len, d_len, cnt * 8}, {seq_off, d_off, cnt * 8}});
     if (e == hipSuccess && h_cur[1]) e = hipMemcpy(seq2bit, d_seq, h_cur[1], hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_export_edges");
     if (h_cur[0] != cnt) return fail(ctx, GK_E_STATE, "edge export count mismatch");
@@ -1260,21 +1240,21 @@ int gk_graph_position_map(gk_graph *g, gk_vmap *vm, uint64_t *entries) {
     unsigned long long *first = nullptr, *d_cur = nullptr, h_cur[2] = {0, 0};
     u64 *lo = nullptr, *hi = nullptr, *val = nullptr;
     DevScratch tmp(ctx);
-    hipError_t e = tmp.get(&first, v.n_edges);
-    if (e == hipSuccess) e = tmp.get(&d_cur, 2);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 16, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: alloc");
+    tmp.get(&first, v.n_edges);
+    tmp.zeroed(&d_cur, 2);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_position_map: alloc");
     if (v.n_edges) hipLaunchKernelGGL(k_pos_reserve, dim3(ggrid(ctx, v.n_edges)), dim3(BLOCK), 0, ctx->stream, v, first, &d_cur[0]);
-    if ((e = read_back(ctx, h_cur, d_cur, 1)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: reserve");
+    hipError_t e = read_back(ctx, h_cur, d_cur, 1);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: reserve");
     // the reference's own check, printed side by side at :117: size == sum of edge lengths + nodes - edges
     const u64 total = g->live_nodes + h_cur[0];
     if (h_cur[0] != g->live_len - g->live_edges) return fail(ctx, GK_E_STATE, "gk_graph_position_map: interior k-mer count does not match the graph's counters");
     if (total == 0) return GK_OK;
-    e = tmp.get(&lo, total);
-    if (e == hipSuccess) e = tmp.get(&hi, total);
-    if (e == hipSuccess) e = tmp.get(&val, total);
-    if (e == hipSuccess && g->W == 1) e = hipMemsetAsync(hi, 0, total * 8, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_position_map: entries");
+    tmp.get(&lo, total);
+    if (g->W == 1) tmp.zeroed(&hi, total);
+    else tmp.get(&hi, total);
+    tmp.get(&val, total);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_position_map: entries");
     hipLaunchKernelGGL(k_pos_nodes, dim3(ggrid(ctx, std::max<u64>(v.n_nodes, 1))), dim3(BLOCK), 0, ctx->stream, v, lo, hi, val, &d_cur[1]);
     if (v.n_edges) {
         GK_BY_W(g->W,
@@ -1358,17 +1338,15 @@ int gk_graph_nodes_by_id(gk_graph *g, const uint32_t *ids, uint64_t n, uint64_t 
     u64 *d_lo = nullptr, *d_hi = nullptr;
     uint8_t *d_al = nullptr;
     DevScratch tmp(ctx);
-    hipError_t e = tmp.get(&d_ids, n);
-    if (e == hipSuccess) e = tmp.get(&d_in, n);
-    if (e == hipSuccess) e = tmp.get(&d_out, n);
-    if (e == hipSuccess) e = tmp.get(&d_lo, n);
-    if (e == hipSuccess) e = tmp.get(&d_hi, n);
-    if (e == hipSuccess) e = tmp.get(&d_al, n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_nodes_by_id, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_ids, n, d_lo, d_hi, d_al, d_in, d_out);
-        e = read_back(ctx, {{lo, d_lo, n * 8}, {hi, d_hi, n * 8}, {alive, d_al, n}, {in_deg, d_in, n * 4}, {out_deg, d_out, n * 4}});
-    }
+    tmp.upload(&d_ids, ids, n);
+    tmp.get(&d_in, n);
+    tmp.get(&d_out, n);
+    tmp.get(&d_lo, n);
+    tmp.get(&d_hi, n);
+    tmp.get(&d_al, n);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_nodes_by_id");
+    hipLaunchKernelGGL(k_nodes_by_id, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_ids, n, d_lo, d_hi, d_al, d_in, d_out);
+    const hipError_t e = read_back(ctx, {{lo, d_lo, n * 8}, {hi, d_hi, n * 8}, {alive, d_al, n}, {in_deg, d_in, n * 4}, {out_deg, d_out, n * 4}});
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_nodes_by_id");
     return GK_OK;
 }
@@ -1382,17 +1360,15 @@ int gk_graph_edges_by_id(gk_graph *g, const uint32_t *ids, uint64_t n, uint32_t 
     u64 *d_len = nullptr;
     uint8_t *d_f = nullptr, *d_al = nullptr;
     DevScratch tmp(ctx);
-    hipError_t e = tmp.get(&d_ids, n);
-    if (e == hipSuccess) e = tmp.get(&d_s, n);
-    if (e == hipSuccess) e = tmp.get(&d_e, n);
-    if (e == hipSuccess) e = tmp.get(&d_len, n);
-    if (e == hipSuccess) e = tmp.get(&d_f, n);
-    if (e == hipSuccess) e = tmp.get(&d_al, n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_ids, ids, n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_edges_by_id, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_ids, n, d_s, d_e, d_len, d_f, d_al);
-        e = read_back(ctx, {{start_node, d_s, n * 4}, {end_node, d_e, n * 4}, {len, d_len, n * 8}, {first_base, d_f, n}, {alive, d_al, n}});
-    }
+    tmp.upload(&d_ids, ids, n);
+    tmp.get(&d_s, n);
+    tmp.get(&d_e, n);
+    tmp.get(&d_len, n);
+    tmp.get(&d_f, n);
+    tmp.get(&d_al, n);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_edges_by_id");
+    hipLaunchKernelGGL(k_edges_by_id, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, g->v, d_ids, n, d_s, d_e, d_len, d_f, d_al);
+    const hipError_t e = read_back(ctx, {{start_node, d_s, n * 4}, {end_node, d_e, n * 4}, {len, d_len, n * 8}, {first_base, d_f, n}, {alive, d_al, n}});
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_edges_by_id");
     return GK_OK;
 }

@@ -115,6 +115,23 @@ struct ReadSrc {
     // the records were PREFETCHED: their upload to `rec` is already queued on the copy stream and this event fires when they
     // have landed — the consumer waits for it instead of uploading (gk_map_count_reads looks one chunk ahead; gk_map_prefetch_reads)
     hipEvent_t ready = nullptr;
+    // records of one length resident in HBM (a `_dev` entry point's arguments; read_len checked by check_read_len)
+    static ReadSrc fixed(const void *dev_records, uint64_t nreads, int read_len) {
+        ReadSrc s;
+        s.rec = (const uint8_t *)dev_records;
+        s.nreads = nreads;
+        s.stride = 1 + (uint32_t)(read_len + 3) / 4;         // (bin_record_bytes, gk_binstream.h)
+        s.max_len = read_len;
+        return s;
+    }
+    // records in HBM whose framing the host has walked: record r spans [d_off[r], d_off[r + 1]) and no length byte exceeds 255
+    static ReadSrc framed(const uint8_t *d_rec, const uint32_t *d_off, uint64_t nreads) {
+        ReadSrc s;
+        s.rec = d_rec;
+        s.nreads = nreads;
+        s.off = d_off;
+        return s;
+    }
 };
 int stage_source(gk_ctx *ctx, const ReadSrc &src);      // upload a host-fed source in one piece, stream-ordered on ctx->stream
 }
@@ -135,18 +152,45 @@ template <class T> inline hipError_t pool_malloc(gk_ctx *ctx, T **p, size_t byte
 // Device buffers of one call: whatever get() handed out is freed when the owner goes out of scope, on every return path.
 // release() frees one buffer early (the pool's peak depends on where that happens), take() hands one over to a longer-lived
 // owner.  pool_free waits for the context's streams, so a scope must not end while another stream's work still reads a buffer.
+// The first error sticks: once an allocation or a fill has failed, every later get / zeroed / upload hands out nullptr, touches
+// neither the pool nor the runtime and returns that error.  A call therefore asks for all its buffers in straight-line code and
+// checks error() ONCE — before the first launch that reads any of them (a null scratch pointer in a kernel is a device fault).
 struct __attribute__((visibility("hidden"))) DevScratch {      // (internal: its instantiations are not exported)
     gk_ctx *ctx;
     std::vector<void *> ptrs;
+    hipError_t err = hipSuccess;
+    // what get / zeroed / upload / note return: the sticky error, as a hipError_t that may be left unread (the runtime's own type
+    // is [[nodiscard]], and the point of a sticky error is that a chain of calls is checked once, by error())
+    struct Status {
+        hipError_t e;
+        operator hipError_t() const { return e; }
+    };
     explicit DevScratch(gk_ctx *c) : ctx(c) {}
     DevScratch(const DevScratch &) = delete;
     DevScratch &operator=(const DevScratch &) = delete;
     ~DevScratch() { for (void *p : ptrs) (void)pool_free(ctx, p); }
-    template <class T> hipError_t get(T **p, uint64_t n) {      // n elements (at least one); *p == nullptr on failure
-        const hipError_t e = pool_malloc(ctx, p, (n ? n : 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
+    hipError_t error() const { return err; }
+    Status note(hipError_t e) {                             // a stray runtime call of the same chain (a memset of part of a buffer)
+        if (err == hipSuccess) err = e;
+        return {err};
+    }
+    template <class T> Status get(T **p, uint64_t n) {      // n elements (at least one); *p == nullptr on failure
+        *p = nullptr;
+        if (err != hipSuccess) return {err};
+        if ((err = pool_malloc(ctx, p, (n ? n : 1) * sizeof(T))) == hipSuccess) ptrs.push_back(*p);
         else { *p = nullptr; (void)hipGetLastError(); }
-        return e;
+        return {err};
+    }
+    template <class T> Status zeroed(T **p, uint64_t n) {   // get, and the whole allocation set to 0 on ctx->stream
+        if (get(p, n) == hipSuccess) err = hipMemsetAsync(*p, 0, (n ? n : 1) * sizeof(T), ctx->stream);
+        if (err != hipSuccess) *p = nullptr;                    // (a buffer whose fill failed stays owned and is freed with the rest)
+        return {err};
+    }
+    template <class T, class U> Status upload(T **p, const U *host, uint64_t n) {   // get, and n elements copied in from the host on ctx->stream
+        static_assert(sizeof(U) == sizeof(T), "upload: the host array's elements are not the device array's");
+        if (get(p, n) == hipSuccess) err = hipMemcpyAsync(*p, host, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
+        if (err != hipSuccess) *p = nullptr;
+        return {err};
     }
     template <class T> T *take(T *p) {                          // forget p without freeing it
         for (size_t i = 0; i < ptrs.size(); i++) if (ptrs[i] == p) { ptrs.erase(ptrs.begin() + i); break; }
@@ -245,6 +289,10 @@ int hip_fail(const gk_ctx *ctx, hipError_t e, const char *what);
         if (e__ != hipSuccess) return gk::hip_fail((ctx), e__, #call);      \
     } while (0)
 
+// the read_len of a `_dev` entry point (records of one length): GK_E_FORMAT unless one length byte can hold it
+inline int check_read_len(const gk_ctx *ctx, int read_len) {
+    return read_len < 0 || read_len > 255 ? fail(ctx, GK_E_FORMAT, "read_len must be 0..255 (one length byte per record)") : GK_OK;
+}
 inline bool k_supported(int k) { return (k >= 2 && k <= 31) || (k >= 34 && k <= 64); }
 inline int words_for_k(int k) { return k <= 32 ? 1 : 2; }
 inline size_t slot_bytes(int W) { return W == 1 ? 16 : 24; }      // sizeof(gk::Slot<W>): value maps, and k-mer tables in the GRAPH layout

@@ -707,12 +707,11 @@ int support_bucket(gk_support *s, int P, u64 *d_keys, u32 *d_cnt, u64 room, u64 
     u32 *d_counts = nullptr;
     unsigned long long *d_off = nullptr, *d_region = nullptr;
     u32 *d_bad = nullptr, h_bad = 0;
-    hipError_t e = tmp.get(&d_counts, n);
-    if (e == hipSuccess) e = tmp.get(&d_off, n + 1);
-    if (e == hipSuccess) e = tmp.get(&d_region, (u64)P + 1);
-    if (e == hipSuccess) e = tmp.get(&d_bad, 1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 4, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "support_bucket: scratch");
+    tmp.get(&d_counts, n);
+    tmp.get(&d_off, n + 1);
+    tmp.get(&d_region, (u64)P + 1);
+    tmp.zeroed(&d_bad, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "support_bucket: scratch");
     hipLaunchKernelGGL(k_sup_bucket_count, dim3((unsigned)nwg), dim3(BLOCK), 0, ctx->stream, s->d_keys, s->cap, chunk, (u32)P, canon, nmap, d_counts, d_bad);
     GK_HIP(ctx, hipGetLastError());
     GK_HIP(ctx, scan_counts(ctx, tmp, d_counts, n, d_off));
@@ -759,17 +758,15 @@ int graph_edge_canon(gk_graph *g, DevScratch &keep, u32 **d_canon, u32 **d_inv, 
     unsigned long long *d_out = nullptr, h_out[2] = {0, 0};
     void *d_temp = nullptr;
     size_t temp_bytes = 0;
-    hipError_t e = tmp.get(&d_k, ne);
-    if (e == hipSuccess) e = tmp.get(&d_k2, ne);
-    if (e == hipSuccess) e = tmp.get(&d_id, ne);
-    if (e == hipSuccess) e = tmp.get(&d_id2, ne);
-    if (e == hipSuccess) e = tmp.get(&d_flag, 1);
-    if (e == hipSuccess) e = tmp.get(&d_out, 2);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, 16, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 4, ctx->stream);
-    if (e == hipSuccess && ne) e = rocprim::radix_sort_pairs(nullptr, temp_bytes, d_k, d_k2, d_id, d_id2, (size_t)ne, 0, 64, ctx->stream);
-    if (e == hipSuccess) e = tmp.get((uint8_t **)&d_temp, temp_bytes);
-    if (e != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon: scratch");
+    tmp.get(&d_k, ne);
+    tmp.get(&d_k2, ne);
+    tmp.get(&d_id, ne);
+    tmp.get(&d_id2, ne);
+    tmp.zeroed(&d_flag, 1);
+    tmp.zeroed(&d_out, 2);
+    if (ne) tmp.note(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_k, d_k2, d_id, d_id2, (size_t)ne, 0, 64, ctx->stream));   // (the size query)
+    tmp.get((uint8_t **)&d_temp, temp_bytes);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "graph_edge_canon: scratch");
     if (ne) {
         hipLaunchKernelGGL(k_edge_content, dim3(ggrid(ctx, ne)), dim3(BLOCK), 0, ctx->stream, g->v, d_k, d_id, d_out);
         GK_HIP(ctx, hipGetLastError());
@@ -777,12 +774,12 @@ int graph_edge_canon(gk_graph *g, DevScratch &keep, u32 **d_canon, u32 **d_inv, 
     }
     GK_HIP(ctx, read_back(ctx, h_out, d_out, 2));
     u32 *canon = nullptr, *inv = nullptr;
-    e = keep.get(&canon, ne);
-    if (e == hipSuccess) e = keep.get(&inv, h_out[0]);
-    if (e == hipSuccess) e = hipMemsetAsync(canon, 0xff, std::max<u64>(ne, 1) * 4, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon: maps");
+    keep.get(&canon, ne);
+    keep.get(&inv, h_out[0]);
+    if (canon) keep.note(hipMemsetAsync(canon, 0xff, std::max<u64>(ne, 1) * 4, ctx->stream));
+    if (keep.error() != hipSuccess) return hip_fail(ctx, keep.error(), "graph_edge_canon: maps");
     if (h_out[0]) hipLaunchKernelGGL(k_edge_canon, dim3(ggrid(ctx, h_out[0])), dim3(BLOCK), 0, ctx->stream, d_k2, d_id2, (u64)h_out[0], canon, inv, d_flag);
-    if ((e = read_back(ctx, &h_flag, d_flag)) != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon");
+    if (const hipError_t e = read_back(ctx, &h_flag, d_flag); e != hipSuccess) return hip_fail(ctx, e, "graph_edge_canon");
     if (h_flag) return fail(ctx, GK_E_STATE, "two live edges share a start k-mer and a first base (a node split made copies): their support cannot be summed by content");
     *d_canon = canon; *d_inv = inv;
     *nlive = h_out[0];
@@ -852,13 +849,12 @@ int pairs_front(gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbyt
         if (nbytes >= 2 * npairs * rb) {
             uint8_t *d_bin = nullptr;
             u32 *d_rag = nullptr, h_rag = 0;
-            hipError_t e = tmp.get(&d_bin, 2 * npairs * rb + 16);
-            if (e == hipSuccess) e = tmp.get(&d_lo, 4 * npairs);
-            if (e == hipSuccess && W == 2) e = tmp.get(&d_hi, 4 * npairs);
-            if (e == hipSuccess) e = tmp.get(&d_rag, 1);
-            if (e == hipSuccess) e = hipMemsetAsync(d_rag, 0, 4, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_bin, bin, 2 * npairs * rb, hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) return hip_fail(ctx, e, (w + "upload").c_str());
+            tmp.get(&d_bin, 2 * npairs * rb + 16);
+            if (d_bin) tmp.note(hipMemcpyAsync(d_bin, bin, 2 * npairs * rb, hipMemcpyHostToDevice, ctx->stream));   // (16 bytes of slack behind the records)
+            tmp.get(&d_lo, 4 * npairs);
+            if (W == 2) tmp.get(&d_hi, 4 * npairs);
+            tmp.zeroed(&d_rag, 1);
+            if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), (w + "upload").c_str());
             GK_BY_W(g->W, hipLaunchKernelGGL(k_pair_keys<W>, dim3(ggrid(ctx, npairs)), dim3(BLOCK), 0, ctx->stream, d_bin, npairs, (u32)rb, l0, k, d_lo, d_hi, d_rag));
             GK_HIP(ctx, read_back(ctx, &h_rag, d_rag));
             if (!h_rag) { cut = true; nq = 4 * npairs; }
@@ -889,12 +885,10 @@ int pairs_front(gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbyt
         nq = klo.size();
         if (nq) {
             d_lo = d_hi = nullptr;
-            hipError_t e = tmp.get(&d_lo, nq);
-            if (e == hipSuccess && W == 2) e = tmp.get(&d_hi, nq);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_lo, klo.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess && d_hi) e = hipMemcpyAsync(d_hi, khi.data(), nq * 8, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (klo / khi die with this scope)
-            if (e != hipSuccess) return hip_fail(ctx, e, (w + "keys").c_str());
+            tmp.upload(&d_lo, klo.data(), nq);
+            if (W == 2) tmp.upload(&d_hi, khi.data(), nq);
+            tmp.note(hipStreamSynchronize(ctx->stream));                         // (klo / khi die with this scope)
+            if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), (w + "keys").c_str());
         }
     }
     F.nq = nq;
@@ -906,9 +900,9 @@ int pairs_front(gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbyt
     u64 *d_vals = nullptr;
     unsigned long long total = 0;
     {
-        hipError_t e = tmp.get(&d_cnt, nq);
-        if (e == hipSuccess) e = tmp.get(&d_off, nq + 1);
-        if (e != hipSuccess) return hip_fail(ctx, e, (w + "lookup arrays").c_str());
+        tmp.get(&d_cnt, nq);
+        tmp.get(&d_off, nq + 1);
+        if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), (w + "lookup arrays").c_str());
         if (int rc = vmap_get_all_dev(positions, d_lo, d_hi, nq, nullptr, d_cnt, nullptr)) return rc;
         GK_HIP(ctx, scan_counts(ctx, tmp, d_cnt, nq, d_off));
         GK_HIP(ctx, read_back(ctx, &total, d_off + nq));
@@ -1035,11 +1029,9 @@ int gk_support_add(gk_support *s, const uint32_t *e1, const uint32_t *e2, const 
         DevScratch tmp(ctx);
         u64 *d_k = nullptr;
         u32 *d_c = nullptr;
-        hipError_t e = tmp.get(&d_k, n);
-        if (e == hipSuccess) e = tmp.get(&d_c, n);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_k, keys.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_c, count, n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gk_support_add: upload");
+        tmp.upload(&d_k, keys.data(), n);
+        tmp.upload(&d_c, count, n);
+        if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_support_add: upload");
         bool wrapped = false;
         if (int rc = support_insert(t, d_k, d_c, n, true, &wrapped)) return rc;
         if (wrapped) return fail(ctx, GK_E_CAPACITY, "gk_support_add: a count of the list would pass 2^32-1; nothing was added");
@@ -1261,15 +1253,11 @@ int gk_graph_remove_edges_by_id(gk_graph *g, const uint32_t *edge_ids, uint64_t 
     u32 *d_e = nullptr;
     unsigned long long *d_rm = nullptr, h_rm = 0;
     DevScratch tmp(ctx);
-    hipError_t e = tmp.get(&d_e, ids.size());
-    if (e == hipSuccess) e = tmp.get(&d_rm, 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_e, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_rm, 0, 8, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_remove_edges_by_id, dim3(ggrid(ctx, ids.size())), dim3(BLOCK), 0, ctx->stream, g->v, d_e, (u64)ids.size(), d_rm);
-        e = read_back(ctx, &h_rm, d_rm);
-    }
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_remove_edges_by_id");
+    tmp.upload(&d_e, ids.data(), ids.size());
+    tmp.zeroed(&d_rm, 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_remove_edges_by_id");
+    hipLaunchKernelGGL(k_remove_edges_by_id, dim3(ggrid(ctx, ids.size())), dim3(BLOCK), 0, ctx->stream, g->v, d_e, (u64)ids.size(), d_rm);
+    if (const hipError_t e = read_back(ctx, &h_rm, d_rm); e != hipSuccess) return hip_fail(ctx, e, "gk_graph_remove_edges_by_id");
     if (removed) *removed = h_rm;
     return graph_refresh_counts(g);
 }
@@ -1332,29 +1320,19 @@ int gk_graph_split_by_support(gk_graph *g, const gk_support *sup, int cutoff, ui
     if (v.n_nodes + nnew >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, "more than 2^32 graph nodes");
     if (nnew) {
         if (v.n_nodes + nnew > g->node_cap) { if (int rc = graph_grow_nodes(g, std::max<u64>(g->node_cap * 2, v.n_nodes + nnew))) return rc; }
-        u32 *d_src = nullptr, *d_a = nullptr, *d_b = nullptr;
-        const u64 nmv = std::max<u64>(end_edge.size(), start_edge.size());
+        u32 *d_src = nullptr, *d_ee = nullptr, *d_en = nullptr, *d_se = nullptr, *d_sn = nullptr;
         DevScratch tmp(ctx);
-        hipError_t e = tmp.get(&d_src, nnew);
-        if (e == hipSuccess) e = tmp.get(&d_a, nmv);
-        if (e == hipSuccess) e = tmp.get(&d_b, nmv);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_src, new_src.data(), nnew * 4, hipMemcpyHostToDevice, ctx->stream);
+        tmp.upload(&d_src, new_src.data(), nnew);
+        if (!end_edge.empty()) { tmp.upload(&d_ee, end_edge.data(), end_edge.size()); tmp.upload(&d_en, end_node.data(), end_node.size()); }
+        if (!start_edge.empty()) { tmp.upload(&d_se, start_edge.data(), start_edge.size()); tmp.upload(&d_sn, start_node.data(), start_node.size()); }
+        hipError_t e = tmp.error();
         if (e == hipSuccess) {
             hipLaunchKernelGGL(k_add_nodes, dim3(ggrid(ctx, nnew)), dim3(BLOCK), 0, ctx->stream, v, first_new, d_src, nnew);
             e = hipGetLastError();
         }
         v.n_nodes += nnew;                                    // (the kernels below index the new nodes)
-        if (e == hipSuccess && !end_edge.empty()) {
-            e = hipMemcpyAsync(d_a, end_edge.data(), end_edge.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_b, end_node.data(), end_node.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) { hipLaunchKernelGGL(k_move_ends, dim3(ggrid(ctx, end_edge.size())), dim3(BLOCK), 0, ctx->stream, v, d_a, d_b, (u64)end_edge.size()); e = hipGetLastError(); }
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // d_a / d_b are reused below
-        }
-        if (e == hipSuccess && !start_edge.empty()) {
-            e = hipMemcpyAsync(d_a, start_edge.data(), start_edge.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_b, start_node.data(), start_node.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) { hipLaunchKernelGGL(k_move_starts, dim3(ggrid(ctx, start_edge.size())), dim3(BLOCK), 0, ctx->stream, v, d_a, d_b, (u64)start_edge.size()); e = hipGetLastError(); }
-        }
+        if (e == hipSuccess && !end_edge.empty()) { hipLaunchKernelGGL(k_move_ends, dim3(ggrid(ctx, end_edge.size())), dim3(BLOCK), 0, ctx->stream, v, d_ee, d_en, (u64)end_edge.size()); e = hipGetLastError(); }
+        if (e == hipSuccess && !start_edge.empty()) { hipLaunchKernelGGL(k_move_starts, dim3(ggrid(ctx, start_edge.size())), dim3(BLOCK), 0, ctx->stream, v, d_se, d_sn, (u64)start_edge.size()); e = hipGetLastError(); }
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_split_by_support");
         g->index_ready = false;                                // several nodes share a sequence now: the next point query rebuilds the index with all of them

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "gk_binstream.h"
 #include "gk_internal.h"
 #include "gk_tile.h"
 
@@ -243,10 +244,10 @@ int pf_for_each_host_chunk(gk_prefilter *pf, const uint8_t *bin, size_t nbytes, 
             }
         }
         while (!fast_prefix && r < nreads) {
-            if (pos >= nbytes) return fail(ctx, GK_E_FORMAT, "truncated .bin stream: record " + std::to_string(r) + " starts past the end");
+            if (pos >= nbytes) return bin_truncated(ctx, BIN_PAST_END, r);
             const int len = bin[pos];
             const size_t rb = 1 + (size_t)(len + 3) / 4;
-            if (pos + rb > nbytes) return fail(ctx, GK_E_FORMAT, "truncated .bin stream inside record " + std::to_string(r));
+            if (pos + rb > nbytes) return bin_truncated(ctx, BIN_INSIDE, r);
             const u64 nk = len >= pf->k ? (u64)(len - pf->k + 1) : 0;
             if (r > r_begin && (pos + rb - chunk_begin > MAX_STAGE || occ + nk > max_windows)) break;
             offs.push_back((u32)(pos - chunk_begin));

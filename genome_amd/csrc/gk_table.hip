@@ -18,6 +18,7 @@
 #include <cstring>
 #include <vector>
 
+#include "gk_binstream.h"
 #include "gk_internal.h"
 #include "gk_scan.h"
 #include "gk_tile.h"
@@ -1484,10 +1485,7 @@ int gk_map_count_reads(gk_map *m, const uint8_t *bin, size_t nbytes, uint64_t nr
     // cutting the stream into launches bounded in bytes (staging area) and in windows (load limit, key scratch).
     using Chunk = BinChunk;
     auto cut = [&](size_t pos, u64 r, bool walk, int *err) { return map_cut_chunk(m, bin, nbytes, nreads, pos, r, walk, err); };
-    auto format_error = [&](int err, const Chunk &c) {
-        return fail(ctx, GK_E_FORMAT, err == 1 ? "truncated .bin stream: record " + std::to_string(c.r_begin + c.reads) + " starts past the end"
-                                                : "truncated .bin stream inside record " + std::to_string(c.r_begin + c.reads));
-    };
+    auto format_error = [&](int err, const Chunk &c) { return bin_truncated(ctx, err, c.r_begin + c.reads); };
     int err = 0;
     Chunk cur = cut(0, 0, false, &err);
     if (err) return format_error(err, cur);

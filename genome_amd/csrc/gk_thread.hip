@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <memory>
 
+#include "gk_binstream.h"
 #include "gk_graph.h"
 #include "gk_support.h"
 #include "gk_vmap_probe.h"
@@ -196,10 +197,8 @@ int thread_begin(ThreadCall &c, DevScratch &tmp) {
     // a crossing is (in-edge, out-edge) of one node: at most 4 out-edges behind every edge, at most 16 pairs at every node
     const GraphView &v = c.g->v;
     if (int rc = support_reserve(c.local, std::min<u64>(4 * v.n_edges, 16 * v.n_nodes))) return rc;
-    GK_HIP(ctx, tmp.get(&c.d_bad, 1));
-    GK_HIP(ctx, tmp.get(&c.d_stats, TH_NSTATS));
-    GK_HIP(ctx, hipMemsetAsync(c.d_bad, 0, 4, ctx->stream));
-    GK_HIP(ctx, hipMemsetAsync(c.d_stats, 0, TH_NSTATS * 8, ctx->stream));
+    GK_HIP(ctx, tmp.zeroed(&c.d_bad, 1));
+    GK_HIP(ctx, tmp.zeroed(&c.d_stats, TH_NSTATS));
     return GK_OK;
 }
 
@@ -245,19 +244,14 @@ int gk_graph_thread_reads_dev(gk_graph *g, gk_vmap *positions, gk_support *sup, 
     if (int rc = thread_check_args(g, positions, sup, stats7, "gk_graph_thread_reads_dev")) return rc;
     gk_ctx *ctx = g->ctx;
     if (nreads && !dev_records) return fail(ctx, GK_E_INVALID, "gk_graph_thread_reads_dev: null records");
-    if (read_len < 0 || read_len > 255) return fail(ctx, GK_E_FORMAT, "read_len must be 0..255 (one length byte per record)");
+    if (int rc = check_read_len(ctx, read_len)) return rc;
     if (nreads == 0) return GK_OK;
     ThreadCall c{g, positions};
     DevScratch tmp(ctx);
     int rc = thread_begin(c, tmp);
     std::unique_ptr<gk_support, void (*)(gk_support *)> own(c.local, gk_support_destroy);
     if (rc) return rc;
-    ReadSrc src;
-    src.rec = (const uint8_t *)dev_records;
-    src.nreads = nreads;
-    src.stride = 1 + (u32)(read_len + 3) / 4;
-    src.max_len = read_len;
-    if ((rc = thread_launch(c, src, ctx->d_flags))) return rc;
+    if ((rc = thread_launch(c, ReadSrc::fixed(dev_records, nreads, read_len), ctx->d_flags))) return rc;
     return thread_end(c, sup, true, stats7, "gk_graph_thread_reads_dev");
 }
 
@@ -266,73 +260,16 @@ int gk_graph_thread_reads(gk_graph *g, gk_vmap *positions, gk_support *sup, cons
     gk_ctx *ctx = g->ctx;
     if (nreads && !bin) return fail(ctx, GK_E_INVALID, "gk_graph_thread_reads: null stream");
     if (nreads == 0) return GK_OK;
-    // the framing, walked on the host before anything is launched (gk_reads_correct's checks and messages)
+    // the framing, walked on the host before anything is launched
     size_t end = 0;
-    for (u64 r = 0; r < nreads; r++) {
-        if (end >= nbytes) return fail(ctx, GK_E_FORMAT, "truncated .bin stream: record " + std::to_string(r) + " starts past the end");
-        end += 1 + (size_t)(bin[end] + 3) / 4;
-        if (end > nbytes) return fail(ctx, GK_E_FORMAT, "truncated .bin stream inside record " + std::to_string(r));
-    }
+    if (int rc = bin_walk(ctx, bin, nbytes, nreads, &end)) return rc;
     ThreadCall c{g, positions};
     DevScratch tmp(ctx);
     int rc = thread_begin(c, tmp);
     std::unique_ptr<gk_support, void (*)(gk_support *)> own(c.local, gk_support_destroy);
     if (rc) return rc;
-    // Chunks of whole records, bounded by the staging area; two areas, so that the next chunk's upload (copy stream) runs beside
-    // this chunk's kernel (gk_reads_correct's scheme, without the way back).
-    const size_t stage_cap = ctx->hook_max_stage > 0 ? (size_t)ctx->hook_max_stage : (size_t)704 << 20;
-    struct Piece { size_t begin = 0, bytes = 0; std::vector<u32> offs; };
-    auto cut = [&](size_t pos) {
-        Piece p;
-        p.begin = pos;
-        while (pos < end) {
-            const size_t rb = 1 + (size_t)(bin[pos] + 3) / 4;
-            if (!p.offs.empty() && pos + rb - p.begin > stage_cap) break;
-            p.offs.push_back((u32)(pos - p.begin));
-            pos += rb;
-        }
-        p.offs.push_back((u32)(pos - p.begin));
-        p.bytes = pos - p.begin;
-        return p;
-    };
-    uint8_t *d_area[2] = {nullptr, nullptr};
-    u32 *d_off = nullptr;
-    size_t off_cap = 0;
-    const size_t area = std::min(stage_cap + 260, end) + 64;
-    auto run = [&]() -> int {
-        GK_HIP(ctx, tmp.get(&d_area[0], area));
-        Piece cur = cut(0);
-        GK_HIP(ctx, hipMemcpyAsync(d_area[0], bin, cur.bytes, hipMemcpyHostToDevice, ctx->stream));
-        for (int i = 0; cur.bytes; i ^= 1) {
-            Piece nxt;
-            if (cur.begin + cur.bytes < end) nxt = cut(cur.begin + cur.bytes);
-            if (cur.offs.size() > off_cap) {
-                if (d_off) tmp.release(d_off);
-                GK_HIP(ctx, tmp.get(&d_off, cur.offs.size()));
-                off_cap = cur.offs.size();
-            }
-            GK_HIP(ctx, hipMemcpyAsync(d_off, cur.offs.data(), cur.offs.size() * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-            ReadSrc src;
-            src.rec = d_area[i];
-            src.nreads = cur.offs.size() - 1;
-            src.off = d_off;
-            src.max_len = 255;                 // the host has walked this framing: every length byte is what the offsets say
-            if (int r = thread_launch(c, src, nullptr)) return r;
-            if (nxt.bytes) {
-                if (!d_area[i ^ 1]) GK_HIP(ctx, tmp.get(&d_area[i ^ 1], area));
-                GK_HIP(ctx, hipMemcpyAsync(d_area[i ^ 1], bin + nxt.begin, nxt.bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-                GK_HIP(ctx, hipEventRecord(ctx->cev[0], ctx->copy_stream));
-            }
-            // (the end of every chunk waits for the main stream: the offsets and the other area are free for the next chunk)
-            GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (nxt.bytes) GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->cev[0], 0));
-            cur = std::move(nxt);
-        }
-        return GK_OK;
-    };
-    rc = run();
-    (void)hipStreamSynchronize(ctx->copy_stream);            // (the areas go back to the pool, which does not wait for uploads)
-    if (rc) return rc;
+    // nothing comes back from a piece: the feeder's end of a piece is the plain wait for the main stream
+    if ((rc = bin_feed(ctx, tmp, bin, end, [&](const ReadSrc &src, uint8_t *, const BinPiece &, D2H *) { return thread_launch(c, src, nullptr); }))) return rc;
     return thread_end(c, sup, false, stats7, "gk_graph_thread_reads");
 }
 

@@ -300,13 +300,10 @@ int gk_vmap_put_new_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, co
     if (int rc = vm_check_keys(m, lo, hi, n)) return rc;
     DevScratch b(ctx);
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_val = nullptr;
-    hipError_t e = b.get(&d_lo, n);
-    if (e == hipSuccess && m->W == 2) e = b.get(&d_hi, n);
-    if (e == hipSuccess) e = b.get(&d_val, n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lo, lo, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && d_hi) e = hipMemcpyAsync(d_hi, hi, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_val, values, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_put_new_batch");
+    b.upload(&d_lo, lo, n);
+    if (m->W == 2) b.upload(&d_hi, hi, n);
+    b.upload(&d_val, values, n);
+    if (b.error() != hipSuccess) return hip_fail(ctx, b.error(), "gk_vmap_put_new_batch");
     return vmap_put_new_dev(m, d_lo, d_hi, d_val, n);
 }
 
@@ -321,16 +318,12 @@ int gk_vmap_update_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, con
     DevScratch b(ctx);
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_val = nullptr, *d_slot = nullptr;
     u32 *d_win = nullptr;
-    hipError_t e = b.get(&d_lo, n);
-    if (e == hipSuccess && m->W == 2) e = b.get(&d_hi, n);
-    if (e == hipSuccess) e = b.get(&d_val, n);
-    if (e == hipSuccess) e = b.get(&d_slot, n);
-    if (e == hipSuccess) e = b.get(&d_win, m->capacity);
-    if (e == hipSuccess) e = hipMemsetAsync(d_win, 0, m->capacity * 4, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lo, lo, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && d_hi) e = hipMemcpyAsync(d_hi, hi, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_val, values, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_update_batch");
+    b.upload(&d_lo, lo, n);
+    if (m->W == 2) b.upload(&d_hi, hi, n);
+    b.upload(&d_val, values, n);
+    b.get(&d_slot, n);
+    b.zeroed(&d_win, m->capacity);
+    if (b.error() != hipSuccess) return hip_fail(ctx, b.error(), "gk_vmap_update_batch");
     const int grid = vgrid(ctx, n);
     GK_BY_W(m->W,
         hipLaunchKernelGGL(k_vm_find_or_claim<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, n, d_slot, d_win, m->d_ctr);
@@ -352,13 +345,10 @@ int gk_vmap_get_all_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, ui
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_out = nullptr;
     u32 *d_cnt = nullptr;
     unsigned long long *d_off = nullptr;
-    hipError_t e = b.get(&d_lo, n);
-    if (e == hipSuccess && m->W == 2) e = b.get(&d_hi, n);
-    if (e == hipSuccess) e = b.get(&d_cnt, n);
-    if (e == hipSuccess) e = b.get(&d_off, n + 1);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lo, lo, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && d_hi) e = hipMemcpyAsync(d_hi, hi, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_get_all_batch");
+    b.upload(&d_lo, lo, n);
+    if (m->W == 2) b.upload(&d_hi, hi, n);
+    b.get(&d_cnt, n);
+    if (b.error() != hipSuccess) return hip_fail(ctx, b.error(), "gk_vmap_get_all_batch");
     const int grid = vgrid(ctx, n);
     const u32 nolimit = 0xffffffffu;
     GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_get_all<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, n, nolimit, nullptr, d_cnt, nullptr));
@@ -370,9 +360,9 @@ int gk_vmap_get_all_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, ui
     if (tot > values_cap) return fail(ctx, GK_E_CAPACITY, "value buffer too small: need " + std::to_string(tot));
     if (tot == 0) return GK_OK;
     if (!values_out) return fail(ctx, GK_E_INVALID, "null value buffer");
-    e = b.get(&d_out, tot);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets_out, (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_get_all_batch");
+    b.get(&d_out, tot);
+    b.upload(&d_off, offsets_out, n + 1);
+    if (b.error() != hipSuccess) return hip_fail(ctx, b.error(), "gk_vmap_get_all_batch");
     GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_get_all<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, vtable<W>(m), d_lo, d_hi, n, nolimit, d_off, d_cnt, d_out));
     GK_HIP(ctx, read_back(ctx, values_out, d_out, tot));
     return GK_OK;
@@ -390,16 +380,12 @@ int gk_vmap_get_batch(gk_vmap *m, const uint64_t *lo, const uint64_t *hi, uint64
     unsigned long long *d_off = nullptr;
     std::vector<unsigned long long> off(n + 1);
     for (uint64_t i = 0; i <= n; i++) off[i] = i;
-    hipError_t e = b.get(&d_lo, n);
-    if (e == hipSuccess && m->W == 2) e = b.get(&d_hi, n);
-    if (e == hipSuccess) e = b.get(&d_cnt, n);
-    if (e == hipSuccess) e = b.get(&d_off, n + 1);
-    if (e == hipSuccess) e = b.get(&d_out, n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lo, lo, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && d_hi) e = hipMemcpyAsync(d_hi, hi, n * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, n * 8, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_get_batch");
+    b.upload(&d_lo, lo, n);
+    if (m->W == 2) b.upload(&d_hi, hi, n);
+    b.get(&d_cnt, n);
+    b.upload(&d_off, off.data(), n + 1);
+    b.zeroed(&d_out, n);
+    if (b.error() != hipSuccess) return hip_fail(ctx, b.error(), "gk_vmap_get_batch");
     const int grid = vgrid(ctx, n);
     // apply (ArrayDNAMap.scala:90-101) = the first slot of the probe sequence that holds the key: getAll cut off at one
     for (int pass = 0; pass < 2; pass++)
@@ -421,12 +407,11 @@ int gk_vmap_export(gk_vmap *m, uint64_t *lo, uint64_t *hi, uint64_t *values, uin
     u64 *d_lo = nullptr, *d_hi = nullptr, *d_val = nullptr;
     unsigned long long *d_cur = nullptr;
     const u64 cnt = m->size;
-    hipError_t e = b.get(&d_lo, cnt);
-    if (e == hipSuccess) e = b.get(&d_hi, cnt);
-    if (e == hipSuccess) e = b.get(&d_val, cnt);
-    if (e == hipSuccess) e = b.get(&d_cur, 1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_cur, 0, 8, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gk_vmap_export");
+    b.get(&d_lo, cnt);
+    b.get(&d_hi, cnt);
+    b.get(&d_val, cnt);
+    b.zeroed(&d_cur, 1);
+    if (b.error() != hipSuccess) return hip_fail(ctx, b.error(), "gk_vmap_export");
     GK_BY_W(m->W, hipLaunchKernelGGL(k_vm_export<W>, dim3(vgrid(ctx, m->capacity)), dim3(BLOCK), 0, ctx->stream, (const Slot<W> *)m->slots, m->capacity, m->k == 64 ? 1u : 0u, d_lo, d_hi, d_val, d_cur));
     GK_HIP(ctx, read_back(ctx, {{lo, d_lo, cnt * 8}, {hi, d_hi, cnt * 8}, {values, d_val, cnt * 8}}));
     return GK_OK;

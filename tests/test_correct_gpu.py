@@ -235,6 +235,28 @@ def test_ragged_host_stream(ctx, k):
     m.close()
 
 
+def test_every_record_its_own_chunk(ctx):
+    """a staging limit of one byte: every piece is a single record, so both staging areas and the copy stream's event
+    alternate on every record, and every record comes back from the area it went to"""
+    k = 21
+    reads, counts = ragged_stream(k)
+    reads = reads[:40]
+    assert len(reads) == 40 and len({len(r) for r in reads}) >= 5
+    raw = dna.reads_to_bin(reads)
+    m = table_of(ctx, k, "counted", 0)
+    want, want_st = m.correct_reads(raw, len(reads), 3)          # unchunked
+    assert want != raw and want_st["corrected"] > 0
+    assert (want, {n: want_st[n] for n in X.STATS}) == X.correct_bin(counts, raw, len(reads), k, 3)
+    ctx.set_option("test_max_stage", 1)
+    try:
+        got, st = m.correct_reads(raw, len(reads), 3)
+    finally:
+        ctx.set_option("test_max_stage", 0)
+    assert got == want
+    check_stats(st, {n: want_st[n] for n in X.STATS})
+    m.close()
+
+
 def fixed_records(reads, read_len):
     """records at the fixed stride 1 + ceil(read_len / 4); the bytes a shorter record leaves are filled with 0xEE"""
     stride = 1 + (read_len + 3) // 4

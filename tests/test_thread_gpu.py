@@ -154,6 +154,26 @@ def test_ragged_host_fixed_stride_and_dev_are_identical(ctx, g21):
         x.close()
 
 
+def test_every_record_its_own_chunk(ctx, g21):
+    """a staging limit of one byte: every piece is a single record, so both staging areas and the copy stream's event
+    alternate on every record"""
+    k, reads, g, vm = g21
+    sel = reads[::7][:40]
+    assert len(sel) == 40 and len({len(r) for r in sel}) >= 5
+    want_sup, want = restate(g, sel)
+    assert 0 < want["records"] <= 40 and want["crossings"] > 0
+    sup, st = thread(g, vm, sel)                                   # unchunked
+    assert st == want and gpu_support_by_content(g, k, sup) == want_sup
+    ctx.set_option("test_max_stage", 1)
+    try:
+        sup2, st2 = thread(g, vm, sel)
+    finally:
+        ctx.set_option("test_max_stage", 0)
+    assert st2 == st and snapshot(sup2) == snapshot(sup)
+    for x in (sup, sup2):
+        x.close()
+
+
 def test_one_workgroup_and_the_combine_give_the_same(ctx, g21):
     k, reads, g, vm = g21
     sup, st = thread(g, vm, reads)
