@@ -140,6 +140,12 @@ SIGNATURES = {
     "gk_graph_clip_tips": (C.c_int, [vp, vp, C.c_uint64, u64p]),
     "gk_graph_edge_distance": (C.c_int, [vp, u32p, u32p, C.c_uint64, C.c_uint32, u32p]),
     "gk_graph_pop_bubbles": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, u64p, u64p]),
+    "gk_graph_contigs_plan": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp)]),
+    "gk_contigs_destroy": (None, [vp]),
+    "gk_contigs_stats": (C.c_int, [vp, u64p]),
+    "gk_contigs_read": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, u64p]),
+    "gk_contigs_write": (C.c_int, [vp, C.c_char_p]),
+    "gk_contigs_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "gk_support_create": (C.c_int, [vp, C.POINTER(vp)]),
     "gk_support_destroy": (None, [vp]),
     "gk_support_size": (C.c_int, [vp, u64p, u64p, u64p]),

@@ -63,8 +63,8 @@ __device__ __forceinline__ void cover_run(const Table<W, S> &t, Kmer<2> node, co
     }
 }
 
-// Per-edge results, indexed by edge id; written for the live edges (`want` == nullptr) or the live edges marked in `want`.
-struct EdgeCov { u64 *sum; u32 *mn, *mx, *miss; };
+// Per-edge results (EdgeCov, gk_graph.h), indexed by edge id; written for the live edges (`want` == nullptr) or the live edges
+// marked in `want`.
 static constexpr u64 COV_SHORT = 64;      // windows one lane walks alone
 static constexpr u64 COV_RUN = 16;        // consecutive windows per lane and pass of the long form
 
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(BLOCK) void k_bubble_mark(GraphView g, EdgeCov cov,
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int check_counts(const gk_graph *g, gk_map *counts, const char *who) {
+int check_counts(const gk_graph *g, gk_map *counts, const char *who) {
     if (!counts || !counts->ctx) return fail(g->ctx, GK_E_INVALID, std::string(who) + ": null map handle");
     if (counts->ctx != g->ctx) return fail(g->ctx, GK_E_INVALID, std::string(who) + ": the map belongs to another context");
     if (counts->k != g->k) return fail(g->ctx, GK_E_INVALID, std::string(who) + ": the map's k is not the graph's");
@@ -313,7 +313,7 @@ static int check_counts(const gk_graph *g, gk_map *counts, const char *who) {
 }
 
 // the coverage of every live edge (`want` == nullptr) or of the marked ones into arrays owned by `tmp`; stream-ordered, no sync
-static int coverage_pass(gk_graph *g, gk_map *counts, DevScratch &tmp, const uint8_t *want, EdgeCov *cov) {
+int coverage_pass(gk_graph *g, gk_map *counts, DevScratch &tmp, const uint8_t *want, EdgeCov *cov) {
     gk_ctx *ctx = g->ctx;
     const GraphView &v = g->v;
     tmp.get(&cov->sum, v.n_edges);

@@ -166,6 +166,14 @@ int graph_alloc_edges(gk_graph *g, u64 n);
 // Stream-ordered, no synchronisation; `who` names the entry point in the error text.  (Not exported, like DevScratch.)
 __attribute__((visibility("hidden"))) int graph_in_lists(gk_graph *g, DevScratch &tmp, const char *who, unsigned long long **off, u32 **list);
 
+// Edge coverage from a count table (gk_coverage.hip), for the callers that decide something from it (tips, bubbles) or print it
+// (gk_contigs.hip).  Per-edge results are indexed by edge id and live in the caller's `tmp`; coverage_pass writes them for every
+// live edge (`want` == nullptr) or for the live edges marked in `want`, stream-ordered, without a sync.  check_counts: the table
+// is of this graph's k and context (GK_E_INVALID otherwise) and its slots are materialised.
+struct EdgeCov { u64 *sum; u32 *mn, *mx, *miss; };
+int check_counts(const gk_graph *g, gk_map *counts, const char *who);
+__attribute__((visibility("hidden"))) int coverage_pass(gk_graph *g, gk_map *counts, DevScratch &tmp, const uint8_t *want, EdgeCov *cov);
+
 // The front end every paired-end entry point shares (gk_pairs.hip; GraphSimplifier.scala:213-217): the pairs whose mates both
 // hold k bases are cut from the `.bin` stream (a fixed-stride stream on the device by k_pair_keys, a ragged one on the host),
 // their four getAll run as ONE batch whose results stay in HBM as CSR, and k_check_positions is queued behind it.  Key 4p + q

@@ -406,6 +406,7 @@ int graph_load_impl(gk_ctx *ctx, const std::string &path, gk_graph *g, float *ms
     if (fsize > L.end) return bad("trailing bytes (" + std::to_string(fsize) + " bytes, the header needs " + std::to_string(L.end) + ")");
     g->ctx = ctx;
     g->k = (int)h.k;
+    g->v.k = (int)h.k;           // (the kernels that take the view alone read k from it: edge coverage, the contigs)
     g->W = words_for_k((int)h.k);
     if (int rc = graph_alloc_nodes(g, h.node_bound)) return rc;
     if (int rc = graph_alloc_edges(g, h.edge_bound)) return rc;

@@ -212,6 +212,19 @@ class HipGraph:
                                              C.byref(rm), C.byref(pairs)), self.ctx.h)
         return rm.value, pairs.value
 
+    # ---- contigs as FASTA (this project's own rule: include/genome_amd.h) ----------------------------------------------
+    def contigs(self, counts: HipDNAMap = None, min_len: int = 0, line_width: int = 60, strands: int = 1) -> "Contigs":
+        """The assembly as FASTA text, planned on the device: one record `>e<id> len=<n>[ cov=<mean>]` per live edge whose path
+        (start k-mer ++ seq, n bases) is not above its reverse complement (strands = 2: every live edge), n >= min_len, in
+        ascending edge id, the sequence wrapped at `line_width` (0: one line).  `counts` (any table of this k) adds the cov=
+        field.  -> a Contigs: stats(), read(), text(), write().  Any edit of the graph makes it stale (GkError GK_E_STATE)."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        h = L.vp()
+        L.check(L.lib().gk_graph_contigs_plan(self.h, counts.h if counts is not None else None, int(min_len), int(line_width), int(strands),
+                                              C.byref(h)), self.ctx.h)
+        return Contigs(self, h)
+
     def walkPairs(self, positions, support: "Support", bin_bytes, npairs: int, range_lo: int = 180, range_hi: int = 250):
         """:213-247: the pairs' positions through `positions` (getGraphMap of this graph as it is now), annotate, the bounded
         walks; the supported (edge, edge) pairs are counted in `support`."""
@@ -312,6 +325,66 @@ class HipGraph:
                           dna.unpack(int(e["elo"][i]), int(e["ehi"][i]), k),
                           dna.unpack_2bit(e["seq"][o:o + (ln + 3) // 4], ln)))
         return nodes, edges
+
+
+# the statistics of gk_contigs_stats, in the order of its `stats9` array: live_edges is the sum of the four after it
+CONTIG_STATS = ("live_edges", "short", "forward", "self_twin", "reverse", "records", "bases", "text_bytes", "missing_windows")
+
+
+class Contigs:
+    """A plan of the FASTA text of a graph's contigs (HipGraph.contigs): the text itself is emitted by the device when it is
+    read or written.  Holds its graph; stale (GkError GK_E_STATE from read / text / write) once the graph has been edited."""
+
+    def __init__(self, graph: HipGraph, handle):
+        self.graph, self.ctx, self.h = graph, graph.ctx, handle
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:               # (see HipDNAMap.close)
+                L.lib().gk_contigs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h or not self.ctx.h or not self.graph.h:
+            raise L.GkError(L.GK_E_STATE, "the contigs or their graph are closed")
+
+    def stats(self) -> dict:
+        """the nine numbers of the plan, named as CONTIG_STATS; they still answer when the plan is stale"""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the contigs are closed")
+        st = np.zeros(len(CONTIG_STATS), np.uint64)
+        L.check(L.lib().gk_contigs_stats(self.h, L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(CONTIG_STATS, (int(x) for x in st)))
+
+    def read(self, offset: int, n: int) -> bytes:
+        """bytes [offset, offset + n) of the text, fewer at its end; GkError GK_E_INVALID for an offset beyond it"""
+        self._live()
+        buf = np.empty(max(int(n), 1), np.uint8)
+        got = C.c_uint64()
+        L.check(L.lib().gk_contigs_read(self.h, int(offset), buf.ctypes.data, int(n), C.byref(got)), self.ctx.h)
+        return buf[:got.value].tobytes()
+
+    def text(self) -> bytes:
+        return self.read(0, self.stats()["text_bytes"])
+
+    def last_ms(self) -> dict:
+        """wall ms of the last read / write: the emit kernels (device events), waits for copies, the sink, the whole call"""
+        arr = (C.c_float * 4)()
+        L.check(L.lib().gk_contigs_last_ms(self.h, arr), self.ctx.h)
+        return dict(zip(("emit_kernels", "copies", "sink", "total"), (float(x) for x in arr)))
+
+    def write(self, path):
+        """the whole text to `path`; written aside, then renamed onto it"""
+        self._live()
+        L.check(L.lib().gk_contigs_write(self.h, os.fsencode(path)), self.ctx.h)
 
 
 # the classes of gk_graph_pair_distances, in the order of its `classes` array

@@ -512,6 +512,49 @@ class Support {
     gk_support *h_ = nullptr;
 };
 
+// gk_contigs: a plan of the FASTA text of a graph's contigs (Graph::contigs; the rule: include/genome_amd.h, "contigs").  The text
+// is emitted by the device when it is read or written.  The graph must outlive the plan; after any edit of the graph read / text
+// / write throw GK_E_STATE and stats() still answers.
+class Contigs {
+  public:
+    struct Stats {
+        uint64_t liveEdges = 0, shortEdges = 0, forward = 0, selfTwin = 0, reverse = 0, records = 0, bases = 0, textBytes = 0, missingWindows = 0;
+        std::string json() const {                           // the names of gk_contigs_stats' stats9
+            const uint64_t v[9] = {liveEdges, shortEdges, forward, selfTwin, reverse, records, bases, textBytes, missingWindows};
+            const char *names[9] = {"live_edges", "short", "forward", "self_twin", "reverse", "records", "bases", "text_bytes", "missing_windows"};
+            std::string s = "{";
+            for (int i = 0; i < 9; i++) s += std::string(i ? ",\"" : "\"") + names[i] + "\":" + std::to_string(v[i]);
+            return s + "}";
+        }
+    };
+    Contigs(gk_ctx *ctx, gk_contigs *h) : ctx_(ctx), h_(h) {}
+    ~Contigs() { close(); }
+    void close() { gk_contigs_destroy(h_); h_ = nullptr; }
+    Contigs(Contigs &&o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    Contigs(const Contigs &) = delete;
+    Contigs &operator=(const Contigs &) = delete;
+    Stats stats() const {
+        uint64_t v[9] = {};
+        check(gk_contigs_stats(h_, v), ctx_);
+        return Stats{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
+    }
+    // bytes [offset, offset + n) of the text, fewer at its end
+    std::string read(uint64_t offset, uint64_t n) {
+        std::string out((size_t)n, '\0');
+        uint64_t got = 0;
+        check(gk_contigs_read(h_, offset, out.data(), n, &got), ctx_);
+        out.resize((size_t)got);
+        return out;
+    }
+    std::string text() { return read(0, stats().textBytes); }
+    // the whole text to path, written aside and renamed onto it
+    void write(const std::string &path) { check(gk_contigs_write(h_, path.c_str()), ctx_); }
+
+  private:
+    gk_ctx *ctx_ = nullptr;
+    gk_contigs *h_ = nullptr;
+};
+
 struct Edge {                 // S/data/graph/Edge.scala:11 (ids are not part of the observable result)
     DNASeq start, end;
     std::string seq;
@@ -718,6 +761,14 @@ class Graph {
         return out;
     }
 
+    // The assembly as FASTA, planned on the device (include/genome_amd.h, "contigs"): one record `>e<id> len=<n>[ cov=<mean>]` per
+    // live edge whose path (start k-mer ++ seq) is not above its reverse complement (bothStrands: every live edge), n >= minLen, in
+    // ascending edge id, wrapped at lineWidth (0: one line); `counts` (may be null) adds the cov= field.
+    Contigs contigs(const DNAMap *counts = nullptr, uint64_t minLen = 0, uint32_t lineWidth = 60, bool bothStrands = false) const {
+        gk_contigs *c = nullptr;
+        check(gk_graph_contigs_plan(h_, counts ? counts->handle() : nullptr, minLen, lineWidth, bothStrands ? 2 : 1, &c), ctx_.handle());
+        return Contigs(ctx_.handle(), c);
+    }
     // the `contigs` file of GraphSimplifier.scala:338-347: per edge its sequence, then ">abacaba<i>"
     // (edge order: canonical, since the reference's is ConcurrentHashMap order)
     void writeContigs(std::ostream &out) const {

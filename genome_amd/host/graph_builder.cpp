@@ -6,6 +6,7 @@
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
 //                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]]
 //                 [--out prefix] [--save-graph PATH] [--correct N|auto]
+//                 [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
 //   --fastq converts the FASTQ file on the GPU first (Convert2bin, gk_fastq; --split N = its n, default 36) and takes the pair
 //   count from the conversion; the flow is then the same.  Not with --world (exit 2): convert2bin the file first.
@@ -33,6 +34,13 @@
 //   map, the pairs' walks with range LO to HI (the reference: 180 to 250, :146), node split at genome.cutoff = CUTOFF,
 //   removeEdge, simplifyGraph; its counters join the JSON;
 //   --out writes <prefix>.nodes.txt, .edges.txt, .contigs (GraphSimplifier.scala:338-347) and .dot (Graph.scala:74-88)
+//   --contigs PATH writes the final graph's contigs as FASTA on the device (gk_graph_contigs_plan / gk_contigs_write: this project's
+//   own rule, beside --out's .contigs, which stays the reference's): one record `>e<id> len=<n> cov=<mean>` per live edge whose path
+//   is not above its reverse complement (--contig-both-strands: every live edge), n >= --contig-min-len (default 0), lines of
+//   --contig-width bases (default 60, 0 = one line); the coverage comes from the table the graph was built from.  The JSON gains
+//   "contigs_fasta":{the nine stats}.  Over --world rank 0 writes.  (Where the two strands of the genome are separate components,
+//   the retain keeps one of them and its edges may be the reverse ones, which one strand per contig leaves to their dead twins:
+//   "forward" != "reverse" in the stats says so; --contig-both-strands or --no-retain writes them.)
 //   --save-graph writes the same graph as a graph file (gk_graph_save; GraphBuilder.scala:55-56) for graph_simplifier
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Rank 0 writes the
 //   communicator id to PATH (a file that must not exist yet: written aside, then renamed), the others wait for it (2 minutes at
@@ -93,7 +101,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
                              "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--out prefix] [--save-graph PATH] "
-                             "[--correct N|auto] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string infile = argv[1];
@@ -115,7 +123,10 @@ int main(int argc, char **argv) {
     int walkCutoff = -1, walkLo = 180, walkHi = 250;
     bool walkAuto = false;                                   // --walk-pairs CUTOFF auto: the range is measured from the pairs (graph_simplifier --range auto)
     long maxInsert = 4095;
-    std::string out, idFile, saveGraph, spectrumPath;
+    std::string out, idFile, saveGraph, spectrumPath, contigsPath;
+    uint64_t contigMinLen = 0;
+    uint32_t contigWidth = 60;
+    bool contigBoth = false;
     int world = 0, rank = 0;                      // world 0: one GPU, no communicator
     for (int i = 4; i < argc; i++) {
         if (!std::strcmp(argv[i], "--rounds") && i + 1 < argc) {
@@ -149,6 +160,10 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--walk-pairs") && i + 3 < argc) { walkCutoff = std::stoi(argv[++i]); walkLo = std::stoi(argv[++i]); walkHi = std::stoi(argv[++i]); }
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
+        else if (!std::strcmp(argv[i], "--contigs") && i + 1 < argc) contigsPath = argv[++i];
+        else if (!std::strcmp(argv[i], "--contig-min-len") && i + 1 < argc) contigMinLen = std::stoull(argv[++i]);
+        else if (!std::strcmp(argv[i], "--contig-width") && i + 1 < argc) contigWidth = (uint32_t)std::stoul(argv[++i]);
+        else if (!std::strcmp(argv[i], "--contig-both-strands")) contigBoth = true;
         else if (!std::strcmp(argv[i], "--world") && i + 1 < argc) world = std::stoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) rank = std::stoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--id-file") && i + 1 < argc) idFile = argv[++i];
@@ -290,6 +305,13 @@ int main(int argc, char **argv) {
         auto [n2, e2, l2] = graph.counts();
         if (pm) pm->barrier();
         if (rank != 0) return 0;
+        // --contigs: the text is written after the last graph stage, with the coverage of the table the graph was built from
+        genome::Contigs::Stats fasta;
+        if (!contigsPath.empty()) {
+            auto contigs = graph.contigs(kmersFreq.get(), contigMinLen, contigWidth, contigBoth);
+            contigs.write(contigsPath);
+            fasta = contigs.stats();
+        }
         std::printf("{\"k\":%d,\"rounds\":%d,\"good_kmers\":%llu,\"graph_nodes\":%llu,\"graph_edges\":%llu,"
                     "\"total_edges_length\":%llu,\"components\":%llu,\"max_component_size\":%llu,"
                     "\"retained_nodes\":%llu,\"retained_edges\":%llu,\"retained_edges_length\":%llu,",
@@ -322,6 +344,7 @@ int main(int argc, char **argv) {
             std::printf("\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},",
                         (unsigned long long)supPairs, (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges,
                         (unsigned long long)newNodes);
+        if (!contigsPath.empty()) std::printf("\"contigs_fasta\":%s,", fasta.json().c_str());
         auto dump = [](const char *name, const std::map<uint64_t, uint64_t> &h, const char *tail) {
             std::printf("\"%s\":[", name);
             bool first = true;

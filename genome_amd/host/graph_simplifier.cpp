@@ -5,7 +5,8 @@
 //
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
 //                    [--take-first N] [--thread-reads [--no-pairs]]
-//                    [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]
+//                    [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
+//                    [--world W --rank R --id-file PATH]
 //   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
 //   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
 //   k comes from the graph (:153); the range defaults to the reference's 180 to 250 (:146), the cutoff is genome.cutoff.
@@ -21,6 +22,11 @@
 //   The stage: getGraphMap (:188), walkPairs over the first N pairs (:213-263), splitBySupport (:272-316), simplifyGraph (:318).
 //   --out writes graph_builder's <prefix>.nodes.txt, .edges.txt, .contigs (:338-347) and .dot; --save-graph writes the final
 //   graph as a graph file (the reference's graphFile, :352).
+//   --contigs PATH writes the final graph's contigs as FASTA on the device (gk_graph_contigs_plan / gk_contigs_write: this project's
+//   own rule, beside --out's .contigs, which stays the reference's): one record `>e<id> len=<n>` per live edge whose path is not
+//   above its reverse complement (--contig-both-strands: every live edge), n >= --contig-min-len (default 0), lines of
+//   --contig-width bases (default 60, 0 = one line).  No cov= field: this tool holds no count table.  The JSON gains
+//   "contigs_fasta":{the nine stats}.  Over --world rank 0 writes.
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
 //   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
 //   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
@@ -72,7 +78,8 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
-                             "[--thread-reads [--no-pairs]] [--out prefix] [--save-graph PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--thread-reads [--no-pairs]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
+                             "[--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -80,7 +87,10 @@ int main(int argc, char **argv) {
     data.count = std::stoull(argv[3]);
     int cutoff = -1, rangeLo = 180, rangeHi = 250;          // GraphSimplifier.scala:146
     uint64_t takeFirst = UINT64_MAX;
-    std::string out, saveGraph, idFile, insertHist;
+    std::string out, saveGraph, idFile, insertHist, contigsPath;
+    uint64_t contigMinLen = 0;
+    uint32_t contigWidth = 60;
+    bool contigBoth = false;
     int world = 0, rank = 0;
     bool rangeAuto = false, threadReads = false, noPairs = false;
     long maxInsert = 4095;
@@ -95,6 +105,10 @@ int main(int argc, char **argv) {
         else if (!std::strcmp(argv[i], "--no-pairs")) noPairs = true;
         else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
         else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
+        else if (!std::strcmp(argv[i], "--contigs") && i + 1 < argc) contigsPath = argv[++i];
+        else if (!std::strcmp(argv[i], "--contig-min-len") && i + 1 < argc) contigMinLen = std::stoull(argv[++i]);
+        else if (!std::strcmp(argv[i], "--contig-width") && i + 1 < argc) contigWidth = (uint32_t)std::stoul(argv[++i]);
+        else if (!std::strcmp(argv[i], "--contig-both-strands")) contigBoth = true;
         else if (!std::strcmp(argv[i], "--world") && i + 1 < argc) world = std::stoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) rank = std::stoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--id-file") && i + 1 < argc) idFile = argv[++i];
@@ -190,6 +204,12 @@ int main(int argc, char **argv) {
             for (int c = 0; c < 9; c++)
                 autoJson += std::string(c ? "," : "") + "\"" + genome::Graph::pairClassNames[c] + "\":" + std::to_string(dist.classes[c]);
             autoJson += "}},";
+        }
+        // --contigs: the text of the final graph (this tool holds no count table: no cov= field)
+        if (!contigsPath.empty()) {
+            auto contigs = graph.contigs(nullptr, contigMinLen, contigWidth, contigBoth);
+            contigs.write(contigsPath);
+            autoJson += "\"contigs_fasta\":" + contigs.stats().json() + ",";
         }
         if (threadReads) {
             autoJson += "\"thread_reads\":{";

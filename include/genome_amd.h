@@ -538,6 +538,54 @@ int gk_graph_edge_distance(gk_graph *g, const uint32_t *e1, const uint32_t *e2, 
  * point and unchanged. */
 int gk_graph_pop_bubbles(gk_graph *g, gk_map *counts, uint64_t max_len, uint32_t max_diff, uint64_t *removed_edges, uint64_t *pairs_compared);
 
+/* ---- contigs: this project's own rule (the reference prints every edge's seq BEFORE a ">abacaba<i>" line, both strands, without
+ * the start k-mer: GraphSimplifier.scala:338-347; the host side's Graph::writeContigs is its literal twin and stays) ----
+ * The assembly as FASTA text, written on the device.  Integers only.
+ * Path.  The path of a live edge e is P(e) = start k-mer ++ seq: n = k + len bases in the 2-bit codes A0 G1 C2 T3 (complement =
+ * 3 - code).  The contigs of two edges that meet in a node therefore OVERLAP by that node's k bases.  This is deliberate: a contig
+ * is the whole sequence its edge spells, usable on its own, and the overlap is how a reader re-joins contigs at a junction.
+ * Strand.  R(e) = the reverse complement of P(e).  P and R are compared lexicographically by code: e is FORWARD if P < R,
+ * SELF_TWIN if P == R, REVERSE if P > R.  The twin of an edge has path R(e), so in a strand-closed edge set exactly one edge of
+ * every twin pair is forward, and a self_twin edge is its own twin.  The comparison needs no twin lookup: it is well defined after
+ * node splits (copies share a k-mer) and after edits that left the set not strand-closed.
+ * Classes.  Every live edge falls into exactly one, tested in this order: 1. short: n < min_len (min_len = 0 keeps all);
+ * 2. forward, self_twin or reverse, as above.
+ * Selection.  strands = 1: the records are the forward and self_twin edges (a reverse edge whose twin is dead is NOT written; the
+ * stats show it: in a strand-closed graph forward == reverse).  strands = 2: all three classes (still counted apart).  Any other
+ * value: GK_E_INVALID.
+ * Text.  Records in ascending edge id.  One record:
+ *     >e<id> len=<n>[ cov=<q/100>.<q%100 as two digits>]\n
+ *     <the n bases as ACGT text, a '\n' after every line_width bases and after the last base>
+ * line_width = 0: the whole sequence on one line.  There is never an empty line, also when line_width divides n.  The cov= field is
+ * there iff a count table was passed: q = floor(100 * sum / kmers), with sum and kmers as gk_graph_edge_coverage defines them
+ * (len + 1 windows, both end nodes included), computed without overflow.  Windows the table does not hold count 0 and are summed
+ * into the stats (over the records); they are no error (gk_graph_edge_coverage's contract, not the tips').  The record of an edge
+ * is the same under strands = 1 and strands = 2: always the edge's own path and id.
+ * The plan holds what the text is a pure function of (the selected ids, each record's byte offset, q) and the graph's state
+ * counter.  The graph is not changed, and must outlive the plan.  After ANY edit of the graph gk_contigs_read and gk_contigs_write
+ * return GK_E_STATE; gk_contigs_stats still answers.  `counts` (may be NULL) of another k or context: GK_E_INVALID.  NULL handles:
+ * GK_E_INVALID.  A graph without a live edge: an empty text, GK_OK.  A record of 2^32 bytes or more: GK_E_CAPACITY.  On any error
+ * *out stays NULL and everything the call allocated is freed.
+ * On the device: one wave per live edge compares P with R 64 bases at a time and stops at the first difference; an exclusive scan
+ * over the edge ids gives the record offsets; the text is emitted by byte range — a lane writes one aligned 8-byte word, found by a
+ * binary search in the offsets — in chunks of 64 MiB through two pinned buffers, the next chunk's kernel beside the current
+ * chunk's copy and file write. */
+typedef struct gk_contigs gk_contigs;
+int gk_graph_contigs_plan(gk_graph *g, gk_map *counts, uint64_t min_len, uint32_t line_width, int strands, gk_contigs **out);
+void gk_contigs_destroy(gk_contigs *c);
+/* stats9 = {live_edges, short, forward, self_twin, reverse, records, bases, text_bytes, missing_windows}; element 0 = the sum of
+ * elements 1..4; bases = the sum of n over the records */
+int gk_contigs_stats(const gk_contigs *c, uint64_t *stats9);
+/* bytes [offset, offset + min(cap, text_bytes - offset)) of the text; *n = bytes written (n may be NULL); offset > text_bytes:
+ * GK_E_INVALID */
+int gk_contigs_read(gk_contigs *c, uint64_t offset, char *buf, uint64_t cap, uint64_t *n);
+/* the whole text to `path`, through path + ".tmp" and a rename (gk_graph_save's contract: a failed write leaves nothing at path;
+ * a path that cannot be opened or written: GK_E_INVALID with the errno text) */
+int gk_contigs_write(gk_contigs *c, const char *path);
+/* wall ms of the last gk_contigs_read / gk_contigs_write on this handle: {the emit kernels (device events, summed over the chunks),
+ * waits for the device-to-host copies, the sink (file writes, or the copy into buf), the whole call} */
+int gk_contigs_last_ms(const gk_contigs *c, float *ms4);
+
 /* ---- the graph file: MapGraph.write (Graph.scala:232-261) / Graph(file) (:384-390) --------------------------------------
  * The stage boundary between GraphBuilder (GraphBuilder.scala:55-56) and GraphSimplifier (GraphSimplifier.scala:152-153).
  * This project's own format (the reference's is Kryo).  Version 1, every value little-endian.  Header, 128 bytes:
