@@ -9,11 +9,7 @@
 //
 // Build: g++ -std=c++17 -O2 -I include genome_amd/host/check_graph.cpp -L genome_amd -lgenome_amd
 //        -Wl,-rpath,'$ORIGIN/..' -o genome_amd/host/check_graph
-#include <cstdio>
-#include <cstring>
-#include <string>
-
-#include "genome.hpp"
+#include "tool_common.hpp"
 
 int main(int argc, char **argv) {
     const char *usage = "usage: %s <graph.gkg> <genome.fasta> [--longer-than N] [--per-line] [--missing N]\n";
@@ -21,16 +17,10 @@ int main(int argc, char **argv) {
     const std::string graphFile = argv[1], fasta = argv[2];
     uint64_t longerThan = 200, maxMissing = 0;
     bool perLine = false;
-    try {
-        for (int i = 3; i < argc; i++) {
-            if (!std::strcmp(argv[i], "--longer-than") && i + 1 < argc) longerThan = std::stoull(argv[++i]);
-            else if (!std::strcmp(argv[i], "--missing") && i + 1 < argc) maxMissing = std::stoull(argv[++i]);
-            else if (!std::strcmp(argv[i], "--per-line")) perLine = true;
-            else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); std::fprintf(stderr, usage, argv[0]); return 2; }
-        }
-    } catch (const std::exception &) {
-        std::fprintf(stderr, usage, argv[0]);
-        return 2;
+    for (Args a(argc, argv, 3); a.more(); a.next()) {
+        if (a.value("--longer-than", longerThan) || a.value("--missing", maxMissing)) {}
+        else if (a.flag("--per-line")) perLine = true;
+        else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); std::fprintf(stderr, usage, argv[0]); return 2; }
     }
     try {
         genome::Context ctx(0);

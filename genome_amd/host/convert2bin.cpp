@@ -9,11 +9,7 @@
 //
 // Build: g++ -std=c++17 -O2 -I include genome_amd/host/convert2bin.cpp -L genome_amd -lgenome_amd -Wl,-rpath,'$ORIGIN/..'
 //        -o genome_amd/host/convert2bin
-#include <cstdio>
-#include <cstring>
-#include <string>
-
-#include "genome.hpp"
+#include "tool_common.hpp"
 
 int main(int argc, char **argv) {
     if (argc < 3) {
@@ -22,11 +18,10 @@ int main(int argc, char **argv) {
     }
     const std::string in = argv[1], out = std::string(argv[2]) + ".bin", tmp = out + ".tmp";
     int split = 36, k = 23;
-    for (int i = 3; i < argc; i++) {
-        if (!std::strcmp(argv[i], "--split") && i + 1 < argc) split = std::stoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--interleaved")) split = 0;
-        else if (!std::strcmp(argv[i], "--k") && i + 1 < argc) k = std::stoi(argv[++i]);
-        else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+    for (Args a(argc, argv, 3); a.more(); a.next()) {
+        if (a.value("--split", split) || a.value("--k", k)) {}
+        else if (a.flag("--interleaved")) split = 0;
+        else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
     if (split < 0 || k < 1 || k > 255) {
         std::fprintf(stderr, "--split N needs N >= 1 and --k K needs 1 <= K <= 255\n");

@@ -10,30 +10,17 @@
 //
 // Build: g++ -std=c++17 -O2 -I include genome_amd/host/correct_reads.cpp -L genome_amd -lgenome_amd
 //        -Wl,-rpath,'$ORIGIN/..' -o genome_amd/host/correct_reads
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <iterator>
-#include <string>
-#include <vector>
-
-#include "genome.hpp"
+#include "tool_common.hpp"
 
 int main(int argc, char **argv) {
     std::string out, spectrumPath;
     uint32_t solid = 0;                           // 0 = auto
     bool ok = argc >= 4;
-    for (int i = 4; ok && i < argc; i++) {
-        if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
-        else if (!std::strcmp(argv[i], "--spectrum") && i + 1 < argc) spectrumPath = argv[++i];
-        else if (!std::strcmp(argv[i], "--solid") && i + 1 < argc) {
-            if (!std::strcmp(argv[++i], "auto")) solid = 0;
-            else {
-                char *end = nullptr;
-                solid = (uint32_t)std::strtoul(argv[i], &end, 10);
-                ok = *end == 0 && solid >= 1;
-            }
-        } else ok = false;
+    for (Args a(argc, argv, 4); ok && a.more(); a.next()) {
+        if (a.value("--out", out) || a.value("--spectrum", spectrumPath)) {}
+        else if (a.word("--solid", 1, "auto")) { solid = 0; a.skip(); }
+        else if (a.value("--solid", solid)) ok = solid >= 1;
+        else ok = false;
     }
     if (!ok || out.empty()) {
         std::fprintf(stderr, "usage: %s <reads.bin> <nreads> <k> --out <corrected.bin> [--solid N|auto] [--spectrum PATH]\n", argv[0]);
@@ -43,9 +30,7 @@ int main(int argc, char **argv) {
         const std::string infile = argv[1];
         const uint64_t nreads = std::stoull(argv[2]);
         const int k = std::stoi(argv[3]);
-        std::ifstream f(infile, std::ios::binary);
-        if (!f) throw std::runtime_error("cannot open " + infile);
-        std::vector<uint8_t> bin((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        std::vector<uint8_t> bin = readBin(infile);
         genome::Context ctx(0);
         genome::DNAMap counts(ctx, k);
         const uint64_t occ = counts.countReads(bin.data(), bin.size(), nreads);
@@ -56,13 +41,7 @@ int main(int argc, char **argv) {
             const genome::SpectrumCutoff c = genome::spectrumCutoff(sp.hist);
             valley = c.valley; peak = c.peak;
             if (!solid) { solidAuto = valley != 0; solid = solidAuto ? valley : 3; }
-            if (!spectrumPath.empty()) {
-                std::ofstream sf(spectrumPath);
-                const auto &h = sp.hist;
-                for (size_t c2 = 1; c2 + 1 < h.size(); c2++) if (h[c2]) sf << c2 << "\t" << h[c2] << "\n";
-                if (h.back()) sf << ">=" << h.size() - 1 << "\t" << h.back() << "\n";
-                if (!sf) throw std::runtime_error("cannot write " + spectrumPath);
-            }
+            if (!spectrumPath.empty()) writeSpectrum(spectrumPath, sp.hist);
         }
         const auto st = counts.correctReads(bin.data(), bin.size(), nreads, solid, bin.data());
         std::ofstream of(out, std::ios::binary);

@@ -51,52 +51,14 @@
 //
 // Build: g++ -std=c++17 -O2 -I include genome_amd/host/graph_builder.cpp -L genome_amd -lgenome_amd
 //        -Wl,-rpath,'$ORIGIN/..' -o genome_amd/host/graph_builder
-#include <unistd.h>
-
-#include <chrono>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <iostream>
-#include <iterator>
-#include <memory>
-#include <string>
-#include <vector>
-#include <thread>
-
-#include "genome.hpp"
-#include "rank_id.hpp"
-
-// The --fastq forms: take the FASTQ path and the split options out of argv, and leave the `.bin` form's argv in `args`
-// (the reads file and pair count are filled in after the conversion).  at = argv index of "--fastq"; -> 0, or 2 for a usage error.
-static int fastqArgs(int argc, char **argv, int at, std::string *fastq, int *split, std::vector<char *> *args) {
-    static char empty[] = "", zero[] = "0";
-    if (at + 1 >= argc) return 2;
-    *fastq = argv[at + 1];
-    for (int i = 0; i < argc; i++) {
-        if (i == at) { args->push_back(empty); args->push_back(zero); i++; continue; }
-        if (!std::strcmp(argv[i], "--split") && i + 1 < argc) { *split = std::stoi(argv[++i]); if (*split < 1) return 2; continue; }
-        if (!std::strcmp(argv[i], "--interleaved")) { *split = 0; continue; }
-        if (!std::strcmp(argv[i], "--world")) return 2;      // N-rank ingestion of FASTQ is not supported: convert first
-        args->push_back(argv[i]);
-    }
-    args->push_back(nullptr);
-    return 0;
-}
+#include "tool_common.hpp"
 
 int main(int argc, char **argv) {
-    std::string fastq;
-    int split = 36;
-    std::vector<char *> fargs;
-    const int fastq_at = argc >= 2 && !std::strcmp(argv[1], "--fastq") ? 1 : 0;
-    if (fastq_at) {
-        if (fastqArgs(argc, argv, fastq_at, &fastq, &split, &fargs)) {
-            std::fprintf(stderr, "usage: %s --fastq <reads.fastq> <k> [--split N | --interleaved] [options of the .bin form]\n"
-                                 "       (--fastq takes --split N or --interleaved; it does not run with --world: convert2bin first)\n", argv[0]);
-            return 2;
-        }
-        argc = (int)fargs.size() - 1;
-        argv = fargs.data();
+    FastqForm fastq;
+    if (!fastq.parse(argc, argv, 1)) {
+        std::fprintf(stderr, "usage: %s --fastq <reads.fastq> <k> [--split N | --interleaved] [options of the .bin form]\n"
+                             "       (--fastq takes --split N or --interleaved; it does not run with --world: convert2bin first)\n", argv[0]);
+        return 2;
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
@@ -106,8 +68,9 @@ int main(int argc, char **argv) {
     }
     const std::string infile = argv[1];
     genome::PairedEndData data;
-    data.count = std::stoull(argv[2]);
-    const int k = std::stoi(argv[3]);
+    int k = 0;
+    Args::convert("<pairs>", argv[2], data.count);
+    Args::convert("<k>", argv[3], k);
     int rounds = 3;                               // GraphBuilder.scala:30
     bool autoRounds = false;                      // --rounds auto
     uint64_t takeFirst = UINT64_MAX;              // genome.takeFirst
@@ -120,73 +83,37 @@ int main(int argc, char **argv) {
     uint64_t bubbleMaxLen = 0;                    // 0 = auto: 2k
     bool correct = false;                         // --correct
     uint32_t solid = 0;                           // 0 = auto: the valley of the first count's spectrum
-    int walkCutoff = -1, walkLo = 180, walkHi = 250;
-    bool walkAuto = false;                                   // --walk-pairs CUTOFF auto: the range is measured from the pairs (graph_simplifier --range auto)
-    long maxInsert = 4095;
-    std::string out, idFile, saveGraph, spectrumPath, contigsPath;
-    uint64_t contigMinLen = 0;
-    uint32_t contigWidth = 60;
-    bool contigBoth = false;
-    int world = 0, rank = 0;                      // world 0: one GPU, no communicator
-    for (int i = 4; i < argc; i++) {
-        if (!std::strcmp(argv[i], "--rounds") && i + 1 < argc) {
-            if (!std::strcmp(argv[++i], "auto")) autoRounds = true;   // chosen from the spectrum
-            else { autoRounds = false; rounds = std::stoi(argv[i]); }
-        }
-        else if (!std::strcmp(argv[i], "--spectrum") && i + 1 < argc) spectrumPath = argv[++i];
-        else if (!std::strcmp(argv[i], "--take-first") && i + 1 < argc) takeFirst = std::stoull(argv[++i]);
-        else if (!std::strcmp(argv[i], "--prefilter") && i + 1 < argc) prefilter = std::stoull(argv[++i]);
-        else if (!std::strcmp(argv[i], "--no-retain")) retain = false;
-        else if (!std::strcmp(argv[i], "--simplify")) simplify = true;
-        else if (!std::strcmp(argv[i], "--clip-tips")) {
-            clipTips = true;
-            if (i + 1 < argc && !std::strcmp(argv[i + 1], "auto")) i++;
-            else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') tipMaxLen = std::stoull(argv[++i]);
-        }
-        else if (!std::strcmp(argv[i], "--pop-bubbles")) {
-            popBubbles = true;
-            if (i + 1 < argc && !std::strcmp(argv[i + 1], "auto")) i++;
-            else if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') bubbleMaxDiff = (uint32_t)std::stoul(argv[++i]);
-        }
-        else if (!std::strcmp(argv[i], "--bubble-max-len") && i + 1 < argc) bubbleMaxLen = std::stoull(argv[++i]);
-        else if (!std::strcmp(argv[i], "--edge-coverage")) edgeCoverage = true;
-        else if (!std::strcmp(argv[i], "--correct") && i + 1 < argc) {
+    PairedOpts walk;                              // --walk-pairs: cutoff < 0 = no such stage; rangeAuto = --walk-pairs CUTOFF auto
+    std::string out, saveGraph, spectrumPath;
+    ContigOpts contig;
+    RankOpts ranks;
+    for (Args a(argc, argv, 4); a.more(); a.next()) {
+        if (a.word("--rounds", 1, "auto")) { autoRounds = true; a.skip(); }   // chosen from the spectrum
+        else if (a.value("--rounds", rounds)) autoRounds = false;
+        else if (a.value("--spectrum", spectrumPath) || a.value("--take-first", takeFirst) || a.value("--prefilter", prefilter)) {}
+        else if (a.flag("--no-retain")) retain = false;
+        else if (a.flag("--simplify")) simplify = true;
+        else if (a.optional("--clip-tips", tipMaxLen)) clipTips = true;
+        else if (a.optional("--pop-bubbles", bubbleMaxDiff)) popBubbles = true;
+        else if (a.value("--bubble-max-len", bubbleMaxLen)) {}
+        else if (a.flag("--edge-coverage")) edgeCoverage = true;
+        else if (a.word("--correct", 1, "auto")) { correct = true; solid = 0; a.skip(); }
+        else if (a.value("--correct", solid)) {
             correct = true;
-            if (!std::strcmp(argv[++i], "auto")) solid = 0;
-            else if ((solid = (uint32_t)std::stoul(argv[i])) == 0) { std::fprintf(stderr, "--correct N needs N >= 1 (or auto)\n"); return 2; }
+            if (!solid) { std::fprintf(stderr, "--correct N needs N >= 1 (or auto)\n"); return 2; }
         }
-        else if (!std::strcmp(argv[i], "--walk-pairs") && i + 2 < argc && !std::strcmp(argv[i + 2], "auto")) { walkCutoff = std::stoi(argv[++i]); walkAuto = true; i++; }
-        else if (!std::strcmp(argv[i], "--max-insert") && i + 1 < argc) { maxInsert = std::stol(argv[++i]); if (maxInsert < 1 || maxInsert > 65535) { std::fprintf(stderr, "--max-insert N is 1..65535\n"); return 2; } }
-        else if (!std::strcmp(argv[i], "--walk-pairs") && i + 3 < argc) { walkCutoff = std::stoi(argv[++i]); walkLo = std::stoi(argv[++i]); walkHi = std::stoi(argv[++i]); }
-        else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
-        else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
-        else if (!std::strcmp(argv[i], "--contigs") && i + 1 < argc) contigsPath = argv[++i];
-        else if (!std::strcmp(argv[i], "--contig-min-len") && i + 1 < argc) contigMinLen = std::stoull(argv[++i]);
-        else if (!std::strcmp(argv[i], "--contig-width") && i + 1 < argc) contigWidth = (uint32_t)std::stoul(argv[++i]);
-        else if (!std::strcmp(argv[i], "--contig-both-strands")) contigBoth = true;
-        else if (!std::strcmp(argv[i], "--world") && i + 1 < argc) world = std::stoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) rank = std::stoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--id-file") && i + 1 < argc) idFile = argv[++i];
-        else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+        else if (a.word("--walk-pairs", 2, "auto")) { a.value("--walk-pairs", walk.cutoff); walk.rangeAuto = true; a.skip(); }
+        else if (a.value("--max-insert", walk.maxInsert)) { if (!walk.maxInsertOk()) { std::fprintf(stderr, "--max-insert N is 1..65535\n"); return 2; } }
+        else if (a.value("--walk-pairs", walk.cutoff, walk.lo, walk.hi)) {}
+        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || ranks.parse(a)) {}
+        else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
-    if (world && (world < 1 || rank < 0 || rank >= world || idFile.empty())) {
-        std::fprintf(stderr, "--world W needs --rank R (0 <= R < W) and --id-file PATH\n");
-        return 2;
-    }
-    if (world && prefilter) {
-        std::fprintf(stderr, "--prefilter runs on one GPU only (not with --world)\n");
-        return 2;
-    }
-    if (world && (clipTips || edgeCoverage)) {
-        std::fprintf(stderr, "--clip-tips and --edge-coverage run on one GPU only (not with --world)\n");
-        return 2;
-    }
-    if (world && correct) {
-        std::fprintf(stderr, "--correct runs on one GPU only (not with --world)\n");
-        return 2;
-    }
-    if (world && popBubbles) {
-        std::fprintf(stderr, "--pop-bubbles runs on one GPU only (not with --world)\n");
+    if (!ranks.check()) return 2;
+    const int world = ranks.world, rank = ranks.rank;
+    const char *oneGpu = prefilter ? "--prefilter runs" : clipTips || edgeCoverage ? "--clip-tips and --edge-coverage run" :
+                         correct ? "--correct runs" : popBubbles ? "--pop-bubbles runs" : nullptr;
+    if (world && oneGpu) {
+        std::fprintf(stderr, "%s on one GPU only (not with --world)\n", oneGpu);
         return 2;
     }
     if (popBubbles && bubbleMaxDiff > 31) {
@@ -196,19 +123,9 @@ int main(int argc, char **argv) {
     if (clipTips && !tipMaxLen) tipMaxLen = 2 * (uint64_t)k;
     if (popBubbles && !bubbleMaxLen) bubbleMaxLen = 2 * (uint64_t)k;
     try {
-        if (fastq.empty()) {
-            std::ifstream f(infile, std::ios::binary);
-            if (!f) throw std::runtime_error("cannot open " + infile);
-            data.bin.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-        }
-        int device = 0;
-        if (world) {
-            const int ndev = gk_device_count();
-            if (ndev < 1) throw genome::GkError(GK_E_NODEVICE, "no GPU");
-            device = rank % ndev;
-        }
-        genome::Context ctx(device);
-        if (!fastq.empty()) data = genome::PairedEndData::fromFastq(ctx, fastq, split);     // the pair count comes from the conversion
+        if (fastq.path.empty()) data.bin = readBin(infile);
+        genome::Context ctx(ranks.device());
+        if (!fastq.path.empty()) data = genome::PairedEndData::fromFastq(ctx, fastq.path, fastq.split);     // the pair count comes from the conversion
         // --correct: a count of the reads as they are, the stream corrected against it in place, and the flow below starts over
         genome::DNAMap::CorrectStats corrected;
         bool solidAuto = false;
@@ -232,7 +149,7 @@ int main(int argc, char **argv) {
         chosen.wantSpectrum = !spectrumPath.empty();
         const bool withSpectrum = chosen.autoRounds || chosen.wantSpectrum;
         if (world) {
-            pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, idFile));
+            pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, ranks.idFile));
             std::tie(sent, owned) = genome::FreqFilter::extractFilteredKmers(*pm, data, rounds, takeFirst, &chosen);  // :32 over N ranks
             good = pm->size();                                                                                          // :34
             kmersFreq = std::make_unique<genome::DNAMap>(pm->gathered(true));
@@ -241,13 +158,7 @@ int main(int argc, char **argv) {
             good = kmersFreq->size();                                                                                  // :34
         }
         if (withSpectrum) rounds = chosen.rounds;
-        if (rank == 0 && !spectrumPath.empty()) {
-            std::ofstream sf(spectrumPath);
-            const auto &h = chosen.spectrum.hist;
-            for (size_t c = 1; c + 1 < h.size(); c++) if (h[c]) sf << c << "\t" << h[c] << "\n";
-            if (h.back()) sf << ">=" << h.size() - 1 << "\t" << h.back() << "\n";
-            if (!sf) throw std::runtime_error("cannot write " + spectrumPath);
-        }
+        if (rank == 0 && !spectrumPath.empty()) writeSpectrum(spectrumPath, chosen.spectrum.hist);
         auto graph = genome::Graph::buildGraph(k, *kmersFreq);                                           // :36
         auto [nodes, edges, totalLen] = graph.counts();                                                  // :39
         // :41-47 the two component histograms, on the graph as built (the reference computes them before retain)
@@ -270,98 +181,38 @@ int main(int argc, char **argv) {
         }
         // --simplify = GraphSimplifier.scala:317-318, applied to the graph GraphBuilder hands over (i.e. after retain)
         if (simplify) { graph.removeBubbles(); graph.simplifyGraph(); }
-        uint64_t supPairs = 0, badPairs = 0, walked = 0, removedEdges = 0, newNodes = 0;
-        genome::InsertRange insertEst;
-        if (walkCutoff >= 0) {
-            auto graphMap = graph.getGraphMap();                                                         // GraphSimplifier.scala:188
-            if (walkAuto) {                                                                              // the same pairs, before walking; over the ranks one histogram
-                genome::Graph::PairDistances dist;
-                if (world) {
-                    const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
-                    dist = graph.pairDistances(*pm, graphMap, data, a, b, (uint32_t)maxInsert + 1);
-                } else {
-                    dist = graph.pairDistances(graphMap, data, takeFirst, (uint32_t)maxInsert + 1);
-                }
-                insertEst = genome::insertRange(dist.hist);
-                walkLo = (int)insertEst.lo; walkHi = (int)insertEst.hi;
-                if (rank == 0 && insertEst.estimated)
-                    std::fprintf(stderr, "insert range %u to %u, median %u, from %llu observations\n", insertEst.lo, insertEst.hi, insertEst.median, (unsigned long long)insertEst.observations);
-                else if (rank == 0)
-                    std::fprintf(stderr, "no estimate of the insert range (%llu observations): falling back to the reference's %u to %u\n",
-                                 (unsigned long long)insertEst.observations, insertEst.lo, insertEst.hi);
-            }
-            genome::Support support(ctx);
-            if (world) {                                                                                 // this rank's pairs, then the sum over the ranks
-                const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
-                graph.walkPairs(graphMap, support, data, a, b, walkLo, walkHi);
-                pm->reduceSupport(graph, support);                                                       // (before any node split)
-            } else {
-                graph.walkPairs(graphMap, support, data, takeFirst, walkLo, walkHi);                     // :213-263
-            }
-            std::tie(supPairs, badPairs, walked) = support.sizes();                                      // :266 "Bad pairs"
-            std::tie(removedEdges, newNodes) = graph.splitBySupport(support, walkCutoff);                // :272-316
-            graph.simplifyGraph();                                                                       // :318
-        }
+        PairedResult walked;
+        if (walk.cutoff >= 0) walked = pairedStage(graph, ctx, pm.get(), data, takeFirst, rank, world, walk);
         auto [n2, e2, l2] = graph.counts();
         if (pm) pm->barrier();
         if (rank != 0) return 0;
         // --contigs: the text is written after the last graph stage, with the coverage of the table the graph was built from
         genome::Contigs::Stats fasta;
-        if (!contigsPath.empty()) {
-            auto contigs = graph.contigs(kmersFreq.get(), contigMinLen, contigWidth, contigBoth);
-            contigs.write(contigsPath);
+        if (!contig.path.empty()) {
+            auto contigs = graph.contigs(kmersFreq.get(), contig.minLen, contig.width, contig.both);
+            contigs.write(contig.path);
             fasta = contigs.stats();
         }
-        std::printf("{\"k\":%d,\"rounds\":%d,\"good_kmers\":%llu,\"graph_nodes\":%llu,\"graph_edges\":%llu,"
-                    "\"total_edges_length\":%llu,\"components\":%llu,\"max_component_size\":%llu,"
-                    "\"retained_nodes\":%llu,\"retained_edges\":%llu,\"retained_edges_length\":%llu,",
-                    k, rounds, (unsigned long long)good, (unsigned long long)nodes, (unsigned long long)edges,
-                    (unsigned long long)totalLen, (unsigned long long)comps, (unsigned long long)kept,
-                    (unsigned long long)n2, (unsigned long long)e2, (unsigned long long)l2);
+        std::string js = "{";
+        jsonPut(js, "k", k, "rounds", rounds, "good_kmers", good, "graph_nodes", nodes, "graph_edges", edges, "total_edges_length", totalLen,
+                "components", comps, "max_component_size", kept, "retained_nodes", n2, "retained_edges", e2, "retained_edges_length", l2);
         if (withSpectrum)
-            std::printf("\"rounds_auto\":%s,\"valley\":%u,\"peak\":%u,\"genome_size_estimate\":%llu,", chosen.autoFound ? "true" : "false",
-                        chosen.cutoff.valley, chosen.cutoff.peak, (unsigned long long)chosen.cutoff.genomeSize);
-        if (correct) {
-            std::string st = corrected.json();
-            std::printf("\"correct\":{\"solid\":%u,\"solid_auto\":%s,%s,", solid, solidAuto ? "true" : "false", st.c_str() + 1);
-        }
-        if (clipTips) {
-            std::printf("\"clip_tips\":{\"max_len\":%llu,\"removed\":[", (unsigned long long)tipMaxLen);
-            for (size_t i = 0; i < tipsRemoved.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)tipsRemoved[i]);
-            std::printf("]},");
-        }
-        if (popBubbles) {
-            std::printf("\"pop_bubbles\":{\"max_len\":%llu,\"max_diff\":%u,\"removed\":[", (unsigned long long)bubbleMaxLen, bubbleMaxDiff);
-            for (size_t i = 0; i < bubblesRemoved.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)bubblesRemoved[i]);
-            std::printf("],\"pairs\":[");
-            for (size_t i = 0; i < bubblePairs.size(); i++) std::printf("%s%llu", i ? "," : "", (unsigned long long)bubblePairs[i]);
-            std::printf("]},");
-        }
-        if (walkCutoff >= 0 && walkAuto)
-            std::printf("\"insert_range\":{\"lo\":%u,\"hi\":%u,\"estimated\":%s,\"observations\":%llu},", insertEst.lo, insertEst.hi, insertEst.estimated ? "true" : "false",
-                        (unsigned long long)insertEst.observations);
-        if (walkCutoff >= 0)
-            std::printf("\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},",
-                        (unsigned long long)supPairs, (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges,
-                        (unsigned long long)newNodes);
-        if (!contigsPath.empty()) std::printf("\"contigs_fasta\":%s,", fasta.json().c_str());
-        auto dump = [](const char *name, const std::map<uint64_t, uint64_t> &h, const char *tail) {
-            std::printf("\"%s\":[", name);
-            bool first = true;
-            for (const auto &p : h) { std::printf("%s[%llu,%llu]", first ? "" : ",", (unsigned long long)p.first, (unsigned long long)p.second); first = false; }
-            std::printf("]%s", tail);
-        };
-        dump("components_histogram", hist, ",");          // GraphBuilder.scala:42 "Components histogram"
-        dump("components_histogram_2", hist2, world ? "," : "}\n");     // :47 "Components histogram 2"
-        if (world) std::printf("\"occurrences_sent\":%llu,\"occurrences_owned\":%llu,\"world\":%d}\n", (unsigned long long)sent, (unsigned long long)owned, world);
+            jsonPut(js, "rounds_auto", chosen.autoFound, "valley", chosen.cutoff.valley, "peak", chosen.cutoff.peak, "genome_size_estimate", chosen.cutoff.genomeSize);
+        if (correct) jsonPut(js, "correct", "{\"solid\":" + std::to_string(solid) + ",\"solid_auto\":" + (solidAuto ? "true," : "false,") + corrected.json().substr(1));
+        if (clipTips) jsonPut(js, "clip_tips", jsonObject("max_len", tipMaxLen, "removed", jsonList(tipsRemoved)));
+        if (popBubbles)
+            jsonPut(js, "pop_bubbles", jsonObject("max_len", bubbleMaxLen, "max_diff", bubbleMaxDiff, "removed", jsonList(bubblesRemoved), "pairs", jsonList(bubblePairs)));
+        if (walk.cutoff >= 0 && walk.rangeAuto)
+            jsonPut(js, "insert_range", jsonObject("lo", walked.range.lo, "hi", walked.range.hi, "estimated", walked.range.estimated,
+                                                   "observations", walked.range.observations));
+        if (walk.cutoff >= 0) jsonPut(js, "walk_pairs", walked.walkJson());
+        if (!contig.path.empty()) jsonPut(js, "contigs_fasta", fasta.json());
+        jsonPut(js, "components_histogram", jsonPairs(hist), "components_histogram_2", jsonPairs(hist2));   // GraphBuilder.scala:42, :47
+        if (world) jsonPut(js, "occurrences_sent", sent, "occurrences_owned", owned, "world", world);
+        std::printf("%s}\n", js.c_str());
         if (!saveGraph.empty()) graph.save(saveGraph);                                                   // :55-56 (a Kryo file there)
         if (!out.empty()) {
-            std::ofstream nf(out + ".nodes.txt"), ef(out + ".edges.txt");
-            for (const auto &n : graph.getNodes()) nf << n.toString() << "\n";
-            for (const auto &e : graph.getEdges()) ef << e.start.toString() << " " << e.end.toString() << " " << e.seq << "\n";
-            std::ofstream cf(out + ".contigs"), df(out + ".dot");
-            graph.writeContigs(cf);
-            graph.writeDot(df);
+            writeGraphText(graph, out);
             if (edgeCoverage) {
                 std::ofstream vf(out + ".coverage.txt");
                 const auto c = graph.edgeCoverage(*kmersFreq);

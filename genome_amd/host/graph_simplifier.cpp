@@ -33,48 +33,14 @@
 //
 // Build: g++ -std=c++17 -O2 -I include genome_amd/host/graph_simplifier.cpp -L genome_amd -lgenome_amd
 //        -Wl,-rpath,'$ORIGIN/..' -o genome_amd/host/graph_simplifier
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <iostream>
-#include <iterator>
-#include <memory>
-#include <string>
-#include <vector>
-
-#include "genome.hpp"
-#include "rank_id.hpp"
-
-// The --fastq forms: take the FASTQ path and the split options out of argv, and leave the `.bin` form's argv in `args`
-// (the reads file and pair count are filled in after the conversion).  at = argv index of "--fastq"; -> 0, or 2 for a usage error.
-static int fastqArgs(int argc, char **argv, int at, std::string *fastq, int *split, std::vector<char *> *args) {
-    static char empty[] = "", zero[] = "0";
-    if (at + 1 >= argc) return 2;
-    *fastq = argv[at + 1];
-    for (int i = 0; i < argc; i++) {
-        if (i == at) { args->push_back(empty); args->push_back(zero); i++; continue; }
-        if (!std::strcmp(argv[i], "--split") && i + 1 < argc) { *split = std::stoi(argv[++i]); if (*split < 1) return 2; continue; }
-        if (!std::strcmp(argv[i], "--interleaved")) { *split = 0; continue; }
-        if (!std::strcmp(argv[i], "--world")) return 2;      // N-rank ingestion of FASTQ is not supported: convert first
-        args->push_back(argv[i]);
-    }
-    args->push_back(nullptr);
-    return 0;
-}
+#include "tool_common.hpp"
 
 int main(int argc, char **argv) {
-    std::string fastq;
-    int split = 36;
-    std::vector<char *> fargs;
-    const int fastq_at = argc >= 3 && !std::strcmp(argv[2], "--fastq") ? 2 : 0;
-    if (fastq_at) {
-        if (fastqArgs(argc, argv, fastq_at, &fastq, &split, &fargs)) {
-            std::fprintf(stderr, "usage: %s <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [options of the .bin form]\n"
-                                 "       (--fastq takes --split N or --interleaved; it does not run with --world: convert2bin first)\n", argv[0]);
-            return 2;
-        }
-        argc = (int)fargs.size() - 1;
-        argv = fargs.data();
+    FastqForm fastq;
+    if (!fastq.parse(argc, argv, 2)) {
+        std::fprintf(stderr, "usage: %s <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [options of the .bin form]\n"
+                             "       (--fastq takes --split N or --interleaved; it does not run with --world: convert2bin first)\n", argv[0]);
+        return 2;
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
@@ -84,158 +50,76 @@ int main(int argc, char **argv) {
     }
     const std::string graphFile = argv[1], infile = argv[2];
     genome::PairedEndData data;
-    data.count = std::stoull(argv[3]);
-    int cutoff = -1, rangeLo = 180, rangeHi = 250;          // GraphSimplifier.scala:146
+    Args::convert("<pairs>", argv[3], data.count);
+    PairedOpts stage;                             // --cutoff, --range, --max-insert, --thread-reads, --no-pairs
     uint64_t takeFirst = UINT64_MAX;
-    std::string out, saveGraph, idFile, insertHist, contigsPath;
-    uint64_t contigMinLen = 0;
-    uint32_t contigWidth = 60;
-    bool contigBoth = false;
-    int world = 0, rank = 0;
-    bool rangeAuto = false, threadReads = false, noPairs = false;
-    long maxInsert = 4095;
-    for (int i = 4; i < argc; i++) {
-        if (!std::strcmp(argv[i], "--cutoff") && i + 1 < argc) cutoff = std::stoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--range") && i + 1 < argc && !std::strcmp(argv[i + 1], "auto")) { rangeAuto = true; i++; }
-        else if (!std::strcmp(argv[i], "--max-insert") && i + 1 < argc) maxInsert = std::stol(argv[++i]);
-        else if (!std::strcmp(argv[i], "--insert-hist") && i + 1 < argc) insertHist = argv[++i];
-        else if (!std::strcmp(argv[i], "--range") && i + 2 < argc) { rangeLo = std::stoi(argv[++i]); rangeHi = std::stoi(argv[++i]); }
-        else if (!std::strcmp(argv[i], "--take-first") && i + 1 < argc) takeFirst = std::stoull(argv[++i]);
-        else if (!std::strcmp(argv[i], "--thread-reads")) threadReads = true;
-        else if (!std::strcmp(argv[i], "--no-pairs")) noPairs = true;
-        else if (!std::strcmp(argv[i], "--out") && i + 1 < argc) out = argv[++i];
-        else if (!std::strcmp(argv[i], "--save-graph") && i + 1 < argc) saveGraph = argv[++i];
-        else if (!std::strcmp(argv[i], "--contigs") && i + 1 < argc) contigsPath = argv[++i];
-        else if (!std::strcmp(argv[i], "--contig-min-len") && i + 1 < argc) contigMinLen = std::stoull(argv[++i]);
-        else if (!std::strcmp(argv[i], "--contig-width") && i + 1 < argc) contigWidth = (uint32_t)std::stoul(argv[++i]);
-        else if (!std::strcmp(argv[i], "--contig-both-strands")) contigBoth = true;
-        else if (!std::strcmp(argv[i], "--world") && i + 1 < argc) world = std::stoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--rank") && i + 1 < argc) rank = std::stoi(argv[++i]);
-        else if (!std::strcmp(argv[i], "--id-file") && i + 1 < argc) idFile = argv[++i];
-        else { std::fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+    std::string out, saveGraph, insertHist;
+    ContigOpts contig;
+    RankOpts ranks;
+    for (Args a(argc, argv, 4); a.more(); a.next()) {
+        if (a.value("--cutoff", stage.cutoff)) {}
+        else if (a.word("--range", 1, "auto")) { stage.rangeAuto = true; a.skip(); }
+        else if (a.value("--max-insert", stage.maxInsert) || a.value("--insert-hist", insertHist)) {}
+        else if (a.value("--range", stage.lo, stage.hi) || a.value("--take-first", takeFirst)) {}
+        else if (a.flag("--thread-reads")) stage.threadReads = true;
+        else if (a.flag("--no-pairs")) stage.walk = false;
+        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || ranks.parse(a)) {}
+        else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
-    if (cutoff < 0) {
+    if (stage.cutoff < 0) {
         std::fprintf(stderr, "--cutoff C is required\n");
         return 2;
     }
-    if (maxInsert < 1 || maxInsert > 65535 || (!rangeAuto && !insertHist.empty())) {
+    if (!stage.maxInsertOk() || (!stage.rangeAuto && !insertHist.empty())) {
         std::fprintf(stderr, "--max-insert N is 1..65535; --insert-hist PATH goes with --range auto\n");
         return 2;
     }
-    if (noPairs && (!threadReads || rangeAuto)) {
+    if (!stage.walk && (!stage.threadReads || stage.rangeAuto)) {
         std::fprintf(stderr, "--no-pairs goes with --thread-reads, and not with --range auto (no walk uses the range)\n");
         return 2;
     }
-    if (world && (world < 1 || rank < 0 || rank >= world || idFile.empty())) {
-        std::fprintf(stderr, "--world W needs --rank R (0 <= R < W) and --id-file PATH\n");
-        return 2;
-    }
+    if (!ranks.check()) return 2;
+    const int world = ranks.world, rank = ranks.rank;
     try {
-        if (fastq.empty()) {
-            std::ifstream f(infile, std::ios::binary);
-            if (!f) throw std::runtime_error("cannot open " + infile);
-            data.bin.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-        }
-        int device = 0;
-        if (world) {
-            const int ndev = gk_device_count();
-            if (ndev < 1) throw genome::GkError(GK_E_NODEVICE, "no GPU");
-            device = rank % ndev;
-        }
-        genome::Context ctx(device);
-        if (!fastq.empty()) data = genome::PairedEndData::fromFastq(ctx, fastq, split);     // the pair count comes from the conversion
+        if (fastq.path.empty()) data.bin = readBin(infile);
+        genome::Context ctx(ranks.device());
+        if (!fastq.path.empty()) data = genome::PairedEndData::fromFastq(ctx, fastq.path, fastq.split);     // the pair count comes from the conversion
         auto graph = genome::Graph::load(ctx, graphFile);                                                // :152-153, :157-169
         const int k = graph.k();
         std::unique_ptr<genome::PartitionedDNAMap> pm;
-        if (world) pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, idFile));
+        if (world) pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, ranks.idFile));
         auto [n1, e1, l1] = graph.counts();
-        auto graphMap = graph.getGraphMap();                                                             // :188
-        genome::Graph::PairDistances dist;
-        genome::InsertRange est;
-        if (rangeAuto) {                                                                                 // the same pairs, before walking
-            if (world) {
-                const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
-                dist = graph.pairDistances(*pm, graphMap, data, a, b, (uint32_t)maxInsert + 1);
-            } else {
-                dist = graph.pairDistances(graphMap, data, takeFirst, (uint32_t)maxInsert + 1);
-            }
-            est = genome::insertRange(dist.hist);
-            rangeLo = (int)est.lo; rangeHi = (int)est.hi;
-            if (rank == 0) {
-                if (est.estimated) std::fprintf(stderr, "insert range %u to %u, median %u, from %llu observations\n", est.lo, est.hi, est.median, (unsigned long long)est.observations);
-                else std::fprintf(stderr, "no estimate of the insert range (%llu observations): falling back to the reference's %u to %u\n",
-                                  (unsigned long long)est.observations, est.lo, est.hi);
-            }
-            if (rank == 0 && !insertHist.empty()) {
-                std::ofstream hf(insertHist);
-                for (size_t d = 0; d < dist.hist.size(); d++) if (dist.hist[d]) hf << d << " " << dist.hist[d] << "\n";
-                if (!hf) throw std::runtime_error("cannot write " + insertHist);
-            }
-        }
-        genome::Support support(ctx);
-        genome::Graph::ThreadStats threaded;
-        if (world) {                                                                                     // this rank's pairs, then the sum over the ranks
-            const auto [a, b] = genome::pairShare(data.count, takeFirst, rank, world);
-            if (!noPairs) graph.walkPairs(graphMap, support, data, a, b, rangeLo, rangeHi);
-            if (threadReads) {
-                threaded = graph.threadReads(graphMap, support, data, a, b);
-                double v[7];
-                for (int i = 0; i < 7; i++) v[i] = (double)threaded.v[i];
-                genome::check(gk_dist_allreduce_f64(pm->distHandle(), v, 7, 0), ctx.handle());
-                for (int i = 0; i < 7; i++) threaded.v[i] = (uint64_t)v[i];
-            }
-            pm->reduceSupport(graph, support);                                                           // (before any node split)
-        } else {
-            if (!noPairs) graph.walkPairs(graphMap, support, data, takeFirst, rangeLo, rangeHi);         // :213-263
-            if (threadReads) threaded = graph.threadReads(graphMap, support, data, takeFirst);
-        }
-        auto [supPairs, badPairs, walked] = support.sizes();                                             // :266 "Bad pairs"
-        auto [removedEdges, newNodes] = graph.splitBySupport(support, cutoff);                           // :272-316
-        graph.simplifyGraph();                                                                           // :318
+        const PairedResult res = pairedStage(graph, ctx, pm.get(), data, takeFirst, rank, world, stage);
         auto [n2, e2, l2] = graph.counts();
         auto [hist, hist2] = graph.componentHistograms();                                                // :320-331
         if (pm) pm->barrier();
         if (rank != 0) return 0;
-        std::string autoJson;
-        if (rangeAuto) {
-            autoJson = "\"insert_range\":{\"lo\":" + std::to_string(est.lo) + ",\"hi\":" + std::to_string(est.hi) + ",\"median\":" +
-                       (est.estimated ? std::to_string(est.median) : std::string("null")) + ",\"estimated\":" + (est.estimated ? "true" : "false") +
-                       ",\"observations\":" + std::to_string(est.observations) + ",\"max_insert\":" + std::to_string(maxInsert) + ",\"classes\":{";
-            for (int c = 0; c < 9; c++)
-                autoJson += std::string(c ? "," : "") + "\"" + genome::Graph::pairClassNames[c] + "\":" + std::to_string(dist.classes[c]);
-            autoJson += "}},";
+        std::string js = "{";
+        jsonPut(js, "k", k, "nodes", n1, "edges", e1, "edges_length", l1, "walk_pairs", res.walkJson());
+        if (stage.rangeAuto) {
+            if (!insertHist.empty()) {
+                std::ofstream hf(insertHist);
+                for (size_t d = 0; d < res.dist.hist.size(); d++) if (res.dist.hist[d]) hf << d << " " << res.dist.hist[d] << "\n";
+                if (!hf) throw std::runtime_error("cannot write " + insertHist);
+            }
+            const genome::InsertRange &est = res.range;
+            jsonPut(js, "insert_range", jsonObject("lo", est.lo, "hi", est.hi, "median", est.estimated ? std::to_string(est.median) : "null",
+                                                   "estimated", est.estimated, "observations", est.observations, "max_insert", stage.maxInsert,
+                                                   "classes", "{" + jsonNamed(genome::Graph::pairClassNames, res.dist.classes, 9) + "}"));
         }
         // --contigs: the text of the final graph (this tool holds no count table: no cov= field)
-        if (!contigsPath.empty()) {
-            auto contigs = graph.contigs(nullptr, contigMinLen, contigWidth, contigBoth);
-            contigs.write(contigsPath);
-            autoJson += "\"contigs_fasta\":" + contigs.stats().json() + ",";
+        if (!contig.path.empty()) {
+            auto contigs = graph.contigs(nullptr, contig.minLen, contig.width, contig.both);
+            contigs.write(contig.path);
+            jsonPut(js, "contigs_fasta", contigs.stats().json());
         }
-        if (threadReads) {
-            autoJson += "\"thread_reads\":{";
-            for (int c = 0; c < 7; c++) autoJson += std::string(c ? "," : "") + "\"" + genome::Graph::threadStatNames[c] + "\":" + std::to_string(threaded.v[c]);
-            autoJson += "},";
-        }
-        std::printf("{\"k\":%d,\"nodes\":%llu,\"edges\":%llu,\"edges_length\":%llu,"
-                    "\"walk_pairs\":{\"supported_edge_pairs\":%llu,\"bad_pairs\":%llu,\"orientations_walked\":%llu,\"removed_edges\":%llu,\"new_nodes\":%llu},"
-                    "%s\"simplified_nodes\":%llu,\"simplified_edges\":%llu,\"simplified_edges_length\":%llu,\"components_histogram_2\":[",
-                    k, (unsigned long long)n1, (unsigned long long)e1, (unsigned long long)l1, (unsigned long long)supPairs,
-                    (unsigned long long)badPairs, (unsigned long long)walked, (unsigned long long)removedEdges, (unsigned long long)newNodes, autoJson.c_str(),
-                    (unsigned long long)n2, (unsigned long long)e2, (unsigned long long)l2);
-        bool first = true;
-        for (const auto &p : hist2) { std::printf("%s[%llu,%llu]", first ? "" : ",", (unsigned long long)p.first, (unsigned long long)p.second); first = false; }
-        std::printf("],\"max_component_size\":%llu", (unsigned long long)(hist.empty() ? 0 : hist.rbegin()->first));
-        if (world) std::printf(",\"world\":%d", world);
-        std::printf("}\n");
+        if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");
+        jsonPut(js, "simplified_nodes", n2, "simplified_edges", e2, "simplified_edges_length", l2, "components_histogram_2", jsonPairs(hist2),
+                "max_component_size", hist.empty() ? 0 : hist.rbegin()->first);
+        if (world) jsonPut(js, "world", world);
+        std::printf("%s}\n", js.c_str());
         if (!saveGraph.empty()) graph.save(saveGraph);                                                   // :352 graphFile
-        if (!out.empty()) {
-            std::ofstream nf(out + ".nodes.txt"), ef(out + ".edges.txt");
-            for (const auto &n : graph.getNodes()) nf << n.toString() << "\n";
-            for (const auto &e : graph.getEdges()) ef << e.start.toString() << " " << e.end.toString() << " " << e.seq << "\n";
-            std::ofstream cf(out + ".contigs"), df(out + ".dot");
-            graph.writeContigs(cf);                                                                      // :338-347
-            graph.writeDot(df);
-        }
+        if (!out.empty()) writeGraphText(graph, out);                                                    // :338-347
     } catch (const std::exception &e) {
         std::fprintf(stderr, "graph_simplifier: %s\n", e.what());
         return 1;

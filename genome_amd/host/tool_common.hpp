@@ -1,0 +1,244 @@
+// tool_common.hpp — what the command-line tools in this directory share: a cursor over argv, the option groups and input forms
+// that more than one tool takes, the paired-end stage of graph_builder --walk-pairs and graph_simplifier, and the writers of
+// their text files and JSON fragments.  One header, no library; genome.hpp stays the twin of the reference's API and knows no
+// command line.  (tests/host/tool_common_check.cpp runs the parts that need no device, links nothing, under sanitizers.)
+#pragma once
+
+#include <charconv>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iterator>
+#include <memory>
+#include <type_traits>
+
+#include "genome.hpp"
+#include "rank_id.hpp"
+
+// A cursor over argv: `for (Args a(argc, argv, first); a.more(); a.next())` with one `if (a.…) … else if (a.…) …` chain per
+// argument.  Every method answers for the argument under the cursor and consumes the values it takes.  An option whose values
+// are missing matches nothing, so it ends in the chain's `else` (unknown argument).
+struct Args {
+    int argc;
+    char **argv;
+    int i;
+    Args(int argc_, char **argv_, int first) : argc(argc_), argv(argv_), i(first) {}
+    bool more() const { return i < argc; }
+    void next() { i++; }
+    const char *cur() const { return argv[i]; }
+    bool flag(const char *name) const { return !std::strcmp(argv[i], name); }
+    // `name` with at least n more tokens behind it
+    bool has(const char *name, int n) const { return flag(name) && i + n < argc; }
+    // `name` whose at-th token behind it is the word w (--range auto: at 1; --walk-pairs CUTOFF auto: at 2); consumes nothing
+    bool word(const char *name, int at, const char *w) const { return has(name, at) && !std::strcmp(argv[i + at], w); }
+    void skip(int n = 1) { i += n; }
+    // --x V, --x LO HI, …: one target per value — std::string, or a signed or unsigned integer
+    template <class... T> bool value(const char *name, T &...out) {
+        if (!has(name, (int)sizeof...(T))) return false;
+        (convert(name, argv[++i], out), ...);
+        return true;
+    }
+    // --x [N|auto]: takes the next token if it is `auto` (out stays as it is) or starts with a digit
+    template <class T> bool optional(const char *name, T &out) {
+        if (!flag(name)) return false;
+        const char *n = i + 1 < argc ? argv[i + 1] : nullptr;
+        if (n && !std::strcmp(n, "auto")) i++;
+        else if (n && n[0] >= '0' && n[0] <= '9') convert(name, argv[++i], out);
+        return true;
+    }
+    // the one place numbers are read: the whole of s is a number that T holds, or false (out untouched)
+    template <class T> static bool number(const char *s, T &out) {
+        const char *end = s + std::strlen(s);
+        T v{};
+        const auto r = std::from_chars(s, end, v);
+        if (r.ec != std::errc() || r.ptr != end) return false;
+        out = v;
+        return true;
+    }
+    static void convert(const char *, const char *s, std::string &out) { out = s; }
+    // anything else is a usage error: one line that names the option (or the positional argument), exit 2
+    template <class T> static void convert(const char *name, const char *s, T &out) {
+        if (number(s, out)) return;
+        std::fprintf(stderr, "%s needs %s, not '%s'\n", name, std::is_signed<T>::value ? "an integer" : "a non-negative integer", s);
+        std::exit(2);
+    }
+};
+
+// The --fastq forms: where argv[at] is "--fastq", take the FASTQ path and the split options out of argv and put the `.bin`
+// form's argv in their place (the reads file and pair count are filled in after the conversion).  path stays empty otherwise.
+struct FastqForm {
+    std::string path;
+    int split = 36;                               // Convert2bin's n; 0 = interleaved
+    std::vector<char *> args;
+    // -> false for a usage error
+    bool parse(int &argc, char **&argv, int at) {
+        static char empty[] = "", zero[] = "0";
+        if (argc <= at || std::strcmp(argv[at], "--fastq")) return true;
+        if (at + 1 >= argc) return false;
+        path = argv[at + 1];
+        for (Args a(argc, argv, 0); a.more(); a.next()) {
+            if (a.i == at) { args.push_back(empty); args.push_back(zero); a.skip(); }
+            else if (a.value("--split", split)) { if (split < 1) return false; }
+            else if (a.flag("--interleaved")) split = 0;
+            else if (a.flag("--world")) return false;        // N-rank ingestion of FASTQ is not supported: convert first
+            else args.push_back(argv[a.i]);
+        }
+        args.push_back(nullptr);
+        argc = (int)args.size() - 1;
+        argv = args.data();
+        return true;
+    }
+};
+
+// --contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]
+struct ContigOpts {
+    std::string path;
+    uint64_t minLen = 0;
+    uint32_t width = 60;
+    bool both = false;
+    bool parse(Args &a) {
+        if (a.flag("--contig-both-strands")) { both = true; return true; }
+        return a.value("--contigs", path) || a.value("--contig-min-len", minLen) || a.value("--contig-width", width);
+    }
+};
+
+// --world W --rank R --id-file PATH; world 0: one GPU, no communicator
+struct RankOpts {
+    int world = 0, rank = 0;
+    std::string idFile;
+    bool parse(Args &a) { return a.value("--world", world) || a.value("--rank", rank) || a.value("--id-file", idFile); }
+    bool check() const {
+        if (!world || (world >= 1 && rank >= 0 && rank < world && !idFile.empty())) return true;
+        std::fprintf(stderr, "--world W needs --rank R (0 <= R < W) and --id-file PATH\n");
+        return false;
+    }
+    int device() const {
+        if (!world) return 0;
+        const int ndev = gk_device_count();
+        if (ndev < 1) throw genome::GkError(GK_E_NODEVICE, "no GPU");
+        return rank % ndev;
+    }
+};
+
+inline std::vector<uint8_t> readBin(const std::string &path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+
+// JSON fragments.  No nesting state and no escaping: the callers open and close their objects themselves.
+// [[a,b],…]
+inline std::string jsonPairs(const std::map<uint64_t, uint64_t> &h) {
+    std::string s = "[";
+    for (const auto &p : h) s += (s.size() > 1 ? ",[" : "[") + std::to_string(p.first) + "," + std::to_string(p.second) + "]";
+    return s + "]";
+}
+// [a,b,…]
+template <class T> inline std::string jsonList(const std::vector<T> &v) {
+    std::string s = "[";
+    for (const T &x : v) s += (s.size() > 1 ? "," : "") + std::to_string(x);
+    return s + "]";
+}
+// "a":1,"b":2 (no braces)
+template <class T> inline std::string jsonNamed(const char *const *names, const T *values, int n) {
+    std::string s;
+    for (int c = 0; c < n; c++) s += std::string(c ? ",\"" : "\"") + names[c] + "\":" + std::to_string(values[c]);
+    return s;
+}
+// appends "key":value for each (key, value) given, with a comma before it unless it opens an object.  A value is an integer of
+// any width (no cast at the call site), a bool, or text that is already rendered: null, an array, an object
+inline void jsonPut(std::string &) {}
+template <class V, class... Rest> inline void jsonPut(std::string &s, const char *key, const V &v, const Rest &...rest) {
+    if (!s.empty() && s.back() != '{') s += ',';
+    s += std::string("\"") + key + "\":";
+    if constexpr (std::is_same<V, bool>::value) s += v ? "true" : "false";
+    else if constexpr (std::is_integral<V>::value) s += std::to_string(v);
+    else s += v;
+    jsonPut(s, rest...);
+}
+// {"key":value,…}
+template <class... KV> inline std::string jsonObject(const KV &...kv) {
+    std::string s = "{";
+    jsonPut(s, kv...);
+    return s + "}";
+}
+
+// --spectrum PATH: one `count<TAB>keys` line per non-empty bin, the overflow bin as `>=N`
+inline void writeSpectrum(const std::string &path, const std::vector<uint64_t> &h) {
+    std::ofstream sf(path);
+    for (size_t c = 1; c + 1 < h.size(); c++) if (h[c]) sf << c << "\t" << h[c] << "\n";
+    if (h.back()) sf << ">=" << h.size() - 1 << "\t" << h.back() << "\n";
+    if (!sf) throw std::runtime_error("cannot write " + path);
+}
+
+// --out prefix: <prefix>.nodes.txt, .edges.txt, .contigs (GraphSimplifier.scala:338-347) and .dot (Graph.scala:74-88)
+inline void writeGraphText(genome::Graph &graph, const std::string &prefix) {
+    std::ofstream nf(prefix + ".nodes.txt"), ef(prefix + ".edges.txt");
+    for (const auto &n : graph.getNodes()) nf << n.toString() << "\n";
+    for (const auto &e : graph.getEdges()) ef << e.start.toString() << " " << e.end.toString() << " " << e.seq << "\n";
+    std::ofstream cf(prefix + ".contigs"), df(prefix + ".dot");
+    graph.writeContigs(cf);
+    graph.writeDot(df);
+}
+
+// GraphSimplifier.startup's paired-end stage (GraphSimplifier.scala:188-318) on a graph: position map, the pairs' walks, node
+// split by their support, simplifyGraph — and this project's additions to it: the measured insert range and the threaded reads.
+struct PairedOpts {
+    int cutoff = -1;                              // genome.cutoff
+    int lo = 180, hi = 250;                       // GraphSimplifier.scala:146
+    bool rangeAuto = false;                       // measure the range from the pairs instead
+    long maxInsert = 4095;
+    bool threadReads = false, walk = true;
+    bool maxInsertOk() const { return maxInsert >= 1 && maxInsert <= 65535; }
+};
+struct PairedResult {
+    genome::InsertRange range;                    // rangeAuto only
+    genome::Graph::PairDistances dist;            // rangeAuto only
+    uint64_t supPairs = 0, badPairs = 0, walked = 0, removedEdges = 0, newNodes = 0;
+    genome::Graph::ThreadStats threaded;          // summed over the ranks
+    // the "walk_pairs" object both tools print
+    std::string walkJson() const {
+        return jsonObject("supported_edge_pairs", supPairs, "bad_pairs", badPairs, "orientations_walked", walked, "removed_edges", removedEdges,
+                          "new_nodes", newNodes);
+    }
+};
+// pm = null and world = 0: one GPU, the first takeFirst pairs; else this rank's share of them, and the sums over the ranks
+inline PairedResult pairedStage(genome::Graph &graph, genome::Context &ctx, genome::PartitionedDNAMap *pm, const genome::PairedEndData &data,
+                                uint64_t takeFirst, int rank, int world, const PairedOpts &o) {
+    PairedResult r;
+    int lo = o.lo, hi = o.hi;
+    uint64_t a = 0, b = 0;
+    if (world) std::tie(a, b) = genome::pairShare(data.count, takeFirst, rank, world);
+    auto graphMap = graph.getGraphMap();                                                             // :188
+    if (o.rangeAuto) {                                                                               // the same pairs, before walking; over the ranks one histogram
+        r.dist = world ? graph.pairDistances(*pm, graphMap, data, a, b, (uint32_t)o.maxInsert + 1)
+                       : graph.pairDistances(graphMap, data, takeFirst, (uint32_t)o.maxInsert + 1);
+        r.range = genome::insertRange(r.dist.hist);
+        lo = (int)r.range.lo; hi = (int)r.range.hi;
+        if (rank == 0 && r.range.estimated)
+            std::fprintf(stderr, "insert range %u to %u, median %u, from %llu observations\n", r.range.lo, r.range.hi, r.range.median,
+                         (unsigned long long)r.range.observations);
+        else if (rank == 0)
+            std::fprintf(stderr, "no estimate of the insert range (%llu observations): falling back to the reference's %u to %u\n",
+                         (unsigned long long)r.range.observations, r.range.lo, r.range.hi);
+    }
+    genome::Support support(ctx);
+    if (world) {                                                                                     // this rank's pairs, then the sum over the ranks
+        if (o.walk) graph.walkPairs(graphMap, support, data, a, b, lo, hi);
+        if (o.threadReads) {
+            r.threaded = graph.threadReads(graphMap, support, data, a, b);
+            double v[7];
+            for (int i = 0; i < 7; i++) v[i] = (double)r.threaded.v[i];
+            genome::check(gk_dist_allreduce_f64(pm->distHandle(), v, 7, 0), ctx.handle());
+            for (int i = 0; i < 7; i++) r.threaded.v[i] = (uint64_t)v[i];
+        }
+        pm->reduceSupport(graph, support);                                                           // (before any node split)
+    } else {
+        if (o.walk) graph.walkPairs(graphMap, support, data, takeFirst, lo, hi);                     // :213-263
+        if (o.threadReads) r.threaded = graph.threadReads(graphMap, support, data, takeFirst);
+    }
+    std::tie(r.supPairs, r.badPairs, r.walked) = support.sizes();                                    // :266 "Bad pairs"
+    std::tie(r.removedEdges, r.newNodes) = graph.splitBySupport(support, o.cutoff);                  // :272-316
+    graph.simplifyGraph();                                                                           // :318
+    return r;
+}
