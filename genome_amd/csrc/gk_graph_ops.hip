@@ -30,15 +30,19 @@ template <int W> __global__ __launch_bounds__(BLOCK) void k_build_nidx(GraphView
         while (atomicCAS(&g.nidx[i], NONE, (u32)n) != NONE) i = (i + 1) & g.nidx_mask;
     }
 }
+// The live node with this k-mer.  After a node split several nodes share a sequence, and dead ones stay in the index: the live
+// one with the smallest id is the node a k-mer names (gk_graph_node_lookup's rule), whatever order the index took them in —
+// k_build_nidx inserts in the order its lanes arrive, k_nidx_insert behind what is there.
 template <int W> __device__ __forceinline__ u32 node_find(const GraphView &g, Kmer<W> x) {
+    u32 best = NONE;
     u64 i = slot_hash(x) & g.nidx_mask;
     for (u64 p = 0; p <= g.nidx_mask; p++) {
-        u32 n = g.nidx[i];
-        if (n == NONE) return NONE;
-        if (node_kmer<W>(g, n) == x) return n;
+        const u32 n = g.nidx[i];
+        if (n == NONE) break;
+        if (g.node_alive[n] && node_kmer<W>(g, n) == x && n < best) best = n;
         i = (i + 1) & g.nidx_mask;
     }
-    return NONE;
+    return best;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -656,16 +660,7 @@ template <int W> __global__ void k_node_lookup(GraphView g, u64 lo, u64 hi, int 
     Kmer<W> x;
     if constexpr (W == 1) x = Kmer<1>{lo};
     else x = Kmer<2>{lo, hi};
-    // node_find returns the first index entry with this k-mer; after a node split several nodes share a sequence: the live one
-    // with the smallest id is reported
-    u32 best = NONE;
-    u64 i = slot_hash(x) & g.nidx_mask;
-    for (u64 p = 0; p <= g.nidx_mask; p++) {
-        const u32 n = g.nidx[i];
-        if (n == NONE) break;
-        if (g.node_alive[n] && node_kmer<W>(g, n) == x && n < best) best = n;
-        i = (i + 1) & g.nidx_mask;
-    }
+    const u32 best = node_find<W>(g, x);
     out2[0] = best;
     out2[1] = best != NONE && base >= 0 && base < 4 ? g.out_edge[(u64)best * 4 + base] : NONE;
 }

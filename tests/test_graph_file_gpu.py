@@ -23,6 +23,7 @@ from genome_amd.dnamap import Context, HipDNAMap
 from genome_amd.freqfilter import PairedEndData
 from genome_amd.graph import Support, buildGraph, loadGraph
 from genome_amd.partitioned import PartitionedDNAMap
+from graph_model import same_graph
 from test_dist_bin_gpu import json_line, ragged_pairs, run_world
 from test_pairs_gpu import gpu_canonical, gpu_support_by_content, make_pairs
 
@@ -72,30 +73,6 @@ def header(b):
     k = struct.unpack_from("<I", b, 12)[0]
     nb, eb, nn, ne, pool = struct.unpack_from("<5Q", b, 16)
     return k, nb, eb, nn, ne, pool
-
-
-def same_graph(a, b):
-    """b is a, id for id"""
-    assert a.k == b.k
-    assert a.counts() == b.counts()
-    assert a.idBounds() == b.idBounds()
-    assert a.checksum() == b.checksum()
-    assert a.idFingerprint() == b.idFingerprint()
-    nb, eb = a.idBounds()
-    na, nb_ = a.nodesById(np.arange(nb)), b.nodesById(np.arange(nb))
-    assert np.array_equal(na["alive"], nb_["alive"])
-    live = na["alive"]
-    for key in ("lo", "hi", "in_deg", "out_deg"):
-        assert np.array_equal(na[key][live], nb_[key][live]), key
-    ea, eb_ = a.edgesById(np.arange(eb)), b.edgesById(np.arange(eb))
-    assert np.array_equal(ea["alive"], eb_["alive"])
-    live = ea["alive"]
-    for key in ("start", "end", "len", "first"):
-        assert np.array_equal(ea[key][live], eb_[key][live]), key
-    for lo, hi in zip(na["lo"][na["alive"]], na["hi"][na["alive"]]):
-        kmer = dna.unpack(int(lo), int(hi), a.k)
-        assert a.out_order(kmer) == b.out_order(kmer)
-        assert a.nodeId(kmer) == b.nodeId(kmer)
 
 
 def round_trip(g, tmp_path, name="g.gkg"):
