@@ -210,6 +210,7 @@ TEST_SIGNATURES = {
     "gk_dist_create_loopback": (C.c_int, [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]),
     "gk_test_support_last_walk": (C.c_int, [vp, u64p, u64p]),
     "gk_test_grid_cap_uses": (C.c_int, [vp, u64p]),
+    "gk_test_part_plan": (C.c_int, [vp, vp]),          # (gk_test_part_in *, gk_test_part_out *: tests/test_part_plan_cpu.py)
 }
 TEST_LIB_PATH = os.path.join(_HERE, "libgenome_amd_test.so")
 

@@ -373,6 +373,41 @@ constexpr int PART_NOT_UNIFORM = 2;      // ReadSrc::verify_uniform failed: walk
 struct PartPlan { bool estimate = false; bool fine_exact = false; bool check_canon = false; double grow_ahead = 1.0; };
 int part_count(gk_map *m, PartScratch **pps, const ReadSrc &src, const uint64_t *d_keys, uint64_t nkeys_in, uint64_t nkeys_bound,
                bool from_empty, const PartPlan &plan);
+// One member of P4's kernel family (gk_partition.hip: P4_FORMS): a 4096 / 6144 / 8192 / 12288-key LDS sort, or the exact level's
+// straight scatter.  Plain values and type-erased entry points, so that the choice needs no kernel type.
+struct P4Form {
+    const char *name;                               // gk_map_stats "last_p4"
+    int W, threads, kpt;                            // key words; workgroup size; keys per thread (a chunk is threads x kpt keys)
+    size_t (*lds)(uint32_t nb2, uint32_t nb1);      // dynamic LDS for nb2 fine buckets beside the tables of nb1 L1 buckets
+    int op_wgs_cap;                                 // over-provisioned level: at most this many workgroups per CU, whatever "p4_grid" asks
+    int exact_wgs;                                  // exact level: workgroups per CU
+    const void *kernel[2];                          // [RANGED] (nullptr: no dynamic-LDS limit to raise)
+    void (*launch[2])(const void *p4args);          // [RANGED], over a P4Args<W>
+    uint32_t chunk_keys() const { return (uint32_t)(threads * kpt); }
+};
+// The choices of one batch as a pure function of plain values: no HIP call, no context, no map.  part_run takes every
+// decision from here, and the test build echoes it (gk_test_part_plan), so the auto rules are pinned without a multi-GB table.
+enum PartSource { PART_SRC_DEVICE = 0, PART_SRC_HOST = 1, PART_SRC_PREFETCHED = 2, PART_SRC_RAGGED = 3, PART_SRC_KEYS = 4 };
+struct PartInput {
+    int W = 1, lnb1 = 8;
+    uint32_t nb2 = 1;
+    int source = PART_SRC_DEVICE;
+    int max_windows = 0;                            // fixed-stride records: windows of the longest read (0 for ragged streams and keys)
+    bool from_empty = false, verify_uniform = false;
+    bool estimate = false, fine_exact = false;      // PartPlan's (the "fine_exact" switch arrives through it: gk_table.hip insert_batch)
+    bool part_exact = false;
+    int p4_wide = -1, p4_direct = -1, p2_wide = -1, p2_sorted = -1, p45_stripes = -1, p24_pieces = -1, p4_grid = -1, max_nb2 = 0;
+};
+struct PartChoice {
+    bool supported;                                 // part_supported for this geometry
+    bool op1, fine_exact, sync_between, pipelined;  // (fine_exact: until the sample has been read, see PartBatch::between_levels)
+    int pieces, op_stripes, p4_per_cu;              // pieces asked for; stripes and P4 workgroups per CU of the over-provisioned level
+    const char *p2;                                 // gk_map_stats "last_p2"
+    int p2_threads; bool p2_sorted; uint32_t p2_nb1;    // the k_op_scatter1_reads member behind it (fixed-stride records only)
+    const P4Form *p4_op, *p4_exact;                 // P4 of the over-provisioned / the exact fine level
+};
+PartChoice part_choose(const PartInput &in);
+const P4Form *p4_choose_exact(int W, uint32_t nb2, uint32_t nb1, int p4_wide, int p4_direct);    // (again after the table grew between the levels)
 // one chunk of a host `.bin` stream, cut by gk_map_count_reads' rules (gk_table.hip: map_cut_chunk)
 struct BinChunk {
     size_t begin = 0, bytes = 0;

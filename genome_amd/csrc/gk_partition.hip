@@ -1272,7 +1272,7 @@ struct PartScratch {
 };
 static constexpr int MAX_PIECES = 8;
 #ifndef GK_P24_PIECES_DEFAULT
-#define GK_P24_PIECES_DEFAULT 1          // pieces of a pipelined batch ("p24_pieces"; 0/1 = one piece: the default, see part_run)
+#define GK_P24_PIECES_DEFAULT 1          // pieces of a pipelined batch ("p24_pieces"; 0/1 = one piece: the default, see part_choose)
 #endif
 static constexpr size_t PIECE_WORDS = MAXB1 + MAXB1 + (MAXB1 + 1) + 7;
 // LDS the P4 kernels take for their chunk / range table and L1 extents, in front of the sort buffers
@@ -1397,79 +1397,98 @@ void part_scratch_free(gk_ctx *ctx, PartScratch *ps) {
     delete ps;
 }
 
-// returns GK_OK, an error (< 0), or PART_RETRY_DIRECT: the over-provisioned regions and the spill
-// list overflowed (extreme skew); nothing but scratch was touched, the caller takes the direct path
-template <int W>
-static int part_run(gk_map *m, PartScratch *ps, const ReadSrc &src, const u64 *d_keys, u64 nkeys_in, u64 nkeys_bound, bool from_empty,
-                    const PartPlan &plan) {
-    const unsigned long long occ_before = m->occ_cached;     // the windows counted by earlier batches of this call (every batch ends with map_sync_counters)
-    gk_ctx *ctx = m->ctx;
-    Table<W> t{reinterpret_cast<Slot<W> *>(m->slots), m->nb2, m->lnb1, m->k == 64 ? 1u : 0u, 0u};
-    PartArrays a;
-    const uint8_t *d_rec = src.rec;
-    const u32 *d_off = src.off;
+// ---- P4: the k_part_scatter2 family, each member described once (P4Form: gk_internal.h) ----------------------------------------
+template <int W> struct P4Args {          // what every member is launched with
+    hipStream_t st; int grid; size_t lds;
+    const u64 *bufA; Table<W> t; const PartArrays *a; u64 max_units; u64 *bufB; u32 b_lo, b_hi;
+};
+template <int W, bool RANGED, int NT, int KPT> struct P4Sort {
+    static constexpr auto kernel = &k_part_scatter2<W, RANGED, NT, KPT>;
+    static void launch(const void *p) {
+        const P4Args<W> &x = *static_cast<const P4Args<W> *>(p);
+        hipLaunchKernelGGL(kernel, dim3(x.grid), dim3(NT), x.lds, x.st, x.bufA, x.t, *x.a, x.max_units, x.bufB, x.b_lo, x.b_hi);
+    }
+};
+template <int W> static void p4_direct_launch(const void *p) {      // (ranges of every L1 bucket: no [b_lo, b_hi))
+    const P4Args<W> &x = *static_cast<const P4Args<W> *>(p);
+    hipLaunchKernelGGL(k_part_scatter2_direct<W>, dim3(x.grid), dim3(PBLOCK), x.lds, x.st, x.bufA, x.t, *x.a, x.max_units, x.bufB);
+}
+// the sort buffers behind the chunk / range table and the L1 extents
+template <int W, int NT, int KPT> static size_t p4_sort_lds(u32 nb2, u32 nb1) { return ScatterLds<W, NT, KPT>::bytes(nb2) + part_tables_bytes(nb1); }
+static size_t p4_direct_lds(u32 nb2, u32) { return (size_t)nb2 * 4; }      // one cursor per fine bucket (its tables are static LDS)
+template <int W, int NT, int KPT> static P4Form p4_sort(const char *name, int op_wgs_cap, int exact_wgs) {
+    return P4Form{name, W, NT, KPT, &p4_sort_lds<W, NT, KPT>, op_wgs_cap, exact_wgs,
+                  {reinterpret_cast<const void *>(P4Sort<W, false, NT, KPT>::kernel), reinterpret_cast<const void *>(P4Sort<W, true, NT, KPT>::kernel)},
+                  {&P4Sort<W, false, NT, KPT>::launch, &P4Sort<W, true, NT, KPT>::launch}};
+}
+template <int W> static P4Form p4_direct() {
+    return P4Form{"direct", W, PBLOCK, KEYS_PER_THREAD, &p4_direct_lds, 0, 8, {nullptr, nullptr}, {nullptr, &p4_direct_launch<W>}};
+}
+static constexpr int NO_CAP = 1 << 30;
+static const P4Form P4_FORMS[] = {
+    // 4096-key sorts on 512 threads: the form every supported geometry can run (part_supported); as many workgroups per CU as
+    // "p4_grid" asks for (4), 4 on the exact level
+    p4_sort<1, PBLOCK, KEYS_PER_THREAD>("sort4096", NO_CAP, 4),
+    p4_sort<2, PBLOCK, KEYS_PER_THREAD>("sort4096", NO_CAP, 4),
+    // 8-byte keys, 8192-key sorts on 1024 threads, at most 2 workgroups per CU: half the per-bin bookkeeping per key, and on the
+    // exact level twice the keys per bin and visit, so fewer partial-line writes (measured at C2, nb2 = 370, over-provisioned:
+    // P4 0.66 -> 0.62 ms in mode U, 0.64 -> 0.62 in mode G).  Needs the CU's whole LDS: not with more fine buckets than fit
+    // beside the tables of a 512 / 1024-bucket L1 level.
+    p4_sort<1, 1024, 8>("sort8192", 2, 2),
+    // 12288-key sorts (12 keys per thread, runs half again as long) where they fit the LDS: measured at C2, nb2 = 370: P4 0.58 ->
+    // 0.52-0.56 ms in mode U, no change in mode G
+    p4_sort<1, 1024, 12>("sort12288", 2, 2),
+    // 16-byte keys: 1024 threads x 6 keys (96 KB of keys).  Over-provisioned, measured at C2 scale: k = 55 P4 0.93 -> 0.85 ms,
+    // k = 63 0.86 -> 0.73-0.80; exact: 1.00 / 0.94 -> 0.91 / 0.98 ms at k = 55, no clear gain
+    p4_sort<2, 1024, 6>("sort6144", 2, 2),
+    // exact level, few keys per bin and chunk: straight scatter with per-range cursors (measured at C3, nb2 = 1525: 67 ms
+    // against 52 ms for the sorted form — 8-byte stores to 64 different lines per instruction leave L2 as partial-line writes)
+    p4_direct<1>(), p4_direct<2>(),
+};
+static const P4Form *p4_form(int W, const char *name) {
+    for (const P4Form &f : P4_FORMS)
+        if (f.W == W && std::string_view(f.name) == name) return &f;
+    return nullptr;
+}
+static bool p4_fits(const P4Form *f, u32 nb2, u32 nb1) { return f->lds(nb2, nb1) <= LDS_BYTES_PER_CU; }
+
+// Over-provisioned fine level.  "p4_wide": -1 the 1024-thread forms from 256 fine buckets per L1 bucket, 0 keeps 4096-key sorts,
+// 1 keeps 8192 where 12288 would fit.
+static const P4Form *p4_choose_op(int W, u32 nb2, u32 nb1, int p4_wide) {
+    const P4Form *wide = p4_form(W, W == 1 ? "sort8192" : "sort6144"), *xl = p4_form(1, "sort12288");
+    if (!p4_fits(wide, nb2, nb1) || !(p4_wide >= 0 ? p4_wide != 0 : nb2 >= 256)) return p4_form(W, "sort4096");
+    return W == 1 && p4_wide != 1 && p4_fits(xl, nb2, nb1) ? xl : wide;
+}
+// Exact fine level.  8-byte keys: 8192-key sorts from 512 fine buckets, 12288 from 1024 ("p4_wide" = 2 forces it); 16-byte keys take
+// their wide form only when asked ("p4_wide" > 0); "p4_direct" = 1 is an A/B option, never chosen by default.
+const P4Form *p4_choose_exact(int W, u32 nb2, u32 nb1, int p4_wide, int p4_direct) {
+    if (p4_direct > 0) return p4_form(W, "direct");
+    const P4Form *wide = p4_form(W, W == 1 ? "sort8192" : "sort6144"), *xl = p4_form(1, "sort12288");
+    if (!p4_fits(wide, nb2, nb1) || !(W == 2 ? p4_wide > 0 : p4_wide >= 0 ? p4_wide != 0 : nb2 >= 512)) return p4_form(W, "sort4096");
+    return W == 1 && p4_fits(xl, nb2, nb1) && (p4_wide >= 0 ? p4_wide == 2 : nb2 >= 1024) ? xl : wide;
+}
+
+// the fine level's 4096-key sort must fit the CU's LDS beside its per-bin arrays and the L1 tables (16-byte keys with 1024 L1
+// buckets: ~3500 fine buckets, a 117 GB table)
+static bool part_supported_geom(int W, int lnb1, u32 nb2, int max_nb2) {
+    return nb2 <= (max_nb2 > 0 ? (u32)max_nb2 : MAX_NB2) && p4_fits(p4_form(W, "sort4096"), nb2, 1u << lnb1);
+}
+bool part_supported(const gk_map *m) { return part_supported_geom(m->W, (int)m->lnb1, m->nb2, m->ctx->hook_max_nb2); }
+uint64_t part_max_slots(int W) { return ((u64)MAX_NB2 << MAX_LNB1) << seg_bits_for(W); }
+
+PartChoice part_choose(const PartInput &in) {
+    PartChoice c{};
+    const u32 nb1 = 1u << in.lnb1;
+    const bool reads = in.source != PART_SRC_KEYS;
+    c.supported = part_supported_geom(in.W, in.lnb1, in.nb2, in.max_nb2);
     // fixed-stride records and key arrays: their key count is known exactly, so the L1 regions can be sized
     // up front and the histogram pass P1 dropped; ragged streams keep the exact pipeline
-    const int max_windows = d_rec && !d_off ? std::max(0, src.max_len - m->k + 1) : 0;
-    const bool op1 = !d_off && !ctx->hook_part_exact && (d_keys || (max_windows > 0 && max_windows <= OP_CAP / W));
-    if (int rc = part_prepare_l1(m, ps, nkeys_bound, op1, &a)) return rc;
-    const u32 nb1 = 1u << m->lnb1;
-    const int cu8 = ctx->cu_count * 8;
-    // P5 holds one segment in LDS in the table's own slot type: 12-byte count slots (8-byte keys in a count table), else Slot<W>
-    const bool cslots = W == 1 && m->layout == LAYOUT_COUNT;
-    const size_t lds = ((size_t)1 << SegBits<W>::value) * sizeof(Slot<W>) + 16;        // (the LDS image is Slot<W> for every layout)
-    if (!ps->lds_attr_set) {
-        const int narrow_max = (int)std::min(ScatterLds<W>::bytes(MAX_NB2) + part_tables_bytes(MAXB1), LDS_BYTES_PER_CU);
-        GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter2<W, false, PBLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, narrow_max));
-        GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter2<W, true, PBLOCK>), hipFuncAttributeMaxDynamicSharedMemorySize, narrow_max));
-        if constexpr (W == 2) {
-            GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter2<2, false, 1024, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES_PER_CU));
-            GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter2<2, true, 1024, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES_PER_CU));
-        }
-        if constexpr (W == 1) {
-            const int wide_max = (int)std::min(ScatterLds<1, 1024>::bytes(MAX_NB2) + part_tables_bytes(MAXB1), LDS_BYTES_PER_CU);
-            GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter2<1, true, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, wide_max));
-            GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter2<1, false, 1024>), hipFuncAttributeMaxDynamicSharedMemorySize, wide_max));
-            GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter2<1, true, 1024, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES_PER_CU));
-            GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter2<1, false, 1024, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES_PER_CU));
-        }
-        GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_part_scatter1_keys<W>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)ScatterLds<W>::bytes(MAXB1)));
-        GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_seg_insert<W, Slot<W>>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)(((size_t)1 << SegBits<W>::value) * sizeof(Slot<W>) + 16)));
-        if constexpr (W == 1)
-            GK_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_seg_insert<1, CSlot>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            (int)(((size_t)1 << SegBits<1>::value) * sizeof(Slot<1>) + 16)));
-        ps->lds_attr_set = true;
-    }
-    if (plan.estimate) { if (int rc = map_ensure_sample(m)) return rc; }
-    if (m->d_sample) m->sample_dirty = true;
-    if (plan.check_canon && d_keys) a.noncanon = &m->d_ctr->noncanon;
-    // (the sample keeps learning whenever it exists, also in batches whose estimate nobody waits for: a key it has not
-    //  seen counts as new later — an overestimate, the safe side)
-    const Sampler sp = m->d_sample ? Sampler{m->d_sample, m->sample_mask, &m->d_ctr->sample_claims} : Sampler{nullptr, 0, nullptr};
-    // Over-provisioned fine level with 8-byte keys: 8192-key chunks on 1024 threads when asked for (gk_ctx_set_option "p4_wide")
-    // (measured at C2, nb2 = 370: P4 0.66 -> 0.62 ms in mode U, 0.64 -> 0.62 in mode G: half the per-bin bookkeeping per key)
-    // (the 8192-key forms need the CU's whole LDS: not with more fine buckets than fit beside the tables of a 512/1024-bucket L1 level)
-    auto wide_fits = [&]() { return W == 1 && ScatterLds<1, 1024>::bytes(m->nb2) + part_tables_bytes(nb1) <= LDS_BYTES_PER_CU; };
-    // 12288-key sorts (12 keys per thread) where they fit the LDS: measured at C2, nb2 = 370: P4 0.58 -> 0.52-0.56 ms in mode U, no
-    // change in mode G ("p4_wide" = 1 keeps 8192)
-    auto op_chunk_keys = [&]() -> u32 {
-        if (W == 2) return 6144u;                        // 16-byte keys: 1024 threads x 6 keys (96 KB of keys)
-        const bool xl = ctx->hook_p4_wide != 1 && ScatterLds<1, 1024, 12>::bytes(m->nb2) + part_tables_bytes(nb1) <= LDS_BYTES_PER_CU;
-        return (xl ? 3u : 2u) * (u32)TILE2;
-    };
-    auto wide2_fits = [&]() { return W == 2 && ScatterLds<2, 1024, 6>::bytes(m->nb2) + part_tables_bytes(nb1) <= LDS_BYTES_PER_CU; };
-    auto op_wide_now = [&]() {
-        // (16-byte keys, measured at C2 scale: k = 55 P4 0.93 -> 0.85 ms, k = 63 0.86 -> 0.73-0.80; "p4_wide" = 0 keeps 4096-key sorts)
-        if (W == 2) return wide2_fits() && (ctx->hook_p4_wide >= 0 ? ctx->hook_p4_wide != 0 : m->nb2 >= 256);
-        return wide_fits() && (ctx->hook_p4_wide >= 0 ? ctx->hook_p4_wide != 0 : m->nb2 >= 256);
-    };
+    c.op1 = in.source != PART_SRC_RAGGED && !in.part_exact && (!reads || (in.max_windows > 0 && in.max_windows <= OP_CAP / in.W));
     // Over-provisioned segment regions are only safe to try on a table that is being rebuilt from empty (if they and
     // the spill list overflow, the table is simply cleared again); a table that holds data gets the exact fine level
     // unless the sample says the batch is near-distinct.
-    bool fine_exact = !op1 || plan.fine_exact || !from_empty;
-    const bool sync_between = plan.estimate || (op1 && !from_empty) || (src.verify_uniform && !from_empty);
+    c.fine_exact = !c.op1 || in.fine_exact || !in.from_empty;
+    c.sync_between = in.estimate || (c.op1 && !in.from_empty) || (in.verify_uniform && !in.from_empty);
     // PIPELINED PIECES (option "p24_pieces", off by default).  When nothing has to come back to the host between the levels
     // (table geometry final, both levels over-provisioned), the batch can be cut into pieces: both levels' regions are
     // append-only, so P4 can take the slice of every L1 region that piece j's scatter filled while piece j+1 is being
@@ -1477,46 +1496,137 @@ static int part_run(gk_map *m, PartScratch *ps, const ReadSrc &src, const u64 *d
     // 2.12 / 2.19 / 2.21 / 2.34 in 2 / 3 / 4 / 8 — the two kernels' workgroups do not fit a CU's LDS together, so they take
     // turns on the CUs and pay the extra launches; host-fed input gains only where the upload is slow enough to leave the
     // GPU idle (28 GB/s: 2.99 -> 2.71 ms; 56 GB/s: 2.45 -> 2.47-2.55, the scatter alone keeps pace with the link).
-    const int want_pieces = ctx->hook_p24_pieces >= 0 ? ctx->hook_p24_pieces : GK_P24_PIECES_DEFAULT;
-    const bool pipelined = d_rec && op1 && !fine_exact && !sync_between && want_pieces > 1 && ctx->hook_p45_stripes <= 1 && m->nb2 <= MAX_NB2;
-    const u64 max_chunks = nkeys_bound / TILE2 + MAXB1 + 1;          // (every L1 bucket may end in a partial chunk)
-    if (pipelined) {
-        if (int rc = part_prepare_fine(m, ps, nkeys_bound, true, &a)) return rc;
-        if (op_wide_now()) a.chunk_keys = op_chunk_keys();
+    c.pieces = in.p24_pieces >= 0 ? in.p24_pieces : GK_P24_PIECES_DEFAULT;
+    c.pipelined = reads && c.op1 && !c.fine_exact && !c.sync_between && c.pieces > 1 && in.p45_stripes <= 1 && in.nb2 <= MAX_NB2;
+    if (reads && c.op1) {
+        // bucket-ordered write-out ("p2_sorted"): the same 0.60 ms as the window-ordered form for 8-byte keys (the LDS passes cost
+        // what the 64-lines-per-instruction stores cost), 6 % faster for 16-byte keys (0.97 -> 0.91 ms at k = 55): default there
+        c.p2_sorted = in.p2_sorted >= 0 ? in.p2_sorted > 0 : in.W == 2;
+        // 1024 threads per tile: A/B option ("p2_wide"); tables beyond 34 GB (or the test hook) take the 1024-bucket form, which has
+        // no 1024-thread member
+        c.p2_nb1 = nb1 > 256 ? MAXB1 : 256u;
+        c.p2_threads = in.p2_wide > 0 && nb1 <= 256 ? 1024 : PBLOCK;
+        c.p2 = c.p2_threads == 1024 ? (c.p2_sorted ? "wide_sorted" : "wide") : c.p2_sorted ? "sorted" : "plain";
+    } else {
+        c.p2 = reads ? "exact" : c.op1 ? "keys" : "keys_exact";
     }
-    // P4 of the over-provisioned fine level over L1 buckets [b_lo, b_hi) of `aa` (the whole batch, a stripe, or a piece's slices)
-    auto launch_p4_op = [&](const PartArrays &aa, hipStream_t st, u32 b_lo, u32 b_hi, u64 share) {
-        const int per_cu = ctx->hook_p4_grid > 0 ? ctx->hook_p4_grid : 4;           // ("p4_grid": workgroups per CU, A/B)
-        const int gchunks = (int)std::min<u64>(max_chunks / share + 1, (u64)ctx->cu_count * per_cu);
-        if (W == 2 && aa.chunk_keys == 6144u) {
-            if constexpr (W == 2) {
-                const size_t lds2 = ScatterLds<2, 1024, 6>::bytes(m->nb2) + part_tables_bytes(nb1);
-                m->last_p4 = "sort6144";
-                hipLaunchKernelGGL((k_part_scatter2<2, false, 1024, 6>), dim3(std::min(gchunks, ctx->cu_count * std::min(per_cu, 2))), dim3(1024), lds2, st, ps->bufA, t, aa,
-                                   max_chunks, ps->bufB, b_lo, b_hi);
-            }
-        } else if (aa.chunk_keys >= 2 * TILE2) {
-            if constexpr (W == 1) {
-                const size_t wide_lds = ScatterLds<1, 1024>::bytes(m->nb2) + part_tables_bytes(nb1);
-                const size_t xl_lds = ScatterLds<1, 1024, 12>::bytes(m->nb2) + part_tables_bytes(nb1);
-                m->last_p4 = aa.chunk_keys == 3 * TILE2 ? "sort12288" : "sort8192";
-                if (aa.chunk_keys == 3 * TILE2)
-                    hipLaunchKernelGGL((k_part_scatter2<1, false, 1024, 12>), dim3(std::min(gchunks, ctx->cu_count * std::min(per_cu, 2))), dim3(1024), xl_lds, st,
-                                       ps->bufA, t, aa, max_chunks, ps->bufB, b_lo, b_hi);
-                else
-                hipLaunchKernelGGL((k_part_scatter2<1, false, 1024>), dim3(std::min(gchunks, ctx->cu_count * std::min(per_cu, 2))), dim3(1024), wide_lds, st, ps->bufA, t, aa,
-                                   max_chunks, ps->bufB, b_lo, b_hi);
-            }
-        } else {
-            m->last_p4 = "sort4096";
-            hipLaunchKernelGGL((k_part_scatter2<W, false, PBLOCK>), dim3(gchunks), dim3(PBLOCK), ScatterLds<W>::bytes(m->nb2) + part_tables_bytes(nb1), st, ps->bufA, t, aa,
-                               max_chunks, ps->bufB, b_lo, b_hi);
-        }
-    };
-    PartArrays a_last = a;          // pipelined: the last piece's view (its P4 runs on the main stream, after the join)
+    c.p4_op = p4_choose_op(in.W, in.nb2, nb1, in.p4_wide);
+    c.p4_exact = p4_choose_exact(in.W, in.nb2, nb1, in.p4_wide, in.p4_direct);
+    c.p4_per_cu = in.p4_grid > 0 ? in.p4_grid : 4;          // ("p4_grid": workgroups per CU, A/B)
+    // Stripes (over-provisioned fine level): P4 is bound by its LDS sort and leaves half the memory system idle, P5 streams
+    // the table and leaves the ALUs idle.  With the L1 buckets cut into stripes, P5 of stripe i runs on the second stream
+    // beside P4 of stripe i+1 (option "p45_stripes": 1 = one after the other).
+    c.op_stripes = std::max(1, std::min<int>({in.p45_stripes > 0 ? in.p45_stripes : 1, (int)nb1, 16}));
+    while (nb1 % (u32)c.op_stripes) c.op_stripes--;
+    return c;
+}
+
+// ---- one batch ------------------------------------------------------------------------------------------------------------------
+// [nspill u64][overflow u32][n_failed u32] of the blob -> the pinned area behind the counters' mirror
+struct PartStatus { unsigned long long nspill; u32 overflow, n_failed; };
+static_assert(sizeof(Counters) <= 64 && sizeof(PartStatus) == 16, "pinned status area layout");
+
+template <int W> struct PartBatch {
+    // P5 holds one segment in LDS as Slot<W>, whatever the table's own slot type
+    static constexpr size_t SEG_LDS = ((size_t)1 << SegBits<W>::value) * sizeof(Slot<W>) + 16;
+    gk_map *const m;
+    gk_ctx *const ctx;
+    PartScratch *const ps;
+    const ReadSrc &src;
+    const u64 *const d_keys;
+    const u64 nkeys_in, nkeys_bound;
+    const bool from_empty;
+    const PartPlan &plan;
+    const unsigned long long occ_before;     // the windows counted by earlier batches of this call (every batch ends with map_sync_counters)
+    const u32 nb1;
+    const u64 max_chunks;                    // (every L1 bucket may end in a partial chunk)
+    Counters *const h_ctr;                   // pinned: the counters' mirror and, behind it, the batch's status
+    PartStatus *const h_st;
+    PartChoice ch{};
+    bool fine_exact = true;                  // ch.fine_exact until the sample has been read (size_table_from_sample)
+    Table<W> t;
+    PartArrays a, a_last;                    // a_last: pipelined: the last piece's view (its P4 runs on the main stream, after the join)
     bool have_last = false;
+    int pieces_run = 1;
+    int rs = 1;                              // fixed-stride records: reads per tile of P2
+    Sampler sp{nullptr, 0, nullptr};
+
+    PartBatch(gk_map *m_, PartScratch *ps_, const ReadSrc &src_, const u64 *d_keys_, u64 nkeys_in_, u64 nkeys_bound_, bool from_empty_, const PartPlan &plan_)
+        : m(m_), ctx(m_->ctx), ps(ps_), src(src_), d_keys(d_keys_), nkeys_in(nkeys_in_), nkeys_bound(nkeys_bound_), from_empty(from_empty_), plan(plan_),
+          occ_before(m_->occ_cached), nb1(1u << m_->lnb1), max_chunks(nkeys_bound_ / TILE2 + MAXB1 + 1),
+          h_ctr(reinterpret_cast<Counters *>(m_->h_status)), h_st(reinterpret_cast<PartStatus *>(m_->h_status + 64)), t(table()) {}
+
+    Table<W> table() const { return Table<W>{reinterpret_cast<Slot<W> *>(m->slots), m->nb2, m->lnb1, m->k == 64 ? 1u : 0u, 0u}; }
+
+    // the choices (part_choose), the L1 level's scratch, the kernels' LDS limits, the sample
+    int prepare() {
+        PartInput in;
+        in.W = W; in.lnb1 = (int)m->lnb1; in.nb2 = m->nb2;
+        in.source = !src.rec ? PART_SRC_KEYS : src.off ? PART_SRC_RAGGED : !src.host ? PART_SRC_DEVICE : src.ready ? PART_SRC_PREFETCHED : PART_SRC_HOST;
+        in.max_windows = src.rec && !src.off ? std::max(0, src.max_len - m->k + 1) : 0;
+        in.from_empty = from_empty; in.verify_uniform = src.verify_uniform;
+        in.estimate = plan.estimate; in.fine_exact = plan.fine_exact;
+        in.part_exact = ctx->hook_part_exact;
+        in.p4_wide = ctx->hook_p4_wide; in.p4_direct = ctx->hook_p4_direct; in.p2_wide = ctx->hook_p2_wide; in.p2_sorted = ctx->hook_p2_sorted;
+        in.p45_stripes = ctx->hook_p45_stripes; in.p24_pieces = ctx->hook_p24_pieces; in.p4_grid = ctx->hook_p4_grid; in.max_nb2 = ctx->hook_max_nb2;
+        ch = part_choose(in);
+        fine_exact = ch.fine_exact;
+        if (int rc = part_prepare_l1(m, ps, nkeys_bound, ch.op1, &a)) return rc;
+        if (!ps->lds_attr_set) { if (int rc = raise_lds_limits()) return rc; }
+        if (plan.estimate) { if (int rc = map_ensure_sample(m)) return rc; }
+        if (m->d_sample) m->sample_dirty = true;
+        if (plan.check_canon && d_keys) a.noncanon = &m->d_ctr->noncanon;
+        // (the sample keeps learning whenever it exists, also in batches whose estimate nobody waits for: a key it has not
+        //  seen counts as new later — an overestimate, the safe side)
+        if (m->d_sample) sp = Sampler{m->d_sample, m->sample_mask, &m->d_ctr->sample_claims};
+        if (ch.pipelined) {
+            if (int rc = part_prepare_fine(m, ps, nkeys_bound, true, &a)) return rc;
+            a.chunk_keys = ch.p4_op->chunk_keys();
+        }
+        a_last = a;
+        return GK_OK;
+    }
+    // a kernel that asks for more than 64 KiB of dynamic LDS must be told so once: every P4 form, the key scatter, P5
+    int raise_lds_limits() {
+        auto raise = [&](const void *kernel, size_t bytes) { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::min(bytes, LDS_BYTES_PER_CU)); };
+        for (const P4Form &f : P4_FORMS)
+            for (const void *kernel : f.kernel)
+                if (f.W == W && kernel) GK_HIP(ctx, raise(kernel, f.lds(MAX_NB2, MAXB1)));
+        GK_HIP(ctx, raise(reinterpret_cast<const void *>(&k_part_scatter1_keys<W>), ScatterLds<W>::bytes(MAXB1)));
+        GK_HIP(ctx, raise(reinterpret_cast<const void *>(&k_seg_insert<W, Slot<W>>), SEG_LDS));
+        if constexpr (W == 1) GK_HIP(ctx, raise(reinterpret_cast<const void *>(&k_seg_insert<1, CSlot>), SEG_LDS));
+        ps->lds_attr_set = true;
+        return GK_OK;
+    }
+
+    // ---- P4 ------------------------------------------------------------------------------------------------------------------
+    void launch_p4(const P4Form *f, bool ranged, const PartArrays &aa, hipStream_t st, int grid, u64 max_units, u32 b_lo, u32 b_hi) {
+        m->last_p4 = f->name;
+        const P4Args<W> x{st, grid, f->lds(m->nb2, nb1), ps->bufA, t, &aa, max_units, ps->bufB, b_lo, b_hi};
+        f->launch[ranged](&x);
+    }
+    // over-provisioned fine level, L1 buckets [b_lo, b_hi) of `aa`: the whole batch, a stripe, or a piece's slices (1 / share of its
+    // chunks).  The form was fixed with the chunk tables (a.chunk_keys), before the table could grow between the levels.
+    void launch_p4_op(const PartArrays &aa, hipStream_t st, u32 b_lo, u32 b_hi, u64 share) {
+        const int grid = (int)std::min<u64>(max_chunks / share + 1, (u64)ctx->cu_count * std::min(ch.p4_per_cu, ch.p4_op->op_wgs_cap));
+        launch_p4(ch.p4_op, false, aa, st, grid, max_chunks, b_lo, b_hi);
+    }
+
+    // ---- P2 of fixed-stride records (over-provisioned L1 level) and its four feeders --------------------------------------------
+    int p2_grid(u64 nr) const { return (int)std::min<u64>(std::max<u64>((nr + rs - 1) / rs, 1), (u64)ctx->cu_count * GK_OP_WGS_PER_CU); }
+    void launch_p2(const uint8_t *recs, u64 nr) {
+        m->last_p2 = ch.p2;
+#define GK_P2(NT, SORTED, NB1)                                                                                                                  \
+    hipLaunchKernelGGL((k_op_scatter1_reads<W, NT, SORTED, NB1>), dim3(p2_grid(nr)), dim3(NT), 0, ctx->stream, recs, nr, src.stride, m->k, src.group, \
+                       rs, src.max_len, src.verify_uniform ? 1 : 0, t, a, sp, m->d_ctr, ps->bufA)
+        if (ch.p2_nb1 > 256) { if (ch.p2_sorted) GK_P2(PBLOCK, true, (int)MAXB1); else GK_P2(PBLOCK, false, (int)MAXB1); }
+        else if (ch.p2_threads == 1024) { if (ch.p2_sorted) GK_P2(1024, true, 256); else GK_P2(1024, false, 256); }
+        else if (ch.p2_sorted) GK_P2(PBLOCK, true, 256);
+        else GK_P2(PBLOCK, false, 256);
+#undef GK_P2
+    }
     // after piece j's scatter: its slice tables; every piece but the last goes to the second stream at once
-    auto piece_done = [&](int j, int npieces) -> int {
+    int piece_done(int j, int npieces) {
         unsigned long long *tab = ps->piece_tables + (size_t)j * PIECE_WORDS;
         const unsigned long long *prev = j ? ps->piece_tables + (size_t)(j - 1) * PIECE_WORDS + MAXB1 : nullptr;
         hipLaunchKernelGGL(k_part_prefix1_piece, dim3(1), dim3(MAXB1), 0, ctx->stream, a, nb1, prev, tab, tab + MAXB1, tab + 2 * MAXB1);
@@ -1529,292 +1639,250 @@ static int part_run(gk_map *m, PartScratch *ps, const ReadSrc &src, const u64 *d
         launch_p4_op(aj, ctx->aux_stream, 0u, nb1, (u64)npieces);
         GK_HIP(ctx, hipGetLastError());
         return GK_OK;
-    };
-    // ---- stage A: P1 + prefix + P2 (the L1 level) -----------------------------------------------------------
-    GK_HIP(ctx, hipEventRecord(ctx->pev[0], ctx->stream));
-    // what this batch launches, by name (gk_map_stats "last_*"): noted where each choice is made, host side only
-    int pieces_run = 1;
-    m->last_slot = cslots ? "count12" : W == 1 ? "slot16" : "slot24";
-    m->last_p2 = d_rec ? "exact" : op1 ? "keys" : "keys_exact";
-    if (d_rec && op1) {
-        GK_HIP(ctx, hipEventRecord(ctx->pev[1], ctx->stream));
-        // reads per tile: their windows must fit the LDS key buffer and their bytes the LDS tile
-        const u64 by_bytes = ((u64)OP_TILE_WORDS * 4 - 96) / src.stride;
-        const int rs = (int)std::max<u64>(1, std::min<u64>(by_bytes, (u64)(OP_CAP / W) / (u64)max_windows));
-        const u64 ntiles = (src.nreads + rs - 1) / rs;
-        const int grid = (int)std::min<u64>(std::max<u64>(ntiles, 1), (u64)ctx->cu_count * GK_OP_WGS_PER_CU);
-        const bool p2_wide = ctx->hook_p2_wide > 0;        // 1024 threads per tile: A/B option (gk_ctx_set_option "p2_wide")
-        // bucket-ordered write-out ("p2_sorted"): the same 0.60 ms as the window-ordered form for 8-byte keys (the LDS passes cost
-        // what the 64-lines-per-instruction stores cost), 6 % faster for 16-byte keys (0.97 -> 0.91 ms at k = 55): default there
-        const bool p2_sorted = ctx->hook_p2_sorted >= 0 ? ctx->hook_p2_sorted > 0 : W == 2;
-        const int vu = src.verify_uniform ? 1 : 0;
-        auto launch_p2 = [&](int g, const uint8_t *recs, u64 nr) {
-#define GK_P2(NT, SORTED, NB1)                                                                                                                 \
-    hipLaunchKernelGGL((k_op_scatter1_reads<W, NT, SORTED, NB1>), dim3(g), dim3(NT), 0, ctx->stream, recs, nr, src.stride, m->k, src.group, rs, \
-                       src.max_len, vu, t, a, sp, m->d_ctr, ps->bufA)
-            if (nb1 > 256) {                          // tables beyond 34 GB (or the test hook): the 1024-bucket form
-                if (p2_sorted) { m->last_p2 = "sorted"; GK_P2(PBLOCK, true, (int)MAXB1); }
-                else { m->last_p2 = "plain"; GK_P2(PBLOCK, false, (int)MAXB1); }
-            } else if (p2_wide && p2_sorted) { m->last_p2 = "wide_sorted"; GK_P2(1024, true, 256); }
-            else if (p2_wide) { m->last_p2 = "wide"; GK_P2(1024, false, 256); }
-            else if (p2_sorted) { m->last_p2 = "sorted"; GK_P2(PBLOCK, true, 256); }
-            else { m->last_p2 = "plain"; GK_P2(PBLOCK, false, 256); }
-#undef GK_P2
-        };
-        if (!src.host && !pipelined) {
-            launch_p2(grid, d_rec, src.nreads);
-        } else if (!src.host) {
-            // equal pieces of whole tiles, each big enough to fill the chip a few times over
-            // (an explicit "p24_pieces" also cuts small batches: tests)
-            const u64 min_piece = (u64)rs * (ctx->hook_p24_pieces > 1 ? 64ull : (u64)ctx->cu_count * GK_OP_WGS_PER_CU * 2);
-            const u64 np = std::max<u64>(1, std::min<u64>({(u64)want_pieces, (u64)MAX_PIECES, src.nreads / std::max<u64>(min_piece, 1)}));
-            const u64 sub_reads = ((src.nreads + np - 1) / np + rs - 1) / rs * rs;
-            const int npieces = (int)((src.nreads + sub_reads - 1) / sub_reads);
-            pieces_run = npieces;
-            u64 r0 = 0;
-            for (int j = 0; j < npieces; j++, r0 += sub_reads) {
-                const u64 nr = std::min<u64>(sub_reads, src.nreads - r0);
-                const u64 nt = (nr + rs - 1) / rs;
-                launch_p2((int)std::min<u64>(std::max<u64>(nt, 1), (u64)ctx->cu_count * GK_OP_WGS_PER_CU), d_rec + (size_t)r0 * src.stride, nr);
-                if (int rc = piece_done(j, npieces)) return rc;
-            }
-        } else if (src.ready) {
-            // Host-fed and PREFETCHED: the whole chunk's upload was queued on the copy stream while the previous chunk (or the
-            // caller's previous call) was in its fine level; one scatter behind the event.
-            GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, src.ready, 0));
-            launch_p2(grid, d_rec, src.nreads);
-            if (pipelined) { if (int rc = piece_done(0, 1)) return rc; }
-        } else {
-            // Host-fed: upload in sub-chunks on the copy stream, scatter each as soon as it has landed.  The L1 regions are
-            // append-only (cursor1), so P2 can run once per sub-chunk; P4 and P5 then see one batch.  With the caller's buffer
-            // pinned (gk_host_alloc / gk_host_register) the upload of sub-chunk j+1 overlaps the scatter of sub-chunk j.
-            // The scatter keeps pace with PCIe (0.6 ms against 0.69 ms for 39 MB at 57 GB/s) but slows down beside a running copy,
-            // and every piece costs ~15 us of copy set-up.  Up to 8 equal pieces of whole tiles (measured: a small first and
-            // last piece with four big ones in between — sixteenths 1,3,4,4,3,1 — is 4 % slower).
-            const u64 min_piece = (u64)rs * 1024;
-            u64 piece[8];
-            int npieces = 0;
-            const u64 sub_reads = std::max<u64>(min_piece, ((src.nreads + 7) / 8 + rs - 1) / rs * rs);
-            for (u64 done = 0; done < src.nreads && npieces < 8; done += sub_reads) piece[npieces++] = std::min<u64>(sub_reads, src.nreads - done);
-            if (pipelined) pieces_run = npieces;
-            u64 r0 = 0;
-            for (int j = 0; j < npieces; r0 += piece[j], j++) {
-                const u64 nr = piece[j];
-                if (!nr) continue;
-                const size_t off = (size_t)r0 * src.stride, bytes = (size_t)nr * src.stride;
-                hipEvent_t ev = ctx->cev[j % 16];
-                if (j == 0) {       // the copy stream must not overwrite the staging area while an earlier kernel still reads it
-                    GK_HIP(ctx, hipEventRecord(ev, ctx->stream));
-                    GK_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ev, 0));
-                }
-                GK_HIP(ctx, hipMemcpyAsync(const_cast<uint8_t *>(d_rec) + off, src.host + off, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
-                GK_HIP(ctx, hipEventRecord(ev, ctx->copy_stream));
-                GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
-                const u64 nt = (nr + rs - 1) / rs;
-                const int gsub = (int)std::min<u64>(std::max<u64>(nt, 1), (u64)ctx->cu_count * GK_OP_WGS_PER_CU);
-                launch_p2(gsub, d_rec + off, nr);
-                if (pipelined) { if (int rc = piece_done(j, npieces)) return rc; }
-            }
+    }
+    int feed_device() { launch_p2(src.rec, src.nreads); return GK_OK; }
+    int feed_device_pieces() {
+        // equal pieces of whole tiles, each big enough to fill the chip a few times over
+        // (an explicit "p24_pieces" also cuts small batches: tests)
+        const u64 min_piece = (u64)rs * (ctx->hook_p24_pieces > 1 ? 64ull : (u64)ctx->cu_count * GK_OP_WGS_PER_CU * 2);
+        const u64 np = std::max<u64>(1, std::min<u64>({(u64)ch.pieces, (u64)MAX_PIECES, src.nreads / std::max<u64>(min_piece, 1)}));
+        const u64 sub_reads = ((src.nreads + np - 1) / np + rs - 1) / rs * rs;
+        const int npieces = (int)((src.nreads + sub_reads - 1) / sub_reads);
+        pieces_run = npieces;
+        u64 r0 = 0;
+        for (int j = 0; j < npieces; j++, r0 += sub_reads) {
+            launch_p2(src.rec + (size_t)r0 * src.stride, std::min<u64>(sub_reads, src.nreads - r0));
+            if (int rc = piece_done(j, npieces)) return rc;
         }
-    } else if (d_rec) {
+        return GK_OK;
+    }
+    // Host-fed and PREFETCHED: the whole chunk's upload was queued on the copy stream while the previous chunk (or the
+    // caller's previous call) was in its fine level; one scatter behind the event.
+    int feed_prefetched() {
+        GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, src.ready, 0));
+        launch_p2(src.rec, src.nreads);
+        return ch.pipelined ? piece_done(0, 1) : GK_OK;
+    }
+    // Host-fed: upload in sub-chunks on the copy stream, scatter each as soon as it has landed.  The L1 regions are
+    // append-only (cursor1), so P2 can run once per sub-chunk; P4 and P5 then see one batch.  With the caller's buffer
+    // pinned (gk_host_alloc / gk_host_register) the upload of sub-chunk j+1 overlaps the scatter of sub-chunk j.
+    // The scatter keeps pace with PCIe (0.6 ms against 0.69 ms for 39 MB at 57 GB/s) but slows down beside a running copy,
+    // and every piece costs ~15 us of copy set-up.  Up to 8 equal pieces of whole tiles (measured: a small first and
+    // last piece with four big ones in between — sixteenths 1,3,4,4,3,1 — is 4 % slower).
+    int feed_host() {
+        const u64 min_piece = (u64)rs * 1024;
+        u64 piece[8];
+        int npieces = 0;
+        const u64 sub_reads = std::max<u64>(min_piece, ((src.nreads + 7) / 8 + rs - 1) / rs * rs);
+        for (u64 done = 0; done < src.nreads && npieces < 8; done += sub_reads) piece[npieces++] = std::min<u64>(sub_reads, src.nreads - done);
+        if (ch.pipelined) pieces_run = npieces;
+        u64 r0 = 0;
+        for (int j = 0; j < npieces; r0 += piece[j], j++) {
+            const u64 nr = piece[j];
+            if (!nr) continue;
+            const size_t off = (size_t)r0 * src.stride, bytes = (size_t)nr * src.stride;
+            hipEvent_t ev = ctx->cev[j % 16];
+            if (j == 0) {       // the copy stream must not overwrite the staging area while an earlier kernel still reads it
+                GK_HIP(ctx, hipEventRecord(ev, ctx->stream));
+                GK_HIP(ctx, hipStreamWaitEvent(ctx->copy_stream, ev, 0));
+            }
+            GK_HIP(ctx, hipMemcpyAsync(const_cast<uint8_t *>(src.rec) + off, src.host + off, bytes, hipMemcpyHostToDevice, ctx->copy_stream));
+            GK_HIP(ctx, hipEventRecord(ev, ctx->copy_stream));
+            GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev, 0));
+            launch_p2(src.rec + off, nr);
+            if (ch.pipelined) { if (int rc = piece_done(j, npieces)) return rc; }
+        }
+        return GK_OK;
+    }
+    // the exact L1 level of a read stream: P1, prefix, P2
+    int feed_exact_reads() {
         if (int rc = stage_source(ctx, src)) return rc;
         const u64 ntiles = (src.nreads + PTILE_READS - 1) / PTILE_READS;
         const int grid = (int)std::min<u64>(std::max<u64>(ntiles, 1), (u64)ctx->cu_count * 4);
-        hipLaunchKernelGGL(k_part_hist1_reads<W>, dim3(grid), dim3(PBLOCK), 0, ctx->stream, d_rec, src.nreads, d_off, src.stride, m->k, src.group,
+        hipLaunchKernelGGL(k_part_hist1_reads<W>, dim3(grid), dim3(PBLOCK), 0, ctx->stream, src.rec, src.nreads, src.off, src.stride, m->k, src.group,
                            src.max_len, t, a.hist1, sp, m->d_ctr);
         hipLaunchKernelGGL(k_part_prefix1, dim3(1), dim3(MAXB1), 0, ctx->stream, a, nb1);
         GK_HIP(ctx, hipEventRecord(ctx->pev[1], ctx->stream));
         // (A variant that also sorts THIS kernel's keys in LDS before writing was measured slower,
         //  0.76 vs 0.68 ms at C2: P2 is bound by the two window-extraction passes, not by its stores.)
-        hipLaunchKernelGGL(k_part_scatter1_reads<W>, dim3(grid), dim3(PBLOCK), 0, ctx->stream, d_rec, src.nreads, d_off, src.stride, m->k, src.group,
+        hipLaunchKernelGGL(k_part_scatter1_reads<W>, dim3(grid), dim3(PBLOCK), 0, ctx->stream, src.rec, src.nreads, src.off, src.stride, m->k, src.group,
                            src.max_len, t, a.l1_base, a.cursor1, ps->bufA);
-    } else {
-        if (!op1) {
-            const int grid = (int)std::min<u64>(std::max<u64>((nkeys_in + BLOCK - 1) / BLOCK, 1), (u64)cu8);
+        return GK_OK;
+    }
+    int feed_keys() {
+        if (!ch.op1) {
+            const int grid = (int)std::min<u64>(std::max<u64>((nkeys_in + BLOCK - 1) / BLOCK, 1), (u64)ctx->cu_count * 8);
             hipLaunchKernelGGL(k_part_hist1_keys<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, d_keys, nkeys_in, t, a.hist1);
             hipLaunchKernelGGL(k_part_prefix1, dim3(1), dim3(MAXB1), 0, ctx->stream, a, nb1);
         }
         GK_HIP(ctx, hipEventRecord(ctx->pev[1], ctx->stream));
         const int g2 = (int)std::min<u64>(std::max<u64>((nkeys_in + TILE2 - 1) / TILE2, 1), (u64)ctx->cu_count * 4);
         hipLaunchKernelGGL(k_part_scatter1_keys<W>, dim3(g2), dim3(PBLOCK), ScatterLds<W>::bytes(std::max(256u, nb1)), ctx->stream, d_keys, nkeys_in, t, a, ps->bufA, sp);
+        return GK_OK;
     }
-    if (!pipelined) {
-        if (op_wide_now()) a.chunk_keys = op_chunk_keys();      // (only the over-provisioned fine level's P4 reads it)
-        if (op1) hipLaunchKernelGGL(k_part_prefix1, dim3(1), dim3(MAXB1), 0, ctx->stream, a, nb1);     // chunk / range tables from the cursors
-    }
-    GK_HIP(ctx, hipGetLastError());
-    GK_HIP(ctx, hipEventRecord(ctx->pev[2], ctx->stream));
-    // the NEXT chunk's (or the caller's next batch's) upload, armed before this batch began, starts when this L1 scatter ends
-    if (int rc = map_fire_prefetch(m, ctx->pev[2])) return rc;
 
-    // ---- between the levels ----------------------------------------------------------------------------------
+    // ---- stage 1: P1 + prefix + P2 (the L1 level) --------------------------------------------------------------------------------
+    int l1_level() {
+        GK_HIP(ctx, hipEventRecord(ctx->pev[0], ctx->stream));
+        // what this batch launches, by name (gk_map_stats "last_*"): noted where each launch is made, host side only
+        // P5 builds 12-byte count slots (8-byte keys in a count table), else Slot<W>
+        m->last_slot = W == 1 && m->layout == LAYOUT_COUNT ? "count12" : W == 1 ? "slot16" : "slot24";
+        m->last_p2 = src.rec ? "exact" : ch.p2;          // (fixed-stride records: launch_p2 names its member)
+        int rc;
+        if (src.rec && ch.op1) {
+            GK_HIP(ctx, hipEventRecord(ctx->pev[1], ctx->stream));
+            // reads per tile: their windows must fit the LDS key buffer and their bytes the LDS tile
+            const u64 by_bytes = ((u64)OP_TILE_WORDS * 4 - 96) / src.stride;
+            const u64 max_windows = (u64)std::max(0, src.max_len - m->k + 1);
+            rs = (int)std::max<u64>(1, std::min<u64>(by_bytes, (u64)(OP_CAP / W) / max_windows));
+            rc = !src.host ? (ch.pipelined ? feed_device_pieces() : feed_device()) : src.ready ? feed_prefetched() : feed_host();
+        } else {
+            rc = src.rec ? feed_exact_reads() : feed_keys();
+        }
+        if (rc) return rc;
+        if (!ch.pipelined) {
+            a.chunk_keys = ch.p4_op->chunk_keys();      // (only the over-provisioned fine level's P4 reads it)
+            if (ch.op1) hipLaunchKernelGGL(k_part_prefix1, dim3(1), dim3(MAXB1), 0, ctx->stream, a, nb1);     // chunk / range tables from the cursors
+        }
+        GK_HIP(ctx, hipGetLastError());
+        GK_HIP(ctx, hipEventRecord(ctx->pev[2], ctx->stream));
+        // the NEXT chunk's (or the caller's next batch's) upload, armed before this batch began, starts when this L1 scatter ends
+        return map_fire_prefetch(m, ctx->pev[2]);
+    }
+
+    // ---- the host round trips ---------------------------------------------------------------------------------------------------
+    int request_status() {          // -> h_st, stream-ordered; the caller syncs
+        GK_HIP(ctx, hipMemcpyAsync(h_st, a.nspill, sizeof(PartStatus), hipMemcpyDeviceToHost, ctx->stream));
+        return GK_OK;
+    }
+    int read_counters(Counters *out) {      // one stream sync, also for a status requested before it
+        GK_HIP(ctx, hipMemcpyAsync(h_ctr, m->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, ctx->stream));
+        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        *out = *h_ctr;
+        return GK_OK;
+    }
+    // Give the batch back to the caller: PART_RETRY_DIRECT (the regions and the spill list overflowed: extreme skew), PART_NOT_UNIFORM
+    // (a length byte differed) or PART_OUTGREW.  table_touched = false: between the levels, only scratch was touched and the
+    // batch's timeline ends here (pev[5]); true: P5 has run on a table that was being rebuilt from empty, and whatever it claimed
+    // is void.  Only the retry counts as one ("retries_direct").
+    int give_back(int reason, bool table_touched) {
+        if (reason == PART_NOT_UNIFORM) GK_HIP(ctx, hipMemsetAsync(&m->d_ctr->format, 0, sizeof(u32), ctx->stream));
+        if (!table_touched) GK_HIP(ctx, hipEventRecord(ctx->pev[5], ctx->stream));
+        if (src.rec) {   // P2 already counted this batch's windows: back to what the counter held when the batch began.  (Until round 3
+                         // the batch's BOUND was subtracted — for super-k-mer records an upper bound, not the windows they hold — which
+                         // took earlier batches' windows with it: a 1.9e9-window exchange that retried its second batch reported half.)
+            unsigned long long occ = occ_before;
+            GK_HIP(ctx, hipMemcpy(&m->d_ctr->occurrences, &occ, 8, hipMemcpyHostToDevice));
+            m->occ_cached = occ;
+        }
+        if (table_touched) GK_HIP(ctx, hipMemset(&m->d_ctr->size, 0, 8));
+        if (reason == PART_RETRY_DIRECT) m->retries_direct++;
+        return reason;
+    }
+
+    // ---- stage 2: between the levels ---------------------------------------------------------------------------------------------
     // Did the spill list overflow (extreme skew)?  Then the batch has to take the direct path.  A table
     // that holds data must not be touched before that is known (host round trip here); a table that is
     // being rebuilt from empty can simply be cleared again, so P5 goes out first and the flag is read
     // with everything else after it — one host round trip less per batch on the common path.
     // With plan.estimate the round trip is taken anyway: it brings the distinct-key sample back.
-    unsigned long long nspill = 0;
-    u32 ovf = 0;
-    // [nspill u64][overflow u32][n_failed u32] of the blob -> the pinned area behind the counters' mirror; the caller syncs
-    struct PartStatus { unsigned long long nspill; u32 overflow, n_failed; };
-    PartStatus *h_st = reinterpret_cast<PartStatus *>(m->h_status + 64);
-    static_assert(sizeof(Counters) <= 64 && sizeof(PartStatus) == 16, "pinned status area layout");
-    auto request_status = [&]() -> int {
-        GK_HIP(ctx, hipMemcpyAsync(h_st, a.nspill, sizeof(PartStatus), hipMemcpyDeviceToHost, ctx->stream));
+    int between_levels() {
+        if (src.verify_uniform && !(src.rec && ch.op1)) return fail(ctx, GK_E_STATE, "unverified host stream reached a path that cannot verify it");
+        // (an unverified host stream behind a table that is being rebuilt from empty is checked at the END with everything else:
+        //  if a length byte differed, the half-built table is simply void again — one host round trip less per batch)
+        if (ch.sync_between) {
+            Counters c;
+            if (int rc = request_status()) return rc;
+            if (int rc = read_counters(&c)) return rc;
+            if (src.verify_uniform && c.format) return give_back(PART_NOT_UNIFORM, false);     // not the uniform stream it looked like
+            if (h_st->overflow) return give_back(PART_RETRY_DIRECT, false);
+            if (plan.estimate) { if (int rc = size_table_from_sample(c)) return rc; }
+        }
+        if (!part_supported(m)) {
+            // The table was just grown for this batch with its L1 fan-out kept (P2 has cut the batch by L1 bucket) and now has more
+            // fine buckets per L1 bucket than P4 sorts: only scratch was touched (the table itself is valid), so the batch takes
+            // the direct path; the next growth outside a batch picks a larger fan-out and the pipeline is back.
+            if (!ch.sync_between) return fail(ctx, GK_E_CAPACITY, "table too large for the partitioned insert path");     // (callers check part_supported first)
+            return give_back(PART_OUTGREW, false);
+        }
+        if (!ch.pipelined) { if (int rc = part_prepare_fine(m, ps, nkeys_bound, !fine_exact, &a)) return rc; }
+        GK_HIP(ctx, hipEventRecord(ctx->gev, ctx->stream));
         return GK_OK;
-    };
-    auto abandon = [&](bool table_touched) -> int {
-        if (d_rec) {   // P2 already counted this batch's windows: back to what the counter held when the batch began.  (Until round 3
-                       // the batch's BOUND was subtracted — for super-k-mer records an upper bound, not the windows they hold — which
-                       // took earlier batches' windows with it: a 1.9e9-window exchange that retried its second batch reported half.)
-            unsigned long long occ = occ_before;
-            GK_HIP(ctx, hipMemcpy(&m->d_ctr->occurrences, &occ, 8, hipMemcpyHostToDevice));
-            m->occ_cached = occ;
-        }
-        if (table_touched) GK_HIP(ctx, hipMemset(&m->d_ctr->size, 0, 8));     // from empty: whatever P5 claimed is void
-        m->retries_direct++;
-        return PART_RETRY_DIRECT;
-    };
-    if (src.verify_uniform && !(d_rec && op1)) return fail(ctx, GK_E_STATE, "unverified host stream reached a path that cannot verify it");
-    // (an unverified host stream behind a table that is being rebuilt from empty is checked at the END with everything else:
-    //  if a length byte differed, the half-built table is simply void again — one host round trip less per batch)
-    if (sync_between) {
-        Counters *hc = reinterpret_cast<Counters *>(m->h_status);
-        if (int rc = request_status()) return rc;
-        GK_HIP(ctx, hipMemcpyAsync(hc, m->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        const Counters c = *hc;
-        nspill = h_st->nspill; ovf = h_st->overflow;
-        if (src.verify_uniform && c.format) {       // not the uniform stream it looked like: only scratch was touched
-            GK_HIP(ctx, hipMemsetAsync(&m->d_ctr->format, 0, sizeof(u32), ctx->stream));
-            GK_HIP(ctx, hipEventRecord(ctx->pev[5], ctx->stream));
-            abandon(false);
-            m->retries_direct--;
-            return PART_NOT_UNIFORM;
-        }
-        if (ovf) {
-            GK_HIP(ctx, hipEventRecord(ctx->pev[5], ctx->stream));
-            return abandon(false);
-        }
-        if (plan.estimate) {
-            // new distinct keys of this batch ~ 1024 x the sample keys it added (+ 4 sigma of that estimate + what the
-            // spill list holds, which the sample has seen too but the regions have not)
-            const u64 claims = c.sample_claims - std::min<u64>(c.sample_claims, m->sample_claims_seen);
-            m->sample_claims_seen = c.sample_claims;
-            const bool saturated = c.sample_claims * 2 > m->sample_mask;          // the set is half full: stop trusting it
-            u64 est_new = saturated ? nkeys_bound : (u64)((double)claims * 1024.0 * 1.05 + 4.0 * std::sqrt((double)claims + 1.0) * 1024.0 + 4096.0);
-            est_new = std::min<u64>(est_new, nkeys_bound);
-            m->est_distinct_last = est_new;
-            if (!ctx->hook_no_reserve) {
-                // (error k-mers accumulate sub-linearly with the reads: 60 % of the proportional extrapolation)
-                const u64 ahead = (u64)((double)est_new * (1.0 + 0.6 * (std::max(plan.grow_ahead, 1.0) - 1.0)));
-                if (int rc = map_make_room(m, est_new, ahead, from_empty, true)) return rc;     // may replace the table (same lnb1: P2 has cut the batch by L1 bucket)
-            }
-            t = Table<W>{reinterpret_cast<Slot<W> *>(m->slots), m->nb2, m->lnb1, m->k == 64 ? 1u : 0u, 0u};
-            // many repeats: segment sizes are far from binomial -> exact fine level
-            fine_exact = !op1 || plan.fine_exact || (double)est_new < 0.5 * (double)nkeys_bound;
-        }
     }
-    if (!part_supported(m)) {
-        // The table was just grown for this batch with its L1 fan-out kept (P2 has cut the batch by L1 bucket) and now has more
-        // fine buckets per L1 bucket than P4 sorts: only scratch was touched (the table itself is valid), so the batch takes
-        // the direct path; the next growth outside a batch picks a larger fan-out and the pipeline is back.
-        if (!sync_between) return fail(ctx, GK_E_CAPACITY, "table too large for the partitioned insert path");     // (callers check part_supported first)
-        GK_HIP(ctx, hipEventRecord(ctx->pev[5], ctx->stream));
-        abandon(false);
-        m->retries_direct--;
-        return PART_OUTGREW;
+    // new distinct keys of this batch ~ 1024 x the sample keys it added (+ 4 sigma of that estimate + what the
+    // spill list holds, which the sample has seen too but the regions have not): room for them, and the fine level again
+    int size_table_from_sample(const Counters &c) {
+        const u64 claims = c.sample_claims - std::min<u64>(c.sample_claims, m->sample_claims_seen);
+        m->sample_claims_seen = c.sample_claims;
+        const bool saturated = c.sample_claims * 2 > m->sample_mask;          // the set is half full: stop trusting it
+        u64 est_new = saturated ? nkeys_bound : (u64)((double)claims * 1024.0 * 1.05 + 4.0 * std::sqrt((double)claims + 1.0) * 1024.0 + 4096.0);
+        est_new = std::min<u64>(est_new, nkeys_bound);
+        m->est_distinct_last = est_new;
+        if (!ctx->hook_no_reserve) {
+            // (error k-mers accumulate sub-linearly with the reads: 60 % of the proportional extrapolation)
+            const u64 ahead = (u64)((double)est_new * (1.0 + 0.6 * (std::max(plan.grow_ahead, 1.0) - 1.0)));
+            if (int rc = map_make_room(m, est_new, ahead, from_empty, true)) return rc;     // may replace the table (same lnb1: P2 has cut the batch by L1 bucket)
+        }
+        t = table();
+        // many repeats: segment sizes are far from binomial -> exact fine level
+        fine_exact = !ch.op1 || plan.fine_exact || (double)est_new < 0.5 * (double)nkeys_bound;
+        return GK_OK;
     }
-    if (!pipelined) { if (int rc = part_prepare_fine(m, ps, nkeys_bound, !fine_exact, &a)) return rc; }
-    const u64 nseg = t.nseg();
-    GK_HIP(ctx, hipEventRecord(ctx->gev, ctx->stream));
 
-    // ---- stage B: P3 + scans + P4 (the fine level) ---------------------------------------------------------
-    const u64 max_ranges = max_chunks / a.range_chunks + MAXB1 + 1;
-    const u64 *fine_keys = ps->bufB;
-    m->last_fine = fine_exact ? "exact" : "overprovisioned";
-    m->last_p4_pieces = pieces_run;
-    m->last_nb1 = nb1; m->last_nb2 = m->nb2;
-    // (last_p4: written by the branch that launches — launch_p4_op, or the exact level's below)
-    if (fine_exact) {
+    // ---- stage 3: P3 + scans + P4 (the exact fine level; the over-provisioned one's P4 goes out with its stripes) ----------------
+    int fine_level() {
+        m->last_fine = fine_exact ? "exact" : "overprovisioned";
+        m->last_p4_pieces = pieces_run;
+        m->last_nb1 = nb1; m->last_nb2 = m->nb2;
+        if (!fine_exact) return GK_OK;
+        const u64 max_ranges = max_chunks / a.range_chunks + MAXB1 + 1;
         const int gr = (int)std::min<u64>(max_ranges, (u64)ctx->cu_count * 4);
         hipLaunchKernelGGL(k_part_hist2r<W>, dim3(gr), dim3(PBLOCK), m->nb2 * 4, ctx->stream, ps->bufA, t, a, max_ranges);
         hipLaunchKernelGGL(k_part_scan2, dim3((m->nb2 + 255) / 256, nb1), dim3(256), 0, ctx->stream, a, m->nb2);
         hipLaunchKernelGGL(k_part_prefix2, dim3(nb1), dim3(256), 0, ctx->stream, a, nb1, m->nb2);
         GK_HIP(ctx, hipEventRecord(ctx->pev[3], ctx->stream));
-        // few keys per bin and chunk: straight scatter with per-range cursors; otherwise sort each chunk in LDS (coalesced runs)
-        // (measured at C3, nb2 = 1525: 67 ms against 52 ms for the sorted form — 8-byte stores to 64 different lines per
-        //  instruction leave L2 as partial-line writes; kept as an A/B option, never chosen by default)
-        const bool direct = ctx->hook_p4_direct > 0;
-        if (direct) {
-            m->last_p4 = "direct";
-            hipLaunchKernelGGL(k_part_scatter2_direct<W>, dim3((int)std::min<u64>(max_ranges, (u64)ctx->cu_count * 8)), dim3(PBLOCK), m->nb2 * 4,
-                               ctx->stream, ps->bufA, t, a, max_ranges, ps->bufB);
-        } else if (wide_fits() && (ctx->hook_p4_wide >= 0 ? ctx->hook_p4_wide != 0 : m->nb2 >= 512)) {
-            // many fine buckets: sort 8192 keys at a time (1024 threads) — twice the keys per bin and visit, so fewer
-            // partial-line writes, and half the per-bin bookkeeping per key
-            if constexpr (W == 1) {
-                const size_t wide_lds = ScatterLds<1, 1024>::bytes(m->nb2) + part_tables_bytes(nb1);
-                const int gw = (int)std::min<u64>(max_ranges, (u64)ctx->cu_count * 2);
-                // from ~1000 fine buckets up a 12288-key sort where it still fits the LDS (runs half again as long: "p4_wide" = 2 forces it)
-                const size_t xl_lds = ScatterLds<1, 1024, 12>::bytes(m->nb2) + part_tables_bytes(nb1);
-                const bool xl = xl_lds <= LDS_BYTES_PER_CU && (ctx->hook_p4_wide >= 0 ? ctx->hook_p4_wide == 2 : m->nb2 >= 1024);
-                m->last_p4 = xl ? "sort12288" : "sort8192";
-                if (xl) hipLaunchKernelGGL((k_part_scatter2<1, true, 1024, 12>), dim3(gw), dim3(1024), xl_lds, ctx->stream, ps->bufA, t, a, max_ranges, ps->bufB, 0u, nb1);
-                else hipLaunchKernelGGL((k_part_scatter2<1, true, 1024>), dim3(gw), dim3(1024), wide_lds, ctx->stream, ps->bufA, t, a, max_ranges, ps->bufB, 0u, nb1);
-            }
-        } else if (wide2_fits() && ctx->hook_p4_wide > 0) {
-            if constexpr (W == 2) {      // 16-byte keys: 6144-key sorts on 1024 threads — opt-in ("p4_wide" = 1): 1.00 / 0.94 -> 0.91 / 0.98 ms at k = 55, no clear gain
-                const size_t lds2 = ScatterLds<2, 1024, 6>::bytes(m->nb2) + part_tables_bytes(nb1);
-                const int gw = (int)std::min<u64>(max_ranges, (u64)ctx->cu_count * 2);
-                m->last_p4 = "sort6144";
-                hipLaunchKernelGGL((k_part_scatter2<2, true, 1024, 6>), dim3(gw), dim3(1024), lds2, ctx->stream, ps->bufA, t, a, max_ranges, ps->bufB, 0u, nb1);
-            }
-        } else {
-            m->last_p4 = "sort4096";
-            hipLaunchKernelGGL((k_part_scatter2<W, true, PBLOCK>), dim3(gr), dim3(PBLOCK), ScatterLds<W>::bytes(m->nb2) + part_tables_bytes(nb1), ctx->stream, ps->bufA, t, a,
-                               max_ranges, ps->bufB, 0u, nb1);
-        }
+        const P4Form *f = p4_choose_exact(W, m->nb2, nb1, ctx->hook_p4_wide, ctx->hook_p4_direct);      // (for the table as it is NOW)
+        launch_p4(f, true, a, ctx->stream, (int)std::min<u64>(max_ranges, (u64)ctx->cu_count * f->exact_wgs), max_ranges, 0u, nb1);
+        return GK_OK;
     }
-    auto launch_p5 = [&](hipStream_t st, u64 seg_lo, u64 seg_hi) {
+
+    // ---- stage 4: the segments (P5), beside the over-provisioned level's P4 when the batch is cut into stripes -----------------
+    void launch_p5(hipStream_t st, u64 seg_lo, u64 seg_hi) {
         const int gseg = (int)std::min<u64>(seg_hi - seg_lo, (u64)ctx->cu_count * GK_P5_GRID_PER_CU);
         if constexpr (W == 1) {
-            if (cslots) {
-                hipLaunchKernelGGL((k_seg_insert<1, CSlot>), dim3(gseg), dim3(SBLOCK), lds, st, Table<1, CSlot>{reinterpret_cast<CSlot *>(m->slots), t.nb2, t.lnb1, 0u, 0u}, fine_keys, a,
-                                   from_empty ? 1 : 0, m->d_ctr, seg_lo, seg_hi);
+            if (m->layout == LAYOUT_COUNT) {
+                hipLaunchKernelGGL((k_seg_insert<1, CSlot>), dim3(gseg), dim3(SBLOCK), SEG_LDS, st, Table<1, CSlot>{reinterpret_cast<CSlot *>(m->slots), t.nb2, t.lnb1, 0u, 0u},
+                                   ps->bufB, a, from_empty ? 1 : 0, m->d_ctr, seg_lo, seg_hi);
                 return;
             }
         }
-        hipLaunchKernelGGL((k_seg_insert<W, Slot<W>>), dim3(gseg), dim3(SBLOCK), lds, st, t, fine_keys, a, from_empty ? 1 : 0, m->d_ctr, seg_lo, seg_hi);
-    };
-    // Stripes (over-provisioned fine level): P4 is bound by its LDS sort and leaves half the memory system idle, P5 streams
-    // the table and leaves the ALUs idle.  With the L1 buckets cut into stripes, P5 of stripe i runs on the second stream
-    // beside P4 of stripe i+1 (option "p45_stripes": 1 = one after the other).
-    int stripes = fine_exact ? 1 : std::max(1, std::min<int>({ctx->hook_p45_stripes > 0 ? ctx->hook_p45_stripes : 1, (int)nb1, 16}));
-    while (nb1 % (u64)stripes) stripes--;
-    m->last_p4_stripes = stripes;
-    if (pipelined && !have_last) return fail(ctx, GK_E_STATE, "partitioned insert: a pipelined batch ended without its last piece");
-    if (pipelined) {
-        // the earlier pieces' P4 (second stream) join here; the last piece's runs on this stream
-        GK_HIP(ctx, hipEventRecord(ctx->gev2, ctx->aux_stream));
-        GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->gev2, 0));
-        GK_HIP(ctx, hipEventRecord(ctx->pev[3], ctx->stream));
-        launch_p4_op(a_last, ctx->stream, 0u, (u32)nb1, 1);
-    } else if (!fine_exact && stripes == 1) {
-        GK_HIP(ctx, hipEventRecord(ctx->pev[3], ctx->stream));
-        launch_p4_op(a, ctx->stream, 0u, (u32)nb1, 1);
+        hipLaunchKernelGGL((k_seg_insert<W, Slot<W>>), dim3(gseg), dim3(SBLOCK), SEG_LDS, st, t, ps->bufB, a, from_empty ? 1 : 0, m->d_ctr, seg_lo, seg_hi);
     }
-    if (stripes == 1) {
-        GK_HIP(ctx, hipGetLastError());
-        GK_HIP(ctx, hipEventRecord(ctx->pev[4], ctx->stream));
-        // ---- P5 --------------------------------------------------------------------------------------------
-        launch_p5(ctx->stream, 0, nseg);
-        GK_HIP(ctx, hipGetLastError());
-        GK_HIP(ctx, hipEventRecord(ctx->pev[5], ctx->stream));
-    } else {
+    int build_segments() {
+        const int stripes = fine_exact ? 1 : ch.op_stripes;
+        m->last_p4_stripes = stripes;
+        if (ch.pipelined && !have_last) return fail(ctx, GK_E_STATE, "partitioned insert: a pipelined batch ended without its last piece");
+        if (ch.pipelined) {
+            // the earlier pieces' P4 (second stream) join here; the last piece's runs on this stream
+            GK_HIP(ctx, hipEventRecord(ctx->gev2, ctx->aux_stream));
+            GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->gev2, 0));
+            GK_HIP(ctx, hipEventRecord(ctx->pev[3], ctx->stream));
+            launch_p4_op(a_last, ctx->stream, 0u, nb1, 1);
+        } else if (!fine_exact && stripes == 1) {
+            GK_HIP(ctx, hipEventRecord(ctx->pev[3], ctx->stream));
+            launch_p4_op(a, ctx->stream, 0u, nb1, 1);
+        }
+        if (stripes == 1) {
+            GK_HIP(ctx, hipGetLastError());
+            GK_HIP(ctx, hipEventRecord(ctx->pev[4], ctx->stream));
+            launch_p5(ctx->stream, 0, t.nseg());
+            GK_HIP(ctx, hipGetLastError());
+            GK_HIP(ctx, hipEventRecord(ctx->pev[5], ctx->stream));
+            return GK_OK;
+        }
         // (phase events: [3,4] = the P4 launches with the overlapped P5s beside them, [4,5] = what is left of P5 after the last P4)
         GK_HIP(ctx, hipEventRecord(ctx->pev[3], ctx->stream));
-        const u32 per = (u32)(nb1 / (u64)stripes);
+        const u32 per = nb1 / (u32)stripes;
         for (int s = 0; s < stripes; s++) {
             launch_p4_op(a, ctx->stream, s * per, (s + 1) * per, (u64)stripes);
             GK_HIP(ctx, hipGetLastError());
@@ -1829,35 +1897,37 @@ static int part_run(gk_map *m, PartScratch *ps, const ReadSrc &src, const u64 *d
         GK_HIP(ctx, hipEventRecord(ctx->gev2, ctx->copy_stream));
         GK_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->gev2, 0));
         GK_HIP(ctx, hipEventRecord(ctx->pev[5], ctx->stream));
+        return GK_OK;
     }
+
+    // ---- stage 5: the finish -------------------------------------------------------------------------------------------------------
     // the spill list may also have grown in P4 (over-provisioned fine level): read it (again) behind P5
-    // failures (a segment filled up): grow, then replay those buckets through the direct path
-    if (int rc = request_status()) return rc;
-    if (src.verify_uniform && !sync_between) {                 // the deferred check of an optimistic uniform stream
-        Counters *hc = reinterpret_cast<Counters *>(m->h_status);
-        GK_HIP(ctx, hipMemcpyAsync(hc, m->d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, ctx->stream));
-        GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (hc->format) {
-            GK_HIP(ctx, hipMemsetAsync(&m->d_ctr->format, 0, sizeof(u32), ctx->stream));
-            abandon(true);
-            m->retries_direct--;
-            return PART_NOT_UNIFORM;
+    int finish() {
+        if (int rc = request_status()) return rc;
+        if (src.verify_uniform && !ch.sync_between) {                 // the deferred check of an optimistic uniform stream
+            Counters c;
+            if (int rc = read_counters(&c)) return rc;
+            if (c.format) return give_back(PART_NOT_UNIFORM, true);
         }
+        if (int rc = map_sync_counters(m)) return rc;              // (one stream sync for both copies)
+        const unsigned long long nspill = h_st->nspill;
+        const u32 n_failed = h_st->n_failed;
+        if (h_st->overflow) {
+            if (from_empty) return give_back(PART_RETRY_DIRECT, true);
+            // P4's regions overflowed into a full spill list while the table held data: the keys that did not fit are lost
+            // to this pipeline but P5 has already merged the rest.  Cannot happen with the exact fine level; the
+            // over-provisioned one is only chosen for a table that holds data when the batch is known to be near-distinct.
+            return fail(ctx, GK_E_STATE, "partitioned insert: spill list overflowed behind a non-empty table (internal sizing error)");
+        }
+        m->failed_segments += n_failed;
+        m->spilled_keys += nspill;
+        if (!fine_exact && nspill > nkeys_bound / 64) m->repeats = true;       // regions sized for distinct keys are the wrong tool for this data
+        if (n_failed) { if (int rc = replay_failed(n_failed)) return rc; }
+        return nspill ? map_add_keys_direct(m, ps->spill, nspill) : GK_OK;
     }
-    if (int rc = map_sync_counters(m)) return rc;              // (one stream sync for both copies)
-    nspill = h_st->nspill; ovf = h_st->overflow;
-    const u32 n_failed = h_st->n_failed;
-    if (ovf) {
-        if (from_empty) return abandon(true);
-        // P4's regions overflowed into a full spill list while the table held data: the keys that did not fit are lost
-        // to this pipeline but P5 has already merged the rest.  Cannot happen with the exact fine level; the
-        // over-provisioned one is only chosen for a table that holds data when the batch is known to be near-distinct.
-        return fail(ctx, GK_E_STATE, "partitioned insert: spill list overflowed behind a non-empty table (internal sizing error)");
-    }
-    m->failed_segments += n_failed;
-    m->spilled_keys += nspill;
-    if (!fine_exact && nspill > nkeys_bound / 64) m->repeats = true;       // regions sized for distinct keys are the wrong tool for this data
-    if (n_failed) {
+    // failures (a segment filled up): grow, then replay those segments' keys through the direct path
+    int replay_failed(u32 n_failed) {
+        const u64 nseg = t.nseg();
         std::vector<u32> failed(n_failed);
         GK_HIP(ctx, hipMemcpy(failed.data(), a.failed, n_failed * 4ull, hipMemcpyDeviceToHost));
         std::vector<unsigned long long> fb;
@@ -1870,13 +1940,24 @@ static int part_run(gk_map *m, PartScratch *ps, const ReadSrc &src, const u64 *d
         for (u32 s : failed) total += seg_count(s);
         if (int rc = map_reserve(m, std::max<u64>(std::min<u64>(total, m->capacity), m->capacity / 2))) return rc;
         for (u32 s : failed) {
-            if (int rc = map_add_keys_direct(m, fine_keys + seg_begin(s) * m->W, seg_count(s))) return rc;
+            if (int rc = map_add_keys_direct(m, ps->bufB + seg_begin(s) * m->W, seg_count(s))) return rc;
         }
+        return GK_OK;
     }
-    if (nspill) {
-        if (int rc = map_add_keys_direct(m, ps->spill, nspill)) return rc;
-    }
-    return GK_OK;
+};
+
+// returns GK_OK, an error (< 0), or that the batch was given back (PartBatch::give_back): PART_RETRY_DIRECT, PART_NOT_UNIFORM,
+// PART_OUTGREW — nothing but scratch, or a table that was being rebuilt from empty, was touched
+template <int W>
+static int part_run(gk_map *m, PartScratch *ps, const ReadSrc &src, const u64 *d_keys, u64 nkeys_in, u64 nkeys_bound, bool from_empty,
+                    const PartPlan &plan) {
+    PartBatch<W> b(m, ps, src, d_keys, nkeys_in, nkeys_bound, from_empty, plan);
+    if (int rc = b.prepare()) return rc;
+    if (int rc = b.l1_level()) return rc;
+    if (int rc = b.between_levels()) return rc;
+    if (int rc = b.fine_level()) return rc;
+    if (int rc = b.build_segments()) return rc;
+    return b.finish();
 }
 
 int part_count(gk_map *m, PartScratch **pps, const ReadSrc &src, const u64 *d_keys, u64 nkeys_in, u64 nkeys_bound, bool from_empty,
@@ -1886,13 +1967,5 @@ int part_count(gk_map *m, PartScratch **pps, const ReadSrc &src, const u64 *d_ke
     return part_run<2>(m, *pps, src, d_keys, nkeys_in, nkeys_bound, from_empty, plan);
 }
 
-// the fine level's 4096-key sort must fit the CU's LDS beside its per-bin arrays and the L1 tables (16-byte keys with 1024 L1
-// buckets: ~3500 fine buckets, a 117 GB table)
-bool part_supported(const gk_map *m) {
-    if (m->nb2 > (m->ctx->hook_max_nb2 > 0 ? (u32)m->ctx->hook_max_nb2 : MAX_NB2)) return false;
-    const size_t need = (m->W == 1 ? ScatterLds<1>::bytes(m->nb2) : ScatterLds<2>::bytes(m->nb2)) + part_tables_bytes(1u << m->lnb1);
-    return need <= LDS_BYTES_PER_CU;
-}
-uint64_t part_max_slots(int W) { return ((u64)MAX_NB2 << MAX_LNB1) << seg_bits_for(W); }
-
 }  // namespace gk
+

@@ -2,6 +2,7 @@
 //   * gk_ctx_set_option and the environment switches read at gk_ctx_create: A/B switches of the kernels, test hooks that stage
 //     the large-table paths on small tables or inject failures;
 //   * gk_test_grid_cap_uses: how many launches "test_max_grid" has sized on a context (the switch's echo);
+//   * gk_test_part_plan: what the partitioned insert would choose for a table geometry and a set of switches (part_choose's echo, no device);
 //   * gk_test_support_last_walk: which walker (device kernel / host fallback) did the orientations of the last gk_graph_walk_pairs;
 //   * gk_dist_create_loopback: a transport whose ranks are threads of ONE process on ONE device, so that gk_dist_* runs with
 //     world > 1 on a one-GPU box (RCCL refuses two ranks on one device).
@@ -95,6 +96,30 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
 int gk_test_grid_cap_uses(const gk_ctx *ctx, uint64_t *uses) {
     if (!ctx || !uses) return fail(ctx, GK_E_INVALID, "gk_test_grid_cap_uses: null argument");
     *uses = ctx->hook_max_grid_uses;
+    return GK_OK;
+}
+
+int gk_test_part_plan(const gk_test_part_in *in, gk_test_part_out *out) {
+    if (!in || !out) return fail(nullptr, GK_E_INVALID, "gk_test_part_plan: null argument");
+    if ((in->W != 1 && in->W != 2) || in->lnb1 < 0 || in->lnb1 > (int)gk::MAX_LNB1 || in->source < PART_SRC_DEVICE || in->source > PART_SRC_KEYS)
+        return fail(nullptr, GK_E_INVALID, "gk_test_part_plan: W 1 / 2, lnb1 0..10, source 0..4");
+    PartInput pi;
+    pi.W = in->W; pi.lnb1 = in->lnb1; pi.nb2 = in->nb2; pi.source = in->source; pi.max_windows = in->max_windows;
+    pi.from_empty = in->from_empty != 0; pi.verify_uniform = in->verify_uniform != 0; pi.estimate = in->estimate != 0; pi.fine_exact = in->fine_exact != 0;
+    pi.part_exact = in->part_exact != 0;
+    pi.p4_wide = in->p4_wide; pi.p4_direct = in->p4_direct; pi.p2_wide = in->p2_wide; pi.p2_sorted = in->p2_sorted;
+    pi.p45_stripes = in->p45_stripes; pi.p24_pieces = in->p24_pieces; pi.p4_grid = in->p4_grid; pi.max_nb2 = in->test_max_nb2;
+    const PartChoice c = part_choose(pi);
+    memset(out, 0, sizeof *out);
+    auto echo = [&](const P4Form *f, gk_test_part_form *o) {
+        strncpy(o->name, f->name, sizeof o->name - 1);
+        o->chunk_keys = f->chunk_keys(); o->threads = (uint32_t)f->threads; o->lds_bytes = f->lds(in->nb2, 1u << in->lnb1);
+    };
+    echo(c.p4_op, &out->p4_op);
+    echo(c.p4_exact, &out->p4_exact);
+    strncpy(out->p2, c.p2, sizeof out->p2 - 1);
+    out->supported = c.supported; out->op1 = c.op1; out->fine_exact = c.fine_exact; out->sync_between = c.sync_between; out->pipelined = c.pipelined;
+    out->stripes = c.fine_exact ? 1 : c.op_stripes;
     return GK_OK;
 }
 

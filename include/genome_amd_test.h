@@ -54,6 +54,33 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value);
  * switch is 0).  A call that is meant to run under the cap and leaves the number as it was did not consult it. */
 int gk_test_grid_cap_uses(const gk_ctx *ctx, uint64_t *uses);
 
+/* What one batch of the partitioned insert would choose (gk_partition.hip: part_choose, the function part_run takes every choice
+ * from), for plain values instead of a context and a map: no device is touched, and the call works on a machine without one.  So
+ * the auto rules of tables far too large for a test — which member of P4's family from how many fine buckets per L1 bucket, and
+ * what still fits the CU's LDS — are held to literals by tests/test_part_plan_cpu.py.
+ * in: W (1 / 2 key words), lnb1 (0..10) and nb2 (the table's geometry); source (0 device records of one length, 1 the same in
+ * host memory, 2 the same prefetched, 3 a ragged stream, 4 keys) and max_windows (windows of the longest record; 0 for ragged
+ * streams and keys); from_empty, estimate and fine_exact (PartPlan's: the "fine_exact" switch arrives through it),
+ * verify_uniform; the switches "part_exact", "p4_wide", "p4_direct", "p2_wide", "p2_sorted", "p45_stripes", "p24_pieces", "p4_grid"
+ * and "test_max_nb2" as gk_ctx_set_option takes them (-1 auto; 0 for the two test switches).
+ * out: P4's member on the over-provisioned and on the exact fine level — its "last_p4" name, keys per chunk, threads, dynamic
+ * LDS bytes for this geometry —, the "last_p2" name, part_supported, the batch's first choices (op1, fine_exact — which the
+ * sample may revise between the levels —, sync_between, pipelined) and the stripes of the level it starts with (1 when exact).
+ * GK_E_INVALID for a null pointer, W, lnb1 or source out of range. */
+typedef struct gk_test_part_in {
+    int32_t W, lnb1;
+    uint32_t nb2;
+    int32_t source, max_windows, from_empty, estimate, fine_exact, verify_uniform;
+    int32_t part_exact, p4_wide, p4_direct, p2_wide, p2_sorted, p45_stripes, p24_pieces, p4_grid, test_max_nb2;
+} gk_test_part_in;
+typedef struct gk_test_part_form { char name[16]; uint32_t chunk_keys, threads; uint64_t lds_bytes; } gk_test_part_form;
+typedef struct gk_test_part_out {
+    gk_test_part_form p4_op, p4_exact;
+    char p2[16];
+    int32_t supported, op1, fine_exact, sync_between, pipelined, stripes;
+} gk_test_part_out;
+int gk_test_part_plan(const gk_test_part_in *in, gk_test_part_out *out);
+
 /* Which walker produced the last gk_graph_walk_pairs into `s`: *orientations = pair orientations handed to the walk stage (two per
  * pair whose mates both hold k bases), *overflowed = those of them whose sets outgrew the wave's LDS on the device and were walked
  * by the host walker instead (0 under "pairs_host" = 1, where the host walks all of them by choice).  Two host integers the call

@@ -10,12 +10,12 @@ Every forced option lives inside `with forced(ctx, ...)`, which restores the def
 
 Pairs that cannot run anywhere (by the code, not by choice):
   * p4_wide = 1 with 16-byte keys never sorts 8192 keys: the 16-byte family has ONE 1024-thread member, 6144 keys
-    (gk_partition.hip op_chunk_keys: `if (W == 2) return 6144u`, and the exact level's `wide2_fits() && hook_p4_wide > 0`
-    branch); p4_wide = 1 and 2 are both asserted as "sort6144" there.
-  * p2_wide = 1 under min_lnb1 = 9 / 10: the 1024-bucket L1 scatter has no 1024-thread member (launch_p2: `if (nb1 > 256)`
-    comes first); asserted as "plain" / "sorted".
-  * p45_stripes, p4_grid, p24_pieces on the exact fine level: stripes are `fine_exact ? 1 : ...`, pieces need `!fine_exact`, and
-    only launch_p4_op reads p4_grid; they are run with fine_exact = 0 and asserted on batches that stayed over-provisioned.
+    (gk_partition.hip P4_FORMS; p4_choose_op and p4_choose_exact take "sort12288" for `W == 1` only); p4_wide = 1 and 2 are
+    both asserted as "sort6144" there.
+  * p2_wide = 1 under min_lnb1 = 9 / 10: the 1024-bucket L1 scatter has no 1024-thread member (part_choose: p2_threads is
+    1024 only for `nb1 <= 256`); asserted as "plain" / "sorted".
+  * p45_stripes, p4_grid, p24_pieces on the exact fine level: stripes are `fine_exact ? 1 : ch.op_stripes`, pieces need `!fine_exact`,
+    and only PartBatch::launch_p4_op reads p4_grid (p4_per_cu); they are run with fine_exact = 0 and asserted on batches that stayed over-provisioned.
   * target_load_pct at k = 64: target_load() returns 0.45 for the tagged table before it looks at the switch; asserted as
     "no change of slots()".  graph_load_pct at k = 64 is capped at the tagged table's densest step, 45 (graph_table_load).
   * filter_classic = 0 at k = 64: filter_compact_streaming refuses tagged slots; asserted as "classic".
@@ -257,7 +257,7 @@ def _step(m, feed, opts, batch, want_table, from_empty, fits, total_occ=None):
     st1 = m.stats()
     if st1["retries_direct"] > st0["retries_direct"]:
         # the one legitimate other route: over-provisioned regions AND the spill list overflowed on repeat-heavy input, the batch
-        # was taken again by the direct path (part_run: abandon).  Only forced over-provisioning on the small genome gets there.
+        # was taken again by the direct path (PartBatch::give_back).  Only forced over-provisioning on the small genome gets there.
         assert opts.get("fine_exact", -1) != 1 and kind in ("G", "hostG", "keys"), (opts, kind, st1)
         assert st1["direct_launches"] > st0["direct_launches"] and st1["last_fine"] == "overprovisioned"
     else:
