@@ -162,6 +162,8 @@ int graph_grow_nodes(gk_graph *g, u64 new_cap);
 // the node / edge arrays of a graph without any (ids 0..n-1, none alive, out_edge NONE, out_order / in_deg 0): the build and gk_graph_load
 int graph_alloc_nodes(gk_graph *g, u64 n);
 int graph_alloc_edges(gk_graph *g, u64 n);
+// gk_graph.hip: the pointer-jumping build's slot -> rank structure of a map's table, copied to the host (gk_test_slot_ranks)
+int graph_slot_ranks(gk_map *m, uint64_t *masks, uint64_t *bases, uint64_t cap_blocks, uint64_t *nblk, uint64_t *total);
 // Node.inEdgeIds as CSR by end node of the graph as it is now: (*off)[v] .. (*off)[v+1] index *list; both live in `tmp`.
 // Stream-ordered, no synchronisation; `who` names the entry point in the error text.  (Not exported, like DevScratch.)
 __attribute__((visibility("hidden"))) int graph_in_lists(gk_graph *g, DevScratch &tmp, const char *who, unsigned long long **off, u32 **list);

@@ -676,6 +676,13 @@ __global__ __launch_bounds__(RANK_CHUNK) void k_rank_fill(RankBlk *rb, u64 nblk,
         if (blk < nblk) rb[blk].base = chunk_base[c] + pre + inc - v;
     }
 }
+// the slot -> rank structure of table `t`: rb[0..nblk), chunk_base[nchunks] = the live slots.  Stream-ordered, no sync.
+template <int W, class TT>
+static void rank_build(gk_ctx *ctx, TT t, RankBlk *rb, u64 nblk, u32 *chunk_tot, u64 *chunk_base, u64 nchunks) {
+    hipLaunchKernelGGL((k_rank_masks<W, TT>), dim3((int)std::min<u64>(nchunks, grid_cap(ctx))), dim3(BLOCK), 0, ctx->stream, t, rb, nblk, chunk_tot, nchunks);
+    hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, ctx->stream, chunk_tot, chunk_base, nchunks);
+    hipLaunchKernelGGL(k_rank_fill, dim3((int)std::min<u64>(nchunks, grid_cap(ctx))), dim3(RANK_CHUNK), 0, ctx->stream, rb, nblk, chunk_base, nchunks);
+}
 
 // ---- pointer-jumping state: ONE 64-bit word per oriented live k-mer (index 2 x rank + orientation), updated IN PLACE -------
 //   absorbed (the successor is a terminal k-mer):  PJ_ABS | first base of this oriented k-mer << 32 | node id of that terminal
@@ -902,9 +909,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
             if (e == hipSuccess) e = tmp.get(&st, nstates);
             if (e == hipSuccess) e = hipMemsetAsync(st, 0xff, std::max<u64>(nstates, 1) * 8, ctx->stream);         // PJ_UNREG
             if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: pointer-jumping arrays");
-            hipLaunchKernelGGL((k_rank_masks<W, TT>), dim3((int)std::min<u64>(nchunks, grid_cap(ctx))), dim3(BLOCK), 0, ctx->stream, t, rb, nblk, chunk_tot, nchunks);
-            hipLaunchKernelGGL(k_rank_scan, dim3(1), dim3(1024), 0, ctx->stream, chunk_tot, chunk_base, nchunks);
-            hipLaunchKernelGGL(k_rank_fill, dim3((int)std::min<u64>(nchunks, grid_cap(ctx))), dim3(RANK_CHUNK), 0, ctx->stream, rb, nblk, chunk_base, nchunks);
+            rank_build<W, TT>(ctx, t, rb, nblk, chunk_tot, chunk_base, nchunks);
             unsigned long long ranked = 0;
             if ((e = read_back(ctx, &ranked, chunk_base + nchunks)) != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: slot ranks");
             if (ranked != m->size) return fail(ctx, GK_E_STATE, "live slots (" + std::to_string(ranked) + ") differ from the map's size (" + std::to_string(m->size) + ")");
@@ -1075,6 +1080,38 @@ template <int W> static int graph_build_entry(gk_map *m, gk_graph *g, bool masks
     g->mbt_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     g->mbt_slots = total;
     return graph_build_impl<W, MbTable<W>>(m, g, mt);
+}
+
+// The rank structure of a map's own table on the host (the test build's gk_test_slot_ranks; nothing in the product calls it):
+// the table is brought into the graph layout the way gk_graph_build does, rank_build runs on it as in the build, and the
+// (mask, base) pairs and chunk_base[nchunks] come back.  *nblk is set before the capacity check.
+int graph_slot_ranks(gk_map *m, uint64_t *masks, uint64_t *bases, uint64_t cap_blocks, uint64_t *nblk_out, uint64_t *total) {
+    gk_ctx *ctx = m->ctx;
+    GK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = map_materialize(m)) return rc;
+    if (int rc = map_to_graph_layout(m)) return rc;
+    const u64 nblk = (m->capacity + 63) / 64, nchunks = (nblk + RANK_CHUNK - 1) / RANK_CHUNK;
+    *nblk_out = nblk;
+    if (nblk > cap_blocks) return fail(ctx, GK_E_CAPACITY, "slot ranks: " + std::to_string(nblk) + " blocks, room for " + std::to_string(cap_blocks));
+    DevScratch tmp(ctx);
+    RankBlk *rb = nullptr;
+    u32 *chunk_tot = nullptr;
+    u64 *chunk_base = nullptr;
+    tmp.get(&rb, nblk);
+    tmp.get(&chunk_tot, nchunks);
+    tmp.get(&chunk_base, nchunks + 1);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "slot ranks: alloc");
+    GK_BY_W(m->W, {
+        Table<W> t{reinterpret_cast<Slot<W> *>(m->slots), m->nb2, m->lnb1, m->k == 64 ? 1u : 0u, m->dirty ? 1u : 0u};
+        rank_build<W, Table<W>>(ctx, t, rb, nblk, chunk_tot, chunk_base, nchunks);
+    });
+    std::vector<RankBlk> h(nblk);
+    unsigned long long ranked = 0;
+    const hipError_t e = read_back(ctx, {{h.data(), rb, nblk * sizeof(RankBlk)}, {&ranked, chunk_base + nchunks, 8}});
+    if (e != hipSuccess) return hip_fail(ctx, e, "slot ranks");
+    for (u64 i = 0; i < nblk; i++) { masks[i] = h[i].mask; bases[i] = h[i].base; }
+    *total = ranked;
+    return GK_OK;
 }
 
 extern "C" {

@@ -4,6 +4,8 @@
 //   * gk_test_grid_cap_uses: how many launches "test_max_grid" has sized on a context (the switch's echo);
 //   * gk_test_part_plan: what the partitioned insert would choose for a table geometry and a set of switches (part_choose's echo, no device);
 //   * gk_test_support_last_walk: which walker (device kernel / host fallback) did the orientations of the last gk_graph_walk_pairs;
+//   * gk_test_scan_counts: gk_scan.h's scan_counts over counts from the host, between guard words (either overload);
+//   * gk_test_slot_ranks: the pointer-jumping build's slot -> rank structure of a map's table (gk_graph.hip: rank_build);
 //   * gk_dist_create_loopback: a transport whose ranks are threads of ONE process on ONE device, so that gk_dist_* runs with
 //     world > 1 on a one-GPU box (RCCL refuses two ranks on one device).
 // The product library (libgenome_amd.so) links none of this; its header is include/genome_amd.h, this file's is
@@ -20,6 +22,8 @@
 #include <vector>
 
 #include "gk_dist.h"
+#include "gk_graph.h"
+#include "gk_scan.h"
 #include "gk_support.h"
 #include "../../include/genome_amd_test.h"
 
@@ -128,6 +132,46 @@ int gk_test_support_last_walk(const gk_support *s, uint64_t *orientations, uint6
     if (orientations) *orientations = s->last_orientations;
     if (overflowed) *overflowed = s->last_overflow;
     return GK_OK;
+}
+
+// d_out (n + 1 words) and d_sums (exactly n / SCAN_CHUNK + 2 words) each lie between two guards of SCAN_GUARD words inside one
+// allocation of their own, and the whole allocation starts as 0xA5 bytes: a word of the result the scan did not write shows in
+// the comparison, a write beside the result in *guard_hits.
+static constexpr u64 SCAN_GUARD = 64, SCAN_FILL = 0xA5A5A5A5A5A5A5A5ull;
+int gk_test_scan_counts(gk_ctx *ctx, const uint32_t *in_host, uint64_t n, int via_scratch, uint64_t *out_host, uint64_t *guard_hits) {
+    if (!ctx || !out_host || !guard_hits || (n && !in_host)) return fail(ctx, GK_E_INVALID, "gk_test_scan_counts: null argument");
+    GK_HIP(ctx, hipSetDevice(ctx->device));
+    const u64 nsums = n / SCAN_CHUNK + 2, out_words = n + 1 + 2 * SCAN_GUARD, sums_words = nsums + 2 * SCAN_GUARD;
+    DevScratch tmp(ctx);
+    u32 *d_in = nullptr;
+    u64 *out_blk = nullptr, *sums_blk = nullptr;
+    if (n) tmp.upload(&d_in, in_host, n);
+    tmp.get(&out_blk, out_words);
+    if (!via_scratch) tmp.get(&sums_blk, sums_words);
+    if (tmp.error() == hipSuccess) tmp.note(hipMemsetAsync(out_blk, 0xA5, out_words * 8, ctx->stream));
+    if (tmp.error() == hipSuccess && sums_blk) tmp.note(hipMemsetAsync(sums_blk, 0xA5, sums_words * 8, ctx->stream));
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_test_scan_counts: buffers");
+    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(out_blk + SCAN_GUARD);
+    const hipError_t es = via_scratch ? scan_counts(ctx, tmp, d_in, n, d_out) : scan_counts(ctx, d_in, n, d_out, sums_blk + SCAN_GUARD);
+    if (es != hipSuccess) return hip_fail(ctx, es, "gk_test_scan_counts: scan");
+    u64 guards[4 * SCAN_GUARD];
+    for (u64 &g : guards) g = SCAN_FILL;          // (the two of d_sums stay so under via_scratch)
+    const size_t gb = SCAN_GUARD * 8;
+    const u64 *sums_hi = sums_blk ? sums_blk + SCAN_GUARD + nsums : nullptr;
+    const hipError_t e = read_back(ctx, {{out_host, d_out, (n + 1) * 8}, {guards, out_blk, gb}, {guards + SCAN_GUARD, out_blk + SCAN_GUARD + n + 1, gb},
+                                         {sums_blk ? guards + 2 * SCAN_GUARD : nullptr, sums_blk, gb},
+                                         {sums_hi ? guards + 3 * SCAN_GUARD : nullptr, sums_hi, gb}});
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_test_scan_counts: read back");
+    u64 hits = 0;
+    for (u64 g : guards) hits += g != SCAN_FILL;
+    *guard_hits = hits;
+    return GK_OK;
+}
+
+int gk_test_slot_ranks(gk_map *map, uint64_t *masks, uint64_t *bases, uint64_t cap_blocks, uint64_t *nblk, uint64_t *total) {
+    if (!map || !map->ctx) return fail(nullptr, GK_E_INVALID, "gk_test_slot_ranks: null map handle");
+    if (!masks || !bases || !nblk || !total) return fail(map->ctx, GK_E_INVALID, "gk_test_slot_ranks: null argument");
+    return graph_slot_ranks(map, masks, bases, cap_blocks, nblk, total);
 }
 
 }  // extern "C"

@@ -87,6 +87,23 @@ int gk_test_part_plan(const gk_test_part_in *in, gk_test_part_out *out);
  * leaves in the support; either pointer may be null.  A call that cut no pair leaves (0, 0). */
 int gk_test_support_last_walk(const gk_support *s, uint64_t *orientations, uint64_t *overflowed);
 
+/* The device scan every offset list of the library comes from (csrc/gk_scan.h: scan_counts, u32 counts in, u64 offsets out), run
+ * on its own: in_host[0..n) is uploaded, out_host[0..n] receives the exclusive prefix sums and out_host[n] the total.
+ * via_scratch = 0 takes the overload with the caller's scratch, sized to exactly the n / 4096 + 2 words callers give it;
+ * via_scratch = 1 the overload that takes its scratch from the call's temporaries.  The result — and with via_scratch = 0 the
+ * scratch — lies between guard regions of 64 words, before and after, and every word of the result starts as the guards'
+ * pattern: *guard_hits = the guard words the scan changed (0 unless it wrote out of bounds; the second overload's own scratch
+ * cannot be guarded).  n = 0 is legal (out_host[0] = 0, in_host may be null); any other null pointer is GK_E_INVALID. */
+int gk_test_scan_counts(gk_ctx *ctx, const uint32_t *in_host, uint64_t n, int via_scratch, uint64_t *out_host, uint64_t *guard_hits);
+
+/* The slot -> rank structure the pointer-jumping unitig build makes of a table (csrc/gk_graph.hip: k_rank_masks, k_rank_scan,
+ * k_rank_fill, by the same function the build calls): for every block of 64 slots, masks[b] = its live slots and bases[b] = the
+ * live slots before it; *total = the live slots the scan counted; *nblk = the blocks, ceil(slots / 64).  The graph phase only
+ * ever reads the graph layout, so a count table of 8-byte keys is rebuilt into it first, exactly as gk_graph_build does (the
+ * slot count stays unless the table is too dense for the graph phase); the map is otherwise unchanged and no graph is built.
+ * GK_E_CAPACITY, with *nblk set and nothing copied, when cap_blocks < *nblk; GK_E_INVALID for a null pointer. */
+int gk_test_slot_ranks(gk_map *map, uint64_t *masks, uint64_t *bases, uint64_t cap_blocks, uint64_t *nblk, uint64_t *total);
+
 /* TEST transport: the ranks are threads of ONE process on ONE device; sends, receives and reductions go through a hub in the
  * library (device-to-device copies matched pairwise in posting order) instead of RCCL, which refuses two ranks on one GPU.  Every
  * rank passes the same 128 id bytes (any) and its own context; calls block until the peers have posted the matching operation
