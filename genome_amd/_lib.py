@@ -160,6 +160,14 @@ SIGNATURES = {
     "gk_graph_pair_distances": (C.c_int, [vp, vp, u8p, C.c_size_t, C.c_uint64, C.c_uint32, u64p, u64p]),
     "gk_insert_range": (C.c_int, [u64p, C.c_uint32, C.c_uint32, C.c_uint64, u32p, u32p, u32p]),
     "gk_dist_pair_distances": (C.c_int, [vp, vp, vp, u8p, C.c_size_t, C.c_uint64, C.c_uint32, u64p, u64p]),
+    "gk_links_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "gk_links_destroy": (None, [vp]),
+    "gk_graph_pair_links": (C.c_int, [vp, vp, vp, u8p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64, u64p]),
+    "gk_links_size": (C.c_int, [vp, u64p, u64p]),
+    "gk_links_export": (C.c_int, [vp, u32p, u32p, u32p, u64p, C.c_uint64, u64p]),
+    "gk_links_add": (C.c_int, [vp, u32p, u32p, u32p, u64p, C.c_uint64]),
+    "gk_links_joins": (C.c_int, [vp, C.c_uint32, u32p, u32p, u32p, u64p, C.c_uint64, u64p, u64p]),
+    "gk_scaffold_chains": (C.c_int, [u32p, u32p, C.c_uint64, u32p, C.c_uint64, u64p, C.c_uint64, u64p, u64p]),
     "gk_graph_replace_end": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
     "gk_graph_build": (C.c_int, [vp, C.POINTER(vp)]),
     "gk_graph_destroy": (None, [vp]),

@@ -246,6 +246,21 @@ class HipGraph:
                                                 L.ptr(hist, C.c_uint64), L.ptr(cls, C.c_uint64)), self.ctx.h)
         return hist, dict(zip(PAIR_CLASSES, (int(x) for x in cls)))
 
+    def pairLinks(self, positions, data, links: "HipLinks", min_len: int = 0, max_span: int = 4095, take_first=None) -> dict:
+        """The pairs whose mates' first k-mers lie on two DIFFERENT edges (the rule: include/genome_amd.h, "scaffold links"), added
+        to `links` as (e, f) -> count and sum_u -> {class: orientations} over LINK_CLASSES.  Edges whose contig is shorter than
+        `min_len` bases link nothing; a fragment that needs more than `max_span` bases on the two edges is too_far (the tools pass
+        the insert range's upper end + k).  `data`: a PairedEndData (its first `take_first` pairs), or (bin bytes, npairs).
+        GkError, and `links` unchanged, on any error; the graph and `positions` never change."""
+        bin_bytes, npairs = (data.bin, data.count) if hasattr(data, "bin") else data
+        if take_first is not None:
+            npairs = max(0, min(int(take_first), npairs))
+        buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)
+        cls = np.zeros(len(LINK_CLASSES), np.uint64)
+        L.check(L.lib().gk_graph_pair_links(self.h, positions.h, links.h, L.ptr(buf, C.c_uint8) if buf.size else None, buf.size, npairs, int(min_len),
+                                            int(max_span), L.ptr(cls, C.c_uint64)), self.ctx.h)
+        return dict(zip(LINK_CLASSES, (int(x) for x in cls)))
+
     def threadReads(self, positions, support: "Support", data, take_first=None) -> dict:
         """Every window of every read through `positions` (getGraphMap of this graph as it is now): a window that is a node's
         k-mer, entered by an in-edge and left by an out-edge of that node, adds one to `support` for that (in, out) pair, on both
@@ -391,6 +406,10 @@ class Contigs:
 PAIR_CLASSES = ("orientations", "unplaced", "repetitive", "apart", "ambiguous", "reversed", "beyond", "near_end", "counted")
 # the statistics of gk_graph_thread_reads, in the order of its `stats7` array: inner_windows is the sum of the five after it
 THREAD_STATS = ("records", "inner_windows", "off_graph", "repeated", "on_edge", "broken", "crossings")
+# the classes of gk_graph_pair_links, in the order of its `classes8` array: orientations is the sum of the seven after it
+LINK_CLASSES = ("orientations", "unplaced", "repetitive", "at_node", "same_edge", "short_edge", "too_far", "linked")
+# the statistics of gk_links_joins, in the order of its `stats5` array
+JOIN_STATS = ("links", "supported", "joins", "forks", "merges")
 # what the tools fall back to without an estimate: the reference's `180 to 250` (GraphSimplifier.scala:146)
 REFERENCE_RANGE = (180, 250)
 
@@ -505,3 +524,84 @@ class Support:
         """self += other on the device (same device); other is unchanged.  Same overflow rule as add()."""
         L.check(L.lib().gk_support_merge(self.h, other.h), self.ctx.h)
 
+
+
+class HipLinks:
+    """Scaffold links (include/genome_amd.h, "scaffold links"): (edge id, edge id) -> the pair orientations whose mates lie on the
+    two edges, and the sum of the bases those fragments need on them.  Edge ids are the graph's at the time of pairLinks: the
+    table is meaningless after a graph edit."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = L.vp()
+        L.check(L.lib().gk_links_create(ctx.h, C.byref(h)), ctx.h)
+        self.h = h
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:               # (see HipDNAMap.close)
+                L.lib().gk_links_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def size(self):
+        """-> (distinct links, the sum of their counts)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        L.check(L.lib().gk_links_size(self.h, C.byref(a), C.byref(b)), self.ctx.h)
+        return a.value, b.value
+
+    def export(self):
+        """-> (e1, e2, count, sum_u) arrays, unordered"""
+        n = self.size()[0]
+        e1, e2, cnt, su = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        got = C.c_uint64()
+        L.check(L.lib().gk_links_export(self.h, L.ptr(e1, C.c_uint32), L.ptr(e2, C.c_uint32), L.ptr(cnt, C.c_uint32), L.ptr(su, C.c_uint64), n,
+                                        C.byref(got)), self.ctx.h)
+        return e1, e2, cnt, su
+
+    def add(self, e1, e2, cnt, sum_u):
+        """add (e1, e2, count, sum_u) records (duplicates add up); GK_E_CAPACITY, and nothing added, if a count would pass
+        2^32-1.  export() of one table added into an empty one reproduces it."""
+        e1, e2, cnt = (np.ascontiguousarray(a, np.uint32) for a in (e1, e2, cnt))
+        su = np.ascontiguousarray(sum_u, np.uint64)
+        assert len(e1) == len(e2) == len(cnt) == len(su)
+        L.check(L.lib().gk_links_add(self.h, L.ptr(e1, C.c_uint32), L.ptr(e2, C.c_uint32), L.ptr(cnt, C.c_uint32), L.ptr(su, C.c_uint64), len(e1)), self.ctx.h)
+
+    def joins(self, min_support: int = 3, cap=None):
+        """The links that are the only one of at least `min_support` observations out of their first edge and into their second
+        -> ((e1, e2, count, sum_u) arrays in ascending e1, {stat: count} over JOIN_STATS).  `cap`: room for that many joins
+        (default: as many as there are; less is GkError GK_E_CAPACITY)."""
+        lib = L.lib()
+        n, st = C.c_uint64(), np.zeros(len(JOIN_STATS), np.uint64)
+        if cap is None:
+            rc = lib.gk_links_joins(self.h, int(min_support), None, None, None, None, 0, C.byref(n), None)
+            if rc not in (L.GK_OK, L.GK_E_CAPACITY):
+                L.check(rc, self.ctx.h)
+            cap = n.value
+        e1, e2, cnt, su = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint64)
+        L.check(lib.gk_links_joins(self.h, int(min_support), L.ptr(e1, C.c_uint32), L.ptr(e2, C.c_uint32), L.ptr(cnt, C.c_uint32), L.ptr(su, C.c_uint64),
+                                   cap, C.byref(n), L.ptr(st, C.c_uint64)), self.ctx.h)
+        m = n.value
+        return (e1[:m], e2[:m], cnt[:m], su[:m]), dict(zip(JOIN_STATS, (int(x) for x in st)))
+
+
+def scaffoldChains(e1, e2, with_cycles: bool = False):
+    """gk_scaffold_chains over a join list (HipLinks.joins) -> the chains as lists of edge ids, in ascending order of first member;
+    a cycle starts at its smallest id.  with_cycles: -> (chains, number of cycles among them).  GkError GK_E_INVALID if an id
+    occurs twice as e1 or twice as e2.  Host code: no context, no GPU."""
+    e1, e2 = np.ascontiguousarray(e1, np.uint32), np.ascontiguousarray(e2, np.uint32)
+    assert e1.shape == e2.shape and e1.ndim == 1
+    n = len(e1)
+    members, off = np.zeros(2 * n + 1, np.uint32), np.zeros(n + 1, np.uint64)
+    nch, ncy = C.c_uint64(), C.c_uint64()
+    L.check(L.lib().gk_scaffold_chains(L.ptr(e1, C.c_uint32), L.ptr(e2, C.c_uint32), n, L.ptr(members, C.c_uint32), 2 * n, L.ptr(off, C.c_uint64), n,
+                                       C.byref(nch), C.byref(ncy)))
+    chains = [members[int(off[i]):int(off[i + 1])].tolist() for i in range(nch.value)]
+    return (chains, ncy.value) if with_cycles else chains

@@ -512,6 +512,68 @@ class Support {
     gk_support *h_ = nullptr;
 };
 
+// gk_links: scaffold links (include/genome_amd.h, "scaffold links"): (edge id, edge id) -> the pair orientations whose mates lie on
+// the two edges and the sum of the bases those fragments need on them.  Filled by Graph::pairLinks; meaningless after a graph edit.
+class Links {
+  public:
+    struct Records { std::vector<uint32_t> e1, e2, count; std::vector<uint64_t> sumU; };
+    struct JoinStats { uint64_t v[5] = {}; };     // links, supported, joins, forks, merges
+    static constexpr const char *joinStatNames[5] = {"links", "supported", "joins", "forks", "merges"};
+    explicit Links(Context &ctx) : ctx_(ctx) { check(gk_links_create(ctx.handle(), &h_), ctx.handle()); }
+    ~Links() { gk_links_destroy(h_); }
+    Links(const Links &) = delete;
+    gk_links *handle() const { return h_; }
+    // -> (distinct links, the sum of their counts)
+    std::pair<uint64_t, uint64_t> size() const {
+        uint64_t a = 0, b = 0;
+        check(gk_links_size(h_, &a, &b), ctx_.handle());
+        return {a, b};
+    }
+    // every link, unordered
+    Records exportAll() const {
+        Records r;
+        uint64_t n = size().first;
+        r.e1.resize(n); r.e2.resize(n); r.count.resize(n); r.sumU.resize(n);
+        check(gk_links_export(h_, r.e1.data(), r.e2.data(), r.count.data(), r.sumU.data(), n, &n), ctx_.handle());
+        return r;
+    }
+    // add records (duplicates add up); throws (nothing added) if a count would pass 2^32-1
+    void add(const Records &r) {
+        if (r.e1.size() != r.e2.size() || r.e1.size() != r.count.size() || r.e1.size() != r.sumU.size())
+            throw GkError(GK_E_INVALID, "Links::add: the four lists differ in length");
+        check(gk_links_add(h_, r.e1.data(), r.e2.data(), r.count.data(), r.sumU.data(), r.e1.size()), ctx_.handle());
+    }
+    // the links that are the only supported one (count >= minSupport) out of their first edge and into their second, ascending e1
+    Records joins(uint32_t minSupport, JoinStats *stats = nullptr) const {
+        Records r;
+        uint64_t n = 0;
+        const int rc = gk_links_joins(h_, minSupport, nullptr, nullptr, nullptr, nullptr, 0, &n, nullptr);
+        if (rc != GK_OK && rc != GK_E_CAPACITY) check(rc, ctx_.handle());
+        r.e1.resize(n); r.e2.resize(n); r.count.resize(n); r.sumU.resize(n);
+        check(gk_links_joins(h_, minSupport, r.e1.data(), r.e2.data(), r.count.data(), r.sumU.data(), n, &n, stats ? stats->v : nullptr), ctx_.handle());
+        return r;
+    }
+
+  private:
+    Context &ctx_;
+    gk_links *h_ = nullptr;
+};
+
+// gk_scaffold_chains over a join list: the chains as lists of edge ids in ascending order of first member; *cycles = how many of
+// them are cycles (a cycle starts at its smallest id).  Host code: no context, no GPU.
+inline std::vector<std::vector<uint32_t>> scaffoldChains(const std::vector<uint32_t> &e1, const std::vector<uint32_t> &e2, uint64_t *cycles = nullptr) {
+    if (e1.size() != e2.size()) throw GkError(GK_E_INVALID, "scaffoldChains: the two lists differ in length");
+    const uint64_t n = e1.size();
+    std::vector<uint32_t> members(2 * n + 1);
+    std::vector<uint64_t> off(n + 1);
+    uint64_t nch = 0, ncy = 0;
+    check(gk_scaffold_chains(e1.data(), e2.data(), n, members.data(), 2 * n, off.data(), n, &nch, &ncy), nullptr);
+    std::vector<std::vector<uint32_t>> out(nch);
+    for (uint64_t i = 0; i < nch; i++) out[i].assign(members.begin() + off[i], members.begin() + off[i + 1]);
+    if (cycles) *cycles = ncy;
+    return out;
+}
+
 // gk_contigs: a plan of the FASTA text of a graph's contigs (Graph::contigs; the rule: include/genome_amd.h, "contigs").  The text
 // is emitted by the device when it is read or written.  The graph must outlive the plan; after any edit of the graph read / text
 // / write throw GK_E_STATE and stats() still answers.
@@ -666,6 +728,16 @@ class Graph {
         return r;
     }
     PairDistances pairDistances(PartitionedDNAMap &pm, PositionMap &positions, const PairedEndData &data, uint64_t firstPair, uint64_t endPair, uint32_t bins = 4096);
+    // The pairs whose mates' first k-mers lie on two different edges (include/genome_amd.h, "scaffold links"), added to `links`
+    // -> the eight classes.  On an error `links` is unchanged.
+    struct LinkClasses { uint64_t v[8] = {}; };
+    static constexpr const char *linkClassNames[8] = {"orientations", "unplaced", "repetitive", "at_node", "same_edge", "short_edge", "too_far", "linked"};
+    LinkClasses pairLinks(PositionMap &positions, Links &links, const PairedEndData &data, uint64_t takeFirst, uint64_t minLen, uint64_t maxSpan) {
+        LinkClasses c;
+        check(gk_graph_pair_links(h_, positions.handle(), links.handle(), data.bin.data(), data.bin.size(), std::min<uint64_t>(data.count, takeFirst), minLen,
+                                  maxSpan, c.v), ctx_.handle());
+        return c;
+    }
     gk_graph *handle() const { return h_; }
     // :272-316 -> (edges removed, nodes added); simplifyGraph() is the next call (:318)
     std::pair<uint64_t, uint64_t> splitBySupport(const Support &support, int cutoff) {

@@ -5,6 +5,7 @@
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
 //                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]]
+//                 [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH]]   (with --walk-pairs: graph_simplifier.cpp says what they write)
 //                 [--out prefix] [--save-graph PATH] [--correct N|auto]
 //                 [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
@@ -62,7 +63,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--out prefix] [--save-graph PATH] "
+                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH]] [--out prefix] [--save-graph PATH] "
                              "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
@@ -86,6 +87,7 @@ int main(int argc, char **argv) {
     PairedOpts walk;                              // --walk-pairs: cutoff < 0 = no such stage; rangeAuto = --walk-pairs CUTOFF auto
     std::string out, saveGraph, spectrumPath;
     ContigOpts contig;
+    LinkOpts link;                                // --links / --scaffolds: with --walk-pairs, on the graph that stage leaves
     RankOpts ranks;
     for (Args a(argc, argv, 4); a.more(); a.next()) {
         if (a.word("--rounds", 1, "auto")) { autoRounds = true; a.skip(); }   // chosen from the spectrum
@@ -105,10 +107,14 @@ int main(int argc, char **argv) {
         else if (a.word("--walk-pairs", 2, "auto")) { a.value("--walk-pairs", walk.cutoff); walk.rangeAuto = true; a.skip(); }
         else if (a.value("--max-insert", walk.maxInsert)) { if (!walk.maxInsertOk()) { std::fprintf(stderr, "--max-insert N is 1..65535\n"); return 2; } }
         else if (a.value("--walk-pairs", walk.cutoff, walk.lo, walk.hi)) {}
-        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || ranks.parse(a)) {}
+        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || link.parse(a) || ranks.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
-    if (!ranks.check()) return 2;
+    if (!ranks.check() || !link.check(ranks.world)) return 2;
+    if (link.wanted() && walk.cutoff < 0) {
+        std::fprintf(stderr, "--links goes with --walk-pairs (the links are those of the graph the paired-end stage leaves)\n");
+        return 2;
+    }
     const int world = ranks.world, rank = ranks.rank;
     const char *oneGpu = prefilter ? "--prefilter runs" : clipTips || edgeCoverage ? "--clip-tips and --edge-coverage run" :
                          correct ? "--correct runs" : popBubbles ? "--pop-bubbles runs" : nullptr;
@@ -206,6 +212,7 @@ int main(int argc, char **argv) {
             jsonPut(js, "insert_range", jsonObject("lo", walked.range.lo, "hi", walked.range.hi, "estimated", walked.range.estimated,
                                                    "observations", walked.range.observations));
         if (walk.cutoff >= 0) jsonPut(js, "walk_pairs", walked.walkJson());
+        if (link.wanted()) jsonPut(js, "links", linksStage(graph, ctx, data, takeFirst, link, walk, &walked).json());
         if (!contig.path.empty()) jsonPut(js, "contigs_fasta", fasta.json());
         jsonPut(js, "components_histogram", jsonPairs(hist), "components_histogram_2", jsonPairs(hist2));   // GraphBuilder.scala:42, :47
         if (world) jsonPut(js, "occurrences_sent", sent, "occurrences_owned", owned, "world", world);

@@ -6,6 +6,7 @@
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
 //                    [--take-first N] [--thread-reads [--no-pairs]]
 //                    [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
+//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH]]
 //                    [--world W --rank R --id-file PATH]
 //   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
 //   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
@@ -27,6 +28,15 @@
 //   above its reverse complement (--contig-both-strands: every live edge), n >= --contig-min-len (default 0), lines of
 //   --contig-width bases (default 60, 0 = one line).  No cov= field: this tool holds no count table.  The JSON gains
 //   "contigs_fasta":{the nine stats}.  Over --world rank 0 writes.
+//   --links PATH writes the scaffold links of the FINAL graph (include/genome_amd.h, "scaffold links": this project's own rule):
+//   the pairs of the same --take-first prefix whose mates' first k-mers lie on two different edges, one line
+//   `e1<TAB>e2<TAB>count<TAB>sum_u<TAB>gap` per link in ascending (e1, e2) behind three `#` lines.  Edges whose contig is shorter than
+//   --link-min-len bases (default 0) link nothing; max_span = the range's upper end + k; gap = mid - floor(sum_u / count), where mid
+//   is the median --range auto measured, or (lo + hi) div 2 of the given range or of the fallback 180..250 (stderr says which).
+//   --scaffolds PATH writes the chains of the joins (the only link of at least --link-min-support observations, default 3, out of
+//   one edge and into the next): `s<i><TAB>members<TAB>e<id><TAB>gap<TAB>e<id>...`, a cycle ending in its closing gap and `cycle`;
+//   both strands' chains appear.  The JSON gains "links":{the eight classes, the five join stats, mid, max_span, chains, cycles}.
+//   One GPU only.
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
 //   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
 //   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
@@ -45,7 +55,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
                              "[--thread-reads [--no-pairs]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
-                             "[--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -55,6 +65,7 @@ int main(int argc, char **argv) {
     uint64_t takeFirst = UINT64_MAX;
     std::string out, saveGraph, insertHist;
     ContigOpts contig;
+    LinkOpts link;
     RankOpts ranks;
     for (Args a(argc, argv, 4); a.more(); a.next()) {
         if (a.value("--cutoff", stage.cutoff)) {}
@@ -63,7 +74,7 @@ int main(int argc, char **argv) {
         else if (a.value("--range", stage.lo, stage.hi) || a.value("--take-first", takeFirst)) {}
         else if (a.flag("--thread-reads")) stage.threadReads = true;
         else if (a.flag("--no-pairs")) stage.walk = false;
-        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || ranks.parse(a)) {}
+        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || link.parse(a) || ranks.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
     if (stage.cutoff < 0) {
@@ -78,7 +89,7 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--no-pairs goes with --thread-reads, and not with --range auto (no walk uses the range)\n");
         return 2;
     }
-    if (!ranks.check()) return 2;
+    if (!ranks.check() || !link.check(ranks.world)) return 2;
     const int world = ranks.world, rank = ranks.rank;
     try {
         if (fastq.path.empty()) data.bin = readBin(infile);
@@ -113,6 +124,8 @@ int main(int argc, char **argv) {
             contigs.write(contig.path);
             jsonPut(js, "contigs_fasta", contigs.stats().json());
         }
+        // --links / --scaffolds: on the final graph, with a position map of its own
+        if (link.wanted()) jsonPut(js, "links", linksStage(graph, ctx, data, takeFirst, link, stage, &res).json());
         if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");
         jsonPut(js, "simplified_nodes", n2, "simplified_edges", e2, "simplified_edges_length", l2, "components_histogram_2", jsonPairs(hist2),
                 "max_component_size", hist.empty() ? 0 : hist.rbegin()->first);

@@ -4,11 +4,13 @@
 // command line.  (tests/host/tool_common_check.cpp runs the parts that need no device, links nothing, under sanitizers.)
 #pragma once
 
+#include <algorithm>
 #include <charconv>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <map>
 #include <memory>
 #include <type_traits>
 
@@ -240,5 +242,86 @@ inline PairedResult pairedStage(genome::Graph &graph, genome::Context &ctx, geno
     std::tie(r.supPairs, r.badPairs, r.walked) = support.sizes();                                    // :266 "Bad pairs"
     std::tie(r.removedEdges, r.newNodes) = graph.splitBySupport(support, o.cutoff);                  // :272-316
     graph.simplifyGraph();                                                                           // :318
+    return r;
+}
+
+// --links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH]: scaffold links of the FINAL graph (include/genome_amd.h,
+// "scaffold links"; this project's own rule), after the paired-end stage.  One GPU.
+struct LinkOpts {
+    std::string path, scaffolds;
+    uint32_t minSupport = 3;
+    uint64_t minLen = 0;
+    bool parse(Args &a) {
+        return a.value("--links", path) || a.value("--link-min-support", minSupport) || a.value("--link-min-len", minLen) || a.value("--scaffolds", scaffolds);
+    }
+    bool wanted() const { return !path.empty(); }
+    bool check(int world) const {
+        if (path.empty() && !scaffolds.empty()) { std::fprintf(stderr, "--scaffolds PATH goes with --links PATH\n"); return false; }
+        if (wanted() && world) { std::fprintf(stderr, "--links runs on one GPU only (not with --world): export per rank and add the tables\n"); return false; }
+        return true;
+    }
+};
+struct LinkResult {
+    genome::Graph::LinkClasses classes;
+    genome::Links::JoinStats joins;
+    uint64_t mid = 0, maxSpan = 0, chains = 0, cycles = 0;
+    std::string json() const {
+        return "{" + jsonNamed(genome::Graph::linkClassNames, classes.v, 8) + "," + jsonNamed(genome::Links::joinStatNames, joins.v, 5) + ",\"mid\":" +
+               std::to_string(mid) + ",\"max_span\":" + std::to_string(maxSpan) + ",\"chains\":" + std::to_string(chains) + ",\"cycles\":" + std::to_string(cycles) + "}";
+    }
+};
+// gap of a link = mid - floor(sum_u / count), signed
+inline long long linkGap(uint64_t mid, uint32_t count, uint64_t sumU) { return (long long)mid - (long long)(sumU / (count ? count : 1)); }
+// `walked`: what the paired-end stage measured (null: no such stage ran, the range is o's as given).  max_span = range_hi + k;
+// mid = the median of an estimated range, else (lo + hi) div 2 of the range in force (the fallback 180..250 included).
+inline LinkResult linksStage(genome::Graph &graph, genome::Context &ctx, const genome::PairedEndData &data, uint64_t takeFirst, const LinkOpts &lo,
+                             const PairedOpts &o, const PairedResult *walked) {
+    LinkResult r;
+    const bool measured = walked && o.rangeAuto;
+    const uint64_t rlo = measured ? walked->range.lo : (uint64_t)o.lo, rhi = measured ? walked->range.hi : (uint64_t)o.hi;
+    const bool median = measured && walked->range.estimated;
+    r.mid = median ? walked->range.median : (rlo + rhi) / 2;
+    r.maxSpan = rhi + (uint64_t)graph.k();
+    std::fprintf(stderr, "links: max_span %llu = %llu + k, gap = %llu - floor(sum_u / count): %s\n", (unsigned long long)r.maxSpan, (unsigned long long)rhi,
+                 (unsigned long long)r.mid, median ? "the median of the estimated insert range" :
+                 measured ? "the middle of the fallback range (no estimate)" : "the middle of the given range");
+    auto positions = graph.getGraphMap();                                                            // of the graph as it is NOW
+    genome::Links links(ctx);
+    r.classes = graph.pairLinks(positions, links, data, takeFirst, lo.minLen, r.maxSpan);
+    auto all = links.exportAll();
+    std::vector<size_t> order(all.e1.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return std::make_pair(all.e1[a], all.e2[a]) < std::make_pair(all.e1[b], all.e2[b]); });
+    std::ofstream lf(lo.path);
+    lf << "# scaffold links: pair orientations whose mates lie on two different edges of the final graph (ids as in --contigs / --save-graph)\n"
+       << "# min_len " << lo.minLen << " max_span " << r.maxSpan << " mid " << r.mid << "; gap = mid - floor(sum_u / count), negative: the contigs overlap\n"
+       << "# e1\te2\tcount\tsum_u\tgap\n";
+    for (const size_t i : order)
+        lf << all.e1[i] << "\t" << all.e2[i] << "\t" << all.count[i] << "\t" << all.sumU[i] << "\t" << linkGap(r.mid, all.count[i], all.sumU[i]) << "\n";
+    if (!lf) throw std::runtime_error("cannot write " + lo.path);
+    const auto joins = links.joins(lo.minSupport, &r.joins);
+    uint64_t cycles = 0;
+    const auto chains = genome::scaffoldChains(joins.e1, joins.e2, &cycles);
+    r.chains = chains.size(); r.cycles = cycles;
+    if (!lo.scaffolds.empty()) {
+        std::map<uint32_t, long long> gapAfter;                                                      // an e1 occurs once among the joins
+        for (size_t i = 0; i < joins.e1.size(); i++) gapAfter[joins.e1[i]] = linkGap(r.mid, joins.count[i], joins.sumU[i]);
+        std::ofstream sf(lo.scaffolds);
+        sf << "# scaffold chains: maximal paths of joins (the only link of at least " << lo.minSupport << " observations out of one edge and into the next)\n"
+           << "# both strands' chains appear, as --contigs --contig-both-strands shows the edges: a chain and the chain of its twins are the same scaffold\n"
+           << "# s<i>\t<members>\te<id>\t<gap>\te<id>...; a cycle starts at its smallest id and ends with the closing gap and the word cycle\n";
+        for (size_t i = 0; i < chains.size(); i++) {
+            const auto &c = chains[i];
+            sf << "s" << i << "\t" << c.size();
+            for (size_t j = 0; j < c.size(); j++) {
+                sf << "\te" << c[j];
+                if (j + 1 < c.size()) sf << "\t" << gapAfter.at(c[j]);
+            }
+            const auto closing = gapAfter.find(c.back());                                            // the last member of a path joins nothing
+            if (closing != gapAfter.end()) sf << "\t" << closing->second << "\tcycle";
+            sf << "\n";
+        }
+        if (!sf) throw std::runtime_error("cannot write " + lo.scaffolds);
+    }
     return r;
 }

@@ -747,6 +747,78 @@ int gk_insert_range(const uint64_t *hist, uint32_t bins, uint32_t trim_permille,
  * bad `bins`, is GK_E_INVALID on the rank that passes it, before the collective. */
 int gk_dist_pair_distances(gk_dist *d, gk_graph *g, gk_vmap *positions, const uint8_t *bin, size_t nbytes, uint64_t npairs, uint32_t bins, uint64_t *hist,
                            uint64_t *classes);
+
+/* ---- scaffold links: this project's own rule (the reference ends at the split and the contigs; nothing there orders two edges
+ * that the graph does not connect, or connects only through a tangle) ----
+ * The orientations gk_graph_pair_distances counts as `apart`, the mates on two different edges, are the scaffolding evidence.
+ * gk_graph_pair_links keeps them.  Orientations are exactly gk_graph_pair_distances':
+ *   orientation 0: P1 = getAll(p1.take(k)), P2 = getAll(p2.take(k).revComplement);
+ *   orientation 1: P1 = getAll(p2.take(k)), P2 = getAll(p1.take(k).revComplement);
+ * a pair with a mate shorter than k gives none.  P(e) = start k-mer ++ seq is the path of edge e, k + len_e bases.  An orientation
+ * whose placements are a = Edge(e, da) and b = Edge(f, db) would spell a fragment that starts at base da of P(e) and ends after
+ * base db + k of P(f): D = u + G bases, where G is the number of bases between the end of P(e) and the start of P(f) (G = -k
+ * when f leaves e's end node: the two paths share the node's k-mer) and
+ *   u = (len_e + k - da) + (db + k)
+ * is the number of bases the fragment needs on the two edges.  Every orientation falls into exactly one class, tested in this
+ * order (integers only):
+ *   unplaced    P1 or P2 is empty;
+ *   repetitive  |P1| >= 2 or |P2| >= 2: the lists are not looked at (a fresh graph holds a k-mer once and never gets here, the
+ *               node copies of a split can);
+ *   at_node     either single position is a NODE position;
+ *   same_edge   e == f: that case is gk_graph_pair_distances' business;
+ *   short_edge  k + len_e < min_len or k + len_f < min_len (min_len in contig bases, as gk_graph_contigs_plan's; 0 keeps all);
+ *   too_far     u > max_span;
+ *   linked      links[(e, f)].count += 1 and links[(e, f)].sum_u += u.
+ * The table stores sum_u, not a gap, so the device rule needs no library parameter: a caller that knows the fragment median M
+ * reads the mean gap of a link as M - floor(sum_u / count), signed.  sum_u adds up mod 2^64.
+ * Twins.  Orientation 1 of a pair is the same fragment read on the other strand.  If orientation 0 places p1.take(k) at base da of
+ * P(e) and p2.take(k).revComplement at base db of P(f), then on the twin edges (P(twin x) = revComplement of P(x), same length)
+ * p2.take(k) lies at base len_f - db of P(twin f) and p1.take(k).revComplement at base len_e - da of P(twin e): orientation 1
+ * lands on (twin f, twin e) with u' = (len_f + k - (len_f - db)) + ((len_e - da) + k) = u.  Both distances stay inside 1 .. len - 1,
+ * so both orientations are EDGE positions or neither is, and the same two lengths meet min_len.  A strand-closed graph therefore
+ * gets a strand-closed link table: count and sum_u of (e, f) equal those of (twin f, twin e).
+ * classes8 = uint64[8] = {orientations, unplaced, repetitive, at_node, same_edge, short_edge, too_far, linked}; element 0 is the
+ * sum of the other seven.
+ * gk_graph_pair_links: handles, stream shapes (a ragged or fixed host `.bin` stream, its first `npairs` pairs) and errors are
+ * gk_graph_pair_distances': GK_E_KLEN for a position map of another k, GK_E_STATE for a stale one (a position that names nothing
+ * live in this graph: checked before the kernel reads an edge length), GK_E_FORMAT for a stream that ends inside a pair,
+ * GK_E_INVALID for NULL handles or another context.  It accumulates over calls: it counts into a table of its own and merges
+ * that at the end, as gk_graph_thread_reads does, so on ANY error `links` is unchanged and classes8 is zero.  A count that would
+ * pass 2^32-1 is GK_E_CAPACITY (gk_support_add's rule), here and in gk_links_add.  Neither the graph nor the position map
+ * changes.  Edge ids are the graph's at the time of the call: the table holds no state counter and is MEANINGLESS after a graph
+ * edit; make a new one.  Over N ranks every rank links its share, exports, and one rank takes them with gk_links_add: there is
+ * no collective yet.
+ * On the device: one lane per orientation over the getAll batch's CSR, class counts by ballot, one insert per linked lane into an
+ * open-addressed (e << 32 | f) table with a u32 count plane and a u64 sum plane, sized before the launch for one link per
+ * orientation at load <= 0.5. */
+typedef struct gk_links gk_links;
+int gk_links_create(gk_ctx *ctx, gk_links **out);
+void gk_links_destroy(gk_links *l);
+int gk_graph_pair_links(gk_graph *g, gk_vmap *positions, gk_links *links, const uint8_t *bin, size_t nbytes, uint64_t npairs, uint64_t min_len,
+                        uint64_t max_span, uint64_t *classes8);
+/* distinct (e, f) and the sum of their counts (either may be NULL) */
+int gk_links_size(const gk_links *l, uint64_t *links, uint64_t *observations);
+/* unordered; *n = the links held, GK_E_CAPACITY (nothing copied) when cap is below it */
+int gk_links_export(const gk_links *l, uint32_t *e1, uint32_t *e2, uint32_t *count, uint64_t *sum_u, uint64_t cap, uint64_t *n);
+/* Add n (e1, e2, count, sum_u) records; duplicates in the list add up.  Export, then add into an empty table, reproduces the
+ * table.  A count that would pass 2^32-1 fails with GK_E_CAPACITY, and l is then unchanged.  0xffffffff is not an edge id. */
+int gk_links_add(gk_links *l, const uint32_t *e1, const uint32_t *e2, const uint32_t *count, const uint64_t *sum_u, uint64_t n);
+/* Joins.  A link is SUPPORTED iff count >= min_support.  (e, f) is a JOIN iff it is the only supported link out of e and the only
+ * supported link into f.  The joins come in ascending e1 (an e1 occurs at most once, so the order is total), with their count and
+ * sum_u.  stats5 (may be NULL) = uint64[5] = {links, supported, joins, edges with >= 2 supported successors, edges with >= 2
+ * supported predecessors}.  *n = joins; cap below it is GK_E_CAPACITY with *n and stats5 set and nothing copied.  On the device:
+ * one pass over the slots counts successors and predecessors per edge id, one lane per edge id flags the joins, a scan and a
+ * compaction in id order emit them. */
+int gk_links_joins(const gk_links *l, uint32_t min_support, uint32_t *e1, uint32_t *e2, uint32_t *count, uint64_t *sum_u, uint64_t cap, uint64_t *n,
+                   uint64_t *stats5);
+/* Chains.  Pure host code: no context, no device (gk_insert_range's kind).  Input: a join list, in which no id occurs twice as e1
+ * or twice as e2 (GK_E_INVALID otherwise); such joins form disjoint paths and cycles.  A chain is a maximal path in join order; a
+ * cycle is a chain that starts at its smallest edge id, and is counted in *ncycles.  Edges in no join are not listed.  Chains come
+ * in ascending order of first member: chain i is members[chain_off[i] .. chain_off[i + 1]), so chain_off holds chains_cap + 1
+ * words.  n joins give at most n chains of at most 2n members together; less room than needed is GK_E_CAPACITY with *nchains and
+ * *ncycles set and nothing written. */
+int gk_scaffold_chains(const uint32_t *e1, const uint32_t *e2, uint64_t n, uint32_t *members, uint64_t members_cap, uint64_t *chain_off, uint64_t chains_cap,
+                       uint64_t *nchains, uint64_t *ncycles);
 /* live nodes, unspecified order */
 int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap, uint64_t *n);
 /* live edges, unspecified order: start/end k-mer, length in bases, and the edge sequence as 2-bit
