@@ -168,6 +168,13 @@ SIGNATURES = {
     "gk_links_add": (C.c_int, [vp, u32p, u32p, u32p, u64p, C.c_uint64]),
     "gk_links_joins": (C.c_int, [vp, C.c_uint32, u32p, u32p, u32p, u64p, C.c_uint64, u64p, u64p]),
     "gk_scaffold_chains": (C.c_int, [u32p, u32p, C.c_uint64, u32p, C.c_uint64, u64p, C.c_uint64, u64p, u64p]),
+    "gk_graph_scaffolds_plan": (C.c_int, [vp, u32p, u64p, C.c_uint64, i64p, C.c_int64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(vp)]),
+    "gk_scaffolds_destroy": (None, [vp]),
+    "gk_scaffolds_stats": (C.c_int, [vp, u64p]),
+    "gk_scaffolds_read": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, u64p]),
+    "gk_scaffolds_write": (C.c_int, [vp, C.c_char_p]),
+    "gk_scaffolds_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "gk_scaffolds_segments": (C.c_int, [vp, u64p, u32p, u64p, u64p, u32p, C.c_uint64, u64p]),
     "gk_graph_replace_end": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
     "gk_graph_build": (C.c_int, [vp, C.POINTER(vp)]),
     "gk_graph_destroy": (None, [vp]),

@@ -12,76 +12,14 @@
 // launch.  No LDS, no atomics in the emit kernel.
 //
 // Roofline: the emit kernel reads 2 bits and writes 8 (plus the line ends) per base: it is a streaming write of the text.
-#include <fcntl.h>
-#include <unistd.h>
-
-#include <algorithm>
-#include <cerrno>
-#include <chrono>
-#include <cstring>
 #include <memory>
 
-#include "gk_graph.h"
+#include "gk_fastaout.h"
 #include "gk_scan.h"
 
 static constexpr uint8_t CLS_DEAD = 0, CLS_SHORT = 1, CLS_FORWARD = 2, CLS_SELF = 3, CLS_REVERSE = 4;
-static constexpr u64 CONTIGS_CHUNK_DEFAULT = 64ull << 20;
 // device counters of a plan: the four classes, bases of the records, windows missing from the table, "a record passes 2^32-1 bytes"
 enum { CS_SHORT = 0, CS_FORWARD, CS_SELF, CS_REVERSE, CS_BASES, CS_MISSING, CS_OVERFLOW, CS_N };
-
-// ---------------------------------------------------------------------------------------------
-// the text of one record, from its numbers
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int dec_digits(u64 v) {
-    int d = 1;
-    while (v >= 10) { v /= 10; d++; }
-    return d;
-}
-// digit `pos` (0 = the most significant) of v, which has ndig digits
-__device__ __forceinline__ char dec_digit_at(u64 v, int ndig, int pos) {
-    for (int i = ndig - 1 - pos; i > 0; i--) v /= 10;
-    return (char)('0' + (int)(v % 10));
-}
-// ">e<id> len=<n>[ cov=<q/100>.<q%100, two digits>]\n"
-struct RecHdr {
-    u64 id, n, q;
-    int di, dn, dq;
-    u32 len;
-};
-__device__ __forceinline__ RecHdr rec_hdr(u64 id, u64 n, u64 q, bool has_cov) {
-    RecHdr h;
-    h.id = id; h.n = n; h.q = q;
-    h.di = dec_digits(id); h.dn = dec_digits(n); h.dq = has_cov ? dec_digits(q / 100) : 0;
-    h.len = (u32)(2 + h.di + 5 + h.dn + (has_cov ? 5 + h.dq + 3 : 0) + 1);
-    return h;
-}
-__device__ __forceinline__ char hdr_byte(const RecHdr &h, u32 p, bool has_cov) {
-    if (p < 2) return p ? 'e' : '>';
-    p -= 2;
-    if (p < (u32)h.di) return dec_digit_at(h.id, h.di, (int)p);
-    p -= (u32)h.di;
-    if (p < 5) return " len="[p];
-    p -= 5;
-    if (p < (u32)h.dn) return dec_digit_at(h.n, h.dn, (int)p);
-    p -= (u32)h.dn;
-    if (has_cov) {
-        if (p < 5) return " cov="[p];
-        p -= 5;
-        if (p < (u32)h.dq) return dec_digit_at(h.q / 100, h.dq, (int)p);
-        p -= (u32)h.dq;
-        if (p == 0) return '.';
-        if (p == 1) return (char)('0' + (int)(h.q % 100) / 10);
-        if (p == 2) return (char)('0' + (int)(h.q % 10));
-    }
-    return '\n';
-}
-// the n bases and their line ends: a '\n' after every line_width bases (0: none) and after the last base, never two in a row
-__device__ __forceinline__ u64 body_bytes(u64 n, u32 line_width) { return n + (line_width ? (n + line_width - 1) / line_width : 1); }
-// base i of the path start k-mer ++ seq
-__device__ __forceinline__ int path_base(u64 nlo, u64 nhi, const uint8_t *__restrict__ seq, int k, u64 i) {
-    if (i >= (u64)k) return pool_get(seq, 0, i - (u64)k);
-    return (int)((i < 32 ? nlo >> (2 * i) : nhi >> (2 * (i - 32))) & 3);
-}
 
 // ---------------------------------------------------------------------------------------------
 // classification and sizing: one wave per live edge
@@ -257,52 +195,10 @@ struct gk_contigs {
     u32 *d_id = nullptr;
     unsigned long long *d_off = nullptr;
     u64 *d_q = nullptr;
-    // two device chunks and two pinned staging buffers of buf_bytes each, made by the first read / write
-    uint8_t *d_buf[2] = {nullptr, nullptr};
-    void *h_buf[2] = {nullptr, nullptr};
-    hipEvent_t ev_k0[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr}, ev_c[2] = {nullptr, nullptr};      // a chunk's kernel begins / ends, its copy has landed
-    u64 buf_bytes = 0;
-    float last_ms[4] = {0, 0, 0, 0};     // the last read / write: emit kernels (device events), waits for copies, the sink, the whole call
+    TextStream ts;                       // the chunk buffers, made by the first read / write, and the times of the last one
 };
 
 namespace {
-
-u64 contigs_chunk(const gk_ctx *ctx) {
-    const u64 c = ctx->hook_contigs_chunk > 0 ? (u64)ctx->hook_contigs_chunk : CONTIGS_CHUNK_DEFAULT;
-    return std::max<u64>(8, c & ~(u64)7);
-}
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-void contigs_free_buffers(gk_contigs *c) {
-    for (int i = 0; i < 2; i++) {
-        if (c->ev_k0[i]) { (void)hipEventSynchronize(c->ev_k0[i]); (void)hipEventDestroy(c->ev_k0[i]); c->ev_k0[i] = nullptr; }
-        if (c->ev_k[i]) { (void)hipEventSynchronize(c->ev_k[i]); (void)hipEventDestroy(c->ev_k[i]); c->ev_k[i] = nullptr; }
-        if (c->ev_c[i]) { (void)hipEventSynchronize(c->ev_c[i]); (void)hipEventDestroy(c->ev_c[i]); c->ev_c[i] = nullptr; }
-        if (c->d_buf[i]) { (void)pool_free(c->ctx, c->d_buf[i]); c->d_buf[i] = nullptr; }
-        if (c->h_buf[i]) { (void)gk_host_free(c->ctx, c->h_buf[i]); c->h_buf[i] = nullptr; }
-    }
-    c->buf_bytes = 0;
-}
-
-// the chunk buffers for pieces of at most `chunk` bytes (a piece may start up to 7 bytes into its first word)
-int contigs_buffers(gk_contigs *c, u64 chunk) {
-    gk_ctx *ctx = c->ctx;
-    const u64 want = std::min(chunk, (c->text_bytes + 7) & ~(u64)7) + 8;
-    if (c->buf_bytes == want) return GK_OK;
-    contigs_free_buffers(c);
-    for (int i = 0; i < 2; i++) {
-        const hipError_t e = pool_malloc(ctx, &c->d_buf[i], want);
-        if (e != hipSuccess) { (void)hipGetLastError(); contigs_free_buffers(c); return hip_fail(ctx, e, "gk_contigs: device chunk"); }
-        if (int rc = gk_host_alloc(ctx, want, &c->h_buf[i])) { contigs_free_buffers(c); return rc; }
-        hipError_t e2 = hipEventCreate(&c->ev_k0[i]);
-        if (e2 == hipSuccess) e2 = hipEventCreate(&c->ev_k[i]);
-        if (e2 == hipSuccess) e2 = hipEventCreateWithFlags(&c->ev_c[i], hipEventDisableTiming);
-        if (e2 != hipSuccess) { contigs_free_buffers(c); return hip_fail(ctx, e2, "gk_contigs: events"); }
-    }
-    c->buf_bytes = want;
-    return GK_OK;
-}
 
 int contigs_live(const gk_contigs *c, const char *who) {
     if (!c || !c->ctx) return fail(nullptr, GK_E_INVALID, std::string(who) + ": null contigs handle");
@@ -312,76 +208,12 @@ int contigs_live(const gk_contigs *c, const char *who) {
     return GK_OK;
 }
 
-// Bytes [offset, offset + n) of the text through `sink`, in order, in pieces of at most the chunk size.  Piece i + 1 is emitted on
-// the context's stream while piece i is copied to its pinned buffer on the copy stream and handed to the sink.  A sink that
-// returns false ends the stream (*sink_failed).
-template <class Sink> int contigs_stream(gk_contigs *c, u64 offset, u64 n, Sink &&sink, bool *sink_failed) {
-    gk_ctx *ctx = c->ctx;
-    *sink_failed = false;
-    for (float &m : c->last_ms) m = 0;
-    if (n == 0) return GK_OK;
-    const double t_call = now_ms();
-    double t_wait = 0, t_sink = 0;
-    float t_kernels = 0;
-    const u64 chunk = contigs_chunk(ctx);
-    if (int rc = contigs_buffers(c, chunk)) return rc;
-    const ContigPlan plan{c->d_id, c->d_off, c->d_q, c->records, c->line_width};
-    // pieces end on multiples of the chunk size in the text, so that all but the first start on a word
-    const u64 end = offset + n;
-    auto piece_end = [&](u64 t) { return std::min(end, (t / chunk + 1) * chunk); };
-    auto issue = [&](u64 t, int slot) -> hipError_t {
-        const u64 t1 = piece_end(t);
-        const u64 a0 = std::min(t1, (t + 7) & ~(u64)7), a1 = std::max(a0, t1 & ~(u64)7);
-        hipError_t e = hipEventRecord(c->ev_k0[slot], ctx->stream);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_contig_emit, dim3(ggrid(ctx, (a0 - t) + ((a1 - a0) >> 3) + (t1 - a1))), dim3(BLOCK), 0, ctx->stream, c->g->v, plan, t, t1,
-                           c->d_buf[slot]);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(c->ev_k[slot], ctx->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->copy_stream, c->ev_k[slot], 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->h_buf[slot], c->d_buf[slot] + (t & 7), t1 - t, hipMemcpyDeviceToHost, ctx->copy_stream);
-        if (e == hipSuccess) e = hipEventRecord(c->ev_c[slot], ctx->copy_stream);
-        ctx->copy_other_pending = true;                      // (the copy stream reads a pooled block: pool_free waits for it)
-        return e;
+// the launch of k_contig_emit for bytes [t, t1) of the text (gk_fastaout.h: text_stream)
+auto contigs_emit(gk_contigs *c) {
+    return [c](u64 t, u64 t1, u64 items, uint8_t *out) {
+        const ContigPlan plan{c->d_id, c->d_off, c->d_q, c->records, c->line_width};
+        hipLaunchKernelGGL(k_contig_emit, dim3(ggrid(c->ctx, items)), dim3(BLOCK), 0, c->ctx->stream, c->g->v, plan, t, t1, out);
     };
-    hipError_t he = issue(offset, 0);
-    int slot = 0;
-    for (u64 t = offset; t < end && he == hipSuccess; slot ^= 1) {
-        const u64 t1 = piece_end(t);
-        if (t1 < end) he = issue(t1, slot ^ 1);
-        if (he != hipSuccess) break;
-        double t_ = now_ms();
-        he = hipEventSynchronize(c->ev_c[slot]);
-        t_wait += now_ms() - t_;
-        float k_ms = 0;
-        if (he == hipSuccess) he = hipEventElapsedTime(&k_ms, c->ev_k0[slot], c->ev_k[slot]);
-        if (he != hipSuccess) break;
-        t_kernels += k_ms;
-        t_ = now_ms();
-        const bool ok = sink((const char *)c->h_buf[slot], t1 - t);
-        t_sink += now_ms() - t_;
-        if (!ok) { *sink_failed = true; break; }
-        t = t1;
-    }
-    // nothing of this call is left in flight, whatever ended the loop
-    const hipError_t e1 = hipStreamSynchronize(ctx->stream), e2 = hipStreamSynchronize(ctx->copy_stream);
-    if (he == hipSuccess) he = e1 != hipSuccess ? e1 : e2;
-    if (he != hipSuccess) return hip_fail(ctx, he, "gk_contigs: emit");
-    c->last_ms[0] = t_kernels; c->last_ms[1] = (float)t_wait; c->last_ms[2] = (float)t_sink; c->last_ms[3] = (float)(now_ms() - t_call);
-    return GK_OK;
-}
-
-bool write_all(int fd, const char *p, u64 n) {
-    while (n) {
-        const ssize_t w = ::write(fd, p, std::min<u64>(n, 1ull << 30));
-        if (w < 0) { if (errno == EINTR) continue; return false; }
-        p += w; n -= (u64)w;
-    }
-    return true;
-}
-
-int sys_fail(gk_ctx *ctx, const std::string &what, const std::string &path) {
-    return fail(ctx, GK_E_INVALID, what + " " + path + ": " + std::strerror(errno));
 }
 
 }  // namespace
@@ -392,7 +224,7 @@ void gk_contigs_destroy(gk_contigs *c) {
     if (!c) return;
     if (c->ctx) {
         (void)hipSetDevice(c->ctx->device);
-        contigs_free_buffers(c);
+        text_free_buffers(&c->ts);
         (void)pool_free(c->ctx, c->d_id);
         (void)pool_free(c->ctx, c->d_off);
         (void)pool_free(c->ctx, c->d_q);
@@ -410,7 +242,7 @@ int gk_graph_contigs_plan(gk_graph *g, gk_map *counts, uint64_t min_len, uint32_
     if (counts) { if (int rc = check_counts(g, counts, "gk_graph_contigs_plan")) return rc; }
     const GraphView &v = g->v;
     std::unique_ptr<gk_contigs, void (*)(gk_contigs *)> c(new gk_contigs, gk_contigs_destroy);
-    c->ctx = ctx; c->g = g; c->epoch = g->epoch; c->line_width = line_width;
+    c->ctx = ctx; c->ts.ctx = ctx; c->g = g; c->epoch = g->epoch; c->line_width = line_width;
     if (v.n_edges == 0) { *out = c.release(); return GK_OK; }
     const u64 ne = v.n_edges;
     DevScratch tmp(ctx);
@@ -470,7 +302,7 @@ int gk_contigs_stats(const gk_contigs *c, uint64_t *stats9) {
 int gk_contigs_last_ms(const gk_contigs *c, float *ms4) {
     if (!c || !c->ctx) return fail(nullptr, GK_E_INVALID, "gk_contigs_last_ms: null contigs handle");
     if (!ms4) return fail(c->ctx, GK_E_INVALID, "gk_contigs_last_ms: ms4 is NULL");
-    for (int i = 0; i < 4; i++) ms4[i] = c->last_ms[i];
+    for (int i = 0; i < 4; i++) ms4[i] = c->ts.last_ms[i];
     return GK_OK;
 }
 
@@ -483,7 +315,7 @@ int gk_contigs_read(gk_contigs *c, uint64_t offset, char *buf, uint64_t cap, uin
     if (want && !buf) return fail(ctx, GK_E_INVALID, "gk_contigs_read: buf is NULL");
     u64 done = 0;
     bool sink_failed = false;
-    if (int rc = contigs_stream(c, offset, want, [&](const char *p, u64 m) { std::memcpy(buf + done, p, m); done += m; return true; }, &sink_failed)) return rc;
+    if (int rc = text_stream(&c->ts, c->text_bytes, offset, want, "gk_contigs", contigs_emit(c), [&](const char *p, u64 m) { std::memcpy(buf + done, p, m); done += m; return true; }, &sink_failed)) return rc;
     if (n) *n = done;
     return GK_OK;
 }
@@ -492,17 +324,7 @@ int gk_contigs_write(gk_contigs *c, const char *path) {
     if (int rc = contigs_live(c, "gk_contigs_write")) return rc;
     gk_ctx *ctx = c->ctx;
     if (!path) return fail(ctx, GK_E_INVALID, "gk_contigs_write: path is NULL");
-    const std::string p(path), tmp = p + ".tmp";
-    const int fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
-    if (fd < 0) return sys_fail(ctx, "gk_contigs_write: cannot open", tmp);
-    bool sink_failed = false;
-    int en = 0;
-    const int rc = contigs_stream(c, 0, c->text_bytes, [&](const char *q, u64 m) { if (write_all(fd, q, m)) return true; en = errno; return false; }, &sink_failed);
-    if (::close(fd) != 0 && !sink_failed) { sink_failed = true; en = errno; }
-    if (rc) { ::unlink(tmp.c_str()); return rc; }
-    if (sink_failed) { ::unlink(tmp.c_str()); errno = en; return sys_fail(ctx, "gk_contigs_write: cannot write", tmp); }
-    if (std::rename(tmp.c_str(), p.c_str()) != 0) { en = errno; ::unlink(tmp.c_str()); errno = en; return sys_fail(ctx, "gk_contigs_write: cannot rename to", p); }
-    return GK_OK;
+    return text_write_file(&c->ts, c->text_bytes, path, "gk_contigs", "gk_contigs_write", contigs_emit(c));
 }
 
 }  // extern "C"

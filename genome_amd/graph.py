@@ -225,6 +225,28 @@ class HipGraph:
                                               C.byref(h)), self.ctx.h)
         return Contigs(self, h)
 
+    # ---- scaffolds as FASTA (this project's own rule: include/genome_amd.h) --------------------------------------------
+    def scaffolds(self, chains, gaps, min_gap: int = 10, min_len: int = 0, line_width: int = 60, strands: int = 1, singletons: bool = True) -> "Scaffolds":
+        """The chains (lists of edge ids, scaffoldChains') as FASTA text, planned on the device: one record
+        `>s<c> len=<n> contigs=<m> gaps=<N bases>` per chain whose sequence is not above its reverse complement (strands = 2:
+        every chain).  Consecutive members that meet in a node are joined on its k bases; between any others go
+        max(gap, min_gap) bases N, `gaps[c][i]` being the gap after member i of chain c (scaffoldGaps; an entry for the last member
+        may be left out or is ignored).  singletons: the live edges in no chain follow as contigs() would write them (min_len
+        applies to them alone).  min_gap = 10 is a choice, not a measurement.  -> a Scaffolds: stats(), read(), text(), write(),
+        segments().  Any edit of the graph makes it stale (GkError GK_E_STATE)."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        chains = [list(c) for c in chains]
+        assert len(gaps) == len(chains) and all(len(c) - 1 <= len(g) <= len(c) for c, g in zip(chains, gaps))
+        members = np.array([e for c in chains for e in c], np.uint32)
+        gap = np.array([x for c, g in zip(chains, gaps) for x in list(g)[:len(c) - 1] + [0]], np.int64) if len(members) else np.zeros(0, np.int64)
+        off = np.zeros(len(chains) + 1, np.uint64)
+        off[1:] = np.cumsum([len(c) for c in chains])
+        h = L.vp()
+        L.check(L.lib().gk_graph_scaffolds_plan(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64), int(min_gap),
+                                                int(min_len), int(line_width), int(strands), int(bool(singletons)), C.byref(h)), self.ctx.h)
+        return Scaffolds(self, h)
+
     def walkPairs(self, positions, support: "Support", bin_bytes, npairs: int, range_lo: int = 180, range_hi: int = 250):
         """:213-247: the pairs' positions through `positions` (getGraphMap of this graph as it is now), annotate, the bounded
         walks; the supported (edge, edge) pairs are counted in `support`."""
@@ -400,6 +422,91 @@ class Contigs:
         """the whole text to `path`; written aside, then renamed onto it"""
         self._live()
         L.check(L.lib().gk_contigs_write(self.h, os.fsencode(path)), self.ctx.h)
+
+
+# the statistics of gk_scaffolds_stats, in the order of its `stats13` array
+SCAFFOLD_STATS = ("chains", "chain_forward", "chain_self_twin", "chain_reverse", "singletons", "records", "members", "adjacent", "gapped", "clamped",
+                  "n_bases", "bases", "text_bytes")
+
+
+class Scaffolds:
+    """A plan of the FASTA text of a graph's scaffolds (HipGraph.scaffolds): the text itself is emitted by the device when it is
+    read or written.  Holds its graph; stale (GkError GK_E_STATE from read / text / write) once the graph has been edited."""
+
+    def __init__(self, graph: HipGraph, handle):
+        self.graph, self.ctx, self.h = graph, graph.ctx, handle
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:               # (see HipDNAMap.close)
+                L.lib().gk_scaffolds_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h or not self.ctx.h or not self.graph.h:
+            raise L.GkError(L.GK_E_STATE, "the scaffolds or their graph are closed")
+
+    def stats(self) -> dict:
+        """the thirteen numbers of the plan, named as SCAFFOLD_STATS; they still answer when the plan is stale"""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the scaffolds are closed")
+        st = np.zeros(len(SCAFFOLD_STATS), np.uint64)
+        L.check(L.lib().gk_scaffolds_stats(self.h, L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(SCAFFOLD_STATS, (int(x) for x in st)))
+
+    def read(self, offset: int, n: int) -> bytes:
+        """bytes [offset, offset + n) of the text, fewer at its end; GkError GK_E_INVALID for an offset beyond it"""
+        self._live()
+        buf = np.empty(max(int(n), 1), np.uint8)
+        got = C.c_uint64()
+        L.check(L.lib().gk_scaffolds_read(self.h, int(offset), buf.ctypes.data, int(n), C.byref(got)), self.ctx.h)
+        return buf[:got.value].tobytes()
+
+    def text(self) -> bytes:
+        return self.read(0, self.stats()["text_bytes"])
+
+    def last_ms(self) -> dict:
+        """wall ms of the last read / write: the emit kernels (device events), waits for copies, the sink, the whole call"""
+        arr = (C.c_float * 4)()
+        L.check(L.lib().gk_scaffolds_last_ms(self.h, arr), self.ctx.h)
+        return dict(zip(("emit_kernels", "copies", "sink", "total"), (float(x) for x in arr)))
+
+    def write(self, path):
+        """the whole text to `path`; written aside, then renamed onto it"""
+        self._live()
+        L.check(L.lib().gk_scaffolds_write(self.h, os.fsencode(path)), self.ctx.h)
+
+    def segments(self) -> list:
+        """which piece of which edge lies where: [(record index in the text, edge id, first base in the record's sequence, bases
+        written, bases of the edge's path skipped before them: 0 or k)] in text order; N runs are the bases between rows"""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the scaffolds are closed")
+        st = self.stats()
+        n = st["members"] + st["singletons"]
+        rec, first, bases = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        edge, skip = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        got = C.c_uint64()
+        L.check(L.lib().gk_scaffolds_segments(self.h, L.ptr(rec, C.c_uint64), L.ptr(edge, C.c_uint32), L.ptr(first, C.c_uint64), L.ptr(bases, C.c_uint64),
+                                              L.ptr(skip, C.c_uint32), n, C.byref(got)), self.ctx.h)
+        assert got.value == n
+        return list(zip(rec.tolist(), edge.tolist(), first.tolist(), bases.tolist(), skip.tolist()))
+
+
+def scaffoldGaps(chains, joins, mid: int):
+    """The gap lists HipGraph.scaffolds takes, from a HipLinks.joins result (e1, e2, count, sum_u): mid - floor(sum_u / count) of
+    the join between consecutive members, one entry fewer than a chain has members.  `mid`: the fragment length the library is
+    taken to have (the tools pass the median of the insert range).  KeyError if two consecutive members are no join."""
+    e1, e2, cnt, su = (np.asarray(a).tolist() for a in joins)
+    gap = {(a, b): int(mid) - s // c for a, b, c, s in zip(e1, e2, cnt, su)}
+    return [[gap[(a, b)] for a, b in zip(c, c[1:])] for c in chains]
 
 
 # the classes of gk_graph_pair_distances, in the order of its `classes` array

@@ -617,6 +617,60 @@ class Contigs {
     gk_contigs *h_ = nullptr;
 };
 
+// gk_scaffolds: a plan of the FASTA text of a graph's scaffolds (Graph::scaffolds; the rule: include/genome_amd.h, "scaffolds").
+// As Contigs: the device emits the text when it is read or written, and an edit of the graph makes the plan stale.
+class Scaffolds {
+  public:
+    struct Stats {
+        uint64_t v[13] = {};                                     // gk_scaffolds_stats' stats13, under these names
+        std::string json() const {
+            const char *names[13] = {"chains", "chain_forward", "chain_self_twin", "chain_reverse", "singletons", "records", "members", "adjacent", "gapped",
+                                     "clamped", "n_bases", "bases", "text_bytes"};
+            std::string s = "{";
+            for (int i = 0; i < 13; i++) s += std::string(i ? ",\"" : "\"") + names[i] + "\":" + std::to_string(v[i]);
+            return s + "}";
+        }
+        uint64_t textBytes() const { return v[12]; }
+    };
+    // one piece of an edge in a record: the record's index in the text, the first base in its sequence, bases written, bases skipped
+    struct Segment { uint64_t record; uint32_t edge; uint64_t first, bases; uint32_t skipped; };
+    Scaffolds(gk_ctx *ctx, gk_scaffolds *h) : ctx_(ctx), h_(h) {}
+    ~Scaffolds() { close(); }
+    void close() { gk_scaffolds_destroy(h_); h_ = nullptr; }
+    Scaffolds(Scaffolds &&o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    Scaffolds(const Scaffolds &) = delete;
+    Scaffolds &operator=(const Scaffolds &) = delete;
+    Stats stats() const {
+        Stats st;
+        check(gk_scaffolds_stats(h_, st.v), ctx_);
+        return st;
+    }
+    std::string read(uint64_t offset, uint64_t n) {
+        std::string out((size_t)n, '\0');
+        uint64_t got = 0;
+        check(gk_scaffolds_read(h_, offset, out.data(), n, &got), ctx_);
+        out.resize((size_t)got);
+        return out;
+    }
+    std::string text() { return read(0, stats().textBytes()); }
+    void write(const std::string &path) { check(gk_scaffolds_write(h_, path.c_str()), ctx_); }
+    std::vector<Segment> segments() const {
+        const Stats st = stats();
+        const uint64_t n = st.v[6] + st.v[4];
+        std::vector<uint64_t> rec(n), first(n), bases(n);
+        std::vector<uint32_t> edge(n), skip(n);
+        uint64_t got = 0;
+        check(gk_scaffolds_segments(h_, rec.data(), edge.data(), first.data(), bases.data(), skip.data(), n, &got), ctx_);
+        std::vector<Segment> out(n);
+        for (uint64_t i = 0; i < n; i++) out[i] = Segment{rec[i], edge[i], first[i], bases[i], skip[i]};
+        return out;
+    }
+
+  private:
+    gk_ctx *ctx_ = nullptr;
+    gk_scaffolds *h_ = nullptr;
+};
+
 struct Edge {                 // S/data/graph/Edge.scala:11 (ids are not part of the observable result)
     DNASeq start, end;
     std::string seq;
@@ -840,6 +894,27 @@ class Graph {
         gk_contigs *c = nullptr;
         check(gk_graph_contigs_plan(h_, counts ? counts->handle() : nullptr, minLen, lineWidth, bothStrands ? 2 : 1, &c), ctx_.handle());
         return Contigs(ctx_.handle(), c);
+    }
+    // The chains (scaffoldChains') as scaffold FASTA, planned on the device (include/genome_amd.h, "scaffolds"): gaps[c][i] = the gap
+    // after member i of chain c (an entry for the last member may be left out).  minGap = 10 is a choice, not a measurement.
+    Scaffolds scaffolds(const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps, int64_t minGap = 10, uint64_t minLen = 0,
+                        uint32_t lineWidth = 60, bool bothStrands = false, bool singletons = true) const {
+        if (chains.size() != gaps.size()) throw GkError(GK_E_INVALID, "scaffolds: as many gap lists as chains");
+        std::vector<uint32_t> members;
+        std::vector<int64_t> gap;
+        std::vector<uint64_t> off(1, 0);
+        for (size_t c = 0; c < chains.size(); c++) {
+            if (gaps[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, "scaffolds: a chain with fewer gaps than junctions");
+            for (size_t j = 0; j < chains[c].size(); j++) {
+                members.push_back(chains[c][j]);
+                gap.push_back(j + 1 < chains[c].size() ? gaps[c][j] : 0);
+            }
+            off.push_back(members.size());
+        }
+        gk_scaffolds *s = nullptr;
+        check(gk_graph_scaffolds_plan(h_, members.data(), off.data(), chains.size(), gap.data(), minGap, minLen, lineWidth, bothStrands ? 2 : 1, singletons ? 1 : 0, &s),
+              ctx_.handle());
+        return Scaffolds(ctx_.handle(), s);
     }
     // the `contigs` file of GraphSimplifier.scala:338-347: per edge its sequence, then ">abacaba<i>"
     // (edge order: canonical, since the reference's is ConcurrentHashMap order)

@@ -6,7 +6,7 @@
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
 //                    [--take-first N] [--thread-reads [--no-pairs]]
 //                    [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
-//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH]]
+//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]]]
 //                    [--world W --rank R --id-file PATH]
 //   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
 //   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
@@ -37,6 +37,11 @@
 //   one edge and into the next): `s<i><TAB>members<TAB>e<id><TAB>gap<TAB>e<id>...`, a cycle ending in its closing gap and `cycle`;
 //   both strands' chains appear.  The JSON gains "links":{the eight classes, the five join stats, mid, max_span, chains, cycles}.
 //   One GPU only.
+//   --scaffold-fasta PATH (with --links) writes those chains as FASTA (include/genome_amd.h, "scaffolds": this project's own rule):
+//   `>s<i> len=<n> contigs=<m> gaps=<N bases>` per chain, members that meet in a node joined on its k bases, max(gap,
+//   --scaffold-min-gap) bases N between any others (default 10: a choice, not a measurement), one strand per chain
+//   (--scaffold-both-strands: every chain), lines of --scaffold-width bases (default 60, 0 = one line); the edges in no chain
+//   follow as --contigs would write them, --link-min-len being their length filter.  The JSON gains "scaffolds":{the thirteen stats}.
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
 //   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
 //   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
@@ -55,7 +60,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
                              "[--thread-reads [--no-pairs]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
-                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH]] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -125,7 +130,11 @@ int main(int argc, char **argv) {
             jsonPut(js, "contigs_fasta", contigs.stats().json());
         }
         // --links / --scaffolds: on the final graph, with a position map of its own
-        if (link.wanted()) jsonPut(js, "links", linksStage(graph, ctx, data, takeFirst, link, stage, &res).json());
+        if (link.wanted()) {
+            const LinkResult lr = linksStage(graph, ctx, data, takeFirst, link, stage, &res);
+            jsonPut(js, "links", lr.json());
+            if (!lr.scaffoldsJson.empty()) jsonPut(js, "scaffolds", lr.scaffoldsJson);
+        }
         if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");
         jsonPut(js, "simplified_nodes", n2, "simplified_edges", e2, "simplified_edges_length", l2, "components_histogram_2", jsonPairs(hist2),
                 "max_component_size", hist.empty() ? 0 : hist.rbegin()->first);

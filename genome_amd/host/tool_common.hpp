@@ -247,16 +247,24 @@ inline PairedResult pairedStage(genome::Graph &graph, genome::Context &ctx, geno
 
 // --links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH]: scaffold links of the FINAL graph (include/genome_amd.h,
 // "scaffold links"; this project's own rule), after the paired-end stage.  One GPU.
+// --scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]: the chains of those links as FASTA
+// (include/genome_amd.h, "scaffolds"), the edges in no chain after them; --link-min-len is the singletons' length filter too.
 struct LinkOpts {
-    std::string path, scaffolds;
+    std::string path, scaffolds, scaffoldFasta;
     uint32_t minSupport = 3;
     uint64_t minLen = 0;
+    int64_t scaffoldMinGap = 10;                  // a choice, not a measurement
+    uint32_t scaffoldWidth = 60;
+    bool scaffoldBoth = false;
     bool parse(Args &a) {
-        return a.value("--links", path) || a.value("--link-min-support", minSupport) || a.value("--link-min-len", minLen) || a.value("--scaffolds", scaffolds);
+        if (a.flag("--scaffold-both-strands")) { scaffoldBoth = true; return true; }
+        return a.value("--links", path) || a.value("--link-min-support", minSupport) || a.value("--link-min-len", minLen) || a.value("--scaffolds", scaffolds) ||
+               a.value("--scaffold-fasta", scaffoldFasta) || a.value("--scaffold-min-gap", scaffoldMinGap) || a.value("--scaffold-width", scaffoldWidth);
     }
     bool wanted() const { return !path.empty(); }
     bool check(int world) const {
         if (path.empty() && !scaffolds.empty()) { std::fprintf(stderr, "--scaffolds PATH goes with --links PATH\n"); return false; }
+        if (path.empty() && !scaffoldFasta.empty()) { std::fprintf(stderr, "--scaffold-fasta PATH goes with --links PATH\n"); return false; }
         if (wanted() && world) { std::fprintf(stderr, "--links runs on one GPU only (not with --world): export per rank and add the tables\n"); return false; }
         return true;
     }
@@ -265,6 +273,7 @@ struct LinkResult {
     genome::Graph::LinkClasses classes;
     genome::Links::JoinStats joins;
     uint64_t mid = 0, maxSpan = 0, chains = 0, cycles = 0;
+    std::string scaffoldsJson;                    // the stats of --scaffold-fasta's text; empty without the flag
     std::string json() const {
         return "{" + jsonNamed(genome::Graph::linkClassNames, classes.v, 8) + "," + jsonNamed(genome::Links::joinStatNames, joins.v, 5) + ",\"mid\":" +
                std::to_string(mid) + ",\"max_span\":" + std::to_string(maxSpan) + ",\"chains\":" + std::to_string(chains) + ",\"cycles\":" + std::to_string(cycles) + "}";
@@ -322,6 +331,16 @@ inline LinkResult linksStage(genome::Graph &graph, genome::Context &ctx, const g
             sf << "\n";
         }
         if (!sf) throw std::runtime_error("cannot write " + lo.scaffolds);
+    }
+    if (!lo.scaffoldFasta.empty()) {
+        std::map<std::pair<uint32_t, uint32_t>, int64_t> gapOf;
+        for (size_t i = 0; i < joins.e1.size(); i++) gapOf[{joins.e1[i], joins.e2[i]}] = linkGap(r.mid, joins.count[i], joins.sumU[i]);
+        std::vector<std::vector<int64_t>> gaps(chains.size());
+        for (size_t c = 0; c < chains.size(); c++)
+            for (size_t j = 0; j + 1 < chains[c].size(); j++) gaps[c].push_back(gapOf.at({chains[c][j], chains[c][j + 1]}));
+        auto sc = graph.scaffolds(chains, gaps, lo.scaffoldMinGap, lo.minLen, lo.scaffoldWidth, lo.scaffoldBoth, true);
+        sc.write(lo.scaffoldFasta);
+        r.scaffoldsJson = sc.stats().json();
     }
     return r;
 }

@@ -819,6 +819,70 @@ int gk_links_joins(const gk_links *l, uint32_t min_support, uint32_t *e1, uint32
  * *ncycles set and nothing written. */
 int gk_scaffold_chains(const uint32_t *e1, const uint32_t *e2, uint64_t n, uint32_t *members, uint64_t members_cap, uint64_t *chain_off, uint64_t chains_cap,
                        uint64_t *nchains, uint64_t *ncycles);
+
+/* ---- scaffolds: this project's own rule (the reference has no links and writes no scaffolds) ----
+ * The chains as FASTA text, written on the device: junctions inside the graph joined, gaps N-filled, one strand per chain.
+ * Integers only.
+ * Input.  A chain list in gk_scaffold_chains' shape: chain c is members[chain_off[c] .. chain_off[c + 1]), chain_off[0] = 0, so
+ * `members` holds chain_off[nchains] edge ids.  `gap` is parallel to `members`: gap[j] is the estimated number of bases between
+ * members[j] and members[j + 1] of the same chain (the tools pass mid - floor(sum_u / count) of the join, which may be negative);
+ * the entry at a chain's last member is ignored.  A cycle therefore comes out open, cut where gk_scaffold_chains starts it.
+ * Paths.  P(e) = start k-mer ++ seq, k + len_e bases, as in the contig rule.
+ * Junction.  Every junction between consecutive members e, f falls into exactly one class, tested in this order:
+ *   adjacent  e_end[e] == e_start[f], the same node ID (copies of a node that share a k-mer are different nodes): the two paths
+ *             share that node's k-mer, so f contributes bases k .. of P(f) and nothing goes between; the gap is not looked at;
+ *   gapped    anything else: a run of max(gap, min_gap) bases N, then all of P(f).  A gap below min_gap counts as CLAMPED (it is
+ *             gapped too).  Overlaps are not looked for: a negative gap is clamped like any other.
+ * Sequence.  S(c) = P(first member) followed by what every junction adds, over the codes A0 G1 C2 T3 N4; n = its length.
+ * Strand.  R(S) = S reversed with code c mapped to 3 - c for c < 4, and 4 staying 4.  A chain is FORWARD if S < R
+ * lexicographically by code, SELF_TWIN if S == R, REVERSE otherwise.  No twin lookup is needed, for the reason the contig rule
+ * gives.  On a strand-closed graph with a strand-closed link table (see "scaffold links", Twins) the join (e, f) comes with the
+ * join (twin f, twin e) of the same count and sum_u, hence the same gap; a chain (e1 .. em) comes with (twin em .. twin e1).  Its
+ * junction (twin e[i+1], twin e[i]) is adjacent iff (e[i], e[i+1]) is: end(e[i]) = start(e[i+1]) = v means start(twin e[i]) =
+ * end(twin e[i+1]) = the node of v's reverse complement.  P(twin x) is the reverse complement of P(x), an adjacent junction drops
+ * the same k bases from either side and an N run reads the same backwards, so the twin chain's sequence is R(S): exactly one chain
+ * of such a pair is forward, or both are the same self_twin chain.
+ * Selection.  strands = 1: the forward and self_twin chains (a reverse chain whose twin chain is absent is NOT written; the stats
+ * show it).  strands = 2: all chains.  Other values: GK_E_INVALID.  singletons != 0: every live edge that is a member of no given
+ * chain is written too, with min_len and strands applied exactly as gk_graph_contigs_plan applies them.  Chain members are never
+ * dropped for length.
+ * Text.  The selected chains in input order, then the singletons in ascending edge id.  A chain's record:
+ *     >s<c> len=<n> contigs=<m> gaps=<N bases>\n
+ *     <the n bases as ACGTN text, wrapped as contigs are: a '\n' after every line_width bases (0: one line) and after the last>
+ * c is the chain's index in the input, so a record is the same under both values of `strands`; m = its members.  A singleton's
+ * record is byte for byte the contig rule's without cov=: ">e<id> len=<n>\n" and the wrapped bases.  There is never an empty line.
+ * Errors, all found on the device in one pass before any kernel reads a member's length.  GK_E_INVALID: a member id at or above
+ * the edge id bound, or dead; an edge that occurs twice, in one chain or in two; an empty chain or a chain_off that does not
+ * ascend; min_gap outside 1 .. 2^31-1; a used gap above 2^31-1; strands not 1 or 2; line_width above 2^31-1; NULL handles or
+ * arrays.  GK_E_CAPACITY: a record of 2^32 bytes or more.  nchains = 0 is legal; with singletons the text is then
+ * gk_contigs_read's of the same graph without a count table.  On any error *out stays NULL and everything allocated is freed.
+ * The graph is not changed and must outlive the plan; after ANY edit of it gk_scaffolds_read and gk_scaffolds_write return
+ * GK_E_STATE, while stats and segments still answer.
+ * min_gap has no measured value: the tools and the Python side pass 10, the customary shortest N run, as a choice.
+ * On the device: one lane per member claims its edge (a compare-and-swap on an owner word per edge finds duplicates) and decides
+ * its junction; a scan over the segment lengths places every segment; one wave per chain compares S with R 64 bases at a time,
+ * a lane finding its base by a binary search in the chain's segments; two more scans and a compaction give record -> (segments,
+ * byte offset); the text is emitted by byte range as contigs are, the segment of a lane's first base found by a binary search.
+ * Not there: cov= on scaffold records, overlap detection for negative gaps, a collective over ranks (links are per rank). */
+typedef struct gk_scaffolds gk_scaffolds;
+int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap, int64_t min_gap,
+                            uint64_t min_len, uint32_t line_width, int strands, int singletons, gk_scaffolds **out);
+void gk_scaffolds_destroy(gk_scaffolds *s);
+/* stats13 = {chains, chain_forward, chain_self_twin, chain_reverse, singletons, records, members, adjacent, gapped, clamped,
+ * n_bases, bases, text_bytes}: chains = the sum of the three after it; singletons = singleton records; records = chain records +
+ * singletons; members .. n_bases are over the chain records (members = their pieces, adjacent + gapped = members - chain
+ * records, clamped <= gapped, n_bases = their N); bases = the sum of n over all records */
+int gk_scaffolds_stats(const gk_scaffolds *s, uint64_t *stats13);
+/* gk_contigs_read's, gk_contigs_write's and gk_contigs_last_ms' contracts, for this text */
+int gk_scaffolds_read(gk_scaffolds *s, uint64_t offset, char *buf, uint64_t cap, uint64_t *n);
+int gk_scaffolds_write(gk_scaffolds *s, const char *path);
+int gk_scaffolds_last_ms(const gk_scaffolds *s, float *ms4);
+/* The layout of the records, one row per piece of an edge in text order: the record's index in the text, the edge id, the first
+ * base of the piece in the record's sequence, the bases written, and the bases of P(edge) skipped before them (0, or k after an
+ * adjacent junction).  N runs are the bases between rows.  *n = rows = members + singletons of the stats; cap below it is
+ * GK_E_CAPACITY with *n set and nothing copied. */
+int gk_scaffolds_segments(const gk_scaffolds *s, uint64_t *record, uint32_t *edge, uint64_t *first, uint64_t *bases, uint32_t *skipped, uint64_t cap,
+                          uint64_t *n);
 /* live nodes, unspecified order */
 int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap, uint64_t *n);
 /* live edges, unspecified order: start/end k-mer, length in bases, and the edge sequence as 2-bit
