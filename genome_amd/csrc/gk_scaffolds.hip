@@ -15,33 +15,19 @@
 #include <memory>
 #include <vector>
 
+#include "gk_chains.h"
 #include "gk_fastaout.h"
 #include "gk_scan.h"
 
 static constexpr uint8_t SC_SHORT = 1, SC_FORWARD = 2, SC_SELF = 3, SC_REVERSE = 4;
 static constexpr uint8_t MC_FIRST = 0, MC_ADJACENT = 1, MC_GAPPED = 2, MC_CLAMPED = 3;
-// error flags of the check and the segment pass
-enum { SF_BAD_ID = 0, SF_DUPLICATE, SF_CHAIN, SF_GAP, SF_OVERFLOW, SF_N };
 // device counters of a plan
 enum { SS_FORWARD = 0, SS_SELF, SS_REVERSE, SS_SINGLE, SS_MEMBERS, SS_ADJACENT, SS_GAPPED, SS_CLAMPED, SS_NBASES, SS_BASES, SS_OVERFLOW, SS_N };
 static constexpr int SCAFFOLD_STATS = 13;
 
 // ---------------------------------------------------------------------------------------------
-// checks: before any kernel reads a member's length
+// checks: before any kernel reads a member's length (k_scaf_check and the error flags: gk_chains.h)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_scaf_check(GraphView g, const u32 *__restrict__ members, const unsigned long long *__restrict__ chain_off, u64 nchains,
-                                                      u64 nm, u32 *owner, u32 *flags) {
-    const u64 items = max(nm, nchains);
-    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < items; i += (u64)gridDim.x * BLOCK) {
-        if (i < nchains && !(chain_off[i] < chain_off[i + 1])) flags[SF_CHAIN] = 1;      // (empty, or not ascending)
-        if (i < nm) {
-            const u32 e = members[i];
-            if ((u64)e >= g.n_edges || !g.e_alive[e]) flags[SF_BAD_ID] = 1;
-            else if (atomicCAS(&owner[e], 0u, 1u) != 0u) flags[SF_DUPLICATE] = 1;
-        }
-    }
-}
-
 // Member j of chain c fills slots 2j (an N run, or nothing) and 2j + 1 (its piece).  Runs only behind a clean check.
 __global__ __launch_bounds__(BLOCK) void k_scaf_segments(GraphView g, const u32 *__restrict__ members, const unsigned long long *__restrict__ chain_off, u64 nchains,
                                                          u64 nm, const long long *__restrict__ gap, long long min_gap, u32 *flags, u32 *__restrict__ chain_of,

@@ -247,6 +247,37 @@ class HipGraph:
                                                 int(min_len), int(line_width), int(strands), int(bool(singletons)), C.byref(h)), self.ctx.h)
         return Scaffolds(self, h)
 
+    # ---- gap filling (this project's own rule: include/genome_amd.h) ---------------------------------------------------
+    def fillGaps(self, chains, gaps, tol: int, max_edges: int = 16, max_paths: int = 256):
+        """Between scaffoldChains / scaffoldGaps and scaffolds(): where the graph holds exactly one path of at most `max_edges`
+        edges from the end of a member to the start of the next whose length is within `tol` bases of the gap, and no edge of it is
+        a member or lies on another such path, its edges are spliced in as members -> (chains, gaps, report), the first two in
+        the shape scaffolds() takes (a new junction's gap is -k; it is adjacent and never looked at).  report = the ten stats
+        named as FILL_STATS, plus "classes": per chain the class name of every junction (FILL_CLASSES) and "lengths": per chain
+        the path's gap length L where the class is shared or filled, else 0.  Junctions searched with more than `max_paths`
+        bounded paths from both sides stay as they are (overflow).  max_edges = 16 and max_paths = 256 are choices, not
+        measurements.  The graph is not edited."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        chains = [list(c) for c in chains]
+        if len(gaps) != len(chains) or not all(len(c) - 1 <= len(g) <= len(c) for c, g in zip(chains, gaps)):
+            raise ValueError("fillGaps: one gap list per chain, with an entry per junction")
+        members = np.array([e for c in chains for e in c], np.uint32)
+        gap = np.array([x for c, g in zip(chains, gaps) for x in list(g)[:len(c) - 1] + [0]], np.int64) if len(members) else np.zeros(0, np.int64)
+        off = np.zeros(len(chains) + 1, np.uint64)
+        off[1:] = np.cumsum([len(c) for c in chains])
+        nm, cap = len(members), self.idBounds()[1]             # (no edge is written twice: the filled chains fit the edge ids)
+        out_m, out_g, out_off = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int64), np.zeros(len(chains) + 1, np.uint64)
+        jclass, jlen, st, n = np.zeros(max(nm, 1), np.uint8), np.zeros(max(nm, 1), np.int64), np.zeros(len(FILL_STATS), np.uint64), C.c_uint64()
+        L.check(L.lib().gk_graph_fill_gaps(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64), int(tol), int(max_edges),
+                                           int(max_paths), L.ptr(out_m, C.c_uint32), L.ptr(out_g, C.c_int64), cap, L.ptr(out_off, C.c_uint64),
+                                           L.ptr(jclass, C.c_uint8), L.ptr(jlen, C.c_int64), C.byref(n), L.ptr(st, C.c_uint64)), self.ctx.h)
+        o, i = out_off.tolist(), off.tolist()
+        report = dict(zip(FILL_STATS, (int(x) for x in st)))
+        report["classes"] = [[FILL_CLASSES[x] for x in jclass[a:b - 1].tolist()] for a, b in zip(i, i[1:])]
+        report["lengths"] = [jlen[a:b - 1].tolist() for a, b in zip(i, i[1:])]
+        return [out_m[a:b].tolist() for a, b in zip(o, o[1:])], [out_g[a:b - 1].tolist() for a, b in zip(o, o[1:])], report
+
     def walkPairs(self, positions, support: "Support", bin_bytes, npairs: int, range_lo: int = 180, range_hi: int = 250):
         """:213-247: the pairs' positions through `positions` (getGraphMap of this graph as it is now), annotate, the bounded
         walks; the supported (edge, edge) pairs are counted in `support`."""
@@ -427,6 +458,12 @@ class Contigs:
 # the statistics of gk_scaffolds_stats, in the order of its `stats13` array
 SCAFFOLD_STATS = ("chains", "chain_forward", "chain_self_twin", "chain_reverse", "singletons", "records", "members", "adjacent", "gapped", "clamped",
                   "n_bases", "bases", "text_bytes")
+
+
+# the statistics of gk_graph_fill_gaps, in the order of its `stats10` array: junctions is the sum of the six after it
+FILL_STATS = ("junctions", "adjacent", "overflow", "none", "ambiguous", "shared", "filled", "filler_edges", "filler_bases", "searched_backward")
+# the names of the GK_FILL_* class codes, by code
+FILL_CLASSES = ("last", "adjacent", "overflow", "none", "ambiguous", "shared", "filled")
 
 
 class Scaffolds:

@@ -916,6 +916,55 @@ class Graph {
               ctx_.handle());
         return Scaffolds(ctx_.handle(), s);
     }
+    // Gap filling between scaffoldChains and scaffolds (include/genome_amd.h, "gap filling"): where the graph holds exactly one path
+    // of at most maxEdges edges between two consecutive members whose length is within tol bases of the gap, and no edge of it is
+    // contested, its edges become members.  chains / gaps feed scaffolds() unchanged (a new junction's gap is -k).  classes[c][i] /
+    // lengths[c][i]: the GK_FILL_* class of the junction after member i of input chain c, and the path's L where it is shared or
+    // filled.  maxEdges = 16 and maxPaths = 256 are choices, not measurements.
+    struct Filled {
+        std::vector<std::vector<uint32_t>> chains;
+        std::vector<std::vector<int64_t>> gaps, lengths;
+        std::vector<std::vector<uint8_t>> classes;
+        uint64_t v[10] = {};                                     // gk_graph_fill_gaps' stats10, under these names
+        std::string json() const {
+            const char *names[10] = {"junctions", "adjacent", "overflow", "none", "ambiguous", "shared", "filled", "filler_edges", "filler_bases",
+                                     "searched_backward"};
+            std::string s = "{";
+            for (int i = 0; i < 10; i++) s += std::string(i ? ",\"" : "\"") + names[i] + "\":" + std::to_string(v[i]);
+            return s + "}";
+        }
+    };
+    Filled fillGaps(const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps, uint64_t tol, uint32_t maxEdges = 16,
+                    uint32_t maxPaths = 256) const {
+        if (chains.size() != gaps.size()) throw GkError(GK_E_INVALID, "fillGaps: as many gap lists as chains");
+        std::vector<uint32_t> members;
+        std::vector<int64_t> gap;
+        std::vector<uint64_t> off(1, 0);
+        for (size_t c = 0; c < chains.size(); c++) {
+            if (gaps[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, "fillGaps: a chain with fewer gaps than junctions");
+            for (size_t j = 0; j < chains[c].size(); j++) {
+                members.push_back(chains[c][j]);
+                gap.push_back(j + 1 < chains[c].size() ? gaps[c][j] : 0);
+            }
+            off.push_back(members.size());
+        }
+        uint64_t nodeBound = 0, cap = 0, n = 0;
+        check(gk_graph_id_bounds(h_, &nodeBound, &cap), ctx_.handle());      // (no edge is written twice: the filled chains fit the edge ids)
+        std::vector<uint32_t> outMembers(cap + 1);
+        std::vector<int64_t> outGap(cap + 1), jlen(members.size() + 1);
+        std::vector<uint64_t> outOff(chains.size() + 1);
+        std::vector<uint8_t> jclass(members.size() + 1);
+        Filled r;
+        check(gk_graph_fill_gaps(h_, members.data(), off.data(), chains.size(), gap.data(), tol, maxEdges, maxPaths, outMembers.data(), outGap.data(), cap,
+                                 outOff.data(), jclass.data(), jlen.data(), &n, r.v), ctx_.handle());
+        for (size_t c = 0; c < chains.size(); c++) {
+            r.chains.emplace_back(outMembers.begin() + outOff[c], outMembers.begin() + outOff[c + 1]);
+            r.gaps.emplace_back(outGap.begin() + outOff[c], outGap.begin() + outOff[c + 1] - 1);
+            r.classes.emplace_back(jclass.begin() + off[c], jclass.begin() + off[c + 1] - 1);
+            r.lengths.emplace_back(jlen.begin() + off[c], jlen.begin() + off[c + 1] - 1);
+        }
+        return r;
+    }
     // the `contigs` file of GraphSimplifier.scala:338-347: per edge its sequence, then ">abacaba<i>"
     // (edge order: canonical, since the reference's is ConcurrentHashMap order)
     void writeContigs(std::ostream &out) const {

@@ -249,6 +249,8 @@ inline PairedResult pairedStage(genome::Graph &graph, genome::Context &ctx, geno
 // "scaffold links"; this project's own rule), after the paired-end stage.  One GPU.
 // --scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]: the chains of those links as FASTA
 // (include/genome_amd.h, "scaffolds"), the edges in no chain after them; --link-min-len is the singletons' length filter too.
+// --fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N] (with --scaffolds or --scaffold-fasta): the chains go through
+// gk_graph_fill_gaps first (include/genome_amd.h, "gap filling"), and both files are written from the filled chains.
 struct LinkOpts {
     std::string path, scaffolds, scaffoldFasta;
     uint32_t minSupport = 3;
@@ -256,8 +258,13 @@ struct LinkOpts {
     int64_t scaffoldMinGap = 10;                  // a choice, not a measurement
     uint32_t scaffoldWidth = 60;
     bool scaffoldBoth = false;
+    bool fillGaps = false;
+    int64_t fillTol = -1;                         // -1: half the width of the insert range the stage used; a choice, not a measurement
+    uint32_t fillMaxEdges = 16, fillMaxPaths = 256;   // choices, not measurements
     bool parse(Args &a) {
         if (a.flag("--scaffold-both-strands")) { scaffoldBoth = true; return true; }
+        if (a.optional("--fill-gaps", fillTol)) { fillGaps = true; return true; }
+        if (a.value("--fill-max-edges", fillMaxEdges) || a.value("--fill-max-paths", fillMaxPaths)) return true;
         return a.value("--links", path) || a.value("--link-min-support", minSupport) || a.value("--link-min-len", minLen) || a.value("--scaffolds", scaffolds) ||
                a.value("--scaffold-fasta", scaffoldFasta) || a.value("--scaffold-min-gap", scaffoldMinGap) || a.value("--scaffold-width", scaffoldWidth);
     }
@@ -265,6 +272,7 @@ struct LinkOpts {
     bool check(int world) const {
         if (path.empty() && !scaffolds.empty()) { std::fprintf(stderr, "--scaffolds PATH goes with --links PATH\n"); return false; }
         if (path.empty() && !scaffoldFasta.empty()) { std::fprintf(stderr, "--scaffold-fasta PATH goes with --links PATH\n"); return false; }
+        if (fillGaps && scaffolds.empty() && scaffoldFasta.empty()) { std::fprintf(stderr, "--fill-gaps goes with --scaffolds PATH or --scaffold-fasta PATH\n"); return false; }
         if (wanted() && world) { std::fprintf(stderr, "--links runs on one GPU only (not with --world): export per rank and add the tables\n"); return false; }
         return true;
     }
@@ -274,6 +282,7 @@ struct LinkResult {
     genome::Links::JoinStats joins;
     uint64_t mid = 0, maxSpan = 0, chains = 0, cycles = 0;
     std::string scaffoldsJson;                    // the stats of --scaffold-fasta's text; empty without the flag
+    std::string fillJson;                         // --fill-gaps: tol, the two limits and the ten stats; empty without the flag
     std::string json() const {
         return "{" + jsonNamed(genome::Graph::linkClassNames, classes.v, 8) + "," + jsonNamed(genome::Links::joinStatNames, joins.v, 5) + ",\"mid\":" +
                std::to_string(mid) + ",\"max_span\":" + std::to_string(maxSpan) + ",\"chains\":" + std::to_string(chains) + ",\"cycles\":" + std::to_string(cycles) + "}";
@@ -312,33 +321,43 @@ inline LinkResult linksStage(genome::Graph &graph, genome::Context &ctx, const g
     uint64_t cycles = 0;
     const auto chains = genome::scaffoldChains(joins.e1, joins.e2, &cycles);
     r.chains = chains.size(); r.cycles = cycles;
+    // the gap after every member that joins the next (the closing gap of a cycle stays with the joins: `closing` below)
+    std::map<std::pair<uint32_t, uint32_t>, int64_t> gapOf;
+    for (size_t i = 0; i < joins.e1.size(); i++) gapOf[{joins.e1[i], joins.e2[i]}] = linkGap(r.mid, joins.count[i], joins.sumU[i]);
+    std::vector<std::vector<uint32_t>> members = chains;
+    std::vector<std::vector<int64_t>> gaps(chains.size());
+    for (size_t c = 0; c < chains.size(); c++)
+        for (size_t j = 0; j + 1 < chains[c].size(); j++) gaps[c].push_back(gapOf.at({chains[c][j], chains[c][j + 1]}));
+    if (lo.fillGaps) {                                                                               // both files come from the filled chains
+        const uint64_t tol = lo.fillTol >= 0 ? (uint64_t)lo.fillTol : (rhi - rlo) / 2;
+        auto f = graph.fillGaps(members, gaps, tol, lo.fillMaxEdges, lo.fillMaxPaths);
+        std::fprintf(stderr, "fill-gaps: tol %llu (%s), %llu of %llu junctions filled with %llu edges\n", (unsigned long long)tol,
+                     lo.fillTol >= 0 ? "given" : "half the width of the insert range", (unsigned long long)f.v[6], (unsigned long long)f.v[0], (unsigned long long)f.v[7]);
+        r.fillJson = "{\"tol\":" + std::to_string(tol) + ",\"max_edges\":" + std::to_string(lo.fillMaxEdges) + ",\"max_paths\":" + std::to_string(lo.fillMaxPaths) + "," +
+                     f.json().substr(1);
+        members = std::move(f.chains); gaps = std::move(f.gaps);
+    }
     if (!lo.scaffolds.empty()) {
-        std::map<uint32_t, long long> gapAfter;                                                      // an e1 occurs once among the joins
-        for (size_t i = 0; i < joins.e1.size(); i++) gapAfter[joins.e1[i]] = linkGap(r.mid, joins.count[i], joins.sumU[i]);
         std::ofstream sf(lo.scaffolds);
         sf << "# scaffold chains: maximal paths of joins (the only link of at least " << lo.minSupport << " observations out of one edge and into the next)\n"
            << "# both strands' chains appear, as --contigs --contig-both-strands shows the edges: a chain and the chain of its twins are the same scaffold\n"
            << "# s<i>\t<members>\te<id>\t<gap>\te<id>...; a cycle starts at its smallest id and ends with the closing gap and the word cycle\n";
-        for (size_t i = 0; i < chains.size(); i++) {
-            const auto &c = chains[i];
+        if (lo.fillGaps) sf << "# --fill-gaps: members between two joined edges are the one path the graph holds there; the gap at such a junction is -k\n";
+        for (size_t i = 0; i < members.size(); i++) {
+            const auto &c = members[i];
             sf << "s" << i << "\t" << c.size();
             for (size_t j = 0; j < c.size(); j++) {
                 sf << "\te" << c[j];
-                if (j + 1 < c.size()) sf << "\t" << gapAfter.at(c[j]);
+                if (j + 1 < c.size()) sf << "\t" << gaps[i][j];
             }
-            const auto closing = gapAfter.find(c.back());                                            // the last member of a path joins nothing
-            if (closing != gapAfter.end()) sf << "\t" << closing->second << "\tcycle";
+            const auto closing = gapOf.find({c.back(), c.front()});                                  // the last member of a path joins nothing
+            if (closing != gapOf.end()) sf << "\t" << closing->second << "\tcycle";
             sf << "\n";
         }
         if (!sf) throw std::runtime_error("cannot write " + lo.scaffolds);
     }
     if (!lo.scaffoldFasta.empty()) {
-        std::map<std::pair<uint32_t, uint32_t>, int64_t> gapOf;
-        for (size_t i = 0; i < joins.e1.size(); i++) gapOf[{joins.e1[i], joins.e2[i]}] = linkGap(r.mid, joins.count[i], joins.sumU[i]);
-        std::vector<std::vector<int64_t>> gaps(chains.size());
-        for (size_t c = 0; c < chains.size(); c++)
-            for (size_t j = 0; j + 1 < chains[c].size(); j++) gaps[c].push_back(gapOf.at({chains[c][j], chains[c][j + 1]}));
-        auto sc = graph.scaffolds(chains, gaps, lo.scaffoldMinGap, lo.minLen, lo.scaffoldWidth, lo.scaffoldBoth, true);
+        auto sc = graph.scaffolds(members, gaps, lo.scaffoldMinGap, lo.minLen, lo.scaffoldWidth, lo.scaffoldBoth, true);
         sc.write(lo.scaffoldFasta);
         r.scaffoldsJson = sc.stats().json();
     }

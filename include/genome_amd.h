@@ -883,6 +883,73 @@ int gk_scaffolds_last_ms(const gk_scaffolds *s, float *ms4);
  * GK_E_CAPACITY with *n set and nothing copied. */
 int gk_scaffolds_segments(const gk_scaffolds *s, uint64_t *record, uint32_t *edge, uint64_t *first, uint64_t *bases, uint32_t *skipped, uint64_t cap,
                           uint64_t *n);
+
+/* ---- gap filling: this project's own rule (the reference has no scaffolds) ----
+ * A stage between gk_scaffold_chains and gk_graph_scaffolds_plan: where the graph holds exactly one path of the right length
+ * between two consecutive members of a chain, that path's edges become members.  The junction is then a run of adjacent
+ * junctions, which the scaffold rule joins on their k bases: no N is written there.  Integers only.  The graph is not edited.
+ * Input.  members, chain_off, nchains and gap exactly as gk_graph_scaffolds_plan takes them; tol (bases) 0 .. 2^31-1; max_edges
+ * 1 .. GK_FILL_MAX_EDGES; max_paths 1 .. GK_FILL_MAX_PATHS.
+ * Path.  Take a junction (e, f) of consecutive members with e_end[e] != e_start[f] and G = its gap.  A path is a sequence x1..xm
+ * of live edges, 1 <= m <= max_edges, with e_start[x1] == e_end[e] and e_end[x(i)] == e_start[x(i+1)] throughout; equality is by
+ * node id, as the scaffold rule's `adjacent` is.  An edge may occur twice on a path.  (A live edge that gk_graph_replace_start has
+ * displaced from its start node's out-edge word, as the reference's map does, is on no path, from either side.)  Its sum is S = len(x1) + .. + len(xm)
+ * (every edge has len >= 1) and its gap length is L = S - k: the bases between the end of P(e) and the start of P(f) when the path
+ * ends in e_start[f].  L < 0 (S < k) is legal: the adjacent junctions of the filled chain spell the overlap correctly.
+ * With B = G + tol + k:
+ *   T_fwd  the set of all paths from e_end[e] with S <= B (prefix-closed);
+ *   T_bwd  the set of all edge sequences y1..ym, 1 <= m <= max_edges, S <= B, that run backwards from e_start[f]:
+ *          e_end[y1] == e_start[f], e_start[y(i)] == e_end[y(i+1)];
+ *   hit    a path that ends in e_start[f] with G - tol <= L <= G + tol.  A hit lies in T_fwd, and reversed in T_bwd (it starts
+ *          in e_end[e] there), so the hits are the same from either side.
+ * Classes of a junction, tested in this order (jclass is parallel to members, as gap is; GK_FILL_LAST at a chain's last member):
+ *   adjacent   as in the scaffold rule; nothing is searched, the gap is not looked at;
+ *   overflow   |T_fwd| > max_paths AND |T_bwd| > max_paths.  Set sizes, not a traversal: any implementation decides it alike.
+ *              Both sides, because the twin junction (twin f, twin e) has the mirrored trees: with one side only a chain could be
+ *              filled and its twin chain not;
+ *   none       no hit; B < 1 is this class (nothing is searched);
+ *   ambiguous  two or more hits.  A bubble between e and f stays N: no hit is preferred over another;
+ *   unique     exactly one hit: a candidate.
+ * After all junctions are classed, a candidate is SHARED when any edge of its path is a member of any input chain, lies on
+ * another candidate's path, or occurs twice on its own path: every candidate that touches a contested edge loses, whatever the
+ * order (uses are counted per edge first, then tested).  Every other candidate is FILLED.  jclass holds shared or filled, never
+ * unique.
+ * Output.  The chains in input order; a filled junction e, f becomes e, x1..xm, f; each new junction gets gap -k (the scaffold
+ * plan never looks at it: it is adjacent); every other junction keeps its gap, and so does the unused entry at a chain's last
+ * member.  out_chain_off holds nchains + 1 words.  jlen[j] = L where jclass[j] is shared or filled, else 0.  *n_members = the
+ * members written = chain_off[nchains] + filler_edges; it never exceeds the live edges, since no edge is written twice.
+ * members_cap below it is GK_E_CAPACITY with *n_members and stats10 set and nothing copied.
+ * stats10 = {junctions, adjacent, overflow, none, ambiguous, shared, filled, filler_edges, filler_bases, searched_backward}:
+ * element 0 is the sum of the next six; filler_edges / filler_bases = the sum of m / of S over the filled junctions;
+ * searched_backward = the junctions whose forward tree overflowed (informational, and not strand-symmetric).
+ * Twins.  On a strand-closed graph, a path x1..xm from e_end[e] to e_start[f] comes with (twin xm .. twin x1) from
+ * e_end[twin f] to e_start[twin e], of the same lengths.  So T_fwd of (e, f) is T_bwd of (twin f, twin e) reversed, and the
+ * hits of one are the twins of the hits of the other: with the same G, tol and bounds the two junctions fall into the same
+ * class (overflow takes both trees, hence is symmetric), and a unique hit is the twin of the other's.  An edge is contested
+ * iff its twin is (the uses mirror), so a chain and its twin chain (gk_graph_scaffolds_plan, Strand) are filled alike: the
+ * filled chains are again a chain and its twin chain, and strands = 1 still writes exactly one of them.
+ * Errors.  GK_E_INVALID: the scaffold plan's member and chain errors (an id at or above the bound, or dead; an edge twice; an
+ * empty chain; a chain_off that does not ascend); a parameter out of range; NULL handles or arrays; |G| above 2^31-1 at a junction
+ * that is not adjacent.  All are found on the device before a kernel reads a member's length.  On any error nothing is written
+ * (GK_E_CAPACITY above is the one exception: it sets *n_members and stats10).  The graph is never changed.
+ * The defaults the tools and the Python side pass (max_edges 16, max_paths 256, tol = half the width of the insert range) are
+ * choices, not measurements.
+ * On the device: the scaffold plan's check (one lane per member claims its edge's owner word) and one lane per junction for
+ * adjacent / B < 1; a scan compacts the junctions to search.  k_fill_search: one wave per junction, the tree in LDS (edge, parent
+ * index, running S per entry; GK_FILL_MAX_PATHS entries of 10 bytes = 10 KiB per wave), built level by level: lanes take frontier
+ * entries and read the end node's four out-edge words (the start node's in-edge list for the backward tree), live children
+ * within B are appended by ballot and prefix count, hits are counted by ballot; a direction stops the moment its count passes
+ * max_paths, and the backward tree runs only then.  A unique hit is unwound through the parent indices into HBM in path order.
+ * No global atomics in the search.  Then one atomic add per path edge (uses), one lane per junction (shared / filled), a scan
+ * over the per-member output counts and a write kernel; one read-back at the end.  The in-edge lists are built on every call
+ * (two passes over the edges and a scan over the nodes), needed or not.
+ * Not there: overlap detection for negative gaps, a collective over ranks. */
+#define GK_FILL_MAX_EDGES 64        /* a path's edges: one lane each when a hit is unwound */
+#define GK_FILL_MAX_PATHS 1024      /* entries of one wave's LDS tree: 4 waves x 10 KiB = 40 KiB per workgroup, 4 workgroups per CU */
+enum { GK_FILL_LAST = 0, GK_FILL_ADJACENT = 1, GK_FILL_OVERFLOW = 2, GK_FILL_NONE = 3, GK_FILL_AMBIGUOUS = 4, GK_FILL_SHARED = 5, GK_FILL_FILLED = 6 };
+int gk_graph_fill_gaps(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap, uint64_t tol,
+                       uint32_t max_edges, uint32_t max_paths, uint32_t *out_members, int64_t *out_gap, uint64_t members_cap, uint64_t *out_chain_off,
+                       uint8_t *jclass, int64_t *jlen, uint64_t *n_members, uint64_t *stats10);
 /* live nodes, unspecified order */
 int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap, uint64_t *n);
 /* live edges, unspecified order: start/end k-mer, length in bases, and the edge sequence as 2-bit
