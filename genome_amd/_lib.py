@@ -176,6 +176,9 @@ SIGNATURES = {
     "gk_scaffolds_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "gk_scaffolds_segments": (C.c_int, [vp, u64p, u32p, u64p, u64p, u32p, C.c_uint64, u64p]),
     "gk_graph_fill_gaps": (C.c_int, [vp, u32p, u64p, C.c_uint64, i64p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, i64p, C.c_uint64, u64p, u8p, i64p, u64p, u64p]),
+    "gk_graph_overlap_gaps": (C.c_int, [vp, u32p, u64p, C.c_uint64, i64p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u8p, u64p]),
+    "gk_graph_scaffolds_plan_overlaps": (C.c_int, [vp, u32p, u64p, C.c_uint64, i64p, u32p, C.c_int64, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(vp)]),
+    "gk_scaffolds_overlap_stats": (C.c_int, [vp, u64p]),
     "gk_graph_replace_end": (C.c_int, [vp, C.c_uint32, C.c_uint32]),
     "gk_graph_build": (C.c_int, [vp, C.POINTER(vp)]),
     "gk_graph_destroy": (None, [vp]),

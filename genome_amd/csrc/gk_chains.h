@@ -1,11 +1,11 @@
-// gk_chains.h — the check of a chain list (members, chain_off) that gk_scaffolds.hip and gk_fillgaps.hip share: it runs before any
+// gk_chains.h — the check of a chain list (members, chain_off) that gk_scaffolds.hip, gk_fillgaps.hip and gk_overlaps.hip share: it runs before any
 // kernel reads a member's length, and its owner words say afterwards which edges are members.
 #pragma once
 
 #include "gk_graph.h"
 
 // error flags of the check and of the passes behind it
-enum { SF_BAD_ID = 0, SF_DUPLICATE, SF_CHAIN, SF_GAP, SF_OVERFLOW, SF_N };
+enum { SF_BAD_ID = 0, SF_DUPLICATE, SF_CHAIN, SF_GAP, SF_OVERFLOW, SF_OVERLAP, SF_N };
 
 // one lane per member claims its edge's owner word (a second claim is a duplicate); one lane per chain looks at its bounds
 static __global__ __launch_bounds__(BLOCK) void k_scaf_check(GraphView g, const u32 *__restrict__ members, const unsigned long long *__restrict__ chain_off, u64 nchains,

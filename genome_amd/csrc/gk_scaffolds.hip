@@ -20,17 +20,27 @@
 #include "gk_scan.h"
 
 static constexpr uint8_t SC_SHORT = 1, SC_FORWARD = 2, SC_SELF = 3, SC_REVERSE = 4;
-static constexpr uint8_t MC_FIRST = 0, MC_ADJACENT = 1, MC_GAPPED = 2, MC_CLAMPED = 3;
+static constexpr uint8_t MC_FIRST = 0, MC_ADJACENT = 1, MC_GAPPED = 2, MC_CLAMPED = 3, MC_OVERLAPPED = 4;
 // device counters of a plan
-enum { SS_FORWARD = 0, SS_SELF, SS_REVERSE, SS_SINGLE, SS_MEMBERS, SS_ADJACENT, SS_GAPPED, SS_CLAMPED, SS_NBASES, SS_BASES, SS_OVERFLOW, SS_N };
+enum { SS_FORWARD = 0, SS_SELF, SS_REVERSE, SS_SINGLE, SS_MEMBERS, SS_ADJACENT, SS_GAPPED, SS_CLAMPED, SS_NBASES, SS_BASES, SS_OVERFLOW, SS_OVERLAPPED, SS_DROPPED, SS_N };
 static constexpr int SCAFFOLD_STATS = 13;
 
 // ---------------------------------------------------------------------------------------------
 // checks: before any kernel reads a member's length (k_scaf_check and the error flags: gk_chains.h)
 // ---------------------------------------------------------------------------------------------
-// Member j of chain c fills slots 2j (an N run, or nothing) and 2j + 1 (its piece).  Runs only behind a clean check.
+// Member j of chain c fills slots 2j (an N run, or nothing) and 2j + 1 (its piece).  Runs only behind a clean check.  `overlap`
+// (may be null) is the caller's and is not trusted: an entry that the rule cannot have given raises SF_OVERLAP.
+__device__ __forceinline__ bool scaf_overlap_holds(const GraphView &g, u32 p, u32 e, u64 pp, u32 o) {
+    const u32 sp = g.e_start[p], se = g.e_start[e];
+    const u64 plo = g.node_lo[sp], phi = g.k > 32 ? g.node_hi[sp] : 0ull, elo = g.node_lo[se], ehi = g.k > 32 ? g.node_hi[se] : 0ull;
+    const uint8_t *pseq = g.pool + g.e_off[p], *eseq = g.pool + g.e_off[e];
+    bool same = true;
+    for (u32 i = 0; i < o; i++) same &= path_base(plo, phi, pseq, g.k, pp - o + i) == path_base(elo, ehi, eseq, g.k, i);
+    return same;
+}
 __global__ __launch_bounds__(BLOCK) void k_scaf_segments(GraphView g, const u32 *__restrict__ members, const unsigned long long *__restrict__ chain_off, u64 nchains,
-                                                         u64 nm, const long long *__restrict__ gap, long long min_gap, u32 *flags, u32 *__restrict__ chain_of,
+                                                         u64 nm, const long long *__restrict__ gap, const u32 *__restrict__ overlap, long long min_gap, u32 *flags,
+                                                         u32 *__restrict__ chain_of,
                                                          uint8_t *__restrict__ mclass, u32 *__restrict__ slot_len, u32 *__restrict__ slot_edge,
                                                          uint8_t *__restrict__ slot_skip) {
     if (flags[SF_BAD_ID] | flags[SF_DUPLICATE] | flags[SF_CHAIN]) return;
@@ -43,22 +53,31 @@ __global__ __launch_bounds__(BLOCK) void k_scaf_segments(GraphView g, const u32 
         const u32 e = members[j];
         uint8_t cls = MC_FIRST;
         u64 run = 0;
+        u32 skip = 0;
         if (j != chain_off[lo]) {
             const u32 p = members[j - 1];
-            if (g.e_end[p] == g.e_start[e]) cls = MC_ADJACENT;
-            else {
+            const u32 o = overlap ? overlap[j - 1] : 0u;
+            if (g.e_end[p] == g.e_start[e]) {
+                cls = MC_ADJACENT; skip = (u32)g.k;
+                if (o) flags[SF_OVERLAP] = 1;
+            } else if (o) {                                  // below both path lengths, and the o bases are the same
+                const u64 pp = (u64)g.k + g.e_len[p], pe = (u64)g.k + g.e_len[e];
+                cls = MC_OVERLAPPED;
+                if (o > GK_OVERLAP_MAX || o >= pp || o >= pe || !scaf_overlap_holds(g, p, e, pp, o)) flags[SF_OVERLAP] = 1;
+                else skip = o;
+            } else {
                 const long long gp = gap[j - 1];
                 cls = gp < min_gap ? MC_CLAMPED : MC_GAPPED;
                 if (gp > 0x7fffffffll) flags[SF_GAP] = 1;
                 else run = (u64)max(gp, min_gap);
             }
         }
-        u64 piece = cls == MC_ADJACENT ? g.e_len[e] : (u64)g.k + g.e_len[e];
+        u64 piece = (u64)g.k + g.e_len[e] - skip;
         if (piece > 0xffffffffull) { flags[SF_OVERFLOW] = 1; piece = 0; }
         chain_of[j] = (u32)lo;
         mclass[j] = cls;
         slot_len[2 * j] = (u32)run;       slot_edge[2 * j] = NONE;  slot_skip[2 * j] = 0;
-        slot_len[2 * j + 1] = (u32)piece; slot_edge[2 * j + 1] = e; slot_skip[2 * j + 1] = cls == MC_ADJACENT ? (uint8_t)g.k : (uint8_t)0;
+        slot_len[2 * j + 1] = (u32)piece; slot_edge[2 * j + 1] = e; slot_skip[2 * j + 1] = (uint8_t)skip;
     }
 }
 
@@ -98,13 +117,15 @@ __global__ __launch_bounds__(BLOCK) void k_scaf_strand(GraphView g, const unsign
     for (u64 c = (u64)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); c < nchains; c += waves) {      // (uniform over the wave)
         const u64 m0 = chain_off[c], m1 = chain_off[c + 1], s0 = 2 * m0, s1 = 2 * m1;
         const u64 b0 = slot_base[s0], n = slot_base[s1] - b0;
-        u64 gaps = 0, adj = 0, gapped = 0, clamped = 0;
+        u64 gaps = 0, adj = 0, gapped = 0, clamped = 0, ovl = 0, dropped = 0;
         for (u64 j = m0 + (u64)lane; j < m1; j += 64) {
             const uint8_t mc = mclass[j];
             gaps += slot_len[2 * j];
-            adj += mc == MC_ADJACENT; gapped += mc >= MC_GAPPED; clamped += mc == MC_CLAMPED;
+            adj += mc == MC_ADJACENT; gapped += mc == MC_GAPPED || mc == MC_CLAMPED; clamped += mc == MC_CLAMPED;
+            if (mc == MC_OVERLAPPED) { ovl++; dropped += slot_skip[2 * j + 1]; }
         }
         gaps = wave_sum(gaps); adj = wave_sum(adj); gapped = wave_sum(gapped); clamped = wave_sum(clamped);
+        if (__any(ovl != 0)) { ovl = wave_sum(ovl); dropped = wave_sum(dropped); }
         uint8_t cl = SC_SELF;
         const u64 half = (n + 1) / 2;                        // (the complement is an involution: the second half repeats the first)
         for (u64 i0 = 0; i0 < half; i0 += 64) {
@@ -133,6 +154,7 @@ __global__ __launch_bounds__(BLOCK) void k_scaf_strand(GraphView g, const unsign
                 if (adj) atomicAdd(&stats[SS_ADJACENT], (unsigned long long)adj);
                 if (gapped) atomicAdd(&stats[SS_GAPPED], (unsigned long long)gapped);
                 if (clamped) atomicAdd(&stats[SS_CLAMPED], (unsigned long long)clamped);
+                if (ovl) { atomicAdd(&stats[SS_OVERLAPPED], (unsigned long long)ovl); atomicAdd(&stats[SS_DROPPED], (unsigned long long)dropped); }
                 if (gaps) atomicAdd(&stats[SS_NBASES], (unsigned long long)gaps);
                 atomicAdd(&stats[SS_BASES], (unsigned long long)n);
             }
@@ -206,7 +228,7 @@ struct ScafPlan {
     const u32 *rec_m, *rec_gaps;             // [chain_recs] members, N bases
     const u32 *seg_edge;                     // NONE: an N run
     const u32 *seg_start;                    // its first base in the record
-    const uint8_t *seg_skip;                 // bases of the edge's path left out before it: 0 or k
+    const uint8_t *seg_skip;                 // bases of the edge's path left out before it: 0, k, or an overlap (<= GK_OVERLAP_MAX)
     u64 records, chain_recs;
     u32 line_width;
 };
@@ -374,6 +396,7 @@ struct gk_scaffolds {
     u64 epoch = 0;                       // the graph's when the plan was made: any edit since makes the plan stale
     u32 line_width = 0;
     u64 stats[SCAFFOLD_STATS] = {};
+    u64 ovl_stats[2] = {};               // overlapped junctions of the chain records, and the bases they dropped
     u64 records = 0, chain_recs = 0, segs = 0, text_bytes = 0;
     // the plan, on the device: what the text is a pure function of
     u32 *d_rec_id = nullptr, *d_rec_n = nullptr, *d_rec_m = nullptr, *d_rec_gaps = nullptr, *d_seg_edge = nullptr, *d_seg_start = nullptr;
@@ -409,23 +432,11 @@ void scaffolds_drop_plan(gk_scaffolds *s) {      // the plan's buffers are still
 
 }  // namespace
 
-extern "C" {
+extern "C" void gk_scaffolds_destroy(gk_scaffolds *s);
 
-void gk_scaffolds_destroy(gk_scaffolds *s) {
-    if (!s) return;
-    if (s->ctx) {
-        (void)hipSetDevice(s->ctx->device);
-        text_free_buffers(&s->ts);
-        for (void *p : {(void *)s->d_rec_id, (void *)s->d_rec_n, (void *)s->d_rec_m, (void *)s->d_rec_gaps, (void *)s->d_seg_edge, (void *)s->d_seg_start,
-                        (void *)s->d_rec_off, (void *)s->d_rec_seg, (void *)s->d_seg_skip})
-            (void)pool_free(s->ctx, p);
-    }
-    delete s;
-}
-
-int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap, int64_t min_gap,
-                            uint64_t min_len, uint32_t line_width, int strands, int singletons, gk_scaffolds **out) {
-    const char *who = "gk_graph_scaffolds_plan";
+// gk_graph_scaffolds_plan is the `overlap` == nullptr case
+static int scaffolds_plan(const char *who, gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap,
+                          const uint32_t *overlap, int64_t min_gap, uint64_t min_len, uint32_t line_width, int strands, int singletons, gk_scaffolds **out) {
     if (!out) return fail(g ? g->ctx : nullptr, GK_E_INVALID, std::string(who) + ": out is NULL");
     *out = nullptr;
     if (int rc = check_graph(g)) return rc;
@@ -446,7 +457,7 @@ int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t
     if (ne == 0) { *out = s.release(); return GK_OK; }
     const u64 T = nchains + ne, U = 2 * nm + ne;
     DevScratch tmp(ctx);
-    u32 *d_members = nullptr, *d_owner = nullptr, *d_flags = nullptr, *d_chain_of = nullptr, *d_slot_len = nullptr, *d_slot_edge = nullptr, *d_sel = nullptr,
+    u32 *d_members = nullptr, *d_overlap = nullptr, *d_owner = nullptr, *d_flags = nullptr, *d_chain_of = nullptr, *d_slot_len = nullptr, *d_slot_edge = nullptr, *d_sel = nullptr,
         *d_size = nullptr, *d_chain_n = nullptr, *d_chain_gaps = nullptr, *d_flag = nullptr, h_flags[SF_N] = {};
     uint8_t *d_mclass = nullptr, *d_slot_skip = nullptr;
     long long *d_gap = nullptr;
@@ -455,6 +466,7 @@ int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t
     const u64 zero_off[1] = {0};
     if (nm) { tmp.upload(&d_members, members, nm); tmp.upload(&d_gap, gap, nm); }
     else { tmp.get(&d_members, 1); tmp.get(&d_gap, 1); }
+    if (nm && overlap) tmp.upload(&d_overlap, overlap, nm);
     tmp.upload(&d_chain_off, nchains ? chain_off : zero_off, nchains + 1);
     tmp.zeroed(&d_owner, ne);
     tmp.zeroed(&d_flags, SF_N);
@@ -473,17 +485,19 @@ int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t
     tmp.get(&d_rank, T + 1);
     tmp.get(&d_off, T + 1);
     tmp.get(&d_segrank, U + 1);
-    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_scaffolds_plan: scratch");
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), (std::string(who) + ": scratch").c_str());
     // the checks, and the segments behind them; one read of the flags
     hipLaunchKernelGGL(k_scaf_check, dim3(ggrid(ctx, std::max(nm, (u64)nchains))), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_owner,
                        d_flags);
-    hipLaunchKernelGGL(k_scaf_segments, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_gap, (long long)min_gap,
-                       d_flags, d_chain_of, d_mclass, d_slot_len, d_slot_edge, d_slot_skip);
+    hipLaunchKernelGGL(k_scaf_segments, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_gap, d_overlap,
+                       (long long)min_gap, d_flags, d_chain_of, d_mclass, d_slot_len, d_slot_edge, d_slot_skip);
     GK_HIP(ctx, read_back(ctx, h_flags, d_flags, SF_N));
     if (h_flags[SF_CHAIN]) return fail(ctx, GK_E_INVALID, std::string(who) + ": an empty chain, or a chain_off that does not ascend");
     if (h_flags[SF_BAD_ID]) return fail(ctx, GK_E_INVALID, std::string(who) + ": a member that is no live edge of this graph");
     if (h_flags[SF_DUPLICATE]) return fail(ctx, GK_E_INVALID, std::string(who) + ": an edge occurs twice in the chains");
     if (h_flags[SF_GAP]) return fail(ctx, GK_E_INVALID, std::string(who) + ": a gap above 2^31-1");
+    if (h_flags[SF_OVERLAP])
+        return fail(ctx, GK_E_INVALID, std::string(who) + ": an overlap at an adjacent junction, above GK_OVERLAP_MAX, not below both path lengths, or whose bases differ");
     if (h_flags[SF_OVERFLOW]) return fail(ctx, GK_E_CAPACITY, std::string(who) + ": a record of 2^32 bytes or more");
     // every slot's place in its scaffold, the strand and size of every chain, the edges no chain claimed
     GK_HIP(ctx, scan_counts(ctx, tmp, d_slot_len, 2 * nm, d_slot_base));
@@ -517,13 +531,13 @@ int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t
     tmp.get(&s->d_seg_edge, h_segs);
     tmp.get(&s->d_seg_start, h_segs);
     tmp.get(&s->d_seg_skip, h_segs);
-    if (tmp.error() != hipSuccess) { scaffolds_drop_plan(s.get()); return hip_fail(ctx, tmp.error(), "gk_graph_scaffolds_plan: the plan"); }
+    if (tmp.error() != hipSuccess) { scaffolds_drop_plan(s.get()); return hip_fail(ctx, tmp.error(), (std::string(who) + ": the plan").c_str()); }
     hipLaunchKernelGGL(k_scaf_compact_recs, dim3(ggrid(ctx, T + 1)), dim3(BLOCK), 0, ctx->stream, v, (u64)nchains, nm, d_chain_off, d_sel, d_rank, d_off, d_segrank,
                        d_chain_n, d_chain_gaps, s->d_rec_id, s->d_rec_off, s->d_rec_seg, s->d_rec_n, s->d_rec_m, s->d_rec_gaps);
     hipLaunchKernelGGL(k_scaf_compact_segs, dim3(ggrid(ctx, U)), dim3(BLOCK), 0, ctx->stream, ne, nm, d_chain_off, d_chain_of, d_flag, d_segrank, d_slot_base, d_slot_edge,
                        d_slot_skip, s->d_seg_edge, s->d_seg_start, s->d_seg_skip);
     const hipError_t e = read_back(ctx, {});
-    if (e != hipSuccess) { scaffolds_drop_plan(s.get()); return hip_fail(ctx, e, "gk_graph_scaffolds_plan: compaction"); }
+    if (e != hipSuccess) { scaffolds_drop_plan(s.get()); return hip_fail(ctx, e, (std::string(who) + ": compaction").c_str()); }
     for (void *p : {(void *)s->d_rec_id, (void *)s->d_rec_n, (void *)s->d_rec_m, (void *)s->d_rec_gaps, (void *)s->d_seg_edge, (void *)s->d_seg_start,
                     (void *)s->d_rec_off, (void *)s->d_rec_seg, (void *)s->d_seg_skip})
         tmp.take(p);
@@ -533,14 +547,46 @@ int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t
     st[4] = h_stats[SS_SINGLE]; st[5] = h_records; st[6] = h_stats[SS_MEMBERS];
     st[7] = h_stats[SS_ADJACENT]; st[8] = h_stats[SS_GAPPED]; st[9] = h_stats[SS_CLAMPED];
     st[10] = h_stats[SS_NBASES]; st[11] = h_stats[SS_BASES]; st[12] = h_bytes;
+    s->ovl_stats[0] = h_stats[SS_OVERLAPPED]; s->ovl_stats[1] = h_stats[SS_DROPPED];
     *out = s.release();
     return GK_OK;
+}
+
+extern "C" {
+
+void gk_scaffolds_destroy(gk_scaffolds *s) {
+    if (!s) return;
+    if (s->ctx) {
+        (void)hipSetDevice(s->ctx->device);
+        text_free_buffers(&s->ts);
+        for (void *p : {(void *)s->d_rec_id, (void *)s->d_rec_n, (void *)s->d_rec_m, (void *)s->d_rec_gaps, (void *)s->d_seg_edge, (void *)s->d_seg_start,
+                        (void *)s->d_rec_off, (void *)s->d_rec_seg, (void *)s->d_seg_skip})
+            (void)pool_free(s->ctx, p);
+    }
+    delete s;
+}
+
+int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap, int64_t min_gap,
+                            uint64_t min_len, uint32_t line_width, int strands, int singletons, gk_scaffolds **out) {
+    return scaffolds_plan("gk_graph_scaffolds_plan", g, members, chain_off, nchains, gap, nullptr, min_gap, min_len, line_width, strands, singletons, out);
+}
+
+int gk_graph_scaffolds_plan_overlaps(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap, const uint32_t *overlap,
+                                     int64_t min_gap, uint64_t min_len, uint32_t line_width, int strands, int singletons, gk_scaffolds **out) {
+    return scaffolds_plan("gk_graph_scaffolds_plan_overlaps", g, members, chain_off, nchains, gap, overlap, min_gap, min_len, line_width, strands, singletons, out);
 }
 
 int gk_scaffolds_stats(const gk_scaffolds *s, uint64_t *stats13) {
     if (!s || !s->ctx) return fail(nullptr, GK_E_INVALID, "gk_scaffolds_stats: null scaffolds handle");
     if (!stats13) return fail(s->ctx, GK_E_INVALID, "gk_scaffolds_stats: stats13 is NULL");
     for (int i = 0; i < SCAFFOLD_STATS; i++) stats13[i] = s->stats[i];
+    return GK_OK;
+}
+
+int gk_scaffolds_overlap_stats(const gk_scaffolds *s, uint64_t *stats2) {
+    if (!s || !s->ctx) return fail(nullptr, GK_E_INVALID, "gk_scaffolds_overlap_stats: null scaffolds handle");
+    if (!stats2) return fail(s->ctx, GK_E_INVALID, "gk_scaffolds_overlap_stats: stats2 is NULL");
+    stats2[0] = s->ovl_stats[0]; stats2[1] = s->ovl_stats[1];
     return GK_OK;
 }
 

@@ -226,14 +226,17 @@ class HipGraph:
         return Contigs(self, h)
 
     # ---- scaffolds as FASTA (this project's own rule: include/genome_amd.h) --------------------------------------------
-    def scaffolds(self, chains, gaps, min_gap: int = 10, min_len: int = 0, line_width: int = 60, strands: int = 1, singletons: bool = True) -> "Scaffolds":
+    def scaffolds(self, chains, gaps, min_gap: int = 10, min_len: int = 0, line_width: int = 60, strands: int = 1, singletons: bool = True,
+                  overlaps=None) -> "Scaffolds":
         """The chains (lists of edge ids, scaffoldChains') as FASTA text, planned on the device: one record
         `>s<c> len=<n> contigs=<m> gaps=<N bases>` per chain whose sequence is not above its reverse complement (strands = 2:
         every chain).  Consecutive members that meet in a node are joined on its k bases; between any others go
         max(gap, min_gap) bases N, `gaps[c][i]` being the gap after member i of chain c (scaffoldGaps; an entry for the last member
         may be left out or is ignored).  singletons: the live edges in no chain follow as contigs() would write them (min_len
-        applies to them alone).  min_gap = 10 is a choice, not a measurement.  -> a Scaffolds: stats(), read(), text(), write(),
-        segments().  Any edit of the graph makes it stale (GkError GK_E_STATE)."""
+        applies to them alone).  min_gap = 10 is a choice, not a measurement.  overlaps: overlapGaps' lists, in the shape of `gaps`;
+        where overlaps[c][i] = o > 0 nothing goes between the two members and the next one contributes its path from base o (the
+        plan checks every o against the paths: GkError GK_E_INVALID for one that does not hold).  -> a Scaffolds: stats(),
+        overlapStats(), read(), text(), write(), segments().  Any edit of the graph makes it stale (GkError GK_E_STATE)."""
         if not self.h or not self.ctx.h:
             raise L.GkError(L.GK_E_STATE, "the graph is closed")
         chains = [list(c) for c in chains]
@@ -243,9 +246,45 @@ class HipGraph:
         off = np.zeros(len(chains) + 1, np.uint64)
         off[1:] = np.cumsum([len(c) for c in chains])
         h = L.vp()
-        L.check(L.lib().gk_graph_scaffolds_plan(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64), int(min_gap),
-                                                int(min_len), int(line_width), int(strands), int(bool(singletons)), C.byref(h)), self.ctx.h)
+        if overlaps is None:
+            L.check(L.lib().gk_graph_scaffolds_plan(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64), int(min_gap),
+                                                    int(min_len), int(line_width), int(strands), int(bool(singletons)), C.byref(h)), self.ctx.h)
+            return Scaffolds(self, h)
+        if len(overlaps) != len(chains) or not all(len(c) - 1 <= len(o) <= len(c) for c, o in zip(chains, overlaps)):
+            raise ValueError("scaffolds: one overlap list per chain, with an entry per junction")
+        ovl = np.array([x for c, o in zip(chains, overlaps) for x in list(o)[:len(c) - 1] + [0]], np.uint32) if len(members) else np.zeros(0, np.uint32)
+        L.check(L.lib().gk_graph_scaffolds_plan_overlaps(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64),
+                                                         L.ptr(ovl, C.c_uint32), int(min_gap), int(min_len), int(line_width), int(strands), int(bool(singletons)),
+                                                         C.byref(h)), self.ctx.h)
         return Scaffolds(self, h)
+
+    # ---- overlap detection (this project's own rule: include/genome_amd.h) ---------------------------------------------
+    def overlapGaps(self, chains, gaps, tol: int, min_overlap: int = 10, max_overlap=None):
+        """Between fillGaps (or scaffoldChains / scaffoldGaps) and scaffolds(): where the last o bases of a member's path equal the
+        first o bases of the next member's, exactly, for exactly one o in min_overlap .. max_overlap within `tol` of -gap (and
+        below both path lengths), the junction is an overlap of o bases -> (overlaps, report): overlaps[c][i] = o after member i
+        of chain c, else 0, the shape scaffolds(overlaps=) takes; report = the seven stats named as OVERLAP_STATS, plus
+        "classes": per chain the class name of every junction (OVERLAP_CLASSES).  max_overlap None means k.  min_overlap = 10 and
+        max_overlap = k are choices, not measurements (a chance match of 10 bases is about 1e-6 per candidate).  The graph is not
+        edited and the chains are not rewritten."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        chains = [list(c) for c in chains]
+        if len(gaps) != len(chains) or not all(len(c) - 1 <= len(g) <= len(c) for c, g in zip(chains, gaps)):
+            raise ValueError("overlapGaps: one gap list per chain, with an entry per junction")
+        members = np.array([e for c in chains for e in c], np.uint32)
+        gap = np.array([x for c, g in zip(chains, gaps) for x in list(g)[:len(c) - 1] + [0]], np.int64) if len(members) else np.zeros(0, np.int64)
+        off = np.zeros(len(chains) + 1, np.uint64)
+        off[1:] = np.cumsum([len(c) for c in chains])
+        nm = len(members)
+        ovl, jclass, st = np.zeros(max(nm, 1), np.uint32), np.zeros(max(nm, 1), np.uint8), np.zeros(len(OVERLAP_STATS), np.uint64)
+        L.check(L.lib().gk_graph_overlap_gaps(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64), int(tol),
+                                              int(min_overlap), int(self.k if max_overlap is None else max_overlap), L.ptr(ovl, C.c_uint32),
+                                              L.ptr(jclass, C.c_uint8), L.ptr(st, C.c_uint64)), self.ctx.h)
+        i = off.tolist()
+        report = dict(zip(OVERLAP_STATS, (int(x) for x in st)))
+        report["classes"] = [[OVERLAP_CLASSES[x] for x in jclass[a:b - 1].tolist()] for a, b in zip(i, i[1:])]
+        return [ovl[a:b - 1].tolist() for a, b in zip(i, i[1:])], report
 
     # ---- gap filling (this project's own rule: include/genome_amd.h) ---------------------------------------------------
     def fillGaps(self, chains, gaps, tol: int, max_edges: int = 16, max_paths: int = 256):
@@ -464,6 +503,10 @@ SCAFFOLD_STATS = ("chains", "chain_forward", "chain_self_twin", "chain_reverse",
 FILL_STATS = ("junctions", "adjacent", "overflow", "none", "ambiguous", "shared", "filled", "filler_edges", "filler_bases", "searched_backward")
 # the names of the GK_FILL_* class codes, by code
 FILL_CLASSES = ("last", "adjacent", "overflow", "none", "ambiguous", "shared", "filled")
+# the statistics of gk_graph_overlap_gaps, in the order of its `stats7` array: junctions is the sum of the five after it
+OVERLAP_STATS = ("junctions", "adjacent", "out_of_range", "none", "ambiguous", "overlap", "overlap_bases")
+# the names of the GK_OVL_* class codes, by code
+OVERLAP_CLASSES = ("last", "adjacent", "out_of_range", "none", "ambiguous", "overlap")
 
 
 class Scaffolds:
@@ -499,6 +542,15 @@ class Scaffolds:
         L.check(L.lib().gk_scaffolds_stats(self.h, L.ptr(st, C.c_uint64)), self.ctx.h)
         return dict(zip(SCAFFOLD_STATS, (int(x) for x in st)))
 
+    def overlapStats(self) -> dict:
+        """{overlapped: junctions of the chain records written that scaffolds(overlaps=) joined on an overlap, dropped: the bases
+        they left out}; adjacent + gapped + overlapped = members - chain records"""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the scaffolds are closed")
+        st = np.zeros(2, np.uint64)
+        L.check(L.lib().gk_scaffolds_overlap_stats(self.h, L.ptr(st, C.c_uint64)), self.ctx.h)
+        return {"overlapped": int(st[0]), "dropped": int(st[1])}
+
     def read(self, offset: int, n: int) -> bytes:
         """bytes [offset, offset + n) of the text, fewer at its end; GkError GK_E_INVALID for an offset beyond it"""
         self._live()
@@ -523,7 +575,7 @@ class Scaffolds:
 
     def segments(self) -> list:
         """which piece of which edge lies where: [(record index in the text, edge id, first base in the record's sequence, bases
-        written, bases of the edge's path skipped before them: 0 or k)] in text order; N runs are the bases between rows"""
+        written, bases of the edge's path skipped before them: 0, k, or an overlap)] in text order; N runs are the bases between rows"""
         if not self.h or not self.ctx.h:
             raise L.GkError(L.GK_E_STATE, "the scaffolds are closed")
         st = self.stats()

@@ -652,6 +652,12 @@ class Scaffolds {
         out.resize((size_t)got);
         return out;
     }
+    // {junctions joined on an overlap, bases they left out} over the chain records written (Graph::scaffolds with overlaps)
+    std::pair<uint64_t, uint64_t> overlapStats() const {
+        uint64_t v[2] = {};
+        check(gk_scaffolds_overlap_stats(h_, v), ctx_);
+        return {v[0], v[1]};
+    }
     std::string text() { return read(0, stats().textBytes()); }
     void write(const std::string &path) { check(gk_scaffolds_write(h_, path.c_str()), ctx_); }
     std::vector<Segment> segments() const {
@@ -899,22 +905,46 @@ class Graph {
     // after member i of chain c (an entry for the last member may be left out).  minGap = 10 is a choice, not a measurement.
     Scaffolds scaffolds(const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps, int64_t minGap = 10, uint64_t minLen = 0,
                         uint32_t lineWidth = 60, bool bothStrands = false, bool singletons = true) const {
-        if (chains.size() != gaps.size()) throw GkError(GK_E_INVALID, "scaffolds: as many gap lists as chains");
+        return scaffoldsPlan(chains, gaps, nullptr, minGap, minLen, lineWidth, bothStrands, singletons);
+    }
+    // The same with overlapGaps' overlaps (include/genome_amd.h, "overlap detection"): where overlaps[c][i] = o > 0 nothing goes between
+    // the two members and the next one contributes its path from base o.  The plan checks every o against the paths.
+    Scaffolds scaffolds(const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps,
+                        const std::vector<std::vector<uint32_t>> &overlaps, int64_t minGap = 10, uint64_t minLen = 0, uint32_t lineWidth = 60, bool bothStrands = false,
+                        bool singletons = true) const {
+        return scaffoldsPlan(chains, gaps, &overlaps, minGap, minLen, lineWidth, bothStrands, singletons);
+    }
+    // Overlap detection between fillGaps (or scaffoldChains) and scaffolds (include/genome_amd.h, "overlap detection"): where the last o
+    // bases of a member's path equal the first o of the next member's, exactly, for exactly one o in minOverlap .. maxOverlap within tol
+    // of -gap, overlaps[c][i] = o, else 0.  classes[c][i]: the GK_OVL_* class of the junction after member i of chain c.  maxOverlap 0
+    // means k.  minOverlap = 10 and maxOverlap = k are choices, not measurements (a chance match of 10 bases: about 1e-6 per candidate).
+    struct Overlapped {
+        std::vector<std::vector<uint32_t>> overlaps;
+        std::vector<std::vector<uint8_t>> classes;
+        uint64_t v[7] = {};                                      // gk_graph_overlap_gaps' stats7, under these names
+        std::string json() const {
+            const char *names[7] = {"junctions", "adjacent", "out_of_range", "none", "ambiguous", "overlap", "overlap_bases"};
+            std::string s = "{";
+            for (int i = 0; i < 7; i++) s += std::string(i ? ",\"" : "\"") + names[i] + "\":" + std::to_string(v[i]);
+            return s + "}";
+        }
+    };
+    Overlapped overlapGaps(const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps, uint64_t tol, uint32_t minOverlap = 10,
+                           uint32_t maxOverlap = 0) const {
         std::vector<uint32_t> members;
         std::vector<int64_t> gap;
-        std::vector<uint64_t> off(1, 0);
+        std::vector<uint64_t> off;
+        flatten("overlapGaps", chains, gaps, members, gap, off);
+        std::vector<uint32_t> ovl(members.size() + 1);
+        std::vector<uint8_t> jclass(members.size() + 1);
+        Overlapped r;
+        check(gk_graph_overlap_gaps(h_, members.data(), off.data(), chains.size(), gap.data(), tol, minOverlap, maxOverlap ? maxOverlap : (uint32_t)k_, ovl.data(),
+                                    jclass.data(), r.v), ctx_.handle());
         for (size_t c = 0; c < chains.size(); c++) {
-            if (gaps[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, "scaffolds: a chain with fewer gaps than junctions");
-            for (size_t j = 0; j < chains[c].size(); j++) {
-                members.push_back(chains[c][j]);
-                gap.push_back(j + 1 < chains[c].size() ? gaps[c][j] : 0);
-            }
-            off.push_back(members.size());
+            r.overlaps.emplace_back(ovl.begin() + off[c], ovl.begin() + off[c + 1] - 1);
+            r.classes.emplace_back(jclass.begin() + off[c], jclass.begin() + off[c + 1] - 1);
         }
-        gk_scaffolds *s = nullptr;
-        check(gk_graph_scaffolds_plan(h_, members.data(), off.data(), chains.size(), gap.data(), minGap, minLen, lineWidth, bothStrands ? 2 : 1, singletons ? 1 : 0, &s),
-              ctx_.handle());
-        return Scaffolds(ctx_.handle(), s);
+        return r;
     }
     // Gap filling between scaffoldChains and scaffolds (include/genome_amd.h, "gap filling"): where the graph holds exactly one path
     // of at most maxEdges edges between two consecutive members whose length is within tol bases of the gap, and no edge of it is
@@ -982,6 +1012,42 @@ class Graph {
     }
 
   private:
+    // chains and their per-junction gaps as the C calls take them: members, a gap per member (0 at a chain's last), chain_off
+    static void flatten(const char *who, const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps,
+                        std::vector<uint32_t> &members, std::vector<int64_t> &gap, std::vector<uint64_t> &off) {
+        if (chains.size() != gaps.size()) throw GkError(GK_E_INVALID, std::string(who) + ": as many gap lists as chains");
+        off.assign(1, 0);
+        for (size_t c = 0; c < chains.size(); c++) {
+            if (gaps[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, std::string(who) + ": a chain with fewer gaps than junctions");
+            for (size_t j = 0; j < chains[c].size(); j++) {
+                members.push_back(chains[c][j]);
+                gap.push_back(j + 1 < chains[c].size() ? gaps[c][j] : 0);
+            }
+            off.push_back(members.size());
+        }
+    }
+    Scaffolds scaffoldsPlan(const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps,
+                            const std::vector<std::vector<uint32_t>> *overlaps, int64_t minGap, uint64_t minLen, uint32_t lineWidth, bool bothStrands,
+                            bool singletons) const {
+        std::vector<uint32_t> members, ovl;
+        std::vector<int64_t> gap;
+        std::vector<uint64_t> off;
+        flatten("scaffolds", chains, gaps, members, gap, off);
+        gk_scaffolds *s = nullptr;
+        if (!overlaps) {
+            check(gk_graph_scaffolds_plan(h_, members.data(), off.data(), chains.size(), gap.data(), minGap, minLen, lineWidth, bothStrands ? 2 : 1, singletons ? 1 : 0,
+                                          &s), ctx_.handle());
+            return Scaffolds(ctx_.handle(), s);
+        }
+        if (overlaps->size() != chains.size()) throw GkError(GK_E_INVALID, "scaffolds: as many overlap lists as chains");
+        for (size_t c = 0; c < chains.size(); c++) {
+            if ((*overlaps)[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, "scaffolds: a chain with fewer overlaps than junctions");
+            for (size_t j = 0; j < chains[c].size(); j++) ovl.push_back(j + 1 < chains[c].size() ? (*overlaps)[c][j] : 0);
+        }
+        check(gk_graph_scaffolds_plan_overlaps(h_, members.data(), off.data(), chains.size(), gap.data(), ovl.data(), minGap, minLen, lineWidth, bothStrands ? 2 : 1,
+                                               singletons ? 1 : 0, &s), ctx_.handle());
+        return Scaffolds(ctx_.handle(), s);
+    }
     Graph(Context &ctx, int k) : ctx_(ctx), k_(k) {}
     Context &ctx_;
     int k_;

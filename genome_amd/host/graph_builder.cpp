@@ -5,7 +5,7 @@
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
 //                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]]
-//                 [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]]]   (with --walk-pairs: graph_simplifier.cpp says what they write)
+//                 [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]]   (with --walk-pairs: graph_simplifier.cpp says what they write)
 //                 [--out prefix] [--save-graph PATH] [--correct N|auto]
 //                 [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
@@ -63,7 +63,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]]] [--out prefix] [--save-graph PATH] "
+                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]] [--out prefix] [--save-graph PATH] "
                              "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
@@ -216,6 +216,7 @@ int main(int argc, char **argv) {
             const LinkResult lr = linksStage(graph, ctx, data, takeFirst, link, walk, &walked);
             jsonPut(js, "links", lr.json());
             if (!lr.fillJson.empty()) jsonPut(js, "fill", lr.fillJson);
+            if (!lr.overlapJson.empty()) jsonPut(js, "overlap", lr.overlapJson);
             if (!lr.scaffoldsJson.empty()) jsonPut(js, "scaffolds", lr.scaffoldsJson);
         }
         if (!contig.path.empty()) jsonPut(js, "contigs_fasta", fasta.json());

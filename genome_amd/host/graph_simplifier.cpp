@@ -6,7 +6,7 @@
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
 //                    [--take-first N] [--thread-reads [--no-pairs]]
 //                    [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
-//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]]]
+//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]]
 //                    [--world W --rank R --id-file PATH]
 //   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
 //   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
@@ -48,6 +48,12 @@
 //   from the filled chains.  TOL defaults to half the width of the insert range the stage used; junctions with more than
 //   --fill-max-paths bounded paths from both sides (default 256) stay as they are.  All three defaults are choices, not
 //   measurements.  The JSON gains "fill":{tol, max_edges, max_paths, the ten stats} before "scaffolds".
+//   --overlap-gaps [TOL] (with --scaffolds or --scaffold-fasta) sends the chains, after --fill-gaps when both are given, through
+//   gk_graph_overlap_gaps (include/genome_amd.h, "overlap detection": this project's own rule): where the last o bases of a member
+//   equal the first o of the next, exactly, for exactly one o of --overlap-min (default 10) to --overlap-max (default k) bases
+//   within TOL of -gap, the FASTA writes those bases once and no N, and the id list shows -o as the gap.  TOL defaults as
+//   --fill-gaps' does; the defaults are choices, not measurements.  The JSON gains "overlap":{tol, min_overlap, max_overlap, the
+//   seven stats} beside "fill".
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
 //   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
 //   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
@@ -66,7 +72,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
                              "[--thread-reads [--no-pairs]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
-                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]]] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -140,6 +146,7 @@ int main(int argc, char **argv) {
             const LinkResult lr = linksStage(graph, ctx, data, takeFirst, link, stage, &res);
             jsonPut(js, "links", lr.json());
             if (!lr.fillJson.empty()) jsonPut(js, "fill", lr.fillJson);
+            if (!lr.overlapJson.empty()) jsonPut(js, "overlap", lr.overlapJson);
             if (!lr.scaffoldsJson.empty()) jsonPut(js, "scaffolds", lr.scaffoldsJson);
         }
         if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");

@@ -251,6 +251,10 @@ inline PairedResult pairedStage(genome::Graph &graph, genome::Context &ctx, geno
 // (include/genome_amd.h, "scaffolds"), the edges in no chain after them; --link-min-len is the singletons' length filter too.
 // --fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N] (with --scaffolds or --scaffold-fasta): the chains go through
 // gk_graph_fill_gaps first (include/genome_amd.h, "gap filling"), and both files are written from the filled chains.
+// --overlap-gaps [TOL] [--overlap-min N] [--overlap-max N] (with --scaffolds or --scaffold-fasta): the chains, after --fill-gaps when
+// both are given (a graph path is the stronger evidence, and the junctions it leaves are the ones searched), go through
+// gk_graph_overlap_gaps (include/genome_amd.h, "overlap detection"); the FASTA joins an overlapped junction on its o bases, and
+// the id list shows -o as its gap.
 struct LinkOpts {
     std::string path, scaffolds, scaffoldFasta;
     uint32_t minSupport = 3;
@@ -261,10 +265,15 @@ struct LinkOpts {
     bool fillGaps = false;
     int64_t fillTol = -1;                         // -1: half the width of the insert range the stage used; a choice, not a measurement
     uint32_t fillMaxEdges = 16, fillMaxPaths = 256;   // choices, not measurements
+    bool overlapGaps = false;
+    int64_t overlapTol = -1;                      // -1: as fillTol
+    uint32_t overlapMin = 10, overlapMax = 0;     // 0: k.  Choices, not measurements: a chance match of 10 bases is about 1e-6 per candidate
     bool parse(Args &a) {
         if (a.flag("--scaffold-both-strands")) { scaffoldBoth = true; return true; }
         if (a.optional("--fill-gaps", fillTol)) { fillGaps = true; return true; }
         if (a.value("--fill-max-edges", fillMaxEdges) || a.value("--fill-max-paths", fillMaxPaths)) return true;
+        if (a.optional("--overlap-gaps", overlapTol)) { overlapGaps = true; return true; }
+        if (a.value("--overlap-min", overlapMin) || a.value("--overlap-max", overlapMax)) return true;
         return a.value("--links", path) || a.value("--link-min-support", minSupport) || a.value("--link-min-len", minLen) || a.value("--scaffolds", scaffolds) ||
                a.value("--scaffold-fasta", scaffoldFasta) || a.value("--scaffold-min-gap", scaffoldMinGap) || a.value("--scaffold-width", scaffoldWidth);
     }
@@ -273,6 +282,7 @@ struct LinkOpts {
         if (path.empty() && !scaffolds.empty()) { std::fprintf(stderr, "--scaffolds PATH goes with --links PATH\n"); return false; }
         if (path.empty() && !scaffoldFasta.empty()) { std::fprintf(stderr, "--scaffold-fasta PATH goes with --links PATH\n"); return false; }
         if (fillGaps && scaffolds.empty() && scaffoldFasta.empty()) { std::fprintf(stderr, "--fill-gaps goes with --scaffolds PATH or --scaffold-fasta PATH\n"); return false; }
+        if (overlapGaps && scaffolds.empty() && scaffoldFasta.empty()) { std::fprintf(stderr, "--overlap-gaps goes with --scaffolds PATH or --scaffold-fasta PATH\n"); return false; }
         if (wanted() && world) { std::fprintf(stderr, "--links runs on one GPU only (not with --world): export per rank and add the tables\n"); return false; }
         return true;
     }
@@ -283,6 +293,7 @@ struct LinkResult {
     uint64_t mid = 0, maxSpan = 0, chains = 0, cycles = 0;
     std::string scaffoldsJson;                    // the stats of --scaffold-fasta's text; empty without the flag
     std::string fillJson;                         // --fill-gaps: tol, the two limits and the ten stats; empty without the flag
+    std::string overlapJson;                      // --overlap-gaps: tol, the two bounds and the seven stats; empty without the flag
     std::string json() const {
         return "{" + jsonNamed(genome::Graph::linkClassNames, classes.v, 8) + "," + jsonNamed(genome::Links::joinStatNames, joins.v, 5) + ",\"mid\":" +
                std::to_string(mid) + ",\"max_span\":" + std::to_string(maxSpan) + ",\"chains\":" + std::to_string(chains) + ",\"cycles\":" + std::to_string(cycles) + "}";
@@ -337,18 +348,31 @@ inline LinkResult linksStage(genome::Graph &graph, genome::Context &ctx, const g
                      f.json().substr(1);
         members = std::move(f.chains); gaps = std::move(f.gaps);
     }
+    std::vector<std::vector<uint32_t>> overlaps;
+    if (lo.overlapGaps) {                                                                            // after --fill-gaps: the junctions it left
+        const uint64_t tol = lo.overlapTol >= 0 ? (uint64_t)lo.overlapTol : (rhi - rlo) / 2;
+        const uint32_t omax = lo.overlapMax ? lo.overlapMax : (uint32_t)graph.k();
+        auto ov = graph.overlapGaps(members, gaps, tol, lo.overlapMin, omax);
+        std::fprintf(stderr, "overlap-gaps: tol %llu (%s), overlaps of %u to %u bases: %llu of %llu junctions overlap by %llu bases together\n", (unsigned long long)tol,
+                     lo.overlapTol >= 0 ? "given" : "half the width of the insert range", lo.overlapMin, omax, (unsigned long long)ov.v[5], (unsigned long long)ov.v[0],
+                     (unsigned long long)ov.v[6]);
+        r.overlapJson = "{\"tol\":" + std::to_string(tol) + ",\"min_overlap\":" + std::to_string(lo.overlapMin) + ",\"max_overlap\":" + std::to_string(omax) + "," +
+                        ov.json().substr(1);
+        overlaps = std::move(ov.overlaps);
+    }
     if (!lo.scaffolds.empty()) {
         std::ofstream sf(lo.scaffolds);
         sf << "# scaffold chains: maximal paths of joins (the only link of at least " << lo.minSupport << " observations out of one edge and into the next)\n"
            << "# both strands' chains appear, as --contigs --contig-both-strands shows the edges: a chain and the chain of its twins are the same scaffold\n"
            << "# s<i>\t<members>\te<id>\t<gap>\te<id>...; a cycle starts at its smallest id and ends with the closing gap and the word cycle\n";
         if (lo.fillGaps) sf << "# --fill-gaps: members between two joined edges are the one path the graph holds there; the gap at such a junction is -k\n";
+        if (lo.overlapGaps) sf << "# --overlap-gaps: where the end of a member and the start of the next spell the same o bases, the gap at that junction is -o\n";
         for (size_t i = 0; i < members.size(); i++) {
             const auto &c = members[i];
             sf << "s" << i << "\t" << c.size();
             for (size_t j = 0; j < c.size(); j++) {
                 sf << "\te" << c[j];
-                if (j + 1 < c.size()) sf << "\t" << gaps[i][j];
+                if (j + 1 < c.size()) sf << "\t" << (lo.overlapGaps && overlaps[i][j] ? -(int64_t)overlaps[i][j] : gaps[i][j]);
             }
             const auto closing = gapOf.find({c.back(), c.front()});                                  // the last member of a path joins nothing
             if (closing != gapOf.end()) sf << "\t" << closing->second << "\tcycle";
@@ -357,7 +381,8 @@ inline LinkResult linksStage(genome::Graph &graph, genome::Context &ctx, const g
         if (!sf) throw std::runtime_error("cannot write " + lo.scaffolds);
     }
     if (!lo.scaffoldFasta.empty()) {
-        auto sc = graph.scaffolds(members, gaps, lo.scaffoldMinGap, lo.minLen, lo.scaffoldWidth, lo.scaffoldBoth, true);
+        auto sc = lo.overlapGaps ? graph.scaffolds(members, gaps, overlaps, lo.scaffoldMinGap, lo.minLen, lo.scaffoldWidth, lo.scaffoldBoth, true)
+                                 : graph.scaffolds(members, gaps, lo.scaffoldMinGap, lo.minLen, lo.scaffoldWidth, lo.scaffoldBoth, true);
         sc.write(lo.scaffoldFasta);
         r.scaffoldsJson = sc.stats().json();
     }

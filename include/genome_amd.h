@@ -832,7 +832,8 @@ int gk_scaffold_chains(const uint32_t *e1, const uint32_t *e2, uint64_t n, uint3
  *   adjacent  e_end[e] == e_start[f], the same node ID (copies of a node that share a k-mer are different nodes): the two paths
  *             share that node's k-mer, so f contributes bases k .. of P(f) and nothing goes between; the gap is not looked at;
  *   gapped    anything else: a run of max(gap, min_gap) bases N, then all of P(f).  A gap below min_gap counts as CLAMPED (it is
- *             gapped too).  Overlaps are not looked for: a negative gap is clamped like any other.
+ *             gapped too).  Overlaps are not looked for here: a negative gap is clamped like any other, unless the caller passes
+ *             the overlaps of gk_graph_overlap_gaps to gk_graph_scaffolds_plan_overlaps (below, "overlap detection").
  * Sequence.  S(c) = P(first member) followed by what every junction adds, over the codes A0 G1 C2 T3 N4; n = its length.
  * Strand.  R(S) = S reversed with code c mapped to 3 - c for c < 4, and 4 staying 4.  A chain is FORWARD if S < R
  * lexicographically by code, SELF_TWIN if S == R, REVERSE otherwise.  No twin lookup is needed, for the reason the contig rule
@@ -863,7 +864,7 @@ int gk_scaffold_chains(const uint32_t *e1, const uint32_t *e2, uint64_t n, uint3
  * its junction; a scan over the segment lengths places every segment; one wave per chain compares S with R 64 bases at a time,
  * a lane finding its base by a binary search in the chain's segments; two more scans and a compaction give record -> (segments,
  * byte offset); the text is emitted by byte range as contigs are, the segment of a lane's first base found by a binary search.
- * Not there: cov= on scaffold records, overlap detection for negative gaps, a collective over ranks (links are per rank). */
+ * Not there: cov= on scaffold records, a collective over ranks (links are per rank). */
 typedef struct gk_scaffolds gk_scaffolds;
 int gk_graph_scaffolds_plan(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap, int64_t min_gap,
                             uint64_t min_len, uint32_t line_width, int strands, int singletons, gk_scaffolds **out);
@@ -871,15 +872,17 @@ void gk_scaffolds_destroy(gk_scaffolds *s);
 /* stats13 = {chains, chain_forward, chain_self_twin, chain_reverse, singletons, records, members, adjacent, gapped, clamped,
  * n_bases, bases, text_bytes}: chains = the sum of the three after it; singletons = singleton records; records = chain records +
  * singletons; members .. n_bases are over the chain records (members = their pieces, adjacent + gapped = members - chain
- * records, clamped <= gapped, n_bases = their N); bases = the sum of n over all records */
+ * records, clamped <= gapped, n_bases = their N); bases = the sum of n over all records.  With overlaps
+ * (gk_graph_scaffolds_plan_overlaps) the identity becomes adjacent + gapped + overlapped = members - chain records, `overlapped`
+ * being gk_scaffolds_overlap_stats' first number */
 int gk_scaffolds_stats(const gk_scaffolds *s, uint64_t *stats13);
 /* gk_contigs_read's, gk_contigs_write's and gk_contigs_last_ms' contracts, for this text */
 int gk_scaffolds_read(gk_scaffolds *s, uint64_t offset, char *buf, uint64_t cap, uint64_t *n);
 int gk_scaffolds_write(gk_scaffolds *s, const char *path);
 int gk_scaffolds_last_ms(const gk_scaffolds *s, float *ms4);
 /* The layout of the records, one row per piece of an edge in text order: the record's index in the text, the edge id, the first
- * base of the piece in the record's sequence, the bases written, and the bases of P(edge) skipped before them (0, or k after an
- * adjacent junction).  N runs are the bases between rows.  *n = rows = members + singletons of the stats; cap below it is
+ * base of the piece in the record's sequence, the bases written, and the bases of P(edge) skipped before them (0, k after an
+ * adjacent junction, or o after an overlapped one).  N runs are the bases between rows.  *n = rows = members + singletons of the stats; cap below it is
  * GK_E_CAPACITY with *n set and nothing copied. */
 int gk_scaffolds_segments(const gk_scaffolds *s, uint64_t *record, uint32_t *edge, uint64_t *first, uint64_t *bases, uint32_t *skipped, uint64_t cap,
                           uint64_t *n);
@@ -943,13 +946,84 @@ int gk_scaffolds_segments(const gk_scaffolds *s, uint64_t *record, uint32_t *edg
  * No global atomics in the search.  Then one atomic add per path edge (uses), one lane per junction (shared / filled), a scan
  * over the per-member output counts and a write kernel; one read-back at the end.  The in-edge lists are built on every call
  * (two passes over the edges and a scan over the nodes), needed or not.
- * Not there: overlap detection for negative gaps, a collective over ranks. */
+ * Not there: a collective over ranks. */
 #define GK_FILL_MAX_EDGES 64        /* a path's edges: one lane each when a hit is unwound */
 #define GK_FILL_MAX_PATHS 1024      /* entries of one wave's LDS tree: 4 waves x 10 KiB = 40 KiB per workgroup, 4 workgroups per CU */
 enum { GK_FILL_LAST = 0, GK_FILL_ADJACENT = 1, GK_FILL_OVERFLOW = 2, GK_FILL_NONE = 3, GK_FILL_AMBIGUOUS = 4, GK_FILL_SHARED = 5, GK_FILL_FILLED = 6 };
 int gk_graph_fill_gaps(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap, uint64_t tol,
                        uint32_t max_edges, uint32_t max_paths, uint32_t *out_members, int64_t *out_gap, uint64_t members_cap, uint64_t *out_chain_off,
                        uint8_t *jclass, int64_t *jlen, uint64_t *n_members, uint64_t *stats10);
+
+/* ---- overlap detection: this project's own rule (the reference has no scaffolds) ----
+ * A stage between gk_graph_fill_gaps (or gk_scaffold_chains) and the scaffold plan: where the paths of two consecutive chain
+ * members overlap, exactly, by a number of bases that the gap estimate allows, the plan writes those bases once instead of twice
+ * with min_gap bases N between them.  The commonest cause is a coverage dip: w consecutive k-mers (1 <= w <= k - 2) missing from
+ * the count table leave two contigs whose paths share k - 1 - w bases, no graph path between them (gk_graph_fill_gaps: none),
+ * and a link whose gap is near -(k - 1 - w).  Integers only.  The graph is not edited and the chains are not rewritten.
+ * Input.  members, chain_off, nchains and gap exactly as gk_graph_scaffolds_plan takes them; tol (bases) 0 .. 2^31-1; min_overlap
+ * 1 .. GK_OVERLAP_MAX; max_overlap min_overlap .. GK_OVERLAP_MAX.  GK_OVERLAP_MAX = 127 is a bound of the implementation, not a
+ * measurement: 127 = 2 * 64 - 1 bases, so a side fits four 64-bit words of 2-bit codes and an overlap fits the plan's one-byte skip
+ * column; it is also the longest overlap two edges at k = 64 can have without sharing a whole k-mer of sequence.  (In an unedited
+ * graph two different edges share no interior k-mer, so overlaps are below k; node copies that share a k-mer give exactly k; by-id
+ * edits can give more.)
+ * Paths.  P(e) = start k-mer ++ seq, as in the scaffold rule; |P(e)| = k + len_e.
+ * Candidates.  Take a junction (e, f) of consecutive members that is not adjacent (e_end[e] != e_start[f], by node id, as in the
+ * scaffold rule) and G = its gap.  The candidates are the o in lo .. hi with
+ *   lo = max(min_overlap, -G - tol)
+ *   hi = min(max_overlap, -G + tol, |P(e)| - 1, |P(f)| - 1):
+ * neither member may be contained in the other, and f always adds at least one base.
+ * Hit.  o is a hit when the last o bases of P(e) equal the first o bases of P(f), exactly.
+ * Classes of a junction, tested in this order (jclass is parallel to members, as gap is):
+ *   last          at a chain's last member;
+ *   adjacent      as in the scaffold rule; nothing is searched, the gap is not looked at;
+ *   out_of_range  lo > hi; nothing is searched.  Every ordinary positive gap lands here;
+ *   none          no hit;
+ *   ambiguous     two or more hits.  A periodic end stays N: no hit is preferred over another;
+ *   overlap       exactly one hit.
+ * Output.  overlap[j] = the hit where jclass[j] is overlap, else 0.  stats7 = {junctions, adjacent, out_of_range, none, ambiguous,
+ * overlap, overlap_bases}: element 0 is the sum of the next five, overlap_bases the sum of overlap[].
+ * Why exact.  If the last o bases of P(e) are the first o bases of P(f), the sequence built so far, which ends with all of P(e),
+ * followed by bases o .. of P(f), ends with all of P(f).  The next junction's overlap, however long (it may exceed what f
+ * contributed), is therefore an overlap with the text actually written, and nothing has to choose between two spellings.  With
+ * mismatches allowed a rule would have to say whose bases are written; exactness avoids that.
+ * Twins.  P(twin x) is the reverse complement of P(x), so the last o bases of P(e) equal the first o of P(f) iff the last o bases
+ * of P(twin f) equal the first o of P(twin e).  The two path lengths are the same for the junction (twin f, twin e), and on a
+ * strand-closed link table so is G (see "scaffold links", Twins); adjacent mirrors too (gk_graph_scaffolds_plan, Strand).  Hence lo,
+ * hi and the set of hits are the same: a chain and its twin chain get the same classes and the same o in mirrored order, an
+ * overlapped junction drops the same o bases from either side, and the twin chain's sequence is R(S): strands = 1 still writes
+ * exactly one chain of such a pair.
+ * Errors.  GK_E_INVALID: the scaffold plan's member and chain errors (an id at or above the bound, or dead; an edge twice; an empty
+ * chain; a chain_off that does not ascend), found on the device before a kernel reads a member's length; a parameter out of range;
+ * NULL handles or arrays; |G| above 2^31-1 at a junction that is not adjacent.  On any error nothing is written.
+ * The defaults the tools and the Python side pass (min_overlap 10, max_overlap k, tol = half the width of the insert range) are
+ * choices, not measurements: a chance match of 10 bases has probability 4^-10, about 10^-6, per candidate.
+ * On the device: the scaffold plan's check and one lane per junction for last / adjacent / out_of_range; a scan compacts the
+ * junctions to search.  k_ovl_search: one wave per junction.  The lanes gather the last min(127, |P(e)|) bases of P(e) and the first
+ * min(127, |P(f)|) bases of P(f), two bases per lane and side, and pack them into four 64-bit words per side in LDS (64 bytes per
+ * wave).  A lane then takes the candidates lo + lane and lo + lane + 64 (there are at most 127) and tests each by a multi-word
+ * shift, mask and compare; a ballot per round counts the hits, and a unique hit is read from the ballot.  No global atomics in the
+ * search; the stats are a reduction over jclass and overlap afterwards (one atomic add per wave and counter); one read-back at the
+ * end.
+ * Not there: overlaps with mismatches or indels, a collective over ranks. */
+#define GK_OVERLAP_MAX 127          /* a bound of the implementation, not a measurement */
+enum { GK_OVL_LAST = 0, GK_OVL_ADJACENT = 1, GK_OVL_OUT_OF_RANGE = 2, GK_OVL_NONE = 3, GK_OVL_AMBIGUOUS = 4, GK_OVL_OVERLAP = 5 };
+int gk_graph_overlap_gaps(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap, uint64_t tol,
+                          uint32_t min_overlap, uint32_t max_overlap, uint32_t *overlap, uint8_t *jclass, uint64_t *stats7);
+/* gk_graph_scaffolds_plan with a third junction class, tested after adjacent:
+ *   overlapped  overlap[j] = o > 0 at a junction (members[j], members[j + 1]) that is not adjacent: nothing goes between the
+ *               members, and f contributes bases o .. of P(f); its segment row's `skipped` is o.  The gap is not looked at.  Such a
+ *               junction counts in neither `gapped` nor `clamped`, and adds nothing to gaps= in the header.
+ * `overlap` is parallel to `members` (gk_graph_overlap_gaps' output; the entry at a chain's last member is ignored); NULL, or all
+ * zeros, gives gk_graph_scaffolds_plan's text, stats13 and segments bit for bit.  The plan does not trust the array: in the same
+ * pass as its other checks, on the device, GK_E_INVALID for an overlap[j] above GK_OVERLAP_MAX, one that is not below both path
+ * lengths, a non-zero one at an adjacent junction, or one whose o bases do not match exactly.  So S(c) is always a sequence in
+ * which every member's whole path occurs in order, and, a checked overlap being symmetric under twins (above), the strand argument
+ * of the scaffold rule carries over unchanged.
+ * stats2 = {overlapped junctions, bases dropped (the sum of their o)} over the chain records written. */
+int gk_graph_scaffolds_plan_overlaps(gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap,
+                                     const uint32_t *overlap, int64_t min_gap, uint64_t min_len, uint32_t line_width, int strands, int singletons,
+                                     gk_scaffolds **out);
+int gk_scaffolds_overlap_stats(const gk_scaffolds *s, uint64_t *stats2);
 /* live nodes, unspecified order */
 int gk_graph_export_nodes(gk_graph *g, uint64_t *lo, uint64_t *hi, uint64_t cap, uint64_t *n);
 /* live edges, unspecified order: start/end k-mer, length in bases, and the edge sequence as 2-bit
