@@ -157,6 +157,14 @@ SIGNATURES = {
     "gk_graph_thread_reads": (C.c_int, [vp, vp, vp, u8p, C.c_size_t, C.c_uint64, u64p]),
     "gk_graph_thread_reads_dev": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_int, u64p]),
     "gk_graph_split_by_support": (C.c_int, [vp, vp, C.c_int, u64p, u64p]),
+    "gk_spans_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "gk_spans_destroy": (None, [vp]),
+    "gk_spans_size": (C.c_int, [vp, u64p, u64p]),
+    "gk_spans_export": (C.c_int, [vp, u32p, u32p, u32p, u32p, C.c_uint64, u64p]),
+    "gk_spans_add": (C.c_int, [vp, u32p, u32p, u32p, u32p, C.c_uint64]),
+    "gk_graph_thread_spans": (C.c_int, [vp, vp, vp, u8p, C.c_size_t, C.c_uint64, u64p]),
+    "gk_graph_thread_spans_dev": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_int, u64p]),
+    "gk_graph_split_edges_by_spans": (C.c_int, [vp, vp, C.c_uint32, u64p]),
     "gk_graph_pair_distances": (C.c_int, [vp, vp, u8p, C.c_size_t, C.c_uint64, C.c_uint32, u64p, u64p]),
     "gk_insert_range": (C.c_int, [u64p, C.c_uint32, C.c_uint32, C.c_uint64, u32p, u32p, u32p]),
     "gk_dist_pair_distances": (C.c_int, [vp, vp, vp, u8p, C.c_size_t, C.c_uint64, C.c_uint32, u64p, u64p]),

@@ -159,6 +159,7 @@ int graph_refresh_counts(gk_graph *g);                    // live nodes / edges 
 int graph_build_index(gk_graph *g);                       // k-mer -> node id index
 inline int graph_ensure_index(gk_graph *g) { return g->index_ready ? 0 : graph_build_index(g); }   // before any kernel that calls node_find / reads nidx
 int graph_grow_nodes(gk_graph *g, u64 new_cap);
+int graph_grow_edges(gk_graph *g, u64 new_n);               // contents kept; n_edges is the caller's to raise
 // the node / edge arrays of a graph without any (ids 0..n-1, none alive, out_edge NONE, out_order / in_deg 0): the build and gk_graph_load
 int graph_alloc_nodes(gk_graph *g, u64 n);
 int graph_alloc_edges(gk_graph *g, u64 n);

@@ -797,7 +797,7 @@ int graph_alloc_edges(gk_graph *g, u64 n) {
     g->edge_cap = c;
     return GK_OK;
 }
-static int graph_grow_edges(gk_graph *g, u64 new_n) {
+int graph_grow_edges(gk_graph *g, u64 new_n) {
     gk_ctx *ctx = g->ctx;
     GraphView &v = g->v;
     if (new_n <= g->edge_cap) { return GK_OK; }

@@ -26,6 +26,7 @@
 
 #include "gk_graph.h"
 #include "gk_scan.h"
+#include "gk_spans.h"
 #include "gk_support.h"
 #include "gk_tile.h"
 
@@ -1207,6 +1208,20 @@ __global__ __launch_bounds__(BLOCK) void k_add_nodes(GraphView g, u32 first, con
         for (int b = 0; b < 4; b++) g.out_edge[(u64)v * 4 + b] = NONE;
     }
 }
+// the edge split's copies (gk_graph_split_edges_by_spans): copy i of an edge gets id first + i, from node start[i] to node end[i],
+// with src[i]'s length, first base and pool bytes (shared: see the header).  start[i] is a fresh node that gets this one out-edge.
+__global__ __launch_bounds__(BLOCK) void k_add_edges(GraphView g, u32 first, const u32 *src, const u32 *start, const u32 *end, u64 n) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
+        const u32 x = first + (u32)i, m = src[i], u = start[i], v = end[i];
+        const int b = g.e_first[m];
+        g.e_start[x] = u; g.e_end[x] = v;
+        g.e_len[x] = g.e_len[m]; g.e_off[x] = g.e_off[m]; g.e_first[x] = (uint8_t)b;
+        g.e_alive[x] = 1;
+        g.out_edge[(u64)u * 4 + b] = x;
+        g.out_order[u] = order_append(0u, b);
+        atomicAdd(&g.in_deg[v], 1u);
+    }
+}
 __global__ __launch_bounds__(BLOCK) void k_move_ends(GraphView g, const u32 *edge, const u32 *node, u64 n) {
     for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) {
         const u32 e = edge[i], nn = node[i];                 // graph.replaceEnd(e, newNode)  :307, Graph.scala:204-209
@@ -1342,6 +1357,95 @@ int gk_graph_split_by_support(gk_graph *g, const gk_support *sup, int cutoff, ui
     if (removed_edges) *removed_edges = removed;
     if (new_nodes) *new_nodes = nnew;
     return graph_refresh_counts(g);
+}
+
+// ---- the edge split (this project's own rule: include/genome_amd.h, gk_graph_split_edges_by_spans)
+int gk_graph_split_edges_by_spans(gk_graph *g, const gk_spans *spans, uint32_t cutoff, uint64_t *stats7) {
+    if (stats7) for (int i = 0; i < 7; i++) stats7[i] = 0;
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    const char *who = "gk_graph_split_edges_by_spans";
+    if (!spans) return fail(ctx, GK_E_INVALID, std::string(who) + ": null spans handle");
+    if (spans->ctx != ctx) return fail(ctx, GK_E_INVALID, std::string(who) + ": the spans must live on the graph's context");
+    if (cutoff == 0) return fail(ctx, GK_E_INVALID, std::string(who) + ": cutoff 0 would resolve without evidence");
+    const HostGraph *Hp = nullptr;
+    if (int rc = graph_snapshot_cached(g, &Hp)) return rc;
+    const HostGraph &H = *Hp;
+    // the counts by spanned edge (one download); a triple that names nothing in this graph is never looked up
+    std::vector<u32> se, sm, sf, sc;
+    if (int rc = spans_to_host(spans, se, sm, sf, sc)) return rc;
+    std::unordered_map<u32, std::vector<size_t>> by_m;
+    for (size_t i = 0; i < sm.size(); i++) if (sm[i] < H.n_edges && H.e_alive[sm[i]]) by_m[sm[i]].push_back(i);
+    u64 st[7] = {0, 0, 0, 0, 0, 0, 0};
+    std::vector<u32> node_src, edge_src, edge_start, edge_end, end_edge, end_node, start_edge, start_node;
+    const u32 first_node = (u32)H.n_nodes, first_edge = (u32)H.n_edges;
+    for (u64 m = 0; m < H.n_edges; m++) {
+        if (!H.e_alive[m]) continue;
+        const u32 u = H.e_start[m], v = H.e_end[m];
+        u32 b[4];
+        int outdeg_u = 0, q = 0;
+        for (int c = 0; c < 4; c++) {
+            if (H.out_edge[(u64)u * 4 + c] != NONE) outdeg_u++;
+            if (H.out_edge[(u64)v * 4 + c] != NONE) b[q++] = H.out_edge[(u64)v * 4 + c];
+        }
+        const u32 *a = H.in_list.data() + H.in_off[u];                 // (ascending: the snapshot fills the lists in id order)
+        const int p = (int)(H.in_off[u + 1] - H.in_off[u]);
+        if (outdeg_u != 1 || H.in_off[v + 1] - H.in_off[v] != 1 || p < 2 || q < 2) continue;
+        st[0]++;
+        if (p != q) { st[2]++; continue; }
+        std::sort(b, b + q);
+        bool M[4][4] = {};
+        if (auto it = by_m.find((u32)m); it != by_m.end())
+            for (const size_t t : it->second)
+                for (int i = 0; i < p; i++)
+                    for (int j = 0; j < q; j++)
+                        if (se[t] == a[i] && sf[t] == b[j] && sc[t] >= cutoff) M[i][j] = true;
+        int row[4] = {0, 0, 0, 0}, col[4] = {0, 0, 0, 0};
+        for (int i = 0; i < p; i++) for (int j = 0; j < q; j++) if (M[i][j]) { row[i]++; col[j]++; }
+        bool two = false, none = false;
+        for (int i = 0; i < p; i++) { two |= row[i] >= 2 || col[i] >= 2; none |= row[i] == 0 || col[i] == 0; }
+        if (two) { st[3]++; continue; }
+        if (none) { st[4]++; continue; }
+        st[1]++;
+        for (int i = 1; i < p; i++) {
+            int j = 0;
+            while (!M[i][j]) j++;
+            const u32 nu = first_node + (u32)node_src.size(), nv = nu + 1;
+            node_src.push_back(u); node_src.push_back(v);
+            edge_src.push_back((u32)m); edge_start.push_back(nu); edge_end.push_back(nv);
+            end_edge.push_back(a[i]); end_node.push_back(nu);
+            start_edge.push_back(b[j]); start_node.push_back(nv);
+        }
+    }
+    GraphView &v = g->v;
+    const u64 nnew_e = edge_src.size(), nnew_n = node_src.size();
+    st[5] = nnew_e; st[6] = nnew_n;
+    if (v.n_edges + nnew_e >= 0x7fffffffull) return fail(ctx, GK_E_CAPACITY, std::string(who) + ": more than 2^31 - 1 graph edges; nothing was edited");
+    if (v.n_nodes + nnew_n >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, std::string(who) + ": more than 2^32 graph nodes; nothing was edited");
+    if (nnew_e) {
+        if (v.n_nodes + nnew_n > g->node_cap) { if (int rc = graph_grow_nodes(g, std::max<u64>(g->node_cap * 2, v.n_nodes + nnew_n))) return rc; }
+        if (int rc = graph_grow_edges(g, v.n_edges + nnew_e)) return rc;
+        u32 *d_ns = nullptr, *d_es = nullptr, *d_est = nullptr, *d_een = nullptr, *d_ee = nullptr, *d_en = nullptr, *d_se = nullptr, *d_sn = nullptr;
+        DevScratch tmp(ctx);
+        tmp.upload(&d_ns, node_src.data(), nnew_n);
+        tmp.upload(&d_es, edge_src.data(), nnew_e); tmp.upload(&d_est, edge_start.data(), nnew_e); tmp.upload(&d_een, edge_end.data(), nnew_e);
+        tmp.upload(&d_ee, end_edge.data(), nnew_e); tmp.upload(&d_en, end_node.data(), nnew_e);
+        tmp.upload(&d_se, start_edge.data(), nnew_e); tmp.upload(&d_sn, start_node.data(), nnew_e);
+        if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), who);
+        hipLaunchKernelGGL(k_add_nodes, dim3(ggrid(ctx, nnew_n)), dim3(BLOCK), 0, ctx->stream, v, first_node, d_ns, nnew_n);
+        v.n_nodes += nnew_n;                                  // (the kernels below index the new nodes and edges)
+        hipLaunchKernelGGL(k_add_edges, dim3(ggrid(ctx, nnew_e)), dim3(BLOCK), 0, ctx->stream, v, first_edge, d_es, d_est, d_een, nnew_e);
+        v.n_edges += nnew_e;
+        hipLaunchKernelGGL(k_move_ends, dim3(ggrid(ctx, nnew_e)), dim3(BLOCK), 0, ctx->stream, v, d_ee, d_en, nnew_e);
+        hipLaunchKernelGGL(k_move_starts, dim3(ggrid(ctx, nnew_e)), dim3(BLOCK), 0, ctx->stream, v, d_se, d_sn, nnew_e);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return hip_fail(ctx, e, who);
+        g->index_ready = false;                                // several nodes share a sequence now
+        if (int rc = graph_refresh_counts(g)) return rc;
+    }
+    if (stats7) for (int i = 0; i < 7; i++) stats7[i] = st[i];
+    return GK_OK;
 }
 
 }  // extern "C"

@@ -22,50 +22,14 @@
 #include <memory>
 
 #include "gk_binstream.h"
-#include "gk_graph.h"
 #include "gk_support.h"
-#include "gk_vmap_probe.h"
-
-namespace gk {
-void vmap_table(const gk_vmap *m, void **slots, uint32_t *nb2, uint32_t *lnb1);
-}
+#include "gk_thread_common.h"
 
 namespace {
 
 constexpr int TH_NSTATS = 7;
-constexpr int TH_MAXW = 256;                   // windows of a record: at most 255 - k + 1 <= 254
-// what a window's lookup left, beside a position: no valid GraphPosition has these bit patterns (an edge id of 2^31 - 1)
-constexpr u64 PV_NONE = ~0ull, PV_MANY = ~0ull - 1;
-enum { TC_OFF = 0, TC_REPEATED = 1, TC_ON_EDGE = 2, TC_BROKEN = 3, TC_CROSSING = 4 };
 
 struct ThreadCounts { u32 reads, inner, cls[5]; };
-
-__device__ __forceinline__ void thread_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// getAll(w) reduced to {none, many, the position}.  The one position is untrusted (k_check_positions' test, gk_pairs.hip): one
-// that names nothing live in this graph raises *bad and counts as none, so that nothing below indexes the graph with it.
-template <int W>
-__device__ __forceinline__ u64 thread_lookup(const Table<W> &pm, const GraphView &g, Kmer<W> x, u32 *bad) {
-    u64 v = 0;
-    const u32 n = vmap_count_one(pm, x, &v);
-    if (n == 0) return PV_NONE;
-    if (n > 1) return PV_MANY;
-    const u32 id = GK_POS_ID(v);
-    const bool ok = GK_POS_IS_EDGE(v) ? (id < g.n_edges && g.e_alive[id] && (u64)GK_POS_DIST(v) < g.e_len[id])
-                                      : ((v >> 32) == 0 && id < g.n_nodes && g.node_alive[id]);
-    if (!ok) { *bad = 1u; return PV_NONE; }
-    return v;
-}
-
-// base p of strand s of the record at tile byte `ro` (s = 1: the reverse complement; complement is ^ 3)
-__device__ __forceinline__ int strand_base(const uint8_t *tb, u32 ro, int len, int s, int p) {
-    const int q = s ? len - 1 - p : p;
-    const int b = (tb[ro + 1 + (q >> 2)] >> ((q & 3) * 2)) & 3;
-    return s ? b ^ 3 : b;
-}
 
 // One record, one wave.  pos[s][i] = what window i of strand s found.
 template <int W>
@@ -91,33 +55,7 @@ __device__ __forceinline__ void thread_record(const Table<W> &pm, const GraphVie
             const int i = i0 + lane;
             int cls = -1;
             u64 key = 0;
-            if (i < n - 1) {
-                const u64 P = pos[s][i];
-                if (P == PV_NONE) cls = TC_OFF;
-                else if (P == PV_MANY) cls = TC_REPEATED;
-                else if (GK_POS_IS_EDGE(P)) cls = TC_ON_EDGE;
-                else {
-                    cls = TC_BROKEN;
-                    const u32 v = (u32)P;
-                    const u64 nx = pos[s][i + 1], pv = pos[s][i - 1];
-                    // exit: the out-edge of v by the base behind the window, and the next window one step along it
-                    const u32 f = g.out_edge[(u64)v * 4 + strand_base(tb, ro, len, s, i + k)];
-                    bool ok = f != NONE && g.e_alive[f] != 0 && nx < PV_MANY;
-                    if (ok) ok = nx == (g.e_len[f] > 1 ? ((1ull << 63) | ((u64)f << 32) | 1ull) : (u64)g.e_end[f]);
-                    // entry: the previous window one step before the end of an in-edge of v, or the start node of one of length 1
-                    u32 e = NONE;
-                    if (ok && pv < PV_MANY) {
-                        if (GK_POS_IS_EDGE(pv)) {
-                            const u32 pe = GK_POS_ID(pv);
-                            if ((u64)GK_POS_DIST(pv) + 1 == g.e_len[pe] && g.e_end[pe] == v) e = pe;
-                        } else {
-                            const u32 pe = g.out_edge[(u64)(u32)pv * 4 + strand_base(tb, ro, len, s, i + k - 1)];
-                            if (pe != NONE && g.e_alive[pe] != 0 && g.e_len[pe] == 1 && g.e_end[pe] == v) e = pe;
-                        }
-                    }
-                    if (e != NONE) { cls = TC_CROSSING; key = ((u64)e << 32) | f; }
-                }
-            }
+            if (i < n - 1) cls = thread_window_class(g, tb, ro, len, k, s, i, pos[s], &key);
 #pragma unroll
             for (int c = 0; c < 5; c++) st.cls[c] += (u32)__popcll(__ballot(cls == c));
             if (combine) {

@@ -376,6 +376,40 @@ class HipGraph:
         L.check(L.lib().gk_graph_thread_reads_dev(self.h, positions.h, support.h, d_records, nreads, read_len, L.ptr(st, C.c_uint64)), self.ctx.h)
         return dict(zip(THREAD_STATS, (int(x) for x in st)))
 
+    def threadSpans(self, positions, spans: "HipSpans", data, nreads=None) -> dict:
+        """Every read through `positions` (getGraphMap of this graph as it is now): for every edge m a strand of a read crosses
+        from end to end, one is added to `spans` for (the edge it came by, m, the edge it left by) (the rule: include/genome_amd.h,
+        gk_graph_thread_spans) -> the five stats, named as SPAN_STATS.  `data`: a PairedEndData (both mates of every pair, as
+        single reads), or bin bytes with `nreads` records, or (bin bytes, records).  GkError, and `spans` unchanged, on any
+        error; the graph and `positions` never change."""
+        if hasattr(data, "bin"):
+            bin_bytes, n = data.bin, 2 * data.count
+        elif isinstance(data, tuple):
+            bin_bytes, n = data
+        else:
+            bin_bytes, n = data, nreads
+        if nreads is not None:
+            n = max(0, min(int(nreads), n))
+        buf = np.frombuffer(bin_bytes, np.uint8) if not isinstance(bin_bytes, np.ndarray) else np.ascontiguousarray(bin_bytes, np.uint8).reshape(-1)
+        st = np.zeros(len(SPAN_STATS), np.uint64)
+        L.check(L.lib().gk_graph_thread_spans(self.h, positions.h, spans.h, L.ptr(buf, C.c_uint8) if buf.size else None, buf.size, n,
+                                              L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(SPAN_STATS, (int(x) for x in st)))
+
+    def threadSpansDev(self, positions, spans: "HipSpans", d_records: int, nreads: int, read_len: int) -> dict:
+        """threadSpans over records resident in HBM at stride 1 + ceil(read_len / 4) -> the five stats"""
+        st = np.zeros(len(SPAN_STATS), np.uint64)
+        L.check(L.lib().gk_graph_thread_spans_dev(self.h, positions.h, spans.h, d_records, nreads, read_len, L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(SPAN_STATS, (int(x) for x in st)))
+
+    def splitEdgesBySpans(self, spans: "HipSpans", cutoff: int) -> dict:
+        """Every edge whose in-edges and out-edges the spans pair off one to one at `cutoff` gets a copy per further pair (the
+        rule: include/genome_amd.h, gk_graph_split_edges_by_spans) -> the seven stats, named as SPLIT_EDGE_STATS; call
+        simplifyGraph() next."""
+        st = np.zeros(len(SPLIT_EDGE_STATS), np.uint64)
+        L.check(L.lib().gk_graph_split_edges_by_spans(self.h, spans.h, int(cutoff), L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(SPLIT_EDGE_STATS, (int(x) for x in st)))
+
     def splitBySupport(self, support: "Support", cutoff: int):
         """:272-316 -> (edges removed, nodes added); call simplifyGraph() next (:318)."""
         rm, nn = C.c_uint64(), C.c_uint64()
@@ -602,6 +636,10 @@ def scaffoldGaps(chains, joins, mid: int):
 PAIR_CLASSES = ("orientations", "unplaced", "repetitive", "apart", "ambiguous", "reversed", "beyond", "near_end", "counted")
 # the statistics of gk_graph_thread_reads, in the order of its `stats7` array: inner_windows is the sum of the five after it
 THREAD_STATS = ("records", "inner_windows", "off_graph", "repeated", "on_edge", "broken", "crossings")
+# the statistics of gk_graph_thread_spans, in the order of its `stats5` array: crossings is the sum of the three after it
+SPAN_STATS = ("records", "crossings", "spans", "interrupted", "open")
+# the statistics of gk_graph_split_edges_by_spans, in the order of its `stats7` array: candidates is the sum of the four after it
+SPLIT_EDGE_STATS = ("candidates", "resolved", "unequal", "ambiguous", "unsupported", "new_edges", "new_nodes")
 # the classes of gk_graph_pair_links, in the order of its `classes8` array: orientations is the sum of the seven after it
 LINK_CLASSES = ("orientations", "unplaced", "repetitive", "at_node", "same_edge", "short_edge", "too_far", "linked")
 # the statistics of gk_links_joins, in the order of its `stats5` array
@@ -786,6 +824,54 @@ class HipLinks:
                                    cap, C.byref(n), L.ptr(st, C.c_uint64)), self.ctx.h)
         m = n.value
         return (e1[:m], e2[:m], cnt[:m], su[:m]), dict(zip(JOIN_STATS, (int(x) for x in st)))
+
+
+class HipSpans:
+    """Spans (include/genome_amd.h, gk_graph_thread_spans): (edge id, edge id, edge id) -> the reads that came by the first edge,
+    crossed the second from end to end and left by the third.  Edge ids are the graph's at the time of threadSpans."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = L.vp()
+        L.check(L.lib().gk_spans_create(ctx.h, C.byref(h)), ctx.h)
+        self.h = h
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:               # (see HipDNAMap.close)
+                L.lib().gk_spans_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def size(self):
+        """-> (distinct triples, the sum of their counts)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        L.check(L.lib().gk_spans_size(self.h, C.byref(a), C.byref(b)), self.ctx.h)
+        return a.value, b.value
+
+    def export(self):
+        """-> (e, m, f, count) arrays, unordered"""
+        got = C.c_uint64()
+        L.check(L.lib().gk_spans_size(self.h, C.byref(got), None), self.ctx.h)     # the triples alone: a counter, no table pass
+        n = got.value
+        e, m, f, cnt = (np.zeros(n, np.uint32) for _ in range(4))
+        L.check(L.lib().gk_spans_export(self.h, L.ptr(e, C.c_uint32), L.ptr(m, C.c_uint32), L.ptr(f, C.c_uint32), L.ptr(cnt, C.c_uint32), n, C.byref(got)),
+                self.ctx.h)
+        return e, m, f, cnt
+
+    def add(self, e, m, f, cnt):
+        """add (e, m, f, count) records (duplicates add up); GK_E_CAPACITY, and nothing added, if a count would pass 2^32-1.
+        export() of one table added into an empty one reproduces it."""
+        e, m, f, cnt = (np.ascontiguousarray(a, np.uint32) for a in (e, m, f, cnt))
+        assert len(e) == len(m) == len(f) == len(cnt)
+        L.check(L.lib().gk_spans_add(self.h, L.ptr(e, C.c_uint32), L.ptr(m, C.c_uint32), L.ptr(f, C.c_uint32), L.ptr(cnt, C.c_uint32), len(e)), self.ctx.h)
 
 
 def scaffoldChains(e1, e2, with_cycles: bool = False):

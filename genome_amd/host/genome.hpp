@@ -559,6 +559,43 @@ class Links {
     gk_links *h_ = nullptr;
 };
 
+// gk_spans: reads followed across a whole edge (include/genome_amd.h, "spans"): (in-edge, edge, out-edge) -> how often a read crossed
+// the edge from end to end by those two.  Filled by Graph::threadSpans, read by Graph::splitEdgesBySpans; the ids are the graph's
+// at the time of the call.
+class Spans {
+  public:
+    struct Records { std::vector<uint32_t> e, m, f, count; };
+    explicit Spans(Context &ctx) : ctx_(ctx) { check(gk_spans_create(ctx.handle(), &h_), ctx.handle()); }
+    ~Spans() { gk_spans_destroy(h_); }
+    Spans(const Spans &) = delete;
+    gk_spans *handle() const { return h_; }
+    // -> (distinct triples, the sum of their counts)
+    std::pair<uint64_t, uint64_t> size() const {
+        uint64_t a = 0, b = 0;
+        check(gk_spans_size(h_, &a, &b), ctx_.handle());
+        return {a, b};
+    }
+    // every triple, unordered
+    Records exportAll() const {
+        Records r;
+        uint64_t n = 0;
+        check(gk_spans_size(h_, &n, nullptr), ctx_.handle());                       // the triples alone: a counter, no table pass
+        r.e.resize(n); r.m.resize(n); r.f.resize(n); r.count.resize(n);
+        check(gk_spans_export(h_, r.e.data(), r.m.data(), r.f.data(), r.count.data(), n, &n), ctx_.handle());
+        return r;
+    }
+    // add records (duplicates add up); throws (nothing added) if a count would pass 2^32-1
+    void add(const Records &r) {
+        if (r.e.size() != r.m.size() || r.e.size() != r.f.size() || r.e.size() != r.count.size())
+            throw GkError(GK_E_INVALID, "Spans::add: the four lists differ in length");
+        check(gk_spans_add(h_, r.e.data(), r.m.data(), r.f.data(), r.count.data(), r.e.size()), ctx_.handle());
+    }
+
+  private:
+    Context &ctx_;
+    gk_spans *h_ = nullptr;
+};
+
 // gk_scaffold_chains over a join list: the chains as lists of edge ids in ascending order of first member; *cycles = how many of
 // them are cycles (a cycle starts at its smallest id).  Host code: no context, no GPU.
 inline std::vector<std::vector<uint32_t>> scaffoldChains(const std::vector<uint32_t> &e1, const std::vector<uint32_t> &e2, uint64_t *cycles = nullptr) {
@@ -772,6 +809,28 @@ class Graph {
         if (endPair <= firstPair) return st;
         const auto [b0, b1] = pairBytes(data, firstPair, endPair);
         check(gk_graph_thread_reads(h_, positions.handle(), support.handle(), data.bin.data() + b0, b1 - b0, 2 * (endPair - firstPair), st.v), ctx_.handle());
+        return st;
+    }
+    // Reads followed across a whole edge (this project's own rule, include/genome_amd.h: gk_graph_thread_spans): both mates of the
+    // first `takeFirst` pairs, as single reads; every edge a read crosses from end to end adds one to spans[(the edge it came by,
+    // the edge, the edge it left by)].  -> {records threaded, crossings, spans, interrupted, open}.  On an error `spans` is
+    // unchanged.  One GPU: there is no collective over ranks.
+    struct SpanStats { uint64_t v[5] = {}; };
+    static constexpr const char *spanStatNames[5] = {"records", "crossings", "spans", "interrupted", "open"};
+    SpanStats threadSpans(PositionMap &positions, Spans &spans, const PairedEndData &data, uint64_t takeFirst) {
+        SpanStats st;
+        check(gk_graph_thread_spans(h_, positions.handle(), spans.handle(), data.bin.data(), data.bin.size(), 2 * std::min<uint64_t>(data.count, takeFirst),
+                                    st.v), ctx_.handle());
+        return st;
+    }
+    // gk_graph_split_edges_by_spans: every one-to-one pairing (at least `cutoff` spans each) of the in- and out-edges of a repeat
+    // edge gets its own copy of the edge -> {candidates, resolved, unequal, ambiguous, unsupported, new edges, new nodes};
+    // simplifyGraph() is the next call.
+    struct SplitEdgeStats { uint64_t v[7] = {}; };
+    static constexpr const char *splitEdgeStatNames[7] = {"candidates", "resolved", "unequal", "ambiguous", "unsupported", "new_edges", "new_nodes"};
+    SplitEdgeStats splitEdgesBySpans(const Spans &spans, uint32_t cutoff) {
+        SplitEdgeStats st;
+        check(gk_graph_split_edges_by_spans(h_, spans.handle(), cutoff, st.v), ctx_.handle());
         return st;
     }
     // The fragment lengths of the pairs whose mates' first k-mers lie on one edge (include/genome_amd.h, "the insert range"):

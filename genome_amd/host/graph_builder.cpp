@@ -4,7 +4,7 @@
 // The reference logs its counters through akka Logging (:34-53); here they are one JSON object.
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
-//                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]]
+//                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]]
 //                 [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]]   (with --walk-pairs: graph_simplifier.cpp says what they write)
 //                 [--out prefix] [--save-graph PATH] [--correct N|auto]
 //                 [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
@@ -34,6 +34,9 @@
 //   --walk-pairs runs GraphSimplifier.startup's paired-end stage on the graph GraphBuilder hands over (:188-318): position
 //   map, the pairs' walks with range LO to HI (the reference: 180 to 250, :146), node split at genome.cutoff = CUTOFF,
 //   removeEdge, simplifyGraph; its counters join the JSON;
+//   --resolve-repeats [CUTOFF] [--resolve-rounds N] (with --walk-pairs) adds graph_simplifier's rounds of gk_graph_thread_spans,
+//   gk_graph_split_edges_by_spans and simplifyGraph behind that stage (graph_simplifier.cpp says what they do and print; CUTOFF
+//   defaults to --walk-pairs' CUTOFF, at least 1: a choice, not a measurement).  Not with --world (exit 2).
 //   --out writes <prefix>.nodes.txt, .edges.txt, .contigs (GraphSimplifier.scala:338-347) and .dot (Graph.scala:74-88)
 //   --contigs PATH writes the final graph's contigs as FASTA on the device (gk_graph_contigs_plan / gk_contigs_write: this project's
 //   own rule, beside --out's .contigs, which stays the reference's): one record `>e<id> len=<n> cov=<mean>` per live edge whose path
@@ -63,7 +66,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]] [--out prefix] [--save-graph PATH] "
+                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]] [--out prefix] [--save-graph PATH] "
                              "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
@@ -107,10 +110,15 @@ int main(int argc, char **argv) {
         else if (a.word("--walk-pairs", 2, "auto")) { a.value("--walk-pairs", walk.cutoff); walk.rangeAuto = true; a.skip(); }
         else if (a.value("--max-insert", walk.maxInsert)) { if (!walk.maxInsertOk()) { std::fprintf(stderr, "--max-insert N is 1..65535\n"); return 2; } }
         else if (a.value("--walk-pairs", walk.cutoff, walk.lo, walk.hi)) {}
+        else if (walk.parseResolve(a)) {}
         else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || link.parse(a) || ranks.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
-    if (!ranks.check() || !link.check(ranks.world)) return 2;
+    if (!ranks.check() || !link.check(ranks.world) || !walk.checkResolve(ranks.world)) return 2;
+    if (walk.resolve && walk.cutoff < 0) {
+        std::fprintf(stderr, "--resolve-repeats goes with --walk-pairs (it runs behind the paired-end stage)\n");
+        return 2;
+    }
     if (link.wanted() && walk.cutoff < 0) {
         std::fprintf(stderr, "--links goes with --walk-pairs (the links are those of the graph the paired-end stage leaves)\n");
         return 2;
@@ -212,6 +220,7 @@ int main(int argc, char **argv) {
             jsonPut(js, "insert_range", jsonObject("lo", walked.range.lo, "hi", walked.range.hi, "estimated", walked.range.estimated,
                                                    "observations", walked.range.observations));
         if (walk.cutoff >= 0) jsonPut(js, "walk_pairs", walked.walkJson());
+        if (walk.resolve) jsonPut(js, "resolve_repeats", walked.resolveJson(walk.spanCutoff()));
         if (link.wanted()) {
             const LinkResult lr = linksStage(graph, ctx, data, takeFirst, link, walk, &walked);
             jsonPut(js, "links", lr.json());

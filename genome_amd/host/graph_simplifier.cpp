@@ -4,7 +4,7 @@
 // object.
 //
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
-//                    [--take-first N] [--thread-reads [--no-pairs]]
+//                    [--take-first N] [--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]]
 //                    [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
 //                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]]
 //                    [--world W --rank R --id-file PATH]
@@ -20,6 +20,13 @@
 //   --thread-reads threads both mates of the same pairs through the graph as single reads (include/genome_amd.h,
 //   gk_graph_thread_reads: this project's own rule) into the same support before the split; --no-pairs skips the walks, so
 //   that the reads alone are the evidence.  The JSON then holds "thread_reads": the seven stats (summed over the ranks).
+//   --resolve-repeats [CUTOFF] resolves repeats longer than k that single reads span (include/genome_amd.h, "spans": this project's
+//   own rule), after the stage's split and simplifyGraph: a position map of the graph as it is then, gk_graph_thread_spans over
+//   both mates of the same pairs, gk_graph_split_edges_by_spans at CUTOFF (default: --cutoff's value, at least 1; a choice, not a
+//   measurement), simplifyGraph; up to --resolve-rounds N rounds (default 1) while a round resolves something.  It goes with
+//   --no-pairs too (without --thread-reads no support was gathered, the split by support does not run and the spans alone edit
+//   the graph).  stderr gets one line per round; the JSON gains
+//   "resolve_repeats":{"cutoff","rounds":[{"thread_spans":{the five stats},"split_edges":{the seven stats}} per round]}.  One GPU only.
 //   The stage: getGraphMap (:188), walkPairs over the first N pairs (:213-263), splitBySupport (:272-316), simplifyGraph (:318).
 //   --out writes graph_builder's <prefix>.nodes.txt, .edges.txt, .contigs (:338-347) and .dot; --save-graph writes the final
 //   graph as a graph file (the reference's graphFile, :352).
@@ -71,14 +78,14 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
-                             "[--thread-reads [--no-pairs]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
+                             "[--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
                              "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
     genome::PairedEndData data;
     Args::convert("<pairs>", argv[3], data.count);
-    PairedOpts stage;                             // --cutoff, --range, --max-insert, --thread-reads, --no-pairs
+    PairedOpts stage;                             // --cutoff, --range, --max-insert, --thread-reads, --no-pairs, --resolve-repeats
     uint64_t takeFirst = UINT64_MAX;
     std::string out, saveGraph, insertHist;
     ContigOpts contig;
@@ -91,6 +98,7 @@ int main(int argc, char **argv) {
         else if (a.value("--range", stage.lo, stage.hi) || a.value("--take-first", takeFirst)) {}
         else if (a.flag("--thread-reads")) stage.threadReads = true;
         else if (a.flag("--no-pairs")) stage.walk = false;
+        else if (stage.parseResolve(a)) {}
         else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || link.parse(a) || ranks.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
@@ -102,11 +110,11 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--max-insert N is 1..65535; --insert-hist PATH goes with --range auto\n");
         return 2;
     }
-    if (!stage.walk && (!stage.threadReads || stage.rangeAuto)) {
+    if (!stage.walk && ((!stage.threadReads && !stage.resolve) || stage.rangeAuto)) {
         std::fprintf(stderr, "--no-pairs goes with --thread-reads, and not with --range auto (no walk uses the range)\n");
         return 2;
     }
-    if (!ranks.check() || !link.check(ranks.world)) return 2;
+    if (!ranks.check() || !link.check(ranks.world) || !stage.checkResolve(ranks.world)) return 2;
     const int world = ranks.world, rank = ranks.rank;
     try {
         if (fastq.path.empty()) data.bin = readBin(infile);
@@ -150,6 +158,7 @@ int main(int argc, char **argv) {
             if (!lr.scaffoldsJson.empty()) jsonPut(js, "scaffolds", lr.scaffoldsJson);
         }
         if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");
+        if (stage.resolve) jsonPut(js, "resolve_repeats", res.resolveJson(stage.spanCutoff()));
         jsonPut(js, "simplified_nodes", n2, "simplified_edges", e2, "simplified_edges_length", l2, "components_histogram_2", jsonPairs(hist2),
                 "max_component_size", hist.empty() ? 0 : hist.rbegin()->first);
         if (world) jsonPut(js, "world", world);

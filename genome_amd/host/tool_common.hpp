@@ -184,24 +184,54 @@ inline void writeGraphText(genome::Graph &graph, const std::string &prefix) {
 }
 
 // GraphSimplifier.startup's paired-end stage (GraphSimplifier.scala:188-318) on a graph: position map, the pairs' walks, node
-// split by their support, simplifyGraph — and this project's additions to it: the measured insert range and the threaded reads.
+// split by their support, simplifyGraph — and this project's additions to it: the measured insert range, the threaded reads and,
+// after the reference's stage, the repeats longer than k that single reads span.
+// --resolve-repeats [CUTOFF] [--resolve-rounds N]: after the split and simplifyGraph, up to N rounds (default 1) of: a position map
+// of the graph as it is now, gk_graph_thread_spans over both mates of the same pairs, gk_graph_split_edges_by_spans at CUTOFF,
+// simplifyGraph (include/genome_amd.h, "spans": this project's own rule).  A round that resolves nothing is the last.  CUTOFF
+// defaults to the stage's support cutoff (at least 1): a choice, not a measurement.  One GPU only: the spans have no collective.
 struct PairedOpts {
     int cutoff = -1;                              // genome.cutoff
     int lo = 180, hi = 250;                       // GraphSimplifier.scala:146
     bool rangeAuto = false;                       // measure the range from the pairs instead
     long maxInsert = 4095;
     bool threadReads = false, walk = true;
+    bool resolve = false;
+    int64_t resolveCutoff = -1;                   // -1: the support cutoff
+    uint32_t resolveRounds = 1;
     bool maxInsertOk() const { return maxInsert >= 1 && maxInsert <= 65535; }
+    bool parseResolve(Args &a) {
+        if (a.optional("--resolve-repeats", resolveCutoff)) { resolve = true; return true; }
+        return a.value("--resolve-rounds", resolveRounds);
+    }
+    bool checkResolve(int world) const {
+        if (resolve && (resolveCutoff == 0 || resolveCutoff > UINT32_MAX)) { std::fprintf(stderr, "--resolve-repeats CUTOFF is 1..4294967295\n"); return false; }
+        if (!resolveRounds) { std::fprintf(stderr, "--resolve-rounds N needs N >= 1\n"); return false; }
+        if (!resolve && resolveRounds != 1) { std::fprintf(stderr, "--resolve-rounds N goes with --resolve-repeats\n"); return false; }
+        if (resolve && world) { std::fprintf(stderr, "--resolve-repeats runs on one GPU only (not with --world): the spans have no collective\n"); return false; }
+        return true;
+    }
+    uint32_t spanCutoff() const { return resolveCutoff > 0 ? (uint32_t)resolveCutoff : (uint32_t)std::max(cutoff, 1); }
 };
 struct PairedResult {
     genome::InsertRange range;                    // rangeAuto only
     genome::Graph::PairDistances dist;            // rangeAuto only
     uint64_t supPairs = 0, badPairs = 0, walked = 0, removedEdges = 0, newNodes = 0;
     genome::Graph::ThreadStats threaded;          // summed over the ranks
+    struct ResolveRound { genome::Graph::SpanStats spans; genome::Graph::SplitEdgeStats split; };
+    std::vector<ResolveRound> resolved;           // --resolve-repeats: one entry per round run
     // the "walk_pairs" object both tools print
     std::string walkJson() const {
         return jsonObject("supported_edge_pairs", supPairs, "bad_pairs", badPairs, "orientations_walked", walked, "removed_edges", removedEdges,
                           "new_nodes", newNodes);
+    }
+    // the "resolve_repeats" object both tools print: the cutoff and, per round, the five and the seven counters
+    std::string resolveJson(uint32_t cutoff) const {
+        std::string rounds = "[";
+        for (const ResolveRound &x : resolved)
+            rounds += std::string(rounds.size() > 1 ? "," : "") + "{\"thread_spans\":{" + jsonNamed(genome::Graph::spanStatNames, x.spans.v, 5) + "},\"split_edges\":{" +
+                      jsonNamed(genome::Graph::splitEdgeStatNames, x.split.v, 7) + "}}";
+        return jsonObject("cutoff", cutoff, "rounds", rounds + "]");
     }
 };
 // pm = null and world = 0: one GPU, the first takeFirst pairs; else this rank's share of them, and the sums over the ranks
@@ -240,8 +270,22 @@ inline PairedResult pairedStage(genome::Graph &graph, genome::Context &ctx, geno
         if (o.threadReads) r.threaded = graph.threadReads(graphMap, support, data, takeFirst);
     }
     std::tie(r.supPairs, r.badPairs, r.walked) = support.sizes();                                    // :266 "Bad pairs"
-    std::tie(r.removedEdges, r.newNodes) = graph.splitBySupport(support, o.cutoff);                  // :272-316
+    // (--no-pairs --resolve-repeats without --thread-reads gathered no support: the split would remove every edge at a branching
+    // node for want of evidence, so it does not run and the spans alone edit the graph)
+    if (o.walk || o.threadReads) std::tie(r.removedEdges, r.newNodes) = graph.splitBySupport(support, o.cutoff);   // :272-316
     graph.simplifyGraph();                                                                           // :318
+    for (uint32_t round = 0; o.resolve && round < o.resolveRounds; round++) {                        // this project's own: repeats longer than k
+        auto positions = graph.getGraphMap();                                                        // of the graph as it is NOW
+        genome::Spans spans(ctx);
+        PairedResult::ResolveRound x;
+        x.spans = graph.threadSpans(positions, spans, data, takeFirst);
+        x.split = graph.splitEdgesBySpans(spans, o.spanCutoff());
+        r.resolved.push_back(x);
+        std::fprintf(stderr, "resolve-repeats round %u (cutoff %u): thread_spans %s; split_edges %s\n", round + 1, o.spanCutoff(),
+                     jsonNamed(genome::Graph::spanStatNames, x.spans.v, 5).c_str(), jsonNamed(genome::Graph::splitEdgeStatNames, x.split.v, 7).c_str());
+        if (!x.split.v[1]) break;                                                                    // nothing resolved: the graph is as it was
+        graph.simplifyGraph();
+    }
     return r;
 }
 

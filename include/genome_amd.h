@@ -689,9 +689,88 @@ int gk_graph_split_by_support(gk_graph *g, const gk_support *sup, int cutoff, ui
  * and, reverse-complemented, window L-k-i of the other: two position-map probes per window, the graph is read at node windows
  * only.
  * What it resolves: the split is per node, as the reference's is.  Reads resolve junctions and remove connections that no read
- * spans; a repeat longer than k needs read paths over several nodes, which this call does not build. */
+ * spans; a repeat longer than k is an edge between two nodes, which this call does not follow: gk_graph_thread_spans and
+ * gk_graph_split_edges_by_spans (below) do, as far as a single read spans the repeat. */
 int gk_graph_thread_reads(gk_graph *g, gk_vmap *positions, gk_support *sup, const uint8_t *bin, size_t nbytes, uint64_t nreads, uint64_t *stats7);
 int gk_graph_thread_reads_dev(gk_graph *g, gk_vmap *positions, gk_support *sup, const void *dev_records, uint64_t nreads, int read_len, uint64_t *stats7);
+
+/* ---- spans: reads followed across a whole edge.  This project's own rule (the reference resolves per node,
+ * GraphSimplifier.scala:272-316, and nothing there follows a read from one node to the next) ----
+ * A repeat of r bases, k < r, is an edge m between two nodes: every copy enters it at start(m) and leaves it at end(m).  A read
+ * that holds the repeat and a base more on either side, r <= L - 2 for a read of L bases, says which way in belongs to which
+ * way out.  gk_graph_thread_spans keeps that.
+ * The rule builds on gk_graph_thread_reads': the same records (L >= k + 2), the same two strands, the same position map and
+ * getAll, the same window classes.  On one strand of a threaded record, take a crossing at inner window j with key (e_j, f_j), and
+ * let m = e_j.  The crossing falls into exactly one class, tested in this order:
+ *   1. open         j - len_m < 1: the read began inside m or at its start node;
+ *   2. span         window i = j - len_m is a crossing with f_i = m, and every window t with i < t < j is on_edge with the
+ *                   position Edge(m, t - i) (with len_m = 1 there is no window between): spans[(e_i, m, f_j)] += 1;
+ *   3. interrupted  otherwise.
+ * Counts are per occurrence, as crossings are: a read that crosses three nodes in a row over two short edges adds two spans.
+ * Twins.  If strand s of a read has crossings at i and j = i + len_m with keys (e, m) and (m, f), the other strand has crossings at
+ * L - k - j and L - k - i with keys (twin f, twin m) and (twin m, twin e), len_(twin m) = len_m, and its windows between lie on
+ * twin m at the mirrored distances; both i and j are inner windows, so both mirror images are.  A strand-closed graph therefore
+ * gets a strand-closed table: the count of (e, m, f) equals that of (twin f, twin m, twin e).
+ * stats5 (may be NULL) = uint64[5] = {records threaded, crossings, spans, interrupted, open}; element 1 is the sum of elements
+ * 2..4 and equals stats7[6] of gk_graph_thread_reads on the same input.
+ * gk_spans is an opaque device table (e, m, f) -> u32 count.  It accumulates over calls.  gk_spans_size: distinct triples and the
+ * sum of their counts (either may be NULL).  gk_spans_export: unordered; *n = the triples held, GK_E_CAPACITY (nothing copied) when
+ * cap is below it.  gk_spans_add: n (e, m, f, count) records from the host; duplicates in the list add up; export, then add into
+ * an empty table, reproduces the table.  A count that would pass 2^32-1 fails with GK_E_CAPACITY (gk_support_add's rule), here
+ * and in gk_graph_thread_spans; an id of 2^31 - 1 or more, or a fifth distinct f behind one (e, m) (a node has four out-edges),
+ * is GK_E_INVALID.  The table is unchanged on any error.
+ * gk_graph_thread_spans / _dev: positions are untrusted, stream shapes and errors are gk_graph_thread_reads' to the letter: a
+ * stale position map is GK_E_STATE, one of another k GK_E_KLEN, NULL handles or another context GK_E_INVALID, a host stream that
+ * ends inside a record or a device record whose length byte exceeds read_len GK_E_FORMAT; nreads = 0 is GK_OK with zero stats.
+ * The call counts into a table of its own and merges it at the end, so on ANY error `spans` is unchanged and stats5 is zero.
+ * Neither the graph nor the position map changes.  Edge ids are the graph's at the time of the call; the table holds no state
+ * counter.  Over N ranks every rank threads its share, exports, and one rank takes them with gk_spans_add: there is no
+ * collective.
+ * On the device: k_thread_reads' shape (a workgroup stages 64 records in LDS, a wave takes a record, a lane a window, two
+ * position-map probes per window); every window's crossing key stays in LDS, and after a wave barrier the lane that owns a
+ * crossing at j reads window j - len_m and the positions between.
+ * Where it stops: a repeat that no single read spans, r > L - 2, gives open and interrupted crossings only. */
+typedef struct gk_spans gk_spans;
+int gk_spans_create(gk_ctx *ctx, gk_spans **out);
+void gk_spans_destroy(gk_spans *s);
+int gk_spans_size(const gk_spans *s, uint64_t *triples, uint64_t *observations);
+int gk_spans_export(const gk_spans *s, uint32_t *e, uint32_t *m, uint32_t *f, uint32_t *count, uint64_t cap, uint64_t *n);   /* unordered */
+int gk_spans_add(gk_spans *s, const uint32_t *e, const uint32_t *m, const uint32_t *f, const uint32_t *count, uint64_t n);
+int gk_graph_thread_spans(gk_graph *g, gk_vmap *positions, gk_spans *spans, const uint8_t *bin, size_t nbytes, uint64_t nreads, uint64_t *stats5);
+int gk_graph_thread_spans_dev(gk_graph *g, gk_vmap *positions, gk_spans *spans, const void *dev_records, uint64_t nreads, int read_len, uint64_t *stats5);
+/* The edit.  A live edge m with u = start(m) and v = end(m) is a CANDIDATE iff out-degree(u) = 1, in-degree(v) = 1,
+ * p = in-degree(u) >= 2 and q = out-degree(v) >= 2.  Let a_1..a_p be the in-edges of u and b_1..b_q the out-edges of v, both in
+ * ascending id, and M[i][j] = (spans(a_i, m, b_j) >= cutoff).  A candidate falls into exactly one class, tested in this order:
+ *   1. unequal      p != q;
+ *   2. ambiguous    a row or a column of M holds two or more entries;
+ *   3. unsupported  a row or a column of M holds none;
+ *   4. resolved     M is a permutation.
+ * For a resolved m the pair of a_1 keeps m, u and v.  Every other pair (a_i, b_j), taken in ascending a_i, gets a copy u' of u, a
+ * copy v' of v, a copy m' of m from u' to v' (same length, first base and bases), replaceEnd(a_i, u') and replaceStart(b_j, v').
+ * New ids are appended in order of m's id, then a_i's id: two node ids (u' then v') and one edge id per copy, so the ids are a
+ * function of the input.  An edge that is both an in-edge of u and an out-edge of v is allowed (the genome A R B R C: B runs from
+ * v back to u; one pair moves its end, another its start).  Different candidates touch disjoint edge ends (the end of an in-edge
+ * of u belongs to the one candidate that leaves u, the start of an out-edge of v to the one that enters v), so all edits of a call
+ * are independent and are decided on the graph as it was when the call started.  Follow with gk_graph_simplify, which merges m
+ * and every copy with its two flanks.
+ * Twins.  The rule reads ids only to order, and degrees and counts to decide.  On a strand-closed graph twin m is a candidate iff
+ * m is (its in-edges are the twins of m's out-edges and the other way round), its matrix is M transposed under a relabelling of
+ * rows and columns, and the four classes are invariant under both; a strand-closed table therefore gives twin decisions, and the
+ * pairs of twin m are the twins of the pairs of m.  Which pair keeps the original ids is decided by id order on either strand,
+ * so the new graph is strand-closed by sequence, not by id.
+ * stats7 (may be NULL) = uint64[7] = {candidates, resolved, unequal, ambiguous, unsupported, new edges, new nodes}; element 0 is
+ * the sum of elements 1..4.  cutoff = 0 is GK_E_INVALID.  An edge id bound that would reach 2^31 - 1 (ids in positions are below
+ * it), or a node id bound of 2^32, is GK_E_CAPACITY; nothing is edited in either case.  Triples of `spans` that name dead or
+ * out-of-range ids, or edges that do not meet as (in-edge of u, m, out-edge of v), are ignored: the table may be older than the
+ * graph, and a second call with the same table edits only what the rule still finds.
+ * Coverage.  m and its copies hold the same k-mers, and a count table holds each once: gk_graph_edge_coverage reports the full
+ * count for each of them (the sum over the copies is the copy number times the true coverage), as it does for node copies.
+ * A copy shares m's bases in the sequence pool: after the build nothing rewrites a byte range that an edge owns (the merge of
+ * gk_graph_simplify reads its sources and appends; gk_graph_save compacts edge by edge into the file, so the loaded graph has one
+ * range per edge; the contigs, the scaffolds and gk_graph_checksum only read).
+ * Planning is on the host over the cached snapshot, the edits are device kernels, as gk_graph_split_by_support does it.
+ * Where it stops: repeats a single read spans, one GPU (no collective). */
+int gk_graph_split_edges_by_spans(gk_graph *g, const gk_spans *spans, uint32_t cutoff, uint64_t *stats7);
 
 /* ---- the insert range: this project's own rule (the reference hardcodes `180 to 250`, GraphSimplifier.scala:146, with
  * `160 to 270` commented out beside it, and measures nothing) ----
