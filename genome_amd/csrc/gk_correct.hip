@@ -103,8 +103,7 @@ __device__ __forceinline__ void correct_record(const Table<W, S> &t, bool empty,
                 const u32 d = invalid == 6u ? 1u : invalid == 5u ? 2u : 3u;
                 if (lane == 0) tb[ro + 1 + (p >> 2)] ^= (uint8_t)(d << ((p & 3) * 2));
                 // (a later run of this record may read the word this byte lies in)
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                wave_sync();
                 changed = true;
             }
         }

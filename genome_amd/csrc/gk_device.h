@@ -171,6 +171,20 @@ template <int W> GK_HD int owner_of(Kmer<W> x, int k, int P) {
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------
+// Wave-level helpers of the kernels in which one wave owns one work item (a record, a junction, a chain).
+// ------------------------------------------------------------------------------------------
+// between two phases of a wave: what its lanes wrote (LDS, or their own HBM scratch) is visible to all of them behind it
+GK_D void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+// the sum over the 64 lanes, in every lane (the __shfl_down reductions elsewhere leave it in lane 0 only)
+GK_D unsigned long long wave_sum(unsigned long long v) {
+    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------
 // HBM-resident open-addressed table, array-of-slots so that one probe touches one 64-B sector:
 // key word(s), the int32 count and the graph-phase annotation word live side by side.
 // ------------------------------------------------------------------------------------------

@@ -2,9 +2,9 @@
 // chain, the path's edges become members, so that the scaffold text joins them instead of writing N.
 //
 // The rule is this project's own and stated in include/genome_amd.h ("gap filling"); tests/fillgaps_ref.py restates it.  The chain
-// list comes from gk_scaffold_chains and goes on to gk_graph_scaffolds_plan, whose check (gk_chains.h) runs first here too.
+// list comes from gk_scaffold_chains and goes on to gk_graph_scaffolds_plan; its front end, the check included, is gk_chains.h's.
 //
-// k_fill_junctions: one lane per member decides adjacent / B < 1 / to be searched; a scan compacts the junctions to search.
+// k_chain_junctions by FillRule: adjacent / B < 1 / to be searched; a scan compacts the junctions to search.
 // k_fill_search: one wave per junction builds the tree of bounded paths in LDS, level by level, forward from end(e) and, only if
 // that tree outgrows max_paths, backward from start(f); hits are counted by ballot and a unique one is unwound into HBM.
 // k_fill_uses: one atomic add per path edge.  k_fill_resolve: shared or filled, the output count per member and the stats.  A scan
@@ -23,45 +23,14 @@ static constexpr int FILL_STATS = 10;
 enum { FS_ADJACENT = 0, FS_OVERFLOW, FS_NONE, FS_AMBIGUOUS, FS_SHARED, FS_FILLED, FS_EDGES, FS_BASES, FS_BACKWARD, FS_N };
 enum { FF_INTERNAL = SF_N, FF_N };
 
-__device__ __forceinline__ bool fill_bad(const u32 *flags) { return flags[SF_BAD_ID] | flags[SF_DUPLICATE] | flags[SF_CHAIN] | flags[SF_GAP]; }
-__device__ __forceinline__ void fill_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// ---------------------------------------------------------------------------------------------
-// junctions: behind a clean check; reads no length
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_fill_junctions(GraphView g, const u32 *__restrict__ members, const unsigned long long *__restrict__ chain_off, u64 nchains,
-                                                          u64 nm, const long long *__restrict__ gap, long long tol, u32 *flags, uint8_t *__restrict__ jclass,
-                                                          long long *__restrict__ jlen, u32 *__restrict__ plen, uint8_t *__restrict__ back, u32 *__restrict__ search) {
-    if (flags[SF_BAD_ID] | flags[SF_DUPLICATE] | flags[SF_CHAIN]) return;
-    for (u64 j = (u64)blockIdx.x * BLOCK + threadIdx.x; j < nm; j += (u64)gridDim.x * BLOCK) {
-        u64 lo = 0, hi = nchains;                           // the chain of member j: the last c with chain_off[c] <= j
-        while (hi - lo > 1) {
-            const u64 mid = lo + (hi - lo) / 2;
-            if (chain_off[mid] <= j) lo = mid; else hi = mid;
-        }
-        uint8_t cls = GK_FILL_LAST;
-        u32 s = 0;
-        if (j + 1 != chain_off[lo + 1]) {
-            if (g.e_end[members[j]] == g.e_start[members[j + 1]]) cls = GK_FILL_ADJACENT;
-            else {
-                const long long G = gap[j];
-                cls = GK_FILL_NONE;
-                if (G > 0x7fffffffll || G < -0x7fffffffll) flags[SF_GAP] = 1;
-                else s = G + tol + (long long)g.k >= 1;      // B < 1: none, nothing to search
-            }
-        }
-        jclass[j] = cls; jlen[j] = 0; plen[j] = 0; back[j] = 0; search[j] = s;
+// a junction that is neither adjacent nor out of the gap's range: none so far; B < 1 leaves nothing to search
+struct FillRule {
+    long long tol;
+    __device__ u32 decide(const GraphView &g, u32, u32, long long G, uint8_t *cls) const {
+        *cls = GK_FILL_NONE;
+        return G + tol + (long long)g.k >= 1;
     }
-}
-__global__ __launch_bounds__(BLOCK) void k_fill_list(u64 nm, const u32 *__restrict__ flags, const u32 *__restrict__ search, const unsigned long long *__restrict__ rank,
-                                                    u32 *__restrict__ list) {
-    if (fill_bad(flags)) return;
-    for (u64 j = (u64)blockIdx.x * BLOCK + threadIdx.x; j < nm; j += (u64)gridDim.x * BLOCK)
-        if (search[j]) list[rank[j]] = (u32)j;
-}
+};
 
 // ---------------------------------------------------------------------------------------------
 // the search: one wave per junction, the tree in LDS
@@ -123,7 +92,7 @@ __device__ FillFound fill_tree(FillTree &T, const GraphView &g, const unsigned l
                 if (n > max_paths) { r.over = true; return r; }
             }
         }
-        fill_wave_sync();                                    // the next level reads what this one appended
+        wave_sync();                                    // the next level reads what this one appended
         f0 = n0; f1 = n;
         if (f0 == f1) break;
     }
@@ -136,7 +105,7 @@ __global__ __launch_bounds__(BLOCK) void k_fill_search(GraphView g, const unsign
                                                        const unsigned long long *__restrict__ nsearch, uint8_t *__restrict__ jclass, long long *__restrict__ jlen,
                                                        u32 *__restrict__ plen, uint8_t *__restrict__ back, u32 *__restrict__ path) {
     __shared__ FillTree lds[BLOCK / 64];
-    if (fill_bad(flags)) return;
+    if (chains_bad(flags)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     FillTree &T = lds[wave];
     const u64 ns = *nsearch, waves = (u64)gridDim.x * (BLOCK / 64);
@@ -144,12 +113,12 @@ __global__ __launch_bounds__(BLOCK) void k_fill_search(GraphView g, const unsign
         const u32 j = list[w];
         const u32 from = g.e_end[members[j]], to = g.e_start[members[j + 1]];
         const long long G = gap[j], k = g.k;
-        const u32 B = (u32)(G + tol + k);                    // 1 .. 2^32-1: k_fill_junctions
+        const u32 B = (u32)(G + tol + k);                    // 1 .. 2^32-1: FillRule
         const u32 smin = (u32)max(G - tol + k, 0ll);         // L >= G - tol; L <= G + tol is sum <= B
         FillFound r = fill_tree<true>(T, g, in_off, in_list, from, to, B, smin, max_edges, max_paths);
         const bool backward = r.over;
         if (backward) {
-            fill_wave_sync();
+            wave_sync();
             r = fill_tree<false>(T, g, in_off, in_list, to, from, B, smin, max_edges, max_paths);
         }
         if (lane == 0) {
@@ -163,7 +132,7 @@ __global__ __launch_bounds__(BLOCK) void k_fill_search(GraphView g, const unsign
                 jlen[j] = (long long)T.sum[r.idx] - k;
             }
         }
-        fill_wave_sync();                                    // the next junction reuses the tree
+        wave_sync();                                    // the next junction reuses the tree
     }
 }
 
@@ -172,22 +141,18 @@ __global__ __launch_bounds__(BLOCK) void k_fill_search(GraphView g, const unsign
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void k_fill_uses(u64 nm, u32 max_edges, const u32 *__restrict__ flags, const uint8_t *__restrict__ jclass,
                                                      const u32 *__restrict__ plen, const u32 *__restrict__ path, u32 *use) {
-    if (fill_bad(flags)) return;
+    if (chains_bad(flags)) return;
     for (u64 t = (u64)blockIdx.x * BLOCK + threadIdx.x; t < nm * max_edges; t += (u64)gridDim.x * BLOCK) {
         const u64 j = t / max_edges;
         if (jclass[j] == FC_UNIQUE && t - j * max_edges < plen[j]) atomicAdd(&use[path[t]], 1u);
     }
-}
-__device__ __forceinline__ unsigned long long fill_wave_sum(unsigned long long v) {
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 // a candidate is shared iff an edge of its path is a member (owner) or is used twice (by another candidate, or by this one)
 __global__ __launch_bounds__(BLOCK) void k_fill_resolve(u64 nm, u32 max_edges, long long k, const u32 *__restrict__ flags, const u32 *__restrict__ owner,
                                                         const u32 *__restrict__ use, const u32 *__restrict__ plen, const u32 *__restrict__ path,
                                                         const long long *__restrict__ jlen, const uint8_t *__restrict__ back, uint8_t *__restrict__ jclass,
                                                         u32 *__restrict__ cnt, unsigned long long *stats) {
-    if (fill_bad(flags)) return;
+    if (chains_bad(flags)) return;
     unsigned long long st[FS_N] = {};
     for (u64 j = (u64)blockIdx.x * BLOCK + threadIdx.x; j < nm; j += (u64)gridDim.x * BLOCK) {
         uint8_t cls = jclass[j];
@@ -203,7 +168,7 @@ __global__ __launch_bounds__(BLOCK) void k_fill_resolve(u64 nm, u32 max_edges, l
         st[FS_BACKWARD] += back[j];
     }
     for (int i = 0; i < FS_N; i++) {
-        const unsigned long long v = fill_wave_sum(st[i]);
+        const unsigned long long v = wave_sum(st[i]);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&stats[i], v);
     }
 }
@@ -213,7 +178,7 @@ __global__ __launch_bounds__(BLOCK) void k_fill_write(u64 nm, u64 nchains, u32 m
                                                       const uint8_t *__restrict__ jclass, const u32 *__restrict__ plen, const u32 *__restrict__ path,
                                                       const unsigned long long *__restrict__ out_at, u64 cap, u32 *__restrict__ out_members,
                                                       long long *__restrict__ out_gap, unsigned long long *__restrict__ out_chain_off) {
-    if (fill_bad(flags)) return;
+    if (chains_bad(flags)) return;
     for (u64 j = (u64)blockIdx.x * BLOCK + threadIdx.x; j < max(nm, nchains + 1); j += (u64)gridDim.x * BLOCK) {
         if (j <= nchains) out_chain_off[j] = out_at[chain_off[j]];
         if (j >= nm) continue;
@@ -238,39 +203,30 @@ int gk_graph_fill_gaps(gk_graph *g, const uint32_t *members, const uint64_t *cha
     if (max_edges < 1 || max_edges > GK_FILL_MAX_EDGES) return fail(ctx, GK_E_INVALID, std::string(who) + ": max_edges outside 1 .. " + std::to_string(GK_FILL_MAX_EDGES));
     if (max_paths < 1 || max_paths > GK_FILL_MAX_PATHS) return fail(ctx, GK_E_INVALID, std::string(who) + ": max_paths outside 1 .. " + std::to_string(GK_FILL_MAX_PATHS));
     if (!out_chain_off || !n_members || !stats10) return fail(ctx, GK_E_INVALID, std::string(who) + ": out_chain_off, n_members or stats10 is NULL");
-    if (nchains && !chain_off) return fail(ctx, GK_E_INVALID, std::string(who) + ": chain_off is NULL");
-    const GraphView &v = g->v;
-    const u64 ne = v.n_edges;
-    // an edge occurs once at most and no chain is empty: more chains or members than edge ids cannot be right
-    if (nchains > ne) return fail(ctx, GK_E_INVALID, std::string(who) + ": more chains than edge ids");
-    const u64 nm = nchains ? chain_off[nchains] : 0;
-    if (nchains && (chain_off[0] != 0 || nm < nchains || nm > ne)) return fail(ctx, GK_E_INVALID, std::string(who) + ": chain_off does not start at 0, holds an empty chain, or lists more members than there are edge ids");
-    if (nm && (!members || !gap || !jclass || !jlen)) return fail(ctx, GK_E_INVALID, std::string(who) + ": members, gap, jclass or jlen is NULL");
-    if (nm == 0) {
+    if (nchains == 0) {                                      // (no chain, no member)
         out_chain_off[0] = 0; *n_members = 0;
         for (int i = 0; i < FILL_STATS; i++) stats10[i] = 0;
         return GK_OK;
     }
+    if (!jclass || !jlen) return fail(ctx, GK_E_INVALID, std::string(who) + ": jclass or jlen is NULL");
+    const GraphView &v = g->v;
+    DevScratch tmp(ctx);
+    ChainList cl;
+    if (int rc = chains_begin(who, g, tmp, members, chain_off, nchains, gap, FF_N, &cl)) return rc;
+    const u64 ne = v.n_edges, nm = cl.nm;
     // no edge is written twice (a filled path's edges are no members and lie on no other filled path): the output fits the edge ids
     const u64 cap = std::min<u64>(ne, nm + (nm - nchains) * max_edges);
-    DevScratch tmp(ctx);
-    u32 *d_members = nullptr, *d_owner = nullptr, *d_flags = nullptr, *d_search = nullptr, *d_list = nullptr, *d_plen = nullptr, *d_path = nullptr, *d_use = nullptr,
-        *d_cnt = nullptr, *d_out_members = nullptr, *d_in_list = nullptr, h_flags[FF_N] = {};
+    u32 *d_search = nullptr, *d_list = nullptr, *d_plen = nullptr, *d_path = nullptr, *d_use = nullptr, *d_cnt = nullptr, *d_out_members = nullptr, *d_in_list = nullptr,
+        h_flags[FF_N] = {};
     uint8_t *d_jclass = nullptr, *d_back = nullptr;
-    long long *d_gap = nullptr, *d_jlen = nullptr, *d_out_gap = nullptr;
-    unsigned long long *d_chain_off = nullptr, *d_rank = nullptr, *d_out_at = nullptr, *d_out_chain_off = nullptr, *d_stats = nullptr, *d_in_off = nullptr,
-                       h_stats[FS_N] = {}, h_n = 0;
-    tmp.upload(&d_members, members, nm);
-    tmp.upload(&d_gap, gap, nm);
-    tmp.upload(&d_chain_off, chain_off, nchains + 1);
-    tmp.zeroed(&d_owner, ne);
+    long long *d_jlen = nullptr, *d_out_gap = nullptr;
+    unsigned long long *d_rank = nullptr, *d_out_at = nullptr, *d_out_chain_off = nullptr, *d_stats = nullptr, *d_in_off = nullptr, h_stats[FS_N] = {}, h_n = 0;
     tmp.zeroed(&d_use, ne);
-    tmp.zeroed(&d_flags, FF_N);
     tmp.zeroed(&d_stats, FS_N);
     tmp.get(&d_jclass, nm);
-    tmp.get(&d_back, nm);
-    tmp.get(&d_jlen, nm);
-    tmp.get(&d_plen, nm);
+    tmp.zeroed(&d_back, nm);                                 // (zero: only the search writes these three, and only where it has something to say)
+    tmp.zeroed(&d_jlen, nm);
+    tmp.zeroed(&d_plen, nm);
     tmp.zeroed(&d_search, nm);                               // (zero, like cnt: behind a raised flag nothing writes them, and the scans still run)
     tmp.get(&d_rank, nm + 1);
     tmp.get(&d_list, nm);
@@ -282,34 +238,29 @@ int gk_graph_fill_gaps(gk_graph *g, const uint32_t *members, const uint64_t *cha
     tmp.get(&d_out_chain_off, nchains + 1);
     if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_fill_gaps: scratch");
     if (int rc = graph_in_lists(g, tmp, who, &d_in_off, &d_in_list)) return rc;
-    // the checks and the junctions behind them; every later kernel returns at once behind a raised flag
-    hipLaunchKernelGGL(k_scaf_check, dim3(ggrid(ctx, std::max(nm, (u64)nchains))), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_owner,
-                       d_flags);
-    hipLaunchKernelGGL(k_fill_junctions, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_gap, (long long)tol, d_flags,
-                       d_jclass, d_jlen, d_plen, d_back, d_search);
+    // the junctions behind the check; every later kernel returns at once behind a raised flag
+    hipLaunchKernelGGL(k_chain_junctions<FillRule>, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, v, cl.d_members, cl.d_chain_off, (u64)nchains, nm, cl.d_gap,
+                       FillRule{(long long)tol}, cl.d_flags, d_jclass, d_search);
     GK_HIP(ctx, hipGetLastError());
     GK_HIP(ctx, scan_counts(ctx, tmp, d_search, nm, d_rank));
-    hipLaunchKernelGGL(k_fill_list, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, nm, d_flags, d_search, d_rank, d_list);
-    hipLaunchKernelGGL(k_fill_search, dim3(ggrid(ctx, (nm - nchains) * 64)), dim3(BLOCK), 0, ctx->stream, v, d_in_off, d_in_list, d_members, d_gap, (long long)tol,
-                       max_edges, max_paths, d_flags, d_list, d_rank + nm, d_jclass, d_jlen, d_plen, d_back, d_path);
-    hipLaunchKernelGGL(k_fill_uses, dim3(ggrid(ctx, nm * max_edges)), dim3(BLOCK), 0, ctx->stream, nm, max_edges, d_flags, d_jclass, d_plen, d_path, d_use);
-    hipLaunchKernelGGL(k_fill_resolve, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, nm, max_edges, (long long)v.k, d_flags, d_owner, d_use, d_plen, d_path, d_jlen,
+    hipLaunchKernelGGL(k_chain_list, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, nm, cl.d_flags, d_search, d_rank, d_list);
+    hipLaunchKernelGGL(k_fill_search, dim3(ggrid(ctx, (nm - nchains) * 64)), dim3(BLOCK), 0, ctx->stream, v, d_in_off, d_in_list, cl.d_members, cl.d_gap, (long long)tol,
+                       max_edges, max_paths, cl.d_flags, d_list, d_rank + nm, d_jclass, d_jlen, d_plen, d_back, d_path);
+    hipLaunchKernelGGL(k_fill_uses, dim3(ggrid(ctx, nm * max_edges)), dim3(BLOCK), 0, ctx->stream, nm, max_edges, cl.d_flags, d_jclass, d_plen, d_path, d_use);
+    hipLaunchKernelGGL(k_fill_resolve, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, nm, max_edges, (long long)v.k, cl.d_flags, cl.d_owner, d_use, d_plen, d_path, d_jlen,
                        d_back, d_jclass, d_cnt, d_stats);
     GK_HIP(ctx, hipGetLastError());
     GK_HIP(ctx, scan_counts(ctx, tmp, d_cnt, nm, d_out_at));
-    hipLaunchKernelGGL(k_fill_write, dim3(ggrid(ctx, std::max(nm, (u64)nchains + 1))), dim3(BLOCK), 0, ctx->stream, nm, (u64)nchains, max_edges, (long long)v.k, d_flags,
-                       d_members, d_chain_off, d_gap, d_jclass, d_plen, d_path, d_out_at, cap, d_out_members, d_out_gap, d_out_chain_off);
+    hipLaunchKernelGGL(k_fill_write, dim3(ggrid(ctx, std::max(nm, (u64)nchains + 1))), dim3(BLOCK), 0, ctx->stream, nm, (u64)nchains, max_edges, (long long)v.k, cl.d_flags,
+                       cl.d_members, cl.d_chain_off, cl.d_gap, d_jclass, d_plen, d_path, d_out_at, cap, d_out_members, d_out_gap, d_out_chain_off);
     std::vector<u32> h_members(cap);
     std::vector<long long> h_gap(cap), h_jlen(nm);
     std::vector<unsigned long long> h_chain_off(nchains + 1);
     std::vector<uint8_t> h_jclass(nm);
-    GK_HIP(ctx, read_back(ctx, {{h_flags, d_flags, sizeof(h_flags)}, {h_stats, d_stats, sizeof(h_stats)}, {&h_n, d_out_at + nm, 8}, {h_members.data(), d_out_members, cap * 4},
+    GK_HIP(ctx, read_back(ctx, {{h_flags, cl.d_flags, sizeof(h_flags)}, {h_stats, d_stats, sizeof(h_stats)}, {&h_n, d_out_at + nm, 8}, {h_members.data(), d_out_members, cap * 4},
                                 {h_gap.data(), d_out_gap, cap * 8}, {h_chain_off.data(), d_out_chain_off, (nchains + 1) * 8}, {h_jclass.data(), d_jclass, nm},
                                 {h_jlen.data(), d_jlen, nm * 8}}));
-    if (h_flags[SF_CHAIN]) return fail(ctx, GK_E_INVALID, std::string(who) + ": an empty chain, or a chain_off that does not ascend");
-    if (h_flags[SF_BAD_ID]) return fail(ctx, GK_E_INVALID, std::string(who) + ": a member that is no live edge of this graph");
-    if (h_flags[SF_DUPLICATE]) return fail(ctx, GK_E_INVALID, std::string(who) + ": an edge occurs twice in the chains");
-    if (h_flags[SF_GAP]) return fail(ctx, GK_E_INVALID, std::string(who) + ": a gap beyond +-(2^31-1) at a junction that is not adjacent");
+    if (int rc = chains_failed(who, ctx, h_flags, true)) return rc;
     if (h_flags[FF_INTERNAL] || h_n > cap) return fail(ctx, GK_E_STATE, std::string(who) + ": the filled chains outgrew the edge ids (internal error)");
     if (members_cap >= h_n && (!out_members || !out_gap)) return fail(ctx, GK_E_INVALID, std::string(who) + ": out_members or out_gap is NULL");
     u64 st[FILL_STATS] = {};

@@ -3,11 +3,11 @@
 // bases once instead of twice with N between them.
 //
 // The rule is this project's own and stated in include/genome_amd.h ("overlap detection"); tests/overlaps_ref.py restates it.  The
-// chain list comes from gk_scaffold_chains or gk_graph_fill_gaps and goes on, with the overlaps, to gk_graph_scaffolds_plan_overlaps,
-// whose check (gk_chains.h) runs first here too.
+// chain list comes from gk_scaffold_chains or gk_graph_fill_gaps and goes on, with the overlaps, to gk_graph_scaffolds_plan_overlaps;
+// its front end, the check included, is gk_chains.h's.
 //
-// k_ovl_junctions: one lane per member decides last / adjacent / out_of_range / to be searched; a scan compacts the junctions to
-// search.  k_ovl_search: one wave per junction packs the two ends into four 64-bit words each in LDS; a lane tests the candidates
+// k_chain_junctions by OvlRule: adjacent / out_of_range / to be searched; a scan compacts the junctions to search.
+// k_ovl_search: one wave per junction packs the two ends into four 64-bit words each in LDS; a lane tests the candidates
 // lo + lane and lo + lane + 64 by a multi-word shift, mask and compare; the hits are counted by ballot.  k_ovl_stats: a reduction
 // over the classes.  Nothing but scratch is written on the device; the host copies out after one read-back.
 #include <vector>
@@ -22,55 +22,24 @@ static constexpr int OVL_WORDS = 4;
 // device counters of a call: the five classes in the order of the GK_OVL_* codes, then the overlapped bases
 enum { OS_ADJACENT = 0, OS_OUT_OF_RANGE, OS_NONE, OS_AMBIGUOUS, OS_OVERLAP, OS_BASES, OS_N };
 
-__device__ __forceinline__ bool ovl_bad(const u32 *flags) { return flags[SF_BAD_ID] | flags[SF_DUPLICATE] | flags[SF_CHAIN] | flags[SF_GAP]; }
-__device__ __forceinline__ void ovl_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 // the candidates lo .. hi of a junction whose members' paths hold pe and pf bases (|G| and tol are below 2^31)
 __device__ __forceinline__ void ovl_range(long long G, long long tol, u32 min_overlap, u32 max_overlap, u64 pe, u64 pf, long long *lo, long long *hi) {
     *lo = max((long long)min_overlap, -G - tol);
     *hi = min(min((long long)max_overlap, -G + tol), (long long)min(min(pe, pf) - 1, (u64)GK_OVERLAP_MAX));
 }
 
-// ---------------------------------------------------------------------------------------------
-// junctions: behind a clean check
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_ovl_junctions(GraphView g, const u32 *__restrict__ members, const unsigned long long *__restrict__ chain_off, u64 nchains,
-                                                         u64 nm, const long long *__restrict__ gap, long long tol, u32 min_overlap, u32 max_overlap, u32 *flags,
-                                                         uint8_t *__restrict__ jclass, u32 *__restrict__ overlap, u32 *__restrict__ search) {
-    if (flags[SF_BAD_ID] | flags[SF_DUPLICATE] | flags[SF_CHAIN]) return;
-    for (u64 j = (u64)blockIdx.x * BLOCK + threadIdx.x; j < nm; j += (u64)gridDim.x * BLOCK) {
-        u64 lo = 0, hi = nchains;                           // the chain of member j: the last c with chain_off[c] <= j
-        while (hi - lo > 1) {
-            const u64 mid = lo + (hi - lo) / 2;
-            if (chain_off[mid] <= j) lo = mid; else hi = mid;
-        }
-        uint8_t cls = GK_OVL_LAST;
-        u32 s = 0;
-        if (j + 1 != chain_off[lo + 1]) {
-            const u32 e = members[j], f = members[j + 1];
-            if (g.e_end[e] == g.e_start[f]) cls = GK_OVL_ADJACENT;
-            else {
-                const long long G = gap[j];
-                cls = GK_OVL_OUT_OF_RANGE;
-                if (G > 0x7fffffffll || G < -0x7fffffffll) flags[SF_GAP] = 1;
-                else {
-                    long long a, b;
-                    ovl_range(G, tol, min_overlap, max_overlap, (u64)g.k + g.e_len[e], (u64)g.k + g.e_len[f], &a, &b);
-                    if (a <= b) { cls = GK_OVL_NONE; s = 1; }
-                }
-            }
-        }
-        jclass[j] = cls; overlap[j] = 0; search[j] = s;
+// a junction that is neither adjacent nor out of the gap's range (behind a clean check: it reads the members' lengths): with a
+// candidate, none so far and to be searched
+struct OvlRule {
+    long long tol;
+    u32 min_overlap, max_overlap;
+    __device__ u32 decide(const GraphView &g, u32 e, u32 f, long long G, uint8_t *cls) const {
+        long long a, b;
+        ovl_range(G, tol, min_overlap, max_overlap, (u64)g.k + g.e_len[e], (u64)g.k + g.e_len[f], &a, &b);
+        *cls = a <= b ? GK_OVL_NONE : GK_OVL_OUT_OF_RANGE;
+        return a <= b;
     }
-}
-__global__ __launch_bounds__(BLOCK) void k_ovl_list(u64 nm, const u32 *__restrict__ flags, const u32 *__restrict__ search, const unsigned long long *__restrict__ rank,
-                                                   u32 *__restrict__ list) {
-    if (ovl_bad(flags)) return;
-    for (u64 j = (u64)blockIdx.x * BLOCK + threadIdx.x; j < nm; j += (u64)gridDim.x * BLOCK)
-        if (search[j]) list[rank[j]] = (u32)j;
-}
+};
 
 // ---------------------------------------------------------------------------------------------
 // the search: one wave per junction, the two ends in LDS
@@ -109,7 +78,7 @@ __global__ __launch_bounds__(BLOCK) void k_ovl_search(GraphView g, const u32 *__
                                                      u32 max_overlap, const u32 *__restrict__ flags, const u32 *__restrict__ list,
                                                      const unsigned long long *__restrict__ nsearch, uint8_t *__restrict__ jclass, u32 *__restrict__ overlap) {
     __shared__ u64 lds[BLOCK / 64][2 * OVL_WORDS];
-    if (ovl_bad(flags)) return;
+    if (chains_bad(flags)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     u64 *E = lds[wave], *F = lds[wave] + OVL_WORDS;
     const u64 ns = *nsearch, waves = (u64)gridDim.x * (BLOCK / 64);
@@ -118,11 +87,11 @@ __global__ __launch_bounds__(BLOCK) void k_ovl_search(GraphView g, const u32 *__
         const u32 e = members[j], f = members[j + 1];
         const u64 pe = (u64)g.k + g.e_len[e], pf = (u64)g.k + g.e_len[f];
         long long lo, hi;
-        ovl_range(gap[j], tol, min_overlap, max_overlap, pe, pf, &lo, &hi);      // 1 <= lo <= hi <= 127: k_ovl_junctions
+        ovl_range(gap[j], tol, min_overlap, max_overlap, pe, pf, &lo, &hi);      // 1 <= lo <= hi <= 127: OvlRule
         const u32 ne = (u32)min(pe, (u64)GK_OVERLAP_MAX), nf = (u32)min(pf, (u64)GK_OVERLAP_MAX);
         ovl_pack(g, e, pe - ne, ne, E);
         ovl_pack(g, f, 0, nf, F);
-        ovl_wave_sync();
+        wave_sync();
         u32 hits = 0, hit = 0;
         for (u32 round = 0; round < 2; round++) {
             const long long o = lo + lane + 64 * round;
@@ -135,7 +104,7 @@ __global__ __launch_bounds__(BLOCK) void k_ovl_search(GraphView g, const u32 *__
             jclass[j] = hits == 0 ? GK_OVL_NONE : hits > 1 ? GK_OVL_AMBIGUOUS : GK_OVL_OVERLAP;
             overlap[j] = hits == 1 ? hit : 0u;
         }
-        ovl_wave_sync();                                     // the next junction reuses the words
+        wave_sync();                                     // the next junction reuses the words
     }
 }
 
@@ -144,7 +113,7 @@ __global__ __launch_bounds__(BLOCK) void k_ovl_search(GraphView g, const u32 *__
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void k_ovl_stats(u64 nm, const u32 *__restrict__ flags, const uint8_t *__restrict__ jclass, const u32 *__restrict__ overlap,
                                                     unsigned long long *stats) {
-    if (ovl_bad(flags)) return;
+    if (chains_bad(flags)) return;
     unsigned long long st[OS_N] = {};
     for (u64 j = (u64)blockIdx.x * BLOCK + threadIdx.x; j < nm; j += (u64)gridDim.x * BLOCK) {
         const uint8_t cls = jclass[j];
@@ -152,8 +121,7 @@ __global__ __launch_bounds__(BLOCK) void k_ovl_stats(u64 nm, const u32 *__restri
         st[OS_BASES] += overlap[j];
     }
     for (int i = 0; i < OS_N; i++) {
-        unsigned long long v = st[i];
-        for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+        const unsigned long long v = wave_sum(st[i]);
         if ((threadIdx.x & 63) == 0 && v) atomicAdd(&stats[i], v);
     }
 }
@@ -170,54 +138,40 @@ int gk_graph_overlap_gaps(gk_graph *g, const uint32_t *members, const uint64_t *
     if (max_overlap < min_overlap || max_overlap > GK_OVERLAP_MAX)
         return fail(ctx, GK_E_INVALID, std::string(who) + ": max_overlap outside min_overlap .. " + std::to_string(GK_OVERLAP_MAX));
     if (!stats7) return fail(ctx, GK_E_INVALID, std::string(who) + ": stats7 is NULL");
-    if (nchains && !chain_off) return fail(ctx, GK_E_INVALID, std::string(who) + ": chain_off is NULL");
-    const GraphView &v = g->v;
-    const u64 ne = v.n_edges;
-    // an edge occurs once at most and no chain is empty: more chains or members than edge ids cannot be right
-    if (nchains > ne) return fail(ctx, GK_E_INVALID, std::string(who) + ": more chains than edge ids");
-    const u64 nm = nchains ? chain_off[nchains] : 0;
-    if (nchains && (chain_off[0] != 0 || nm < nchains || nm > ne)) return fail(ctx, GK_E_INVALID, std::string(who) + ": chain_off does not start at 0, holds an empty chain, or lists more members than there are edge ids");
-    if (nm && (!members || !gap || !overlap || !jclass)) return fail(ctx, GK_E_INVALID, std::string(who) + ": members, gap, overlap or jclass is NULL");
-    if (nm == 0) {
+    if (nchains == 0) {                                      // (no chain, no member)
         for (int i = 0; i < OVL_STATS; i++) stats7[i] = 0;
         return GK_OK;
     }
+    if (!overlap || !jclass) return fail(ctx, GK_E_INVALID, std::string(who) + ": overlap or jclass is NULL");
+    const GraphView &v = g->v;
     DevScratch tmp(ctx);
-    u32 *d_members = nullptr, *d_owner = nullptr, *d_flags = nullptr, *d_search = nullptr, *d_list = nullptr, *d_overlap = nullptr, h_flags[SF_N] = {};
+    ChainList cl;
+    if (int rc = chains_begin(who, g, tmp, members, chain_off, nchains, gap, SF_N, &cl)) return rc;
+    const u64 nm = cl.nm;
+    u32 *d_search = nullptr, *d_list = nullptr, *d_overlap = nullptr, h_flags[SF_N] = {};
     uint8_t *d_jclass = nullptr;
-    long long *d_gap = nullptr;
-    unsigned long long *d_chain_off = nullptr, *d_rank = nullptr, *d_stats = nullptr, h_stats[OS_N] = {};
-    tmp.upload(&d_members, members, nm);
-    tmp.upload(&d_gap, gap, nm);
-    tmp.upload(&d_chain_off, chain_off, nchains + 1);
-    tmp.zeroed(&d_owner, ne);
-    tmp.zeroed(&d_flags, SF_N);
+    unsigned long long *d_rank = nullptr, *d_stats = nullptr, h_stats[OS_N] = {};
     tmp.zeroed(&d_stats, OS_N);
     tmp.get(&d_jclass, nm);
-    tmp.get(&d_overlap, nm);
+    tmp.zeroed(&d_overlap, nm);                              // (zero: only the search writes it)
     tmp.zeroed(&d_search, nm);                               // (zero: behind a raised flag nothing writes it, and the scan still runs)
     tmp.get(&d_rank, nm + 1);
     tmp.get(&d_list, nm);
     if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_overlap_gaps: scratch");
-    // the checks and the junctions behind them; every later kernel returns at once behind a raised flag
-    hipLaunchKernelGGL(k_scaf_check, dim3(ggrid(ctx, std::max(nm, (u64)nchains))), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_owner,
-                       d_flags);
-    hipLaunchKernelGGL(k_ovl_junctions, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_gap, (long long)tol, min_overlap,
-                       max_overlap, d_flags, d_jclass, d_overlap, d_search);
+    // the junctions behind the check; every later kernel returns at once behind a raised flag
+    hipLaunchKernelGGL(k_chain_junctions<OvlRule>, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, v, cl.d_members, cl.d_chain_off, (u64)nchains, nm, cl.d_gap,
+                       OvlRule{(long long)tol, min_overlap, max_overlap}, cl.d_flags, d_jclass, d_search);
     GK_HIP(ctx, hipGetLastError());
     GK_HIP(ctx, scan_counts(ctx, tmp, d_search, nm, d_rank));
-    hipLaunchKernelGGL(k_ovl_list, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, nm, d_flags, d_search, d_rank, d_list);
-    hipLaunchKernelGGL(k_ovl_search, dim3(ggrid(ctx, (nm - nchains) * 64)), dim3(BLOCK), 0, ctx->stream, v, d_members, d_gap, (long long)tol, min_overlap, max_overlap,
-                       d_flags, d_list, d_rank + nm, d_jclass, d_overlap);
-    hipLaunchKernelGGL(k_ovl_stats, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, nm, d_flags, d_jclass, d_overlap, d_stats);
+    hipLaunchKernelGGL(k_chain_list, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, nm, cl.d_flags, d_search, d_rank, d_list);
+    hipLaunchKernelGGL(k_ovl_search, dim3(ggrid(ctx, (nm - nchains) * 64)), dim3(BLOCK), 0, ctx->stream, v, cl.d_members, cl.d_gap, (long long)tol, min_overlap, max_overlap,
+                       cl.d_flags, d_list, d_rank + nm, d_jclass, d_overlap);
+    hipLaunchKernelGGL(k_ovl_stats, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, nm, cl.d_flags, d_jclass, d_overlap, d_stats);
     std::vector<u32> h_overlap(nm);
     std::vector<uint8_t> h_jclass(nm);
-    GK_HIP(ctx, read_back(ctx, {{h_flags, d_flags, sizeof(h_flags)}, {h_stats, d_stats, sizeof(h_stats)}, {h_overlap.data(), d_overlap, nm * 4},
+    GK_HIP(ctx, read_back(ctx, {{h_flags, cl.d_flags, sizeof(h_flags)}, {h_stats, d_stats, sizeof(h_stats)}, {h_overlap.data(), d_overlap, nm * 4},
                                 {h_jclass.data(), d_jclass, nm}}));
-    if (h_flags[SF_CHAIN]) return fail(ctx, GK_E_INVALID, std::string(who) + ": an empty chain, or a chain_off that does not ascend");
-    if (h_flags[SF_BAD_ID]) return fail(ctx, GK_E_INVALID, std::string(who) + ": a member that is no live edge of this graph");
-    if (h_flags[SF_DUPLICATE]) return fail(ctx, GK_E_INVALID, std::string(who) + ": an edge occurs twice in the chains");
-    if (h_flags[SF_GAP]) return fail(ctx, GK_E_INVALID, std::string(who) + ": a gap beyond +-(2^31-1) at a junction that is not adjacent");
+    if (int rc = chains_failed(who, ctx, h_flags, true)) return rc;
     stats7[0] = 0;
     for (int i = 0; i < OS_BASES; i++) { stats7[1 + i] = h_stats[i]; stats7[0] += h_stats[i]; }
     stats7[6] = h_stats[OS_BASES];

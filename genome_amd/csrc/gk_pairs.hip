@@ -246,10 +246,6 @@ struct WaveLds {
 };
 struct WalkArgs { int k, lo, hi; u32 rmax, qcap, pmax; };      // (the three set limits: W_RMAX / W_QCAP / W_PMAX, or a test's tiny ones)
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 // reached[node] = min(reached[node], d); false if the set is full
 __device__ __forceinline__ bool reach_relax(WaveLds &L, u32 node, u32 d, u32 rmax) {
     u32 h = hash32(node) & (W_RCAP - 1);

@@ -4,8 +4,8 @@
 // The rule is this project's own and stated in include/genome_amd.h ("scaffolds: this project's own rule"); tests/scaffolds_ref.py
 // restates it.  The chains are gk_scaffold_chains' (gk_links.hip), the text helpers and the chunked stream gk_fastaout.h's.
 //
-// The plan.  k_scaf_check: one lane per member claims its edge's owner word (a second claim is a duplicate).  k_scaf_segments: one
-// lane per member decides its junction and fills two slots, an N run and a piece of the edge's path; a scan over the slot lengths
+// The plan.  The chain list's front end, the check included, is gk_chains.h's.  k_scaf_segments: one lane per member decides the
+// junction before it and fills two slots, an N run and a piece of the edge's path; a scan over the slot lengths
 // places every slot in its scaffold.  k_scaf_strand: one wave per chain compares the scaffold with its reverse complement, a lane
 // finding its base by a binary search in the chain's slots, and sizes the record.  k_scaf_single: k_contig_classify's comparison
 // over the live edges no chain claimed.  Three more scans and two compactions leave the records (name, byte offset, segment range, n)
@@ -26,7 +26,7 @@ enum { SS_FORWARD = 0, SS_SELF, SS_REVERSE, SS_SINGLE, SS_MEMBERS, SS_ADJACENT, 
 static constexpr int SCAFFOLD_STATS = 13;
 
 // ---------------------------------------------------------------------------------------------
-// checks: before any kernel reads a member's length (k_scaf_check and the error flags: gk_chains.h)
+// segments
 // ---------------------------------------------------------------------------------------------
 // Member j of chain c fills slots 2j (an N run, or nothing) and 2j + 1 (its piece).  Runs only behind a clean check.  `overlap`
 // (may be null) is the caller's and is not trusted: an entry that the rule cannot have given raises SF_OVERLAP.
@@ -43,13 +43,9 @@ __global__ __launch_bounds__(BLOCK) void k_scaf_segments(GraphView g, const u32 
                                                          u32 *__restrict__ chain_of,
                                                          uint8_t *__restrict__ mclass, u32 *__restrict__ slot_len, u32 *__restrict__ slot_edge,
                                                          uint8_t *__restrict__ slot_skip) {
-    if (flags[SF_BAD_ID] | flags[SF_DUPLICATE] | flags[SF_CHAIN]) return;
+    if (chains_unchecked(flags)) return;
     for (u64 j = (u64)blockIdx.x * BLOCK + threadIdx.x; j < nm; j += (u64)gridDim.x * BLOCK) {
-        u64 lo = 0, hi = nchains;                           // the chain of member j: the last c with chain_off[c] <= j
-        while (hi - lo > 1) {
-            const u64 mid = lo + (hi - lo) / 2;
-            if (chain_off[mid] <= j) lo = mid; else hi = mid;
-        }
+        const u64 lo = chain_of_member(chain_off, nchains, j);
         const u32 e = members[j];
         uint8_t cls = MC_FIRST;
         u64 run = 0;
@@ -100,10 +96,6 @@ __device__ __forceinline__ int scaf_base(const GraphView &g, const unsigned long
 }
 __device__ __forceinline__ int scaf_hdr_len(bool chain, u64 id, u64 n, u64 m, u64 gaps) {
     return 2 + dec_digits(id) + 5 + dec_digits(n) + (chain ? 9 + dec_digits(m) + 6 + dec_digits(gaps) : 0) + 1;
-}
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-    for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // sel[c] = 1 for a record, size[c] = the bytes of its text, chain_n[c] / chain_gaps[c] = its bases / those of them that are N
@@ -444,32 +436,21 @@ static int scaffolds_plan(const char *who, gk_graph *g, const uint32_t *members,
     if (strands != 1 && strands != 2) return fail(ctx, GK_E_INVALID, std::string(who) + ": strands is 1 (one record per scaffold) or 2 (both strands)");
     if (line_width > 0x7fffffffu) return fail(ctx, GK_E_INVALID, std::string(who) + ": line_width beyond 2^31-1");
     if (min_gap < 1 || min_gap > 0x7fffffffll) return fail(ctx, GK_E_INVALID, std::string(who) + ": min_gap outside 1 .. 2^31-1");
-    if (nchains && !chain_off) return fail(ctx, GK_E_INVALID, std::string(who) + ": chain_off is NULL");
     const GraphView &v = g->v;
     const u64 ne = v.n_edges;
-    // an edge occurs once at most and no chain is empty: more chains or members than edge ids cannot be right
-    if (nchains > ne) return fail(ctx, GK_E_INVALID, std::string(who) + ": more chains than edge ids");
-    const u64 nm = nchains ? chain_off[nchains] : 0;
-    if (nchains && (chain_off[0] != 0 || nm < nchains || nm > ne)) return fail(ctx, GK_E_INVALID, std::string(who) + ": chain_off does not start at 0, holds an empty chain, or lists more members than there are edge ids");
-    if (nm && (!members || !gap)) return fail(ctx, GK_E_INVALID, std::string(who) + ": members or gap is NULL");
     std::unique_ptr<gk_scaffolds, void (*)(gk_scaffolds *)> s(new gk_scaffolds, gk_scaffolds_destroy);
     s->ctx = ctx; s->ts.ctx = ctx; s->g = g; s->epoch = g->epoch; s->line_width = line_width;
-    if (ne == 0) { *out = s.release(); return GK_OK; }
-    const u64 T = nchains + ne, U = 2 * nm + ne;
+    if (ne == 0 && nchains == 0) { *out = s.release(); return GK_OK; }
     DevScratch tmp(ctx);
-    u32 *d_members = nullptr, *d_overlap = nullptr, *d_owner = nullptr, *d_flags = nullptr, *d_chain_of = nullptr, *d_slot_len = nullptr, *d_slot_edge = nullptr, *d_sel = nullptr,
-        *d_size = nullptr, *d_chain_n = nullptr, *d_chain_gaps = nullptr, *d_flag = nullptr, h_flags[SF_N] = {};
+    ChainList cl;
+    if (int rc = chains_begin(who, g, tmp, members, chain_off, nchains, gap, SF_N, &cl)) return rc;
+    const u64 nm = cl.nm, T = nchains + ne, U = 2 * nm + ne;
+    u32 *d_overlap = nullptr, *d_chain_of = nullptr, *d_slot_len = nullptr, *d_slot_edge = nullptr, *d_sel = nullptr, *d_size = nullptr, *d_chain_n = nullptr,
+        *d_chain_gaps = nullptr, *d_flag = nullptr, h_flags[SF_N] = {};
     uint8_t *d_mclass = nullptr, *d_slot_skip = nullptr;
-    long long *d_gap = nullptr;
-    unsigned long long *d_chain_off = nullptr, *d_slot_base = nullptr, *d_rank = nullptr, *d_off = nullptr, *d_segrank = nullptr, *d_stats = nullptr,
-                       h_stats[SS_N] = {}, h_records = 0, h_chain_recs = 0, h_bytes = 0, h_segs = 0;
-    const u64 zero_off[1] = {0};
-    if (nm) { tmp.upload(&d_members, members, nm); tmp.upload(&d_gap, gap, nm); }
-    else { tmp.get(&d_members, 1); tmp.get(&d_gap, 1); }
+    unsigned long long *d_slot_base = nullptr, *d_rank = nullptr, *d_off = nullptr, *d_segrank = nullptr, *d_stats = nullptr, h_stats[SS_N] = {}, h_records = 0,
+                       h_chain_recs = 0, h_bytes = 0, h_segs = 0;
     if (nm && overlap) tmp.upload(&d_overlap, overlap, nm);
-    tmp.upload(&d_chain_off, nchains ? chain_off : zero_off, nchains + 1);
-    tmp.zeroed(&d_owner, ne);
-    tmp.zeroed(&d_flags, SF_N);
     tmp.zeroed(&d_stats, SS_N);
     tmp.get(&d_chain_of, nm);
     tmp.get(&d_mclass, nm);
@@ -486,26 +467,21 @@ static int scaffolds_plan(const char *who, gk_graph *g, const uint32_t *members,
     tmp.get(&d_off, T + 1);
     tmp.get(&d_segrank, U + 1);
     if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), (std::string(who) + ": scratch").c_str());
-    // the checks, and the segments behind them; one read of the flags
-    hipLaunchKernelGGL(k_scaf_check, dim3(ggrid(ctx, std::max(nm, (u64)nchains))), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_owner,
-                       d_flags);
-    hipLaunchKernelGGL(k_scaf_segments, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, v, d_members, d_chain_off, (u64)nchains, nm, d_gap, d_overlap,
-                       (long long)min_gap, d_flags, d_chain_of, d_mclass, d_slot_len, d_slot_edge, d_slot_skip);
-    GK_HIP(ctx, read_back(ctx, h_flags, d_flags, SF_N));
-    if (h_flags[SF_CHAIN]) return fail(ctx, GK_E_INVALID, std::string(who) + ": an empty chain, or a chain_off that does not ascend");
-    if (h_flags[SF_BAD_ID]) return fail(ctx, GK_E_INVALID, std::string(who) + ": a member that is no live edge of this graph");
-    if (h_flags[SF_DUPLICATE]) return fail(ctx, GK_E_INVALID, std::string(who) + ": an edge occurs twice in the chains");
-    if (h_flags[SF_GAP]) return fail(ctx, GK_E_INVALID, std::string(who) + ": a gap above 2^31-1");
+    // the segments behind the check; one read of the flags
+    hipLaunchKernelGGL(k_scaf_segments, dim3(ggrid(ctx, nm)), dim3(BLOCK), 0, ctx->stream, v, cl.d_members, cl.d_chain_off, (u64)nchains, nm, cl.d_gap, d_overlap,
+                       (long long)min_gap, cl.d_flags, d_chain_of, d_mclass, d_slot_len, d_slot_edge, d_slot_skip);
+    GK_HIP(ctx, read_back(ctx, h_flags, cl.d_flags, SF_N));
+    if (int rc = chains_failed(who, ctx, h_flags, false)) return rc;
     if (h_flags[SF_OVERLAP])
         return fail(ctx, GK_E_INVALID, std::string(who) + ": an overlap at an adjacent junction, above GK_OVERLAP_MAX, not below both path lengths, or whose bases differ");
     if (h_flags[SF_OVERFLOW]) return fail(ctx, GK_E_CAPACITY, std::string(who) + ": a record of 2^32 bytes or more");
     // every slot's place in its scaffold, the strand and size of every chain, the edges no chain claimed
     GK_HIP(ctx, scan_counts(ctx, tmp, d_slot_len, 2 * nm, d_slot_base));
-    hipLaunchKernelGGL(k_scaf_strand, dim3(ggrid(ctx, (u64)nchains * 64)), dim3(BLOCK), 0, ctx->stream, v, d_chain_off, (u64)nchains, d_slot_base, d_slot_len, d_slot_edge,
+    hipLaunchKernelGGL(k_scaf_strand, dim3(ggrid(ctx, (u64)nchains * 64)), dim3(BLOCK), 0, ctx->stream, v, cl.d_chain_off, (u64)nchains, d_slot_base, d_slot_len, d_slot_edge,
                        d_slot_skip, d_mclass, (u32)line_width, strands, d_sel, d_size, d_chain_n, d_chain_gaps, d_stats);
     GK_HIP(ctx, hipGetLastError());
     if (singletons) {
-        hipLaunchKernelGGL(k_scaf_single, dim3(ggrid(ctx, ne * 64)), dim3(BLOCK), 0, ctx->stream, v, d_owner, (u64)min_len, (u32)line_width, strands, d_sel + nchains,
+        hipLaunchKernelGGL(k_scaf_single, dim3(ggrid(ctx, ne * 64)), dim3(BLOCK), 0, ctx->stream, v, cl.d_owner, (u64)min_len, (u32)line_width, strands, d_sel + nchains,
                            d_size + nchains, d_flag + 2 * nm, d_stats);
         GK_HIP(ctx, hipGetLastError());
     } else {
@@ -532,9 +508,9 @@ static int scaffolds_plan(const char *who, gk_graph *g, const uint32_t *members,
     tmp.get(&s->d_seg_start, h_segs);
     tmp.get(&s->d_seg_skip, h_segs);
     if (tmp.error() != hipSuccess) { scaffolds_drop_plan(s.get()); return hip_fail(ctx, tmp.error(), (std::string(who) + ": the plan").c_str()); }
-    hipLaunchKernelGGL(k_scaf_compact_recs, dim3(ggrid(ctx, T + 1)), dim3(BLOCK), 0, ctx->stream, v, (u64)nchains, nm, d_chain_off, d_sel, d_rank, d_off, d_segrank,
+    hipLaunchKernelGGL(k_scaf_compact_recs, dim3(ggrid(ctx, T + 1)), dim3(BLOCK), 0, ctx->stream, v, (u64)nchains, nm, cl.d_chain_off, d_sel, d_rank, d_off, d_segrank,
                        d_chain_n, d_chain_gaps, s->d_rec_id, s->d_rec_off, s->d_rec_seg, s->d_rec_n, s->d_rec_m, s->d_rec_gaps);
-    hipLaunchKernelGGL(k_scaf_compact_segs, dim3(ggrid(ctx, U)), dim3(BLOCK), 0, ctx->stream, ne, nm, d_chain_off, d_chain_of, d_flag, d_segrank, d_slot_base, d_slot_edge,
+    hipLaunchKernelGGL(k_scaf_compact_segs, dim3(ggrid(ctx, U)), dim3(BLOCK), 0, ctx->stream, ne, nm, cl.d_chain_off, d_chain_of, d_flag, d_segrank, d_slot_base, d_slot_edge,
                        d_slot_skip, s->d_seg_edge, s->d_seg_start, s->d_seg_skip);
     const hipError_t e = read_back(ctx, {});
     if (e != hipSuccess) { scaffolds_drop_plan(s.get()); return hip_fail(ctx, e, (std::string(who) + ": compaction").c_str()); }

@@ -79,7 +79,7 @@ __device__ __forceinline__ void spans_record(const Table<W> &pm, const GraphView
         pos[0][p] = thread_lookup(pm, g, x, bad);
         pos[1][n - 1 - p] = thread_lookup(pm, g, revcomp(x, k), bad);
     }
-    thread_wave_sync();
+    wave_sync();
     // phase 2: every inner window's crossing key, or none (the loops are wave-uniform, a lane may have no window)
     for (int s = 0; s < 2; s++)
         for (int i0 = 1; i0 < n - 1; i0 += 64) {
@@ -92,7 +92,7 @@ __device__ __forceinline__ void spans_record(const Table<W> &pm, const GraphView
             }
             st.cross += (u32)__popcll(__ballot(cross));
         }
-    thread_wave_sync();                                       // window j - len_m may lie in any earlier trip: all of them have written
+    wave_sync();                                       // window j - len_m may lie in any earlier trip: all of them have written
     // phase 3: the lane that owns a crossing at j looks back over the edge it arrived by
     for (int s = 0; s < 2; s++)
         for (int j0 = 1; j0 < n - 1; j0 += 64) {
@@ -115,7 +115,7 @@ __device__ __forceinline__ void spans_record(const Table<W> &pm, const GraphView
 #pragma unroll
             for (int c = 0; c < 3; c++) st.cls[c] += (u32)__popcll(__ballot(cls == c));
         }
-    thread_wave_sync();                                       // before the next record's positions land in `pos`
+    wave_sync();                                       // before the next record's positions land in `pos`
 }
 
 template <int W>

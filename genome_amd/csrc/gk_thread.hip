@@ -48,7 +48,7 @@ __device__ __forceinline__ void thread_record(const Table<W> &pm, const GraphVie
         pos[0][p] = thread_lookup(pm, g, x, bad);
         pos[1][n - 1 - p] = thread_lookup(pm, g, revcomp(x, k), bad);
     }
-    thread_wave_sync();
+    wave_sync();
     // phase 2: the class of every inner window of either strand (the loops are wave-uniform, a lane may have no window)
     for (int s = 0; s < 2; s++)
         for (int i0 = 1; i0 < n - 1; i0 += 64) {
@@ -70,7 +70,7 @@ __device__ __forceinline__ void thread_record(const Table<W> &pm, const GraphVie
                 }
             } else if (cls == TC_CROSSING) sup_add_checked(sup, key, 1u);
         }
-    thread_wave_sync();                                       // before the next record's positions land in `pos`
+    wave_sync();                                       // before the next record's positions land in `pos`
 }
 
 template <int W>

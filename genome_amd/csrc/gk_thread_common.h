@@ -1,7 +1,7 @@
 // gk_thread_common.h — what the two kernels that thread single reads through the graph share: k_thread_reads (gk_thread.hip: the
 // crossings of one node) and k_thread_spans (gk_spans.hip: the crossings at both ends of one edge).  The lookup of a window in
-// the position map with its untrusted-position check, a strand's bases, the window classes of gk_graph_thread_reads' rule
-// (include/genome_amd.h) and the wave-level sync between the phases.  Device code only.
+// the position map with its untrusted-position check, a strand's bases and the window classes of gk_graph_thread_reads' rule
+// (include/genome_amd.h).  Device code only.
 #pragma once
 
 #include "gk_graph.h"
@@ -15,11 +15,6 @@ constexpr int TH_MAXW = 256;                   // windows of a record: at most 2
 // what a window's lookup left, beside a position: no valid GraphPosition has these bit patterns (an edge id of 2^31 - 1)
 constexpr u64 PV_NONE = ~0ull, PV_MANY = ~0ull - 1;
 enum { TC_OFF = 0, TC_REPEATED = 1, TC_ON_EDGE = 2, TC_BROKEN = 3, TC_CROSSING = 4 };
-
-__device__ __forceinline__ void thread_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // the position Edge(e, d) as the position map holds it
 __device__ __forceinline__ u64 thread_edge_pos(u32 e, u64 d) { return (1ull << 63) | ((u64)e << 32) | d; }

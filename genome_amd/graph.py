@@ -240,19 +240,16 @@ class HipGraph:
         if not self.h or not self.ctx.h:
             raise L.GkError(L.GK_E_STATE, "the graph is closed")
         chains = [list(c) for c in chains]
-        assert len(gaps) == len(chains) and all(len(c) - 1 <= len(g) <= len(c) for c, g in zip(chains, gaps))
-        members = np.array([e for c in chains for e in c], np.uint32)
-        gap = np.array([x for c, g in zip(chains, gaps) for x in list(g)[:len(c) - 1] + [0]], np.int64) if len(members) else np.zeros(0, np.int64)
-        off = np.zeros(len(chains) + 1, np.uint64)
-        off[1:] = np.cumsum([len(c) for c in chains])
+        assert _junction_lists(chains, gaps)
+        (members, off), gap = _flat_chains(chains), _flat_junctions(chains, gaps, np.int64)
         h = L.vp()
         if overlaps is None:
             L.check(L.lib().gk_graph_scaffolds_plan(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64), int(min_gap),
                                                     int(min_len), int(line_width), int(strands), int(bool(singletons)), C.byref(h)), self.ctx.h)
             return Scaffolds(self, h)
-        if len(overlaps) != len(chains) or not all(len(c) - 1 <= len(o) <= len(c) for c, o in zip(chains, overlaps)):
+        if not _junction_lists(chains, overlaps):
             raise ValueError("scaffolds: one overlap list per chain, with an entry per junction")
-        ovl = np.array([x for c, o in zip(chains, overlaps) for x in list(o)[:len(c) - 1] + [0]], np.uint32) if len(members) else np.zeros(0, np.uint32)
+        ovl = _flat_junctions(chains, overlaps, np.uint32)
         L.check(L.lib().gk_graph_scaffolds_plan_overlaps(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64),
                                                          L.ptr(ovl, C.c_uint32), int(min_gap), int(min_len), int(line_width), int(strands), int(bool(singletons)),
                                                          C.byref(h)), self.ctx.h)
@@ -270,21 +267,17 @@ class HipGraph:
         if not self.h or not self.ctx.h:
             raise L.GkError(L.GK_E_STATE, "the graph is closed")
         chains = [list(c) for c in chains]
-        if len(gaps) != len(chains) or not all(len(c) - 1 <= len(g) <= len(c) for c, g in zip(chains, gaps)):
+        if not _junction_lists(chains, gaps):
             raise ValueError("overlapGaps: one gap list per chain, with an entry per junction")
-        members = np.array([e for c in chains for e in c], np.uint32)
-        gap = np.array([x for c, g in zip(chains, gaps) for x in list(g)[:len(c) - 1] + [0]], np.int64) if len(members) else np.zeros(0, np.int64)
-        off = np.zeros(len(chains) + 1, np.uint64)
-        off[1:] = np.cumsum([len(c) for c in chains])
+        (members, off), gap = _flat_chains(chains), _flat_junctions(chains, gaps, np.int64)
         nm = len(members)
         ovl, jclass, st = np.zeros(max(nm, 1), np.uint32), np.zeros(max(nm, 1), np.uint8), np.zeros(len(OVERLAP_STATS), np.uint64)
         L.check(L.lib().gk_graph_overlap_gaps(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64), int(tol),
                                               int(min_overlap), int(self.k if max_overlap is None else max_overlap), L.ptr(ovl, C.c_uint32),
                                               L.ptr(jclass, C.c_uint8), L.ptr(st, C.c_uint64)), self.ctx.h)
-        i = off.tolist()
         report = dict(zip(OVERLAP_STATS, (int(x) for x in st)))
-        report["classes"] = [[OVERLAP_CLASSES[x] for x in jclass[a:b - 1].tolist()] for a, b in zip(i, i[1:])]
-        return [ovl[a:b - 1].tolist() for a, b in zip(i, i[1:])], report
+        report["classes"] = [[OVERLAP_CLASSES[x] for x in c] for c in _per_junction(jclass, off)]
+        return _per_junction(ovl, off), report
 
     # ---- gap filling (this project's own rule: include/genome_amd.h) ---------------------------------------------------
     def fillGaps(self, chains, gaps, tol: int, max_edges: int = 16, max_paths: int = 256):
@@ -299,23 +292,20 @@ class HipGraph:
         if not self.h or not self.ctx.h:
             raise L.GkError(L.GK_E_STATE, "the graph is closed")
         chains = [list(c) for c in chains]
-        if len(gaps) != len(chains) or not all(len(c) - 1 <= len(g) <= len(c) for c, g in zip(chains, gaps)):
+        if not _junction_lists(chains, gaps):
             raise ValueError("fillGaps: one gap list per chain, with an entry per junction")
-        members = np.array([e for c in chains for e in c], np.uint32)
-        gap = np.array([x for c, g in zip(chains, gaps) for x in list(g)[:len(c) - 1] + [0]], np.int64) if len(members) else np.zeros(0, np.int64)
-        off = np.zeros(len(chains) + 1, np.uint64)
-        off[1:] = np.cumsum([len(c) for c in chains])
+        (members, off), gap = _flat_chains(chains), _flat_junctions(chains, gaps, np.int64)
         nm, cap = len(members), self.idBounds()[1]             # (no edge is written twice: the filled chains fit the edge ids)
         out_m, out_g, out_off = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.int64), np.zeros(len(chains) + 1, np.uint64)
         jclass, jlen, st, n = np.zeros(max(nm, 1), np.uint8), np.zeros(max(nm, 1), np.int64), np.zeros(len(FILL_STATS), np.uint64), C.c_uint64()
         L.check(L.lib().gk_graph_fill_gaps(self.h, L.ptr(members, C.c_uint32), L.ptr(off, C.c_uint64), len(chains), L.ptr(gap, C.c_int64), int(tol), int(max_edges),
                                            int(max_paths), L.ptr(out_m, C.c_uint32), L.ptr(out_g, C.c_int64), cap, L.ptr(out_off, C.c_uint64),
                                            L.ptr(jclass, C.c_uint8), L.ptr(jlen, C.c_int64), C.byref(n), L.ptr(st, C.c_uint64)), self.ctx.h)
-        o, i = out_off.tolist(), off.tolist()
+        o = out_off.tolist()
         report = dict(zip(FILL_STATS, (int(x) for x in st)))
-        report["classes"] = [[FILL_CLASSES[x] for x in jclass[a:b - 1].tolist()] for a, b in zip(i, i[1:])]
-        report["lengths"] = [jlen[a:b - 1].tolist() for a, b in zip(i, i[1:])]
-        return [out_m[a:b].tolist() for a, b in zip(o, o[1:])], [out_g[a:b - 1].tolist() for a, b in zip(o, o[1:])], report
+        report["classes"] = [[FILL_CLASSES[x] for x in c] for c in _per_junction(jclass, off)]
+        report["lengths"] = _per_junction(jlen, off)
+        return [out_m[a:b].tolist() for a, b in zip(o, o[1:])], _per_junction(out_g, out_off), report
 
     def walkPairs(self, positions, support: "Support", bin_bytes, npairs: int, range_lo: int = 180, range_hi: int = 250):
         """:213-247: the pairs' positions through `positions` (getGraphMap of this graph as it is now), annotate, the bounded
@@ -630,6 +620,29 @@ def scaffoldGaps(chains, joins, mid: int):
     e1, e2, cnt, su = (np.asarray(a).tolist() for a in joins)
     gap = {(a, b): int(mid) - s // c for a, b, c, s in zip(e1, e2, cnt, su)}
     return [[gap[(a, b)] for a, b in zip(c, c[1:])] for c in chains]
+
+
+def _junction_lists(chains, lists) -> bool:
+    """Is `lists` one list per chain with an entry per junction (one for the last member may be there and is ignored)?"""
+    return len(lists) == len(chains) and all(len(c) - 1 <= len(x) <= len(c) for c, x in zip(chains, lists))
+
+
+def _flat_chains(chains):
+    """Chains as the C API takes them -> (members, chain_off)."""
+    off = np.zeros(len(chains) + 1, np.uint64)
+    off[1:] = np.cumsum([len(c) for c in chains])
+    return np.array([e for c in chains for e in c], np.uint32), off
+
+
+def _flat_junctions(chains, lists, dtype):
+    """Per-junction lists -> their entries parallel to the members, with 0 behind a chain's last member."""
+    return np.array([x for c, g in zip(chains, lists) for x in list(g)[:len(c) - 1] + [0]], dtype)
+
+
+def _per_junction(flat, off):
+    """An array parallel to the members of the chains at `off` -> per chain the list of its junctions' entries."""
+    i = off.tolist()
+    return [flat[a:b - 1].tolist() for a, b in zip(i, i[1:])]
 
 
 # the classes of gk_graph_pair_distances, in the order of its `classes` array

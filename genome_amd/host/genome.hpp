@@ -993,7 +993,7 @@ class Graph {
         std::vector<uint32_t> members;
         std::vector<int64_t> gap;
         std::vector<uint64_t> off;
-        flatten("overlapGaps", chains, gaps, members, gap, off);
+        flatten("overlapGaps", "gap", chains, gaps, gap, &members, &off);
         std::vector<uint32_t> ovl(members.size() + 1);
         std::vector<uint8_t> jclass(members.size() + 1);
         Overlapped r;
@@ -1025,18 +1025,10 @@ class Graph {
     };
     Filled fillGaps(const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps, uint64_t tol, uint32_t maxEdges = 16,
                     uint32_t maxPaths = 256) const {
-        if (chains.size() != gaps.size()) throw GkError(GK_E_INVALID, "fillGaps: as many gap lists as chains");
         std::vector<uint32_t> members;
         std::vector<int64_t> gap;
-        std::vector<uint64_t> off(1, 0);
-        for (size_t c = 0; c < chains.size(); c++) {
-            if (gaps[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, "fillGaps: a chain with fewer gaps than junctions");
-            for (size_t j = 0; j < chains[c].size(); j++) {
-                members.push_back(chains[c][j]);
-                gap.push_back(j + 1 < chains[c].size() ? gaps[c][j] : 0);
-            }
-            off.push_back(members.size());
-        }
+        std::vector<uint64_t> off;
+        flatten("fillGaps", "gap", chains, gaps, gap, &members, &off);
         uint64_t nodeBound = 0, cap = 0, n = 0;
         check(gk_graph_id_bounds(h_, &nodeBound, &cap), ctx_.handle());      // (no edge is written twice: the filled chains fit the edge ids)
         std::vector<uint32_t> outMembers(cap + 1);
@@ -1071,18 +1063,18 @@ class Graph {
     }
 
   private:
-    // chains and their per-junction gaps as the C calls take them: members, a gap per member (0 at a chain's last), chain_off
-    static void flatten(const char *who, const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps,
-                        std::vector<uint32_t> &members, std::vector<int64_t> &gap, std::vector<uint64_t> &off) {
-        if (chains.size() != gaps.size()) throw GkError(GK_E_INVALID, std::string(who) + ": as many gap lists as chains");
-        off.assign(1, 0);
+    // per-junction lists of chains (`what`: "gap", "overlap") as the C calls take them: an entry per member (0 at a chain's last);
+    // with them, where asked for, the members and chain_off
+    template <class T>
+    static void flatten(const char *who, const std::string &what, const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<T>> &lists,
+                        std::vector<T> &flat, std::vector<uint32_t> *members = nullptr, std::vector<uint64_t> *off = nullptr) {
+        if (chains.size() != lists.size()) throw GkError(GK_E_INVALID, std::string(who) + ": as many " + what + " lists as chains");
+        if (off) off->assign(1, 0);
         for (size_t c = 0; c < chains.size(); c++) {
-            if (gaps[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, std::string(who) + ": a chain with fewer gaps than junctions");
-            for (size_t j = 0; j < chains[c].size(); j++) {
-                members.push_back(chains[c][j]);
-                gap.push_back(j + 1 < chains[c].size() ? gaps[c][j] : 0);
-            }
-            off.push_back(members.size());
+            if (lists[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, std::string(who) + ": a chain with fewer " + what + "s than junctions");
+            for (size_t j = 0; j < chains[c].size(); j++) flat.push_back(j + 1 < chains[c].size() ? lists[c][j] : 0);
+            if (members) members->insert(members->end(), chains[c].begin(), chains[c].end());
+            if (off) off->push_back(off->back() + chains[c].size());
         }
     }
     Scaffolds scaffoldsPlan(const std::vector<std::vector<uint32_t>> &chains, const std::vector<std::vector<int64_t>> &gaps,
@@ -1091,18 +1083,14 @@ class Graph {
         std::vector<uint32_t> members, ovl;
         std::vector<int64_t> gap;
         std::vector<uint64_t> off;
-        flatten("scaffolds", chains, gaps, members, gap, off);
+        flatten("scaffolds", "gap", chains, gaps, gap, &members, &off);
         gk_scaffolds *s = nullptr;
         if (!overlaps) {
             check(gk_graph_scaffolds_plan(h_, members.data(), off.data(), chains.size(), gap.data(), minGap, minLen, lineWidth, bothStrands ? 2 : 1, singletons ? 1 : 0,
                                           &s), ctx_.handle());
             return Scaffolds(ctx_.handle(), s);
         }
-        if (overlaps->size() != chains.size()) throw GkError(GK_E_INVALID, "scaffolds: as many overlap lists as chains");
-        for (size_t c = 0; c < chains.size(); c++) {
-            if ((*overlaps)[c].size() + 1 < chains[c].size()) throw GkError(GK_E_INVALID, "scaffolds: a chain with fewer overlaps than junctions");
-            for (size_t j = 0; j < chains[c].size(); j++) ovl.push_back(j + 1 < chains[c].size() ? (*overlaps)[c][j] : 0);
-        }
+        flatten("scaffolds", "overlap", chains, *overlaps, ovl);
         check(gk_graph_scaffolds_plan_overlaps(h_, members.data(), off.data(), chains.size(), gap.data(), ovl.data(), minGap, minLen, lineWidth, bothStrands ? 2 : 1,
                                                singletons ? 1 : 0, &s), ctx_.handle());
         return Scaffolds(ctx_.handle(), s);

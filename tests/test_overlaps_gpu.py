@@ -332,6 +332,37 @@ def test_errors_write_nothing_and_leave_the_graph_alone(ctx):
     g.close()
 
 
+def test_the_three_entries_hold_one_chain_list_contract(ctx):
+    """the plan, gap filling and overlap detection give the same malformed chain list the same error code and write nothing; the
+    one difference is a gap of -(2^31) at a junction that is not adjacent, which the plan clamps and the other two refuse"""
+    from test_fillgaps_gpu import pristine as fill_pristine, raw as raw_fill
+    g, edges, ids = built(ctx, 31, small_pairs(100 + 31, 31))
+    x, y = next((a, b) for a in sorted(edges) for b in sorted(edges) if a != b and ids[a][1] != ids[b][0])        # not adjacent
+    z, w = [a for a in sorted(edges) if a not in (x, y)][:2]
+    fp = g.idFingerprint()
+
+    def codes(members, off, gap):
+        rc_plan, s = raw_plan(g, members, off, gap, None)
+        rc_fill, out_fill = raw_fill(g, members, off, gap)
+        rc_ovl, out_ovl = raw_stage(g, members, off, gap)
+        if rc_plan == L.GK_OK:
+            L.lib().gk_scaffolds_destroy(s)
+        assert (s is None) == (rc_plan != L.GK_OK) and g.idFingerprint() == fp
+        assert rc_fill == L.GK_OK or fill_pristine(out_fill)
+        assert rc_ovl == L.GK_OK or all(set(out_ovl[name]) == {PATTERN[name]} for name in PATTERN)
+        return rc_plan, rc_fill, rc_ovl
+
+    assert codes([x, y, z, w], [0, 2, 4], [5, 0, 5, 0]) == (L.GK_OK,) * 3
+    for kw in (dict(members=[x, g.idBounds()[1]], off=[0, 2], gap=[0] * 2),                 # an id at the bound
+               dict(members=[x, y, z, x], off=[0, 2, 4], gap=[0] * 4),                      # a duplicate across two chains
+               dict(members=[x, y], off=[0, 2, 2], gap=[0] * 2),                            # an empty chain
+               dict(members=[x, y], off=[1, 2], gap=[0] * 2),                               # a chain_off that does not start at 0
+               dict(members=[x, y, z], off=[0, 3, 2], gap=[0] * 3)):                        # a chain_off that descends
+        assert codes(**kw) == (L.GK_E_INVALID,) * 3, kw
+    assert codes([x, y], [0, 2], [-I31 - 1, 0]) == (L.GK_OK, L.GK_E_INVALID, L.GK_E_INVALID)
+    g.close()
+
+
 # ---- 6. end to end ---------------------------------------------------------------------------------------------------------------
 
 def test_three_dips_end_to_end(ctx):
