@@ -219,6 +219,13 @@ SIGNATURES = {
     "gk_fasta_check_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p, u64p]),
     "gk_fasta_check_missing": (C.c_int, [vp, u64p, u64p, u64p, u64p, u64p, C.c_uint64, u64p]),
     "gk_fasta_check_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "gk_placements_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "gk_placements_destroy": (None, [vp]),
+    "gk_placements_add_record": (C.c_int, [vp, vp, C.c_uint64]),
+    "gk_placements_stats": (C.c_int, [vp, u64p]),
+    "gk_placements_edges": (C.c_int, [vp, u32p, C.c_uint64, u8p, u32p, i64p, u32p, u32p]),
+    "gk_placements_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "gk_scaffolds_judge": (C.c_int, [vp, vp, C.c_uint64, u8p, i64p, C.c_uint64, u64p, u64p]),
     "gk_graph_contig_stats": (C.c_int, [vp, C.c_uint64, u64p, u64p, u64p, u64p, u64p]),
     "gk_synth_reads_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
     "gk_prefilter_create": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp)]),

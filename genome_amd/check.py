@@ -79,6 +79,77 @@ class FastaCheck:
         return dict(zip(("upload", "parse", "lookup", "total"), (float(x) for x in out)))
 
 
+def fasta_records(text) -> list:
+    """The records of a FASTA text as joined sequence bytes, by the record rule of the FASTA check with per_line == 0
+    (include/genome_amd.h): a line ends at "\\n", "\\r" or "\\r\\n"; a line that starts with '>' is a header and starts a record;
+    sequence characters before the first header are record 0; terminators are dropped, every other character is kept as it is."""
+    text = bytes(text)
+    records, cur, seen_header = [], [], False
+    for line in text.replace(b"\r\n", b"\n").replace(b"\r", b"\n").split(b"\n"):
+        if line[:1] == b">":
+            if seen_header or cur:
+                records.append(b"".join(cur))
+            cur, seen_header = [], True
+        elif line:
+            cur.append(line)
+    if seen_header or cur:
+        records.append(b"".join(cur))
+    return records
+
+
+def n50(lengths) -> int:
+    """lengths descending, the first at which twice the running sum reaches the total (gk_graph_contig_stats' n50); 0 for none"""
+    c = sorted((int(x) for x in lengths), reverse=True)
+    total, run = sum(c), 0
+    for x in c:
+        run += x
+        if 2 * run >= total:
+            return x
+    return 0
+
+
+MISJOINS = ("other_record", "strand", "order", "distance")
+
+
+def scaffold_n50s(segments, classes) -> dict:
+    """From Scaffolds.segments() and the junction classes of Scaffolds.judge(): the N50 of the records as written, and the N50 after
+    every record is broken at each misjoin (the N run of a broken junction belongs to neither piece)."""
+    whole, broken, j = [], [], 0
+    for i, (rec, _e, first, bases, _s) in enumerate(segments):
+        if i == 0 or segments[i - 1][0] != rec:
+            start = piece = first
+        elif classes[j - 1] in MISJOINS:
+            broken.append(segments[i - 1][2] + segments[i - 1][3] - piece)
+            piece = first
+        if i + 1 == len(segments) or segments[i + 1][0] != rec:
+            whole.append(first + bases - start)
+            broken.append(first + bases - piece)
+        else:
+            j += 1
+    return {"n50": n50(whole), "n50_broken": n50(broken), "records": len(whole), "pieces": len(broken)}
+
+
+def judge_scaffolds(graph, fasta, scaffolds, tol: int) -> dict:
+    """The judge for a graph, a reference FASTA (a path, `.gz` read with the standard library, or its bytes) and a Scaffolds plan of
+    that graph: the edges are placed on the reference with a position map of the graph as it is, every junction of the plan is
+    judged -> {"k", "tol", "placements": the placement stats, "classes", "err", "stats": Scaffolds.judge's, "n50", "n50_broken"}.
+    `tol` is a choice, not a measurement."""
+    if isinstance(fasta, (str, os.PathLike)):
+        text = b"".join(bytes(piece) for piece, _ in iter_pieces(fasta, 256 << 20))
+    else:
+        text = bytes(fasta)
+    vm = graph.getGraphMap()
+    try:
+        with graph.place(vm, fasta_records(text)) as pl:
+            out = {"k": graph.k, "tol": int(tol), "placements": pl.stats()}
+            out.update(scaffolds.judge(pl, tol))
+    finally:
+        vm.close()
+    ns = scaffold_n50s(scaffolds.segments(), out["classes"])
+    out["n50"], out["n50_broken"] = ns["n50"], ns["n50_broken"]
+    return out
+
+
 def check_graph(graph, fasta, longer_than: int = 200, per_line: bool = False, max_missing: int = 0, piece_bytes: int = 256 << 20) -> dict:
     """CheckGraph.startup for a graph and a FASTA file (a path, `.gz` read with the standard library) or its bytes: one dict with
     k, the contig statistics (:37-41), the check's counters (:48-55), the coverage and, with max_missing, the missing list."""

@@ -177,6 +177,19 @@ struct EdgeCov { u64 *sum; u32 *mn, *mx, *miss; };
 int check_counts(const gk_graph *g, gk_map *counts, const char *who);
 __attribute__((visibility("hidden"))) int coverage_pass(gk_graph *g, gk_map *counts, DevScratch &tmp, const uint8_t *want, EdgeCov *cov);
 
+// The rows of a scaffold plan (gk_scaffolds.hip) as the judge reads them (gk_place.hip): the plan's own device arrays.  Segment i of
+// record r (rec_seg[r] <= i < rec_seg[r + 1]) is an N run (seg_edge == NONE) or a piece of P(seg_edge[i]) that starts at base
+// seg_start[i] of the record and leaves out the first seg_skip[i] bases of the path.  rows = the edge segments.
+struct ScafRows {
+    gk_ctx *ctx;
+    gk_graph *g;
+    u64 epoch, records, chain_recs, segs, rows;
+    const unsigned long long *rec_seg;
+    const u32 *seg_edge, *seg_start;
+    const uint8_t *seg_skip;
+};
+__attribute__((visibility("hidden"))) void scaffolds_rows(const gk_scaffolds *s, ScafRows *out);
+
 // The front end every paired-end entry point shares (gk_pairs.hip; GraphSimplifier.scala:213-217): the pairs whose mates both
 // hold k bases are cut from the `.bin` stream (a fixed-stride stream on the device by k_pair_keys, a ragged one on the host),
 // their four getAll run as ONE batch whose results stay in HBM as CSR, and k_check_positions is queued behind it.  Key 4p + q

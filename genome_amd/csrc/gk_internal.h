@@ -85,6 +85,7 @@ struct gk_ctx {
                                      // most this many workgroups (0: cu_count * 8), so that a small input makes every workgroup take several trips
     mutable uint64_t hook_max_grid_uses = 0;   // ... and how many launches were sized under it (gk_test_grid_cap_uses: the switch's echo)
     int64_t hook_contigs_chunk = 0;  // test hook: text bytes per device chunk of gk_contigs_read / gk_contigs_write (0: 64 MiB)
+    int64_t hook_place_slice = 0;    // test hook: characters per device slice of gk_placements_add_record (0: 64 Mi)
 };
 // most workgroups of a grid-stride launch: 8 resident 256-thread workgroups per CU, or what the test hook says
 inline uint64_t grid_cap(const gk_ctx *ctx) {

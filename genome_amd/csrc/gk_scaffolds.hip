@@ -426,6 +426,10 @@ void scaffolds_drop_plan(gk_scaffolds *s) {      // the plan's buffers are still
 
 extern "C" void gk_scaffolds_destroy(gk_scaffolds *s);
 
+void scaffolds_rows(const gk_scaffolds *s, ScafRows *out) {
+    *out = ScafRows{s->ctx, s->g, s->epoch, s->records, s->chain_recs, s->segs, s->stats[6] + s->stats[4], s->d_rec_seg, s->d_seg_edge, s->d_seg_start, s->d_seg_skip};
+}
+
 // gk_graph_scaffolds_plan is the `overlap` == nullptr case
 static int scaffolds_plan(const char *who, gk_graph *g, const uint32_t *members, const uint64_t *chain_off, uint64_t nchains, const int64_t *gap,
                           const uint32_t *overlap, int64_t min_gap, uint64_t min_len, uint32_t line_width, int strands, int singletons, gk_scaffolds **out) {

@@ -91,6 +91,7 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
         if (value < 0) return fail(ctx, GK_E_INVALID, "test_max_grid: 0 off, else the most workgroups of a grid-stride launch");
         ctx->hook_max_grid = (int)std::min<int64_t>(value, 1 << 30);
     }
+    else if (n == "test_place_slice") ctx->hook_place_slice = (int64_t)std::max<int64_t>(0, value);
     else if (n == "contigs_chunk_bytes") ctx->hook_contigs_chunk = (int64_t)std::max<int64_t>(0, value);
     else if (n == "fine_exact") ctx->hook_fine_exact = value < 0 ? -1 : value != 0;
     else return fail(ctx, GK_E_INVALID, "gk_ctx_set_option: unknown option '" + n + "'");

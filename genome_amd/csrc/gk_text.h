@@ -99,18 +99,22 @@ struct TextUpload {
         if (!ok) (void)hipGetLastError();
         return ok;
     }
+    // the two pinned staging buffers hold at least `bytes` each (a caller that knows its largest upload asks once, up front)
+    int reserve(gk_ctx *ctx, u64 bytes) {
+        if (h_stage_cap >= bytes) return GK_OK;
+        GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+        for (int i = 0; i < 2; i++) { if (h_stage[i]) (void)hipHostFree(h_stage[i]); h_stage[i] = nullptr; }
+        h_stage_cap = 0;
+        const u64 cap = pow2ceil(std::max<u64>(bytes, 4096));
+        for (int i = 0; i < 2; i++) GK_HIP(ctx, hipHostMalloc((void **)&h_stage[i], cap, 0));
+        h_stage_cap = cap;
+        return GK_OK;
+    }
     // text [src, src + bytes) -> d_dst; *host_ms grows by the time of the host's copy into the staging buffer
     int upload(gk_ctx *ctx, int b, void *d_dst, const char *src, u64 bytes, bool pinned, double *host_ms) {
         const void *from = src;
         if (!pinned) {
-            if (h_stage_cap < bytes) {
-                GK_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-                for (int i = 0; i < 2; i++) { if (h_stage[i]) (void)hipHostFree(h_stage[i]); h_stage[i] = nullptr; }
-                h_stage_cap = 0;
-                const u64 cap = pow2ceil(std::max<u64>(bytes, 4096));
-                for (int i = 0; i < 2; i++) GK_HIP(ctx, hipHostMalloc((void **)&h_stage[i], cap, 0));
-                h_stage_cap = cap;
-            }
+            if (int rc = reserve(ctx, bytes)) return rc;
             const auto t0 = clk::now();
             memcpy(h_stage[b], src, bytes);
             *host_ms += ms_since(t0);

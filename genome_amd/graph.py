@@ -255,6 +255,22 @@ class HipGraph:
                                                          C.byref(h)), self.ctx.h)
         return Scaffolds(self, h)
 
+    # ---- placements on a reference (this project's own rule: include/genome_amd.h) -------------------------------------
+    def place(self, positions, records) -> "Placements":
+        """Every edge placed on a reference genome: `records` is an iterable of str / bytes, one joined sequence per reference
+        record (genome_amd.check.fasta_records splits a FASTA text), `positions` getGraphMap of this graph as it is now.
+        -> a Placements: stats(), edges(), last_ms(); Scaffolds.judge takes it.  Any edit of the graph makes it stale."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        p = Placements(self, positions)
+        try:
+            for r in records:
+                p.add(r)
+        except Exception:
+            p.close()
+            raise
+        return p
+
     # ---- overlap detection (this project's own rule: include/genome_amd.h) ---------------------------------------------
     def overlapGaps(self, chains, gaps, tol: int, min_overlap: int = 10, max_overlap=None):
         """Between fillGaps (or scaffoldChains / scaffoldGaps) and scaffolds(): where the last o bases of a member's path equal the
@@ -611,6 +627,102 @@ class Scaffolds:
                                               L.ptr(skip, C.c_uint32), n, C.byref(got)), self.ctx.h)
         assert got.value == n
         return list(zip(rec.tolist(), edge.tolist(), first.tolist(), bases.tolist(), skip.tolist()))
+
+    def judge(self, placements: "Placements", tol: int) -> dict:
+        """Every junction of the plan (two consecutive rows of segments() in one record) held against the placements of its two
+        edges -> {"classes": the class name of every junction in row order (JUDGE_CLASSES), "err": scaffold distance minus
+        reference distance where the class is order, distance or correct, else 0, "stats": the numbers named as JUDGE_STATS}.
+        A gapped junction is correct within `tol` bases, an adjacent or overlapped one only at err = 0.  `tol` is a choice, not a
+        measurement (half the width of the insert range, the fill / overlap tolerance, is the customary value)."""
+        self._live()
+        st = self.stats()
+        cap = st["members"] + st["singletons"] - st["records"]
+        cls, err = np.zeros(max(cap, 1), np.uint8), np.zeros(max(cap, 1), np.int64)
+        n, js = C.c_uint64(), np.zeros(len(JUDGE_STATS), np.uint64)
+        L.check(L.lib().gk_scaffolds_judge(self.h, placements.h, int(tol), L.ptr(cls, C.c_uint8), L.ptr(err, C.c_int64), cap, C.byref(n), L.ptr(js, C.c_uint64)),
+                self.ctx.h)
+        assert n.value == cap
+        return {"classes": [JUDGE_CLASSES[x] for x in cls[:cap]], "err": err[:cap].tolist(), "stats": dict(zip(JUDGE_STATS, (int(x) for x in js)))}
+
+
+# the statistics of gk_placements_stats, in the order of its array: each strand's four lookup classes add up to windows, the five edge
+# classes to the live edges
+PLACE_STATS = ("records", "bases", "valid_bases", "windows", "fwd_absent", "fwd_repetitive", "fwd_at_node", "fwd_edge", "rev_absent", "rev_repetitive",
+               "rev_at_node", "rev_edge", "unplaced", "both_strands", "scattered", "forward", "reverse", "forward_bases", "reverse_bases", "saturated")
+# the names of the GK_PLACE_* edge classes, by code
+PLACE_CLASSES = ("unplaced", "both_strands", "scattered", "forward", "reverse")
+# the names of the GK_JUDGE_* junction classes, by code, and of the junction kinds
+JUDGE_CLASSES = ("unjudged", "other_record", "strand", "order", "distance", "correct")
+JUDGE_KINDS = ("adjacent", "gapped", "overlapped")
+# the statistics of gk_scaffolds_judge, in the order of its array: junctions is the sum of the six classes, each class the sum of its three kinds
+JUDGE_STATS = (("junctions",) + JUDGE_CLASSES + tuple(f"{kd}_{c}" for kd in JUDGE_KINDS for c in JUDGE_CLASSES)
+               + ("gapped_correct_abs_err_sum", "gapped_correct_abs_err_max", "records_judged", "records_clean"))
+
+
+class Placements:
+    """Where every edge of a graph lies on a reference genome (include/genome_amd.h, "placements"): per edge and strand the
+    windows of the reference that hit it, and the diagonal if there is exactly one.  Holds its graph and position map; stale
+    (GkError GK_E_STATE) once the graph has been edited."""
+
+    def __init__(self, graph: HipGraph, positions):
+        self.graph, self.ctx, self.positions = graph, graph.ctx, positions
+        h = L.vp()
+        L.check(L.lib().gk_placements_create(graph.h, positions.h, C.byref(h)), self.ctx.h)
+        self.h = h
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:               # (see HipDNAMap.close)
+                L.lib().gk_placements_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h or not self.ctx.h or not self.graph.h:
+            raise L.GkError(L.GK_E_STATE, "the placements or their graph are closed")
+
+    def add(self, record):
+        """the next reference record: its joined sequence characters (str or bytes)"""
+        self._live()
+        b = record.encode("latin-1") if isinstance(record, str) else bytes(record)
+        L.check(L.lib().gk_placements_add_record(self.h, b, len(b)), self.ctx.h)
+
+    def stats(self) -> dict:
+        self._live()
+        st = np.zeros(len(PLACE_STATS), np.uint64)
+        L.check(L.lib().gk_placements_stats(self.h, L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(PLACE_STATS, (int(x) for x in st)))
+
+    def edges(self, edge_ids=None) -> dict:
+        """per id asked for (default: every id below the bound): {"cls": class names (PLACE_CLASSES), "record", "pos": where base 0
+        of the edge's path lies (forward and reverse edges; 0 otherwise), "windows_fwd", "windows_rev": the hit counts}"""
+        self._live()
+        ids = np.arange(self.graph.idBounds()[1], dtype=np.uint32) if edge_ids is None else np.ascontiguousarray(edge_ids, np.uint32)
+        n = len(ids)
+        cls, rec, pos = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.int64)
+        wf, wr = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        L.check(L.lib().gk_placements_edges(self.h, L.ptr(ids, C.c_uint32), n, L.ptr(cls, C.c_uint8), L.ptr(rec, C.c_uint32), L.ptr(pos, C.c_int64),
+                                            L.ptr(wf, C.c_uint32), L.ptr(wr, C.c_uint32)), self.ctx.h)
+        return {"cls": [PLACE_CLASSES[x] for x in cls], "record": rec.tolist(), "pos": pos.tolist(), "windows_fwd": wf.tolist(), "windows_rev": wr.tolist()}
+
+    def last_ms(self) -> dict:
+        """wall ms of the last record added: host staging + upload, the lookup kernels (device events), the whole call"""
+        arr = (C.c_float * 4)()
+        L.check(L.lib().gk_placements_last_ms(self.h, arr), self.ctx.h)
+        return {"upload": float(arr[0]), "lookup_kernels": float(arr[2]), "total": float(arr[3])}
 
 
 def scaffoldGaps(chains, joins, mid: int):

@@ -654,6 +654,42 @@ class Contigs {
     gk_contigs *h_ = nullptr;
 };
 
+// gk_placements: where every edge of a graph lies on a reference genome (Graph::place; the rule: include/genome_amd.h,
+// "placements").  Holds neither the graph nor the position map: both must outlive it, and an edit of the graph makes it stale.
+class Placements {
+  public:
+    static constexpr const char *statNames[GK_PLACE_NSTATS] = {"records", "bases", "valid_bases", "windows", "fwd_absent", "fwd_repetitive", "fwd_at_node", "fwd_edge",
+                                                               "rev_absent", "rev_repetitive", "rev_at_node", "rev_edge", "unplaced", "both_strands", "scattered",
+                                                               "forward", "reverse", "forward_bases", "reverse_bases", "saturated"};
+    struct Stats { uint64_t v[GK_PLACE_NSTATS] = {}; };
+    struct Edges { std::vector<uint8_t> cls; std::vector<uint32_t> record; std::vector<int64_t> pos; std::vector<uint32_t> windowsFwd, windowsRev; };
+    Placements(gk_ctx *ctx, gk_graph *g, gk_vmap *positions) : ctx_(ctx) { check(gk_placements_create(g, positions, &h_), ctx_); }
+    ~Placements() { close(); }
+    void close() { gk_placements_destroy(h_); h_ = nullptr; }
+    Placements(Placements &&o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    Placements(const Placements &) = delete;
+    Placements &operator=(const Placements &) = delete;
+    gk_placements *handle() const { return h_; }
+    // the next reference record: its joined sequence characters
+    void add(const std::string &record) { check(gk_placements_add_record(h_, record.data(), record.size()), ctx_); }
+    Stats stats() const {
+        Stats st;
+        check(gk_placements_stats(h_, st.v), ctx_);
+        return st;
+    }
+    Edges edges(const std::vector<uint32_t> &ids) const {
+        Edges e;
+        const size_t n = ids.size();
+        e.cls.resize(n); e.record.resize(n); e.pos.resize(n); e.windowsFwd.resize(n); e.windowsRev.resize(n);
+        check(gk_placements_edges(h_, ids.data(), n, e.cls.data(), e.record.data(), e.pos.data(), e.windowsFwd.data(), e.windowsRev.data()), ctx_);
+        return e;
+    }
+
+  private:
+    gk_ctx *ctx_ = nullptr;
+    gk_placements *h_ = nullptr;
+};
+
 // gk_scaffolds: a plan of the FASTA text of a graph's scaffolds (Graph::scaffolds; the rule: include/genome_amd.h, "scaffolds").
 // As Contigs: the device emits the text when it is read or written, and an edit of the graph makes the plan stale.
 class Scaffolds {
@@ -707,6 +743,30 @@ class Scaffolds {
         std::vector<Segment> out(n);
         for (uint64_t i = 0; i < n; i++) out[i] = Segment{rec[i], edge[i], first[i], bases[i], skip[i]};
         return out;
+    }
+    // Every junction of the plan (two consecutive rows of segments() in one record) held against the placements of its two edges
+    // (include/genome_amd.h, "the judge"): the GK_JUDGE_* class and err per junction in row order, and the stats under these names.
+    // tol is a choice, not a measurement.
+    static constexpr const char *judgeStatNames[GK_JUDGE_NSTATS] = {
+        "junctions", "unjudged", "other_record", "strand", "order", "distance", "correct",
+        "adjacent_unjudged", "adjacent_other_record", "adjacent_strand", "adjacent_order", "adjacent_distance", "adjacent_correct",
+        "gapped_unjudged", "gapped_other_record", "gapped_strand", "gapped_order", "gapped_distance", "gapped_correct",
+        "overlapped_unjudged", "overlapped_other_record", "overlapped_strand", "overlapped_order", "overlapped_distance", "overlapped_correct",
+        "gapped_correct_abs_err_sum", "gapped_correct_abs_err_max", "records_judged", "records_clean"};
+    struct Judged {
+        std::vector<uint8_t> classes;
+        std::vector<int64_t> err;
+        uint64_t v[GK_JUDGE_NSTATS] = {};
+        static bool misjoin(uint8_t c) { return c >= GK_JUDGE_OTHER_RECORD && c <= GK_JUDGE_DISTANCE; }
+    };
+    Judged judge(const Placements &placements, uint64_t tol) const {
+        const Stats st = stats();
+        const uint64_t cap = st.v[6] + st.v[4] - st.v[5];          // rows - records
+        Judged j;
+        j.classes.resize(cap); j.err.resize(cap);
+        uint64_t n = 0;
+        check(gk_scaffolds_judge(h_, placements.handle(), tol, j.classes.data(), j.err.data(), cap, &n, j.v), ctx_);
+        return j;
     }
 
   private:
@@ -778,6 +838,13 @@ class Graph {
         uint64_t entries = 0;
         check(gk_graph_position_map(h_, pm.handle(), &entries), ctx_.handle());
         return pm;
+    }
+    // Every edge placed on a reference genome (include/genome_amd.h, "placements"): `records` = the joined sequence of every reference
+    // record, `positions` = getGraphMap of the graph as it is now.  Scaffolds::judge takes the result.
+    Placements place(PositionMap &positions, const std::vector<std::string> &records) const {
+        Placements p(ctx_.handle(), h_, positions.handle());
+        for (const std::string &r : records) p.add(r);
+        return p;
     }
     // GraphSimplifier.scala:213-247: the pairs' positions, annotate, the bounded walks -> support counts
     void walkPairs(PositionMap &positions, Support &support, const PairedEndData &data, uint64_t takeFirst, int rangeLo = 180, int rangeHi = 250) {

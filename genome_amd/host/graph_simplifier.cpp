@@ -6,7 +6,7 @@
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
 //                    [--take-first N] [--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]]
 //                    [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
-//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]]
+//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N]]]
 //                    [--world W --rank R --id-file PATH]
 //   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
 //   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
@@ -61,6 +61,13 @@
 //   within TOL of -gap, the FASTA writes those bases once and no N, and the id list shows -o as the gap.  TOL defaults as
 //   --fill-gaps' does; the defaults are choices, not measurements.  The JSON gains "overlap":{tol, min_overlap, max_overlap, the
 //   seven stats} beside "fill".
+//   --judge GENOME.fasta [--judge-tol N] (with --scaffold-fasta) judges the scaffolds that were written against a reference genome
+//   (include/genome_amd.h, "placements" and "the judge": this project's own rules): the edges of the final graph are placed on the
+//   reference's records (plain FASTA text) with a position map of that graph, and every junction of the plan is classed unjudged,
+//   other_record, strand, order, distance or correct.  N defaults to the fill / overlap TOL, half the width of the insert range: a
+//   choice, not a measurement.  stderr gets one line; the JSON gains "judge":{tol, "placements":{the twenty stats}, "stats":{the
+//   twenty-nine stats}, "classes", "err" per junction, n50, n50_broken: the scaffold N50 as written and after breaking every chain
+//   record at each misjoin}.
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
 //   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
 //   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
@@ -79,7 +86,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
                              "[--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
-                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]]] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N]]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -156,6 +163,7 @@ int main(int argc, char **argv) {
             if (!lr.fillJson.empty()) jsonPut(js, "fill", lr.fillJson);
             if (!lr.overlapJson.empty()) jsonPut(js, "overlap", lr.overlapJson);
             if (!lr.scaffoldsJson.empty()) jsonPut(js, "scaffolds", lr.scaffoldsJson);
+            if (!lr.judgeJson.empty()) jsonPut(js, "judge", lr.judgeJson);
         }
         if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");
         if (stage.resolve) jsonPut(js, "resolve_repeats", res.resolveJson(stage.spanCutoff()));

@@ -299,6 +299,10 @@ inline PairedResult pairedStage(genome::Graph &graph, genome::Context &ctx, geno
 // both are given (a graph path is the stronger evidence, and the junctions it leaves are the ones searched), go through
 // gk_graph_overlap_gaps (include/genome_amd.h, "overlap detection"); the FASTA joins an overlapped junction on its o bases, and
 // the id list shows -o as its gap.
+// --judge GENOME.fasta [--judge-tol N] (with --scaffold-fasta): the edges of the final graph are placed on the reference (plain FASTA
+// text) with the links' position map, and every junction of the plan that was written is judged (include/genome_amd.h,
+// "placements" and "the judge").  N defaults to the fill / overlap TOL, half the width of the insert range: a choice, not a
+// measurement.
 struct LinkOpts {
     std::string path, scaffolds, scaffoldFasta;
     uint32_t minSupport = 3;
@@ -312,12 +316,15 @@ struct LinkOpts {
     bool overlapGaps = false;
     int64_t overlapTol = -1;                      // -1: as fillTol
     uint32_t overlapMin = 10, overlapMax = 0;     // 0: k.  Choices, not measurements: a chance match of 10 bases is about 1e-6 per candidate
+    std::string judge;                            // --judge: the reference FASTA
+    int64_t judgeTol = -1;                        // -1: as fillTol; a choice, not a measurement
     bool parse(Args &a) {
         if (a.flag("--scaffold-both-strands")) { scaffoldBoth = true; return true; }
         if (a.optional("--fill-gaps", fillTol)) { fillGaps = true; return true; }
         if (a.value("--fill-max-edges", fillMaxEdges) || a.value("--fill-max-paths", fillMaxPaths)) return true;
         if (a.optional("--overlap-gaps", overlapTol)) { overlapGaps = true; return true; }
         if (a.value("--overlap-min", overlapMin) || a.value("--overlap-max", overlapMax)) return true;
+        if (a.value("--judge", judge) || a.value("--judge-tol", judgeTol)) return true;
         return a.value("--links", path) || a.value("--link-min-support", minSupport) || a.value("--link-min-len", minLen) || a.value("--scaffolds", scaffolds) ||
                a.value("--scaffold-fasta", scaffoldFasta) || a.value("--scaffold-min-gap", scaffoldMinGap) || a.value("--scaffold-width", scaffoldWidth);
     }
@@ -327,6 +334,9 @@ struct LinkOpts {
         if (path.empty() && !scaffoldFasta.empty()) { std::fprintf(stderr, "--scaffold-fasta PATH goes with --links PATH\n"); return false; }
         if (fillGaps && scaffolds.empty() && scaffoldFasta.empty()) { std::fprintf(stderr, "--fill-gaps goes with --scaffolds PATH or --scaffold-fasta PATH\n"); return false; }
         if (overlapGaps && scaffolds.empty() && scaffoldFasta.empty()) { std::fprintf(stderr, "--overlap-gaps goes with --scaffolds PATH or --scaffold-fasta PATH\n"); return false; }
+        if (!judge.empty() && scaffoldFasta.empty()) { std::fprintf(stderr, "--judge GENOME.fasta goes with --scaffold-fasta PATH\n"); return false; }
+        if (judge.empty() && judgeTol != -1) { std::fprintf(stderr, "--judge-tol N goes with --judge GENOME.fasta\n"); return false; }
+        if (judgeTol < -1) { std::fprintf(stderr, "--judge-tol N needs N >= 0\n"); return false; }
         if (wanted() && world) { std::fprintf(stderr, "--links runs on one GPU only (not with --world): export per rank and add the tables\n"); return false; }
         return true;
     }
@@ -338,11 +348,64 @@ struct LinkResult {
     std::string scaffoldsJson;                    // the stats of --scaffold-fasta's text; empty without the flag
     std::string fillJson;                         // --fill-gaps: tol, the two limits and the ten stats; empty without the flag
     std::string overlapJson;                      // --overlap-gaps: tol, the two bounds and the seven stats; empty without the flag
+    std::string judgeJson;                        // --judge: tol, both stats arrays by name, n50 and n50_broken; empty without the flag
     std::string json() const {
         return "{" + jsonNamed(genome::Graph::linkClassNames, classes.v, 8) + "," + jsonNamed(genome::Links::joinStatNames, joins.v, 5) + ",\"mid\":" +
                std::to_string(mid) + ",\"max_span\":" + std::to_string(maxSpan) + ",\"chains\":" + std::to_string(chains) + ",\"cycles\":" + std::to_string(cycles) + "}";
     }
 };
+// The records of a FASTA text as joined sequence characters, by the record rule of the FASTA check with per_line == 0
+// (include/genome_amd.h): a line ends at "\n", "\r" or "\r\n"; a line that starts with '>' is a header and starts a record; sequence
+// characters before the first header are record 0; terminators are dropped, every other character is kept as it is.
+inline std::vector<std::string> fastaRecords(const std::string &text) {
+    std::vector<std::string> records;
+    std::string cur;
+    bool seenHeader = false;
+    size_t i = 0;
+    const size_t n = text.size();
+    while (i < n) {
+        size_t e = i;
+        while (e < n && text[e] != '\n' && text[e] != '\r') e++;
+        if (e > i && text[i] == '>') {
+            if (seenHeader || !cur.empty()) records.push_back(cur);
+            cur.clear();
+            seenHeader = true;
+        } else cur.append(text, i, e - i);
+        i = e < n ? e + ((text[e] == '\r' && e + 1 < n && text[e + 1] == '\n') ? 2 : 1) : e;
+    }
+    if (seenHeader || !cur.empty()) records.push_back(cur);
+    return records;
+}
+// lengths descending, the first at which twice the running sum reaches the total (gk_graph_contig_stats' n50); 0 for none
+inline uint64_t n50Of(std::vector<uint64_t> lengths) {
+    std::sort(lengths.rbegin(), lengths.rend());
+    uint64_t total = 0, run = 0;
+    for (const uint64_t x : lengths) total += x;
+    for (const uint64_t x : lengths) {
+        run += x;
+        if (2 * run >= total) return x;
+    }
+    return 0;
+}
+// From the segment rows and the junction classes: the N50 of the records as written, and the N50 after every record is broken at
+// each misjoin (the N run of a broken junction belongs to neither piece).
+inline std::pair<uint64_t, uint64_t> scaffoldN50s(const std::vector<genome::Scaffolds::Segment> &rows, const std::vector<uint8_t> &classes) {
+    std::vector<uint64_t> whole, broken;
+    uint64_t start = 0, piece = 0;
+    size_t j = 0;
+    for (size_t i = 0; i < rows.size(); i++) {
+        if (i == 0 || rows[i - 1].record != rows[i].record) start = piece = rows[i].first;
+        else if (genome::Scaffolds::Judged::misjoin(classes[j - 1])) {
+            broken.push_back(rows[i - 1].first + rows[i - 1].bases - piece);
+            piece = rows[i].first;
+        }
+        if (i + 1 == rows.size() || rows[i + 1].record != rows[i].record) {
+            whole.push_back(rows[i].first + rows[i].bases - start);
+            broken.push_back(rows[i].first + rows[i].bases - piece);
+        } else j++;
+    }
+    return {n50Of(whole), n50Of(broken)};
+}
 // gap of a link = mid - floor(sum_u / count), signed
 inline long long linkGap(uint64_t mid, uint32_t count, uint64_t sumU) { return (long long)mid - (long long)(sumU / (count ? count : 1)); }
 // `walked`: what the paired-end stage measured (null: no such stage ran, the range is o's as given).  max_span = range_hi + k;
@@ -429,6 +492,22 @@ inline LinkResult linksStage(genome::Graph &graph, genome::Context &ctx, const g
                                  : graph.scaffolds(members, gaps, lo.scaffoldMinGap, lo.minLen, lo.scaffoldWidth, lo.scaffoldBoth, true);
         sc.write(lo.scaffoldFasta);
         r.scaffoldsJson = sc.stats().json();
+        if (!lo.judge.empty()) {                                                                     // the plan that was written, on the final graph
+            const uint64_t tol = lo.judgeTol >= 0 ? (uint64_t)lo.judgeTol : (rhi - rlo) / 2;
+            const std::vector<uint8_t> text = readBin(lo.judge);
+            const auto placements = graph.place(positions, fastaRecords(std::string(text.begin(), text.end())));
+            const auto pst = placements.stats();
+            const auto jd = sc.judge(placements, tol);
+            const auto n50 = scaffoldN50s(sc.segments(), jd.classes);
+            std::fprintf(stderr, "judge: tol %llu (%s), %llu junctions: %llu correct, %llu unjudged, %llu misjoins (other_record %llu, strand %llu, order %llu, distance %llu); "
+                                 "N50 %llu, %llu broken at the misjoins\n", (unsigned long long)tol, lo.judgeTol >= 0 ? "given" : "half the width of the insert range",
+                         (unsigned long long)jd.v[0], (unsigned long long)jd.v[6], (unsigned long long)jd.v[1], (unsigned long long)(jd.v[2] + jd.v[3] + jd.v[4] + jd.v[5]),
+                         (unsigned long long)jd.v[2], (unsigned long long)jd.v[3], (unsigned long long)jd.v[4], (unsigned long long)jd.v[5], (unsigned long long)n50.first,
+                         (unsigned long long)n50.second);
+            r.judgeJson = jsonObject("tol", tol, "placements", "{" + jsonNamed(genome::Placements::statNames, pst.v, GK_PLACE_NSTATS) + "}", "stats",
+                                     "{" + jsonNamed(genome::Scaffolds::judgeStatNames, jd.v, GK_JUDGE_NSTATS) + "}", "classes", jsonList(std::vector<uint32_t>(jd.classes.begin(), jd.classes.end())),
+                                     "err", jsonList(jd.err), "n50", n50.first, "n50_broken", n50.second);
+        }
     }
     return r;
 }

@@ -1236,6 +1236,104 @@ int gk_fasta_check_missing(const gk_fasta_check *fc, uint64_t *text_offset, uint
 /* wall ms of the last feed: {host staging + upload, parse kernels, lookup kernels, whole call} */
 int gk_fasta_check_last_ms(const gk_fasta_check *fc, float *ms4);
 
+/* ---- placements: this project's own rule (the reference's CheckGraph asks whether a window of the genome is in the graph, never
+ * where an edge lies) ----
+ * Every edge of a graph placed on a reference genome: for each edge and strand, how many windows of the reference hit it and on
+ * which diagonal.  Integers only.
+ * Input.  One reference record per gk_placements_add_record call, as its joined sequence characters: the caller splits the FASTA
+ * text by the record rule of the "FASTA check" section with per_line == 0 (headers start records, sequence lines before the first
+ * header are record 0, terminators are dropped).  Records are numbered 0, 1, ... in call order.  A character is valid iff it is an
+ * UPPERCASE A, G, C or T; a window is k consecutive valid characters of one record, k = gk_vmap_k of the position map.  Long
+ * records are cut into device slices; a slice brings the k-1 characters before it along, so nothing is carried between slices, and
+ * the next slice's upload runs on the context's copy stream beside the current slice's kernel.
+ * Lookups.  P(e) = start k-mer ++ seq is the path of edge e, as in the contig rule.  For the window W at record coordinate x
+ * (0-based, of its first character) BOTH W and revComplement(W) are looked up as they read, with getAll and the position decoding
+ * of gk_graph_pair_links.  Each of the two lookups falls into exactly one class, tested in this order:
+ *   absent      the list is empty;
+ *   repetitive  the list has two or more entries: they are not looked at;
+ *   at_node     the single position is a NODE position;
+ *   edge        the single position is Edge(e, d), 1 <= d <= len_e - 1.
+ * Candidates.  An `edge` hit of W at Edge(e, d) gives the FORWARD candidate (r, x - d) for e: the record coordinate of base 0 of
+ * P(e), with P(e) reading toward higher coordinates.  An `edge` hit of revComplement(W) at Edge(e', d') gives the REVERSE candidate
+ * (r, x + d' + k - 1) for e': the record coordinate of base 0 of P(e'), with P(e') reading toward lower coordinates (the window's
+ * last character, at x + k - 1, is the complement of base d' of P(e'), and base 0 lies d' characters further up).
+ * Both are constant along a diagonal: if the reference spells P(e) forward from coordinate c, the window at x = c + d is the k-mer
+ * at distance d, so x - d = c for every d; if it spells the reverse complement of P(e) ending at coordinate c, the window at x is
+ * the reverse complement of the k-mer at distance d = c - (x + k - 1), so x + d + k - 1 = c for every d.
+ * Per edge and strand the table holds a u32 hit count and the minimum and maximum of the candidate packed as
+ * record << 40 | (coordinate + 2^39).  More than 2^24 records, or a record of 2^39 bases or more, is GK_E_CAPACITY.  A count that
+ * would pass 2^32-1 saturates at 2^32-1 (no test reaches this: it takes 2^32 hits of one edge).
+ * Edge classes: the first that holds (gk_placements_edges' cls):
+ *   0 unplaced      no hit on either strand (a live edge with len == 1 has no interior k-mer and is always unplaced);
+ *   1 both_strands  hits on both strands;
+ *   2 scattered     min != max on the hit strand: a repeat, or an edge that differs from the reference by an indel;
+ *   3 forward, 4 reverse   exactly one diagonal; `record` and `pos` (the candidate's coordinate, which may be negative or lie past
+ *                   the record's end when the reference covers only part of P(e)) are set, and are 0 in every other class.
+ * windows_fwd / windows_rev are the two hit counts.  A dead edge id gives unplaced and zeros.  An id at or above the bound the
+ * graph had at create is GK_E_INVALID with nothing written.  Any output array may be NULL.
+ * Stats: uint64[GK_PLACE_NSTATS] = {records, bases, valid_bases, windows, fwd absent, fwd repetitive, fwd at_node, fwd edge, rev
+ * absent, rev repetitive, rev at_node, rev edge, edges unplaced, both_strands, scattered, forward, reverse, path bases (k + len)
+ * of the forward edges, of the reverse edges, edges with a saturated count}.  Identities: [4] + [5] + [6] + [7] = [3] and
+ * [8] + [9] + [10] + [11] = [3]; [12] + .. + [16] = the live edges; [2] <= [1]; [19] counts live edges only.
+ * Errors.  gk_placements_create: GK_E_KLEN for a position map of another k, GK_E_INVALID for NULL handles or a map of another
+ * context.  gk_placements_add_record: GK_E_STATE for a stale position map (a position that names nothing live in this graph:
+ * tested, bound first, before any per-edge array is indexed by it); after a failed add_record the handle refuses further records
+ * with GK_E_STATE.  Every call but destroy and last_ms returns GK_E_STATE once the graph has been edited since create.  Device
+ * memory comes from the context's block pool; a call's slice buffers go back when it returns.  The graph and the position map must
+ * outlive the handle; neither is changed.
+ * On the device: a lane owns 16 consecutive window starts of the slice, staged in LDS with a k-1 halo, and rolls W and its
+ * reverse complement together; hits of one edge are folded to (count, min, max) inside the lane's run and again over the wave, and
+ * one 32-bit add plus a 64-bit min and a 64-bit max go to HBM per folded run.
+ * Not there: a collective over ranks, circular references, alignment inside a scattered edge. */
+#define GK_PLACE_NSTATS 20
+enum { GK_PLACE_UNPLACED = 0, GK_PLACE_BOTH_STRANDS = 1, GK_PLACE_SCATTERED = 2, GK_PLACE_FORWARD = 3, GK_PLACE_REVERSE = 4 };
+typedef struct gk_placements gk_placements;
+int gk_placements_create(gk_graph *g, gk_vmap *positions, gk_placements **out);
+void gk_placements_destroy(gk_placements *p);
+int gk_placements_add_record(gk_placements *p, const char *bases, uint64_t n);
+int gk_placements_stats(const gk_placements *p, uint64_t *stats);
+int gk_placements_edges(const gk_placements *p, const uint32_t *edge_ids, uint64_t n, uint8_t *cls, uint32_t *record, int64_t *pos,
+                        uint32_t *windows_fwd, uint32_t *windows_rev);
+/* wall ms of the last add_record: {host staging + upload, 0, lookup kernels, whole call} */
+int gk_placements_last_ms(const gk_placements *p, float *ms4);
+
+/* ---- the judge: every junction of a scaffold plan against the placements.  This project's own rule. ----
+ * A written piece of a plan is always bases skipped .. of P(edge) read FORWARD, whichever strand the chain was selected on
+ * (`strands` only selects which chains are written, gk_scaffolds.hip), so one rule serves strands = 1 and 2.
+ * A junction is two consecutive rows of gk_scaffolds_segments with the same `record`; the outputs are parallel to those rows in
+ * row order: *n = rows - records.  Its KIND is what the plan recorded: gapped (1) iff an N run lies between the two rows; else
+ * adjacent (0) iff the first row's edge ends at the node ID the second row's edge starts at; else overlapped (2).  That IS the plan's
+ * own class of the junction, read back from what it wrote: the plan tests `adjacent` first and by the same node IDs, min_gap >= 1
+ * makes every gapped junction write an N run, and an overlapped one writes none (skipped alone cannot tell an overlap of exactly k
+ * bases from an adjacent junction, so the node IDs decide it, as in the plan).
+ * Distances.  Rows (e, first_e, skipped_e) and (f, first_f, skipped_f): dscaf = first_f - first_e; with both edges forward
+ * dref = (pos_f + skipped_f) - (pos_e + skipped_e); with both reverse dref = (pos_e - skipped_e) - (pos_f - skipped_f);
+ * err = dscaf - dref.
+ * Classes, tested in this order:
+ *   0 unjudged      either edge is not placed forward or reverse;
+ *   1 other_record  the two edges are placed on different reference records;
+ *   2 strand        one edge is forward and the other reverse;
+ *   3 order         dref <= 0;
+ *   4 distance      |err| > tol at a gapped junction, err != 0 at an adjacent or overlapped one (those write no N and must fit);
+ *   5 correct       none of the above.
+ * err[j] is written for order, distance and correct, and is 0 otherwise.  A MISJOIN is a junction of class 1 .. 4.
+ * Stats: uint64[GK_JUDGE_NSTATS] = {junctions, the six classes [1 + c], the six classes of the adjacent junctions [7 + c], of the
+ * gapped [13 + c], of the overlapped [19 + c], [25] the sum and [26] the maximum of |err| over the correct gapped junctions, [27]
+ * chain records with at least one junction that is not unjudged, [28] chain records with no misjoin}.  Identities: [1] + .. + [6]
+ * = [0]; [1 + c] = [7 + c] + [13 + c] + [19 + c]; [27], [28] <= the plan's chain records; a chain record without junctions has no
+ * misjoin.
+ * Known limit: a join across the two ends of a circular chromosome is classed `order`; there is no circular mode.
+ * tol has no measured value: the tools' --judge-tol defaults to their fill / overlap TOL, half the width of the insert range, as a
+ * choice.
+ * Errors: GK_E_INVALID for NULL handles, or a plan and placements of different graphs or contexts; GK_E_STATE if the graph was
+ * edited; cap below *n is GK_E_CAPACITY with *n and the stats set and nothing copied.
+ * On the device: one lane per segment of the plan, the junction's index from a scan over the edge segments; the stats by ballot
+ * and one atomic per wave. */
+#define GK_JUDGE_NSTATS 29
+enum { GK_JUDGE_UNJUDGED = 0, GK_JUDGE_OTHER_RECORD = 1, GK_JUDGE_STRAND = 2, GK_JUDGE_ORDER = 3, GK_JUDGE_DISTANCE = 4, GK_JUDGE_CORRECT = 5 };
+int gk_scaffolds_judge(const gk_scaffolds *s, const gk_placements *p, uint64_t tol, uint8_t *cls, int64_t *err, uint64_t cap, uint64_t *n,
+                       uint64_t *stats);
+
 /* ---- synthetic reads (bench / tests) ---------------------------------------- */
 /* Fill dev_records with nreads fixed-length `.bin` records generated on device, bit-identical to
  * genome_amd/synth.py.  mode 0 = U (uniform bases); mode 1 = G (genome of G bases, error rate

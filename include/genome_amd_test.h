@@ -46,7 +46,9 @@ extern "C" {
  * gk_contigs_read / gk_contigs_write) are capped by it too.
  * "contigs_chunk_bytes" (0: the default, 64 MiB; else rounded down to a multiple of 8, at least 8): the bytes of FASTA text
  * gk_contigs_read / gk_contigs_write emit per device chunk, so that a text of a few KiB goes through many chunks and both
- * staging buffers. */
+ * staging buffers.
+ * "test_place_slice" (0: the default, 64 Mi characters): the characters of a reference record gk_placements_add_record puts
+ * through the device per slice, so that a record of a few kbp is cut inside a contig and both upload buffers are used. */
 int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value);
 
 /* The echo of "test_max_grid": *uses = the launches on this context whose grid was bounded by the switch's value instead of by
