@@ -118,6 +118,8 @@ SIGNATURES = {
     "gk_dist_gather_classified_map": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "gk_dist_classify_queries": (C.c_int, [vp, u64p]),
     "gk_dist_reduce_support": (C.c_int, [vp, vp, vp]),
+    "gk_dist_reduce_links": (C.c_int, [vp, vp, vp]),
+    "gk_dist_reduce_spans": (C.c_int, [vp, vp, vp]),
     "gk_vmap_create": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp)]),
     "gk_vmap_destroy": (None, [vp]),
     "gk_vmap_k": (C.c_int, [vp]),
@@ -247,6 +249,7 @@ TEST_SIGNATURES = {
     "gk_test_part_plan": (C.c_int, [vp, vp]),          # (gk_test_part_in *, gk_test_part_out *: tests/test_part_plan_cpu.py)
     "gk_test_scan_counts": (C.c_int, [vp, u32p, C.c_uint64, C.c_int, u64p, u64p]),
     "gk_test_slot_ranks": (C.c_int, [vp, u64p, u64p, C.c_uint64, u64p, u64p]),
+    "gk_test_edge_path_keys": (C.c_int, [vp, u64p, u64p, u32p, u8p, u64p, u64p]),
 }
 TEST_LIB_PATH = os.path.join(_HERE, "libgenome_amd_test.so")
 

@@ -35,6 +35,7 @@
 #include "gk_binstream.h"
 #include "gk_dist.h"
 #include "gk_graph.h"
+#include "gk_links.h"
 #include "gk_support.h"
 #include "gk_tile.h"
 
@@ -1233,3 +1234,204 @@ extern "C" int gk_dist_reduce_support(gk_dist *d, gk_graph *g, gk_support *sup) 
 #undef XPR
 #undef HIPR
 }
+
+// ---- link and span tables over the ranks (gk_dist_reduce_links, gk_dist_reduce_spans) --------------------------------------------
+// gk_dist_reduce_support's seven steps, written once for a table type T whose records travel as the three planes of gk_links.h
+// (key u64, count u32, extra u64: 20 bytes a record).  Two things differ from the support's reduce.  These tables are taken on the
+// FINAL graph, whose node splits and edge copies share k-mers, so the canonical numbering is the one by path content
+// (graph_edge_pathkeys) and a record that names a dead edge, or one of two edges with the same path, is GK_E_STATE on its rank
+// (hence everywhere).  And a record's owner is a hash of its key plane alone: the at most four out-edges behind a span's (e, m)
+// meet at one owner, whose insert is the table's own.  world == 1: the checks of steps 1 and 2 and nothing else.
+namespace {
+template <class T> struct RecHandle {       // a temporary table on the handle's context
+    T *t = nullptr;
+    ~RecHandle() { if (t) rec_free(t); }
+};
+
+// The one-word agreements of a collective, over the handle's own device words (d->d_cnt: they exist whatever fails in the
+// caller): out[p] -> rank p and in[p] <- rank p; one word of every rank in rank order; "some rank cannot go on".  (Compiled once:
+// the exchange below is a template, these are not.  gk_dist_reduce_support keeps its own copies as lambdas.)
+struct RankWords {
+    gk_dist *d;
+    const char *who;
+#define HIPR(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_fail(ctx, e__, #call); } while (0)
+#define XPR(call) do { const int g__ = (call); if (g__ != XP_SUCCESS) return fail(ctx, GK_E_COMM, who + comm_error_text(g__)); } while (0)
+    int all_to_all(const unsigned long long *out, unsigned long long *in) const {
+        gk_ctx *ctx = d->ctx;
+        unsigned long long *d_w = d->d_cnt;
+        const int P = d->world;
+        HIPR(hipMemcpyAsync(d_w + 4 * 64, out, P * 8, hipMemcpyHostToDevice, ctx->stream));
+        int grc = xGroupStart(d);
+        for (int p = 0; p < P && grc == XP_SUCCESS; p++) {
+            grc = xSend(d, d_w + 4 * 64 + p, 1, XP_UINT64, p, ctx->stream);
+            if (grc == XP_SUCCESS) grc = xRecv(d, d_w + 5 * 64 + p, 1, XP_UINT64, p, ctx->stream);
+        }
+        { const int gend = xGroupEnd(d); if (grc == XP_SUCCESS) grc = gend; }
+        XPR(grc);
+        HIPR(hipMemcpyAsync(in, d_w + 5 * 64, P * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPR(hipStreamSynchronize(ctx->stream));
+        return GK_OK;
+    }
+    int all_gather(unsigned long long mine, unsigned long long *all) const {
+        gk_ctx *ctx = d->ctx;
+        unsigned long long *d_w = d->d_cnt;
+        HIPR(hipMemcpyAsync(d_w + 2 * 64, &mine, 8, hipMemcpyHostToDevice, ctx->stream));
+        XPR(xAllGather(d, d_w + 2 * 64, d_w, 1, XP_UINT64, ctx->stream));
+        HIPR(hipMemcpyAsync(all, d_w, d->world * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPR(hipStreamSynchronize(ctx->stream));
+        return GK_OK;
+    }
+    int any(bool mine, bool *any_of) const {
+        gk_ctx *ctx = d->ctx;
+        unsigned long long *d_w = d->d_cnt, w = mine ? 1ull : 0ull;
+        HIPR(hipMemcpyAsync(d_w + 2 * 64, &w, 8, hipMemcpyHostToDevice, ctx->stream));
+        XPR(xAllReduce(d, d_w + 2 * 64, d_w + 2 * 64 + 1, 1, XP_UINT64, XP_MAX, ctx->stream));
+        HIPR(hipMemcpyAsync(&w, d_w + 2 * 64 + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPR(hipStreamSynchronize(ctx->stream));
+        *any_of = w != 0;
+        return GK_OK;
+    }
+#undef XPR
+#undef HIPR
+};
+
+template <class T> int dist_reduce_records(gk_dist *d, gk_graph *g, T *tab, const char *who, const char *what) {
+    if (int rc = dist_check(d)) return rc;
+    gk_ctx *ctx = d->ctx;
+    if (int rc = dist_quiesce(d)) return rc;
+    const int P = d->world, me = d->rank;
+    int my_rc = GK_OK;
+    std::string my_err;
+    auto local = [&](int rc) { if (rc != GK_OK && my_rc == GK_OK) { my_rc = rc; my_err = ctx->err; } };
+    auto comm_fail = [&](int grc) { return fail(ctx, GK_E_COMM, who + comm_error_text(grc)); };
+    auto give_up = [&](const std::string &why) { return my_rc ? fail(ctx, my_rc, my_err) : fail(ctx, GK_E_COMM, who + why); };
+    RankWords rw{d, who};
+    auto words_all_to_all = [&](const unsigned long long *out, unsigned long long *in) { return rw.all_to_all(out, in); };
+    auto word_all_gather = [&](unsigned long long mine, unsigned long long *all) { return rw.all_gather(mine, all); };
+    auto any_rank = [&](bool mine, bool *any) { return rw.any(mine, any); };
+    // the three planes of n records, and one region of them to or from a peer
+    DevScratch buf(ctx);
+    auto planes = [&](RecPlanes *p, u64 n) { return buf.get(&p->key, n) == hipSuccess && buf.get(&p->cnt, n) == hipSuccess && buf.get(&p->x, n) == hipSuccess; };
+    auto send_planes = [&](const RecPlanes &p, u64 at, u64 n, int peer) {
+        int grc = xSend(d, p.key + at, (size_t)n, XP_UINT64, peer, ctx->stream);
+        if (grc == XP_SUCCESS) grc = xSend(d, p.cnt + at, (size_t)n * 4, XP_UINT8, peer, ctx->stream);
+        if (grc == XP_SUCCESS) grc = xSend(d, p.x + at, (size_t)n, XP_UINT64, peer, ctx->stream);
+        return grc;
+    };
+    auto recv_planes = [&](const RecPlanes &p, u64 at, u64 n, int peer) {
+        int grc = xRecv(d, p.key + at, (size_t)n, XP_UINT64, peer, ctx->stream);
+        if (grc == XP_SUCCESS) grc = xRecv(d, p.cnt + at, (size_t)n * 4, XP_UINT8, peer, ctx->stream);
+        if (grc == XP_SUCCESS) grc = xRecv(d, p.x + at, (size_t)n, XP_UINT64, peer, ctx->stream);
+        return grc;
+    };
+    // ---- 1. status and the replicas' content
+    u64 fp = 0, nlive = 0, mine = 0;
+    u32 *d_canon = nullptr, *d_inv = nullptr;
+    uint8_t *d_dup = nullptr;
+    if (!g || !tab) local(fail(ctx, GK_E_INVALID, std::string(who) + "null graph or table"));
+    else if (check_graph(g) != GK_OK) local(GK_E_INVALID);
+    else if (g->ctx != ctx || rec_ctx(tab) != ctx) local(fail(ctx, GK_E_INVALID, std::string(who) + "the graph and the table must live on the handle's context"));
+    if (!my_rc) local(graph_edge_pathkeys(g, buf, &d_canon, &d_inv, &d_dup, &nlive, &fp));
+    if (!my_rc) local(rec_distinct(tab, &mine));
+    std::vector<unsigned long long> st(P), fps(P);
+    if (int rc = word_all_gather(my_rc ? ~0ull : mine, st.data())) return rc;
+    if (int rc = word_all_gather(fp, fps.data())) return rc;
+    for (int p = 0; p < P; p++)
+        if (st[p] == ~0ull) return give_up("rank " + std::to_string(p) + " could not take part; every rank gave up, nothing was changed");
+    for (int p = 0; p < P; p++)
+        if (fps[p] != fps[me])
+            return fail(ctx, GK_E_STATE, std::string(who) + "the graph replicas differ (path fingerprint of rank " + std::to_string(p) + ": " + std::to_string(fps[p]) +
+                                             ", of this rank: " + std::to_string(fps[me]) + "): they do not hold the same edge paths, nothing was added up");
+    // ---- 2. this rank's records by owner, in the canonical numbering; region sizes to every owner
+    RecHandle<T> shard, fresh;
+    RecPlanes snd, rcv, all;                                      // by owner (send) | arrivals, then this rank's shard | every shard
+    std::vector<u64> region(P + 1, 0);
+    if (!planes(&snd, mine)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(mine) + " records"));
+    if (!my_rc) local(rec_bucket(tab, P, snd, mine, region.data(), d_canon, d_dup, g->v.n_edges));
+    if (P == 1) return my_rc ? fail(ctx, my_rc, my_err) : GK_OK;
+    std::vector<unsigned long long> out(P), in(P);
+    for (int p = 0; p < P; p++) out[p] = my_rc ? ~0ull : region[p + 1] - region[p];
+    if (int rc = words_all_to_all(out.data(), in.data())) return rc;
+    u64 nin = 0;
+    std::vector<u64> roff(P + 1, 0);
+    for (int p = 0; p < P; p++) {
+        if (in[p] == ~0ull) return give_up("rank " + std::to_string(p) + " could not bucket " + what + "; every rank gave up, nothing was changed");
+        roff[p] = nin;
+        nin += in[p];
+    }
+    if (my_rc) return give_up("");                                // (unreachable: this rank sent ~0 to itself)
+    // ---- 3. room for the arrivals and the shard table
+    if (!planes(&rcv, nin)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(nin) + " arriving records"));
+    if (!my_rc) local(rec_new(ctx, nin, (u64)nlive, &shard.t));
+    {
+        bool any = false;
+        if (int rc = any_rank(my_rc != GK_OK, &any)) return rc;
+        if (any) return give_up(std::string("a rank had no room for ") + what + " it owns; every rank gave up, nothing was changed");
+    }
+    // ---- 4. the records to their owners, the owner merge
+    {
+        int grc = xGroupStart(d);
+        for (int p = 0; p < P && grc == XP_SUCCESS; p++) {
+            const u64 n = region[p + 1] - region[p];
+            if (n) grc = send_planes(snd, region[p], n, p);
+            if (in[p] && grc == XP_SUCCESS) grc = recv_planes(rcv, roff[p], in[p], p);
+        }
+        { const int gend = xGroupEnd(d); if (grc == XP_SUCCESS) grc = gend; }
+        if (grc != XP_SUCCESS) return comm_fail(grc);
+    }
+    bool wrapped = false;
+    local(rec_insert(shard.t, rcv, nin, &wrapped));
+    if (ctx->hook_dist_fail_reduce) {         // test hook: this rank alone fails its owner merge, after the payload has moved
+        ctx->hook_dist_fail_reduce = 0;
+        local(fail(ctx, GK_E_STATE, std::string(who) + "injected failure (test_dist_fail_reduce)"));
+    }
+    std::vector<u64> sreg(2, 0);
+    if (!my_rc && !wrapped) local(rec_bucket(shard.t, 1, rcv, nin, sreg.data(), nullptr, nullptr, 0));     // the shard, compacted where the arrivals were
+    // ---- 5. shard sizes: the owners' verdicts
+    std::vector<unsigned long long> ssz(P);
+    if (int rc = word_all_gather(my_rc ? ~0ull : wrapped ? ~0ull - 1 : sreg[1], ssz.data())) return rc;
+    bool over = false;
+    for (int p = 0; p < P; p++) {
+        if (ssz[p] == ~0ull) return give_up("rank " + std::to_string(p) + " failed its owner merge; every rank gave up, nothing was changed");
+        over |= ssz[p] == ~0ull - 1;
+    }
+    if (over) return fail(ctx, GK_E_CAPACITY, std::string(who) + "a count summed over the ranks would pass 2^32-1; nothing was changed");
+    u64 total = 0;
+    std::vector<u64> soff(P + 1, 0);
+    for (int p = 0; p < P; p++) { soff[p] = total; total += ssz[p]; }
+    // ---- 6. room for every shard and the new table
+    if (!planes(&all, total)) local(fail(ctx, GK_E_HIP, std::string(who) + "staging of " + std::to_string(total) + " records"));
+    if (!my_rc) local(rec_new(ctx, total, g->v.n_edges, &fresh.t));
+    {
+        bool any = false;
+        if (int rc = any_rank(my_rc != GK_OK, &any)) return rc;
+        if (any) return give_up(std::string("a rank had no room for the summed ") + what + "; every rank gave up, nothing was changed");
+    }
+    // ---- 7. every shard to every rank, the rebuild, the last agreement
+    {
+        const u64 n = ssz[me];
+        int grc = xGroupStart(d);
+        for (int p = 0; p < P && grc == XP_SUCCESS; p++) {
+            if (n) grc = send_planes(rcv, 0, n, p);
+            if (ssz[p] && grc == XP_SUCCESS) grc = recv_planes(all, soff[p], ssz[p], p);
+        }
+        { const int gend = xGroupEnd(d); if (grc == XP_SUCCESS) grc = gend; }
+        if (grc != XP_SUCCESS) return comm_fail(grc);
+    }
+    local(rec_uncanon<T>(ctx, all, total, d_inv, nlive));             // back to this replica's own edge ids
+    bool never = false;
+    if (!my_rc) local(rec_insert(fresh.t, all, total, &never));       // (the shards are disjoint: every record is a new one)
+    u64 got = 0;
+    if (!my_rc) local(rec_distinct(fresh.t, &got));
+    if (!my_rc && (got != total || never)) local(fail(ctx, GK_E_STATE, std::string(who) + "rebuilt " + std::to_string(got) + " records from " + std::to_string(total) + " shard records"));
+    {
+        bool any = false;
+        if (int rc = any_rank(my_rc != GK_OK, &any)) return rc;
+        if (any) return give_up(std::string("a rank could not rebuild the summed ") + what + "; every rank gave up, nothing was changed");
+    }
+    return rec_adopt(tab, fresh.t);
+}
+}  // namespace
+
+extern "C" int gk_dist_reduce_links(gk_dist *d, gk_graph *g, gk_links *links) { return dist_reduce_records(d, g, links, "gk_dist_reduce_links: ", "the links"); }
+extern "C" int gk_dist_reduce_spans(gk_dist *d, gk_graph *g, gk_spans *spans) { return dist_reduce_records(d, g, spans, "gk_dist_reduce_spans: ", "the spans"); }

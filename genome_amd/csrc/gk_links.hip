@@ -16,6 +16,11 @@
 // the leader's key by __shfl, a ballot on equality, the leader adds the popcount and the summed u) was built and measured, and
 // does not win: 1.045 ms against 1.042 ms a call on a 4 Mbp genome (profiles/r11/pair_links_4Mbp_400k_pairs_combine_LOSES.txt);
 // a wave's neighbours in the stream are unrelated fragments.  It is gone.
+//
+// The second half of the file is what the N-rank reduce of the table needs (gk_links.h): the canonical edge numbering by path
+// content (graph_edge_pathkeys) and the table's records as planes (rec_bucket / rec_insert / rec_uncanon).
+#include <rocprim/device/device_radix_sort.hpp>
+
 #include <algorithm>
 #include <memory>
 #include <unordered_map>
@@ -23,6 +28,7 @@
 #include <vector>
 
 #include "gk_graph.h"
+#include "gk_records.h"
 #include "gk_scan.h"
 #include "gk_support.h"
 
@@ -260,7 +266,248 @@ int links_merge(gk_links *dst, const gk_links *src, const char *who) {
 // a call's own table (what it counts into before the merge), destroyed with the scope
 using LocalLinks = std::unique_ptr<gk_links, void (*)(gk_links *)>;
 
+// ---- the path key: a canonical edge numbering by content, for graphs whose edits made copies (gk_links.h) ------------------------
+// The work is the pool's live WORDS, not its edges: word j of edge e (the 32 bases seq[32j .. 32j + 31], read from the edge's own
+// first byte, so that where the pool put the edge does not matter) has the number woff[e] + j, woff the scan of the live edges'
+// word counts.  That number space is cut into chunks of PK_CHUNK_WORDS = 64 words, one wave step each, whatever edge they fall in:
+// an edge of a megabase is spread over the whole grid and 64 edges of one word share a step.  A step's lanes load 512 contiguous
+// bytes (8 per lane), add their two terms per word, and the wave reduces them before anything leaves it: one 64-bit atomic add
+// per sum and (edge, chunk).  Where all PK_STEPS chunks of a wave's trip lie in one edge — all but the trips at an edge's ends —
+// they are summed in registers first and the trip costs one add, by __shfl_down; a trip that crosses edges finds every lane's
+// edge by a search between the trip's first and last edge and reduces by SEGMENT (a Hillis-Steele scan that adds only across
+// lanes of one edge; edges ascend with the lane), and the last lane of each segment adds.  No LDS: the sums live in registers and
+// the only cross-lane traffic is the shuffles.  Cost: the pool's live bytes read once (8 B per word against three mix64, six
+// 64-bit multiplies); the atomics are 16 B per 512 B read at worst; and, before a trip's first pool byte, one binary search of
+// woff for the trip's first edge — about log2(n_edges) dependent loads, 20 on a graph of 10^6 edges, whose upper levels every wave
+// shares in L2 — which is why a trip is PK_STEPS = 8 chunks (4 KiB) and not one.  The trip's last edge is searched FROM the first
+// (doubling steps, then bisection): one load where the trip lies in one edge.  A wave's next trip lies a whole grid further on, so
+// nothing carries over.  None of this has been timed yet (scripts/time_links_reduce.py reports the pass against a copy of the
+// same bytes).
+constexpr u32 PK_STEPS = 8;
+// the largest e in [lo, hi] with woff[e] <= w: the edge that holds word w (dead edges hold none: woff[e] == woff[e + 1])
+__device__ __forceinline__ u32 pk_edge_of(const unsigned long long *__restrict__ woff, u32 lo, u32 hi, u64 w) {
+    while (lo < hi) {
+        const u32 mid = lo + (hi - lo + 1) / 2;
+        if (woff[mid] <= w) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// the same, searched upwards from lo (woff[lo] <= w): doubling steps, then bisection — O(log(answer - lo)) loads, one when the answer is lo
+__device__ __forceinline__ u32 pk_edge_from(const unsigned long long *__restrict__ woff, u32 lo, u32 top, u64 w) {
+    for (u32 step = 1; lo < top; step <<= 1) {
+        const u32 nx = top - lo < step ? top : lo + step;
+        if (woff[nx] > w) return pk_edge_of(woff, lo, nx - 1, w);
+        lo = nx;
+    }
+    return lo;
+}
+// word j of an edge whose sequence starts at byte p: a whole word is one (unaligned) 8-byte load; the ragged last word is read byte
+// by byte, only the bytes the edge owns, and the bases past its end are masked off
+__device__ __forceinline__ u64 pk_load_word(const uint8_t *__restrict__ p, u64 j, u64 len) {
+    const u64 rem = len - 32 * j;
+    u64 w = 0;
+    if (rem >= 32) { __builtin_memcpy(&w, p + 8 * j, 8); return w; }
+    const u32 nb = (u32)(rem + 3) / 4;
+    for (u32 b = 0; b < nb; b++) w |= (u64)p[8 * j + b] << (8 * b);
+    return w & low_mask((int)(2 * rem));
+}
+__global__ __launch_bounds__(BLOCK) void k_pk_words(GraphView g, u32 *nw) {
+    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK) nw[e] = g.e_alive[e] ? (u32)((g.e_len[e] + 31) / 32) : 0u;
+}
+__global__ __launch_bounds__(BLOCK) void k_pk_hash(GraphView g, const unsigned long long *__restrict__ woff, u64 nwords, unsigned long long *sums) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr u64 TRIP = (u64)PK_CHUNK_WORDS * PK_STEPS;
+    const u64 stride = (u64)gridDim.x * (BLOCK / 64) * TRIP;
+    const u32 ne = (u32)g.n_edges;
+    for (u64 base = ((u64)blockIdx.x * (BLOCK / 64) + wave) * TRIP; base < nwords; base += stride) {      // (uniform over the wave)
+        const u64 last = min(base + TRIP, nwords) - 1;
+        const u32 e_lo = pk_edge_of(woff, 0, ne - 1, base), e_hi = pk_edge_from(woff, e_lo, ne - 1, last);
+        if (e_lo == e_hi) {
+            const u64 w0 = woff[e_lo], len = g.e_len[e_lo];
+            const uint8_t *p = g.pool + g.e_off[e_lo];
+            u64 a1 = 0, a2 = 0;
+#pragma unroll
+            for (u32 s = 0; s < PK_STEPS; s++) {
+                const u64 w = base + s * PK_CHUNK_WORDS + lane;
+                if (w > last) continue;
+                u64 t1, t2;
+                pk_word_terms(pk_load_word(p, w - w0, len), w - w0, &t1, &t2);
+                a1 += t1; a2 += t2;
+            }
+            for (int d = 32; d; d >>= 1) { a1 += __shfl_down(a1, d); a2 += __shfl_down(a2, d); }
+            if (lane == 0) { atomicAdd(&sums[2 * (u64)e_lo], (unsigned long long)a1); atomicAdd(&sums[2 * (u64)e_lo + 1], (unsigned long long)a2); }
+            continue;
+        }
+        for (u32 s = 0; s < PK_STEPS; s++) {
+            const u64 w = base + s * PK_CHUNK_WORDS + lane;
+            const bool in = w <= last;
+            u32 e = NONE;
+            u64 t1 = 0, t2 = 0;
+            if (in) {
+                e = pk_edge_of(woff, e_lo, e_hi, w);
+                const u64 j = w - woff[e];
+                pk_word_terms(pk_load_word(g.pool + g.e_off[e], j, g.e_len[e]), j, &t1, &t2);
+            }
+            for (int d = 1; d < 64; d <<= 1) {
+                const u64 u1 = __shfl_up(t1, d), u2 = __shfl_up(t2, d);
+                const u32 ue = __shfl_up(e, d);
+                if (lane >= d && ue == e) { t1 += u1; t2 += u2; }
+            }
+            const u32 next = __shfl_down(e, 1);
+            if (in && (lane == 63 || next != e)) { atomicAdd(&sums[2 * (u64)e], (unsigned long long)t1); atomicAdd(&sums[2 * (u64)e + 1], (unsigned long long)t2); }
+        }
+    }
+}
+// h1[e], h2[e] = the key (~0, ~0 dead), ids[e] = e; out[0] += live edges, out[1] += the fingerprint's term of every live edge
+__global__ __launch_bounds__(BLOCK) void k_pk_keys(GraphView g, const unsigned long long *__restrict__ sums, u64 *h1, u64 *h2, u32 *ids, unsigned long long *out) {
+    u64 live = 0, fp = 0;
+    for (u64 e = (u64)blockIdx.x * BLOCK + threadIdx.x; e < g.n_edges; e += (u64)gridDim.x * BLOCK) {
+        ids[e] = (u32)e;
+        if (!g.e_alive[e]) { h1[e] = h2[e] = ~0ull; continue; }
+        const u32 s = g.e_start[e];
+        u64 a, b;
+        pk_finish(sums[2 * e], sums[2 * e + 1], g.node_lo[s], g.node_hi[s], g.e_len[e], &a, &b);
+        h1[e] = a; h2[e] = b;
+        live++;
+        fp += mix64(a ^ mix64(b + PK_FP));
+    }
+    for (int d = 32; d; d >>= 1) { live += __shfl_down(live, d); fp += __shfl_down(fp, d); }
+    if ((threadIdx.x & 63) == 0) { atomicAdd(&out[0], (unsigned long long)live); atomicAdd(&out[1], (unsigned long long)fp); }
+}
+__global__ __launch_bounds__(BLOCK) void k_pk_gather(const u64 *__restrict__ h1, const u32 *__restrict__ ids, u64 n, u64 *out) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) out[i] = h1[ids[i]];
+}
+// after the sorts (by h2, then stably by h1): canon[local id] = rank, inv[rank] = local id; an edge whose neighbour in the order
+// has its key is a duplicate
+__global__ __launch_bounds__(BLOCK) void k_pk_canon(const u64 *__restrict__ sk1, const u32 *__restrict__ sid, const u64 *__restrict__ h2, u64 nlive, u32 *canon,
+                                                    u32 *inv, uint8_t *dup) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < nlive; i += (u64)gridDim.x * BLOCK) {
+        const u32 id = sid[i];
+        canon[id] = (u32)i;
+        inv[i] = id;
+        const bool before = i && sk1[i - 1] == sk1[i] && h2[sid[i - 1]] == h2[id], after = i + 1 < nlive && sk1[i + 1] == sk1[i] && h2[sid[i + 1]] == h2[id];
+        dup[id] = before || after ? 1 : 0;
+    }
+}
+
+// ---- the link table's records as planes (gk_links.h) -----------------------------------------------------------------------------
+struct LinkSrc {
+    const u64 *keys; const u32 *cnt; const unsigned long long *sum; u64 cap;
+    __device__ __forceinline__ bool get(u64 i, const RecCanon &c, u64 *key, u32 *n, u64 *x) const {
+        const u64 k = keys[i];
+        if (k == SUP_EMPTY) return false;
+        const u32 a = rec_canon_id(c, (u32)(k >> 32)), b = rec_canon_id(c, (u32)k);
+        if (a == NONE || b == NONE) return false;
+        *key = ((u64)a << 32) | b; *n = cnt[i]; *x = sum[i];
+        return true;
+    }
+};
+__global__ __launch_bounds__(BLOCK) void k_link_add_planes(RecPlanes p, u64 n, LinkView t) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) link_add(t, p.key[i], p.cnt[i], p.x[i]);
+}
+
 }  // namespace
+
+namespace gk {
+int graph_edge_pathkeys(gk_graph *g, DevScratch &keep, u32 **d_canon, u32 **d_inv, uint8_t **d_dup, u64 *nlive, u64 *content_fp, u64 **d_h1, u64 **d_h2) {
+    gk_ctx *ctx = g->ctx;
+    *d_canon = *d_inv = nullptr; *d_dup = nullptr;
+    *nlive = 0; *content_fp = 0;
+    const u64 ne = g->v.n_edges;
+    if (ne >= (u64)NONE) return fail(ctx, GK_E_CAPACITY, "graph_edge_pathkeys: more than 2^32 - 1 edge ids");
+    DevScratch tmp(ctx);
+    u32 *d_nw = nullptr, *d_id = nullptr, *d_id2 = nullptr, *d_id3 = nullptr;
+    u64 *h1 = nullptr, *h2 = nullptr, *d_k = nullptr, *d_k2 = nullptr;
+    unsigned long long *d_woff = nullptr, *d_sums = nullptr, *d_out = nullptr, h_out[2] = {0, 0}, h_words = 0;
+    void *d_temp = nullptr;
+    size_t temp_bytes = 0;
+    u32 *canon = nullptr, *inv = nullptr;
+    uint8_t *dup = nullptr;
+    keep.get(&h1, ne);
+    keep.get(&h2, ne);
+    keep.get(&canon, ne);
+    keep.zeroed(&dup, ne);
+    if (canon) keep.note(hipMemsetAsync(canon, 0xff, std::max<u64>(ne, 1) * 4, ctx->stream));
+    if (keep.error() != hipSuccess) return hip_fail(ctx, keep.error(), "graph_edge_pathkeys: maps");
+    tmp.get(&d_nw, ne);
+    tmp.get(&d_woff, ne + 1);
+    tmp.zeroed(&d_sums, 2 * ne);
+    tmp.get(&d_id, ne); tmp.get(&d_id2, ne); tmp.get(&d_id3, ne);
+    tmp.get(&d_k, ne); tmp.get(&d_k2, ne);
+    tmp.zeroed(&d_out, 2);
+    if (ne) tmp.note(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_k, d_k2, d_id, d_id2, (size_t)ne, 0, 64, ctx->stream));   // (the size query)
+    tmp.get((uint8_t **)&d_temp, temp_bytes);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "graph_edge_pathkeys: scratch");
+    if (ne) {
+        hipLaunchKernelGGL(k_pk_words, dim3(ggrid(ctx, ne)), dim3(BLOCK), 0, ctx->stream, g->v, d_nw);
+        GK_HIP(ctx, hipGetLastError());
+        GK_HIP(ctx, scan_counts(ctx, tmp, d_nw, ne, d_woff));
+        GK_HIP(ctx, read_back(ctx, &h_words, d_woff + ne));
+        if (h_words) {
+            constexpr u64 per_wg = (u64)PK_CHUNK_WORDS * PK_STEPS * (BLOCK / 64);
+            const u64 grid = std::min<u64>((h_words + per_wg - 1) / per_wg, grid_cap(ctx));
+            hipLaunchKernelGGL(k_pk_hash, dim3((unsigned)grid), dim3(BLOCK), 0, ctx->stream, g->v, d_woff, (u64)h_words, d_sums);
+        }
+        hipLaunchKernelGGL(k_pk_keys, dim3(ggrid(ctx, ne)), dim3(BLOCK), 0, ctx->stream, g->v, d_sums, h1, h2, d_id, d_out);
+        GK_HIP(ctx, hipGetLastError());
+        // by (h1, h2): the radix sort is stable, so the minor key goes first
+        GK_HIP(ctx, hipMemcpyAsync(d_k, h2, ne * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        GK_HIP(ctx, rocprim::radix_sort_pairs(d_temp, temp_bytes, d_k, d_k2, d_id, d_id2, (size_t)ne, 0, 64, ctx->stream));
+        hipLaunchKernelGGL(k_pk_gather, dim3(ggrid(ctx, ne)), dim3(BLOCK), 0, ctx->stream, h1, d_id2, ne, d_k);
+        GK_HIP(ctx, rocprim::radix_sort_pairs(d_temp, temp_bytes, d_k, d_k2, d_id2, d_id3, (size_t)ne, 0, 64, ctx->stream));
+    }
+    GK_HIP(ctx, read_back(ctx, h_out, d_out, 2));
+    keep.get(&inv, h_out[0]);
+    if (keep.error() != hipSuccess) return hip_fail(ctx, keep.error(), "graph_edge_pathkeys: maps");
+    if (h_out[0]) hipLaunchKernelGGL(k_pk_canon, dim3(ggrid(ctx, h_out[0])), dim3(BLOCK), 0, ctx->stream, d_k2, d_id3, h2, (u64)h_out[0], canon, inv, dup);
+    GK_HIP(ctx, hipGetLastError());
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));                 // (the scratch goes with this scope)
+    *d_canon = canon; *d_inv = inv; *d_dup = dup;
+    if (d_h1) *d_h1 = h1;
+    if (d_h2) *d_h2 = h2;
+    *nlive = h_out[0];
+    *content_fp = h_out[1] + mix64(h_out[0] ^ PK_LIVE);
+    return GK_OK;
+}
+
+template <> gk_ctx *rec_ctx<gk_links>(const gk_links *l) { return l->ctx; }
+template <> int rec_distinct<gk_links>(const gk_links *l, u64 *n) {
+    unsigned long long h = 0;
+    GK_HIP(l->ctx, read_back(l->ctx, &h, l->d_ctr));
+    *n = h;
+    return GK_OK;
+}
+template <> int rec_bucket<gk_links>(gk_links *l, int P, const RecPlanes &out, u64 room, u64 *region, const u32 *canon, const uint8_t *dup, u64 nmap) {
+    return records_bucket(l->ctx, LinkSrc{l->d_keys, l->d_cnt, l->d_sum, l->cap}, P, out, room, region, canon, dup, nmap, "the links");
+}
+template <> int rec_insert<gk_links>(gk_links *l, const RecPlanes &in, u64 n, bool *overflow) {
+    gk_ctx *ctx = l->ctx;
+    *overflow = false;
+    if (n == 0) return GK_OK;
+    u64 have = 0;
+    if (int rc = rec_distinct(l, &have)) return rc;
+    if (int rc = links_reserve(l, have + n)) return rc;
+    hipLaunchKernelGGL(k_link_add_planes, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, in, n, link_view(l));
+    unsigned long long f[2] = {0, 0};                          // [3] table full, [4] a count wrapped
+    GK_HIP(ctx, read_back(ctx, f, l->d_ctr + 3, 2));
+    if (f[0]) return fail(ctx, GK_E_CAPACITY, "the link table filled up (internal sizing error)");
+    *overflow = f[1] != 0;
+    return GK_OK;
+}
+template <> int rec_uncanon<gk_links>(gk_ctx *ctx, const RecPlanes &p, u64 n, const u32 *d_inv, u64 nlive) { return records_uncanon(ctx, p, n, false, d_inv, nlive); }
+template <> int rec_new<gk_links>(gk_ctx *ctx, u64 want, u64 id_bound, gk_links **out) {
+    if (int rc = gk_links_create(ctx, out)) return rc;
+    (*out)->id_bound = id_bound;
+    return links_reserve(*out, want);
+}
+template <> void rec_free<gk_links>(gk_links *l) { gk_links_destroy(l); }
+template <> int rec_adopt<gk_links>(gk_links *s, gk_links *t) {
+    GK_HIP(s->ctx, hipStreamSynchronize(s->ctx->stream));
+    std::swap(s->d_keys, t->d_keys); std::swap(s->d_cnt, t->d_cnt); std::swap(s->d_sum, t->d_sum); std::swap(s->cap, t->cap); std::swap(s->d_ctr, t->d_ctr);
+    s->id_bound = std::max(s->id_bound, t->id_bound);
+    return GK_OK;
+}
+}  // namespace gk
 
 extern "C" {
 

@@ -20,6 +20,7 @@
 #include <memory>
 
 #include "gk_binstream.h"
+#include "gk_records.h"
 #include "gk_spans.h"
 #include "gk_support.h"
 #include "gk_thread_common.h"
@@ -287,9 +288,62 @@ int spans_end(const SpanCall &c, gk_spans *spans, bool dev_format, uint64_t *sta
     return GK_OK;
 }
 
+// ---- the span table's records as planes (gk_links.h): key plane (e << 32 | m), extra plane f ----------------------------------
+struct SpanSrc {
+    const u64 *keys; const u32 *f; const u32 *cnt; u64 cap;
+    __device__ __forceinline__ bool get(u64 i, const RecCanon &c, u64 *key, u32 *n, u64 *x) const {
+        const u64 k = keys[i];
+        if (k == SUP_EMPTY || f[i] == NONE) return false;
+        const u32 e = rec_canon_id(c, (u32)(k >> 33)), m = rec_canon_id(c, (u32)(k >> 2) & 0x7fffffffu), o = rec_canon_id(c, f[i]);
+        if (e == NONE || m == NONE || o == NONE) return false;
+        *key = ((u64)e << 32) | m; *n = cnt[i]; *x = o;
+        return true;
+    }
+};
+__global__ __launch_bounds__(BLOCK) void k_span_add_planes(RecPlanes p, u64 n, SpanView t) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) span_add(t, (u32)(p.key[i] >> 32), (u32)p.key[i], (u32)p.x[i], p.cnt[i]);
+}
+
 }  // namespace
 
 namespace gk {
+template <> gk_ctx *rec_ctx<gk_spans>(const gk_spans *s) { return s->ctx; }
+template <> int rec_distinct<gk_spans>(const gk_spans *s, u64 *n) {
+    unsigned long long h = 0;
+    GK_HIP(s->ctx, read_back(s->ctx, &h, s->d_ctr));
+    *n = h;
+    return GK_OK;
+}
+template <> int rec_bucket<gk_spans>(gk_spans *s, int P, const RecPlanes &out, u64 room, u64 *region, const u32 *canon, const uint8_t *dup, u64 nmap) {
+    return records_bucket(s->ctx, SpanSrc{s->d_keys, s->d_f, s->d_cnt, s->cap}, P, out, room, region, canon, dup, nmap, "the spans");
+}
+template <> int rec_insert<gk_spans>(gk_spans *s, const RecPlanes &in, u64 n, bool *overflow) {
+    gk_ctx *ctx = s->ctx;
+    *overflow = false;
+    if (n == 0) return GK_OK;
+    u64 have = 0;
+    if (int rc = rec_distinct(s, &have)) return rc;
+    if (s->cap < 2 * (have + n)) return fail(ctx, GK_E_STATE, "rec_insert: the span table was not made for " + std::to_string(have + n) + " triples");
+    hipLaunchKernelGGL(k_span_add_planes, dim3(ggrid(ctx, n)), dim3(BLOCK), 0, ctx->stream, in, n, span_view(s));
+    unsigned long long fl[3] = {0, 0, 0};                      // [3] table full, [4] a count wrapped, [5] a fifth out-edge
+    GK_HIP(ctx, read_back(ctx, fl, s->d_ctr + 3, 3));
+    if (fl[0]) return fail(ctx, GK_E_CAPACITY, "the span table filled up (internal sizing error)");
+    if (fl[2]) return fail(ctx, GK_E_STATE, "more than four out-edges behind one (in-edge, edge) over the ranks: the spans do not belong to this graph");
+    *overflow = fl[1] != 0;
+    return GK_OK;
+}
+template <> int rec_uncanon<gk_spans>(gk_ctx *ctx, const RecPlanes &p, u64 n, const u32 *d_inv, u64 nlive) { return records_uncanon(ctx, p, n, true, d_inv, nlive); }
+template <> int rec_new<gk_spans>(gk_ctx *ctx, u64 want, u64, gk_spans **out) {
+    if (int rc = gk_spans_create(ctx, out)) return rc;
+    return spans_alloc(*out, want);
+}
+template <> void rec_free<gk_spans>(gk_spans *s) { gk_spans_destroy(s); }
+template <> int rec_adopt<gk_spans>(gk_spans *s, gk_spans *t) {
+    GK_HIP(s->ctx, hipStreamSynchronize(s->ctx->stream));
+    std::swap(s->d_keys, t->d_keys); std::swap(s->d_f, t->d_f); std::swap(s->d_cnt, t->d_cnt); std::swap(s->cap, t->cap); std::swap(s->d_ctr, t->d_ctr);
+    return GK_OK;
+}
+
 int spans_to_host(const gk_spans *s, std::vector<u32> &e, std::vector<u32> &m, std::vector<u32> &f, std::vector<u32> &count) {
     gk_ctx *ctx = s->ctx;
     e.clear(); m.clear(); f.clear(); count.clear();

@@ -23,6 +23,7 @@
 
 #include "gk_dist.h"
 #include "gk_graph.h"
+#include "gk_links.h"
 #include "gk_scan.h"
 #include "gk_support.h"
 #include "../../include/genome_amd_test.h"
@@ -166,6 +167,22 @@ int gk_test_scan_counts(gk_ctx *ctx, const uint32_t *in_host, uint64_t n, int vi
     u64 hits = 0;
     for (u64 g : guards) hits += g != SCAN_FILL;
     *guard_hits = hits;
+    return GK_OK;
+}
+
+int gk_test_edge_path_keys(gk_graph *g, uint64_t *h1, uint64_t *h2, uint32_t *canon, uint8_t *dup, uint64_t *nlive, uint64_t *fingerprint) {
+    if (!g || !g->ctx) return fail(nullptr, GK_E_INVALID, "gk_test_edge_path_keys: null graph handle");
+    gk_ctx *ctx = g->ctx;
+    if (!h1 || !h2 || !canon || !dup || !nlive || !fingerprint) return fail(ctx, GK_E_INVALID, "gk_test_edge_path_keys: null argument");
+    GK_HIP(ctx, hipSetDevice(ctx->device));
+    DevScratch keep(ctx);
+    u32 *d_canon = nullptr, *d_inv = nullptr;
+    uint8_t *d_dup = nullptr;
+    u64 *d_h1 = nullptr, *d_h2 = nullptr, n = 0, fp = 0;
+    if (int rc = graph_edge_pathkeys(g, keep, &d_canon, &d_inv, &d_dup, &n, &fp, &d_h1, &d_h2)) return rc;
+    const size_t ne = g->v.n_edges;
+    if (ne) GK_HIP(ctx, read_back(ctx, {{h1, d_h1, ne * 8}, {h2, d_h2, ne * 8}, {canon, d_canon, ne * 4}, {dup, d_dup, ne}}));
+    *nlive = n; *fingerprint = fp;
     return GK_OK;
 }
 

@@ -80,6 +80,20 @@ class HipDist:
         L.check(L.lib().gk_dist_reduce_support(self.h, graph.h if graph is not None else None,
                                                support.h if support is not None else None), self.ctx.h)
 
+    def reduce_links(self, graph, links):
+        """COLLECTIVE (gk_dist_reduce_links): every rank's `links` (HipGraph.pairLinks of its share of the pairs on its replica
+        `graph`) becomes the element-wise sum over all ranks, in this rank's own edge ids.  The graph may be edited (split,
+        simplified): the records travel in a numbering by path content (include/genome_amd.h, "the path key"), so the replicas
+        must hold the same edge paths (GK_E_STATE on every rank otherwise) and no record may name a dead edge or one of two
+        edges with equal paths.  On any failure every rank raises and every table is unchanged.  `graph` / `links` may be None
+        on a rank that cannot take part: it still joins the agreement, and every rank raises."""
+        L.check(L.lib().gk_dist_reduce_links(self.h, graph.h if graph is not None else None, links.h if links is not None else None), self.ctx.h)
+
+    def reduce_spans(self, graph, spans):
+        """COLLECTIVE (gk_dist_reduce_spans): reduce_links for a span table, (e, m, f) -> count: every rank's `spans`
+        (HipGraph.threadSpans of its share of the reads) becomes the sum over all ranks, in this rank's own edge ids."""
+        L.check(L.lib().gk_dist_reduce_spans(self.h, graph.h if graph is not None else None, spans.h if spans is not None else None), self.ctx.h)
+
     def pair_distances(self, graph, positions, bin_bytes, npairs: int, bins: int = 4096):
         """COLLECTIVE (gk_dist_pair_distances): HipGraph.pairDistances of this rank's share of the pairs on its replica, summed
         over the ranks -> (hist, classes) of ALL pairs on every rank.  `graph` / `positions` may be None on a rank that cannot

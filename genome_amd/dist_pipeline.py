@@ -23,7 +23,8 @@ import numpy as np
 from . import dna
 from .dist import DistDNAMap, HipDist
 from .freqfilter import PairedEndData, auto_rounds
-from .graph import REFERENCE_RANGE, THREAD_STATS, HipGraph, Support, buildGraph, insertRange, loadGraph
+from .graph import (LINK_CLASSES, REFERENCE_RANGE, SPAN_STATS, THREAD_STATS, HipGraph, HipLinks, HipSpans, Support, buildGraph, insertRange,
+                    loadGraph, scaffoldChains, scaffoldGaps)
 
 
 def pair_share(npairs: int, world: int, rank: int, take_first: int | None = None) -> tuple[int, int]:
@@ -90,6 +91,54 @@ def _pairs_stage(hd: HipDist, g: HipGraph, share, npairs: int, walk_pairs, auto_
     return out
 
 
+def _resolve_stage(hd: HipDist, g: HipGraph, share, nreads: int, cutoff: int, rounds: int) -> list:
+    """Repeats longer than k, over the ranks (include/genome_amd.h, gk_graph_thread_spans): per round, on every rank, the position
+    map of the replica as it is now, threadSpans of the rank's `nreads` records in `share`, the span tables summed over the ranks
+    (gk_dist_reduce_spans: the graph is an edited one), splitEdgesBySpans at `cutoff`, simplifyGraph -> per round {"thread_spans"
+    (the five stats over all ranks), "split_edges"}.  A round that resolves nothing is the last: the summed table is the same on
+    every rank, so every rank stops in the same round."""
+    out = []
+    for _ in range(max(0, int(rounds))):
+        vm, sp = g.getGraphMap(), HipSpans(hd.ctx)
+        try:
+            mine = g.threadSpans(vm, sp, share, nreads) if nreads > 0 else dict.fromkeys(SPAN_STATS, 0)
+            total = hd.allreduce([float(mine[key]) for key in SPAN_STATS])
+            hd.reduce_spans(g, sp)
+            split = g.splitEdgesBySpans(sp, cutoff)
+        finally:
+            sp.close()
+            vm.close()
+        out.append({"thread_spans": {key: int(v) for key, v in zip(SPAN_STATS, total)}, "split_edges": split})
+        if not split["resolved"]:
+            break
+        g.simplifyGraph()
+    return out
+
+
+def _links_stage(hd: HipDist, g: HipGraph, share, npairs: int, min_support: int = 3, min_len: int = 0, max_span: int = 4095, mid=None) -> dict:
+    """Scaffold links of the FINAL graph over the ranks (include/genome_amd.h, "scaffold links"): pairLinks of the rank's `npairs`
+    pairs in `share` on its replica, the classes summed over the ranks, the link tables summed by gk_dist_reduce_links, then — per
+    rank, on the summed table — joins at `min_support`, chains and gaps (mid - floor(sum_u / count); mid defaults to max_span
+    div 2) -> {"links" (the HipLinks: the caller closes it), "classes", "joins", "join_stats", "chains", "cycles", "gaps"}.
+    Joins, chains and the records of a scaffold text follow THIS rank's edge ids: the ranks agree on the set of joins, chains and
+    records, not on their order."""
+    vm, links = g.getGraphMap(), HipLinks(hd.ctx)
+    try:
+        mine = g.pairLinks(vm, (share, npairs), links, min_len=min_len, max_span=max_span) if npairs > 0 else dict.fromkeys(LINK_CLASSES, 0)
+        total = hd.allreduce([float(mine[key]) for key in LINK_CLASSES])
+        hd.reduce_links(g, links)
+        joins, join_stats = links.joins(min_support)
+        chains, cycles = scaffoldChains(joins[0], joins[1], with_cycles=True)
+        gaps = scaffoldGaps(chains, joins, max_span // 2 if mid is None else mid)
+    except BaseException:
+        links.close()
+        raise
+    finally:
+        vm.close()
+    return {"links": links, "classes": {key: int(v) for key, v in zip(LINK_CLASSES, total)}, "joins": joins, "join_stats": join_stats,
+            "chains": chains, "cycles": cycles, "gaps": gaps}
+
+
 def _rank_share(hd: HipDist, data: PairedEndData, take_first: int | None):
     a, b = pair_share(data.count, hd.world, hd.rank, take_first)
     off = dna.bin_pair_offsets(data.bin, b)
@@ -152,7 +201,7 @@ def build_graph(hd: HipDist, data: PairedEndData, k: int, rounds=3, take_first: 
 
 def simplify_graph(hd: HipDist, graph_path, data: PairedEndData, cutoff: int, lo=180, hi=250,
                    take_first: int | None = None, max_insert: int = 4095, trim: int = 25, min_observations: int = 1000,
-                   thread_reads: bool = False, walk: bool = True) -> tuple[HipGraph, dict]:
+                   thread_reads: bool = False, walk: bool = True, resolve_repeats=None, links=None) -> tuple[HipGraph, dict]:
     """One rank's part of GraphSimplifier.startup (S/scripts/GraphSimplifier.scala:152-318) over N ranks: every rank loads the
     same graph file (:152-153, so the replicas are identical, ids included), then walks its own share of the pairs and the
     supports are summed over the ranks before the split, as in build_graph's pairs stage.  The range defaults to the
@@ -162,14 +211,27 @@ def simplify_graph(hd: HipDist, graph_path, data: PairedEndData, cutoff: int, lo
     components_histogram_2 and max_component_size of the final graph (:320-331), and world.  thread_reads = True threads each
     rank's share of the reads through the graph into the same support before the reduce (this project's own rule,
     gk_graph_thread_reads; walk_pairs["thread_reads"] holds the stats over all ranks); walk = False skips the walks, so that the
-    reads alone are the evidence.  COLLECTIVE.  The caller closes
-    the graph."""
+    reads alone are the evidence.
+    resolve_repeats = (cutoff, rounds) (default None: off): after the stage's split and simplify, up to `rounds` rounds of
+    _resolve_stage over this rank's share of the reads (both mates of its pairs); stats["resolve_repeats"] holds the rounds.
+    With it, walk = False without thread_reads is allowed: the paired-end stage is skipped altogether (stats["walk_pairs"] is
+    None), as `graph_simplifier --no-pairs --resolve-repeats` does on one GPU.
+    links = dict(min_support, min_len, max_span, mid) (default None: off; any key may be left out): _links_stage on the FINAL
+    graph; stats["links"] holds its result — the summed HipLinks under "links" (the caller closes it), the classes over all
+    ranks, joins, chains and gaps — so that the caller goes on to HipGraph.scaffolds, fillGaps, overlapGaps and judge_scaffolds
+    as on one GPU.  Record order in a scaffold text follows a rank's own edge ids: the ranks agree on the SET of records, not
+    on their order.  COLLECTIVE.  The caller closes the graph."""
     g = loadGraph(hd.ctx, graph_path)
     try:
         a, b, share = _rank_share(hd, data, take_first)
         n1, e1, l1 = g.counts()
-        walk = _pairs_stage(hd, g, share, b - a, (cutoff, lo, hi),
-                            {"max_insert": max_insert, "trim": trim, "min_observations": min_observations}, thread_reads, walk)
+        if not walk and not thread_reads and resolve_repeats is not None:
+            walk = None                     # no support was gathered: the node split does not run and the spans alone edit the graph
+        else:
+            walk = _pairs_stage(hd, g, share, b - a, (cutoff, lo, hi),
+                                {"max_insert": max_insert, "trim": trim, "min_observations": min_observations}, thread_reads, walk)
+        resolved = _resolve_stage(hd, g, share, 2 * (b - a), *resolve_repeats) if resolve_repeats is not None else None
+        linked = _links_stage(hd, g, share, b - a, **links) if links is not None else None
         n2, e2, l2 = g.counts()
         sizes, _ = g.componentStats()
         _, hist2 = g.componentHistograms()
@@ -179,4 +241,8 @@ def simplify_graph(hd: HipDist, graph_path, data: PairedEndData, cutoff: int, lo
     stats = {"k": g.k, "nodes": n1, "edges": e1, "edges_length": l1, "walk_pairs": walk, "simplified_nodes": n2, "simplified_edges": e2,
              "simplified_edges_length": l2, "components_histogram_2": [list(x) for x in hist2],
              "max_component_size": int(sizes.max()) if len(sizes) else 0, "world": hd.world}
+    if resolved is not None:
+        stats["resolve_repeats"] = resolved
+    if linked is not None:
+        stats["links"] = linked
     return g, stats

@@ -303,6 +303,8 @@ class DNAMap {
 // not `hashCode mod P` (:60-63): the partition function is unobservable in results and keeps x and rc(x) together.
 class Graph;
 class Support;
+class Links;
+class Spans;
 class PartitionedDNAMap {
   public:
     static std::vector<uint8_t> uniqueId() {
@@ -369,6 +371,12 @@ class PartitionedDNAMap {
     void barrier() { check(gk_dist_barrier(d_), ctx_.handle()); }
     // every rank's support (its share of the pairs walked on its replica) becomes the sum over all ranks (gk_dist_reduce_support)
     void reduceSupport(Graph &graph, Support &support);
+    // every rank's link table (pairLinks of its share of the pairs on its replica) / span table (threadSpans of its share of the
+    // reads) becomes the sum over all ranks, keyed by this rank's edge ids (gk_dist_reduce_links / gk_dist_reduce_spans).  The graph
+    // may be an edited one: the records travel in a numbering of the edges by path content.  COLLECTIVE; on any failure every rank
+    // throws and every table is unchanged.
+    void reduceLinks(Graph &graph, Links &links);
+    void reduceSpans(Graph &graph, Spans &spans);
     gk_dist *distHandle() const { return d_; }
 
   private:
@@ -881,7 +889,7 @@ class Graph {
     // Reads followed across a whole edge (this project's own rule, include/genome_amd.h: gk_graph_thread_spans): both mates of the
     // first `takeFirst` pairs, as single reads; every edge a read crosses from end to end adds one to spans[(the edge it came by,
     // the edge, the edge it left by)].  -> {records threaded, crossings, spans, interrupted, open}.  On an error `spans` is
-    // unchanged.  One GPU: there is no collective over ranks.
+    // unchanged.  Over N ranks every rank threads its share and PartitionedDNAMap::reduceSpans sums the tables.
     struct SpanStats { uint64_t v[5] = {}; };
     static constexpr const char *spanStatNames[5] = {"records", "crossings", "spans", "interrupted", "open"};
     SpanStats threadSpans(PositionMap &positions, Spans &spans, const PairedEndData &data, uint64_t takeFirst) {
@@ -1194,6 +1202,12 @@ inline InsertRange insertRange(const std::vector<uint64_t> &hist, uint32_t trimP
 
 inline void PartitionedDNAMap::reduceSupport(Graph &graph, Support &support) {
     check(gk_dist_reduce_support(d_, graph.handle(), support.handle()), ctx_.handle());
+}
+inline void PartitionedDNAMap::reduceLinks(Graph &graph, Links &links) {
+    check(gk_dist_reduce_links(d_, graph.handle(), links.handle()), ctx_.handle());
+}
+inline void PartitionedDNAMap::reduceSpans(Graph &graph, Spans &spans) {
+    check(gk_dist_reduce_spans(d_, graph.handle(), spans.handle()), ctx_.handle());
 }
 
 }  // namespace genome

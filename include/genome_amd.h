@@ -769,7 +769,8 @@ int gk_graph_thread_spans_dev(gk_graph *g, gk_vmap *positions, gk_spans *spans, 
  * gk_graph_simplify reads its sources and appends; gk_graph_save compacts edge by edge into the file, so the loaded graph has one
  * range per edge; the contigs, the scaffolds and gk_graph_checksum only read).
  * Planning is on the host over the cached snapshot, the edits are device kernels, as gk_graph_split_by_support does it.
- * Where it stops: repeats a single read spans, one GPU (no collective). */
+ * Where it stops: repeats a single read spans.  Over N ranks every rank threads its share of the reads and gk_dist_reduce_spans
+ * sums the tables on every rank before the split. */
 int gk_graph_split_edges_by_spans(gk_graph *g, const gk_spans *spans, uint32_t cutoff, uint64_t *stats7);
 
 /* ---- the insert range: this project's own rule (the reference hardcodes `180 to 250`, GraphSimplifier.scala:146, with
@@ -865,8 +866,7 @@ int gk_dist_pair_distances(gk_dist *d, gk_graph *g, gk_vmap *positions, const ui
  * that at the end, as gk_graph_thread_reads does, so on ANY error `links` is unchanged and classes8 is zero.  A count that would
  * pass 2^32-1 is GK_E_CAPACITY (gk_support_add's rule), here and in gk_links_add.  Neither the graph nor the position map
  * changes.  Edge ids are the graph's at the time of the call: the table holds no state counter and is MEANINGLESS after a graph
- * edit; make a new one.  Over N ranks every rank links its share, exports, and one rank takes them with gk_links_add: there is
- * no collective yet.
+ * edit; make a new one.  Over N ranks every rank links its share and gk_dist_reduce_links sums the tables on every rank.
  * On the device: one lane per orientation over the getAll batch's CSR, class counts by ballot, one insert per linked lane into an
  * open-addressed (e << 32 | f) table with a u32 count plane and a u64 sum plane, sized before the launch for one link per
  * orientation at load <= 0.5. */
@@ -882,6 +882,42 @@ int gk_links_export(const gk_links *l, uint32_t *e1, uint32_t *e2, uint32_t *cou
 /* Add n (e1, e2, count, sum_u) records; duplicates in the list add up.  Export, then add into an empty table, reproduces the
  * table.  A count that would pass 2^32-1 fails with GK_E_CAPACITY, and l is then unchanged.  0xffffffff is not an edge id. */
 int gk_links_add(gk_links *l, const uint32_t *e1, const uint32_t *e2, const uint32_t *count, const uint64_t *sum_u, uint64_t n);
+
+/* ---- links and spans over the ranks: this project's own rules ----------------------------------------------------------------
+ * Links and spans are taken on the FINAL graph: after gk_graph_split_by_support and gk_graph_simplify, and for later resolve
+ * rounds after gk_graph_split_edges_by_spans too.  The replicas of such a graph hold the same edges under different ids, and their
+ * copies share k-mers, so gk_dist_reduce_support's numbering by (start k-mer, first base) cannot name them.  These two collectives
+ * number the edges by what they spell.
+ * The path key.  P(e) = start k-mer ++ seq, k + len bases.  With mix64 the 64-bit finalizer
+ *     mix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33
+ * and fold(a, v) = mix64(a ^ (v + 0x9e3779b97f4a7c15)), all arithmetic mod 2^64:
+ *     word j of e, j = 0 .. ceil(len / 32) - 1: the bases seq[32j .. 32j + 31], base 32j + i at bits 2i and 2i + 1 (codes A0 G1
+ *         C2 T3), the bases past the end of seq zero — counted from the edge's own first base, wherever the edge lies in memory;
+ *     t(j) = word j ^ mix64(j + 0x70617468776f7264);   S1 = sum over j of mix64(t(j));   S2 = sum of mix64(t(j) ^ 0x7365636f6e64);
+ *     h1 = fold(fold(fold(fold(0x7061746831, S1), lo), hi), len),   h2 = the same from 0x7061746832 and S2,
+ *         (lo, hi) the start k-mer's two words (gk_graph_nodes_by_id's); an h1 of 2^64 - 1 becomes 2^64 - 2.
+ * (h1, h2) is a function of the path alone, and the sums over words are what lets the device hash a long edge in pieces.  The
+ * canonical order of the live edges is ascending (h1, h2) — the length is no third sort key: it is folded into both hashes, so
+ * two paths of different length share a key only by a 128-bit collision, and would then count as duplicates.  Two live edges with equal keys are DUPLICATES: neighbours in the
+ * order, told apart by nothing a replica agrees on.  They are no error in themselves — every k-mer of such an edge has two
+ * positions, gk_graph_pair_links classes it `repetitive` and gk_graph_thread_spans follows no read through it, so no table these
+ * calls made names one — but a record that does name one, or a dead edge, fails the reduce with GK_E_STATE.  The replicas'
+ * FINGERPRINT is mix64(live edges ^ 0x6c697665) + the sum over live edges of mix64(h1 ^ mix64(h2 + 0x66696e676572)): equal on two
+ * replicas iff they hold the same multiset of paths (up to a 128-bit collision).  tests/pathkey_ref.py restates all of this.
+ * gk_dist_reduce_links.  Every rank holds a replica of g and has linked ITS share of the pairs into `links`; afterwards every
+ * rank's table holds the element-wise sum over all ranks — counts added (a sum past 2^32-1: GK_E_CAPACITY), sum_u added mod 2^64 —
+ * keyed by THIS rank's edge ids.  The contract is gk_dist_reduce_support's, step for step: the ranks agree on every rank's status
+ * and on equal fingerprints (GK_E_STATE otherwise) before any payload moves; a record goes to its owner rank by a hash of the
+ * canonical (e1, e2), one all-to-all of (key u64, count u32, sum_u u64) planes; after the owners' merge the ranks agree on "no
+ * count passed 2^32-1" and on the shard sizes, every shard goes to every rank, the keys go back to this replica's ids, and after
+ * the rebuild the ranks agree once more before anything is swapped in.  If any of this fails on any rank, every rank returns an
+ * error, every table is unchanged, no rank is left in a receive and the handle stays usable.  world == 1: only the checks run.
+ * gk_dist_reduce_spans: the same for (e, m, f) -> count.  The owner is a hash of the canonical (e, m), so the at most four
+ * out-edges behind one (e, m) meet at one owner; more than four over the ranks is GK_E_STATE.
+ * Both: COLLECTIVE, world <= 64, the graph is only read.  The joins, chains and scaffold text that follow are per rank and follow
+ * the rank's own ids: ranks agree on the SET of joins, chains and records, not on their order. */
+int gk_dist_reduce_links(gk_dist *d, gk_graph *g, gk_links *links);
+int gk_dist_reduce_spans(gk_dist *d, gk_graph *g, gk_spans *spans);
 /* Joins.  A link is SUPPORTED iff count >= min_support.  (e, f) is a JOIN iff it is the only supported link out of e and the only
  * supported link into f.  The joins come in ascending e1 (an e1 occurs at most once, so the order is total), with their count and
  * sum_u.  stats5 (may be NULL) = uint64[5] = {links, supported, joins, edges with >= 2 supported successors, edges with >= 2

@@ -36,7 +36,7 @@ extern "C" {
  * same range and refusal; 0 or -1 = chosen by free memory; at k = 64 a value above 45 means 45, the tagged table's densest step),
  * and the failure injections of the exchange: "test_dist_small_send" (a send region far too small: re-routed in place), "test_dist_fail_exchange" (this rank's next exchange fails locally with the given code), "test_dist_fail_classify"
  * (this rank cannot stage the queries of its next classified gather), "test_dist_fail_reduce" (this rank fails the owner merge of
- * its next gk_dist_reduce_support, after the records were exchanged).
+ * its next gk_dist_reduce_support, gk_dist_reduce_links or gk_dist_reduce_spans, after the records were exchanged).
  * "test_max_grid" (0: off; a positive value: every grid-stride launch of the graph phase — build, simplify, components,
  * coverage, tips, bubbles, distance, export, the graph file, the position map, the paired-end stage —, of the value maps, the
  * spectrum and the read correction gets at most that many workgroups, the pair walks twice as many, instead of 8 (16) per CU; a
@@ -105,6 +105,13 @@ int gk_test_scan_counts(gk_ctx *ctx, const uint32_t *in_host, uint64_t n, int vi
  * slot count stays unless the table is too dense for the graph phase); the map is otherwise unchanged and no graph is built.
  * GK_E_CAPACITY, with *nblk set and nothing copied, when cap_blocks < *nblk; GK_E_INVALID for a null pointer. */
 int gk_test_slot_ranks(gk_map *map, uint64_t *masks, uint64_t *bases, uint64_t cap_blocks, uint64_t *nblk, uint64_t *total);
+
+/* The canonical edge numbering by path content that gk_dist_reduce_links / gk_dist_reduce_spans use (include/genome_amd.h, "the
+ * path key"; csrc/gk_links.hip: graph_edge_pathkeys, the same function), run on its own.  Every array has one entry per edge id
+ * below gk_graph_id_bounds' edge bound: h1 / h2 = the key (2^64 - 1 twice for a dead edge), canon = the edge's place in the
+ * canonical order (0xffffffff dead), dup = 1 where another live edge has the same key.  *nlive = the live edges, *fingerprint =
+ * the replica's path fingerprint.  The hash kernel's grid honours "test_max_grid".  GK_E_INVALID for a null pointer. */
+int gk_test_edge_path_keys(gk_graph *g, uint64_t *h1, uint64_t *h2, uint32_t *canon, uint8_t *dup, uint64_t *nlive, uint64_t *fingerprint);
 
 /* TEST transport: the ranks are threads of ONE process on ONE device; sends, receives and reductions go through a hub in the
  * library (device-to-device copies matched pairwise in posting order) instead of RCCL, which refuses two ranks on one GPU.  Every
