@@ -20,12 +20,15 @@ main(k)    two reference records G0 (2400 bp) and G1 (1200 bp).  The reads are e
 variants   the reference with an N and a lowercase run inside c0a and one substituted base inside c3 (still one diagonal, fewer
            windows), and with one base deleted inside d1 (scattered)
 repeats(k) a genome with an exact repeat and an inverted repeat longer than k: a scattered and a both_strands edge
+long_record(k)  one record of 3 T + 700 bases, T = 4096 window starts being one workgroup's tile of the placement pass, with
+           contigs on and around every tile boundary (long_coords), long_marks: invalid characters on, just before and k - 1
+           after a boundary, long_truncations: records that end at the first boundary
 """
 import random
 
 from overlaps_cases import rand, rc, tile  # noqa: F401
 
-KS = (21, 31, 55)
+KS = (21, 31, 34, 55, 64)                                  # one word, a full word, the first two-word k, two words, the tagged table
 OVERLAP = 12
 GAP_C0B_C1, GAP_C2_C3, GAP_D0_D1 = 50, 60, 45
 LOWER = {"A": "a", "C": "c", "G": "g", "T": "t"}
@@ -96,6 +99,55 @@ def repeats(k, seed=None):
     R, Q = rand(rnd, k + 10), rand(rnd, k + 10)
     G = A + R + B + R + Cc + Q + D + rc(Q) + E
     return dict(reads=tile([G], k), records=[G], R=R, Q=Q)
+
+
+# ---- a record of several tiles ---------------------------------------------------------------------------------------------------
+T = 4096                                                   # window starts per workgroup of the placement pass
+LONG_LEN = 3 * T + 700
+LONG_KS = (31, 34, 64)
+
+
+def long_record(k, seed=None):
+    """-> dict(reads, record, paths={name: path}).  The contigs, by the record's coordinates (long_coords):
+      a     G[T - 300 : T + 300]          crosses the first boundary: its run of hits is cut by it
+      b     G[2T - 5 : 2T + 400]          crosses the second: its first windows start in the last k - 1 characters of a tile
+      e     G[3T - 400 : 3T + k]          ends at the k-mer at 3T, which a spur X + G[3T : 3T + k] enters a second way, so it is a node:
+      f     G[3T : 3T + k + 4]            e's last interior window starts at 3T - 1 and f's path starts at 3T.  The break between two
+                                          edges falls exactly on the third boundary (the first two lie inside a and b)
+      tail  G[3T + 10 : ]                 only the last, partly filled tile"""
+    rnd = random.Random(9500 + k if seed is None else seed)
+    G, X = rand(rnd, LONG_LEN), rand(rnd, 40)
+    if X[-1] == G[3 * T - 1]:                              # the spur must enter the k-mer at 3T by another base than the record does
+        X = X[:-1] + OTHER[X[-1]]
+    pieces = [G[T - 300:T + 300], G[2 * T - 5:2 * T + 400], G[3 * T - 400:3 * T + k + 4], X + G[3 * T:3 * T + k + 4], G[3 * T + 10:]]
+    paths = dict(a=pieces[0], b=pieces[1], e=G[3 * T - 400:3 * T + k], f=G[3 * T:3 * T + k + 4], tail=pieces[4], spur=X + G[3 * T:3 * T + k])
+    return dict(reads=tile(pieces, k), record=G, paths=paths)
+
+
+# where base 0 of each path of long_record lies on the record, forward; the twin lies at that coordinate + len(path) - 1, reverse
+def long_coords(k):
+    return dict(a=T - 300, b=2 * T - 5, e=3 * T - 400, f=3 * T, tail=3 * T + 10)
+
+
+def long_marked_at(k):
+    """the coordinates long_marks changes: an N, a lowercase base, a substituted base"""
+    return (T - 1, 2 * T, 2 * T + k - 2)
+
+
+def long_marks(record, k):
+    """an N at T - 1 (inside a), a lowercase base at 2T and a substituted base at 2T + k - 2 (inside b): on, just before and k - 1
+    after a tile boundary"""
+    g = list(record)
+    n_at, lower_at, subst_at = long_marked_at(k)
+    g[n_at] = "N"
+    g[lower_at] = LOWER[g[lower_at]]
+    g[subst_at] = OTHER[g[subst_at]]
+    return "".join(g)
+
+
+def long_truncations(record, k):
+    """the record cut to T - 1, T and T + 1 windows; at T windows the second workgroup holds k - 1 characters and no window"""
+    return [record[:T - 1 + k - 1], record[:T + k - 1], record[:T + k]]
 
 
 def fasta(records, width=70, names=None):

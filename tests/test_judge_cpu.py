@@ -158,6 +158,56 @@ def OR_find(edges3, path):
     return got[0]
 
 
+@pytest.mark.parametrize("k", JC.LONG_KS)
+def test_long_record_lies_where_it_is_built_to_lie(k):
+    """the inputs of the GPU tile tests: every contig of long_record on its own diagonal with every interior k-mer once, the break
+    between e and f on the third tile boundary, and the marks removing exactly the windows that contain a marked character"""
+    T = JC.T
+    case = JC.long_record(k)
+    rec = case["record"]
+    assert len(rec) == 3 * T + 700 and max(len(r) for r in case["reads"]) <= 200
+    edges3, nodes, edges = oracle_model(k, case["reads"])
+    find = lambda path: OR_find(edges3, path)
+    assert len(edges) == 12                                                      # the five contigs and the spur, on both strands
+    pst, placed = JR.place(k, nodes, edges, [rec])
+    JR.identities(pst=pst, live_edges=len(edges))
+    coords = JC.long_coords(k)
+    assert coords == dict(a=3796, b=8187, e=11888, f=12288, tail=12298)
+    for name, x in coords.items():
+        path = case["paths"][name]
+        n = len(path) - k - 1                                                    # a path's first and last k-mer are nodes
+        assert placed[find(path)] == ("forward", 0, x, n, 0), name
+        assert placed[find(JC.rc(path))] == ("reverse", 0, x + len(path) - 1, 0, n), name
+    assert placed[find(case["paths"]["spur"])][0] == "unplaced"
+    # by hand: a's interior windows start at T - 299 .. T + 299 - k, b's at 2T - 4 .. 2T + 399 - k, e's at 3T - 399 .. 3T - 1 (the last
+    # window start of the third tile), f's at 3T + 1 .. 3T + 3, the tail's at 3T + 11 .. the record's last window but one
+    assert [placed[find(case["paths"][n])][3] for n in ("a", "b", "e", "f", "tail")] == [599 - k, 404 - k, 399, 3, 689 - k]
+    assert pst["windows"] == 3 * T + 700 - k + 1 and pst["fwd_at_node"] == 9 and pst["forward"] == pst["reverse"] == 5 and pst["unplaced"] == 2
+    assert pst["fwd_edge"] == sum(v[3] for v in placed.values()) == 599 + 404 + 399 + 3 + 689 - 3 * k
+    # the marks: an N at T - 1 takes the k windows that start at T - k .. T - 1, all interior to a; a lowercase base at 2T and a
+    # substituted one at 2T + k - 2 take the windows 2T - k + 1 .. 2T + k - 2, of which 2T - 4 .. 2T + k - 2 are interior to b
+    marked = JC.long_marks(rec, k)
+    at = JC.long_marked_at(k)
+    assert at == (T - 1, 2 * T, 2 * T + k - 2) and [i for i in range(len(rec)) if rec[i] != marked[i]] == list(at)
+    assert marked[at[0]] == "N" and marked[at[1]] == rec[at[1]].lower() and marked[at[2]] in "AGCT"
+    mst, mplaced = JR.place(k, nodes, edges, [marked])
+    JR.identities(pst=mst, live_edges=len(edges))
+    for name, x in coords.items():
+        path = case["paths"][name]
+        lost = sum(any(w <= m < w + k for m in at) for w in range(x + 1, x + len(path) - k))
+        assert lost == dict(a=k, b=k + 3).get(name, 0)
+        assert mplaced[find(path)] == ("forward", 0, x, len(path) - k - 1 - lost, 0), name
+        assert mplaced[find(JC.rc(path))] == ("reverse", 0, x + len(path) - 1, 0, len(path) - k - 1 - lost), name
+    assert mst["valid_bases"] == mst["bases"] - 2 and mst["windows"] == pst["windows"] - 2 * k
+    assert mst["fwd_edge"] == pst["fwd_edge"] - (2 * k + 3) and mst["fwd_absent"] == pst["fwd_absent"] + 4 and mst["fwd_at_node"] == 8
+    # the truncations: T - 1, T and T + 1 windows, of which a's first 298, 299 and 300 interior ones (the one at T - 300 is a node)
+    for cut, windows in zip(JC.long_truncations(rec, k), (T - 1, T, T + 1)):
+        tst, tplaced = JR.place(k, nodes, edges, [cut])
+        assert len(cut) == windows + k - 1 and tst["windows"] == windows
+        assert tplaced[find(case["paths"]["a"])] == ("forward", 0, T - 300, windows - (T - 299), 0)
+        assert tst["forward"] == tst["reverse"] == 1 and tst["unplaced"] == 10
+
+
 @pytest.mark.parametrize("k", JC.KS)
 def test_repeats_give_scattered_and_both_strands(k):
     case = JC.repeats(k)

@@ -96,7 +96,7 @@ def graph_from(ctx, k, seqs, cap=0):
     return g
 
 
-@pytest.mark.parametrize("k", [15, 31, 41])
+@pytest.mark.parametrize("k", [15, 31, 34, 41, 64])
 def test_keys_match_the_restatement_and_replicas_agree(ctx, k):
     """A genome with repeats (a branching graph: edges of a few to a few hundred bases) built twice from tables of another
     capacity: every key bit-exact; equal fingerprints; the edge at every canonical place spells the same path on both; one
@@ -119,8 +119,9 @@ def test_keys_match_the_restatement_and_replicas_agree(ctx, k):
     a.close(); b.close()
 
 
-def test_constructed_paths(ctx):
-    k = 31
+@pytest.mark.parametrize("k", [31, 64])
+def test_constructed_paths(ctx, k):
+    """k = 64: the start k-mer fills both words of the key"""
     rnd = random.Random(2049)
     lens = [1, CHUNK_BASES - 1, CHUNK_BASES, CHUNK_BASES + 1, 2 * CHUNK_BASES - 1, 2 * CHUNK_BASES, 2 * CHUNK_BASES + 1, 66001]
     base = [rand_seq(rnd, k + n) for n in lens]

@@ -21,18 +21,18 @@ pytestmark = pytest.mark.gpu
 K, L_ = 35, 150
 
 
-def fixture():
-    A, Rp, B, Cc = pieces(K, K, [300, K + 60, 280, 310], lambda A, Rp, B, Cc: [A + Rp + B + Rp + Cc])
+def fixture(k=K):
+    A, Rp, B, Cc = pieces(k, k, [300, k + 60, 280, 310], lambda A, Rp, B, Cc: [A + Rp + B + Rp + Cc])
     gen = A + Rp + B + Rp + Cc
     reads = [gen[i:i + L_] for i in range(len(gen) - L_ + 1)]
     random.Random(5).shuffle(reads)                              # (contiguous shares would leave the spanning reads to one rank)
     return gen, reads
 
 
-def replica(c, reads, rank):
-    m = HipDNAMap(c, K, (1 << 15) * (rank + 1) if rank % 2 else 0)
+def replica(c, reads, rank, k=K):
+    m = HipDNAMap(c, k, (1 << 15) * (rank + 1) if rank % 2 else 0)
     m.count_reads(dna.reads_to_bin(reads), len(reads))
-    g = buildGraph(K, m)
+    g = buildGraph(k, m)
     m.close()
     g.simplifyGraph()
     return g
@@ -48,12 +48,21 @@ def thread_share(c, g, vm, reads, share):
 
 @pytest.mark.parametrize("world", [2, 3, 8])
 def test_sum_over_ranks_equals_one_rank(world):
-    gen, reads = fixture()
+    sum_over_ranks(world, K)
+
+
+def test_sum_over_two_ranks_on_the_tagged_table():
+    """k = 64: the spans come from threadSpans on the tagged table, the records travel by path keys whose start k-mer fills both words"""
+    sum_over_ranks(2, 64)
+
+
+def sum_over_ranks(world, k):
+    gen, reads = fixture(k)
     # (pair_shares leaves rank world // 2 without reads: with two ranks both get some, so that two ranks contribute)
     shares = pair_shares(len(reads), world) if world > 2 else [(0, len(reads) // 3), (len(reads) // 3, len(reads))]
 
     def body(rank, c, hd):
-        g = replica(c, reads, rank)
+        g = replica(c, reads, rank, k)
         vm = g.getGraphMap()
         whole = thread_share(c, g, vm, reads, (0, len(reads)))
         sp = thread_share(c, g, vm, reads, shares[rank])
