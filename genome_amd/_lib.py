@@ -246,7 +246,8 @@ TEST_SIGNATURES = {
     "gk_dist_create_loopback": (C.c_int, [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]),
     "gk_test_support_last_walk": (C.c_int, [vp, u64p, u64p]),
     "gk_test_grid_cap_uses": (C.c_int, [vp, u64p]),
-    "gk_test_part_plan": (C.c_int, [vp, vp]),          # (gk_test_part_in *, gk_test_part_out *: tests/test_part_plan_cpu.py)
+    "gk_test_prefilter_chunks": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+    "gk_test_part_plan": (C.c_int, [vp, vp]),         # (gk_test_part_in *, gk_test_part_out *: tests/test_part_plan_cpu.py)
     "gk_test_scan_counts": (C.c_int, [vp, u32p, C.c_uint64, C.c_int, u64p, u64p]),
     "gk_test_slot_ranks": (C.c_int, [vp, u64p, u64p, C.c_uint64, u64p, u64p]),
     "gk_test_edge_path_keys": (C.c_int, [vp, u64p, u64p, u32p, u8p, u64p, u64p]),

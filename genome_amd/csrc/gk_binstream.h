@@ -3,7 +3,8 @@
 //
 // Who feeds from here: gk_reads_correct and gk_graph_thread_reads.  Who does not, on purpose: gk_map_count_reads /
 // gk_dist_count_reads (map_cut_chunk: chunks bounded by windows too, possibly unwalked, prefetched) and the pre-filter
-// (pf_for_each_host_chunk: validates as it goes, one area).
+// (pf_for_each_host_chunk, gk_prefilter.hip: chunks bounded in bytes by "test_max_stage" and, in pass 2, in windows by
+// "test_prefilter_chunk_windows"; gk_test_prefilter_chunks echoes what it staged — include/genome_amd_test.h).
 #pragma once
 
 #include <algorithm>

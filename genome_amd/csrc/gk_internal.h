@@ -86,6 +86,7 @@ struct gk_ctx {
     mutable uint64_t hook_max_grid_uses = 0;   // ... and how many launches were sized under it (gk_test_grid_cap_uses: the switch's echo)
     int64_t hook_contigs_chunk = 0;  // test hook: text bytes per device chunk of gk_contigs_read / gk_contigs_write (0: 64 MiB)
     int64_t hook_place_slice = 0;    // test hook: characters per device slice of gk_placements_add_record (0: 64 Mi)
+    int64_t hook_pf_chunk_windows = 0;   // test hook: windows per pass-2 chunk of the singleton pre-filter (0: 2^28), host-fed and `_dev` alike
 };
 // most workgroups of a grid-stride launch: 8 resident 256-thread workgroups per CU, or what the test hook says
 inline uint64_t grid_cap(const gk_ctx *ctx) {
@@ -429,6 +430,10 @@ int map_ensure_sample(gk_map *m);                    // allocate the distinct-ke
 int map_make_room(gk_map *m, uint64_t new_distinct, uint64_t size_for, bool from_empty, bool keep_lnb1 = false);
 uint64_t part_max_slots(int W);                      // largest table the partitioned path can address
 int ctx_check_format(gk_ctx *ctx);                   // GK_E_FORMAT (and reset) if a map-less kernel raised ctx->d_flags[0]
+// what a pre-filter handle has run so far (gk_prefilter.hip; gk_test_prefilter_chunks echoes it): out[0] host chunks staged with a
+// fixed stride, out[1] host chunks staged with an offset table (either pass), out[2] pass-2 chunks of the `_dev` entry point,
+// out[3] launches of the pass-2 kernel
+void prefilter_chunk_counts(const gk_prefilter *pf, uint64_t out[4]);
 // super-k-mer routing in two halves (gk_skm.hip): launch on any stream without waiting, finish after that stream was synchronised
 constexpr int SKM_COUNT_WORDS = 2 * 64 + 1;
 int skm_route_launch(gk_ctx *ctx, hipStream_t st, unsigned long long *d_counts, unsigned long long *h_counts, int k, const void *dev_records,

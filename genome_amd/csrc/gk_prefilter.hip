@@ -38,6 +38,7 @@ struct gk_prefilter {
     u32 *d_offsets = nullptr;
     size_t offsets_bytes = 0;
     u64 windows_added = 0;
+    u64 chunks_fixed = 0, chunks_offsets = 0, chunks_dev = 0, select_launches = 0;   // what ran so far (prefilter_chunk_counts)
 };
 
 // bucket of a canonical k-mer: a second mix of the slot hash, so that the filter's collisions are
@@ -156,7 +157,7 @@ int pf_check(gk_prefilter *pf) { return pf && pf->ctx ? GK_OK : GK_E_INVALID; }
 int pf_launch_add(gk_prefilter *pf, const uint8_t *d_rec, u64 nreads, const u32 *d_off, u32 stride, int max_len = 255) {
     gk_ctx *ctx = pf->ctx;
     const u64 ntiles = (nreads + TILE_READS - 1) / TILE_READS;
-    const int grid = (int)std::min<u64>(std::max<u64>(ntiles, 1), (u64)ctx->cu_count * 8);
+    const int grid = (int)std::min<u64>(std::max<u64>(ntiles, 1), grid_cap(ctx));
     GK_BY_W(pf->W, hipLaunchKernelGGL(k_pf_add<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, d_rec, nreads, d_off, stride, pf->k, WindowLimits{max_len, ctx->d_flags}, pf->words, pf->nbuckets, pf->d_cursor + 1));
     GK_HIP(ctx, hipGetLastError());
     return GK_OK;
@@ -164,7 +165,7 @@ int pf_launch_add(gk_prefilter *pf, const uint8_t *d_rec, u64 nreads, const u32 
 
 // pass 2 for one chunk of records whose windows fit the key buffer; feeds the admitted keys to the table
 int pf_select_and_insert(gk_prefilter *pf, gk_map *m, const uint8_t *d_rec, u64 nreads, const u32 *d_off, u32 stride, u64 max_windows,
-                         u64 max_windows_per_read, u64 *admitted_total, int max_len = 255) {
+                         u64 max_windows_per_read, u64 *admitted_total, int max_len = 255, u64 *looked = nullptr /* cursor[1] after this chunk */) {
     gk_ctx *ctx = pf->ctx;
     if (pf->keybuf_keys < max_windows) {
         if (pf->keybuf) GK_HIP(ctx, pool_free(ctx, pf->keybuf));
@@ -178,7 +179,8 @@ int pf_select_and_insert(gk_prefilter *pf, gk_map *m, const uint8_t *d_rec, u64 
     const u64 per_read = std::max<u64>(1, max_windows_per_read);
     const int rs = (int)std::max<u64>(1, std::min<u64>(TILE_READS, (u64)PF_PARK_BYTES / (8ull * pf->W) / per_read));
     const u64 ntiles = (nreads + rs - 1) / rs;
-    const int grid = (int)std::min<u64>(std::max<u64>(ntiles, 1), (u64)ctx->cu_count * 8);
+    const int grid = (int)std::min<u64>(std::max<u64>(ntiles, 1), grid_cap(ctx));
+    pf->select_launches++;
     const size_t lds = (size_t)rs * per_read * 8 * pf->W;
     GK_BY_W(pf->W, hipLaunchKernelGGL(k_pf_select<W>, dim3(grid), dim3(BLOCK), lds, ctx->stream, d_rec, nreads, d_off, stride, pf->k, WindowLimits{max_len, ctx->d_flags}, rs, pf->words, pf->nbuckets,
                                       pf->keybuf, pf->keybuf_keys, pf->d_cursor, d_ovf));
@@ -187,6 +189,7 @@ int pf_select_and_insert(gk_prefilter *pf, gk_map *m, const uint8_t *d_rec, u64 
     if ((u32)h[2]) return fail(ctx, GK_E_CAPACITY, "prefilter: admitted keys exceed the key buffer (internal sizing error)");
     if (int rc = ctx_check_format(ctx)) return rc;
     *admitted_total += h[0];
+    if (looked) *looked = h[1];
     if (h[0]) { if (int rc = map_insert_keys_dev(m, pf->keybuf, h[0], false)) return rc; }     // canonical by construction
     return GK_OK;
 }
@@ -213,7 +216,7 @@ int pf_ensure_stage(gk_prefilter *pf, size_t bytes, size_t noffs) {
 template <class F>
 int pf_for_each_host_chunk(gk_prefilter *pf, const uint8_t *bin, size_t nbytes, u64 nreads, u64 max_windows, F f) {
     gk_ctx *ctx = pf->ctx;
-    const size_t MAX_STAGE = 256u << 20;
+    const size_t MAX_STAGE = ctx->hook_max_stage > 0 ? (size_t)ctx->hook_max_stage : (size_t)256 << 20;      // ("test_max_stage")
     size_t pos = 0;
     u64 r = 0;
     std::vector<u32> offs;
@@ -255,6 +258,7 @@ int pf_for_each_host_chunk(gk_prefilter *pf, const uint8_t *bin, size_t nbytes, 
         }
         if (!fast_prefix) offs.push_back((u32)(pos - chunk_begin));
         const size_t cbytes = pos - chunk_begin;
+        (fast_prefix ? pf->chunks_fixed : pf->chunks_offsets)++;
         if (int rc = pf_ensure_stage(pf, cbytes, std::max<size_t>(offs.size(), 1))) return rc;
         GK_HIP(ctx, hipMemcpyAsync(pf->d_stage, bin + chunk_begin, cbytes, hipMemcpyHostToDevice, ctx->stream));
         if (!fast_prefix) GK_HIP(ctx, hipMemcpyAsync(pf->d_offsets, offs.data(), offs.size() * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
@@ -265,8 +269,13 @@ int pf_for_each_host_chunk(gk_prefilter *pf, const uint8_t *bin, size_t nbytes, 
 }
 
 constexpr u64 PF_CHUNK_WINDOWS = 1ull << 28;     // pass-2 key buffer: at most 2 GiB (k <= 31) / 4 GiB of admitted keys
+u64 pf_chunk_windows(const gk_ctx *ctx) { return ctx->hook_pf_chunk_windows > 0 ? (u64)ctx->hook_pf_chunk_windows : PF_CHUNK_WINDOWS; }   // ("test_prefilter_chunk_windows")
 
 }  // namespace
+
+void gk::prefilter_chunk_counts(const gk_prefilter *pf, uint64_t out[4]) {
+    out[0] = pf->chunks_fixed; out[1] = pf->chunks_offsets; out[2] = pf->chunks_dev; out[3] = pf->select_launches;
+}
 
 extern "C" {
 
@@ -318,9 +327,13 @@ int gk_prefilter_add_reads_dev(gk_prefilter *pf, const void *dev_records, uint64
     if (read_len < 0 || read_len > 255) return fail(ctx, GK_E_FORMAT, "read_len must be 0..255 (one length byte per record)");
     GK_HIP(ctx, hipSetDevice(ctx->device));
     if (nreads == 0 || read_len < pf->k) return GK_OK;
+    // (a record may be shorter than read_len and then has fewer windows: the kernel's own count is the one that is added)
+    GK_HIP(ctx, hipMemsetAsync(pf->d_cursor + 1, 0, 8, ctx->stream));
     if (int rc = pf_launch_add(pf, (const uint8_t *)dev_records, nreads, nullptr, 1 + (read_len + 3) / 4, read_len)) return rc;
+    unsigned long long seen = 0;
+    GK_HIP(ctx, read_back(ctx, &seen, pf->d_cursor + 1));
     if (int rc = ctx_check_format(ctx)) return rc;
-    pf->windows_added += nreads * (u64)(read_len - pf->k + 1);
+    pf->windows_added += seen;
     return GK_OK;
 }
 
@@ -348,14 +361,15 @@ int gk_map_count_reads_prefiltered_dev(gk_map *m, gk_prefilter *pf, const void *
     if (nreads == 0 || read_len < pf->k) return GK_OK;
     const u32 stride = 1 + (read_len + 3) / 4;
     const u64 nk = (u64)(read_len - pf->k + 1);
-    const u64 chunk_reads = std::max<u64>(1, PF_CHUNK_WINDOWS / nk);
+    const u64 chunk_reads = std::max<u64>(1, pf_chunk_windows(ctx) / nk);
     GK_HIP(ctx, hipMemsetAsync(pf->d_cursor + 1, 0, 8, ctx->stream));
-    u64 adm = 0;
+    u64 adm = 0, looked = 0;          // (looked: the kernels' count, summed over the chunks on the device; records may be shorter than read_len)
     for (u64 done = 0; done < nreads; done += chunk_reads) {
         const u64 n = std::min(chunk_reads, nreads - done);
-        if (int rc = pf_select_and_insert(pf, m, (const uint8_t *)dev_records + done * stride, n, nullptr, stride, n * nk, nk, &adm, read_len)) return rc;
+        pf->chunks_dev++;
+        if (int rc = pf_select_and_insert(pf, m, (const uint8_t *)dev_records + done * stride, n, nullptr, stride, n * nk, nk, &adm, read_len, &looked)) return rc;
     }
-    if (occurrences) *occurrences = nreads * nk;
+    if (occurrences) *occurrences = looked;
     if (admitted) *admitted = adm;
     return GK_OK;
 }
@@ -370,7 +384,7 @@ int gk_map_count_reads_prefiltered(gk_map *m, gk_prefilter *pf, const uint8_t *b
     if (!bin && nreads) return fail(ctx, GK_E_INVALID, "gk_map_count_reads_prefiltered: null stream");
     GK_HIP(ctx, hipSetDevice(ctx->device));
     u64 adm = 0, occ_total = 0;
-    int rc = pf_for_each_host_chunk(pf, bin, nbytes, nreads, PF_CHUNK_WINDOWS, [&](const uint8_t *d_rec, u64 n, const u32 *d_off, u32 stride, u64 occ) {
+    int rc = pf_for_each_host_chunk(pf, bin, nbytes, nreads, pf_chunk_windows(ctx), [&](const uint8_t *d_rec, u64 n, const u32 *d_off, u32 stride, u64 occ) {
         occ_total += occ;
         const u64 per_read = stride ? occ / std::max<u64>(n, 1) : (u64)std::max(1, 255 - pf->k + 1);
         return occ ? pf_select_and_insert(pf, m, d_rec, n, d_off, stride, occ, per_read, &adm) : GK_OK;
@@ -386,7 +400,7 @@ int gk_prefilter_stats(gk_prefilter *pf, uint64_t *buckets, uint64_t *seen_once,
     gk_ctx *ctx = pf->ctx;
     GK_HIP(ctx, hipSetDevice(ctx->device));
     GK_HIP(ctx, hipMemsetAsync(pf->d_cursor + 2, 0, 16, ctx->stream));
-    const int grid = (int)std::min<u64>(std::max<u64>((pf->nwords + BLOCK - 1) / BLOCK, 1), (u64)ctx->cu_count * 8);
+    const int grid = (int)std::min<u64>(std::max<u64>((pf->nwords + BLOCK - 1) / BLOCK, 1), grid_cap(ctx));
     hipLaunchKernelGGL(k_pf_stats, dim3(grid), dim3(BLOCK), 0, ctx->stream, pf->words, pf->nwords, pf->d_cursor + 2);
     unsigned long long h[2] = {0, 0};
     GK_HIP(ctx, read_back(ctx, h, pf->d_cursor + 2, 2));

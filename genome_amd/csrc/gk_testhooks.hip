@@ -2,6 +2,7 @@
 //   * gk_ctx_set_option and the environment switches read at gk_ctx_create: A/B switches of the kernels, test hooks that stage
 //     the large-table paths on small tables or inject failures;
 //   * gk_test_grid_cap_uses: how many launches "test_max_grid" has sized on a context (the switch's echo);
+//   * gk_test_prefilter_chunks: the chunks a singleton pre-filter handle has staged and run ("test_max_stage" / "test_prefilter_chunk_windows"' echo);
 //   * gk_test_part_plan: what the partitioned insert would choose for a table geometry and a set of switches (part_choose's echo, no device);
 //   * gk_test_support_last_walk: which walker (device kernel / host fallback) did the orientations of the last gk_graph_walk_pairs;
 //   * gk_test_scan_counts: gk_scan.h's scan_counts over counts from the host, between guard words (either overload);
@@ -93,6 +94,7 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
         ctx->hook_max_grid = (int)std::min<int64_t>(value, 1 << 30);
     }
     else if (n == "test_place_slice") ctx->hook_place_slice = (int64_t)std::max<int64_t>(0, value);
+    else if (n == "test_prefilter_chunk_windows") ctx->hook_pf_chunk_windows = (int64_t)std::max<int64_t>(0, value);
     else if (n == "contigs_chunk_bytes") ctx->hook_contigs_chunk = (int64_t)std::max<int64_t>(0, value);
     else if (n == "fine_exact") ctx->hook_fine_exact = value < 0 ? -1 : value != 0;
     else return fail(ctx, GK_E_INVALID, "gk_ctx_set_option: unknown option '" + n + "'");
@@ -102,6 +104,17 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
 int gk_test_grid_cap_uses(const gk_ctx *ctx, uint64_t *uses) {
     if (!ctx || !uses) return fail(ctx, GK_E_INVALID, "gk_test_grid_cap_uses: null argument");
     *uses = ctx->hook_max_grid_uses;
+    return GK_OK;
+}
+
+int gk_test_prefilter_chunks(const gk_prefilter *pf, uint64_t *host_fixed, uint64_t *host_offsets, uint64_t *dev_pass2, uint64_t *pass2_launches) {
+    if (!pf) return fail(nullptr, GK_E_INVALID, "gk_test_prefilter_chunks: null filter handle");
+    uint64_t c[4];
+    prefilter_chunk_counts(pf, c);
+    if (host_fixed) *host_fixed = c[0];
+    if (host_offsets) *host_offsets = c[1];
+    if (dev_pass2) *dev_pass2 = c[2];
+    if (pass2_launches) *pass2_launches = c[3];
     return GK_OK;
 }
 

@@ -24,7 +24,8 @@ class HipPrefilter:
 
     def close(self):
         if getattr(self, "h", None):
-            L.lib().gk_prefilter_destroy(self.h)
+            if self.ctx.h:               # (a handle that outlived its context — a failed test's traceback — is dropped, not followed)
+                L.lib().gk_prefilter_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -58,6 +59,13 @@ class HipPrefilter:
         occ, adm = C.c_uint64(), C.c_uint64()
         L.check(L.lib().gk_map_count_reads_prefiltered_dev(m.h, self.h, d_records, nreads, read_len, C.byref(occ), C.byref(adm)), self.ctx.h)
         return occ.value, adm.value
+
+    def chunks(self) -> dict:
+        """What this handle has staged and run so far (a test hook: GkError on the product library): host chunks with a fixed
+        stride / with an offset table, pass-2 chunks of count_reads_dev, launches of the pass-2 kernel."""
+        f, o, d, s = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        L.check(L.test_hook("gk_test_prefilter_chunks")(self.h, C.byref(f), C.byref(o), C.byref(d), C.byref(s)), self.ctx.h)
+        return {"host_fixed": f.value, "host_offsets": o.value, "dev_pass2": d.value, "pass2_launches": s.value}
 
     def stats(self) -> dict:
         b, o, t, w = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()

@@ -1164,7 +1164,11 @@ int gk_prefilter_create(gk_ctx *ctx, int k, uint64_t expected_distinct, gk_prefi
 void gk_prefilter_destroy(gk_prefilter *pf);
 int gk_prefilter_add_reads(gk_prefilter *pf, const uint8_t *bin_host, size_t nbytes, uint64_t nreads);
 int gk_prefilter_add_reads_dev(gk_prefilter *pf, const void *dev_records, uint64_t nreads, int read_len);
-/* *occurrences = windows looked at, *admitted = windows inserted (either may be NULL) */
+/* *occurrences = windows looked at, *admitted = windows inserted (either may be NULL).
+ * The `_dev` forms take records of one stride, 1 + (read_len + 3) / 4 bytes.  A record whose length byte is below read_len is
+ * legal: it contributes its own len - k + 1 windows (none if len < k), and *occurrences and windows_added count those, not
+ * nreads x (read_len - k + 1).  A length byte above read_len is GK_E_FORMAT from either `_dev` call (the kernels clamp it, nothing
+ * is read past the record); the filter or table may by then hold part of the call's windows, the context stays usable. */
 int gk_map_count_reads_prefiltered(gk_map *m, gk_prefilter *pf, const uint8_t *bin_host, size_t nbytes, uint64_t nreads,
                                    uint64_t *occurrences, uint64_t *admitted);
 int gk_map_count_reads_prefiltered_dev(gk_map *m, gk_prefilter *pf, const void *dev_records, uint64_t nreads, int read_len,
