@@ -458,7 +458,16 @@ int gk_graph_classified_by_owners(gk_graph *g, int *flag);
 /* Graph.getGraphMap (Graph.scala:90-119): putNew of every node's k-mer -> NodeGraphPosition(node id) and of the k-mers at
  * distance 1 .. len-1 along every edge -> EdgeGraphPosition(edge id, dist) into `vm` (same k, same context).  *entries =
  * number of entries added = sum of edge lengths + nodes - edges (the reference prints both side by side, :117; here the
- * equality is checked). */
+ * equality is checked).
+ * How many positions a k-mer has.  On a graph as gk_graph_build leaves it every k-mer lies on one node or at one distance of one
+ * edge, so getAll gives one position or none, palindromes included: a k-mer that is its own reverse complement is either a node
+ * (one node, which is its own twin) or the centre window of an edge that is its own twin (P(e) = its reverse complement), at
+ * distance len / 2, once; it is not entered a second time for the other strand.  Two or more positions come from edits alone:
+ * the node copies of gk_graph_split_by_support and the edge and node copies of gk_graph_split_edges_by_spans share their k-mers.
+ * So the classes that need a list of two (`repeated` of gk_graph_thread_reads, `ambiguous` and `repetitive` of
+ * gk_graph_pair_distances, `repetitive` of gk_graph_pair_links and of the placements) are empty on a fresh graph, whatever it
+ * folds back on; and a pair whose two mates lie on one edge, a self-twin edge or a self-loop included, is `same_edge` for
+ * gk_graph_pair_links: the table never holds a link (e, e). */
 int gk_graph_position_map(gk_graph *g, gk_vmap *vm, uint64_t *entries);
 /* Ids.  Node and edge ids are array indices (arbitrary, like the reference's AtomicLong ids; stable for a graph's lifetime).
  * gk_graph_node_lookup: the live node with this k-mer (smallest id if a node split left several) and, for base in 0..3, the id
