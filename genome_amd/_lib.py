@@ -228,6 +228,15 @@ SIGNATURES = {
     "gk_placements_edges": (C.c_int, [vp, u32p, C.c_uint64, u8p, u32p, i64p, u32p, u32p]),
     "gk_placements_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "gk_scaffolds_judge": (C.c_int, [vp, vp, C.c_uint64, u8p, i64p, C.c_uint64, u64p, u64p]),
+    "gk_blocks_create": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "gk_blocks_destroy": (None, [vp]),
+    "gk_blocks_add_record": (C.c_int, [vp, vp, C.c_uint64]),
+    "gk_blocks_finish": (C.c_int, [vp, C.c_uint64]),
+    "gk_blocks_stats": (C.c_int, [vp, u64p]),
+    "gk_blocks_rows": (C.c_int, [vp, u32p, u8p, u32p, i64p, u32p, u32p, u8p, i64p, C.c_uint64, u64p]),
+    "gk_blocks_edges": (C.c_int, [vp, u32p, C.c_uint64, u8p, u8p, u32p, u32p]),
+    "gk_blocks_pieces": (C.c_int, [vp, u64p, u32p, C.c_uint64, u64p]),
+    "gk_blocks_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "gk_graph_contig_stats": (C.c_int, [vp, C.c_uint64, u64p, u64p, u64p, u64p, u64p]),
     "gk_synth_reads_dev": (C.c_int, [vp, vp, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
     "gk_prefilter_create": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp)]),

@@ -150,6 +150,26 @@ def judge_scaffolds(graph, fasta, scaffolds, tol: int) -> dict:
     return out
 
 
+def align_contigs(graph, fasta, tol: int = 1000) -> dict:
+    """The alignment blocks of a graph against a reference FASTA (a path, `.gz` read with the standard library, or its bytes), with a
+    position map of the graph as it is -> {"k", "tol", "stats", "rows", "edges", "pieces", "genome_fraction", "na50", "nga50"}.
+    `tol` is a choice, not a measurement."""
+    if isinstance(fasta, (str, os.PathLike)):
+        text = b"".join(bytes(piece) for piece, _ in iter_pieces(fasta, 256 << 20))
+    else:
+        text = bytes(fasta)
+    vm = graph.getGraphMap()
+    try:
+        with graph.alignBlocks(vm, fasta_records(text), tol) as b:
+            st = b.stats()
+            out = {"k": graph.k, "tol": int(tol), "stats": st, "rows": b.rows(), "edges": b.edges(), "pieces": b.pieces()}
+            out["genome_fraction"] = st["covered"] / st["windows"] if st["windows"] else 0.0
+            out.update(b.na50())
+    finally:
+        vm.close()
+    return out
+
+
 def check_graph(graph, fasta, longer_than: int = 200, per_line: bool = False, max_missing: int = 0, piece_bytes: int = 256 << 20) -> dict:
     """CheckGraph.startup for a graph and a FASTA file (a path, `.gz` read with the standard library) or its bytes: one dict with
     k, the contig statistics (:37-41), the check's counters (:48-55), the coverage and, with max_missing, the missing list."""

@@ -271,6 +271,23 @@ class HipGraph:
             raise
         return p
 
+    def alignBlocks(self, positions, records=(), tol=None) -> "Blocks":
+        """Every edge aligned to a reference genome in blocks (include/genome_amd.h, "alignment blocks" and "breakpoints"):
+        `positions` getGraphMap of this graph as it is now; `records` as for place(), fed at once; with `tol` the result is
+        finished too.  -> a Blocks: add_record(), finish(tol), stats(), rows(), edges(), pieces(), na50()."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        b = Blocks(self, positions)
+        try:
+            for r in records:
+                b.add_record(r)
+            if tol is not None:
+                b.finish(tol)
+        except Exception:
+            b.close()
+            raise
+        return b
+
     # ---- overlap detection (this project's own rule: include/genome_amd.h) ---------------------------------------------
     def overlapGaps(self, chains, gaps, tol: int, min_overlap: int = 10, max_overlap=None):
         """Between fillGaps (or scaffoldChains / scaffoldGaps) and scaffolds(): where the last o bases of a member's path equal the
@@ -723,6 +740,125 @@ class Placements:
         arr = (C.c_float * 4)()
         L.check(L.lib().gk_placements_last_ms(self.h, arr), self.ctx.h)
         return {"upload": float(arr[0]), "lookup_kernels": float(arr[2]), "total": float(arr[3])}
+
+
+# the names of the GK_BREAK_* breakpoint classes and of the GK_BLOCKS_* edge classes, by code; gk_blocks_stats in the order of its array
+BLOCK_BREAKS = ("first", "overlap", "translocation", "inversion", "relocation", "indel", "colinear")
+BLOCK_CLASSES = ("unaligned", "repeat", "misassembled", "indel", "colinear", "exact")
+BLOCK_STATS = (("records", "bases", "valid_bases", "windows", "covered", "rows") + tuple("brk_" + b for b in BLOCK_BREAKS[1:])
+               + tuple("edges_" + c for c in BLOCK_CLASSES)
+               + ("full_edges", "aligned_kmers", "pieces", "piece_bases", "indel_shift_sum", "indel_shift_max"))
+
+
+def _nx50(lengths, total: int) -> int:
+    run = 0
+    for x in sorted((int(v) for v in lengths), reverse=True):
+        run += x
+        if 2 * run >= total:
+            return x
+    return 0
+
+
+class Blocks:
+    """Every edge of a graph aligned to a reference genome as exact runs, and the breakpoints between them (include/genome_amd.h,
+    "alignment blocks" and "breakpoints").  Feed the records, finish(tol) once or several times, then read.  Holds its graph and
+    position map; stale (GkError GK_E_STATE) once the graph has been edited."""
+
+    def __init__(self, graph: HipGraph, positions):
+        self.graph, self.ctx, self.positions = graph, graph.ctx, positions
+        h = L.vp()
+        L.check(L.lib().gk_blocks_create(graph.h, positions.h, C.byref(h)), self.ctx.h)
+        self.h = h
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:               # (see HipDNAMap.close)
+                L.lib().gk_blocks_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h or not self.ctx.h or not self.graph.h:
+            raise L.GkError(L.GK_E_STATE, "the blocks or their graph are closed")
+
+    def add_record(self, record):
+        """the next reference record: its joined sequence characters (str or bytes)"""
+        self._live()
+        b = record.encode("latin-1") if isinstance(record, str) else bytes(record)
+        L.check(L.lib().gk_blocks_add_record(self.h, b, len(b)), self.ctx.h)
+
+    def finish(self, tol: int):
+        """order the rows, class every breakpoint and edge, cut the pieces; again with another tol without feeding again"""
+        self._live()
+        L.check(L.lib().gk_blocks_finish(self.h, int(tol)), self.ctx.h)
+        return self
+
+    def stats(self) -> dict:
+        self._live()
+        st = np.zeros(len(BLOCK_STATS), np.uint64)
+        L.check(L.lib().gk_blocks_stats(self.h, L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(BLOCK_STATS, (int(x) for x in st)))
+
+    def rows(self) -> list:
+        """[(edge, strand, record, pos, dlo, dhi, brk, shift)] in the rule's order; brk is the class code (BLOCK_BREAKS)"""
+        self._live()
+        n = C.c_uint64()
+        rc = L.lib().gk_blocks_rows(self.h, None, None, None, None, None, None, None, None, 0, C.byref(n))
+        if rc != L.GK_E_CAPACITY:
+            L.check(rc, self.ctx.h)
+        m = n.value
+        a = [np.zeros(max(m, 1), t) for t in (np.uint32, np.uint8, np.uint32, np.int64, np.uint32, np.uint32, np.uint8, np.int64)]
+        ct = (C.c_uint32, C.c_uint8, C.c_uint32, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint8, C.c_int64)
+        L.check(L.lib().gk_blocks_rows(self.h, *[L.ptr(x, t) for x, t in zip(a, ct)], m, C.byref(n)), self.ctx.h)
+        return list(zip(*[x[:m].tolist() for x in a]))
+
+    def edges(self, edge_ids=None) -> dict:
+        """per id asked for (default: every id below the bound): {"cls": class names (BLOCK_CLASSES), "full", "first_row", "nrows"}"""
+        self._live()
+        ids = np.arange(self.graph.idBounds()[1], dtype=np.uint32) if edge_ids is None else np.ascontiguousarray(edge_ids, np.uint32)
+        n = len(ids)
+        cls, full, first, nrows = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        L.check(L.lib().gk_blocks_edges(self.h, L.ptr(ids, C.c_uint32), n, L.ptr(cls, C.c_uint8), L.ptr(full, C.c_uint8), L.ptr(first, C.c_uint32),
+                                        L.ptr(nrows, C.c_uint32)), self.ctx.h)
+        return {"cls": [BLOCK_CLASSES[x] for x in cls], "full": full.tolist(), "first_row": first.tolist(), "nrows": nrows.tolist()}
+
+    def pieces(self) -> list:
+        """[(bases, edge)] in row order"""
+        self._live()
+        n = C.c_uint64()
+        rc = L.lib().gk_blocks_pieces(self.h, None, None, 0, C.byref(n))
+        if rc != L.GK_E_CAPACITY:
+            L.check(rc, self.ctx.h)
+        m = n.value
+        ln, ed = np.zeros(max(m, 1), np.uint64), np.zeros(max(m, 1), np.uint32)
+        L.check(L.lib().gk_blocks_pieces(self.h, L.ptr(ln, C.c_uint64), L.ptr(ed, C.c_uint32), m, C.byref(n)), self.ctx.h)
+        return list(zip(ln[:m].tolist(), ed[:m].tolist()))
+
+    def na50(self) -> dict:
+        """{"na50": against the piece bases, "nga50": against the valid bases of the reference (0 if the pieces never reach half)}"""
+        st = self.stats()
+        lens = [p[0] for p in self.pieces()]
+        return {"na50": _nx50(lens, st["piece_bases"]), "nga50": _nx50(lens, st["valid_bases"])}
+
+    def last_ms(self) -> dict:
+        """wall ms of the last record added (host staging + upload, count launches, emit launches, the whole call) and of the last
+        finish (device time, the whole call)"""
+        arr = (C.c_float * 6)()
+        L.check(L.lib().gk_blocks_last_ms(self.h, arr), self.ctx.h)
+        return dict(zip(("upload", "count_kernels", "emit_kernels", "total", "finish_kernels", "finish_total"), (float(x) for x in arr)))
 
 
 def scaffoldGaps(chains, joins, mid: int):

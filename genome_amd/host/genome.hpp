@@ -698,6 +698,81 @@ class Placements {
     gk_placements *h_ = nullptr;
 };
 
+// gk_blocks: every edge of a graph aligned to a reference genome as exact runs, and the breakpoints between them (Graph::alignBlocks;
+// the rules: include/genome_amd.h, "alignment blocks" and "breakpoints").  Feed the records, finish(tol) once or several times,
+// then read.  Holds neither the graph nor the position map: both must outlive it, and an edit of the graph makes it stale.
+class Blocks {
+  public:
+    static constexpr const char *statNames[GK_BLOCKS_NSTATS] = {"records", "bases", "valid_bases", "windows", "covered", "rows", "brk_overlap", "brk_translocation",
+                                                                "brk_inversion", "brk_relocation", "brk_indel", "brk_colinear", "edges_unaligned", "edges_repeat",
+                                                                "edges_misassembled", "edges_indel", "edges_colinear", "edges_exact", "full_edges", "aligned_kmers",
+                                                                "pieces", "piece_bases", "indel_shift_sum", "indel_shift_max"};
+    struct Stats { uint64_t v[GK_BLOCKS_NSTATS] = {}; };
+    struct Rows { std::vector<uint32_t> edge; std::vector<uint8_t> strand; std::vector<uint32_t> record; std::vector<int64_t> pos; std::vector<uint32_t> dlo, dhi;
+                  std::vector<uint8_t> brk; std::vector<int64_t> shift; };
+    struct Edges { std::vector<uint8_t> cls, full; std::vector<uint32_t> firstRow, nrows; };
+    struct Pieces { std::vector<uint64_t> len; std::vector<uint32_t> edge; };
+    Blocks(gk_ctx *ctx, gk_graph *g, gk_vmap *positions) : ctx_(ctx) { check(gk_blocks_create(g, positions, &h_), ctx_); }
+    ~Blocks() { close(); }
+    void close() { gk_blocks_destroy(h_); h_ = nullptr; }
+    Blocks(Blocks &&o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    Blocks(const Blocks &) = delete;
+    Blocks &operator=(const Blocks &) = delete;
+    gk_blocks *handle() const { return h_; }
+    // the next reference record: its joined sequence characters
+    void addRecord(const std::string &record) { check(gk_blocks_add_record(h_, record.data(), record.size()), ctx_); }
+    // order the rows, class every breakpoint and edge, cut the pieces; again with another tol without feeding again
+    void finish(uint64_t tol) { check(gk_blocks_finish(h_, tol), ctx_); }
+    Stats stats() const {
+        Stats st;
+        check(gk_blocks_stats(h_, st.v), ctx_);
+        return st;
+    }
+    Rows rows() const {
+        Rows r;
+        const size_t n = (size_t)stats().v[5];
+        uint64_t got = 0;
+        r.edge.resize(n); r.strand.resize(n); r.record.resize(n); r.pos.resize(n); r.dlo.resize(n); r.dhi.resize(n); r.brk.resize(n); r.shift.resize(n);
+        check(gk_blocks_rows(h_, r.edge.data(), r.strand.data(), r.record.data(), r.pos.data(), r.dlo.data(), r.dhi.data(), r.brk.data(), r.shift.data(), n, &got), ctx_);
+        return r;
+    }
+    Edges edges(const std::vector<uint32_t> &ids) const {
+        Edges e;
+        const size_t n = ids.size();
+        e.cls.resize(n); e.full.resize(n); e.firstRow.resize(n); e.nrows.resize(n);
+        check(gk_blocks_edges(h_, ids.data(), n, e.cls.data(), e.full.data(), e.firstRow.data(), e.nrows.data()), ctx_);
+        return e;
+    }
+    Pieces pieces() const {
+        Pieces p;
+        const size_t n = (size_t)stats().v[20];
+        uint64_t got = 0;
+        p.len.resize(n); p.edge.resize(n);
+        check(gk_blocks_pieces(h_, p.len.data(), p.edge.data(), n, &got), ctx_);
+        return p;
+    }
+    // lengths descending, the first at which twice the running sum reaches `total`; 0 for none
+    static uint64_t nx50(std::vector<uint64_t> lengths, uint64_t total) {
+        std::sort(lengths.rbegin(), lengths.rend());
+        uint64_t run = 0;
+        for (const uint64_t x : lengths) {
+            run += x;
+            if (2 * run >= total) return x;
+        }
+        return 0;
+    }
+    // NA50 against the piece bases, NGA50 against the valid bases of the reference
+    std::pair<uint64_t, uint64_t> na50() const {
+        const Stats st = stats();
+        const Pieces p = pieces();
+        return {nx50(p.len, st.v[21]), nx50(p.len, st.v[2])};
+    }
+
+  private:
+    gk_ctx *ctx_ = nullptr;
+    gk_blocks *h_ = nullptr;
+};
+
 // gk_scaffolds: a plan of the FASTA text of a graph's scaffolds (Graph::scaffolds; the rule: include/genome_amd.h, "scaffolds").
 // As Contigs: the device emits the text when it is read or written, and an edit of the graph makes the plan stale.
 class Scaffolds {
@@ -853,6 +928,14 @@ class Graph {
         Placements p(ctx_.handle(), h_, positions.handle());
         for (const std::string &r : records) p.add(r);
         return p;
+    }
+    // Every edge aligned to a reference genome in blocks (include/genome_amd.h, "alignment blocks" and "breakpoints"): the records
+    // are fed and the result finished at `tol`; Blocks::finish may be called again with another.
+    Blocks alignBlocks(PositionMap &positions, const std::vector<std::string> &records, uint64_t tol) const {
+        Blocks b(ctx_.handle(), h_, positions.handle());
+        for (const std::string &r : records) b.addRecord(r);
+        b.finish(tol);
+        return b;
     }
     // GraphSimplifier.scala:213-247: the pairs' positions, annotate, the bounded walks -> support counts
     void walkPairs(PositionMap &positions, Support &support, const PairedEndData &data, uint64_t takeFirst, int rangeLo = 180, int rangeHi = 250) {

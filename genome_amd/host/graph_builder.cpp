@@ -5,7 +5,7 @@
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
 //                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]]
-//                 [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N]]]   (with --walk-pairs: graph_simplifier.cpp says what they write)
+//                 [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N] [--block-rows PATH]]]]   (with --walk-pairs: graph_simplifier.cpp says what they write)
 //                 [--out prefix] [--save-graph PATH] [--correct N|auto]
 //                 [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
@@ -66,7 +66,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N]]] [--out prefix] [--save-graph PATH] "
+                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--out prefix] [--save-graph PATH] "
                              "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
@@ -228,6 +228,7 @@ int main(int argc, char **argv) {
             if (!lr.overlapJson.empty()) jsonPut(js, "overlap", lr.overlapJson);
             if (!lr.scaffoldsJson.empty()) jsonPut(js, "scaffolds", lr.scaffoldsJson);
             if (!lr.judgeJson.empty()) jsonPut(js, "judge", lr.judgeJson);
+            if (!lr.blocksJson.empty()) jsonPut(js, "blocks", lr.blocksJson);
         }
         if (!contig.path.empty()) jsonPut(js, "contigs_fasta", fasta.json());
         jsonPut(js, "components_histogram", jsonPairs(hist), "components_histogram_2", jsonPairs(hist2));   // GraphBuilder.scala:42, :47

@@ -6,7 +6,7 @@
 //   graph_simplifier <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]]
 //                    [--take-first N] [--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]]
 //                    [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
-//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N]]]
+//                    [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N] [--block-rows PATH]]]]
 //                    [--world W --rank R --id-file PATH]
 //   graph_simplifier <graph.gkg> --fastq <reads.fastq> --cutoff C [--split N | --interleaved] [the options above but --world]
 //   --fastq converts the FASTQ file on the GPU (Convert2bin, gk_fastq) and takes the pair count from the conversion.
@@ -68,6 +68,10 @@
 //   choice, not a measurement.  stderr gets one line; the JSON gains "judge":{tol, "placements":{the twenty stats}, "stats":{the
 //   twenty-nine stats}, "classes", "err" per junction, n50, n50_broken: the scaffold N50 as written and after breaking every chain
 //   record at each misjoin}.
+//   --blocks [--block-tol N] [--block-rows PATH] (with --judge) aligns the edges of the final graph to the same reference in blocks
+//   and classes every breakpoint (include/genome_amd.h, "alignment blocks" and "breakpoints").  N defaults to 1000: a choice, not a
+//   measurement.  stderr gets one line; the JSON gains "blocks":{tol, "stats":{the twenty-four stats}, genome_fraction, na50, nga50};
+//   PATH gets one text line per row.
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
 //   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
 //   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
@@ -86,7 +90,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
                              "[--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
-                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N]]] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -164,6 +168,7 @@ int main(int argc, char **argv) {
             if (!lr.overlapJson.empty()) jsonPut(js, "overlap", lr.overlapJson);
             if (!lr.scaffoldsJson.empty()) jsonPut(js, "scaffolds", lr.scaffoldsJson);
             if (!lr.judgeJson.empty()) jsonPut(js, "judge", lr.judgeJson);
+            if (!lr.blocksJson.empty()) jsonPut(js, "blocks", lr.blocksJson);
         }
         if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");
         if (stage.resolve) jsonPut(js, "resolve_repeats", res.resolveJson(stage.spanCutoff()));

@@ -303,6 +303,26 @@ inline PairedResult pairedStage(genome::Graph &graph, genome::Context &ctx, geno
 // text) with the links' position map, and every junction of the plan that was written is judged (include/genome_amd.h,
 // "placements" and "the judge").  N defaults to the fill / overlap TOL, half the width of the insert range: a choice, not a
 // measurement.
+// --blocks [--block-tol N] [--block-rows PATH]: the edges of the graph aligned to the reference in blocks and every breakpoint classed
+// (include/genome_amd.h, "alignment blocks" and "breakpoints").  N defaults to 1000: a choice, not a measurement.  PATH gets one
+// text line per row.  check_graph takes them beside its FASTA; graph_simplifier and graph_builder --walk-pairs beside --judge, whose
+// FASTA they read.
+struct BlockOpts {
+    bool blocks = false;
+    int64_t tol = -1;                             // -1: 1000; a choice, not a measurement
+    std::string rows;
+    bool parse(Args &a) {
+        if (a.flag("--blocks")) { blocks = true; return true; }
+        return a.value("--block-tol", tol) || a.value("--block-rows", rows);
+    }
+    bool check() const {
+        if (!blocks && tol != -1) { std::fprintf(stderr, "--block-tol N goes with --blocks\n"); return false; }
+        if (!blocks && !rows.empty()) { std::fprintf(stderr, "--block-rows PATH goes with --blocks\n"); return false; }
+        if (tol < -1) { std::fprintf(stderr, "--block-tol N needs N >= 0\n"); return false; }
+        return true;
+    }
+    uint64_t tolerance() const { return tol >= 0 ? (uint64_t)tol : 1000; }
+};
 struct LinkOpts {
     std::string path, scaffolds, scaffoldFasta;
     uint32_t minSupport = 3;
@@ -318,7 +338,9 @@ struct LinkOpts {
     uint32_t overlapMin = 10, overlapMax = 0;     // 0: k.  Choices, not measurements: a chance match of 10 bases is about 1e-6 per candidate
     std::string judge;                            // --judge: the reference FASTA
     int64_t judgeTol = -1;                        // -1: as fillTol; a choice, not a measurement
+    BlockOpts block;                              // --blocks [--block-tol N] [--block-rows PATH], beside --judge
     bool parse(Args &a) {
+        if (block.parse(a)) return true;
         if (a.flag("--scaffold-both-strands")) { scaffoldBoth = true; return true; }
         if (a.optional("--fill-gaps", fillTol)) { fillGaps = true; return true; }
         if (a.value("--fill-max-edges", fillMaxEdges) || a.value("--fill-max-paths", fillMaxPaths)) return true;
@@ -337,6 +359,8 @@ struct LinkOpts {
         if (!judge.empty() && scaffoldFasta.empty()) { std::fprintf(stderr, "--judge GENOME.fasta goes with --scaffold-fasta PATH\n"); return false; }
         if (judge.empty() && judgeTol != -1) { std::fprintf(stderr, "--judge-tol N goes with --judge GENOME.fasta\n"); return false; }
         if (judgeTol < -1) { std::fprintf(stderr, "--judge-tol N needs N >= 0\n"); return false; }
+        if (!block.check()) return false;
+        if (block.blocks && judge.empty()) { std::fprintf(stderr, "--blocks goes with --judge GENOME.fasta\n"); return false; }
         if (wanted() && world) { std::fprintf(stderr, "--links runs on one GPU only (not with --world): export per rank and add the tables\n"); return false; }
         return true;
     }
@@ -349,6 +373,7 @@ struct LinkResult {
     std::string fillJson;                         // --fill-gaps: tol, the two limits and the ten stats; empty without the flag
     std::string overlapJson;                      // --overlap-gaps: tol, the two bounds and the seven stats; empty without the flag
     std::string judgeJson;                        // --judge: tol, both stats arrays by name, n50 and n50_broken; empty without the flag
+    std::string blocksJson;                       // --blocks: blocksStage's object; empty without the flag
     std::string json() const {
         return "{" + jsonNamed(genome::Graph::linkClassNames, classes.v, 8) + "," + jsonNamed(genome::Links::joinStatNames, joins.v, 5) + ",\"mid\":" +
                std::to_string(mid) + ",\"max_span\":" + std::to_string(maxSpan) + ",\"chains\":" + std::to_string(chains) + ",\"cycles\":" + std::to_string(cycles) + "}";
@@ -375,6 +400,35 @@ inline std::vector<std::string> fastaRecords(const std::string &text) {
     }
     if (seenHeader || !cur.empty()) records.push_back(cur);
     return records;
+}
+// --blocks: the records aligned at o's tol with `positions` (of the graph as it is now); one line to stderr, the rows to o.rows if
+// given -> {"tol", "stats": the 24 by name, "genome_fraction": covered / windows, "na50", "nga50"}
+inline std::string blocksStage(const genome::Graph &graph, genome::PositionMap &positions, const std::vector<std::string> &records, const BlockOpts &o) {
+    const uint64_t tol = o.tolerance();
+    const auto b = graph.alignBlocks(positions, records, tol);
+    const auto st = b.stats();
+    const auto n = b.na50();
+    const double fraction = st.v[3] ? (double)st.v[4] / (double)st.v[3] : 0.0;
+    typedef unsigned long long ull;
+    std::fprintf(stderr, "blocks: tol %llu (%s), %llu rows on %llu edges: %llu exact, %llu colinear, %llu indel, %llu misassembled, %llu repeat, %llu unaligned; "
+                         "genome fraction %.6f, NA50 %llu, NGA50 %llu\n", (ull)tol, o.tol >= 0 ? "given" : "the default, a choice", (ull)st.v[5],
+                 (ull)(st.v[13] + st.v[14] + st.v[15] + st.v[16] + st.v[17]), (ull)st.v[17], (ull)st.v[16], (ull)st.v[15], (ull)st.v[14], (ull)st.v[13], (ull)st.v[12],
+                 fraction, (ull)n.first, (ull)n.second);
+    if (!o.rows.empty()) {
+        const auto r = b.rows();
+        std::ofstream rf(o.rows);
+        rf << "# alignment blocks of the graph's edges on the reference, in the rule's order (include/genome_amd.h); tol " << tol << "\n"
+           << "# brk: 0 first, 1 overlap, 2 translocation, 3 inversion, 4 relocation, 5 indel, 6 colinear\n"
+           << "# edge\tstrand\trecord\tpos\tdlo\tdhi\tbrk\tshift\n";
+        for (size_t i = 0; i < r.edge.size(); i++)
+            rf << r.edge[i] << "\t" << (int)r.strand[i] << "\t" << r.record[i] << "\t" << r.pos[i] << "\t" << r.dlo[i] << "\t" << r.dhi[i] << "\t" << (int)r.brk[i] << "\t"
+               << r.shift[i] << "\n";
+        if (!rf) throw std::runtime_error("cannot write " + o.rows);
+    }
+    char frac[40];
+    std::snprintf(frac, sizeof frac, "%.17g", fraction);
+    return jsonObject("tol", tol, "stats", "{" + jsonNamed(genome::Blocks::statNames, st.v, GK_BLOCKS_NSTATS) + "}", "genome_fraction", std::string(frac), "na50", n.first,
+                      "nga50", n.second);
 }
 // lengths descending, the first at which twice the running sum reaches the total (gk_graph_contig_stats' n50); 0 for none
 inline uint64_t n50Of(std::vector<uint64_t> lengths) {
@@ -495,7 +549,8 @@ inline LinkResult linksStage(genome::Graph &graph, genome::Context &ctx, const g
         if (!lo.judge.empty()) {                                                                     // the plan that was written, on the final graph
             const uint64_t tol = lo.judgeTol >= 0 ? (uint64_t)lo.judgeTol : (rhi - rlo) / 2;
             const std::vector<uint8_t> text = readBin(lo.judge);
-            const auto placements = graph.place(positions, fastaRecords(std::string(text.begin(), text.end())));
+            const std::vector<std::string> records = fastaRecords(std::string(text.begin(), text.end()));
+            const auto placements = graph.place(positions, records);
             const auto pst = placements.stats();
             const auto jd = sc.judge(placements, tol);
             const auto n50 = scaffoldN50s(sc.segments(), jd.classes);
@@ -507,6 +562,7 @@ inline LinkResult linksStage(genome::Graph &graph, genome::Context &ctx, const g
             r.judgeJson = jsonObject("tol", tol, "placements", "{" + jsonNamed(genome::Placements::statNames, pst.v, GK_PLACE_NSTATS) + "}", "stats",
                                      "{" + jsonNamed(genome::Scaffolds::judgeStatNames, jd.v, GK_JUDGE_NSTATS) + "}", "classes", jsonList(std::vector<uint32_t>(jd.classes.begin(), jd.classes.end())),
                                      "err", jsonList(jd.err), "n50", n50.first, "n50_broken", n50.second);
+            if (lo.block.blocks) r.blocksJson = blocksStage(graph, positions, records, lo.block);
         }
     }
     return r;

@@ -1333,7 +1333,7 @@ int gk_fasta_check_last_ms(const gk_fasta_check *fc, float *ms4);
  * On the device: a lane owns 16 consecutive window starts of the slice, staged in LDS with a k-1 halo, and rolls W and its
  * reverse complement together; hits of one edge are folded to (count, min, max) inside the lane's run and again over the wave, and
  * one 32-bit add plus a 64-bit min and a 64-bit max go to HBM per folded run.
- * Not there: a collective over ranks, circular references, alignment inside a scattered edge. */
+ * Not there: a collective over ranks, circular references.  Alignment inside a scattered edge is the next section's. */
 #define GK_PLACE_NSTATS 20
 enum { GK_PLACE_UNPLACED = 0, GK_PLACE_BOTH_STRANDS = 1, GK_PLACE_SCATTERED = 2, GK_PLACE_FORWARD = 3, GK_PLACE_REVERSE = 4 };
 typedef struct gk_placements gk_placements;
@@ -1382,6 +1382,99 @@ int gk_placements_last_ms(const gk_placements *p, float *ms4);
 enum { GK_JUDGE_UNJUDGED = 0, GK_JUDGE_OTHER_RECORD = 1, GK_JUDGE_STRAND = 2, GK_JUDGE_ORDER = 3, GK_JUDGE_DISTANCE = 4, GK_JUDGE_CORRECT = 5 };
 int gk_scaffolds_judge(const gk_scaffolds *s, const gk_placements *p, uint64_t tol, uint8_t *cls, int64_t *err, uint64_t cap, uint64_t *n,
                        uint64_t *stats);
+
+/* ---- alignment blocks: this project's own rule (the placements fold the hits of an edge to one count, one minimum and one
+ * maximum; this pass keeps the runs) ----
+ * Every edge of a graph aligned to a reference genome as the exact runs of k-mers it shares with it.  Integers only.
+ * Hits.  The input, the validity of characters, the windows, the two lookups per window and the candidates are exactly those of
+ * "placements".  For strand s (0: W as it reads, 1: revComplement(W)) and window start x of record r the HIT h_s(x) is (e, c) when
+ * the lookup's class is `edge`: e the edge, c the candidate, x - d for a forward hit and x + d + k - 1 for a reverse hit.  It is
+ * NONE otherwise: absent, repetitive, at_node, and no valid window at x.
+ * Run.  A run is a maximal interval x0 .. x1 of consecutive window starts of one record and one strand with the same hit that is
+ * not NONE.  Equal (e, c) at consecutive x means consecutive d, so a run is an exact match of n = x1 - x0 + 1 consecutive k-mers
+ * of P(e).
+ * Block row.  (edge, strand, record, pos = c, dlo, dhi); dlo .. dhi is the inclusive range of k-mer distances of the run:
+ * forward dlo = x0 - c, dhi = x1 - c; reverse dlo = c - (x1 + k - 1), dhi = c - (x0 + k - 1).  1 <= dlo <= dhi <= len_e - 1.
+ * Order.  Rows are ordered by (edge, dlo, dhi, strand, record, x0).  Two rows of one strand and record differ in x0, so the order
+ * is total; rows are numbered in it, and an edge's rows are consecutive.
+ *
+ * ---- breakpoints ----
+ * Every row after the first row of its edge carries a breakpoint class against the row before it, the first that holds:
+ *   1 overlap        dlo <= dhi of the row before: the same graph k-mer lies at two places of the reference;
+ *   2 translocation  another record;
+ *   3 inversion      another strand;
+ *   4 relocation     |shift| > tol;
+ *   5 indel          0 < |shift| <= tol;
+ *   6 colinear       shift == 0: substitutions, N or lowercase in between.
+ * The first row of an edge has class 0.  shift of rows i, i + 1 (same record and strand) = pos(i + 1) - pos(i) when forward and
+ * pos(i) - pos(i + 1) when reverse: positive means the reference holds that many more bases between the two blocks than P(e)
+ * does.  `shift` is written per row and is 0 for the classes 0 to 3.
+ * Adjacent rows are enough for `overlap`: if rows i < j of an edge overlap, dlo(j) <= dhi(i), then the order gives
+ * dlo(i) <= dlo(i + 1) <= dlo(j) <= dhi(i), so row i + 1 overlaps row i already: an edge has some overlapping pair of rows iff it
+ * has an `overlap` breakpoint.
+ * Edge classes, the first that holds (gk_blocks_edges' cls):
+ *   0 unaligned     no row;
+ *   1 repeat        some `overlap` breakpoint;
+ *   2 misassembled  some breakpoint of class 2 to 4;
+ *   3 indel         some breakpoint of class 5;
+ *   4 colinear      more than one row, all breakpoints of class 6;
+ *   5 exact         one row.
+ * `full` is set iff the edge's first row has dlo == 1 and its last row has dhi == len_e - 1.  first_row and nrows give the edge's
+ * rows by number.  A dead edge id gives unaligned and zeros; an id at or above the bound the graph had at create is
+ * GK_E_INVALID with nothing written.
+ * Pieces.  For every edge that is not `repeat` the row list is cut at every breakpoint of class 2 to 4; a piece spans
+ * (dhi of its last row - dlo of its first row + k) bases.  gk_blocks_pieces gives (bases, edge) in row order.  NA50 and NGA50 are
+ * the caller's to compute from the piece lengths, as from gk_scaffolds_segments' rows: lengths descending, the first at which
+ * twice the running sum reaches the piece bases [21] (NA50) or the valid bases of the reference [2] (NGA50; 0 if never).
+ * Stats: uint64[GK_BLOCKS_NSTATS] = {records, bases, valid_bases, windows, [4] covered: windows with an `edge` hit on at least
+ * one strand (the numerator of the genome fraction, over [3]), [5] rows, [6 .. 11] the breakpoint classes 1 .. 6, [12 .. 17] the
+ * edge classes 0 .. 5, [18] full edges, [19] aligned k-mers: the sum of n over all rows, [20] pieces, [21] piece bases, [22] the
+ * sum and [23] the maximum of |shift| over the `indel` breakpoints}.  Identities: [12] + .. + [17] = the live edges;
+ * [6] + .. + [11] = [5] - ([13] + .. + [17]) (every aligned edge has one first row); [2] <= [1]; [4] <= [3]; [4] <= [19] <= 2 [3];
+ * [20] >= [14] + .. + [17]; [18] <= [13] + .. + [17]; [23] <= [22].
+ * Strand symmetry.  Where the graph holds both e and its twin e' (P(e') = revComplement(P(e)), len the same), the k-mer at
+ * distance d of P(e') is the reverse complement of the k-mer at distance len - d of P(e).  So W hits Edge(e, d) iff
+ * revComplement(W) hits Edge(e', len - d): every forward run of e is a reverse run of e' over the same starts and the other way
+ * round, with d -> len - d, hence (dlo, dhi) -> (len - dhi, len - dlo), and pos' = pos + len + k - 1 for a forward row of e,
+ * pos' = pos - len - k + 1 for a reverse one.  The map d -> len - d reverses the order of an edge's rows wherever the order is
+ * decided by non-overlapping ranges, so neighbours stay neighbours: records agree, strands are flipped on both sides of a
+ * breakpoint, and pos(i + 1) - pos(i) of a forward pair becomes pos'(i) - pos'(i + 1) of the reverse pair read the other way
+ * round: the classes and |shift| agree (the sign of shift too).  An overlap stays an overlap.  Both edge classes and `full`
+ * agree; within a repeat the order of overlapping rows, and with it the sequence of their classes, may differ.
+ * Limits.  tol is a choice, not a measurement: the tools' --block-tol defaults to 1000.  The capacity rules are the placements'
+ * own (2^24 records, records below 2^39 bases: GK_E_CAPACITY); more than 2^32 - 1 rows is GK_E_CAPACITY from gk_blocks_finish.
+ * Calls.  gk_blocks_add_record feeds one record, as gk_placements_add_record does (slices of the record honour the same test
+ * switch; a slice brings k characters along, one more than the placements', for the hit before its first start).
+ * gk_blocks_finish(tol) orders the rows, classes every breakpoint and edge and cuts the pieces; it may be called again with
+ * another tol, without feeding the records again.  gk_blocks_rows: any array may be NULL; cap below *n is GK_E_CAPACITY with *n
+ * set and nothing copied (so does gk_blocks_pieces).
+ * Errors are the placements' own (GK_E_KLEN, GK_E_INVALID, GK_E_STATE for a stale position map, tested bound first before any
+ * per-edge array is indexed, and for an edited graph).  In addition: stats, rows, edges and pieces before the first finish are
+ * GK_E_STATE, and so is add_record after a finish.
+ * On the device: gk_blocks.hip.  A window start is an EVENT on a strand iff its hit differs from the hit one start before (NONE
+ * before a record's first window; a change to NONE is an event too), a definition that knows nothing of lanes, waves, tiles or
+ * slices.  A run is an event with a hit; it ends one start before the next event of its strand.  A count launch, a scan over
+ * the workgroups' counts and an emit launch write the events in stream order with plain 16-byte stores; every window is looked
+ * up twice, which is accepted for an instrument.  The event buffers come from the context's block pool and grow between slices.
+ * Not there: a collective over ranks, circular references, any alignment with mismatches inside a block, feeding the result
+ * back into gk_scaffolds_judge (whose classes do not change). */
+#define GK_BLOCKS_NSTATS 24
+enum { GK_BREAK_FIRST = 0, GK_BREAK_OVERLAP = 1, GK_BREAK_TRANSLOCATION = 2, GK_BREAK_INVERSION = 3, GK_BREAK_RELOCATION = 4, GK_BREAK_INDEL = 5,
+       GK_BREAK_COLINEAR = 6 };
+enum { GK_BLOCKS_UNALIGNED = 0, GK_BLOCKS_REPEAT = 1, GK_BLOCKS_MISASSEMBLED = 2, GK_BLOCKS_INDEL = 3, GK_BLOCKS_COLINEAR = 4, GK_BLOCKS_EXACT = 5 };
+typedef struct gk_blocks gk_blocks;
+int gk_blocks_create(gk_graph *g, gk_vmap *positions, gk_blocks **out);
+void gk_blocks_destroy(gk_blocks *b);
+int gk_blocks_add_record(gk_blocks *b, const char *bases, uint64_t n);
+int gk_blocks_finish(gk_blocks *b, uint64_t tol);
+int gk_blocks_stats(const gk_blocks *b, uint64_t *stats);
+int gk_blocks_rows(const gk_blocks *b, uint32_t *edge, uint8_t *strand, uint32_t *record, int64_t *pos, uint32_t *dlo, uint32_t *dhi, uint8_t *brk,
+                   int64_t *shift, uint64_t cap, uint64_t *n);
+int gk_blocks_edges(const gk_blocks *b, const uint32_t *edge_ids, uint64_t n, uint8_t *cls, uint8_t *full, uint32_t *first_row, uint32_t *nrows);
+int gk_blocks_pieces(const gk_blocks *b, uint64_t *len, uint32_t *edge, uint64_t cap, uint64_t *n);
+/* wall ms: {host staging + upload, count launches + scans, emit launches, whole call} of the last add_record, {device time, whole
+ * call} of the last finish */
+int gk_blocks_last_ms(const gk_blocks *b, float *ms6);
 
 /* ---- synthetic reads (bench / tests) ---------------------------------------- */
 /* Fill dev_records with nreads fixed-length `.bin` records generated on device, bit-identical to
