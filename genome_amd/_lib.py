@@ -148,6 +148,13 @@ SIGNATURES = {
     "gk_contigs_read": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "gk_contigs_write": (C.c_int, [vp, C.c_char_p]),
     "gk_contigs_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "gk_graph_edge_twins": (C.c_int, [vp, u32p, C.c_uint64, u32p, u8p, u64p]),
+    "gk_graph_gfa_plan": (C.c_int, [vp, vp, C.POINTER(vp)]),
+    "gk_gfa_destroy": (None, [vp]),
+    "gk_gfa_stats": (C.c_int, [vp, u64p]),
+    "gk_gfa_read": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, u64p]),
+    "gk_gfa_write": (C.c_int, [vp, C.c_char_p]),
+    "gk_gfa_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "gk_support_create": (C.c_int, [vp, C.POINTER(vp)]),
     "gk_support_destroy": (None, [vp]),
     "gk_support_size": (C.c_int, [vp, u64p, u64p, u64p]),

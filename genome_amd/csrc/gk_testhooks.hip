@@ -96,6 +96,10 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
     else if (n == "test_place_slice") ctx->hook_place_slice = (int64_t)std::max<int64_t>(0, value);
     else if (n == "test_prefilter_chunk_windows") ctx->hook_pf_chunk_windows = (int64_t)std::max<int64_t>(0, value);
     else if (n == "contigs_chunk_bytes") ctx->hook_contigs_chunk = (int64_t)std::max<int64_t>(0, value);
+    else if (n == "twin_key_bits") {
+        if (value < 0 || value > 128) return fail(ctx, GK_E_INVALID, "twin_key_bits: 0..128");
+        ctx->hook_twin_key_bits = (int)value;
+    }
     else if (n == "fine_exact") ctx->hook_fine_exact = value < 0 ? -1 : value != 0;
     else return fail(ctx, GK_E_INVALID, "gk_ctx_set_option: unknown option '" + n + "'");
     return GK_OK;

@@ -225,6 +225,32 @@ class HipGraph:
                                               C.byref(h)), self.ctx.h)
         return Contigs(self, h)
 
+    # ---- edge twins and the graph as GFA 1.0 (this project's own rules: include/genome_amd.h) ---------------------------
+    def edgeTwins(self, ids=None):
+        """The twin of every edge asked for (default: every id below idBounds()), by content, exactly -> (twin, cls, stats).
+        cls[i] indexes TWIN_CLASSES; twin[i] is the twin's id for `paired`, the edge's own for `self`, 0xffffffff for `missing`,
+        `ambiguous` and a dead or out-of-range id.  stats: the six numbers of TWIN_STATS over ALL live edges."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        ids = np.arange(self.idBounds()[1], dtype=np.uint32) if ids is None else np.ascontiguousarray(ids, np.uint32)
+        n = len(ids)
+        twin, cls = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        st = np.zeros(len(TWIN_STATS), np.uint64)
+        L.check(L.lib().gk_graph_edge_twins(self.h, L.ptr(ids, C.c_uint32), n, L.ptr(twin, C.c_uint32), L.ptr(cls, C.c_uint8), L.ptr(st, C.c_uint64)),
+                self.ctx.h)
+        return twin, cls, dict(zip(TWIN_STATS, (int(x) for x in st)))
+
+    def gfa(self, counts: HipDNAMap = None) -> "Gfa":
+        """The graph as GFA 1.0 text, planned on the device: one S line per segment (a twin pair's forward edge, or an edge that
+        has no single twin), one L line per pair of edges that meet in a node, each mirror pair once, the overlap being the node's
+        k bases.  `counts` (any table of this k) adds KC:i: to the S lines.  -> a Gfa: stats(), read(), text(), write().  Any edit
+        of the graph makes it stale (GkError GK_E_STATE)."""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the graph is closed")
+        h = L.vp()
+        L.check(L.lib().gk_graph_gfa_plan(self.h, counts.h if counts is not None else None, C.byref(h)), self.ctx.h)
+        return Gfa(self, h)
+
     # ---- scaffolds as FASTA (this project's own rule: include/genome_amd.h) --------------------------------------------
     def scaffolds(self, chains, gaps, min_gap: int = 10, min_len: int = 0, line_width: int = 60, strands: int = 1, singletons: bool = True,
                   overlaps=None) -> "Scaffolds":
@@ -549,6 +575,70 @@ class Contigs:
         """the whole text to `path`; written aside, then renamed onto it"""
         self._live()
         L.check(L.lib().gk_contigs_write(self.h, os.fsencode(path)), self.ctx.h)
+
+
+# the statistics of gk_graph_edge_twins, in the order of its `stats6` array: live_edges is the sum of the four after it
+TWIN_STATS = ("live_edges", "paired", "self", "missing", "ambiguous", "key_collisions")
+# the names of gk_graph_edge_twins' class codes, by code (dead: a dead or out-of-range id)
+TWIN_CLASSES = ("dead", "paired", "self", "missing", "ambiguous")
+# the statistics of gk_gfa_stats, in the order of its `stats9` array: live_edges = segments + folded, pairs = links + mirrored
+GFA_STATS = ("live_edges", "segments", "folded", "pairs", "links", "mirrored", "bases", "text_bytes", "missing_windows")
+
+
+class Gfa:
+    """A plan of the GFA 1.0 text of a graph (HipGraph.gfa): the text itself is emitted by the device when it is read or
+    written.  Holds its graph; stale (GkError GK_E_STATE from read / text / write) once the graph has been edited."""
+
+    def __init__(self, graph: HipGraph, handle):
+        self.graph, self.ctx, self.h = graph, graph.ctx, handle
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:               # (see HipDNAMap.close)
+                L.lib().gk_gfa_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not self.h or not self.ctx.h or not self.graph.h:
+            raise L.GkError(L.GK_E_STATE, "the GFA plan or its graph are closed")
+
+    def stats(self) -> dict:
+        """the nine numbers of the plan, named as GFA_STATS; they still answer when the plan is stale"""
+        if not self.h or not self.ctx.h:
+            raise L.GkError(L.GK_E_STATE, "the GFA plan is closed")
+        st = np.zeros(len(GFA_STATS), np.uint64)
+        L.check(L.lib().gk_gfa_stats(self.h, L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(GFA_STATS, (int(x) for x in st)))
+
+    def read(self, offset: int, n: int) -> bytes:
+        """bytes [offset, offset + n) of the text, fewer at its end; GkError GK_E_INVALID for an offset beyond it"""
+        self._live()
+        buf = np.empty(max(int(n), 1), np.uint8)
+        got = C.c_uint64()
+        L.check(L.lib().gk_gfa_read(self.h, int(offset), buf.ctypes.data, int(n), C.byref(got)), self.ctx.h)
+        return buf[:got.value].tobytes()
+
+    def text(self) -> bytes:
+        return self.read(0, self.stats()["text_bytes"])
+
+    def last_ms(self) -> dict:
+        """wall ms of the last read / write: the emit kernels (device events), waits for copies, the sink, the whole call"""
+        arr = (C.c_float * 4)()
+        L.check(L.lib().gk_gfa_last_ms(self.h, arr), self.ctx.h)
+        return dict(zip(("emit_kernels", "copies", "sink", "total"), (float(x) for x in arr)))
+
+    def write(self, path):
+        """the whole text to `path`; written aside, then renamed onto it"""
+        self._live()
+        L.check(L.lib().gk_gfa_write(self.h, os.fsencode(path)), self.ctx.h)
 
 
 # the statistics of gk_scaffolds_stats, in the order of its `stats13` array

@@ -10,6 +10,8 @@
 //   (include/genome_amd.h, "alignment blocks" and "breakpoints"; plain FASTA text, records joined whatever --per-line says).  N
 //   defaults to 1000: a choice, not a measurement.  stderr gets one line; the JSON gains "blocks":{tol, "stats":{the twenty-four
 //   stats}, genome_fraction, na50, nga50}; PATH gets one text line per row.
+//   --twins: the twin census of the graph's edges (include/genome_amd.h, "edge twins"): stderr gets the six stats on one line, the
+//   JSON gains "twins":{live_edges, paired, self, missing, ambiguous, key_collisions}.  missing == 0: the graph is strand-closed.
 //
 // Build: g++ -std=c++17 -O2 -I include genome_amd/host/check_graph.cpp -L genome_amd -lgenome_amd
 //        -Wl,-rpath,'$ORIGIN/..' -o genome_amd/host/check_graph
@@ -21,11 +23,12 @@ int main(int argc, char **argv) {
     if (argc < 3) { std::fprintf(stderr, usage, argv[0]); return 2; }
     const std::string graphFile = argv[1], fasta = argv[2];
     uint64_t longerThan = 200, maxMissing = 0;
-    bool perLine = false;
+    bool perLine = false, twins = false;
     BlockOpts block;
     for (Args a(argc, argv, 3); a.more(); a.next()) {
         if (a.value("--longer-than", longerThan) || a.value("--missing", maxMissing)) {}
         else if (a.flag("--per-line")) perLine = true;
+        else if (a.flag("--twins")) twins = true;
         else if (block.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); std::fprintf(stderr, usage, argv[0]); return 2; }
     }
@@ -56,6 +59,12 @@ int main(int argc, char **argv) {
         if (block.blocks) {
             const std::vector<uint8_t> text = readBin(fasta);
             std::printf(",\"blocks\":%s", blocksStage(graph, graphMap, fastaRecords(std::string(text.begin(), text.end())), block).c_str());
+        }
+        if (twins) {
+            const auto t = graph.edgeTwins();
+            std::fprintf(stderr, "twins: live_edges %llu paired %llu self %llu missing %llu ambiguous %llu key_collisions %llu\n", (ull)t.liveEdges, (ull)t.paired,
+                         (ull)t.self, (ull)t.missing, (ull)t.ambiguous, (ull)t.keyCollisions);
+            std::printf(",\"twins\":%s", t.json().c_str());
         }
         std::printf("}\n");
     } catch (const std::exception &e) {

@@ -662,6 +662,48 @@ class Contigs {
     gk_contigs *h_ = nullptr;
 };
 
+// gk_gfa: a plan of the GFA 1.0 text of a graph (Graph::gfa; the rule: include/genome_amd.h, "the graph as GFA").  As Contigs: the
+// device emits the text when it is read or written, and an edit of the graph makes the plan stale.
+class Gfa {
+  public:
+    struct Stats {
+        uint64_t liveEdges = 0, segments = 0, folded = 0, pairs = 0, links = 0, mirrored = 0, bases = 0, textBytes = 0, missingWindows = 0;
+        std::string json() const {                           // the names of gk_gfa_stats' stats9
+            const uint64_t v[9] = {liveEdges, segments, folded, pairs, links, mirrored, bases, textBytes, missingWindows};
+            const char *names[9] = {"live_edges", "segments", "folded", "pairs", "links", "mirrored", "bases", "text_bytes", "missing_windows"};
+            std::string s = "{";
+            for (int i = 0; i < 9; i++) s += std::string(i ? ",\"" : "\"") + names[i] + "\":" + std::to_string(v[i]);
+            return s + "}";
+        }
+    };
+    Gfa(gk_ctx *ctx, gk_gfa *h) : ctx_(ctx), h_(h) {}
+    ~Gfa() { close(); }
+    void close() { gk_gfa_destroy(h_); h_ = nullptr; }
+    Gfa(Gfa &&o) noexcept : ctx_(o.ctx_), h_(o.h_) { o.h_ = nullptr; }
+    Gfa(const Gfa &) = delete;
+    Gfa &operator=(const Gfa &) = delete;
+    Stats stats() const {
+        uint64_t v[9] = {};
+        check(gk_gfa_stats(h_, v), ctx_);
+        return Stats{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
+    }
+    // bytes [offset, offset + n) of the text, fewer at its end
+    std::string read(uint64_t offset, uint64_t n) {
+        std::string out((size_t)n, '\0');
+        uint64_t got = 0;
+        check(gk_gfa_read(h_, offset, out.data(), n, &got), ctx_);
+        out.resize((size_t)got);
+        return out;
+    }
+    std::string text() { return read(0, stats().textBytes); }
+    // the whole text to path, written aside and renamed onto it
+    void write(const std::string &path) { check(gk_gfa_write(h_, path.c_str()), ctx_); }
+
+  private:
+    gk_ctx *ctx_ = nullptr;
+    gk_gfa *h_ = nullptr;
+};
+
 // gk_placements: where every edge of a graph lies on a reference genome (Graph::place; the rule: include/genome_amd.h,
 // "placements").  Holds neither the graph nor the position map: both must outlive it, and an edit of the graph makes it stale.
 class Placements {
@@ -1110,6 +1152,32 @@ class Graph {
         return out;
     }
 
+    // The twin of every edge asked for, by content (include/genome_amd.h, "edge twins"): twin[i] (0xffffffff: none), cls[i]
+    // (GK_TWIN_*) and the six stats over all live edges, named as gk_graph_edge_twins' stats6
+    struct EdgeTwins {
+        std::vector<uint32_t> twin;
+        std::vector<uint8_t> cls;
+        uint64_t liveEdges = 0, paired = 0, self = 0, missing = 0, ambiguous = 0, keyCollisions = 0;
+        std::string json() const {
+            return "{\"live_edges\":" + std::to_string(liveEdges) + ",\"paired\":" + std::to_string(paired) + ",\"self\":" + std::to_string(self) +
+                   ",\"missing\":" + std::to_string(missing) + ",\"ambiguous\":" + std::to_string(ambiguous) + ",\"key_collisions\":" + std::to_string(keyCollisions) + "}";
+        }
+    };
+    EdgeTwins edgeTwins(const std::vector<uint32_t> &ids = {}) const {
+        EdgeTwins t;
+        t.twin.resize(ids.size());
+        t.cls.resize(ids.size());
+        uint64_t st[6] = {};
+        check(gk_graph_edge_twins(h_, ids.data(), ids.size(), t.twin.data(), t.cls.data(), st), ctx_.handle());
+        t.liveEdges = st[0]; t.paired = st[1]; t.self = st[2]; t.missing = st[3]; t.ambiguous = st[4]; t.keyCollisions = st[5];
+        return t;
+    }
+    // The graph as GFA 1.0, planned on the device (include/genome_amd.h, "the graph as GFA"): counts (may be null) adds KC:i:
+    Gfa gfa(const DNAMap *counts = nullptr) const {
+        gk_gfa *c = nullptr;
+        check(gk_graph_gfa_plan(h_, counts ? counts->handle() : nullptr, &c), ctx_.handle());
+        return Gfa(ctx_.handle(), c);
+    }
     // The assembly as FASTA, planned on the device (include/genome_amd.h, "contigs"): one record `>e<id> len=<n>[ cov=<mean>]` per
     // live edge whose path (start k-mer ++ seq) is not above its reverse complement (bothStrands: every live edge), n >= minLen, in
     // ascending edge id, wrapped at lineWidth (0: one line); `counts` (may be null) adds the cov= field.

@@ -72,6 +72,8 @@
 //   and classes every breakpoint (include/genome_amd.h, "alignment blocks" and "breakpoints").  N defaults to 1000: a choice, not a
 //   measurement.  stderr gets one line; the JSON gains "blocks":{tol, "stats":{the twenty-four stats}, genome_fraction, na50, nga50};
 //   PATH gets one text line per row.
+//   --gfa PATH writes the final graph as GFA 1.0 on the device (gk_graph_gfa_plan / gk_gfa_write; include/genome_amd.h, "the graph
+//   as GFA"), without KC tags: there is no count table after a load.  The JSON gains "gfa":{the nine stats}.  Not with --world.
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
 //   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
 //   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
@@ -89,7 +91,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
-                             "[--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] "
+                             "[--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--gfa PATH] "
                              "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
@@ -100,6 +102,7 @@ int main(int argc, char **argv) {
     uint64_t takeFirst = UINT64_MAX;
     std::string out, saveGraph, insertHist;
     ContigOpts contig;
+    GfaOpts gfaOpt;
     LinkOpts link;
     RankOpts ranks;
     for (Args a(argc, argv, 4); a.more(); a.next()) {
@@ -110,7 +113,7 @@ int main(int argc, char **argv) {
         else if (a.flag("--thread-reads")) stage.threadReads = true;
         else if (a.flag("--no-pairs")) stage.walk = false;
         else if (stage.parseResolve(a)) {}
-        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || link.parse(a) || ranks.parse(a)) {}
+        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || gfaOpt.parse(a) || link.parse(a) || ranks.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
     if (stage.cutoff < 0) {
@@ -125,7 +128,7 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--no-pairs goes with --thread-reads, and not with --range auto (no walk uses the range)\n");
         return 2;
     }
-    if (!ranks.check() || !link.check(ranks.world) || !stage.checkResolve(ranks.world)) return 2;
+    if (!ranks.check() || !link.check(ranks.world) || !gfaOpt.check(ranks.world) || !stage.checkResolve(ranks.world)) return 2;
     const int world = ranks.world, rank = ranks.rank;
     try {
         if (fastq.path.empty()) data.bin = readBin(infile);
@@ -170,6 +173,8 @@ int main(int argc, char **argv) {
             if (!lr.judgeJson.empty()) jsonPut(js, "judge", lr.judgeJson);
             if (!lr.blocksJson.empty()) jsonPut(js, "blocks", lr.blocksJson);
         }
+        // --gfa: the final graph as GFA 1.0 (this tool holds no count table: no KC tag)
+        if (const std::string gj = gfaOpt.run(graph, nullptr); !gj.empty()) jsonPut(js, "gfa", gj);
         if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");
         if (stage.resolve) jsonPut(js, "resolve_repeats", res.resolveJson(stage.spanCutoff()));
         jsonPut(js, "simplified_nodes", n2, "simplified_edges", e2, "simplified_edges_length", l2, "components_histogram_2", jsonPairs(hist2),

@@ -104,6 +104,24 @@ struct ContigOpts {
     }
 };
 
+// --gfa PATH: the final graph as GFA 1.0 (gk_graph_gfa_plan / gk_gfa_write); one GPU only, as --links is
+struct GfaOpts {
+    std::string path;
+    bool parse(Args &a) { return a.value("--gfa", path); }
+    bool check(int world) const {
+        if (path.empty() || !world) return true;
+        std::fprintf(stderr, "--gfa runs on one GPU only (not with --world): write it from the saved graph\n");
+        return false;
+    }
+    // writes the text; -> the nine stats as JSON ("" if --gfa was not given)
+    std::string run(const genome::Graph &graph, const genome::DNAMap *counts) const {
+        if (path.empty()) return "";
+        auto gfa = graph.gfa(counts);
+        gfa.write(path);
+        return gfa.stats().json();
+    }
+};
+
 // --world W --rank R --id-file PATH; world 0: one GPU, no communicator
 struct RankOpts {
     int world = 0, rank = 0;

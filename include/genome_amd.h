@@ -595,6 +595,68 @@ int gk_contigs_write(gk_contigs *c, const char *path);
  * waits for the device-to-host copies, the sink (file writes, or the copy into buf), the whole call} */
 int gk_contigs_last_ms(const gk_contigs *c, float *ms4);
 
+/* ---- edge twins: this project's own rule (the reference keeps both strands of everything as unrelated edges) ----
+ * Which live edge is the reverse complement of which, by content, exactly.  Integers only; no edge id enters the rule.
+ * P(e) and R(e) are the contigs' (above): the start k-mer followed by the sequence, and its reverse complement.
+ * C(e)  = the live edges f with P(f) = P(e); e is one of them.   C'(e) = the live edges f with P(f) = R(e).
+ * Classes.  Every live edge falls into exactly one, tested in this order:
+ *   1. missing:   C'(e) is empty;
+ *   2. ambiguous: |C(e)| > 1 or |C'(e)| > 1 — the copies a node split or a span split leaves until simplifyGraph merges them with
+ *      their flanks;
+ *   3. self:      C'(e) = {e};
+ *   4. paired:    C'(e) = {f}, f != e, and twin(e) = f.
+ * Twins.  The classes of e and of twin(e) agree and twin(twin(e)) = e: P(f) = R(e) iff P(e) = R(f), since reverse complement
+ * is an involution, so e is in C'(f), and C(f) = C'(e), C'(f) = C(e) as sets; e paired means |C(e)| = |C'(e)| = 1, hence |C'(f)| =
+ * |C(f)| = 1 with C'(f) = {e}.  A graph is strand-closed iff missing == 0, and free of copies iff also ambiguous == 0.
+ * Per id asked for, in the order asked (ids as gk_graph_edge_coverage takes them): cls[i] = GK_TWIN_*, twin[i] = the twin's id for
+ * paired, the edge's own for self, 0xFFFFFFFF for missing and ambiguous; a dead or out-of-range id gives GK_TWIN_DEAD and
+ * 0xFFFFFFFF.  stats6 = {live_edges, paired, self, missing, ambiguous, key_collisions}, over ALL live edges whatever ids were asked
+ * for (n may be 0): live_edges is the sum of the four after it and paired is even.  Any output pointer may be NULL.  The graph is not
+ * changed.
+ * On the device: the 128-bit path key (below, "the path key") of P(e) and of R(e) — the latter by walking the edge's words
+ * backwards with complemented codes — for every live edge; (key of P, id) sorted by radix sort; one wave per live edge finds the
+ * runs of key(P(e)) and key(R(e)) by binary search and confirms every candidate by comparing the paths, 64 bases per step.  A
+ * candidate with the key but another content is skipped and counted in key_collisions: the answer never rests on the hash. */
+#define GK_TWIN_DEAD 0
+#define GK_TWIN_PAIRED 1
+#define GK_TWIN_SELF 2
+#define GK_TWIN_MISSING 3
+#define GK_TWIN_AMBIGUOUS 4
+int gk_graph_edge_twins(gk_graph *g, const uint32_t *edge_ids, uint64_t n, uint32_t *twin, uint8_t *cls, uint64_t *stats6);
+
+/* ---- the graph as GFA: this project's own rule (GFA 1.0; the reference writes no graph text but its nodes / edges files) ----
+ * A GFA segment stands for both strands, the graph holds each strand as an edge: the twins above fold them.
+ * Segment.  seg(e) = (twin(e), '-') if e is paired and REVERSE by the contigs' strand rule (P(e) > R(e)); otherwise (e, '+').
+ * The segments are the live edges with seg(e) = (e, '+'): of a twin pair the forward edge; self, missing and ambiguous edges are
+ * their own segments, so a graph that is not strand-closed, or that holds copies, degrades to a faithful directed picture and
+ * loses nothing.  e -> seg(e) is injective over the live edges (a segment s is the image of s itself, and with '-' of twin(s)
+ * alone), which is why no two links coincide.
+ * Text, in this order:
+ *     H\tVN:Z:1.0\n
+ *     S\te<id>\t<P(e) as ACGT, one line>\tLN:i:<k + len>[\tKC:i:<sum>]\n        one per segment, ascending id
+ *     L\te<a>\t<oa>\te<b>\t<ob>\t<k>M\n                                        one per emitted pair
+ * KC is there iff a count table was passed: gk_graph_edge_coverage's `sum` over the len + 1 windows; windows the table does not
+ * hold count 0 and are totalled in the stats (over the segments).
+ * Pairs.  (e, f) is a pair iff e and f are live and end(e) = start(f) as NODE IDS (copies share a k-mer).  Its line says
+ * seg(e) -> seg(f); the overlap is the node's k bases, what the contigs overlap by.  The mirror of (e, f) is (twin f, twin e); it
+ * exists iff e and f are each paired or self and end(twin f) = start(twin e).  (e, f) is skipped iff its mirror exists, differs
+ * from it and is the smaller id pair (first ids, then second): every mirror pair is written once, a pair that is its own mirror
+ * once.  Pairs go in ascending e and, within e, by the first base 0..3 of f (the order of the end node's out-edge slots).
+ * stats9 = {live_edges, segments, folded, pairs, links, mirrored, bases, text_bytes, missing_windows}: live_edges = segments +
+ * folded, pairs = links + mirrored, bases = the sum of k + len over the segments.
+ * The plan, the stale-plan rule (GK_E_STATE from read / write after ANY edit), `counts` (may be NULL; another k or context:
+ * GK_E_INVALID), NULL handles, *out on errors and the read / write / last_ms contracts are the contigs' (above).  A graph without
+ * a live edge: the header line alone.  A line of 2^32 bytes or more: GK_E_CAPACITY.
+ * On the device: the twin pass; one lane per edge sizes its S line and its 0..4 L lines; two scans over the edge ids; the text is
+ * emitted by byte range as the contigs' is.  An S line always spells the segment's own path. */
+typedef struct gk_gfa gk_gfa;
+int gk_graph_gfa_plan(gk_graph *g, gk_map *counts, gk_gfa **out);
+void gk_gfa_destroy(gk_gfa *c);
+int gk_gfa_stats(const gk_gfa *c, uint64_t *stats9);
+int gk_gfa_read(gk_gfa *c, uint64_t offset, char *buf, uint64_t cap, uint64_t *n);
+int gk_gfa_write(gk_gfa *c, const char *path);
+int gk_gfa_last_ms(const gk_gfa *c, float *ms4);
+
 /* ---- the graph file: MapGraph.write (Graph.scala:232-261) / Graph(file) (:384-390) --------------------------------------
  * The stage boundary between GraphBuilder (GraphBuilder.scala:55-56) and GraphSimplifier (GraphSimplifier.scala:152-153).
  * This project's own format (the reference's is Kryo).  Version 1, every value little-endian.  Header, 128 bytes:

@@ -47,6 +47,11 @@ extern "C" {
  * "contigs_chunk_bytes" (0: the default, 64 MiB; else rounded down to a multiple of 8, at least 8): the bytes of FASTA text
  * gk_contigs_read / gk_contigs_write emit per device chunk, so that a text of a few KiB goes through many chunks and both
  * staging buffers.
+ * "twin_key_bits" (0..128, the default and the product: 128; anything else is GK_E_INVALID): both content keys of
+ * gk_graph_edge_twins / gk_graph_gfa_plan are cut to their low bits.  With few bits a run of equal keys holds many edges of
+ * different content, so the exact confirmation and the walk along a run decide every answer; at 0 every live edge is in one run
+ * (quadratic: for graphs of a few hundred edges).  The answers do not change, only `key_collisions`.  The GFA text's chunks follow
+ * "contigs_chunk_bytes" and the twin and GFA kernels' grids "test_max_grid".
  * "test_place_slice" (0: the default, 64 Mi characters): the characters of a reference record gk_placements_add_record puts
  * through the device per slice, so that a record of a few kbp is cut inside a contig and both upload buffers are used.
  * The singleton pre-filter: "test_max_stage" is also the bytes of `.bin` records its host-fed passes stage per chunk (0: 256 MiB),
