@@ -81,7 +81,7 @@ struct gk_ctx {
     std::string err;
     int hook_dist_fail_reduce = 0;   // test hook: this context's next gk_dist_reduce_support fails its owner merge, after the records have been exchanged
     float graph_io_ms[4] = {0, 0, 0, 0};   // the last gk_graph_save / gk_graph_load on this context: file I/O, copies, kernels, whole call
-    int hook_max_grid = 0;           // test hook: the grid-stride launches of the graph phase, the value maps, the spectrum and the read correction get at
+    int hook_max_grid = 0;           // test hook: the grid-stride launches of the graph phase, the value maps, the spectrum, gk_map_verify and the read correction get at
                                      // most this many workgroups (0: cu_count * 8), so that a small input makes every workgroup take several trips
     mutable uint64_t hook_max_grid_uses = 0;   // ... and how many launches were sized under it (gk_test_grid_cap_uses: the switch's echo)
     int64_t hook_contigs_chunk = 0;  // test hook: text bytes per device chunk of gk_contigs_read / gk_contigs_write (0: 64 MiB)

@@ -1970,7 +1970,7 @@ int gk_map_verify(gk_map *m, uint64_t *live, uint64_t *bad_slots, uint64_t *sum_
     unsigned long long *d = (unsigned long long *)map_scratch(m, 256), h[4] = {0, 0, 0, 0};
     if (!d) return GK_E_CAPACITY;
     GK_HIP(ctx, hipMemsetAsync(d, 0, 32, ctx->stream));
-    int grid = grid_for(ctx, m->capacity, BLOCK);
+    int grid = (int)std::min<u64>(grid_for(ctx, m->capacity, BLOCK), grid_cap(ctx));       // (the same cap, unless the test hook lowers it)
     GK_BY_SLOT(m, hipLaunchKernelGGL((k_verify<W, S>), dim3(grid), dim3(BLOCK), 0, ctx->stream, table_of<W, S>(m), d));
     GK_HIP(ctx, read_back(ctx, h, d, 4));
     if (live) *live = h[0];

@@ -119,7 +119,13 @@ int gk_map_slots(gk_map *m, uint64_t *slots);              /* current table capa
  * their hash does not name (must be 0), *sum_counts = sum of all counts (== occurrences inserted), *checksum = an
  * order-independent 64-bit checksum of the (key, count) set: two maps hold the same table iff (live, sum, checksum)
  * agree — whatever their sizes, slot orders and insert histories (partitions of one table ADD UP: the checksum of a
- * PartitionedDNAMap is the sum of its partitions' checksums mod 2^64).  Any may be NULL. */
+ * PartitionedDNAMap is the sum of its partitions' checksums mod 2^64).  Any may be NULL.
+ * The checksum, exactly (tests/checksum_ref.py restates it; 64-bit arithmetic mod 2^64 throughout).  mix64(x): x ^= x >> 33;
+ * x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33.  G = 0x9e3779b97f4a7c15.  With (lo, hi) the key
+ * as it crosses this ABI:
+ *     checksum = sum over the live entries of mix64(kh + count * G),
+ *     kh = mix64(lo ^ 0x243f6a8885a308d3)                       for k <= 31,
+ *     kh = mix64(lo ^ mix64(hi ^ 0x13198a2e03707344))           for k >= 34. */
 int gk_map_verify(gk_map *m, uint64_t *live, uint64_t *bad_slots, uint64_t *sum_counts, uint64_t *checksum);
 /* The count spectrum of the table: how many distinct k-mers occur exactly c times (what any k-mer counter reports: the coverage
  * peak, the error valley, a genome-size estimate).  One streaming pass over the slots on the device; nothing but the histogram
@@ -443,7 +449,8 @@ int gk_graph_retain_largest(gk_graph *g, uint64_t *kept_nodes, uint64_t *compone
  * of its nodes; order unspecified.  If cap < *n the call fails with GK_E_CAPACITY and *n holds the required size. */
 int gk_graph_component_stats(gk_graph *g, uint32_t *nodes_per_component, uint64_t *edge_len_per_component, uint64_t cap, uint64_t *n);
 /* Order-independent 64-bit checksums of the canonical serialisation: the node k-mer set, and the edge set
- * as (start k-mer, end k-mer, length, every base).  Two graphs with equal counts and checksums are the same graph. */
+ * as (start k-mer, end k-mer, length, every base).  Two graphs with equal counts and checksums are the same graph.  The exact
+ * formulas, and gk_graph_id_fingerprint's, stand with the graph file below, whose header stores all three. */
 int gk_graph_checksum(gk_graph *g, uint64_t *nodes_checksum, uint64_t *edges_checksum);
 /* How gk_graph_build spent its time: phase_ms6 = {degree classification (k_classify), terminals -> nodes + edge stubs,
  * unitig measurement (k_walk pass 0 or pointer jumping), pool reservation, unitig emission, node index + counts} (wall ms,
@@ -681,7 +688,19 @@ int gk_gfa_last_ms(const gk_gfa *c, float *ms4);
  * first base); out-orders that list exactly the bases with an out-edge; pool size = sum of ceil(len/4) and zero padding bits;
  * the last k bases of (start k-mer ++ sequence) = the end node's k-mer; then the recomputed checksum and id fingerprint =
  * the header's.  Any failure: GK_E_FORMAT (GK_E_INVALID if the file cannot be opened or read), *out stays NULL and
- * everything the call allocated is freed. */
+ * everything the call allocated is freed.
+ * The three values of header bytes 56..79 are part of format version 1, and these formulas are normative for it (restated in
+ * tests/checksum_ref.py, which tests/test_graph_file_cpu.py holds to the committed files).  mix64 and G as at gk_map_verify, all
+ * arithmetic mod 2^64, (lo, hi) a node's k-mer with hi = 0 for k <= 31:
+ *     nodes checksum = sum over the live nodes of mix64(lo ^ mix64(hi ^ 0x13198a2e03707344))
+ *     edges checksum = sum over the live edges of h(nbytes), where with s the start node's and t the end node's k-mer
+ *         h(0) = mix64(lo_s ^ mix64(hi_s ^ 1)) + 3 * mix64(lo_t ^ mix64(hi_t ^ 2)) + 5 * mix64(len),
+ *         h(i + 1) = mix64(h(i) ^ (byte_i + G * (i + 1))),  byte_i = byte i of the edge's ceil(len/4) pool bytes as the file stores
+ *         them (the unused high bits of the last byte zero); ids, array order and pool offsets do not enter
+ *     id fingerprint = mix64(mix64(node id bound ^ 0x626f756e6473) ^ (edge id bound + G))
+ *         + sum over the live nodes of m(m(m(0x6e6f6465, id), lo), hi)
+ *         + sum over the live edges of m(m(m(m(m(0x65646765, id), start node id), end node id), first base code), len),
+ *         m(a, v) = mix64(a ^ (v + G)). */
 int gk_graph_save(gk_graph *g, const char *path);                  /* MapGraph.write, Graph.scala:232-248 */
 int gk_graph_load(gk_ctx *ctx, const char *path, gk_graph **out);  /* Graph(file), Graph.scala:384-390 + GraphSimplifier.scala:157-169 */
 int gk_graph_k(const gk_graph *g);                                 /* GraphSimplifier.scala:153: k comes from the graph (< 0: error) */

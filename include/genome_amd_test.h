@@ -42,7 +42,7 @@ extern "C" {
  * spectrum and the read correction gets at most that many workgroups, the pair walks twice as many, instead of 8 (16) per CU; a
  * negative value is GK_E_INVALID): a graph the oracle can follow then makes every workgroup take several trips through its loop,
  * and one workgroup sees more component roots than its LDS table holds.  The insert pipeline's grids follow the table's geometry
- * and are not capped.  The list of capped kernels is in DESIGN.md section 5.  The contig kernels (gk_graph_contigs_plan,
+ * and are not capped; gk_map_verify's one pass over the slots is (its checksum is what the tests compare tables by).  The list of capped kernels is in DESIGN.md section 5.  The contig kernels (gk_graph_contigs_plan,
  * gk_contigs_read / gk_contigs_write) are capped by it too.
  * "contigs_chunk_bytes" (0: the default, 64 MiB; else rounded down to a multiple of 8, at least 8): the bytes of FASTA text
  * gk_contigs_read / gk_contigs_write emit per device chunk, so that a text of a few KiB goes through many chunks and both

@@ -1,12 +1,14 @@
 """The committed version-1 graph files (tests/golden/graph_v1_k*.gkg), read by a decoder of the documented layout
 (include/genome_amd.h) without the library or a GPU: the header and the (start, end, sequence) edge set must be the golden
-graph's.  This pins the file format."""
+graph's, and the header's checksum pair and id fingerprint are the documented formulas (tests/checksum_ref.py) over that content.
+This pins the file format, the three formulas included."""
 import json
 import os
 import struct
 
 import pytest
 
+import checksum_ref as CS
 from genome_amd import dna
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -67,3 +69,9 @@ def test_committed_graph_file_decodes_to_the_golden_graph(name, k):
     for n, o in order.items():
         listed = sorted("AGCT"[(o >> (4 + 2 * i)) & 3] for i in range(o & 7))
         assert listed == sorted(seq[0] for _, s, _, seq in edges if s == n)
+    # the three values of header bytes 56..79 are the formulas of include/genome_amd.h (restated in tests/checksum_ref.py) over
+    # the content just decoded
+    assert head["checksum"] == CS.graph_checksum(list(nodes.values()), [(nodes[s], nodes[t], seq) for _, s, t, seq in edges])
+    assert head["checksum"] == CS.graph_checksum(fx["nodes"], fx["edges"])
+    assert head["fingerprint"] == CS.id_fingerprint_of(nodes, edges, head["node_bound"], head["edge_bound"])
+    assert len({head["fingerprint"], *head["checksum"]}) == 3 and 0 not in head["checksum"] + (head["fingerprint"],)
