@@ -267,6 +267,7 @@ TEST_SIGNATURES = {
     "gk_test_scan_counts": (C.c_int, [vp, u32p, C.c_uint64, C.c_int, u64p, u64p]),
     "gk_test_slot_ranks": (C.c_int, [vp, u64p, u64p, C.c_uint64, u64p, u64p]),
     "gk_test_edge_path_keys": (C.c_int, [vp, u64p, u64p, u32p, u8p, u64p, u64p]),
+    "gk_test_skm_route_offsets": (C.c_int, [vp, C.c_int, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, C.c_uint64, u64p, u64p]),
 }
 TEST_LIB_PATH = os.path.join(_HERE, "libgenome_amd_test.so")
 

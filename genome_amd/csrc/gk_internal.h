@@ -81,8 +81,8 @@ struct gk_ctx {
     std::string err;
     int hook_dist_fail_reduce = 0;   // test hook: this context's next gk_dist_reduce_support fails its owner merge, after the records have been exchanged
     float graph_io_ms[4] = {0, 0, 0, 0};   // the last gk_graph_save / gk_graph_load on this context: file I/O, copies, kernels, whole call
-    int hook_max_grid = 0;           // test hook: the grid-stride launches of the graph phase, the value maps, the spectrum, gk_map_verify and the read correction get at
-                                     // most this many workgroups (0: cu_count * 8), so that a small input makes every workgroup take several trips
+    int hook_max_grid = 0;           // test hook: the grid-stride launches of the graph phase, the value maps, the spectrum, gk_map_verify, the read correction and the
+                                     // owner routing get at most this many workgroups (0: cu_count * 8; the super-k-mer routing cu_count * 6), so that a small input makes every workgroup take several trips
     mutable uint64_t hook_max_grid_uses = 0;   // ... and how many launches were sized under it (gk_test_grid_cap_uses: the switch's echo)
     int64_t hook_contigs_chunk = 0;  // test hook: text bytes per device chunk of gk_contigs_read / gk_contigs_write (0: 64 MiB)
     int64_t hook_place_slice = 0;    // test hook: characters per device slice of gk_placements_add_record (0: 64 Mi)
@@ -94,6 +94,10 @@ inline uint64_t grid_cap(const gk_ctx *ctx) {
     if (ctx->hook_max_grid <= 0) return (uint64_t)ctx->cu_count * 8;
     ctx->hook_max_grid_uses++;
     return (uint64_t)ctx->hook_max_grid;
+}
+// the same for a launch whose own limit is `per_cu` resident workgroups per CU (k_skm_route: 6, by its LDS)
+inline uint64_t grid_cap(const gk_ctx *ctx, int per_cu) {
+    return ctx->hook_max_grid > 0 ? grid_cap(ctx) : (uint64_t)ctx->cu_count * (uint64_t)per_cu;
 }
 
 namespace gk {

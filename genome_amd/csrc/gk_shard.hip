@@ -169,7 +169,7 @@ int gk_shard_reads_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_t nre
     GK_HIP(ctx, tmp.get(&d_cnt, 2 * MAX_PARTS));
     hipError_t e = hipMemsetAsync(d_cnt, 0, 2 * MAX_PARTS * sizeof(unsigned long long), ctx->stream);
     const u64 ntiles = (nreads + TILE_READS - 1) / TILE_READS;
-    const int grid = (int)std::min<u64>(ntiles, (u64)ctx->cu_count * 8);
+    int grid = (int)std::min<u64>(ntiles, grid_cap(ctx));       // (8 per CU, unless the test hook lowers it; asked once per launch)
     const uint8_t *rec = (const uint8_t *)dev_records;
     unsigned long long h_cnt[MAX_PARTS], h_cur[MAX_PARTS];
     if (e == hipSuccess) {
@@ -182,6 +182,7 @@ int gk_shard_reads_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_t nre
         e = hipMemcpyAsync(d_cnt + MAX_PARTS, h_cur, P * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream);
     }
     if (e == hipSuccess) {
+        grid = (int)std::min<u64>(ntiles, grid_cap(ctx));
         GK_BY_W(words_for_k(k), hipLaunchKernelGGL(k_shard_scatter<W>, dim3(grid), dim3(BLOCK), 0, ctx->stream, rec, nreads, stride, k, P, WindowLimits{read_len, nullptr}, d_cnt + MAX_PARTS, (u64 *)dev_keys_out));
         e = hipGetLastError();
     }

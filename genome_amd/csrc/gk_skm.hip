@@ -265,7 +265,7 @@ static int skm_route_go(gk_ctx *ctx, hipStream_t st, unsigned long long *d_count
     GK_HIP(ctx, hipMemsetAsync(d_counts, 0, SKM_COUNT_WORDS * sizeof(unsigned long long), st));
     const u32 stride = 1 + (read_len + 3) / 4;
     const u64 ntiles = (nreads + TILE_READS - 1) / TILE_READS;
-    const int grid = (int)std::min<u64>(ntiles, (u64)ctx->cu_count * 6);
+    const int grid = (int)std::min<u64>(ntiles, grid_cap(ctx, 6));       // (6 per CU, unless the test hook lowers it)
     const uint8_t *rec = (const uint8_t *)dev_records;
     // the last counter word: [0] a region overflowed, [1] a record's length byte exceeded read_len (clamped).  Both travel back
     // with the counts, so whoever finishes the route — on any thread — needs no other stream and no shared flag word.

@@ -7,6 +7,7 @@
 //   * gk_test_support_last_walk: which walker (device kernel / host fallback) did the orientations of the last gk_graph_walk_pairs;
 //   * gk_test_scan_counts: gk_scan.h's scan_counts over counts from the host, between guard words (either overload);
 //   * gk_test_slot_ranks: the pointer-jumping build's slot -> rank structure of a map's table (gk_graph.hip: rank_build);
+//   * gk_test_skm_route_offsets: the super-k-mer routing over an offset table (gk_skm.hip: k_skm_route<SLOT, true>), in one process;
 //   * gk_dist_create_loopback: a transport whose ranks are threads of ONE process on ONE device, so that gk_dist_* runs with
 //     world > 1 on a one-GPU box (RCCL refuses two ranks on one device).
 // The product library (libgenome_amd.so) links none of this; its header is include/genome_amd.h, this file's is
@@ -207,6 +208,18 @@ int gk_test_slot_ranks(gk_map *map, uint64_t *masks, uint64_t *bases, uint64_t c
     if (!map || !map->ctx) return fail(nullptr, GK_E_INVALID, "gk_test_slot_ranks: null map handle");
     if (!masks || !bases || !nblk || !total) return fail(map->ctx, GK_E_INVALID, "gk_test_slot_ranks: null argument");
     return graph_slot_ranks(map, masks, bases, cap_blocks, nblk, total);
+}
+
+// gk_shard_superkmers_dev's three steps over the offset-table overload of the launch (the product reaches it through gk_dist_* only)
+int gk_test_skm_route_offsets(gk_ctx *ctx, int k, const void *dev_records, const uint32_t *dev_offsets, uint64_t nreads, uint64_t windows, int P,
+                              void *dev_out, uint64_t out_cap_records, uint64_t *rec_counts_host, uint64_t *kmer_counts_host) {
+    if (!ctx) return fail(nullptr, GK_E_INVALID, "null ctx");
+    if (!rec_counts_host || !kmer_counts_host) return fail(ctx, GK_E_INVALID, "gk_test_skm_route_offsets: null argument");
+    if (!ctx->skm_counts) GK_HIP(ctx, pool_malloc(ctx, &ctx->skm_counts, SKM_COUNT_WORDS * sizeof(unsigned long long)));
+    unsigned long long h[SKM_COUNT_WORDS];
+    if (int rc = skm_route_launch(ctx, ctx->stream, (unsigned long long *)ctx->skm_counts, h, k, dev_records, dev_offsets, nreads, windows, P, dev_out, out_cap_records)) return rc;
+    GK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return skm_route_finish(ctx, h, nreads && windows, P, out_cap_records, rec_counts_host, kmer_counts_host);
 }
 
 }  // extern "C"

@@ -287,7 +287,20 @@ int gk_shard_reads_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_t nre
  * gk_map_count_superkmers_dev.  dev_out is cut into P regions of out_cap_records / P slots; owner p's
  * records fill the start of region p; rec_counts_host[p] / kmer_counts_host[p] = records / windows
  * for owner p.  If a region is too small the call fails with GK_E_CAPACITY after filling the counts
- * (max of rec_counts_host = slots a region needs); retry with a larger buffer. */
+ * (max of rec_counts_host = slots a region needs); retry with a larger buffer.  A region that holds
+ * exactly its records is large enough; slots of a region past its records are not written.
+ * A read's length byte may be below read_len (a shorter read in the same stride; the bytes past
+ * its last base are ignored); a read shorter than k has no window and gives no record.
+ * What a receiver may rely on: every window of every read appears in exactly one record; every
+ * window of a record is at its owner (gk_owner_of); k <= len <= (slot - 1) * 4 for the length byte
+ * of every record; the slot's bits past the last base are zero.
+ * How the runs are cut is THIS VERSION's rule, pinned by tests/route_ref.py and
+ * tests/test_route_gpu.py, and nothing a receiver may build on: a read of `len` bases has
+ * len - k + 1 windows; they are taken in blocks of 64 counted from the read's first window; inside
+ * a block every maximal run of equal owners is cut, from its start, into pieces of at most
+ * rmax = (slot - 1) * 4 - k + 1 windows; a piece of wl windows starting at window p is one record:
+ * byte 0 = wl + k - 1, then bases p .. p + wl + k - 2 of the read.  The ORDER of the records inside
+ * a region is unspecified (it differs from call to call). */
 int gk_skm_slot_bytes(int k);
 int gk_shard_superkmers_dev(gk_ctx *ctx, int k, const void *dev_records, uint64_t nreads, int read_len, int P,
                             void *dev_out, uint64_t out_cap_records, uint64_t *rec_counts_host, uint64_t *kmer_counts_host);

@@ -42,7 +42,10 @@ extern "C" {
  * spectrum and the read correction gets at most that many workgroups, the pair walks twice as many, instead of 8 (16) per CU; a
  * negative value is GK_E_INVALID): a graph the oracle can follow then makes every workgroup take several trips through its loop,
  * and one workgroup sees more component roots than its LDS table holds.  The insert pipeline's grids follow the table's geometry
- * and are not capped; gk_map_verify's one pass over the slots is (its checksum is what the tests compare tables by).  The list of capped kernels is in DESIGN.md section 5.  The contig kernels (gk_graph_contigs_plan,
+ * and are not capped; gk_map_verify's one pass over the slots is (its checksum is what the tests compare tables by).  The owner
+ * routing is capped as well: the one launch of gk_shard_superkmers_dev (and of the routing inside gk_dist_*, fixed stride or
+ * offset table: 6 workgroups per CU when the switch is 0) and both launches of gk_shard_reads_dev, so that 200 reads — four
+ * tiles — make one workgroup take a regrouped tile and then ordinary ones and carry its counters across tiles.  The list of capped kernels is in DESIGN.md section 5.  The contig kernels (gk_graph_contigs_plan,
  * gk_contigs_read / gk_contigs_write) are capped by it too.
  * "contigs_chunk_bytes" (0: the default, 64 MiB; else rounded down to a multiple of 8, at least 8): the bytes of FASTA text
  * gk_contigs_read / gk_contigs_write emit per device chunk, so that a text of a few KiB goes through many chunks and both
@@ -126,6 +129,14 @@ int gk_test_slot_ranks(gk_map *map, uint64_t *masks, uint64_t *bases, uint64_t c
  * canonical order (0xffffffff dead), dup = 1 where another live edge has the same key.  *nlive = the live edges, *fingerprint =
  * the replica's path fingerprint.  The hash kernel's grid honours "test_max_grid".  GK_E_INVALID for a null pointer. */
 int gk_test_edge_path_keys(gk_graph *g, uint64_t *h1, uint64_t *h2, uint32_t *canon, uint8_t *dup, uint64_t *nlive, uint64_t *fingerprint);
+
+/* gk_shard_superkmers_dev over a ragged stream: record r spans [dev_offsets[r], dev_offsets[r + 1]) of dev_records (nreads + 1
+ * 32-bit offsets on the device; the records lie back to back, each 1 + ceil(len / 4) bytes with len its length byte, as a host
+ * that walked the framing builds the table) and `windows` = the k-mer windows of all records.  It is the offset-table form of
+ * the routing launch that only gk_dist_* reaches in the product (csrc/gk_skm.hip: skm_route_launch, the same function), followed
+ * by the same wait and the same finish as gk_shard_superkmers_dev: regions, counts and GK_E_CAPACITY are as described there. */
+int gk_test_skm_route_offsets(gk_ctx *ctx, int k, const void *dev_records, const uint32_t *dev_offsets, uint64_t nreads, uint64_t windows, int P,
+                              void *dev_out, uint64_t out_cap_records, uint64_t *rec_counts_host, uint64_t *kmer_counts_host);
 
 /* TEST transport: the ranks are threads of ONE process on ONE device; sends, receives and reductions go through a hub in the
  * library (device-to-device copies matched pairwise in posting order) instead of RCCL, which refuses two ranks on one GPU.  Every
