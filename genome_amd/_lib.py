@@ -201,6 +201,8 @@ SIGNATURES = {
     "gk_graph_destroy": (None, [vp]),
     "gk_graph_counts": (C.c_int, [vp, u64p, u64p, u64p]),
     "gk_graph_simplify": (C.c_int, [vp]),
+    "gk_graph_build_cycles": (C.c_int, [vp, C.POINTER(vp), u64p]),
+    "gk_graph_simplify_keep_cycles": (C.c_int, [vp, u64p]),
     "gk_graph_remove_bubbles": (C.c_int, [vp]),
     "gk_graph_remove_edges": (C.c_int, [vp, u64p, u64p, u8p, C.c_uint64, u64p]),
     "gk_graph_retain_largest": (C.c_int, [vp, u64p, u64p]),

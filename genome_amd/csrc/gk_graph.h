@@ -65,6 +65,8 @@ struct gk_graph {
     int used_masks = 0;          // the classify came with the table (masks computed by the keys' owners, gk_dist_gather_map): no k_classify ran
     float mbt_ms = 0;            // building the minimizer-bucketed copy of the table, when the build used one ("graph_mbt")
     u64 mbt_slots = 0;
+    bool keep_cycles = false;    // gk_graph_build_cycles: the build ends by appending the perfect cycles' anchors and arcs
+    u64 cycle_stats[6] = {0, 0, 0, 0, 0, 0};
     // host snapshot of the edge arrays for the paired-end walks, valid while `epoch` (bumped by every edit) has not moved:
     // a stream of gk_graph_walk_pairs batches downloads the graph once
     u64 epoch = 0, snap_epoch = ~0ull;
@@ -123,6 +125,23 @@ __device__ __forceinline__ u64 block_reserve(u32 v, unsigned long long *cursor, 
     return r;
 }
 
+// byte offsets of the sequences of the edges first_edge .. n_edges-1 in the pool (each edge starts on a byte boundary): base +
+// what the cursor, which counts from 0, hands out.  The pointer-jumping build (all edges) and the perfect cycles' arcs.
+static __global__ __launch_bounds__(BLOCK) void k_reserve_pool(GraphView g, u64 first_edge, u64 base, unsigned long long *cursor) {
+    __shared__ u32 lds4[BLOCK / 64];
+    __shared__ unsigned long long s_base;
+    const u64 n = g.n_edges - first_edge;
+    const u64 ngroups = (n + BLOCK - 1) / BLOCK;
+    for (u64 grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
+        const u64 e = first_edge + grp * BLOCK + threadIdx.x;
+        // per-block totals stay < 2^32 for edges up to 16M bases each; longer ones reserve alone
+        u64 bytes = e < g.n_edges ? (g.e_len[e] + 3) / 4 : 0;
+        u32 small = bytes < (1u << 22) ? (u32)bytes : 0u;
+        u64 o = block_reserve(small, cursor, lds4, &s_base);
+        if (e < g.n_edges) g.e_off[e] = base + (small == bytes ? o : atomicAdd(cursor, (unsigned long long)bytes));
+    }
+}
+
 // MapGraph.removeEdge (Graph.scala:191-195) of a live edge, safe beside other lanes removing other edges: the start node's
 // out-edge slot and insertion order, the edge itself, the end node's in-degree (k_remove_edges_by_id, k_tip_apply)
 __device__ __forceinline__ void graph_remove_edge(const GraphView &g, u32 e) {
@@ -168,6 +187,22 @@ int graph_slot_ranks(gk_map *m, uint64_t *masks, uint64_t *bases, uint64_t cap_b
 // Node.inEdgeIds as CSR by end node of the graph as it is now: (*off)[v] .. (*off)[v+1] index *list; both live in `tmp`.
 // Stream-ordered, no synchronisation; `who` names the entry point in the error text.  (Not exported, like DevScratch.)
 __attribute__((visibility("hidden"))) int graph_in_lists(gk_graph *g, DevScratch &tmp, const char *who, unsigned long long **off, u32 **list);
+
+// Perfect cycles (gk_cycles.hip; the rule is in include/genome_amd.h, "perfect cycles").  The hot step at both levels is the minimum
+// over each cycle of a functional graph, by pointer doubling on ONE packed word per element: bits 0..31 the pointer, bits 32..63
+// the index of the smallest key met so far (CY_LEAVES: the chain ends outside the set), CY_UNREG: not in the set.
+static constexpr u64 CY_UNREG = ~0ull;
+static constexpr u32 CY_LEAVES = 0xFFFFFFFFu;
+// st[0..n) as the caller initialised it — a cycle candidate u: succ(u) | u << 32; an element whose successor is outside the set:
+// u | CY_LEAVES << 32 (a fixed point); anything else CY_UNREG.  On return every element of a cycle holds the index of its cycle's
+// smallest key (the first one met going forward on a tie), every other candidate CY_LEAVES.  *rounds = ceil(log2 n).  No sync.
+__attribute__((visibility("hidden"))) int cycles_min(gk_ctx *ctx, DevScratch &tmp, u64 *st, u64 n, const u64 *klo, const u64 *khi, u64 *rounds);
+// the members of the k-mer table's perfect cycles, dense (gk_graph.hip fills it): successor, anchor key, the base that follows
+// (bits 0..1) | the k-mer is not its own anchor key << 2 | palindrome << 3, and the member that is the reverse complement
+struct CycleMembers { u64 n; u32 *succ; u64 *klo, *khi; uint8_t *meta; u32 *twin; };
+__attribute__((visibility("hidden"))) int graph_append_cycles(gk_graph *g, DevScratch &tmp, const CycleMembers &cm, uint64_t *stats6);
+// the keeping simplify's part between k_node_class and k_chain: class 2 -> 0, the anchors of all-interior cycles -> 0
+__attribute__((visibility("hidden"))) int cycles_keep_classes(gk_graph *g, DevScratch &tmp, uint8_t *cls, uint64_t *stats4);
 
 // Edge coverage from a count table (gk_coverage.hip), for the callers that decide something from it (tips, bubbles) or print it
 // (gk_contigs.hip).  Per-edge results are indexed by edge id and live in the caller's `tmp`; coverage_pass writes them for every

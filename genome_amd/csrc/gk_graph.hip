@@ -806,20 +806,165 @@ __global__ __launch_bounds__(BLOCK) void k_pj_emit(TT t, int k, GraphView g, con
     }
 }
 
-// byte offsets of the edge sequences in the pool (each edge starts on a byte boundary)
-__global__ __launch_bounds__(BLOCK) void k_reserve_pool(GraphView g, u64 first_edge, unsigned long long *cursor) {
-    __shared__ u32 lds4[BLOCK / 64];
-    __shared__ unsigned long long s_base;
-    const u64 n = g.n_edges - first_edge;
-    const u64 ngroups = (n + BLOCK - 1) / BLOCK;
-    for (u64 grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const u64 e = first_edge + grp * BLOCK + threadIdx.x;
-        // per-block totals stay < 2^32 for edges up to 16M bases each; longer ones reserve alone
-        u64 bytes = e < g.n_edges ? (g.e_len[e] + 3) / 4 : 0;
-        u32 small = bytes < (1u << 22) ? (u32)bytes : 0u;
-        u64 o = block_reserve(small, cursor, lds4, &s_base);
-        if (e < g.n_edges) g.e_off[e] = small == bytes ? o : atomicAdd(cursor, (unsigned long long)bytes);
+// ---------------------------------------------------------------------------------------------
+// Perfect cycles kept (gk_graph_build_cycles; the rule: include/genome_amd.h "perfect cycles").  The table-reading half: which
+// oriented k-mers the plain build left on no node and inside no edge, and — dense, for gk_cycles.hip — their successors, anchor
+// keys and next bases.  The plain build has run: a terminal slot's annotation is its node, every other slot still has its masks.
+// ---------------------------------------------------------------------------------------------
+// oriented k-mers with one way in and one way out (a palindrome is ONE): those inside the plain build's edges, and the members
+template <int W, class TT>
+__global__ __launch_bounds__(BLOCK) void k_cyc_census(TT t, int k, unsigned long long *out) {
+    __shared__ u32 s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    u32 cnt = 0;
+    const u64 ncap = t.capacity();
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < ncap; i += (u64)gridDim.x * BLOCK) {
+        if (!slot_live(&t.slots[i])) continue;
+        const u32 aux = t.slots[i].aux;
+        if (aux & (AUX_NODE | AUX_TERMINAL | AUX_SECONDARY)) continue;
+        if (__popc(aux & 15u) != 1 || __popc((aux >> 4) & 15u) != 1) continue;
+        const Kmer<W> y = slot_key(t, i);
+        cnt += (y == revcomp(y, k)) ? 1u : 2u;
     }
+    if (cnt) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(out, (unsigned long long)s_cnt);
+}
+// after the absorbing rounds (k_pj_init, k_pj_round): a registered state whose pointer has not reached a pre-terminal is on a
+// cycle.  Both orientations of a palindrome were registered and nothing points at the second: it is left out.
+template <int W, class TT>
+__global__ __launch_bounds__(BLOCK) void k_cyc_members(TT t, int k, const RankBlk *__restrict__ rb, const u64 *__restrict__ st, u32 *flag) {
+    const u64 ncap = t.capacity();
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < ncap; i += (u64)gridDim.x * BLOCK) {
+        if (!slot_live(&t.slots[i])) continue;
+        const u32 aux = t.slots[i].aux;
+        if (aux & (AUX_NODE | AUX_TERMINAL | AUX_SECONDARY)) continue;
+        const Kmer<W> y = slot_key(t, i);
+        const bool pal = y == revcomp(y, k);
+        const u64 r = rank_of(rb, i);
+        for (int ori = 0; ori < (pal ? 1 : 2); ori++) {
+            const u64 su = st[2 * r + ori];
+            if (su == PJ_UNREG) continue;
+            const u64 pu = (su & PJ_ABS) ? su : st[pj_nxt(su)];
+            if (!pj_absorbed(pu)) flag[2 * r + ori] = 1u;
+        }
+    }
+}
+template <int W, class TT>
+__global__ __launch_bounds__(BLOCK) void k_cyc_fill(TT t, int k, const RankBlk *__restrict__ rb, const u32 *__restrict__ flag,
+                                                    const unsigned long long *__restrict__ off, CycleMembers cm, u32 *err) {
+    const u64 ncap = t.capacity();
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < ncap; i += (u64)gridDim.x * BLOCK) {
+        if (!slot_live(&t.slots[i])) continue;
+        const u32 aux = t.slots[i].aux;
+        if (aux & (AUX_NODE | AUX_TERMINAL | AUX_SECONDARY)) continue;
+        const u64 r = rank_of(rb, i);
+        if (!flag[2 * r] && !flag[2 * r + 1]) continue;
+        const Kmer<W> y = slot_key(t, i), ry = revcomp(y, k);
+        const bool pal = y == ry;
+        for (int ori = 0; ori < 2; ori++) {
+            const u64 u = 2 * r + ori;
+            if (!flag[u]) continue;
+            const u64 d = off[u];
+            if (d >= cm.n) { *err = 1; continue; }
+            const Kmer<W> x = ori ? ry : y, rx = ori ? y : ry;
+            const int nb = single_out_base(aux, ori);
+            bool fwd = true;
+            const i64 ws = nb < 0 ? -1 : table_find_either(t, append_base(x, nb, k), k, &fwd);
+            u64 sd = d;
+            if (ws < 0) *err = 2;
+            else {
+                const u64 su = 2 * rank_of(rb, (u64)ws) + (fwd ? 0u : 1u);
+                if (!flag[su] || off[su] >= cm.n) *err = 3;             // the successor of a member is a member
+                else sd = off[su];
+            }
+            cm.succ[d] = (u32)sd;
+            const bool isrc = kmer_less(rx, x);
+            const Kmer<W> key = isrc ? rx : x;                          // the anchor key: min(x, rc x)
+            cm.klo[d] = key.lo;
+            if constexpr (W == 2) cm.khi[d] = key.hi;
+            cm.meta[d] = (uint8_t)((nb & 3) | (isrc ? 4 : 0) | (pal ? 8 : 0));
+            u64 tw = d;
+            if (!pal) { if (!flag[u ^ 1] || off[u ^ 1] >= cm.n) *err = 4; else tw = off[u ^ 1]; }      // the reverse complement of a cycle is a cycle
+            cm.twin[d] = (u32)tw;
+        }
+    }
+}
+// succ must be a permutation of the members for the way back (k_cya_init's pred) to be defined: every member is hit once
+__global__ __launch_bounds__(BLOCK) void k_cyc_hits(const u32 *__restrict__ succ, u64 n, u32 *hits) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) atomicAdd(&hits[succ[i]], 1u);
+}
+__global__ __launch_bounds__(BLOCK) void k_cyc_hits_check(const u32 *__restrict__ hits, u64 n, u32 *err) {
+    for (u64 i = (u64)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (u64)gridDim.x * BLOCK) if (hits[i] != 1u) *err = 5;
+}
+
+template <int W, class TT> static int graph_add_cycles(gk_map *m, gk_graph *g, TT t) {
+    gk_ctx *ctx = m->ctx;
+    const int k = m->k;
+    const u64 tcap = t.capacity();
+    DevScratch tmp(ctx);
+    unsigned long long *d_cand = nullptr, cand = 0;
+    u32 *d_err = nullptr;
+    tmp.zeroed(&d_cand, 1);
+    tmp.zeroed(&d_err, 4);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_build_cycles: alloc");
+    // the cheap exit: every (1,1) oriented k-mer is inside one edge of the plain build (len - 1 of them per edge) or on a cycle
+    hipLaunchKernelGGL((k_cyc_census<W, TT>), dim3(ggrid(ctx, tcap)), dim3(BLOCK), 0, ctx->stream, t, k, d_cand);
+    hipError_t e = read_back(ctx, &cand, d_cand);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build_cycles: census");
+    const u64 inside = g->live_len - g->live_edges;
+    if (cand < inside) return fail(ctx, GK_E_STATE, "gk_graph_build_cycles: the edges hold more interior k-mers than the table has");
+    const u64 members = cand - inside;
+    if (!members) return GK_OK;
+    if (members >= (1ull << 31)) return fail(ctx, GK_E_CAPACITY, "more than 2^31 k-mers on perfect cycles");
+    // which ones: the build's absorbing pointer jumping again (whichever unitig construction the build used, its state is gone)
+    const u64 nstates = 2 * m->size, nblk = (tcap + 63) / 64, nchunks = (nblk + RANK_CHUNK - 1) / RANK_CHUNK;
+    if (nstates >= PJ_MAX_STATES) return fail(ctx, GK_E_CAPACITY, "more than 2^33 k-mers: beyond the pointer-jumping state's index");
+    u64 *st = nullptr;
+    RankBlk *rb = nullptr;
+    u32 *chunk_tot = nullptr, *flag = nullptr, *hits = nullptr;
+    u64 *chunk_base = nullptr;
+    unsigned long long *off = nullptr;
+    tmp.get(&rb, nblk); tmp.get(&chunk_tot, nchunks); tmp.get(&chunk_base, nchunks + 1); tmp.get(&st, nstates);
+    tmp.zeroed(&flag, nstates); tmp.get(&off, nstates + 1);
+    if (tmp.error() == hipSuccess) tmp.note(hipMemsetAsync(st, 0xff, nstates * 8, ctx->stream));       // PJ_UNREG
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_build_cycles: pointer-jumping arrays");
+    rank_build<W, TT>(ctx, t, rb, nblk, chunk_tot, chunk_base, nchunks);
+    hipLaunchKernelGGL((k_pj_init<W, TT>), dim3(ggrid(ctx, tcap)), dim3(BLOCK), 0, ctx->stream, t, k, rb, st);
+    int max_rounds = 2;
+    while ((1ull << (max_rounds - 2)) < std::max<u64>(nstates, 2)) max_rounds++;
+    for (int round = 0; round < max_rounds; round++)        // (no early exit: with members something moves in every round)
+        hipLaunchKernelGGL(k_pj_round, dim3(ggrid(ctx, nstates)), dim3(BLOCK), 0, ctx->stream, st, nstates, d_err + 1);
+    hipLaunchKernelGGL((k_cyc_members<W, TT>), dim3(ggrid(ctx, tcap)), dim3(BLOCK), 0, ctx->stream, t, k, rb, st, flag);
+    tmp.note(scan_counts(ctx, tmp, flag, nstates, off));
+    unsigned long long ranked = 0, M = 0;
+    u32 h_err[4] = {0, 0, 0, 0};
+    e = tmp.error();
+    if (e == hipSuccess) e = read_back(ctx, {{&ranked, chunk_base + nchunks, 8}, {&M, off + nstates, 8}, {h_err, d_err, 16}});
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build_cycles: members");
+    if (ranked != m->size) return fail(ctx, GK_E_STATE, "live slots (" + std::to_string(ranked) + ") differ from the map's size (" + std::to_string(m->size) + ")");
+    if (h_err[2]) return fail(ctx, GK_E_STATE, "pointer jumping met an unregistered successor (code " + std::to_string(h_err[2]) + ")");
+    if (M != members) return fail(ctx, GK_E_STATE, "gk_graph_build_cycles: " + std::to_string(M) + " k-mers on cycles, the census says " + std::to_string(members));
+    tmp.release(st);
+    CycleMembers cm{};
+    cm.n = M;
+    tmp.get(&cm.succ, M); tmp.get(&cm.klo, M); tmp.get(&cm.meta, M); tmp.get(&cm.twin, M);
+    if (W == 2) tmp.get(&cm.khi, M);
+    tmp.zeroed(&hits, M);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_build_cycles: member arrays");
+    hipLaunchKernelGGL((k_cyc_fill<W, TT>), dim3(ggrid(ctx, tcap)), dim3(BLOCK), 0, ctx->stream, t, k, rb, flag, off, cm, d_err);
+    hipLaunchKernelGGL(k_cyc_hits, dim3(ggrid(ctx, M)), dim3(BLOCK), 0, ctx->stream, cm.succ, (u64)M, hits);
+    hipLaunchKernelGGL(k_cyc_hits_check, dim3(ggrid(ctx, M)), dim3(BLOCK), 0, ctx->stream, hits, (u64)M, d_err);
+    e = read_back(ctx, h_err, d_err, 1);
+    if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build_cycles: fill");
+    if (h_err[0]) return fail(ctx, GK_E_STATE, "gk_graph_build_cycles: the cycle members are not closed (code " + std::to_string(h_err[0]) + ")");
+    tmp.release(rb); tmp.release(chunk_tot); tmp.release(chunk_base); tmp.release(flag); tmp.release(off); tmp.release(hits);
+    if (int rc = graph_append_cycles(g, tmp, cm, g->cycle_stats)) return rc;
+    g->index_ready = false;
+    const int rc = graph_refresh_counts(g);
+    g->walked_bases = g->live_len;
+    return rc;
 }
 
 static void graph_free_arrays(gk_graph *g) {
@@ -949,7 +1094,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
         lap(2);
         g->used_pj = use_pj ? 1 : 0;
-        if (e == hipSuccess && use_pj) hipLaunchKernelGGL(k_reserve_pool, dim3(ggrid(ctx, nE)), dim3(BLOCK), 0, ctx->stream, g->v, (u64)0, &d_cnt[4]);
+        if (e == hipSuccess && use_pj) hipLaunchKernelGGL(k_reserve_pool, dim3(ggrid(ctx, nE)), dim3(BLOCK), 0, ctx->stream, g->v, (u64)0, (u64)0, &d_cnt[4]);
         if (e == hipSuccess) e = read_back(ctx, {{h_cnt, d_cnt, 56}, {&h_err, d_err, 4}});
         if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_build: walk");
         if (h_err) return fail(ctx, GK_E_STATE, "unitig construction failed (code " + std::to_string(h_err) +
@@ -991,6 +1136,7 @@ template <int W, class TT> static int graph_build_impl(gk_map *m, gk_graph *g, T
     rc = graph_refresh_counts(g);
     g->walked_bases = g->live_len;
     lap(5);
+    if (rc == GK_OK && g->keep_cycles) rc = graph_add_cycles<W, TT>(m, g, t);      // (gk_graph_build_cycles: after the plain build, which it leaves as it is)
     return rc;
 }
 
@@ -1114,9 +1260,7 @@ int graph_slot_ranks(gk_map *m, uint64_t *masks, uint64_t *bases, uint64_t cap_b
     return GK_OK;
 }
 
-extern "C" {
-
-int gk_graph_build(gk_map *m, gk_graph **out) {
+static int graph_build_common(gk_map *m, gk_graph **out, bool keep_cycles, uint64_t *stats6) {
     if (!m || !m->ctx) return fail(nullptr, GK_E_INVALID, "null map handle");
     if (!out) return fail(m->ctx, GK_E_INVALID, "gk_graph_build: out is NULL");
     *out = nullptr;
@@ -1129,6 +1273,7 @@ int gk_graph_build(gk_map *m, gk_graph **out) {
     g->ctx = m->ctx;
     g->k = m->k;
     g->W = m->W;
+    g->keep_cycles = keep_cycles;
     // (the build re-uses the annotation word — a terminal slot's becomes its node — so owner-computed masks serve ONE build)
     const bool masks_valid = m->masks_valid;
     m->masks_valid = false;
@@ -1138,8 +1283,18 @@ int gk_graph_build(gk_map *m, gk_graph **out) {
         delete g;
         return rc;
     }
+    if (stats6) for (int i = 0; i < 6; i++) stats6[i] = g->cycle_stats[i];
     *out = g;
     return GK_OK;
+}
+
+extern "C" {
+
+int gk_graph_build(gk_map *m, gk_graph **out) { return graph_build_common(m, out, false, nullptr); }
+
+int gk_graph_build_cycles(gk_map *m, gk_graph **out, uint64_t *stats6) {
+    if (stats6) for (int i = 0; i < 6; i++) stats6[i] = 0;
+    return graph_build_common(m, out, true, stats6);
 }
 
 void gk_graph_destroy(gk_graph *g) {

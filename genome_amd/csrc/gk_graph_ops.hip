@@ -932,7 +932,10 @@ int gk_graph_contig_stats(gk_graph *g, uint64_t longer_than, uint64_t *count, ui
     return GK_OK;
 }
 
-int gk_graph_simplify(gk_graph *g) {
+}  // extern "C"
+
+// keep_stats4 == nullptr: MapGraph.simplifyGraph as it is; otherwise the keeping form (gk_graph_simplify_keep_cycles)
+static int graph_simplify(gk_graph *g, uint64_t *keep_stats4) {
     if (int rc = check_graph(g)) return rc;
     gk_ctx *ctx = g->ctx;
     GraphView &v = g->v;
@@ -954,6 +957,10 @@ int gk_graph_simplify(gk_graph *g) {
     const int gn = ggrid(ctx, v.n_nodes), ge = ggrid(ctx, std::max<u64>(v.n_edges, 1));
     hipLaunchKernelGGL(k_in_single, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, in_single);
     hipLaunchKernelGGL(k_node_class, dim3(gn), dim3(BLOCK), 0, ctx->stream, v, in_single, cls);
+    const u64 nodes_before = g->live_nodes;
+    if (keep_stats4) {
+        if (int rc = cycles_keep_classes(g, tmp, cls, keep_stats4)) return rc;
+    }
     const u64 old_edges = v.n_edges, old_pool = g->pool_used;
     hipLaunchKernelGGL(k_chain, dim3(ge), dim3(BLOCK), 0, ctx->stream, v, cls, 0, old_edges, old_pool, d_cnt, merged_key, (LongPiece *)nullptr);
     hipError_t e = read_back(ctx, h_cnt, d_cnt, 3);
@@ -981,7 +988,20 @@ int gk_graph_simplify(gk_graph *g) {
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gk_graph_simplify: finish");
-    return graph_refresh_counts(g);
+    const int rc = graph_refresh_counts(g);
+    if (keep_stats4) keep_stats4[3] = nodes_before - g->live_nodes;
+    return rc;
+}
+
+extern "C" {
+
+int gk_graph_simplify(gk_graph *g) { return graph_simplify(g, nullptr); }
+
+int gk_graph_simplify_keep_cycles(gk_graph *g, uint64_t *stats4) {
+    uint64_t st[4] = {0, 0, 0, 0};
+    const int rc = graph_simplify(g, st);
+    if (stats4) for (int i = 0; i < 4; i++) stats4[i] = st[i];
+    return rc;
 }
 
 int gk_graph_remove_bubbles(gk_graph *g) {

@@ -21,6 +21,7 @@ class HipGraph:
 
     def __init__(self, ctx, k: int, handle):
         self.ctx, self.k, self.h = ctx, k, handle
+        self._cycle_stats = None
 
     def close(self):
         if self.h:
@@ -50,8 +51,19 @@ class HipGraph:
         L.check(L.lib().gk_graph_contig_stats(self.h, int(longer_than), *[C.byref(x) for x in v]), self.ctx.h)
         return dict(zip(("count", "sum", "median", "n50", "max"), (x.value for x in v)))
 
-    def simplifyGraph(self):                       # Graph.scala:211-230
-        L.check(L.lib().gk_graph_simplify(self.h), self.ctx.h)
+    def simplifyGraph(self, keep_cycles: bool = False):    # Graph.scala:211-230
+        """keep_cycles: self-loop nodes stay and every cycle of merge-away nodes keeps its anchors (include/genome_amd.h, "perfect
+        cycles"); returns the CYCLE_SIMPLIFY_STATS dict then, None otherwise."""
+        if not keep_cycles:
+            L.check(L.lib().gk_graph_simplify(self.h), self.ctx.h)
+            return None
+        st = (C.c_uint64 * 4)()
+        L.check(L.lib().gk_graph_simplify_keep_cycles(self.h, st), self.ctx.h)
+        return dict(zip(CYCLE_SIMPLIFY_STATS, (int(x) for x in st)))
+
+    def cycleStats(self):
+        """The CYCLE_BUILD_STATS dict of buildGraph(keep_cycles=True); None for a graph built without it (or loaded)."""
+        return self._cycle_stats
 
     def removeBubbles(self):                       # Graph.scala:125-149
         L.check(L.lib().gk_graph_remove_bubbles(self.h), self.ctx.h)
@@ -1012,20 +1024,34 @@ def insertRange(hist, trim: int = 25, min_observations: int = 1000):
     return lo.value, hi.value, med.value
 
 
-def buildGraph(k: int, kmersFreq) -> HipGraph:
+CYCLE_BUILD_STATS = ("cycle_kmers", "cycles", "anchors", "self_complementary", "longest", "rounds")
+
+CYCLE_SIMPLIFY_STATS = ("kept_self_loops", "cycles_merged", "anchors_kept", "nodes_removed")
+
+
+def buildGraph(k: int, kmersFreq, keep_cycles: bool = False) -> HipGraph:
     """Graph.buildGraph(k, kmersFreq) (Graph.scala:269-382).  A PartitionedDNAMap is gathered into
-    one table first (the walk crosses partitions arbitrarily)."""
+    one table first (the walk crosses partitions arbitrarily).
+    keep_cycles: perfect cycles, which the reference ignores (:375), become self-loops at their anchors (gk_graph_build_cycles);
+    the CYCLE_BUILD_STATS are then HipGraph.cycleStats()."""
     own = None
     if isinstance(kmersFreq, PartitionedDNAMap):
         own = kmersFreq = kmersFreq.merged()
     assert isinstance(kmersFreq, HipDNAMap) and kmersFreq.k == k
     h = L.vp()
+    st = (C.c_uint64 * 6)()
     try:
-        L.check(L.lib().gk_graph_build(kmersFreq.h, C.byref(h)), kmersFreq.ctx.h)
+        if keep_cycles:
+            L.check(L.lib().gk_graph_build_cycles(kmersFreq.h, C.byref(h), st), kmersFreq.ctx.h)
+        else:
+            L.check(L.lib().gk_graph_build(kmersFreq.h, C.byref(h)), kmersFreq.ctx.h)
     finally:
         if own is not None:
             own.close()
-    return HipGraph(kmersFreq.ctx, k, h)
+    g = HipGraph(kmersFreq.ctx, k, h)
+    if keep_cycles:
+        g._cycle_stats = dict(zip(CYCLE_BUILD_STATS, (int(x) for x in st)))
+    return g
 
 
 def loadGraph(ctx, path) -> HipGraph:

@@ -908,12 +908,26 @@ struct Edge {                 // S/data/graph/Edge.scala:11 (ids are not part of
 class Graph {
   public:
     // Graph.buildGraph(k, kmersFreq) :269-382
-    static Graph buildGraph(int k, DNAMap &kmersFreq) {
+    // keepCycles: perfect cycles, which the reference ignores (:375), become self-loops at their anchors (gk_graph_build_cycles;
+    // include/genome_amd.h, "perfect cycles"); cycleStats() holds the six statistics then, and every simplifyGraph() of this
+    // object keeps cycles too (keepCycles(false) turns that off again).
+    static Graph buildGraph(int k, DNAMap &kmersFreq, bool keepCycles = false) {
         if (kmersFreq.k() != k) throw KeyLengthError(GK_E_KLEN, "map k != k");
         Graph g(kmersFreq.context(), k);
-        check(gk_graph_build(kmersFreq.handle(), &g.h_), kmersFreq.context().handle());
+        if (keepCycles) check(gk_graph_build_cycles(kmersFreq.handle(), &g.h_, g.cycleStats_.v), kmersFreq.context().handle());
+        else check(gk_graph_build(kmersFreq.handle(), &g.h_), kmersFreq.context().handle());
+        g.keepCycles_ = keepCycles;
         return g;
     }
+    static Graph build(int k, DNAMap &kmersFreq, bool keepCycles = false) { return buildGraph(k, kmersFreq, keepCycles); }
+    struct CycleStats { uint64_t v[6] = {}; };              // gk_graph_build_cycles' stats6
+    static constexpr const char *cycleStatNames[6] = {"cycle_kmers", "cycles", "anchors", "self_complementary", "longest", "rounds"};
+    struct KeepStats { uint64_t v[4] = {}; };               // gk_graph_simplify_keep_cycles' stats4
+    static constexpr const char *keepStatNames[4] = {"kept_self_loops", "cycles_merged", "anchors_kept", "nodes_removed"};
+    const CycleStats &cycleStats() const { return cycleStats_; }
+    const KeepStats &keptTotal() const { return keptTotal_; }   // summed over this object's keeping simplifyGraph calls
+    void keepCycles(bool on) { keepCycles_ = on; }
+    bool keepsCycles() const { return keepCycles_; }
     // Graph(file) (Graph.scala:384-390) with GraphSimplifier's checks of the loaded graph (GraphSimplifier.scala:157-169); k comes
     // from the file (:153).  A malformed or corrupt file throws GK_E_FORMAT.
     static Graph load(Context &ctx, const std::string &path) {
@@ -926,10 +940,18 @@ class Graph {
     void save(const std::string &path) const { check(gk_graph_save(h_, path.c_str()), ctx_.handle()); }
     int k() const { return k_; }
     ~Graph() { gk_graph_destroy(h_); }
-    Graph(Graph &&o) noexcept : ctx_(o.ctx_), k_(o.k_), h_(o.h_) { o.h_ = nullptr; }
+    Graph(Graph &&o) noexcept : ctx_(o.ctx_), k_(o.k_), h_(o.h_), keepCycles_(o.keepCycles_), cycleStats_(o.cycleStats_), keptTotal_(o.keptTotal_) { o.h_ = nullptr; }
     Graph(const Graph &) = delete;
 
-    void simplifyGraph() { check(gk_graph_simplify(h_), ctx_.handle()); }           // :211-230
+    void simplifyGraph() { simplifyGraph(keepCycles_); }                            // :211-230
+    // keepCycles: self-loop nodes stay and every cycle of merge-away nodes keeps its anchors -> the four statistics (zeros otherwise)
+    KeepStats simplifyGraph(bool keepCycles) {
+        KeepStats st;
+        if (!keepCycles) { check(gk_graph_simplify(h_), ctx_.handle()); return st; }
+        check(gk_graph_simplify_keep_cycles(h_, st.v), ctx_.handle());
+        for (int i = 0; i < 4; i++) keptTotal_.v[i] += st.v[i];
+        return st;
+    }
     void removeBubbles() { check(gk_graph_remove_bubbles(h_), ctx_.handle()); }     // :125-149
     bool removeEdge(const DNASeq &start, char firstBase) {                          // :191-195
         uint8_t b = (uint8_t)DNASeq::code(firstBase);
@@ -1325,6 +1347,9 @@ class Graph {
     Context &ctx_;
     int k_;
     gk_graph *h_ = nullptr;
+    bool keepCycles_ = false;
+    CycleStats cycleStats_;
+    KeepStats keptTotal_;
 };
 
 inline Graph::PairDistances Graph::pairDistances(PartitionedDNAMap &pm, PositionMap &positions, const PairedEndData &data, uint64_t firstPair, uint64_t endPair,

@@ -49,6 +49,10 @@
 //   --gfa PATH writes the final graph as GFA 1.0 on the device (gk_graph_gfa_plan / gk_gfa_write; include/genome_amd.h, "the graph
 //   as GFA"), after all edits, with KC:i: from the table the graph was built from.  The JSON gains "gfa":{the nine stats}.  Not
 //   with --world (exit 2).
+//   --keep-cycles keeps perfect cycles (include/genome_amd.h, "perfect cycles": this project's own rule): the build is
+//   gk_graph_build_cycles and every simplifyGraph this tool runs (the clip / pop rounds, --simplify, the paired-end stage,
+//   --resolve-repeats) keeps self-loop nodes and the anchors of all-interior cycles.  The JSON gains "cycles":{"build":{the six
+//   stats},"simplify":{the four stats, summed}}, stderr one line.  Not with --world (exit 2).
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Rank 0 writes the
 //   communicator id to PATH (a file that must not exist yet: written aside, then renamed), the others wait for it (2 minutes at
 //   most).  Each rank counts its contiguous share of the pairs into its partition (gk_dist_count_reads), the partitions are
@@ -70,7 +74,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
                              "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--out prefix] [--save-graph PATH] "
-                             "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--gfa PATH] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--gfa PATH] [--keep-cycles] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string infile = argv[1];
@@ -96,6 +100,7 @@ int main(int argc, char **argv) {
     GfaOpts gfaOpt;
     LinkOpts link;                                // --links / --scaffolds: with --walk-pairs, on the graph that stage leaves
     RankOpts ranks;
+    CycleOpts cyc;                                // --keep-cycles
     for (Args a(argc, argv, 4); a.more(); a.next()) {
         if (a.word("--rounds", 1, "auto")) { autoRounds = true; a.skip(); }   // chosen from the spectrum
         else if (a.value("--rounds", rounds)) autoRounds = false;
@@ -115,10 +120,10 @@ int main(int argc, char **argv) {
         else if (a.value("--max-insert", walk.maxInsert)) { if (!walk.maxInsertOk()) { std::fprintf(stderr, "--max-insert N is 1..65535\n"); return 2; } }
         else if (a.value("--walk-pairs", walk.cutoff, walk.lo, walk.hi)) {}
         else if (walk.parseResolve(a)) {}
-        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || gfaOpt.parse(a) || link.parse(a) || ranks.parse(a)) {}
+        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || gfaOpt.parse(a) || link.parse(a) || ranks.parse(a) || cyc.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
-    if (!ranks.check() || !link.check(ranks.world) || !gfaOpt.check(ranks.world) || !walk.checkResolve(ranks.world)) return 2;
+    if (!ranks.check() || !link.check(ranks.world) || !gfaOpt.check(ranks.world) || !walk.checkResolve(ranks.world) || !cyc.check(ranks.world)) return 2;
     if (walk.resolve && walk.cutoff < 0) {
         std::fprintf(stderr, "--resolve-repeats goes with --walk-pairs (it runs behind the paired-end stage)\n");
         return 2;
@@ -177,7 +182,7 @@ int main(int argc, char **argv) {
         }
         if (withSpectrum) rounds = chosen.rounds;
         if (rank == 0 && !spectrumPath.empty()) writeSpectrum(spectrumPath, chosen.spectrum.hist);
-        auto graph = genome::Graph::buildGraph(k, *kmersFreq);                                           // :36
+        auto graph = genome::Graph::buildGraph(k, *kmersFreq, cyc.keep);                                          // :36
         auto [nodes, edges, totalLen] = graph.counts();                                                  // :39
         // :41-47 the two component histograms, on the graph as built (the reference computes them before retain)
         auto [hist, hist2] = graph.componentHistograms();
@@ -234,6 +239,7 @@ int main(int argc, char **argv) {
             if (!lr.judgeJson.empty()) jsonPut(js, "judge", lr.judgeJson);
             if (!lr.blocksJson.empty()) jsonPut(js, "blocks", lr.blocksJson);
         }
+        if (const std::string cj = cyc.report(graph, true); !cj.empty()) jsonPut(js, "cycles", cj);
         if (!contig.path.empty()) jsonPut(js, "contigs_fasta", fasta.json());
         // --gfa: after all edits (the links stage's included), with KC from the table the graph was built from
         if (const std::string gj = gfaOpt.run(graph, kmersFreq.get()); !gj.empty()) jsonPut(js, "gfa", gj);

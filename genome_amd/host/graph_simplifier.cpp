@@ -74,6 +74,9 @@
 //   PATH gets one text line per row.
 //   --gfa PATH writes the final graph as GFA 1.0 on the device (gk_graph_gfa_plan / gk_gfa_write; include/genome_amd.h, "the graph
 //   as GFA"), without KC tags: there is no count table after a load.  The JSON gains "gfa":{the nine stats}.  Not with --world.
+//   --keep-cycles keeps perfect cycles (include/genome_amd.h, "perfect cycles": this project's own rule): every simplifyGraph of
+//   the stage (after the split by support, after each --resolve-repeats round) keeps self-loop nodes and the anchors of
+//   all-interior cycles.  The JSON gains "cycles":{"simplify":{the four stats, summed}}, stderr one line.  Not with --world (exit 2).
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Every rank loads
 //   the same file, so the replicas are identical, ids included; each walks its contiguous share of the pairs and the supports
 //   are summed over the ranks before the split.  Rank 0 alone prints the JSON (plus world) and writes --out / --save-graph.
@@ -92,7 +95,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <graph.gkg> <reads.bin> <pairs> --cutoff C [--range LO HI | --range auto [--max-insert N] [--insert-hist PATH]] [--take-first N] "
                              "[--thread-reads [--no-pairs]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--out prefix] [--save-graph PATH] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--gfa PATH] "
-                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--keep-cycles] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string graphFile = argv[1], infile = argv[2];
@@ -105,6 +108,7 @@ int main(int argc, char **argv) {
     GfaOpts gfaOpt;
     LinkOpts link;
     RankOpts ranks;
+    CycleOpts cyc;                                // --keep-cycles
     for (Args a(argc, argv, 4); a.more(); a.next()) {
         if (a.value("--cutoff", stage.cutoff)) {}
         else if (a.word("--range", 1, "auto")) { stage.rangeAuto = true; a.skip(); }
@@ -113,7 +117,7 @@ int main(int argc, char **argv) {
         else if (a.flag("--thread-reads")) stage.threadReads = true;
         else if (a.flag("--no-pairs")) stage.walk = false;
         else if (stage.parseResolve(a)) {}
-        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || gfaOpt.parse(a) || link.parse(a) || ranks.parse(a)) {}
+        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || gfaOpt.parse(a) || link.parse(a) || ranks.parse(a) || cyc.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
     if (stage.cutoff < 0) {
@@ -128,7 +132,7 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--no-pairs goes with --thread-reads, and not with --range auto (no walk uses the range)\n");
         return 2;
     }
-    if (!ranks.check() || !link.check(ranks.world) || !gfaOpt.check(ranks.world) || !stage.checkResolve(ranks.world)) return 2;
+    if (!ranks.check() || !link.check(ranks.world) || !gfaOpt.check(ranks.world) || !stage.checkResolve(ranks.world) || !cyc.check(ranks.world)) return 2;
     const int world = ranks.world, rank = ranks.rank;
     try {
         if (fastq.path.empty()) data.bin = readBin(infile);
@@ -136,6 +140,7 @@ int main(int argc, char **argv) {
         if (!fastq.path.empty()) data = genome::PairedEndData::fromFastq(ctx, fastq.path, fastq.split);     // the pair count comes from the conversion
         auto graph = genome::Graph::load(ctx, graphFile);                                                // :152-153, :157-169
         const int k = graph.k();
+        graph.keepCycles(cyc.keep);
         std::unique_ptr<genome::PartitionedDNAMap> pm;
         if (world) pm = std::make_unique<genome::PartitionedDNAMap>(ctx, k, rank, world, shareId(rank, ranks.idFile));
         auto [n1, e1, l1] = graph.counts();
@@ -177,6 +182,7 @@ int main(int argc, char **argv) {
         if (const std::string gj = gfaOpt.run(graph, nullptr); !gj.empty()) jsonPut(js, "gfa", gj);
         if (stage.threadReads) jsonPut(js, "thread_reads", "{" + jsonNamed(genome::Graph::threadStatNames, res.threaded.v, 7) + "}");
         if (stage.resolve) jsonPut(js, "resolve_repeats", res.resolveJson(stage.spanCutoff()));
+        if (const std::string cj = cyc.report(graph, false); !cj.empty()) jsonPut(js, "cycles", cj);
         jsonPut(js, "simplified_nodes", n2, "simplified_edges", e2, "simplified_edges_length", l2, "components_histogram_2", jsonPairs(hist2),
                 "max_component_size", hist.empty() ? 0 : hist.rbegin()->first);
         if (world) jsonPut(js, "world", world);

@@ -201,6 +201,32 @@ inline void writeGraphText(genome::Graph &graph, const std::string &prefix) {
     graph.writeDot(df);
 }
 
+// --keep-cycles: perfect cycles are kept (include/genome_amd.h, "perfect cycles": this project's own rule; the reference ignores
+// them, Graph.scala:375, :220-221).  graph_builder builds with gk_graph_build_cycles; every simplifyGraph either tool runs —
+// the clip / pop rounds, --simplify, after the split by support, after each --resolve-repeats round — becomes
+// gk_graph_simplify_keep_cycles (genome::Graph::keepCycles).  The JSON gains "cycles":{["build":{the six stats},] "simplify":{the
+// four stats, summed over the calls}} and stderr one line.  One GPU only: there is no collective over ranks.
+struct CycleOpts {
+    bool keep = false;
+    bool parse(Args &a) {
+        if (!a.flag("--keep-cycles")) return false;
+        keep = true;
+        return true;
+    }
+    bool check(int world) const {
+        if (keep && world) { std::fprintf(stderr, "--keep-cycles runs on one GPU only (not with --world): perfect cycles have no collective\n"); return false; }
+        return true;
+    }
+    // after the last graph stage: the "cycles" object (empty text without the option), and the line on stderr
+    std::string report(const genome::Graph &graph, bool built) const {
+        if (!keep) return "";
+        const std::string b = "{" + jsonNamed(genome::Graph::cycleStatNames, graph.cycleStats().v, 6) + "}";
+        const std::string s = "{" + jsonNamed(genome::Graph::keepStatNames, graph.keptTotal().v, 4) + "}";
+        std::fprintf(stderr, "keep-cycles:%s%s simplify %s\n", built ? " build " : "", built ? b.c_str() : "", s.c_str());
+        return built ? jsonObject("build", b, "simplify", s) : jsonObject("simplify", s);
+    }
+};
+
 // GraphSimplifier.startup's paired-end stage (GraphSimplifier.scala:188-318) on a graph: position map, the pairs' walks, node
 // split by their support, simplifyGraph — and this project's additions to it: the measured insert range, the threaded reads and,
 // after the reference's stage, the repeats longer than k that single reads span.

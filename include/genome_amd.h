@@ -451,6 +451,46 @@ int gk_graph_counts(gk_graph *g, uint64_t *nodes, uint64_t *edges, uint64_t *tot
 int gk_graph_contig_stats(gk_graph *g, uint64_t longer_than, uint64_t *count, uint64_t *sum, uint64_t *median, uint64_t *n50, uint64_t *max);
 int gk_graph_simplify(gk_graph *g);          /* MapGraph.simplifyGraph :211-230 */
 int gk_graph_remove_bubbles(gk_graph *g);    /* Graph.removeBubbles :125-149 */
+
+/* ---- perfect cycles ---------------------------------------------------------------------------
+ * The reference drops every circular sequence it assembles without a blemish (Graph.scala:375 "perfect cycles are ignored";
+ * simplifyGraph :220-221 removes a node whose way in and way out are one edge), and so do gk_graph_build and gk_graph_simplify,
+ * bit for bit.  The two entry points below keep them.  Nothing else changes: not the two plain calls, not the graph file.
+ *
+ * Cycle members.  An oriented k-mer u of the table is a member iff it has exactly one successor and one predecessor (so it is
+ * not terminal by the classify's predicate, and not an isolated k-mer without neighbours either) and following successors from
+ * u never reaches a terminal k-mer: what the plain build puts on no node and inside no edge.  Members form disjoint oriented
+ * cycles under the successor map; the reverse complement of a cycle is a cycle, possibly the same one.
+ * Anchors.  The anchor key of a k-mer x is min(x, rc x) as 2-bit-packed integers compared as (hi, lo): it depends on content
+ * only, is the same for both strands, and does not depend on the table's orientation rule, slot order or capacity.  It is a
+ * CONVENTION (any strand-symmetric total order would serve), not a measurement.  A member whose anchor key is its cycle's
+ * minimum is an anchor.  Two different k-mers share a key only as x and rc x, so a cycle has one anchor — or two, when it is its
+ * own reverse complement and its smallest k-mer is not a palindrome.
+ * gk_graph_build_cycles = gk_graph_build, then: every anchor becomes a node with one out-edge, the arc from it to the next anchor
+ * of its cycle (itself when it is the only one); seq = the bases appended on the way, len = the steps.  A cycle of L k-mers with
+ * one anchor is a self-loop of len L whose path (L + k bases) ends in the anchor's k-mer again; a homopolymer is a self-loop of
+ * one base.  Strand closure: rc maps a cycle onto a cycle and keeps keys, so the anchors of a cycle and of its reverse
+ * complement are twins, and so are their arcs; in a self-complementary cycle with anchors x and rc x, rc maps the arc from x to
+ * rc x onto a path from x to rc x, which successors being unique is the same arc: each of the two arcs is its own twin.
+ * Ids: the plain build's nodes and edges keep theirs (a table without members gives the identical graph: ids, gk_graph_checksum,
+ * gk_graph_id_fingerprint; with members, removing what was added leaves the plain build's graph).  Anchor nodes follow in pairs
+ * — even id: the anchor that is its own key, odd id: its reverse complement (dead for a palindrome) — in table slot order;
+ * the arcs follow the plain build's edges, one per anchor, in table slot order (stored orientation first).
+ * stats6 = {cycle_kmers (oriented members), cycles (oriented), anchors (nodes added == edges added), self_complementary (cycles
+ * equal to their reverse complement), longest (k-mers), rounds (doubling rounds of the minimum)}.  The summed len of the added
+ * edges == cycle_kmers; anchors == cycles + cycles with two anchors.  No members: all 0, and nothing but one census pass ran.
+ * GK_E_CAPACITY: 2^31 members or more.  stats6 may be NULL.
+ *
+ * gk_graph_simplify_keep_cycles = gk_graph_simplify, except: a node whose way in and way out are the same edge stays with it
+ * (it is an anchor already), and in a cycle made only of merge-away nodes the nodes whose k-mer has the cycle's smallest anchor key
+ * (one, or two twins) are kept, so that each arc between them is merged into one edge as any other chain.  Isolated nodes still go.
+ * Where node copies (gk_graph_split_edges_by_spans, gk_graph_split_by_support) put the same k-mer on one such cycle more than
+ * once, every node with the smallest key is kept: more than two anchors then, each arc still merged into one edge.
+ * Idempotent.  On a graph with neither shape the result is gk_graph_simplify's, checksums and id fingerprint included.
+ * stats4 = {kept_self_loops, cycles_merged (cycles of merge-away nodes that lost a node), anchors_kept, nodes_removed}; may be NULL.
+ * Not there: a collective over ranks, circular references in the judge and the blocks, a `circular` tag in the FASTA records. */
+int gk_graph_build_cycles(gk_map *m, gk_graph **out, uint64_t *stats6);
+int gk_graph_simplify_keep_cycles(gk_graph *g, uint64_t *stats4);
 /* MapGraph.removeEdge :191-195 for the edges leaving start[i] with first base base[i] */
 int gk_graph_remove_edges(gk_graph *g, const uint64_t *start_lo, const uint64_t *start_hi, const uint8_t *base,
                           uint64_t n, uint64_t *removed);
