@@ -148,6 +148,7 @@ SIGNATURES = {
     "gk_contigs_read": (C.c_int, [vp, C.c_uint64, vp, C.c_uint64, u64p]),
     "gk_contigs_write": (C.c_int, [vp, C.c_char_p]),
     "gk_contigs_last_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "gk_map_add_graph_paths": (C.c_int, [vp, vp, C.c_uint32, u64p]),
     "gk_graph_edge_twins": (C.c_int, [vp, u32p, C.c_uint64, u32p, u8p, u64p]),
     "gk_graph_gfa_plan": (C.c_int, [vp, vp, C.POINTER(vp)]),
     "gk_gfa_destroy": (None, [vp]),
@@ -265,6 +266,7 @@ TEST_SIGNATURES = {
     "gk_test_support_last_walk": (C.c_int, [vp, u64p, u64p]),
     "gk_test_grid_cap_uses": (C.c_int, [vp, u64p]),
     "gk_test_prefilter_chunks": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+    "gk_test_multik_chunks": (C.c_int, [vp, u64p]),
     "gk_test_part_plan": (C.c_int, [vp, vp]),         # (gk_test_part_in *, gk_test_part_out *: tests/test_part_plan_cpu.py)
     "gk_test_scan_counts": (C.c_int, [vp, u32p, C.c_uint64, C.c_int, u64p, u64p]),
     "gk_test_slot_ranks": (C.c_int, [vp, u64p, u64p, C.c_uint64, u64p, u64p]),

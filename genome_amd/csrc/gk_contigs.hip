@@ -17,7 +17,6 @@
 #include "gk_fastaout.h"
 #include "gk_scan.h"
 
-static constexpr uint8_t CLS_DEAD = 0, CLS_SHORT = 1, CLS_FORWARD = 2, CLS_SELF = 3, CLS_REVERSE = 4;
 // device counters of a plan: the four classes, bases of the records, windows missing from the table, "a record passes 2^32-1 bytes"
 enum { CS_SHORT = 0, CS_FORWARD, CS_SELF, CS_REVERSE, CS_BASES, CS_MISSING, CS_OVERFLOW, CS_N };
 
@@ -37,24 +36,7 @@ __global__ __launch_bounds__(BLOCK) void k_contig_classify(GraphView g, u64 min_
             continue;
         }
         const u64 n = (u64)g.k + g.e_len[e];
-        uint8_t c = CLS_SELF;
-        if (n < min_len) c = CLS_SHORT;
-        else {
-            const u32 s = g.e_start[e];
-            const u64 nlo = g.node_lo[s], nhi = g.k > 32 ? g.node_hi[s] : 0ull;
-            const uint8_t *seq = g.pool + g.e_off[e];
-            const u64 half = (n + 1) / 2;                    // (an odd n differs at its middle base at the latest: 3 - b != b)
-            for (u64 i0 = 0; i0 < half; i0 += 64) {
-                const u64 i = i0 + (u64)lane;
-                int a = 0, b = 0;
-                if (i < half) { a = path_base(nlo, nhi, seq, g.k, i); b = 3 - path_base(nlo, nhi, seq, g.k, n - 1 - i); }
-                const unsigned long long differ = __ballot(a != b);
-                if (differ) {
-                    c = __shfl(a < b ? 1 : 0, __ffsll((long long)differ) - 1) ? CLS_FORWARD : CLS_REVERSE;
-                    break;
-                }
-            }
-        }
+        const uint8_t c = wave_contig_class(g, e, min_len);
         if (lane == 0) {
             const bool rec = c == CLS_FORWARD || c == CLS_SELF || (c == CLS_REVERSE && strands == 2);
             u64 bytes = 0;

@@ -16,31 +16,8 @@
 #include "gk_scan.h"
 
 // ---------------------------------------------------------------------------------------------
-// windows of start.seq ++ edge.seq without a per-base loop per window
+// windows of start.seq ++ edge.seq without a per-base loop per window: pool_bits / path_bits / window_at (gk_graph.h)
 // ---------------------------------------------------------------------------------------------
-// n <= 32 bases from base i0 of a 2-bit sequence (4 bases per byte, LSB first).  Touches only bytes that hold a base asked for.
-__device__ __forceinline__ u64 pool_bits(const uint8_t *__restrict__ p, u64 i0, int n) {
-    if (n <= 0) return 0;
-    const u64 b0 = i0 >> 2;
-    const int sh = (int)(i0 & 3) * 2, nb = (int)(((i0 + (u64)n + 3) >> 2) - b0);      // 1 .. 9 bytes
-    u64 lo = 0, hi = 0;
-    for (int j = 0; j < nb && j < 8; j++) lo |= (u64)p[b0 + j] << (8 * j);
-    if (nb > 8) hi = p[b0 + 8];
-    const u64 r = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-    return r & low_mask(2 * n);
-}
-// n <= 32 bases from base i0 of the path (the start node's k bases, then the edge's)
-__device__ __forceinline__ u64 path_bits(Kmer<2> node, const uint8_t *__restrict__ seq, int k, u64 i0, int n) {
-    if (i0 >= (u64)k) return pool_bits(seq, i0 - (u64)k, n);
-    const int m = min(n, k - (int)i0);                       // of them from the node
-    const u64 a = window_bits(node, 2 * (int)i0) & low_mask(2 * m);
-    return m == n ? a : a | (pool_bits(seq, 0, n - m) << (2 * m));
-}
-template <int W> __device__ __forceinline__ Kmer<W> window_at(Kmer<2> node, const uint8_t *__restrict__ seq, int k, u64 d) {
-    if constexpr (W == 1) return Kmer<1>{path_bits(node, seq, k, d, k)};
-    else return Kmer<2>{path_bits(node, seq, k, d, 32), path_bits(node, seq, k, d + 32, k - 32)};
-}
-
 // sum / min / max / missing over a run of windows, rolled: the forward window takes the next base at its end, the reverse
 // complement its complement at the front; the bases come out of the pool one byte per four steps
 struct CovAcc {
@@ -51,7 +28,7 @@ struct CovAcc {
 };
 template <int W, class S>
 __device__ __forceinline__ void cover_run(const Table<W, S> &t, Kmer<2> node, const uint8_t *__restrict__ seq, int k, u64 d0, u64 d1, CovAcc &acc) {
-    Kmer<W> x = window_at<W>(node, seq, k, d0), rc = revcomp(x, k);
+    Kmer<W> x = window_at<W>(node, seq, k, k, d0), rc = revcomp(x, k);
     acc.add(window_count(t, x, rc));
     u32 byte = (d0 & 3) ? seq[d0 >> 2] : 0u;                 // the window at distance d + 1 ends with base d of the edge
     for (u64 d = d0; d + 1 < d1; d++) {

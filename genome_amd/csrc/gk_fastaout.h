@@ -68,6 +68,29 @@ __device__ __forceinline__ int path_base(u64 nlo, u64 nhi, const uint8_t *__rest
     return (int)((i < 32 ? nlo >> (2 * i) : nhi >> (2 * (i - 32))) & 3);
 }
 
+// The contigs' classes (include/genome_amd.h, "contigs": short, then forward / self_twin / reverse by comparing the path with its
+// reverse complement), shared by the contig plan (gk_contigs.hip) and the multi-k seeding (gk_multik.hip).
+static constexpr uint8_t CLS_DEAD = 0, CLS_SHORT = 1, CLS_FORWARD = 2, CLS_SELF = 3, CLS_REVERSE = 4;
+// the class of LIVE edge e, by one wave: every lane of the wave calls it with the same e and gets the answer; 64 bases of each
+// strand per step, it stops at the first difference
+__device__ __forceinline__ uint8_t wave_contig_class(const GraphView &g, u64 e, u64 min_len) {
+    const int lane = threadIdx.x & 63;
+    const u64 n = (u64)g.k + g.e_len[e];
+    if (n < min_len) return CLS_SHORT;
+    const u32 s = g.e_start[e];
+    const u64 nlo = g.node_lo[s], nhi = g.k > 32 ? g.node_hi[s] : 0ull;
+    const uint8_t *seq = g.pool + g.e_off[e];
+    const u64 half = (n + 1) / 2;                            // (an odd n differs at its middle base at the latest: 3 - b != b)
+    for (u64 i0 = 0; i0 < half; i0 += 64) {
+        const u64 i = i0 + (u64)lane;
+        int a = 0, b = 0;
+        if (i < half) { a = path_base(nlo, nhi, seq, g.k, i); b = 3 - path_base(nlo, nhi, seq, g.k, n - 1 - i); }
+        const unsigned long long differ = __ballot(a != b);
+        if (differ) return __shfl(a < b ? 1 : 0, __ffsll((long long)differ) - 1) ? CLS_FORWARD : CLS_REVERSE;
+    }
+    return CLS_SELF;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side: a text emitted by byte range, streamed to a sink
 // ---------------------------------------------------------------------------------------------

@@ -86,6 +86,31 @@ __device__ __forceinline__ u32 order_remove(u32 o, int b) {
 }
 __device__ __forceinline__ u32 rev4(u32 m) { return ((m & 1) << 3) | ((m & 2) << 1) | ((m & 4) >> 1) | ((m & 8) >> 3); }
 __device__ __forceinline__ int pool_get(const uint8_t *pool, u64 off, u64 i) { return (pool[off + (i >> 2)] >> ((i & 3) * 2)) & 3; }
+// Windows of the path start.seq ++ edge.seq without a per-base loop per window (gk_coverage.hip: windows of the graph's own k;
+// gk_multik.hip: windows of a larger k).
+// n <= 32 bases from base i0 of a 2-bit sequence (4 bases per byte, LSB first).  Touches only bytes that hold a base asked for.
+__device__ __forceinline__ u64 pool_bits(const uint8_t *__restrict__ p, u64 i0, int n) {
+    if (n <= 0) return 0;
+    const u64 b0 = i0 >> 2;
+    const int sh = (int)(i0 & 3) * 2, nb = (int)(((i0 + (u64)n + 3) >> 2) - b0);      // 1 .. 9 bytes
+    u64 lo = 0, hi = 0;
+    for (int j = 0; j < nb && j < 8; j++) lo |= (u64)p[b0 + j] << (8 * j);
+    if (nb > 8) hi = p[b0 + 8];
+    const u64 r = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+    return r & low_mask(2 * n);
+}
+// n <= 32 bases from base i0 of the path (the start node's k bases, then the edge's)
+__device__ __forceinline__ u64 path_bits(Kmer<2> node, const uint8_t *__restrict__ seq, int k, u64 i0, int n) {
+    if (i0 >= (u64)k) return pool_bits(seq, i0 - (u64)k, n);
+    const int m = min(n, k - (int)i0);                       // of them from the node
+    const u64 a = window_bits(node, 2 * (int)i0) & low_mask(2 * m);
+    return m == n ? a : a | (pool_bits(seq, 0, n - m) << (2 * m));
+}
+// the window of kw bases at base d of the path of a node of k bases (kw = k: a k-mer of the graph; W = the words of kw)
+template <int W> __device__ __forceinline__ Kmer<W> window_at(Kmer<2> node, const uint8_t *__restrict__ seq, int k, int kw, u64 d) {
+    if constexpr (W == 1) return Kmer<1>{path_bits(node, seq, k, d, kw)};
+    else return Kmer<2>{path_bits(node, seq, k, d, 32), path_bits(node, seq, k, d + 32, kw - 32)};
+}
 template <int W> __device__ __forceinline__ Kmer<W> node_kmer(const GraphView &g, u64 n);
 template <> __device__ __forceinline__ Kmer<1> node_kmer<1>(const GraphView &g, u64 n) { return Kmer<1>{g.node_lo[n]}; }
 template <> __device__ __forceinline__ Kmer<2> node_kmer<2>(const GraphView &g, u64 n) { return Kmer<2>{g.node_lo[n], g.node_hi[n]}; }

@@ -87,7 +87,9 @@ struct gk_ctx {
     int64_t hook_contigs_chunk = 0;  // test hook: text bytes per device chunk of gk_contigs_read / gk_contigs_write (0: 64 MiB)
     int64_t hook_place_slice = 0;    // test hook: characters per device slice of gk_placements_add_record (0: 64 Mi)
     int64_t hook_pf_chunk_windows = 0;   // test hook: windows per pass-2 chunk of the singleton pre-filter (0: 2^28), host-fed and `_dev` alike
-    int hook_twin_key_bits = 128;    // test hook: the bits of the 128-bit content keys gk_graph_edge_twins sorts and searches by (0..128; the product: 128)
+    int64_t hook_multik_chunk_windows = 0;   // test hook: windows per chunk of gk_map_add_graph_paths (0: 2^26)
+    uint64_t multik_last_chunks = 0;     // the chunks the last gk_map_add_graph_paths on this context ran (gk_test_multik_chunks: the switch's echo)
+    int hook_twin_key_bits = 128;   // test hook: the bits of the 128-bit content keys gk_graph_edge_twins sorts and searches by (0..128; the product: 128)
 };
 // most workgroups of a grid-stride launch: 8 resident 256-thread workgroups per CU, or what the test hook says
 inline uint64_t grid_cap(const gk_ctx *ctx) {

@@ -3,6 +3,7 @@
 //     the large-table paths on small tables or inject failures;
 //   * gk_test_grid_cap_uses: how many launches "test_max_grid" has sized on a context (the switch's echo);
 //   * gk_test_prefilter_chunks: the chunks a singleton pre-filter handle has staged and run ("test_max_stage" / "test_prefilter_chunk_windows"' echo);
+//   * gk_test_multik_chunks: the chunks the last gk_map_add_graph_paths on a context ran ("test_multik_chunk_windows"' echo);
 //   * gk_test_part_plan: what the partitioned insert would choose for a table geometry and a set of switches (part_choose's echo, no device);
 //   * gk_test_support_last_walk: which walker (device kernel / host fallback) did the orientations of the last gk_graph_walk_pairs;
 //   * gk_test_scan_counts: gk_scan.h's scan_counts over counts from the host, between guard words (either overload);
@@ -96,6 +97,7 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value) {
     }
     else if (n == "test_place_slice") ctx->hook_place_slice = (int64_t)std::max<int64_t>(0, value);
     else if (n == "test_prefilter_chunk_windows") ctx->hook_pf_chunk_windows = (int64_t)std::max<int64_t>(0, value);
+    else if (n == "test_multik_chunk_windows") ctx->hook_multik_chunk_windows = (int64_t)std::max<int64_t>(0, value);
     else if (n == "contigs_chunk_bytes") ctx->hook_contigs_chunk = (int64_t)std::max<int64_t>(0, value);
     else if (n == "twin_key_bits") {
         if (value < 0 || value > 128) return fail(ctx, GK_E_INVALID, "twin_key_bits: 0..128");
@@ -120,6 +122,12 @@ int gk_test_prefilter_chunks(const gk_prefilter *pf, uint64_t *host_fixed, uint6
     if (host_offsets) *host_offsets = c[1];
     if (dev_pass2) *dev_pass2 = c[2];
     if (pass2_launches) *pass2_launches = c[3];
+    return GK_OK;
+}
+
+int gk_test_multik_chunks(const gk_ctx *ctx, uint64_t *chunks) {
+    if (!ctx || !chunks) return fail(ctx, GK_E_INVALID, "gk_test_multik_chunks: null argument");
+    *chunks = ctx->multik_last_chunks;
     return GK_OK;
 }
 

@@ -47,6 +47,12 @@ class Context:
         L.check(L.test_hook("gk_test_grid_cap_uses")(self.h, C.byref(n)), self.h)
         return n.value
 
+    def multik_chunks(self) -> int:
+        """Chunks the last HipDNAMap.add_graph_paths on this context ran (a test hook: GkError on the product library)."""
+        n = C.c_uint64()
+        L.check(L.test_hook("gk_test_multik_chunks")(self.h, C.byref(n)), self.h)
+        return n.value
+
     def sync(self):
         """Wait for everything queued on the context's stream."""
         L.check(L.lib().gk_ctx_sync(self.h), self.h)
@@ -140,6 +146,9 @@ def _keys(k: int, keys):
 # the GK_CORRECT_* indices of gk_reads_correct's statistics, in order
 CORRECT_STATS = ("reads", "short", "windows", "weak_windows", "weak_runs", "corrected", "ambiguous", "unresolved", "skipped", "reads_changed")
 
+# gk_map_add_graph_paths' stats6, in order
+GRAPH_PATHS_STATS = ("live_edges", "short", "forward", "self_twin", "reverse", "windows")
+
 
 class HipDNAMap:
     """`ArrayDNAMap[Int]` resident in HBM (one partition)."""
@@ -216,6 +225,14 @@ class HipDNAMap:
 
     def add_map(self, other: "HipDNAMap"):                   # update(key, c, _ + c) for every entry of `other`, device to device
         L.check(L.lib().gk_map_add_map(self.h, other.h), self.ctx.h)
+
+    def add_graph_paths(self, graph, weight: int) -> dict:
+        """Multi-k seeding (gk_map_add_graph_paths; include/genome_amd.h, "multi-k"): every window of this map's k of every
+        contig of `graph` (a HipGraph of a smaller k; one strand per contig) is added `weight` times, oriented as a read's
+        window is -> the six stats by name.  The graph is not changed."""
+        st = np.zeros(6, np.uint64)
+        L.check(L.lib().gk_map_add_graph_paths(self.h, graph.h, int(weight), L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(GRAPH_PATHS_STATS, (int(x) for x in st)))
 
     def update_inc_dev(self, d_keys: int, n: int):
         L.check(L.lib().gk_map_update_inc_dev(self.h, d_keys, n), self.ctx.h)

@@ -196,6 +196,7 @@ inline SpectrumCutoff spectrumCutoff(const std::vector<uint64_t> &hist, uint32_t
     return c;
 }
 
+class Graph;
 // trait DNAMap[Int] over one HBM-resident partition (ArrayDNAMap.scala:49-60, 62-243)
 class DNAMap {
   public:
@@ -279,6 +280,11 @@ class DNAMap {
         return st;
     }
     void clear() { check(gk_map_clear(h_), ctx_.handle()); }       // back to an empty table of the same capacity
+    // multi-k seeding (gk_map_add_graph_paths; include/genome_amd.h, "multi-k"): every window of this map's k of every contig of
+    // `graph` (a smaller k; one strand per contig) is added `weight` times, oriented as a read's window is; the graph is not changed
+    struct GraphPathStats { uint64_t v[6] = {}; };            // gk_map_add_graph_paths' stats6
+    static constexpr const char *graphPathStatNames[6] = {"live_edges", "short", "forward", "self_twin", "reverse", "windows"};
+    GraphPathStats addGraphPaths(const Graph &graph, uint32_t weight);      // (defined behind Graph)
     // the table's invariants and an order-independent content checksum (gk_map_verify)
     struct Verify { uint64_t live, bad, sumCounts, checksum; };
     Verify verify() const {
@@ -411,9 +417,10 @@ template <class Map> inline int chooseRounds(Map &kmersFreq, int rounds, uint32_
 // prefilterDistinct > 0 (rounds >= 2 only): the exact two-pass singleton pre-filter sized for that many
 // distinct k-mers runs first (include/genome_amd.h); same result, k-mers seen once take no table slot
 // chosen->autoRounds: the cutoff is the valley of the table's count spectrum (chooseRounds; min_count = 2 behind the pre-filter)
+// beforeFilter(table, rounds): called between the count and deleteAll, with the rounds that will be used
 inline DNAMap extractFilteredKmers(Context &ctx, const PairedEndData &data, int k, int rounds,
                                    uint64_t takeFirst = UINT64_MAX, uint64_t capacityHint = 0, uint64_t prefilterDistinct = 0,
-                                   Chosen *chosen = nullptr) {
+                                   Chosen *chosen = nullptr, const std::function<void(DNAMap &, int)> &beforeFilter = {}) {
     DNAMap kmersFreq(ctx, k, capacityHint);
     const uint64_t pairs = std::min<uint64_t>(data.count, takeFirst);
     if (prefilterDistinct) {
@@ -429,6 +436,7 @@ inline DNAMap extractFilteredKmers(Context &ctx, const PairedEndData &data, int 
     }
     rounds = chooseRounds(kmersFreq, rounds, prefilterDistinct ? 2 : 1, chosen);
     if (prefilterDistinct && rounds < 2) rounds = 2;       // (auto only: a number below 2 was refused above)
+    if (beforeFilter) beforeFilter(kmersFreq, rounds);     // (multi-k: the seeds go in behind the choice of rounds — they would move the valley)
     kmersFreq.deleteAll(ValueLessThan{rounds});
     return kmersFreq;
 }
@@ -1361,6 +1369,12 @@ inline Graph::PairDistances Graph::pairDistances(PartitionedDNAMap &pm, Position
     check(gk_dist_pair_distances(pm.distHandle(), h_, positions.handle(), data.bin.data() + b0, b1 - b0, endPair > firstPair ? endPair - firstPair : 0, bins,
                                  r.hist.data(), r.classes), ctx_.handle());
     return r;
+}
+
+inline DNAMap::GraphPathStats DNAMap::addGraphPaths(const Graph &graph, uint32_t weight) {
+    GraphPathStats st;
+    check(gk_map_add_graph_paths(h_, graph.handle(), weight, st.v), ctx_.handle());
+    return st;
 }
 
 // gk_insert_range over a pairDistances histogram: lo / hi cut trimPermille thousandths off either tail, median; estimated =

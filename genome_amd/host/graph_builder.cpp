@@ -7,7 +7,7 @@
 //                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]]
 //                 [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N] [--block-rows PATH]]]]   (with --walk-pairs: graph_simplifier.cpp says what they write)
 //                 [--out prefix] [--save-graph PATH] [--correct N|auto]
-//                 [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]]
+//                 [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--seed-k K1[,K2,...]]
 //   graph_builder --fastq <reads.fastq> <k> [--split N | --interleaved] [the options above]
 //   --fastq converts the FASTQ file on the GPU first (Convert2bin, gk_fastq; --split N = its n, default 36) and takes the pair
 //   count from the conversion; the flow is then the same.  Not with --world (exit 2): convert2bin the file first.
@@ -53,6 +53,9 @@
 //   gk_graph_build_cycles and every simplifyGraph this tool runs (the clip / pop rounds, --simplify, the paired-end stage,
 //   --resolve-repeats) keeps self-loop nodes and the anchors of all-interior cycles.  The JSON gains "cycles":{"build":{the six
 //   stats},"simplify":{the four stats, summed}}, stderr one line.  Not with --world (exit 2).
+//   --seed-k K1[,K2,...] assembles at the listed smaller ks first, each stage seeding the next one's count table with its contigs
+//   (tool_common.hpp: SeedOpts; include/genome_amd.h, "multi-k"); the positional <k> stays the final stage.  The JSON gains
+//   "seed_stages".  Not with --world or --prefilter (exit 2).
 //   --world W --rank R --id-file PATH: one rank of W (one process per rank, on device R % gk_device_count()).  Rank 0 writes the
 //   communicator id to PATH (a file that must not exist yet: written aside, then renamed), the others wait for it (2 minutes at
 //   most).  Each rank counts its contiguous share of the pairs into its partition (gk_dist_count_reads), the partitions are
@@ -74,7 +77,7 @@ int main(int argc, char **argv) {
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
                              "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--out prefix] [--save-graph PATH] "
-                             "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--gfa PATH] [--keep-cycles] [--world W --rank R --id-file PATH]\n", argv[0]);
+                             "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--gfa PATH] [--keep-cycles] [--seed-k K1[,K2,...]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
     const std::string infile = argv[1];
@@ -101,6 +104,7 @@ int main(int argc, char **argv) {
     LinkOpts link;                                // --links / --scaffolds: with --walk-pairs, on the graph that stage leaves
     RankOpts ranks;
     CycleOpts cyc;                                // --keep-cycles
+    SeedOpts seed;                                // --seed-k
     for (Args a(argc, argv, 4); a.more(); a.next()) {
         if (a.word("--rounds", 1, "auto")) { autoRounds = true; a.skip(); }   // chosen from the spectrum
         else if (a.value("--rounds", rounds)) autoRounds = false;
@@ -120,10 +124,10 @@ int main(int argc, char **argv) {
         else if (a.value("--max-insert", walk.maxInsert)) { if (!walk.maxInsertOk()) { std::fprintf(stderr, "--max-insert N is 1..65535\n"); return 2; } }
         else if (a.value("--walk-pairs", walk.cutoff, walk.lo, walk.hi)) {}
         else if (walk.parseResolve(a)) {}
-        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || gfaOpt.parse(a) || link.parse(a) || ranks.parse(a) || cyc.parse(a)) {}
+        else if (a.value("--out", out) || a.value("--save-graph", saveGraph) || contig.parse(a) || gfaOpt.parse(a) || link.parse(a) || ranks.parse(a) || cyc.parse(a) || seed.parse(a)) {}
         else { std::fprintf(stderr, "unknown argument %s\n", a.cur()); return 2; }
     }
-    if (!ranks.check() || !link.check(ranks.world) || !gfaOpt.check(ranks.world) || !walk.checkResolve(ranks.world) || !cyc.check(ranks.world)) return 2;
+    if (!ranks.check() || !link.check(ranks.world) || !gfaOpt.check(ranks.world) || !walk.checkResolve(ranks.world) || !cyc.check(ranks.world) || !seed.check(ranks.world, prefilter != 0, k)) return 2;
     if (walk.resolve && walk.cutoff < 0) {
         std::fprintf(stderr, "--resolve-repeats goes with --walk-pairs (it runs behind the paired-end stage)\n");
         return 2;
@@ -143,8 +147,25 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--pop-bubbles MAXDIFF is at most 31\n");
         return 2;
     }
+    const uint64_t tipGiven = tipMaxLen, bubbleGiven = bubbleMaxLen;      // (0 = auto: 2k of the stage that clips)
     if (clipTips && !tipMaxLen) tipMaxLen = 2 * (uint64_t)k;
     if (popBubbles && !bubbleMaxLen) bubbleMaxLen = 2 * (uint64_t)k;
+    // --clip-tips / --pop-bubbles: clip, pop, then simplifyGraph, until a round removes nothing, 8 rounds at most (the counts are the
+    // table the graph was built from)
+    auto cleanRounds = [&](genome::Graph &graph, genome::DNAMap &counts, uint64_t tipLen, uint64_t bubbleLen, std::vector<uint64_t> &tipsRemoved,
+                           std::vector<uint64_t> &bubblesRemoved, std::vector<uint64_t> &bubblePairs) {
+        for (int round = 0; (clipTips || popBubbles) && round < 8; round++) {
+            uint64_t gone = 0;
+            if (clipTips) { tipsRemoved.push_back(graph.clipTips(counts, tipLen)); gone += tipsRemoved.back(); }
+            if (popBubbles) {
+                const auto [removed, pairs] = graph.popBubbles(counts, bubbleLen, bubbleMaxDiff);
+                bubblesRemoved.push_back(removed); bubblePairs.push_back(pairs);
+                gone += removed;
+            }
+            if (!gone) break;
+            graph.simplifyGraph();
+        }
+    };
     try {
         if (fastq.path.empty()) data.bin = readBin(infile);
         genome::Context ctx(ranks.device());
@@ -164,6 +185,36 @@ int main(int argc, char **argv) {
             }
             corrected = raw.correctReads(data.bin.data(), nbytes, 2 * pairs, solid, data.bin.data());
         }
+        // --seed-k: the seed stages, each seeded by the graph the one before left; `seedInto` is what a stage's count calls between
+        // its count and its deleteAll
+        std::unique_ptr<genome::DNAMap> seedMap;
+        std::unique_ptr<genome::Graph> seedGraph;
+        int stageRounds = 0;
+        uint64_t stageBefore = 0, stageAfter = 0;
+        genome::DNAMap::GraphPathStats stageStats;
+        const auto seedInto = [&](genome::DNAMap &table, int r) {
+            stageRounds = r;
+            stageStats = {};
+            stageBefore = table.size();
+            if (seedGraph) stageStats = table.addGraphPaths(*seedGraph, (uint32_t)r);
+            seedGraph.reset();
+            seedMap.reset();
+            stageAfter = table.size();
+        };
+        for (const int sk : seed.ks) {
+            genome::FreqFilter::Chosen ch;
+            ch.autoRounds = autoRounds;
+            auto m = std::make_unique<genome::DNAMap>(genome::FreqFilter::extractFilteredKmers(ctx, data, sk, rounds, takeFirst, 0, 0, &ch, seedInto));
+            auto g = std::make_unique<genome::Graph>(genome::Graph::buildGraph(sk, *m, cyc.keep));
+            std::vector<uint64_t> t, b, p;
+            cleanRounds(*g, *m, tipGiven ? tipGiven : 2 * (uint64_t)sk, bubbleGiven ? bubbleGiven : 2 * (uint64_t)sk, t, b, p);
+            g->simplifyGraph();                               // (a seed stage always simplifies and never retains: that would drop replicons)
+            const auto [sn, se, sl] = g->counts();
+            (void)sl;
+            seed.report(sk, stageRounds, stageBefore, stageAfter, stageStats, sn, se);
+            seedMap = std::move(m);
+            seedGraph = std::move(g);
+        }
         std::unique_ptr<genome::PartitionedDNAMap> pm;
         uint64_t sent = 0, owned = 0, good = 0;
         std::unique_ptr<genome::DNAMap> kmersFreq;
@@ -177,31 +228,21 @@ int main(int argc, char **argv) {
             good = pm->size();                                                                                          // :34
             kmersFreq = std::make_unique<genome::DNAMap>(pm->gathered(true));
         } else {
-            kmersFreq = std::make_unique<genome::DNAMap>(genome::FreqFilter::extractFilteredKmers(ctx, data, k, rounds, takeFirst, 0, prefilter, &chosen));   // :32
+            kmersFreq = std::make_unique<genome::DNAMap>(genome::FreqFilter::extractFilteredKmers(ctx, data, k, rounds, takeFirst, 0, prefilter, &chosen,
+                                                                                                      seed.given ? std::function<void(genome::DNAMap &, int)>(seedInto) : nullptr));   // :32
             good = kmersFreq->size();                                                                                  // :34
         }
         if (withSpectrum) rounds = chosen.rounds;
         if (rank == 0 && !spectrumPath.empty()) writeSpectrum(spectrumPath, chosen.spectrum.hist);
         auto graph = genome::Graph::buildGraph(k, *kmersFreq, cyc.keep);                                          // :36
         auto [nodes, edges, totalLen] = graph.counts();                                                  // :39
+        if (seed.given) seed.report(k, stageRounds, stageBefore, stageAfter, stageStats, nodes, edges);
         // :41-47 the two component histograms, on the graph as built (the reference computes them before retain)
         auto [hist, hist2] = graph.componentHistograms();
         uint64_t kept = nodes, comps = 0;
         if (retain) std::tie(kept, comps) = graph.retainLargestComponent();                              // :52-54
-        // --clip-tips / --pop-bubbles: clip, pop, then simplifyGraph, until a round removes nothing (the counts are the table the
-        // graph was built from)
         std::vector<uint64_t> tipsRemoved, bubblesRemoved, bubblePairs;
-        for (int round = 0; (clipTips || popBubbles) && round < 8; round++) {
-            uint64_t gone = 0;
-            if (clipTips) { tipsRemoved.push_back(graph.clipTips(*kmersFreq, tipMaxLen)); gone += tipsRemoved.back(); }
-            if (popBubbles) {
-                const auto [removed, pairs] = graph.popBubbles(*kmersFreq, bubbleMaxLen, bubbleMaxDiff);
-                bubblesRemoved.push_back(removed); bubblePairs.push_back(pairs);
-                gone += removed;
-            }
-            if (!gone) break;
-            graph.simplifyGraph();
-        }
+        cleanRounds(graph, *kmersFreq, tipMaxLen, bubbleMaxLen, tipsRemoved, bubblesRemoved, bubblePairs);
         // --simplify = GraphSimplifier.scala:317-318, applied to the graph GraphBuilder hands over (i.e. after retain)
         if (simplify) { graph.removeBubbles(); graph.simplifyGraph(); }
         PairedResult walked;
@@ -240,6 +281,7 @@ int main(int argc, char **argv) {
             if (!lr.blocksJson.empty()) jsonPut(js, "blocks", lr.blocksJson);
         }
         if (const std::string cj = cyc.report(graph, true); !cj.empty()) jsonPut(js, "cycles", cj);
+        if (seed.given) jsonPut(js, "seed_stages", seed.json());
         if (!contig.path.empty()) jsonPut(js, "contigs_fasta", fasta.json());
         // --gfa: after all edits (the links stage's included), with KC from the table the graph was built from
         if (const std::string gj = gfaOpt.run(graph, kmersFreq.get()); !gj.empty()) jsonPut(js, "gfa", gj);

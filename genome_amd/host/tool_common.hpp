@@ -227,6 +227,62 @@ struct CycleOpts {
     }
 };
 
+// --seed-k K1[,K2,...]: multi-k assembly (include/genome_amd.h, "multi-k": this project's own rule).  The listed ks are seed stages,
+// run before the count at the positional <k>: count the reads at K, add the contigs of the stage before at weight = rounds
+// (genome::DNAMap::addGraphPaths), deleteAll(< rounds), buildGraph, the tool's clip / pop rounds, simplifyGraph; no retain (that would
+// drop replicons).  The last seed stage's contigs go into the <k> table between its count and its deleteAll, and everything behind the
+// count is unchanged.  The ks must be strictly increasing, below <k> and supported.  The JSON gains "seed_stages":[one object per
+// stage: k, rounds, distinct k-mers before and after seeding, the six stats, nodes, edges] — the stage at <k> last — and stderr one
+// line per stage.  One GPU only, and not with --prefilter (the seeds' k-mers are not in the reads' census).
+struct SeedOpts {
+    std::vector<int> ks;
+    bool given = false;
+    std::vector<std::string> stages;              // the per-stage JSON objects
+    bool parse(Args &a) {
+        std::string list;
+        if (!a.value("--seed-k", list)) return false;
+        given = true;
+        ks.clear();
+        size_t at = 0;
+        while (at <= list.size()) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            int k = 0;
+            if (!Args::number(list.substr(at, comma - at).c_str(), k)) { ks.assign(1, -1); break; }      // (refused by check)
+            ks.push_back(k);
+            at = comma + 1;
+        }
+        return true;
+    }
+    static bool supported(int k) { return (k >= 2 && k <= 31) || (k >= 34 && k <= 64); }
+    bool check(int world, bool prefilter, int k) const {
+        if (!given) return true;
+        if (world) { std::fprintf(stderr, "--seed-k runs on one GPU only (not with --world): the seeding has no collective\n"); return false; }
+        if (prefilter) { std::fprintf(stderr, "--seed-k does not run with --prefilter\n"); return false; }
+        for (size_t i = 0; i < ks.size(); i++)
+            if (!supported(ks[i]) || ks[i] >= k || (i && ks[i] <= ks[i - 1])) {
+                std::fprintf(stderr, "usage: --seed-k K1[,K2,...] takes supported ks (2..31, 34..64), strictly increasing and below <k> = %d\n", k);
+                return false;
+            }
+        return true;
+    }
+    // one stage's record: the JSON object and the line on stderr
+    void report(int k, int rounds, uint64_t before, uint64_t after, const genome::DNAMap::GraphPathStats &st, uint64_t nodes, uint64_t edges) {
+        const std::string paths = jsonNamed(genome::DNAMap::graphPathStatNames, st.v, 6);
+        std::string js = "{";
+        jsonPut(js, "k", k, "rounds", rounds, "distinct_before_seed", before, "distinct_after_seed", after);
+        js += "," + paths;
+        jsonPut(js, "nodes", nodes, "edges", edges);
+        stages.push_back(js + "}");
+        std::fprintf(stderr, "seed-k: k %d rounds %d distinct %llu -> %llu {%s} nodes %llu edges %llu\n", k, rounds, (unsigned long long)before,
+                     (unsigned long long)after, paths.c_str(), (unsigned long long)nodes, (unsigned long long)edges);
+    }
+    std::string json() const {
+        std::string s = "[";
+        for (size_t i = 0; i < stages.size(); i++) s += (i ? "," : "") + stages[i];
+        return s + "]";
+    }
+};
+
 // GraphSimplifier.startup's paired-end stage (GraphSimplifier.scala:188-318) on a graph: position map, the pairs' walks, node
 // split by their support, simplifyGraph — and this project's additions to it: the measured insert range, the threaded reads and,
 // after the reference's stage, the repeats longer than k that single reads span.

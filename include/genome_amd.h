@@ -655,6 +655,34 @@ int gk_contigs_write(gk_contigs *c, const char *path);
  * waits for the device-to-host copies, the sink (file writes, or the copy into buf), the whole call} */
 int gk_contigs_last_ms(const gk_contigs *c, float *ms4);
 
+/* ---- multi-k: this project's own rule (the reference builds its graph at one k) ----
+ * The k2-mers of a graph's contigs added to a count table of a larger k, on the device: the step that lets a graph of a small k
+ * seed the table of a large one (assemble at k1, clean, seed, count the reads at k2 beside it, build).  Integers only.
+ * Terms.  k1 = the graph's k, k2 = gk_map_k(dst).  P(e), n = k1 + len and the classes are the contigs' (above) with min_len = k2,
+ * tested in the same order: short (n < k2), then forward, self_twin, reverse.
+ * Rule.  For every forward or self_twin edge that is not short, every k2-window of P(e) — positions 0 .. n - k2 — is oriented
+ * exactly as a window of a read is when it is counted at k2 (the hash rule at k2, a tie of the two hashes goes to the reverse
+ * complement: FreqFilter.scala:31-32) and update(key, weight, _ + weight) is applied to dst.  In one sentence: dst ends as if every
+ * record of gk_graph_contigs_plan(g, NULL, 0, 0, strands = 1) that holds k2 bases had been a read counted `weight` times at k2.
+ * What follows from that sentence and is not special-cased: a self_twin path contributes each of its mirrored windows twice (the
+ * window at position i and the one at n - k2 - i are reverse complements of each other, hence one key), a palindromic window once
+ * per occurrence.  Contigs that meet in a node overlap by k1 < k2 bases: they share no window except where the sequence truly
+ * repeats, and a k2-window that crosses a junction node is in no contig and is not added (the reads supply those).  A reverse edge
+ * whose twin is dead is NOT added; the stats show it.
+ * The graph is not changed and its state counter does not move: contig, GFA and scaffold plans made before the call stay valid.
+ * stats6 (may be NULL) = {live_edges, short, forward, self_twin, reverse, windows}: element 0 = the sum of elements 1..4, windows =
+ * the sum of n - k2 + 1 over the forward and self_twin edges = the updates applied.
+ * NULL handles, handles of different contexts, k2 <= k1, weight == 0 or weight > 65535: GK_E_INVALID, and dst is untouched.  A
+ * table that cannot grow: GK_E_CAPACITY as from gk_map_add_counts, with the windows of the chunks before it added.  A graph
+ * without a live edge: GK_OK, zeros.  Every combination of key widths works (8-byte graph keys into an 8- or 16-byte table, 16 into
+ * 16, k2 = 64 with its tagged slots), into a count-layout table and into a graph-layout one (gk_map_create_for_graph).
+ * On the device: one wave per live edge classifies it (the contig plan's comparison); the work item of the emission is a RUN of 16
+ * consecutive windows of one contig, so that one long edge spreads over the device: per-edge run counts are scanned, a lane finds
+ * its run's edge by binary search in the offsets, builds the first window from the node k-mer and the edge's bases without a
+ * per-base loop, rolls window and reverse complement through the rest and stores canonical keys and the weight; the host loop feeds
+ * chunks of at most 2^24 windows to the table's insert of counted device keys. */
+int gk_map_add_graph_paths(gk_map *dst, gk_graph *g, uint32_t weight, uint64_t *stats6);
+
 /* ---- edge twins: this project's own rule (the reference keeps both strands of everything as unrelated edges) ----
  * Which live edge is the reverse complement of which, by content, exactly.  Integers only; no edge id enters the rule.
  * P(e) and R(e) are the contigs' (above): the start k-mer followed by the sequence, and its reverse complement.

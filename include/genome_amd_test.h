@@ -59,7 +59,10 @@ extern "C" {
  * through the device per slice, so that a record of a few kbp is cut inside a contig and both upload buffers are used.
  * The singleton pre-filter: "test_max_stage" is also the bytes of `.bin` records its host-fed passes stage per chunk (0: 256 MiB),
  * "test_prefilter_chunk_windows" (0: the default, 2^28) the k-mer windows of one pass-2 chunk, of the host-fed call and of the
- * `_dev` call alike, and its three launches (both passes and the counters' census of gk_prefilter_stats) obey "test_max_grid". */
+ * `_dev` call alike, and its three launches (both passes and the counters' census of gk_prefilter_stats) obey "test_max_grid".
+ * "test_multik_chunk_windows" (0: the default, 2^24): the k-mer windows of one chunk of gk_map_add_graph_paths, rounded down to
+ * whole runs of 16 windows and at least one run, so that a graph of a few thousand windows goes through many chunks; its
+ * classification and emission launches obey "test_max_grid". */
 int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value);
 
 /* The echo of the pre-filter's chunking: what this filter handle has run since it was created.  *host_fixed / *host_offsets = the
@@ -67,6 +70,10 @@ int gk_ctx_set_option(gk_ctx *ctx, const char *name, int64_t value);
  * *dev_pass2 = the chunks of gk_map_count_reads_prefiltered_dev; *pass2_launches = launches of the pass-2 kernel (a staged chunk
  * without a window launches none).  Any pointer may be null; a null handle is GK_E_INVALID. */
 int gk_test_prefilter_chunks(const gk_prefilter *pf, uint64_t *host_fixed, uint64_t *host_offsets, uint64_t *dev_pass2, uint64_t *pass2_launches);
+
+/* The echo of "test_multik_chunk_windows": *chunks = the chunks the last gk_map_add_graph_paths on this context emitted and
+ * inserted (0 after a call that was refused or found no window). */
+int gk_test_multik_chunks(const gk_ctx *ctx, uint64_t *chunks);
 
 /* The echo of "test_max_grid": *uses = the launches on this context whose grid was bounded by the switch's value instead of by
  * 8 workgroups per CU, since the context was created (every capped launch site asks once per launch; nothing is counted while the
