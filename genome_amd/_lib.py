@@ -142,6 +142,7 @@ SIGNATURES = {
     "gk_graph_clip_tips": (C.c_int, [vp, vp, C.c_uint64, u64p]),
     "gk_graph_edge_distance": (C.c_int, [vp, u32p, u32p, C.c_uint64, C.c_uint32, u32p]),
     "gk_graph_pop_bubbles": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, u64p, u64p]),
+    "gk_graph_remove_weak_edges": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, u64p]),
     "gk_graph_contigs_plan": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp)]),
     "gk_contigs_destroy": (None, [vp]),
     "gk_contigs_stats": (C.c_int, [vp, u64p]),

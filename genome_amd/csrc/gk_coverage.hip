@@ -6,7 +6,9 @@
 // stated in include/genome_amd.h; tests/tips_ref.py restates them.  So are the two that remove bubbles by the same numbers
 // (gk_graph_edge_distance: a thresholded, banded edit distance of two edges, one wave per pair; gk_graph_pop_bubbles: the weaker of
 // two similar parallel edges goes; restated in tests/bubbles_ref.py) — gk_graph_remove_bubbles, the reference's own unfinished
-// rule (Graph.scala:121-149), stays in gk_graph.hip as it is.
+// rule (Graph.scala:121-149), stays in gk_graph.hip as it is.  And the one that removes weak connections (gk_graph_remove_weak_edges:
+// an edge with a way on at both ends and a competitor `ratio` times stronger at each, or a mean below a floor; restated in
+// tests/weak_ref.py).
 //
 // Roofline: one independent random table probe per k-mer of every live edge (total edge length + live edges of them) and
 // nothing else of size: the random-load rate of HBM, as the unitig walk — whose probes depend on each other, these do not.
@@ -163,9 +165,56 @@ __global__ __launch_bounds__(BLOCK) void k_tip_apply(GraphView g, const uint8_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// weak connections (the rule: include/genome_amd.h, gk_graph_remove_weak_edges)
+// ---------------------------------------------------------------------------------------------
+static constexpr u32 WEAK_MAX_RATIO = 65535;             // ratio * kmers stays inside 64 bits
+// one lane per edge, from the graph as it is (nothing is written but `mark`, flags[0] and the counters): (A) a competitor `ratio`
+// times stronger among the other out-edges of the start node AND among the other in-edges of the end node, (B) a mean below `floor`.
+// stats[0] += candidates, stats[1] += marked under (A), stats[2] += marked under (B) alone, once per wave (stats[3] is the apply's).
+__global__ __launch_bounds__(BLOCK) void k_weak_mark(GraphView g, EdgeCov cov, const unsigned long long *__restrict__ in_off, const u32 *__restrict__ in_list,
+                                                     u64 max_len, u64 ratio, u64 floor, uint8_t *mark, u32 *flags, unsigned long long *stats) {
+    const u64 stride = (u64)gridDim.x * BLOCK;
+    for (u64 e0 = (u64)blockIdx.x * BLOCK; e0 < g.n_edges; e0 += stride) {  // (uniform over the wave: every lane takes the ballots)
+        const u64 e = e0 + threadIdx.x;
+        bool cand = false, by_ratio = false, by_floor = false;
+        if (e < g.n_edges) {
+            const bool live = g.e_alive[e];
+            if (live && cov.miss[e]) flags[0] = 1u;
+            const u64 len = live ? g.e_len[e] : 0;
+            if (live && len <= max_len) {
+                const u32 u = g.e_start[e], v = g.e_end[e];
+                const u64 sum_e = cov.sum[e], kmers_e = len + 1;
+                cand = order_count(g.out_order[u]) >= 2 && in_off[v + 1] - in_off[v] >= 2;
+                if (cand && ratio) {
+                    bool out_stronger = false, in_stronger = false;
+                    for (int b = 0; b < 4; b++) {
+                        const u32 f = g.out_edge[(u64)u * 4 + b];
+                        if (f != NONE && f != (u32)e && g.e_alive[f]) out_stronger |= cov_weaker(sum_e, kmers_e, cov.sum[f], ratio * (g.e_len[f] + 1));
+                    }
+                    if (out_stronger)
+                        for (u64 j = in_off[v]; j < in_off[v + 1]; j++) {
+                            const u32 f = in_list[j];
+                            if (f != (u32)e) in_stronger |= cov_weaker(sum_e, kmers_e, cov.sum[f], ratio * (g.e_len[f] + 1));
+                        }
+                    by_ratio = in_stronger;
+                }
+                by_floor = floor && !by_ratio && cov_weaker(sum_e, kmers_e, floor, 1);
+            }
+            mark[e] = by_ratio || by_floor;
+        }
+        const unsigned long long c = __ballot(cand), a = __ballot(by_ratio), b = __ballot(by_floor);
+        if ((threadIdx.x & 63) == 0) {
+            if (c) atomicAdd(stats + 0, (unsigned long long)__popcll(c));
+            if (a) atomicAdd(stats + 1, (unsigned long long)__popcll(a));
+            if (b) atomicAdd(stats + 2, (unsigned long long)__popcll(b));
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // bubbles (the rules: include/genome_amd.h, gk_graph_edge_distance and gk_graph_pop_bubbles)
 // ---------------------------------------------------------------------------------------------
-static constexpr u32 DIST_MAX_DIFF = 31;                 // a band of 2 * 31 + 1 = 63 diagonals: one wave, lane 63 the wall beside it
+static constexpr u32 DIST_MAX_DIFF = 31;                // a band of 2 * 31 + 1 = 63 diagonals: one wave, lane 63 the wall beside it
 static constexpr u32 DIST_INVALID = 0xffffffffu;
 
 // bases s .. s + 31 of a sequence of n bases as 32 2-bit codes; s may be negative and s + 32 may pass n: those read as 0, and no
@@ -370,6 +419,36 @@ int gk_graph_clip_tips(gk_graph *g, gk_map *counts, uint64_t max_len, uint64_t *
     GK_HIP(ctx, read_back(ctx, {{&h_flags, d_flags, 4}, {&h_removed, d_removed, 8}}));
     if (h_flags) return fail(ctx, GK_E_STATE, "gk_graph_clip_tips: the map does not hold every k-mer of the graph (not the table it was built from?)");
     if (removed_edges) *removed_edges = h_removed;
+    return graph_refresh_counts(g);
+}
+
+int gk_graph_remove_weak_edges(gk_graph *g, gk_map *counts, uint64_t max_len, uint32_t ratio, uint32_t floor, uint64_t *stats4) {
+    if (int rc = check_graph(g)) return rc;
+    gk_ctx *ctx = g->ctx;
+    if (int rc = check_counts(g, counts, "gk_graph_remove_weak_edges")) return rc;
+    if (ratio > WEAK_MAX_RATIO) return fail(ctx, GK_E_INVALID, "gk_graph_remove_weak_edges: ratio is at most 65535 (ratio * kmers stays inside 64 bits)");
+    if (stats4) std::fill(stats4, stats4 + 4, (uint64_t)0);
+    const GraphView &v = g->v;
+    if (max_len == 0 || v.n_edges == 0) return GK_OK;
+    DevScratch tmp(ctx);
+    EdgeCov cov{};
+    if (int rc = coverage_pass(g, counts, tmp, nullptr, &cov)) return rc;
+    // the in-edge lists of the graph as it is
+    unsigned long long *d_in_off = nullptr, *d_stats = nullptr, h_stats[4] = {0, 0, 0, 0};
+    u32 *d_in_list = nullptr, *d_flags = nullptr, h_flags = 0;
+    uint8_t *d_mark = nullptr;
+    tmp.get(&d_mark, v.n_edges);
+    tmp.zeroed(&d_flags, 1);
+    tmp.zeroed(&d_stats, 4);
+    if (tmp.error() != hipSuccess) return hip_fail(ctx, tmp.error(), "gk_graph_remove_weak_edges: marks");
+    if (int rc = graph_in_lists(g, tmp, "gk_graph_remove_weak_edges", &d_in_off, &d_in_list)) return rc;
+    const int grid = ggrid(ctx, v.n_edges);
+    hipLaunchKernelGGL(k_weak_mark, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, cov, d_in_off, d_in_list, (u64)max_len, (u64)ratio, (u64)floor, d_mark, d_flags, d_stats);
+    // the decision is complete before anything is applied, and a map that is not this graph's leaves the graph as it was
+    hipLaunchKernelGGL(k_tip_apply, dim3(grid), dim3(BLOCK), 0, ctx->stream, v, d_mark, d_flags, d_stats + 3);
+    GK_HIP(ctx, read_back(ctx, {{&h_flags, d_flags, 4}, {h_stats, d_stats, 32}}));
+    if (h_flags) return fail(ctx, GK_E_STATE, "gk_graph_remove_weak_edges: the map does not hold every k-mer of the graph (not the table it was built from?)");
+    if (stats4) std::copy(h_stats, h_stats + 4, stats4);
     return graph_refresh_counts(g);
 }
 

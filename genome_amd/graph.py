@@ -224,6 +224,17 @@ class HipGraph:
                                              C.byref(rm), C.byref(pairs)), self.ctx.h)
         return rm.value, pairs.value
 
+    def removeWeakEdges(self, counts: HipDNAMap, max_len=None, ratio: int = 5, floor: int = 0) -> dict:
+        """One round of weak-connection removal: an edge of at most `max_len` bases (default 2k) whose start node has another way
+        out and whose end node another way in goes if at each end one of those other edges has more than `ratio` times its mean
+        coverage (ratio = 0: off; at most 65535); so does any edge whose mean coverage is below `floor` (0: off).  -> the four
+        numbers of WEAK_STATS.  ratio 5 and 2k are choices, not measurements.  Call simplifyGraph() next.  GkError GK_E_STATE if
+        `counts` is not this graph's table."""
+        st = np.zeros(len(WEAK_STATS), np.uint64)
+        L.check(L.lib().gk_graph_remove_weak_edges(self.h, counts.h, 2 * self.k if max_len is None else int(max_len), int(ratio), int(floor),
+                                                   L.ptr(st, C.c_uint64)), self.ctx.h)
+        return dict(zip(WEAK_STATS, (int(x) for x in st)))
+
     # ---- contigs as FASTA (this project's own rule: include/genome_amd.h) ----------------------------------------------
     def contigs(self, counts: HipDNAMap = None, min_len: int = 0, line_width: int = 60, strands: int = 1) -> "Contigs":
         """The assembly as FASTA text, planned on the device: one record `>e<id> len=<n>[ cov=<mean>]` per live edge whose path
@@ -590,6 +601,7 @@ class Contigs:
 
 
 # the statistics of gk_graph_edge_twins, in the order of its `stats6` array: live_edges is the sum of the four after it
+WEAK_STATS = ("candidates", "removed_ratio", "removed_floor_only", "removed")     # gk_graph_remove_weak_edges' stats4
 TWIN_STATS = ("live_edges", "paired", "self", "missing", "ambiguous", "key_collisions")
 # the names of gk_graph_edge_twins' class codes, by code (dead: a dead or out-of-range id)
 TWIN_CLASSES = ("dead", "paired", "self", "missing", "ambiguous")

@@ -1135,6 +1135,16 @@ class Graph {
         check(gk_graph_pop_bubbles(h_, counts.handle(), maxLen ? maxLen : 2 * (uint64_t)k_, maxDiff, &removed, &pairs), ctx_.handle());
         return {removed, pairs};
     }
+    // One round of weak-connection removal (include/genome_amd.h): an edge of at most maxLen bases (0 = the default, 2k) with another
+    // way out of its start node and another way into its end node goes if at each end one of those has more than `ratio` times its
+    // mean coverage (0: off; at most 65535), and so does any edge whose mean is below `floor` (0: off); simplifyGraph() is the next
+    // call.  ratio 5 and 2k are choices, not measurements.  GK_E_STATE if `counts` is not this graph's.
+    struct WeakStats { uint64_t candidates = 0, removedRatio = 0, removedFloorOnly = 0, removed = 0; };
+    WeakStats removeWeakEdges(const DNAMap &counts, uint64_t maxLen = 0, uint32_t ratio = 5, uint32_t floor = 0) {
+        uint64_t st[4] = {0, 0, 0, 0};
+        check(gk_graph_remove_weak_edges(h_, counts.handle(), maxLen ? maxLen : 2 * (uint64_t)k_, ratio, floor, st), ctx_.handle());
+        return {st[0], st[1], st[2], st[3]};
+    }
     // CheckGraph.scala:37-41 over the live edges longer than longerThan: count, summed length, median (sorted[count / 2], the
     // reference's "N50"), the real N50, the maximum; computed on the device
     struct ContigStats { uint64_t count = 0, sum = 0, median = 0, n50 = 0, max = 0; };

@@ -4,7 +4,7 @@
 // The reference logs its counters through akka Logging (:34-53); here they are one JSON object.
 //
 //   graph_builder <reads.bin> <pairs> <k> [--rounds 3 | --rounds auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify]
-//                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]]
+//                 [--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--remove-weak [RATIO] [--weak-max-len N] [--min-coverage N]] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]]
 //                 [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N] [--block-rows PATH]]]]   (with --walk-pairs: graph_simplifier.cpp says what they write)
 //                 [--out prefix] [--save-graph PATH] [--correct N|auto]
 //                 [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--seed-k K1[,K2,...]]
@@ -26,6 +26,14 @@
 //   round removes nothing, 8 rounds at most.  MAXDIFF = the edit distance two branches may be apart (auto, the default: 3, at most
 //   31); --bubble-max-len N = the longest edge a branch may be (default 2k).  The JSON gains
 //   "pop_bubbles":{"max_len","max_diff","removed":[per round],"pairs":[per round]}.  Not with --world (exit 2).
+//   --remove-weak [RATIO] removes weak connections (gk_graph_remove_weak_edges: this project's own rule) in the same rounds, after
+//   the clip and the pop and before the round's simplifyGraph: an edge whose start node has another way out and whose end node
+//   another way in goes if at each end one of those others has more than RATIO times its mean coverage (auto, the default: 5; at
+//   most 65535).  --weak-max-len N = the longest edge that may go (default 2k); --min-coverage N (only with --remove-weak) also
+//   removes every edge within that length whose mean coverage is below N (default 0: off).  RATIO 5 and 2k are choices, not
+//   measurements.  A round that removes anything keeps the loop going; 8 rounds at most.  The JSON gains
+//   "remove_weak":{"max_len","ratio","floor","candidates":[per round],"removed_ratio":[per round],"removed_floor":[per round]},
+//   stderr one line.  Not with --world (exit 2).
 //   --correct N|auto corrects the reads before they are counted (gk_reads_correct: this project's own rule, the reference has none):
 //   count, correct the stream in host memory against that count (solid = N, or the valley of its spectrum; 3 when it has none),
 //   then count the corrected stream and go on as without the flag — --rounds auto sees the second spectrum, and --walk-pairs walks
@@ -76,7 +84,7 @@ int main(int argc, char **argv) {
     }
     if (argc < 4) {
         std::fprintf(stderr, "usage: %s <reads.bin> <pairs> <k> [--rounds 3|auto] [--spectrum PATH] [--take-first N] [--prefilter DISTINCT] [--no-retain] [--simplify] "
-                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--out prefix] [--save-graph PATH] "
+                             "[--clip-tips [MAXLEN|auto]] [--pop-bubbles [MAXDIFF|auto]] [--bubble-max-len N] [--remove-weak [RATIO (default 5: a choice, not a measurement)] [--weak-max-len N (default 2k: a choice too)] [--min-coverage N]] [--edge-coverage] [--walk-pairs CUTOFF LO HI | --walk-pairs CUTOFF auto [--max-insert N]] [--resolve-repeats [CUTOFF] [--resolve-rounds N]] [--links PATH [--link-min-support N] [--link-min-len N] [--scaffolds PATH] [--scaffold-fasta PATH [--scaffold-min-gap N] [--scaffold-width N] [--scaffold-both-strands]] [--fill-gaps [TOL] [--fill-max-edges N] [--fill-max-paths N]] [--overlap-gaps [TOL] [--overlap-min N] [--overlap-max N]] [--judge GENOME.fasta [--judge-tol N] [--blocks [--block-tol N (default 1000: a choice, not a measurement)] [--block-rows PATH]]]] [--out prefix] [--save-graph PATH] "
                              "[--correct N|auto] [--contigs PATH [--contig-min-len N] [--contig-width W] [--contig-both-strands]] [--gfa PATH] [--keep-cycles] [--seed-k K1[,K2,...]] [--world W --rank R --id-file PATH]\n", argv[0]);
         return 2;
     }
@@ -95,6 +103,9 @@ int main(int argc, char **argv) {
     bool popBubbles = false;
     uint32_t bubbleMaxDiff = 3;                   // auto: the reference's commented-out maxerrors (Graph.scala:121-123)
     uint64_t bubbleMaxLen = 0;                    // 0 = auto: 2k
+    bool removeWeak = false, minCoverageGiven = false;
+    uint32_t weakRatio = 5, weakFloor = 0;        // auto: 5 (a choice, not a measurement); --min-coverage
+    uint64_t weakMaxLen = 0;                      // 0 = auto: 2k
     bool correct = false;                         // --correct
     uint32_t solid = 0;                           // 0 = auto: the valley of the first count's spectrum
     PairedOpts walk;                              // --walk-pairs: cutoff < 0 = no such stage; rangeAuto = --walk-pairs CUTOFF auto
@@ -114,6 +125,9 @@ int main(int argc, char **argv) {
         else if (a.optional("--clip-tips", tipMaxLen)) clipTips = true;
         else if (a.optional("--pop-bubbles", bubbleMaxDiff)) popBubbles = true;
         else if (a.value("--bubble-max-len", bubbleMaxLen)) {}
+        else if (a.optional("--remove-weak", weakRatio)) removeWeak = true;
+        else if (a.value("--weak-max-len", weakMaxLen)) {}
+        else if (a.value("--min-coverage", weakFloor)) minCoverageGiven = true;
         else if (a.flag("--edge-coverage")) edgeCoverage = true;
         else if (a.word("--correct", 1, "auto")) { correct = true; solid = 0; a.skip(); }
         else if (a.value("--correct", solid)) {
@@ -138,7 +152,7 @@ int main(int argc, char **argv) {
     }
     const int world = ranks.world, rank = ranks.rank;
     const char *oneGpu = prefilter ? "--prefilter runs" : clipTips || edgeCoverage ? "--clip-tips and --edge-coverage run" :
-                         correct ? "--correct runs" : popBubbles ? "--pop-bubbles runs" : nullptr;
+                         correct ? "--correct runs" : popBubbles ? "--pop-bubbles runs" : removeWeak ? "--remove-weak runs" : nullptr;
     if (world && oneGpu) {
         std::fprintf(stderr, "%s on one GPU only (not with --world)\n", oneGpu);
         return 2;
@@ -147,20 +161,35 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "--pop-bubbles MAXDIFF is at most 31\n");
         return 2;
     }
-    const uint64_t tipGiven = tipMaxLen, bubbleGiven = bubbleMaxLen;      // (0 = auto: 2k of the stage that clips)
+    if (removeWeak && weakRatio > 65535) {
+        std::fprintf(stderr, "--remove-weak RATIO is at most 65535\n");
+        return 2;
+    }
+    if (minCoverageGiven && !removeWeak) {
+        std::fprintf(stderr, "--min-coverage goes with --remove-weak (it is that step's floor)\n");
+        return 2;
+    }
+    const uint64_t tipGiven = tipMaxLen, bubbleGiven = bubbleMaxLen, weakGiven = weakMaxLen;      // (0 = auto: 2k of the stage that clips)
     if (clipTips && !tipMaxLen) tipMaxLen = 2 * (uint64_t)k;
     if (popBubbles && !bubbleMaxLen) bubbleMaxLen = 2 * (uint64_t)k;
-    // --clip-tips / --pop-bubbles: clip, pop, then simplifyGraph, until a round removes nothing, 8 rounds at most (the counts are the
-    // table the graph was built from)
-    auto cleanRounds = [&](genome::Graph &graph, genome::DNAMap &counts, uint64_t tipLen, uint64_t bubbleLen, std::vector<uint64_t> &tipsRemoved,
-                           std::vector<uint64_t> &bubblesRemoved, std::vector<uint64_t> &bubblePairs) {
-        for (int round = 0; (clipTips || popBubbles) && round < 8; round++) {
+    if (removeWeak && !weakMaxLen) weakMaxLen = 2 * (uint64_t)k;
+    struct WeakRounds { std::vector<uint64_t> candidates, removedRatio, removedFloor; };
+    // --clip-tips / --pop-bubbles / --remove-weak: clip, pop, remove weak connections, then simplifyGraph, until a round removes
+    // nothing, 8 rounds at most (the counts are the table the graph was built from)
+    auto cleanRounds = [&](genome::Graph &graph, genome::DNAMap &counts, uint64_t tipLen, uint64_t bubbleLen, uint64_t weakLen, std::vector<uint64_t> &tipsRemoved,
+                           std::vector<uint64_t> &bubblesRemoved, std::vector<uint64_t> &bubblePairs, WeakRounds &weak) {
+        for (int round = 0; (clipTips || popBubbles || removeWeak) && round < 8; round++) {
             uint64_t gone = 0;
             if (clipTips) { tipsRemoved.push_back(graph.clipTips(counts, tipLen)); gone += tipsRemoved.back(); }
             if (popBubbles) {
                 const auto [removed, pairs] = graph.popBubbles(counts, bubbleLen, bubbleMaxDiff);
                 bubblesRemoved.push_back(removed); bubblePairs.push_back(pairs);
                 gone += removed;
+            }
+            if (removeWeak) {
+                const auto w = graph.removeWeakEdges(counts, weakLen, weakRatio, weakFloor);
+                weak.candidates.push_back(w.candidates); weak.removedRatio.push_back(w.removedRatio); weak.removedFloor.push_back(w.removedFloorOnly);
+                gone += w.removed;
             }
             if (!gone) break;
             graph.simplifyGraph();
@@ -207,7 +236,8 @@ int main(int argc, char **argv) {
             auto m = std::make_unique<genome::DNAMap>(genome::FreqFilter::extractFilteredKmers(ctx, data, sk, rounds, takeFirst, 0, 0, &ch, seedInto));
             auto g = std::make_unique<genome::Graph>(genome::Graph::buildGraph(sk, *m, cyc.keep));
             std::vector<uint64_t> t, b, p;
-            cleanRounds(*g, *m, tipGiven ? tipGiven : 2 * (uint64_t)sk, bubbleGiven ? bubbleGiven : 2 * (uint64_t)sk, t, b, p);
+            WeakRounds w;
+            cleanRounds(*g, *m, tipGiven ? tipGiven : 2 * (uint64_t)sk, bubbleGiven ? bubbleGiven : 2 * (uint64_t)sk, weakGiven ? weakGiven : 2 * (uint64_t)sk, t, b, p, w);
             g->simplifyGraph();                               // (a seed stage always simplifies and never retains: that would drop replicons)
             const auto [sn, se, sl] = g->counts();
             (void)sl;
@@ -242,7 +272,15 @@ int main(int argc, char **argv) {
         uint64_t kept = nodes, comps = 0;
         if (retain) std::tie(kept, comps) = graph.retainLargestComponent();                              // :52-54
         std::vector<uint64_t> tipsRemoved, bubblesRemoved, bubblePairs;
-        cleanRounds(graph, *kmersFreq, tipMaxLen, bubbleMaxLen, tipsRemoved, bubblesRemoved, bubblePairs);
+        WeakRounds weak;
+        cleanRounds(graph, *kmersFreq, tipMaxLen, bubbleMaxLen, weakMaxLen, tipsRemoved, bubblesRemoved, bubblePairs, weak);
+        if (removeWeak && rank == 0) {
+            uint64_t byRatio = 0, byFloor = 0;
+            for (const uint64_t x : weak.removedRatio) byRatio += x;
+            for (const uint64_t x : weak.removedFloor) byFloor += x;
+            std::fprintf(stderr, "remove-weak: %llu edges by ratio %u, %llu more below coverage %u, in %zu rounds (max_len %llu)\n", (unsigned long long)byRatio,
+                         weakRatio, (unsigned long long)byFloor, weakFloor, weak.candidates.size(), (unsigned long long)weakMaxLen);
+        }
         // --simplify = GraphSimplifier.scala:317-318, applied to the graph GraphBuilder hands over (i.e. after retain)
         if (simplify) { graph.removeBubbles(); graph.simplifyGraph(); }
         PairedResult walked;
@@ -266,6 +304,9 @@ int main(int argc, char **argv) {
         if (clipTips) jsonPut(js, "clip_tips", jsonObject("max_len", tipMaxLen, "removed", jsonList(tipsRemoved)));
         if (popBubbles)
             jsonPut(js, "pop_bubbles", jsonObject("max_len", bubbleMaxLen, "max_diff", bubbleMaxDiff, "removed", jsonList(bubblesRemoved), "pairs", jsonList(bubblePairs)));
+        if (removeWeak)
+            jsonPut(js, "remove_weak", jsonObject("max_len", weakMaxLen, "ratio", weakRatio, "floor", weakFloor, "candidates", jsonList(weak.candidates),
+                                                  "removed_ratio", jsonList(weak.removedRatio), "removed_floor", jsonList(weak.removedFloor)));
         if (walk.cutoff >= 0 && walk.rangeAuto)
             jsonPut(js, "insert_range", jsonObject("lo", walked.range.lo, "hi", walked.range.hi, "estimated", walked.range.estimated,
                                                    "observations", walked.range.observations));

@@ -30,16 +30,19 @@ def check_ks(ks):
     return ks
 
 
-def clean(graph, counts, clip_tips: bool, pop_bubbles: bool, keep_cycles: bool = False) -> int:
-    """graph_builder's clean-up loop: clip if asked, pop if asked, simplifyGraph, until a round removes nothing, MAX_CLEAN_ROUNDS
-    at most -> the rounds that removed something"""
+def clean(graph, counts, clip_tips: bool, pop_bubbles: bool, keep_cycles: bool = False, remove_weak=None) -> int:
+    """graph_builder's clean-up loop: clip if asked, pop if asked, remove weak connections if asked, simplifyGraph, until a round
+    removes nothing, MAX_CLEAN_ROUNDS at most -> the rounds that removed something.  remove_weak: None (off), or a dict with any of
+    "max_len" (default 2k), "ratio" (default 5), "floor" (default 0) — HipGraph.removeWeakEdges' keywords."""
     rounds = 0
-    while (clip_tips or pop_bubbles) and rounds < MAX_CLEAN_ROUNDS:
+    while (clip_tips or pop_bubbles or remove_weak is not None) and rounds < MAX_CLEAN_ROUNDS:
         gone = 0
         if clip_tips:
             gone += graph.clipTips(counts)
         if pop_bubbles:
             gone += graph.popBubbles(counts)[0]
+        if remove_weak is not None:
+            gone += graph.removeWeakEdges(counts, **remove_weak)["removed"]
         if not gone:
             break
         graph.simplifyGraph(keep_cycles)
@@ -48,15 +51,18 @@ def clean(graph, counts, clip_tips: bool, pop_bubbles: bool, keep_cycles: bool =
 
 
 def assemble(ctx: Context, bin_bytes, nreads: int, ks, rounds=3, clip_tips: bool = False, pop_bubbles: bool = False,
-             keep_cycles: bool = False):
+             keep_cycles: bool = False, remove_weak=None):
     """One stage per k of `ks` (strictly increasing, every member supported: ValueError before any device work otherwise):
     count the reads at k; seed the table with the previous stage's contigs at weight = rounds; deleteAll(< rounds); buildGraph;
-    the clean-up loop.  Every stage but the last — a seed stage — ends in simplifyGraph and never retains the largest component
+    the clean-up loop (remove_weak: off by default; a dict of HipGraph.removeWeakEdges' keywords — "max_len", "ratio", "floor", {} for
+    its defaults — adds that step to every stage's rounds).  Every stage but the last — a seed stage — ends in simplifyGraph and never retains the largest component
     (that would drop replicons); the last stage's graph is left to the caller as buildGraph + the loop leave it.
     rounds = "auto": the valley of that stage's spectrum BEFORE seeding (the seeds would move it), 3 when it has none.
     -> (map, graph, stages): the last stage's table and graph (the caller closes both) and one dict per stage: "k", "rounds",
     "distinct_before_seed", "distinct_after_seed", the six add_graph_paths stats (zeros for the first stage), "nodes", "edges"."""
     ks = check_ks(ks)
+    if remove_weak is not None and not (isinstance(remove_weak, dict) and set(remove_weak) <= {"max_len", "ratio", "floor"}):
+        raise ValueError('remove_weak is None or a dict with keys among "max_len", "ratio", "floor"')
     if rounds != "auto" and not (isinstance(rounds, int) and 1 <= rounds <= 65535):
         raise ValueError('rounds is 1..65535 or "auto"')
     stages = []
@@ -78,7 +84,7 @@ def assemble(ctx: Context, bin_bytes, nreads: int, ks, rounds=3, clip_tips: bool
             after = m.size()
             m.deleteAll_lt(r)
             g = buildGraph(k, m, keep_cycles)
-            clean(g, m, clip_tips, pop_bubbles, keep_cycles)
+            clean(g, m, clip_tips, pop_bubbles, keep_cycles, remove_weak)
             if i + 1 < len(ks):
                 g.simplifyGraph(keep_cycles)
             nodes, edges, _ = g.counts()

@@ -606,6 +606,35 @@ int gk_graph_edge_distance(gk_graph *g, const uint32_t *e1, const uint32_t *e2, 
  * gk_graph_remove_bubbles — the reference's rule: lengths within a fifth, no sequences, no coverage — is a different entry
  * point and unchanged. */
 int gk_graph_pop_bubbles(gk_graph *g, gk_map *counts, uint64_t max_len, uint32_t max_diff, uint64_t *removed_edges, uint64_t *pairs_compared);
+/* Weak connections.  One round, decided entirely from the graph's state at entry and then applied at once, as the tips and the
+ * bubbles are (the result depends neither on scheduling nor on id order).  The tips remove dead ends and the bubbles the weaker of
+ * two SIMILAR parallel edges; this removes an edge that is a proper connection by shape — both of its ends have another way on —
+ * but is carried by a handful of reads where its neighbours are carried by many: a chimeric read, a coincidental overlap of errors,
+ * a bubble arm too dissimilar for max_diff.  Coverage is gk_graph_edge_coverage's: len + 1 windows, both end nodes included, sum
+ * and kmers per edge.  "R times e is below f" means sum_e * (R * kmers_f) < sum_f * kmers_e, compared exactly as 128-bit integers:
+ * the tips' comparison with R * kmers_f in the place of kmers_f.  No floating point.  ratio > 65535: GK_E_INVALID — the bound
+ * keeps R * kmers_f inside 64 bits for any edge that fits in memory (kmers < 2^48).
+ * A live edge e (start u, end v, by node id) with len_e <= max_len is removed iff (A) or (B) holds:
+ *   (A) connection, when ratio >= 1: u has out-degree >= 2, and v has in-degree >= 2, and some OTHER live out-edge f of u has
+ *       `ratio` times e below f, and some OTHER live in-edge f' of v has `ratio` times e below f' (f' may be f);
+ *   (B) floor, when floor >= 1: sum_e < floor * kmers_e (mean coverage strictly below `floor`), whatever the edge's shape.
+ * ratio == 0 switches (A) off, floor == 0 switches (B) off, max_len == 0 removes nothing.  So:
+ *   a tip is not a connection: an out-tip's v has in-degree 1, an in-tip's u out-degree 1 — (A) leaves both to gk_graph_clip_tips;
+ *   ties remove nothing under (A), and with ratio = 1 the comparison is the tips' strict "below";
+ *   under (A) the strongest out-edge of every node and the strongest in-edge of every node survive: an edge that is removed has a
+ *   strictly stronger competitor at each end, and the maximum has none — (A) never takes a node's last way out or last way in;
+ *   a self-loop at u competes with u's other out-edges and with u's other in-edges;
+ *   parallel edges compete whatever their sequences are (a bubble arm beyond max_diff goes if it is weak enough);
+ *   an isolated contig is kept by (A) and goes under (B) if it is below the floor;
+ *   strand symmetry: the twin of e runs from rc v to rc u, the out-edges of rc v are the twins of the in-edges of v and carry the
+ *   same numbers — a strand-closed edge set stays strand-closed under (A), under (B) and under both together.
+ * Competitors are found by node id: the copies a node split leaves are different nodes.  Removal is MapGraph.removeEdge (:191-195);
+ * nodes stay for the caller's next simplifyGraph.  stats4 (may be NULL) = {candidates, removed_ratio, removed_floor_only, removed}:
+ * candidates = the live edges within max_len whose u has out-degree >= 2 and whose v has in-degree >= 2; removed_ratio = the edges
+ * removed under (A); removed_floor_only = those removed under (B) that (A) did not remove; removed = the sum of the last two.
+ * Coverage is computed for every live edge.  If any window of any live edge is missing from `counts` the map is not this graph's:
+ * GK_E_STATE, and the graph is untouched, as with the tips.  Handles as for gk_graph_clip_tips. */
+int gk_graph_remove_weak_edges(gk_graph *g, gk_map *counts, uint64_t max_len, uint32_t ratio, uint32_t floor, uint64_t *stats4);
 
 /* ---- contigs: this project's own rule (the reference prints every edge's seq BEFORE a ">abacaba<i>" line, both strands, without
  * the start k-mer: GraphSimplifier.scala:338-347; the host side's Graph::writeContigs is its literal twin and stays) ----
